@@ -19,6 +19,7 @@ children's exit code); under `python -m torch.distributed.run ... bench.py --gpu
 Other documented invocations:
   config 5 (fp8 weights + chunked prompt prefill, B=64):  python bench.py --weights fp8 --batch 64 --prefill-chunk 128
   launcher rehearsal without a GPU (gloo, no compute):    python bench.py --gpus 2 --rehearse-launcher
+  outputs of the last timed step, for comparing builds:  python bench.py --dump-outputs DIR   (DIR/codes.npy, DIR/pcm.npy)
 
 Output: ONE JSON line on rank 0 (driver contract) with `roofline` (dominant kernel: the fused
 RMSNorm + w1|w3 GEMM + SwiGLU, timed in situ with HIP events; plus the whole frame-step against
@@ -100,7 +101,42 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=1, help="independent decode streams per GPU (slots are split evenly)")
     ap.add_argument("--kv", default="fp32", choices=["fp32", "bf16"], help="KV-cache storage of the slow transformer (bf16: K/V rounded once when written; the oracle rounds identically)")
     ap.add_argument("--rehearse-launcher", action="store_true", help="no GPU, no compute: start the ranks, run the distributed plumbing of the bench (rendezvous, ranks_seen all-reduce, weight broadcast, sharding, barriers, timing reductions) over gloo and print the line")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): codes.npy = the step's "
+                         "frames [slot, frame, slow id + 8 codebook ids], pcm.npy = the PCM of the Mimi chunk decoded in that step [slot, sample]; "
+                         f"at most {DUMP_BYTES >> 20} MB in all (a larger array is replaced by a seeded sample of its elements, see dump_outputs); "
+                         "with --gpus N: rank 0's slots")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+# ------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, seed=0):
+    """Write ``arrays`` (name -> numpy array) as ``d/<name>.npy`` in float32, at most DUMP_BYTES in all.  An array over its share
+    of the budget (DUMP_BYTES / len(arrays)) is replaced by the elements at a fixed, seeded choice of flat indices, kept in
+    ascending order: ``<name>.npy`` holds those values and ``<name>_index.npy`` the indices (float64, exact)."""
+    import numpy as np
+
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1) - 1024  # (room for the .npy headers)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            k = share // (4 + 8)  # float32 value + float64 index per sampled element
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))
+            np.save(d / f"{name}_index.npy", idx.astype(np.float64))
+            written[f"{name}_index"] = [k]
+            a = a.reshape(-1)[idx]
+        np.save(d / f"{name}.npy", a)
+        written[name] = list(a.shape)
+    return written
 
 
 # ------------------------------------------------------------------------------------------- launcher
@@ -491,6 +527,13 @@ def run_rank(args) -> None:
     assert int(n_frames.min()) == n_total, (n_frames, n_total)
     if not args.no_mimi:
         assert bool(torch.isfinite(pcm[:, : (W + K) * CH * 1920]).all())
+    if args.dump_outputs and rank == 0:
+        # the last timed step i decoded frames 1 + i*CH .. (frame 0 came from the prefill) and the Mimi chunk of frames i*CH ..
+        i = W + K - 1
+        outs = {"codes": codes[:, 1 + i * CH: 1 + (i + 1) * CH]}
+        if not args.no_mimi:
+            outs["pcm"] = pcm[:, i * CH * 1920: (i + 1) * CH * 1920].cpu().numpy()
+        log(f"outputs of timed step {i - W} of {K} -> {args.dump_outputs}: {dump_outputs(args.dump_outputs, outs)}")
     us_per_frame_step = elapsed / (K * CH) * 1e6
     L_mean = float(np.mean([p.shape[1] for p in mine])) + (W + K / 2) * CH  # mean context over the timed steps
 
