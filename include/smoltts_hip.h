@@ -407,6 +407,47 @@ int smoltts_mimi_encode(SmolttsMimiEncoder* e, const float* pcm_dev, int32_t n_s
                         float* emb_dev, float* gap_dev, void* workspace_dev, size_t workspace_bytes,
                         void* stream);
 
+/* ------------------------------------------------------------------------------ Streamed output formats
+ * The codec's 24 kHz fp32 PCM -> 16-bit little-endian PCM at 8000 / 16000 / 22050 / 44100 / 48000 Hz, or 8 kHz G.711 mu-law
+ * bytes, chunk by chunk (smoltts_amd/csrc/resample.hip).  Over a whole stream the samples equal
+ * scipy.signal.resample_poly(x, up, down) with scipy's default filter (up / down = out_rate / 24000 in lowest terms,
+ * half_len = 10 max(up, down), h = firwin(2 half_len + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up, zero padding at both
+ * ends), quantised as rint(clip(y, -1, 1) * 32767); mu-law is Sun's linear2ulaw of that int16 (bias 0x84, clip 32635).
+ * After N inputs output m is final when half_len + m down <= up N - 1: each call emits the outputs that became final in it and,
+ * behind them, the tail up to ceil(N up / down) computed as if the input ended at N (at most 20 samples).  Outputs are summed in
+ * fp64 in a fixed order, so the bytes do not depend on how the input is chunked. */
+#define SMOLTTS_RESAMPLE_OFF 0   /* slot not converted (its stream stays fp32 at 24 kHz): no outputs, its state does not move */
+#define SMOLTTS_RESAMPLE_S16 1   /* int16 little-endian, 2 bytes per sample */
+#define SMOLTTS_RESAMPLE_ULAW 2  /* G.711 mu-law, 1 byte per sample, out_rate 8000 only */
+
+typedef struct SmolttsResampler SmolttsResampler;
+
+/* Pure host, no device: the filter of out_rate in double (2 half_len + 1 taps into taps[cap]; taps may be NULL to query
+ * up / down / half_len, each of which may be NULL).  SMOLTTS_E_INVALID for an unsupported rate, SMOLTTS_E_CAPACITY when cap is
+ * too small. */
+int smoltts_resample_design(int32_t out_rate, double* taps, int32_t cap, int32_t* up, int32_t* down, int32_t* half_len);
+
+/* Device slab of a resampler for max_batch slots (256-byte aligned, caller-owned): the polyphase tap tables, each slot's rate and
+ * encoding, and two copies of each slot's stream state (<= 64 history samples, int64 input / output positions).  Every slot
+ * starts off.  create uploads the tap tables synchronously. */
+size_t smoltts_resampler_bytes(int32_t max_batch);
+int smoltts_resampler_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsResampler** out);
+void smoltts_resampler_destroy(SmolttsResampler* r);
+/* Bytes per output row that any slot needs for a call of n_in input samples (finals + tail, at the widest rate). */
+size_t smoltts_resampler_out_bytes(int32_t n_in);
+
+/* Start new streams in the listed slots (host arrays) with their rate and encoding (SMOLTTS_RESAMPLE_*; out_rate is ignored
+ * for SMOLTTS_RESAMPLE_OFF); the other slots' streams continue.  Stream-ordered. */
+int smoltts_resampler_reset_slots(SmolttsResampler* r, const int32_t* slots_host, const int32_t* out_rates_host,
+                                  const int32_t* encodings_host, int32_t n_slots, void* stream);
+
+/* One launch for slots [0, batch): slot b consumes valid_in_dev[b] (clamped to [0, n_in]; NULL = n_in) samples of
+ * pcm_dev float [batch][pcm_stride] and writes its outputs of this call, finals then tail, to out_dev bytes [batch][out_stride];
+ * counts_dev int32 [batch][2] = (finals, tail).  Slots that are off write (0, 0).  Calls on one resampler must be ordered on
+ * one stream (the slot states alternate between their two copies). */
+int smoltts_resample_chunk(SmolttsResampler* r, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
+                           const int32_t* valid_in_dev, void* out_dev, int64_t out_stride, int32_t* counts_dev, void* stream);
+
 /* --------------------------------------------------------------- operator-level test entry points */
 enum {  /* prologue applied to the activation operand */
   SMOLTTS_PRO_NONE = 0,

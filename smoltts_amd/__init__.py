@@ -149,7 +149,7 @@ class SmolTTS:
         return np.concatenate(turns, axis=1).astype(np.int32)
 
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
-               reference_upsample: bool = False) -> Iterator["np.ndarray"]:
+               reference_upsample: bool = False, output_format: Optional[str] = None) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -157,8 +157,16 @@ class SmolTTS:
         no tap overlap from the previous frame) -- the chunks then equal the reference's own ``stream`` and no longer its batch
         decode; a quirk kept switchable like ``NumericsMode``'s.
         ``overlap``: the codec step of frame f runs beside frame f + 1 on a second stream (``generate.stream_pcm``); the chunks
-        are the same numbers either way."""
+        are the same numbers either way.
+        ``output_format``: ``pcm_8000`` / ``pcm_16000`` / ``pcm_22050`` / ``pcm_44100`` / ``pcm_48000`` (int16 chunks) or
+        ``ulaw_8000`` (uint8 chunks), converted on the GPU chunk by chunk; over the utterance they concatenate to
+        ``scipy.signal.resample_poly`` of the float32 stream, quantised (formats.py).  ``None`` / ``pcm_24000``: float32."""
         import numpy as np
+
+        from .formats import parse_stream_format
+
+        if output_format is not None:
+            parse_stream_format(output_format)  # an unknown format is refused before any work
 
         from .engine import LMSession, MimiSession
         from .generate import _apply_sampling, stream_pcm
@@ -173,7 +181,7 @@ class SmolTTS:
         _apply_sampling(sess, settings)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
-            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap)
+            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=output_format)
         finally:
             msess.close()
             sess.close()

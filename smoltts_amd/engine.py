@@ -109,6 +109,8 @@ _EXPORTS = [
     "smoltts_session_slab_bytes_kv", "smoltts_session_create_kv", "smoltts_k_attention_kv", "smoltts_session_set_sampling", "smoltts_k_sample",
     "smoltts_lm_prefill_chunk", "smoltts_lm_prefill_deferred", "smoltts_mimi_reset_slots", "smoltts_mimi_encoder_create", "smoltts_mimi_encoder_destroy", "smoltts_mimi_encode_frames",
     "smoltts_mimi_encode_workspace_bytes", "smoltts_mimi_encode", "smoltts_mimi_session_set_option",
+    "smoltts_resample_design", "smoltts_resampler_bytes", "smoltts_resampler_create", "smoltts_resampler_destroy",
+    "smoltts_resampler_out_bytes", "smoltts_resampler_reset_slots", "smoltts_resample_chunk",
 ]
 
 
@@ -196,6 +198,17 @@ def load_library(path: Optional[Path] = None):
         lib.smoltts_profile_begin.argtypes = [C.c_int32] * 4
         lib.smoltts_profile_end.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     lib.smoltts_mimi_session_set_option.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.smoltts_resample_design.argtypes = [C.c_int32, C.c_void_p, C.c_int32] + [C.POINTER(C.c_int32)] * 3
+    lib.smoltts_resampler_bytes.argtypes = [C.c_int32]
+    lib.smoltts_resampler_bytes.restype = C.c_size_t
+    lib.smoltts_resampler_out_bytes.argtypes = [C.c_int32]
+    lib.smoltts_resampler_out_bytes.restype = C.c_size_t
+    lib.smoltts_resampler_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.smoltts_resampler_destroy.argtypes = [C.c_void_p]
+    lib.smoltts_resampler_destroy.restype = None
+    lib.smoltts_resampler_reset_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.smoltts_resample_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_void_p]
     if lib.smoltts_abi_version() != 6:
         raise SmolttsError("libsmoltts_hip.so ABI version mismatch")
     if path is None:
@@ -769,6 +782,89 @@ class MimiSession:
         if getattr(self, "handle", None):
             torch.cuda.synchronize()
             self.lib.smoltts_mimi_session_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------------------- streamed output formats
+def resample_design(out_rate: int):
+    """(taps float64 [2 half_len + 1], up, down, half_len) of ``out_rate``: scipy.signal.resample_poly's default filter, designed
+    on the host by the library (no device needed).  Raises SmolttsError for an unsupported rate."""
+    lib = load_library()
+    up, down, half = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.smoltts_resample_design(int(out_rate), None, 0, C.byref(up), C.byref(down), C.byref(half)), "smoltts_resample_design")
+    taps = np.zeros(2 * half.value + 1, np.float64)
+    check(lib.smoltts_resample_design(int(out_rate), taps.ctypes.data, taps.size, C.byref(up), C.byref(down), C.byref(half)),
+          "smoltts_resample_design")
+    return taps, up.value, down.value, half.value
+
+
+class Resampler:
+    """Per-slot conversion of streamed 24 kHz fp32 PCM to ``pcm_<rate>`` int16 / ``ulaw_8000`` bytes on the GPU
+    (include/smoltts_hip.h, "Streamed output formats"): one launch per call for every slot, each at its own format.  Slots
+    start off; ``reset_slots`` starts a new stream in a slot with its format."""
+
+    def __init__(self, device: torch.device, max_batch: int, max_in: int):
+        self.lib = load_library()
+        self.device, self.B, self.max_in = device, max_batch, max_in
+        need = self.lib.smoltts_resampler_bytes(max_batch)
+        if need == 0:
+            raise SmolttsError("smoltts_resampler_bytes returned 0 (bad sizes)")
+        self.slab = _alloc_slab(need, device)
+        h = C.c_void_p()
+        check(self.lib.smoltts_resampler_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_resampler_create")
+        self.handle = h
+        self.out_stride = int(self.lib.smoltts_resampler_out_bytes(max_in))
+        self.formats = [(24000, 0)] * max_batch  # (rate, SMOLTTS_RESAMPLE_*) per slot
+
+    def reset_slots(self, slots: Sequence[int], formats: Sequence[str]) -> None:
+        """Start new streams in ``slots`` with their ``output_format`` (``pcm_24000``: the slot is not converted)."""
+        from .formats import parse_stream_format
+
+        parsed = [parse_stream_format(f) for f in formats]
+        n = len(slots)
+        arr = lambda v: (C.c_int32 * n)(*v)  # noqa: E731
+        check(self.lib.smoltts_resampler_reset_slots(self.handle, arr(slots), arr([p[0] for p in parsed]), arr([p[1] for p in parsed]), n,
+                                                     current_stream_ptr()), "smoltts_resampler_reset_slots")
+        for b, p in zip(slots, parsed):
+            self.formats[b] = p
+
+    def new_outputs(self, batch: int):
+        """Device buffers of one call: (bytes uint8 [batch, out_stride], counts int32 [batch, 2])."""
+        return (torch.empty(batch, self.out_stride, dtype=torch.uint8, device=self.device),
+                torch.empty(batch, 2, dtype=torch.int32, device=self.device))
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
+        """Convert ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream;
+        ``valid``: device int32 [batch], the samples of each row that are real (the rest is not consumed)."""
+        batch = pcm.shape[0]
+        assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and batch <= self.B and 0 <= n_in <= min(self.max_in, pcm.shape[1])
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[0] >= batch and out.shape[1] >= self.out_stride
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 2 * batch
+        assert valid is None or (valid.dtype == torch.int32 and valid.is_contiguous() and valid.numel() >= batch)
+        check(self.lib.smoltts_resample_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1],
+                                              dptr(counts), current_stream_ptr()), "smoltts_resample_chunk")
+
+    def slot_bytes(self, host_out: np.ndarray, host_counts: np.ndarray, b: int, tail: bool = False,
+                   output_format: Optional[str] = None) -> np.ndarray:
+        """Slot ``b``'s samples of a call, copied to the host: int16 for pcm_*, uint8 for ulaw_8000; with the tail if ``tail``.
+        ``output_format``: the format the call ran with, when the slot may have been restarted since (default: its current one)."""
+        from .formats import parse_stream_format
+
+        enc = self.formats[b][1] if output_format is None else parse_stream_format(output_format)[1]
+        n = int(host_counts[b, 0]) + (int(host_counts[b, 1]) if tail else 0)
+        width = 1 if enc == 2 else 2
+        return host_out[b, : n * width].view(np.uint8 if enc == 2 else np.int16).copy()
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize()
+            self.lib.smoltts_resampler_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

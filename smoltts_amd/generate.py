@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from .config import GenerationSettings
-from .engine import LMEngine, LMSession
+from .engine import LMEngine, LMSession, Resampler
+from .formats import ENC_OFF, parse_stream_format
 
 
 @dataclass
@@ -185,7 +186,7 @@ def generate_blocking(model: LMEngine, prompt: np.ndarray, generation_settings: 
 
 
 def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bool = True, max_frames: Optional[int] = None,
-               overlap: bool = True) -> Iterator[np.ndarray]:
+               overlap: bool = True, output_format: Optional[str] = None) -> Iterator[np.ndarray]:
     """One utterance in slot 0 of ``session`` -> one 1920-sample float32 chunk per generated frame, as the reference's
     ``SmolTTS.stream`` yields them (mlx_inference/src/smoltts_mlx/__init__.py:83-95: every frame of ``SingleBatchGenerator`` through
     ``codec.decode_step``), the terminating ``<|im_end|>`` frame included.
@@ -195,7 +196,12 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     the codec step of frame f goes out on a second stream -- the host has waited for frame f's event by then, it never parks a
     device-side wait in a queue.  Every chunk still leaves as soon as its own codec step has run; the numbers are those of the
     one-stream loop (``overlap=False``), only the order in which the GPU sees the launches changes.  A frame queued behind the
-    last one is not a frame: a stopped slot is frozen (smoltts_lm_decode)."""
+    last one is not a frame: a stopped slot is frozen (smoltts_lm_decode).
+
+    ``output_format`` (``pcm_<rate>`` / ``ulaw_8000``, formats.py): every chunk is converted on the codec stream right behind its
+    decode (``engine.Resampler``) and leaves as int16 / uint8 samples -- the outputs that became final with it; the resampler's
+    tail (<= 20 samples) follows the last chunk.  A frame the slot did not produce is not fed to the resampler (its valid count is
+    taken from the device's frame counter), so the tail is that of the last real frame.  ``None`` / ``pcm_24000``: float32."""
     s = session
     limit = s.max_frames if max_frames is None else min(max_frames, s.max_frames)
     dev = s.engine.device
@@ -207,8 +213,16 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     pcm_dev = torch.empty(1, 1920, dtype=torch.float32, device=dev)
     pcm_host = torch.empty(1, 1920, dtype=torch.float32).pin_memory()
     state_host = torch.zeros(2, dtype=torch.int32).pin_memory()  # n_frames[0], done[0]
+    rs = None
+    if output_format is not None and parse_stream_format(output_format)[1] != ENC_OFF:
+        rs = Resampler(dev, 1, 1920)
+        rs_out, rs_counts = rs.new_outputs(1)
+        rs_out_host = torch.empty(rs_out.shape, dtype=torch.uint8).pin_memory()
+        rs_counts_host = torch.empty(rs_counts.shape, dtype=torch.int32).pin_memory()
     with torch.cuda.stream(codec_stream):
         msession.reset()
+        if rs is not None:
+            rs.reset_slots([0], [output_format])
     with torch.cuda.stream(lm_stream):
         s.prefill([prompt], stop_on_eos=stop_on_eos)  # frame 0
         ev = torch.cuda.Event()
@@ -227,12 +241,24 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
                 state_host[0:1].copy_(s.n_frames[0:1], non_blocking=True)
                 state_host[1:2].copy_(s.done[0:1], non_blocking=True)
                 msession.decode_chunk(s.codes[:, f:f + 1], 0, 1, pcm_dev, code_offset=1)  # (decode_chunk writes frame f0 at pcm[:, 1920 f0:])
-                pcm_host.copy_(pcm_dev, non_blocking=True)
+                if rs is not None:
+                    valid = (s.n_frames[0:1] > f).to(torch.int32) * 1920  # 0 once the slot has stopped: garbage is not consumed
+                    rs.chunk(pcm_dev, 1920, rs_out, rs_counts, valid=valid)
+                    rs_out_host.copy_(rs_out, non_blocking=True)
+                    rs_counts_host.copy_(rs_counts, non_blocking=True)
+                else:
+                    pcm_host.copy_(pcm_dev, non_blocking=True)
             codec_stream.synchronize()
             n, done = int(state_host[0]), int(state_host[1])
             if n <= f:  # the slot had stopped before this frame
+                if rs is not None:  # (this call consumed nothing: its tail is that of the last frame)
+                    yield rs.slot_bytes(rs_out_host.numpy(), rs_counts_host.numpy(), 0, tail=True)
                 break
-            yield pcm_host.numpy().reshape(-1).copy()
+            last = bool(done and n == f + 1) or f + 1 >= limit
+            if rs is not None:
+                yield rs.slot_bytes(rs_out_host.numpy(), rs_counts_host.numpy(), 0, tail=last)
+            else:
+                yield pcm_host.numpy().reshape(-1).copy()
             if done and n == f + 1:
                 break
             if not overlap and f + 1 < limit:
@@ -246,3 +272,5 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     finally:
         lm_stream.synchronize()
         codec_stream.synchronize()
+        if rs is not None:
+            rs.close()

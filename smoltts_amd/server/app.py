@@ -18,7 +18,11 @@ from fastapi import APIRouter, FastAPI, HTTPException, Query, Request, Response
 from fastapi.responses import StreamingResponse
 from pydantic import BaseModel, Field
 
+from ..formats import lin2ulaw
 from .wav import pcm_to_wav_bytes
+
+# output_format of the stream route: the codec's float32 at 24 kHz, or a format converted on the GPU (formats.py)
+StreamFormat = Literal["pcm_24000", "pcm_8000", "pcm_16000", "pcm_22050", "pcm_44100", "pcm_48000", "ulaw_8000"]
 
 
 class TTSCore:
@@ -44,13 +48,16 @@ class TTSCore:
             raise HTTPException(status_code=400, detail=str(e))
         return self.format_audio_chunk(pcm, response_format)
 
-    def stream_audio(self, input_text: str, voice: Union[str, int]):
-        chunks = (self.scheduler.iter_chunks(self.scheduler.submit(input_text, str(voice), stream=True))
-                  if self.scheduler is not None else self.model.stream(input_text, str(voice)))
+    def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000"):
+        """Chunks as bytes: float32 at 24 kHz for ``pcm_24000``; otherwise the int16 / mu-law samples the model or scheduler
+        converted on the GPU (the format is passed on only when it is not ``pcm_24000``)."""
+        kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
+        chunks = (self.scheduler.iter_chunks(self.scheduler.submit(input_text, str(voice), stream=True, **kw))
+                  if self.scheduler is not None else self.model.stream(input_text, str(voice), **kw))
         try:
             for chunk in chunks:
                 if chunk is not None:
-                    yield np.asarray(chunk, dtype=np.float32).tobytes()
+                    yield (np.asarray(chunk, dtype=np.float32) if not kw else np.ascontiguousarray(chunk)).tobytes()
         finally:
             chunks.close()  # a client that went away mid-stream: the scheduler takes its slot back (BatchScheduler.cancel)
 
@@ -60,7 +67,9 @@ class TTSCore:
         kind, _, rate = output_format.partition("_")
         sample_rate = int(rate.split("_")[0]) if rate else 24000
         pcm_data = np.asarray(pcm_data, dtype=np.float32).reshape(-1)
-        if kind not in ("pcm", "wav", "mp3"):
+        if kind == "ulaw" and sample_rate != 8000:
+            raise HTTPException(status_code=400, detail=f"Format {output_format} not yet supported (ulaw_8000 only)")
+        if kind not in ("pcm", "wav", "mp3", "ulaw"):
             raise HTTPException(status_code=400, detail=f"Format {output_format} not yet supported")
         if kind == "mp3":
             raise HTTPException(status_code=501, detail="mp3 output is not available in this build (no encoder in the image)")
@@ -71,8 +80,9 @@ class TTSCore:
 
             n = int(len(pcm_data) * sample_rate / 24000)
             pcm_data = signal.resample(pcm_data, n).astype(np.float32) if n > 0 else np.zeros(0, np.float32)
-        if kind == "pcm":
-            return np.rint(np.clip(pcm_data, -1.0, 1.0) * 32767).astype(np.int16).tobytes(), "audio/x-pcm"
+        if kind in ("pcm", "ulaw"):
+            s16 = np.rint(np.clip(pcm_data, -1.0, 1.0) * 32767).astype(np.int16)
+            return (s16.tobytes(), "audio/x-pcm") if kind == "pcm" else (lin2ulaw(s16).tobytes(), "audio/basic")  # ulaw: G.711 of the int16
         return pcm_to_wav_bytes(pcm_data, sample_rate), "audio/wav"
 
 
@@ -112,10 +122,12 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
 
 @eleven_router.post("/text-to-speech/{voice_id}/stream")
 def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
-                     output_format: Literal["pcm_24000"] = "pcm_24000"):
+                     output_format: StreamFormat = "pcm_24000"):
+    """pcm_24000: raw float32 (the reference's stream); pcm_<rate>: int16 little-endian; ulaw_8000: G.711 mu-law bytes."""
     core = http_request.app.state.tts_core
-    return StreamingResponse(core.stream_audio(item.text, voice=voice_id), media_type="audio/wav", headers={
-        "Content-Disposition": 'attachment; filename="speech.pcm"', "X-Sample-Rate": "24000"})
+    kind, rate = output_format.split("_")
+    return StreamingResponse(core.stream_audio(item.text, voice=voice_id, output_format=output_format), media_type="audio/wav", headers={
+        "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate})
 
 
 @eleven_router.get("/stats")

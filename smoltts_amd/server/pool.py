@@ -72,7 +72,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
     def pump(rid: int, req) -> None:
         try:
             for chunk in sched.iter_chunks(req):
-                res_q.put((rid, "chunk", np.ascontiguousarray(chunk, dtype=np.float32)))
+                res_q.put((rid, "chunk", np.ascontiguousarray(chunk)))  # float32, or int16 / uint8 for a streamed output_format
             res_q.put((rid, "end", None))
         except Exception as e:
             res_q.put((rid, "error", (type(e).__name__, str(e))))
@@ -86,8 +86,9 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
             if msg[0] == "close":
                 break
             if msg[0] == "submit":
-                _, rid, text, voice, stream, max_new_tokens = msg
-                req = sched.submit(text, voice, stream=stream, max_new_tokens=max_new_tokens)
+                _, rid, text, voice, stream, max_new_tokens = msg[:6]
+                extra = msg[6] if len(msg) > 6 else {}  # (output_format, only when the client set one)
+                req = sched.submit(text, voice, stream=stream, max_new_tokens=max_new_tokens, **extra)
                 with lock:
                     live[rid] = req
                 threading.Thread(target=pump, args=(rid, req), name=f"smoltts-pump-{rid}", daemon=True).start()
@@ -158,7 +159,12 @@ class GpuPool:
         return None if kind == "ready" else f"GPU worker failed to start: {payload}"
 
     # ------------------------------------------------------------------ client side (the BatchScheduler interface)
-    def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None) -> _PoolRequest:
+    def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
+               output_format: Optional[str] = None) -> _PoolRequest:
+        if output_format is not None:  # refused here, before a worker sees it
+            from ..formats import parse_stream_format
+
+            parse_stream_format(output_format)
         with self._lock:
             if self._closing:
                 raise RuntimeError("pool closed")
@@ -169,7 +175,8 @@ class GpuPool:
             req = _PoolRequest(next(self._ids), w)
             self._reqs[req.rid] = req
             self._load[w] += 1
-        self._req_qs[w].put(("submit", req.rid, text, voice, stream, max_new_tokens))
+        msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
+        self._req_qs[w].put(msg + ({"output_format": output_format},) if output_format is not None else msg)
         return req
 
     def synthesize(self, text: str, voice: str = "heart", max_new_tokens: Optional[int] = None) -> np.ndarray:

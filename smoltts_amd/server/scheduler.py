@@ -46,6 +46,7 @@ class _Request:
     stream_done: bool = False  # streaming: the last frames have been seen (the end marker goes out with the last codec pass)
     cancelled: bool = False  # set by the client side (cancel / an abandoned chunk iterator), honoured by the worker at its next look
     closed: bool = False  # the end marker (None or an exception) has been queued
+    output_format: Optional[str] = None  # streaming: pcm_<rate> / ulaw_8000 converted on the GPU (None: float32 at 24 kHz)
 
 
 @dataclass
@@ -102,6 +103,7 @@ class BatchScheduler:
         self._codec_slot_age = [0] * self.CODEC_BATCH  # passes a slot has seen since its last restart
         self._codec_wait = 0                    # ticks since the last pass while work was waiting
         self._stream_codec = None               # codec session whose slot b carries the stream of LM slot b (streaming requests)
+        self._stream_rs = None                  # engine.Resampler beside it: slot b converts the stream of LM slot b when it has a format
         self._codec_age = [0] * max_batch       # codec passes each of its slots has seen since that slot's last reset
         self._deliveries: List[tuple] = []      # (event, pcm on the device, [(request, first sample, n samples, last?)]) in order
         self._snaps: List[tuple] = []           # snapshots of the output ring the host has not looked at yet (oldest first)
@@ -116,12 +118,23 @@ class BatchScheduler:
         self._thread.start()
 
     # ------------------------------------------------------------------ client side
-    def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None) -> _Request:
+    def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
+               output_format: Optional[str] = None) -> _Request:
+        """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
+        in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32."""
+        if output_format is not None:
+            from ..formats import ENC_OFF, parse_stream_format
+
+            if not stream:
+                raise ValueError("output_format applies to streaming requests")
+            if parse_stream_format(output_format)[1] == ENC_OFF:
+                output_format = None
         if self._dead is not None:  # the worker is gone (engine failure or close): nobody would ever answer
             raise RuntimeError(f"scheduler is not running: {self._dead}")
         if self._draining:
             raise RuntimeError("scheduler is not running: shutting down")
-        req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens))
+        req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
+                       output_format=output_format)
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
@@ -166,7 +179,7 @@ class BatchScheduler:
         self._stop.set()
         self._wake.set()
         self._thread.join(timeout=30)
-        for name in ("_batch_codec", "_stream_codec"):
+        for name in ("_batch_codec", "_stream_codec", "_stream_rs"):
             if getattr(self, name) is not None:
                 getattr(self, name).close()
                 setattr(self, name, None)
@@ -202,14 +215,45 @@ class BatchScheduler:
             if self._stream_codec is None:
                 self._stream_codec = MimiSession(self.tts.codec, max_batch=self.B, max_chunk_frames=max(self.tick, 1), products=self.codec_products)
                 self._stream_codec.reset()
+            if self._stream_rs is None and any(r.output_format for r in new if r.stream):
+                from ..engine import Resampler
+
+                self._stream_rs = Resampler(self.session.engine.device, self.B, max(self.tick, 1) * 1920)  # every slot starts off
             if not self.overlap_stream_codec:  # (overlapped: the slot's stream restarts on the codec stream, right before the pass
                 self._stream_codec.reset_slots(streams)  # of the request's first tick and behind the previous tenant's last pass)
+                self._reset_formats([r for r in new if r.stream])
                 for b in streams:
                     self._codec_age[b] = 0
         for r in new:
             r.first_tick = self._tick_no
             r.last_tick = self._tick_no + -(-(r.max_new_tokens + 1) // self.tick) - 1  # ceil(frames / tick) ticks from first_tick on
             self._active[r.slot] = r
+
+    def _reset_formats(self, reqs: List[_Request]) -> None:
+        """Start the resampler streams of new streaming tenants (a slot without a format is switched off)."""
+        if self._stream_rs is not None and reqs:
+            self._stream_rs.reset_slots([r.slot for r in reqs], [r.output_format or "pcm_24000" for r in reqs])
+
+    def _convert(self, pcm, n_frames_d, reqs: List[_Request], tick_no: int):
+        """The resample launch of a stream codec pass (current stream, right behind the decode): slot b of a request in ``reqs``
+        consumes the samples of the frames the tick's frame counter ``n_frames_d`` (device) gives it; every other slot none.
+        Returns (bytes, counts) on the device, or None when no request of the pass has a format (no launch)."""
+        rs = self._stream_rs
+        if rs is None or not any(r.output_format for r in reqs):
+            return None
+        from ..engine import upload
+
+        torch = self._torch
+        f0 = np.zeros(self.B, np.int32)
+        cap = np.zeros(self.B, np.int32)  # frames the request may have: 0 for slots without a live stream
+        for r in reqs:
+            f0[r.slot] = (tick_no - r.first_tick) * self.tick
+            cap[r.slot] = r.max_new_tokens + 1
+        f0_d, cap_d = upload([f0, cap], self.session.engine.device)
+        valid = ((torch.minimum(n_frames_d.to(torch.int32), cap_d) - f0_d).clamp_(0, self.tick) * 1920).to(torch.int32)
+        out, counts = rs.new_outputs(self.B)
+        rs.chunk(pcm, self.tick * 1920, out, counts, valid=valid)
+        return out, counts
 
     def _admit(self) -> None:
         if self._side is not None and self._side["state"] == "running":
@@ -324,7 +368,10 @@ class BatchScheduler:
             chunk = s.codes[torch.arange(self.B, device="cuda")[:, None], idx][:, :, -nq:].contiguous()
             pcm = torch.empty(self.B, self.tick * 1920, dtype=torch.float32, device="cuda")
             self._stream_codec.decode_chunk(chunk, 0, self.tick, pcm, code_offset=0)
-        snap = (s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no, pcm)
+            conv = self._convert(pcm, s.n_frames, streaming, self._tick_no)
+        else:
+            conv = None
+        snap = (s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no, pcm, conv)
         snap[3].record(torch.cuda.current_stream())
         self._snaps.append(snap)
         self._tick_no += 1
@@ -334,23 +381,26 @@ class BatchScheduler:
         only just been queued; its predecessor finished before that tick could start)."""
         torch = self._torch
         while len(self._snaps) > keep:
-            codes_d, n_d, done_d, ev, tick_no, pcm_d = self._snaps.pop(0)
+            codes_d, n_d, done_d, ev, tick_no, pcm_d, conv_d = self._snaps.pop(0)
             # the host waits for the snapshot, then copies on the copy stream: a device-side wait would park a blocked barrier
             # packet in a second hardware queue for the whole tick, and the frame graphs' dependent launches get slower for it
             self._wait_event(ev)
-            stream_pass = self._launch_stream_codec(codes_d, tick_no) if self.overlap_stream_codec else None
+            stream_pass = self._launch_stream_codec(codes_d, n_d, tick_no) if self.overlap_stream_codec else None
             with torch.cuda.stream(self._copy_stream):
                 codes = codes_d.to("cpu", non_blocking=True)
                 n_frames = n_d.to("cpu", non_blocking=True)
                 done = done_d.to("cpu", non_blocking=True)
                 pcm = pcm_d.to("cpu", non_blocking=True) if pcm_d is not None else None
+                conv = tuple(t.to("cpu", non_blocking=True) for t in conv_d) if conv_d is not None else None
             self._sync_copies()
-            self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), tick_no, None if pcm is None else pcm.numpy(), stream_pass)
+            self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), tick_no, None if pcm is None else pcm.numpy(), stream_pass,
+                        None if conv is None else tuple(t.numpy() for t in conv))
 
-    def _launch_stream_codec(self, codes_d, tick_no: int):
+    def _launch_stream_codec(self, codes_d, n_d, tick_no: int):
         """The codec pass of the streaming requests for tick ``tick_no``, on the codec stream, from the tick's snapshot of the
         output ring (the host has just seen that snapshot's event, so the next tick is running meanwhile).  Returns
-        (pcm on the device, event) or None when no stream was alive in that tick."""
+        (pcm on the device, event, what to keep alive, converted bytes and counts on the device or None) or None when no stream was
+        alive in that tick."""
         torch = self._torch
         alive = [r for r in self._retiring + list(self._active.values())
                  if r.stream and r.first_tick <= tick_no <= r.last_tick and not r.closed and not r.stream_done]
@@ -365,6 +415,7 @@ class BatchScheduler:
             restart += [b for b in range(self.B) if b not in live and (self._codec_age[b] + 2) * 2 * self.tick > cap]  # ... idle slots before they overflow
             if restart:
                 self._stream_codec.reset_slots(sorted(set(restart)))
+                self._reset_formats([r for r in alive if r.first_tick == tick_no])
                 for b in restart:
                     self._codec_age[b] = 0
             for b in range(self.B):
@@ -378,9 +429,10 @@ class BatchScheduler:
             chunk = codes_d[torch.arange(self.B, device="cuda")[:, None], idx][:, :, -nq:].contiguous()
             pcm = torch.empty(self.B, self.tick * 1920, dtype=torch.float32, device="cuda")
             self._stream_codec.decode_chunk(chunk, 0, self.tick, pcm, code_offset=0)
+            conv = self._convert(pcm, n_d, alive, tick_no)
             ev = torch.cuda.Event()
             ev.record(self._codec_stream)
-        return pcm, ev, codes_d  # (codes_d: kept alive until the pass has run)
+        return pcm, ev, (codes_d, n_d), conv  # (codes_d, n_d: kept alive until the pass has run)
 
     def _wait_event(self, ev) -> None:
         t = time.perf_counter()
@@ -392,7 +444,7 @@ class BatchScheduler:
         self._copy_stream.synchronize()
         self._gpu_wait_s += time.perf_counter() - t
 
-    def _drain(self, codes, n_frames, done, tick_no: int, pcm, stream_pass=None) -> None:
+    def _drain(self, codes, n_frames, done, tick_no: int, pcm, stream_pass=None, conv=None) -> None:
         stream_items = []  # overlapped codec pass of this tick: (request, pcm row, samples, last?) handed out by _deliver
         nq = self.tts.config.num_codebooks
         tc = self.tts.token_config
@@ -432,7 +484,12 @@ class BatchScheduler:
                         r.stream_done = True
                         release(r)  # the end marker follows the last chunk, in _deliver
                     continue
-                if k > 0:
+                if r.output_format and conv is not None and (k > 0 or finished):
+                    chunk = self._stream_rs.slot_bytes(conv[0], conv[1], slot, tail=finished, output_format=r.output_format)  # (the tail goes out with the last chunk)
+                    if chunk.size:
+                        r.out.put(chunk)
+                    self._counts["frames_delivered"] += max(k, 0)
+                elif k > 0:
                     assert pcm is not None and r.emitted == (tick_no - r.first_tick) * self.tick, "stream bookkeeping out of step"
                     r.out.put(pcm[slot, : k * 1920].copy())
                     self._counts["frames_delivered"] += k
@@ -452,9 +509,9 @@ class BatchScheduler:
                 release(r)
                 self._finished.append(r)
         if stream_items:
-            pcm_d, ev, keep = stream_pass if stream_pass is not None else (None, None, None)
+            pcm_d, ev, keep, conv_d = stream_pass if stream_pass is not None else (None, None, None, None)
             urgent = any(it[4] for it in stream_items)  # a first chunk: handed out as soon as the pass is through
-            self._deliveries.append((ev, pcm_d, [it[:4] for it in stream_items], urgent, keep))
+            self._deliveries.append((ev, pcm_d, [it[:4] for it in stream_items], urgent, keep, conv_d))
 
     # ------------------------------------------------------------------ worker: codec passes and delivery
     def _codec_backlog(self) -> bool:
@@ -484,7 +541,7 @@ class BatchScheduler:
             cols = np.concatenate(r.pending) if r.pending else np.zeros((0, nq), np.int32)
             r.pending = []
             if cols.shape[0] == 0:  # nothing to decode (every frame was non-semantic): just close the response, in order
-                self._deliveries.append((None, None, [(r, 0, 0, True)], False, None))
+                self._deliveries.append((None, None, [(r, 0, 0, True)], False, None, None))
                 continue
             b = jobs.index(None)
             jobs[b] = _CodecJob(r, cols)
@@ -543,25 +600,33 @@ class BatchScheduler:
             items.append((j.req, b, n[b] * 1920, fin))
             if fin:
                 jobs[b] = None
-        self._deliveries.append((ev, pcm, items, False, None))
+        self._deliveries.append((ev, pcm, items, False, None, None))
 
     def _deliver(self, wait: bool) -> None:
         """Hand finished codec passes to their requests, in order; ``wait``: block on the oldest one."""
         torch = self._torch
         while self._deliveries:
-            ev, pcm, items, _, _ = self._deliveries[0]
+            ev, pcm, items, _, _, conv = self._deliveries[0]
             wait = wait or any(d[3] for d in self._deliveries)  # a stream's first chunk is somewhere in the line: do not dawdle
+            host = conv_h = None
             if ev is not None:
                 if not (wait or ev.query()):
                     return
                 self._wait_event(ev)
                 with torch.cuda.stream(self._copy_stream):
                     host = pcm.to("cpu", non_blocking=True)
+                    conv_h = tuple(t.to("cpu", non_blocking=True) for t in conv) if conv is not None else None
                 self._sync_copies()
                 host = host.numpy()
+                conv_h = tuple(t.numpy() for t in conv_h) if conv_h is not None else None
             self._deliveries.pop(0)
             for r, b, n, fin in items:
-                if n and not r.cancelled:
+                if r.output_format and conv_h is not None:
+                    chunk = self._stream_rs.slot_bytes(conv_h[0], conv_h[1], b, tail=fin, output_format=r.output_format)  # (the tail goes out with the last chunk)
+                    if chunk.size and not r.cancelled:
+                        r.out.put(chunk)
+                        self._counts["frames_delivered"] += n // 1920
+                elif n and not r.cancelled:
                     r.out.put(host[b, :n].copy())
                     self._counts["frames_delivered"] += n // 1920
                 if fin:
