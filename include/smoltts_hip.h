@@ -262,6 +262,30 @@ int smoltts_session_set_option(SmolttsSession* s, int32_t option, int32_t value)
  * keeps only tokens with p >= min_p * p_max (applied to the depth tokens only when fast_temp > 0). */
 int smoltts_session_set_sampling(SmolttsSession* s, float temp, float fast_temp, float min_p, uint64_t seed);
 
+/* (ABI 6) Per-slot sampling ("slot mode").  One entry per slot; a slot whose temp (slow token) / fast_temp (depth codes) is <= 0
+ * picks that token greedily (torch.argmax, margin bookkeeping as above).  min_p is the effective cut (0 = none; applied to the
+ * depth codes only when fast_temp > 0).  A sampled row of slot mode draws with the REQUEST key
+ *   u = uniform01(seed, 0, frames[slot], step, column)       (smoltts_amd/csrc/argmax_dev.h)
+ * -- the entry's own seed, unsalted, and the slot's frame counter (0 at the tenant's frame 0): the draw does not depend on the
+ * slot, on the slot's earlier tenants or on the other slots of the batch.  Step 0 is the slow token, step i the depth code i - 1. */
+typedef struct SmolttsSlotSampling {
+  float temp;
+  float fast_temp;
+  float min_p;
+  uint32_t reserved;  /* 0 */
+  uint64_t seed;
+} SmolttsSlotSampling;
+
+/* Set the entries of slots_host[0 .. n) (the arrays are read before the call returns).  The first call switches the session to
+ * slot mode for good (every other slot starts greedy, seed 0); smoltts_session_set_sampling no longer affects the picks then.
+ * The entries are uploaded on `stream` from a pinned staging ring of the session (the host never waits for the stream) and
+ * are seen by the first pick behind them on that stream.  The session's frame graphs come in one captured set per form --
+ * slow token greedy for every slot or not, depth codes greedy for every slot or not -- chosen from the entries at each decode /
+ * prefill call: a form where no slot samples is exactly the session-wide greedy launch sequence.  Calls that set entries
+ * and the frames that read them must be ordered on one stream. */
+int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* temp_host,
+                                      const float* fast_temp_host, const float* min_p_host, const uint64_t* seed_host, void* stream);
+
 /* Device pointers to the session's results (valid for the session's lifetime):
  *   codes      int32 [max_batch][max_frames][1 + n_fast]   emitted columns (slow id, codes)
  *   n_frames   int32 [max_batch]                            frames emitted so far per slot
@@ -669,6 +693,11 @@ int smoltts_k_argmax(const float* logits_dev, int32_t n_rows, int32_t n_cols, in
 /* ids[r] ~ softmax(logits[r] / temp) (min_p as above); row r uses the stream (seed, r, frame_base + r, step). */
 int smoltts_k_sample(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, float temp, float min_p,
                      uint64_t seed, int32_t frame_base, int32_t step, int32_t* ids_dev, void* stream);
+
+/* (ABI 6) One row per workgroup, row r with its own entry table_dev[r] at `step` (0: temp; > 0: fast_temp, min_p as in the
+ * session) and the request key of slot mode with frame frames_dev[r] (NULL: r); ids_dev[r] receives the pick. */
+int smoltts_k_sample_rows(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const SmolttsSlotSampling* table_dev,
+                          const int32_t* frames_dev, int32_t step, int32_t* ids_dev, void* stream);
 
 int smoltts_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, int32_t n_rows,
                         int32_t dim, float eps, float* out_dev, void* stream);

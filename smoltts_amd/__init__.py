@@ -52,6 +52,7 @@ class SmolTTS:
         self._encoder = None
         self.sampling_rate = 24_000
         self.verbose = verbose  # print the reference's per-call timing lines (lm/generate.py:187-214)
+        self.last_sampling = None  # resolved RequestSampling list of the last call that was given sampling= (seeds included)
         self.last_stats: dict = {}  # timing of the last generate_codes / __call__ (BatchGenerator.stats + codec_ms)
 
     # -- prompt (``_get_prompt``, __init__.py:120-151)
@@ -64,16 +65,24 @@ class SmolTTS:
         # the reference façade always uses GenerationSettings() (temp 0.7 / 0.7, __init__.py:77,85)
         return generation_settings or GenerationSettings()
 
-    def generate_codes(self, inputs: List[str], voices: Optional[List[str]] = None, generation_settings=None, speakers=None):
-        """Batched synthesis to audio-code grids: one (n_codebooks, F_b) uint32 array per input."""
+    def generate_codes(self, inputs: List[str], voices: Optional[List[str]] = None, generation_settings=None, speakers=None,
+                       sampling=None):
+        """Batched synthesis to audio-code grids: one (n_codebooks, F_b) uint32 array per input.
+        ``sampling``: a ``config.RequestSampling`` for every input, or a list of one per input; missing fields come from the
+        generation settings, and a sampled entry without a seed draws one (see ``last_sampling``).  The inputs then sample
+        independently, each with the request key of its seed: the same seed gives the same codes whatever the
+        other inputs are, as long as the batch selects the same kernel variants.  None: every input samples with the settings."""
         import numpy as np
 
-        from .generate import BatchGenerator
+        from .generate import BatchGenerator, resolve_sampling
 
         voices = voices or ["heart"] * len(inputs)
         speakers = speakers or [None] * len(inputs)
         prompts = [self._get_prompt(t, v, sp) for t, v, sp in zip(inputs, voices, speakers)]
-        gen = BatchGenerator(self.lm, prompts, self._settings(generation_settings), frames_per_sync=16)
+        settings = self._settings(generation_settings)
+        resolved = resolve_sampling(sampling, settings, len(inputs))
+        self.last_sampling = resolved  # what the call sampled with, seeds included (None: the settings, session-wide)
+        gen = BatchGenerator(self.lm, prompts, settings, frames_per_sync=16, sampling=resolved)
         cols: List[list] = [[] for _ in inputs]
         for row in gen:
             for b, tok in enumerate(row):
@@ -111,10 +120,11 @@ class SmolTTS:
             print(f"Decoded {F_} frames to PCM in {self.last_stats['codec_ms']:.1f} ms")
         return pcm
 
-    def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None):
-        """Returns flattened float32 PCM (reference __call__, __init__.py:64-81)."""
+    def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None):
+        """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
+        (per-request temperature / min_p / seed, as in ``generate_codes``)."""
         codes = self.generate_codes([input], [voice if voice is not None else "heart"], generation_settings,
-                                    speakers=None if speaker is None else [speaker])[0]
+                                    speakers=None if speaker is None else [speaker], sampling=sampling)[0]
         return self.decode_codes(codes)
 
     # -- voice-clone prompts (``create_speaker``, __init__.py:97-118)
@@ -149,7 +159,7 @@ class SmolTTS:
         return np.concatenate(turns, axis=1).astype(np.int32)
 
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
-               reference_upsample: bool = False, output_format: Optional[str] = None) -> Iterator["np.ndarray"]:
+               reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -160,7 +170,8 @@ class SmolTTS:
         are the same numbers either way.
         ``output_format``: ``pcm_8000`` / ``pcm_16000`` / ``pcm_22050`` / ``pcm_44100`` / ``pcm_48000`` (int16 chunks) or
         ``ulaw_8000`` (uint8 chunks), converted on the GPU chunk by chunk; over the utterance they concatenate to
-        ``scipy.signal.resample_poly`` of the float32 stream, quantised (formats.py).  ``None`` / ``pcm_24000``: float32."""
+        ``scipy.signal.resample_poly`` of the float32 stream, quantised (formats.py).  ``None`` / ``pcm_24000``: float32.
+        ``sampling``: a ``config.RequestSampling`` (as in ``generate_codes``); it is resolved when the generator starts."""
         import numpy as np
 
         from .formats import parse_stream_format
@@ -169,7 +180,7 @@ class SmolTTS:
             parse_stream_format(output_format)  # an unknown format is refused before any work
 
         from .engine import LMSession, MimiSession
-        from .generate import _apply_sampling, stream_pcm
+        from .generate import _apply_sampling, _apply_slot_sampling, resolve_sampling, stream_pcm
 
         prompt = np.asarray(self._get_prompt(input, voice if voice is not None else "0"))
         if prompt.ndim == 3:
@@ -179,6 +190,10 @@ class SmolTTS:
         T = int(prompt.shape[1])
         sess = LMSession(self.lm, 1, max_seq=min(self.config.max_seq_len, T + max_new + 2), max_rows=T, max_frames=max_new + 1)
         _apply_sampling(sess, settings)
+        resolved = resolve_sampling(sampling, settings, 1)
+        self.last_sampling = resolved
+        if resolved is not None:
+            _apply_slot_sampling(sess, [0], resolved)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
             yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=output_format)

@@ -198,6 +198,49 @@ class GenerationSettings:
 
 
 @dataclass
+class RequestSampling:
+    """Sampling of one request (per-request settings of the server and the façade).  ``None`` fields take the server's or
+    caller's ``GenerationSettings``: ``temperature`` <- ``default_temp``, ``fast_temperature`` <- ``default_fast_temp``,
+    ``min_p`` <- ``min_p`` (then through that settings' ``min_p_mode``, ``effective_min_p``).  ``seed`` (0 .. 2**64 - 1) keys the
+    request's draws: the same seed gives the same ids in any slot of any batch ("per-request sampling")."""
+
+    temperature: Optional[float] = None
+    fast_temperature: Optional[float] = None
+    min_p: Optional[float] = None
+    seed: Optional[int] = None
+
+    def __post_init__(self):
+        import math
+
+        for name in ("temperature", "fast_temperature"):
+            v = getattr(self, name)
+            if v is not None and not (math.isfinite(v) and v >= 0):
+                raise ValueError(f"{name} must be finite and >= 0, got {v!r}")
+        if self.min_p is not None and not (0 <= self.min_p < 1):
+            raise ValueError(f"min_p must be in [0, 1), got {self.min_p!r}")
+        if self.seed is not None and not (0 <= int(self.seed) < 2**64):
+            raise ValueError(f"seed must be in [0, 2**64), got {self.seed!r}")
+
+    @property
+    def is_sampled(self) -> bool:
+        return (self.temperature or 0.0) > 0 or (self.fast_temperature or 0.0) > 0
+
+    def resolve(self, settings: "GenerationSettings", draw_seed: bool = True) -> "RequestSampling":
+        """Every field filled in from ``settings``; ``min_p`` becomes the effective cut the device applies.  A sampled request
+        without a seed gets one from ``os.urandom`` (``draw_seed``); a greedy one keeps ``seed`` as given (None: unused)."""
+        import os
+
+        fast_default = settings.default_fast_temp if settings.default_fast_temp is not None else 0.0
+        t = float(self.temperature if self.temperature is not None else settings.default_temp)
+        ft = float(self.fast_temperature if self.fast_temperature is not None else max(fast_default, 0.0))
+        cut = GenerationSettings(min_p=self.min_p if self.min_p is not None else settings.min_p, min_p_mode=settings.min_p_mode).effective_min_p
+        out = RequestSampling(max(t, 0.0), max(ft, 0.0), cut, self.seed)
+        if out.seed is None and draw_seed and out.is_sampled:
+            out.seed = int.from_bytes(os.urandom(8), "little")
+        return out
+
+
+@dataclass
 class NumericsMode:
     """Which half of the reference the arithmetic quirks follow (SURVEY.md §7 'quirks').
 

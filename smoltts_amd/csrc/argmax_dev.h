@@ -27,6 +27,10 @@ __device__ __forceinline__ Top2 top2_merge(Top2 a, Top2 b) {
 
 // Counter-based uniform in (0, 1): a function of (seed, slot, frame, step, column) only, so sampling is
 // reproducible under graph replay and independent of launch geometry.
+//   session-wide mode: uniform01(seed + 0x9E3779B97F4A7C15 * salt[r], r, frame, step, col)  (slot r's salt = its tenant count)
+//   slot mode (SampleArgs.table): the REQUEST key uniform01(table[r].seed, 0, frames[r], step, col) -- the request's own seed and
+//   frame number only, so a request draws the same numbers in any slot, after any tenants, beside any companions.
+// Host model: smoltts_amd/sampling.py.
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
   return x;
@@ -50,6 +54,17 @@ struct ArgmaxScratch {  // LDS of one call; a workgroup that makes several calls
 __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_vec, int r, float* margin, const int* margin_mask,
                                           const SampleArgs& sa, ArgmaxScratch& S) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the row's sampling parameters (uniform in the workgroup: scalar loads, no divergence)
+  float temp = sa.temp, min_p = sa.min_p;
+  uint64_t seed = sa.seed;
+  int key_slot = r;
+  if (sa.table) {
+    const SmolttsSlotSampling en = sa.table[r];
+    temp = sa.step == 0 ? en.temp : en.fast_temp;
+    min_p = temp > 0.f ? en.min_p : 0.f;
+    seed = en.seed;
+    key_slot = 0;
+  }
   Top2 t{-INFINITY, 0x7fffffff, -INFINITY};
 #define ST_TAKE(V, J)                                                                               \
   {                                                                                                 \
@@ -88,17 +103,17 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
   if (lane == 0) S.sh[wave] = t;
   __syncthreads();
   Top2 a = top2_merge(top2_merge(S.sh[0], S.sh[1]), top2_merge(S.sh[2], S.sh[3]));
-  if (sa.temp > 0.f) {  // uniform: second pass over the row with perturbed keys
+  if (temp > 0.f) {  // uniform: second pass over the row with perturbed keys
     const int frame = sa.frames ? sa.frames[r] : sa.frame_base + r;
-    const uint64_t seed = sa.seed + (sa.salt ? 0x9E3779B97F4A7C15ULL * (uint64_t)sa.salt[r] : 0ULL);
-    const float inv_t = 1.0f / sa.temp;
-    const float cut = sa.min_p > 0.f ? logf(sa.min_p) : -INFINITY;
+    if (!sa.table && sa.salt) seed += 0x9E3779B97F4A7C15ULL * (uint64_t)sa.salt[r];
+    const float inv_t = 1.0f / temp;
+    const float cut = min_p > 0.f ? logf(min_p) : -INFINITY;
     Top2 k{-INFINITY, 0x7fffffff, -INFINITY};
 #define ST_KEY(V, J)                                                  \
   {                                                                   \
     const float z = ((V) - a.v1) * inv_t; /* <= 0 */                  \
     if (z >= cut) {                                                   \
-      const float u = uniform01(seed, r, frame, sa.step, (J));        \
+      const float u = uniform01(seed, key_slot, frame, sa.step, (J)); \
       const float key = z - logf(-logf(u));                           \
       if (key > k.v1) { k.v1 = key; k.i1 = (J); }                     \
     }                                                                 \
@@ -126,7 +141,7 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
   }
   if (a.i1 < 0 || a.i1 >= n_cols) a.i1 = 0;  // all-NaN row: stay inside the tables
   if (tid == 0) {
-    if (sa.temp <= 0.f && margin && (margin_mask == nullptr || margin_mask[r])) {
+    if (temp <= 0.f && margin && (margin_mask == nullptr || margin_mask[r])) {
       const float gap = a.v1 - a.v2;
       if (gap < margin[r]) {  // also remember where the slot's smallest gap occurred: frame * 64 + step (0 = slow id)
         margin[r] = gap;

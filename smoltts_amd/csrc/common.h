@@ -178,6 +178,9 @@ struct SampleArgs {
   const int32_t* frames;
   const int32_t* salt;  // per-row generation counter mixed into the seed (a slot's n-th tenant draws its own numbers), or null
   int32_t* margin_at;   // greedy only, optional: [rows] receives frame * 64 + step where the row's smallest top-2 gap occurred
+  // slot mode, or null: row r's own temperature (step 0: temp, else fast_temp), min_p and seed replace the fields above, and a
+  // sampled row draws with the request key (seed unsalted, slot 0: argmax_dev.h)
+  const SmolttsSlotSampling* table;
 };
 
 // Launchers implemented across the .hip files (all asynchronous on `stream`).

@@ -73,12 +73,23 @@ struct SmolttsSession {
   hipEvent_t stage_ev[8];      // recorded behind the async copies out of each area
   bool stage_ev_live[8];
   int stage_next;
-  hipGraphExec_t graph_exec;   // one decode frame (slow step + tail)
-  bool graph_ready;
-  hipGraphExec_t tail_exec;    // the tail alone (slow head + depth steps + commit) as run after a prefill
-  bool tail_ready;
-  hipGraphExec_t multi_exec;   // `multi_frames` consecutive decode frames in one graph (fewer graph launches per tick / chunk)
-  bool multi_ready;
+  // captured graphs, one set per form (GRAPH_FORMS: which picks sample; index 0 outside slot mode), each created when first needed
+  hipGraphExec_t graph_exec[4];   // one decode frame (slow step + tail)
+  bool graph_ready[4];
+  hipGraphExec_t tail_exec[4];    // the tail alone (slow head + depth steps + commit) as run after a prefill
+  bool tail_ready[4];
+  hipGraphExec_t multi_exec[4];   // `multi_frames` consecutive decode frames in one graph (fewer graph launches per tick / chunk)
+  bool multi_ready[4];
+  int form;                       // the form the next launches are built / replayed in (pick_form)
+  // slot mode (smoltts_session_set_slot_sampling): per-slot sampling entries
+  bool slot_mode;
+  SmolttsSlotSampling* slot_tab;      // [B] read by the picks; null until slot mode
+  SmolttsSlotSampling* slot_tab_area; // where it is carved (the slab's tail): [B] table, [B] upload entries, [B] upload slots
+  SmolttsSlotSampling* h_slot;        // host mirror of the table: chooses the graph form
+  char* h_slot_stage;                 // STAGE_RING pinned areas of B entries + B slots, used in turn
+  hipEvent_t slot_ev[STAGE_RING];
+  bool slot_ev_live[STAGE_RING];
+  int slot_next;
   int flight_limit;            // SMOLTTS_MAX_FRAMES_IN_FLIGHT as read at creation (0 = unbounded)
   int multi_frames;            // frames per multi-frame graph (1 = single-frame graphs only): SMOLTTS_FRAMES_PER_GRAPH, else
                                // smoltts_session_set_frames_per_graph, else min(n_frames, 4) of the largest decode call so far
@@ -169,6 +180,9 @@ void carve(SmolttsSession* s, char* base, size_t* total) {
   s->attn_ticket = cv.take<int>(ATT_SPLIT_MAX_PAIRS);
   s->margin_at = cv.take<int>(B);
   s->codes = cv.take<int>(B * (size_t)s->max_frames * H);
+  // slot mode only (smoltts_session_set_slot_sampling): the table, then the upload area (B entries, B slot numbers) -- the
+  // tail of the slab, in use once the session enters slot mode
+  s->slot_tab_area = cv.take<SmolttsSlotSampling>(2 * B + (B * sizeof(int) + sizeof(SmolttsSlotSampling) - 1) / sizeof(SmolttsSlotSampling));
   *total = cv.off;
 }
 
@@ -183,6 +197,12 @@ __global__ void init_state_kernel(int B, int n_fast, int* iota, int* fastpos, in
   pos[b] = 0; frames[b] = 0; done[b] = 1; mask[b] = 0; salt[b] = 0;
   margin[b] = INFINITY;
   for (int i = 0; i <= n_fast; ++i) { cur_col[b * (1 + n_fast) + i] = 0; new_col[b * (1 + n_fast) + i] = 0; }
+}
+
+// Slot mode: table[slots[i]] = entries[i] for the n entries of one upload (distinct slots)
+__global__ void slot_sampling_scatter_kernel(int n, const SmolttsSlotSampling* entries, const int* slots, SmolttsSlotSampling* table) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) table[slots[i]] = entries[i];
 }
 
 // Restart the listed slots: position = prompt length, counters cleared; only they commit this frame.
@@ -448,9 +468,25 @@ EmbedTables embed_tables(const SmolttsEngine* e) {
                      c.vocab_size, c.codebook_size * c.num_codebooks, c.n_fast};
 }
 
+// Whether some row samples its slow token / depth codes: the session-wide temperatures, or in slot mode the form of the launches
+// being built (pick_form).  A part that no row samples is built exactly as the session-wide greedy one.
+bool slow_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & 1) != 0 : s->temp > 0.f; }
+bool fast_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & 2) != 0 : s->fast_temp > 0.f; }
+
+// The pick arguments of step 0 (slow token) / step >= 1 (depth codes).  Slot mode, sampling form: every row reads its own entry
+// (a greedy row then takes the argmax inside argmax_row); greedy form: plain greedy arguments.
+SampleArgs pick_args(const SmolttsSession* s, int step) {
+  if (s->slot_mode) {
+    const bool sampled = step == 0 ? slow_sampled(s) : fast_sampled(s);
+    return SampleArgs{0.f, 0.f, 0, step, 0, s->frames, nullptr, s->margin_at, sampled ? s->slot_tab : nullptr};
+  }
+  if (step == 0) return SampleArgs{s->temp, s->min_p, s->seed, 0, 0, s->frames, s->salt, s->margin_at, nullptr};
+  return SampleArgs{s->fast_temp, s->fast_temp > 0.f ? s->min_p : 0.f, s->seed, step, 0, s->frames, s->salt, s->margin_at, nullptr};
+}
+
 // The commit kernel's greedy picks read the head GEMMs' tile candidates where run_tail has had them written (same conditions there)
-bool commit_cand_slow(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && s->temp <= 0.f && s->B < 256; }
-bool commit_cand_last(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && s->fast_temp <= 0.f && s->B < 256; }
+bool commit_cand_slow(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && !slow_sampled(s) && s->B < 256; }
+bool commit_cand_last(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && !fast_sampled(s) && s->B < 256; }
 
 // commit (optional) + next-frame mask + embedding of every slot's current column (see commit_embed_kernel); `picks`: the
 // frame's slow token and last depth code are still logits (run_tail) and are picked here
@@ -467,9 +503,9 @@ int launch_commit_embed(SmolttsSession* s, int do_commit, int advance_pos, hipSt
   a.attn_ticket = s->attn_ticket;
   if (picks) {
     a.slow_logits = s->logits_slow; a.slow_cols = c.vocab_size;
-    a.slow_sa = SampleArgs{s->temp, s->min_p, s->seed, 0, 0, s->frames, s->salt, s->margin_at};
+    a.slow_sa = pick_args(s, 0);
     a.last_logits = s->logits; a.last_cols = c.codebook_size;
-    a.last_sa = SampleArgs{s->fast_temp, s->fast_temp > 0.f ? s->min_p : 0.f, s->seed, c.n_fast, 0, s->frames, s->salt, s->margin_at};
+    a.last_sa = pick_args(s, c.n_fast);
     if (commit_cand_slow(s)) { a.slow_cand = s->cand_slow; a.slow_tiles = (c.vocab_size + 15) / 16; }
     if (commit_cand_last(s)) { a.last_cand = s->cand; a.last_tiles = (c.codebook_size + 15) / 16; }
   }
@@ -494,7 +530,7 @@ int run_tail(SmolttsSession* s, int advance_pos, hipStream_t st) {
   }
   const bool picks = s->commit_picks;
   if (!picks) {  // (A/B: the pick as a launch of its own)
-    const SampleArgs slow_sa{s->temp, s->min_p, s->seed, 0, 0, s->frames, s->salt, s->margin_at};
+    const SampleArgs slow_sa = pick_args(s, 0);
     ST_TRY(launch_argmax(s->logits_slow, B, c.vocab_size, c.vocab_size, s->new_col, H, s->margin, s->mask, nullptr, 0, 0, nullptr,
                          nullptr, &slow_sa, st));
   }
@@ -512,7 +548,7 @@ int run_tail(SmolttsSession* s, int advance_pos, hipStream_t st) {
   const size_t fl_stride = (size_t)B * c.fast_n_kv_head * c.n_fast * 64;
   const bool table = e->fast_qkv != nullptr && s->use_qkv_table;
   // greedy depth codes are picked by the launch that consumes them (the next step's layer-0 attention + wo: SmolttsPickArgs)
-  const bool pick_fused = s->fuse_pick && table && s->fuse_depth_attn && s->fast_temp <= 0.f && B < 256 && c.codebook_size % 16 == 0 &&
+  const bool pick_fused = s->fuse_pick && table && s->fuse_depth_attn && !fast_sampled(s) && B < 256 && c.codebook_size % 16 == 0 &&
                           c.fast_dim == c.fast_n_head * 64 && smoltts_gemm3_attn_fusable(c.fast_n_head, c.fast_n_kv_head, c.n_fast);
   SmolttsPickArgs pk;
   memset(&pk, 0, sizeof(pk));
@@ -540,7 +576,7 @@ int run_tail(SmolttsSession* s, int advance_pos, hipStream_t st) {
       if (i + 1 == c.n_fast && commit_cand_last(s)) a.cand_out_dev = s->cand;  // (no pick is pending on the buffer at the last step)
       ST_TRY(launch_gemm3_m(s, a, st));
     }
-    const SampleArgs fast_sa{s->fast_temp, s->fast_temp > 0.f ? s->min_p : 0.f, s->seed, 1 + i, 0, s->frames, s->salt, s->margin_at};
+    const SampleArgs fast_sa = pick_args(s, 1 + i);
     if (i + 1 == c.n_fast) {  // the last code has no consumer inside the frame: picked by the commit kernel
       if (!picks)
         ST_TRY(launch_argmax(s->logits, B, c.codebook_size, c.codebook_size, s->new_col + 1 + i, H, s->margin, s->mask, nullptr, 0, 0,
@@ -624,10 +660,27 @@ int stage_upload(SmolttsSession* s, const int32_t* slots_host, const int32_t* la
   return SMOLTTS_OK;
 }
 
+void drop_multi_graphs(SmolttsSession* s) {
+  for (int f = 0; f < 4; ++f)
+    if (s->multi_ready[f]) { (void)hipGraphExecDestroy(s->multi_exec[f]); s->multi_ready[f] = false; }
+}
+
 void drop_graphs(SmolttsSession* s) {
-  if (s->graph_ready) { (void)hipGraphExecDestroy(s->graph_exec); s->graph_ready = false; }
-  if (s->tail_ready) { (void)hipGraphExecDestroy(s->tail_exec); s->tail_ready = false; }
-  if (s->multi_ready) { (void)hipGraphExecDestroy(s->multi_exec); s->multi_ready = false; }
+  for (int f = 0; f < 4; ++f) {
+    if (s->graph_ready[f]) { (void)hipGraphExecDestroy(s->graph_exec[f]); s->graph_ready[f] = false; }
+    if (s->tail_ready[f]) { (void)hipGraphExecDestroy(s->tail_exec[f]); s->tail_ready[f] = false; }
+  }
+  drop_multi_graphs(s);
+}
+
+// The form of the frame launches: bit 0 = some slot samples its slow token, bit 1 = some slot samples its depth codes.  Outside
+// slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
+// point that launches or captures picks, after the last change of the table.
+void pick_form(SmolttsSession* s) {
+  int f = 0;
+  if (s->slot_mode)
+    for (int b = 0; b < s->B; ++b) f |= (s->h_slot[b].temp > 0.f ? 1 : 0) | (s->h_slot[b].fast_temp > 0.f ? 2 : 0);
+  s->form = f;
 }
 
 // Record `body` (a fixed launch sequence on the given stream) into an executable graph.
@@ -667,12 +720,12 @@ int run_decode_frame(SmolttsSession* s, hipStream_t st);
 int ensure_multi_graph(SmolttsSession* s, int n_frames, hipStream_t st) {
   if (s->flight_limit > 0 && s->multi_frames > s->flight_limit) s->multi_frames = s->flight_limit;
   const int mf = s->multi_frames;
-  if (mf > 1 && n_frames >= mf && !s->multi_ready) {
-    ST_TRY(capture_graph(st, &s->multi_exec, [&](hipStream_t cap) {
+  if (mf > 1 && n_frames >= mf && !s->multi_ready[s->form]) {
+    ST_TRY(capture_graph(st, &s->multi_exec[s->form], [&](hipStream_t cap) {
       for (int i = 0; i < mf; ++i) ST_TRY(run_decode_frame(s, cap));
       return (int)SMOLTTS_OK;
     }));
-    s->multi_ready = true;
+    s->multi_ready[s->form] = true;
   }
   return SMOLTTS_OK;
 }
@@ -896,6 +949,10 @@ void smoltts_session_destroy(SmolttsSession* s) {
   if (s->h_stage) (void)hipHostFree(s->h_stage);
   for (int k = 0; k < 2; ++k)
     if (s->flight_ev[k]) (void)hipEventDestroy(s->flight_ev[k]);
+  for (int k = 0; k < STAGE_RING; ++k)
+    if (s->slot_ev[k]) (void)hipEventDestroy(s->slot_ev[k]);
+  if (s->h_slot_stage) (void)hipHostFree(s->h_slot_stage);
+  delete[] s->h_slot;
   delete s;
 }
 
@@ -915,6 +972,7 @@ int smoltts_lm_prefill(SmolttsSession* s, const int32_t* grid_dev, const int32_t
   const SmolttsLMConfig& c = e->cfg;
   if (s->stop_on_eos != stop_on_eos) drop_graphs(s);  // the flag is baked into the captured commit nodes
   s->stop_on_eos = stop_on_eos;
+  pick_form(s);
   ST_TRY(stage_upload(s, slots_host, last_row_host, n_slots, st));
   hipLaunchKernelGGL(slot_reset_kernel, dim3((s->B + 63) / 64), dim3(64), 0, st, s->B, n_slots, s->stage_slots, s->stage_last,
                      row_pos_dev, s->pos, s->frames, s->done, s->mask, s->margin, s->salt);
@@ -930,11 +988,11 @@ int smoltts_lm_prefill(SmolttsSession* s, const int32_t* grid_dev, const int32_t
   // frame 0: the tail is the same ~180 launches after every prefill -> replayed from a graph (host launch time is what
   // a single short prompt waits for)
   if (graphs_enabled()) {
-    if (!s->tail_ready) {
-      ST_TRY(capture_graph(st, &s->tail_exec, [&](hipStream_t cap) { return run_tail(s, /*advance_pos=*/0, cap); }));
-      s->tail_ready = true;
+    if (!s->tail_ready[s->form]) {
+      ST_TRY(capture_graph(st, &s->tail_exec[s->form], [&](hipStream_t cap) { return run_tail(s, /*advance_pos=*/0, cap); }));
+      s->tail_ready[s->form] = true;
     }
-    ST_CHECK_HIP(hipGraphLaunch(s->tail_exec, st));
+    ST_CHECK_HIP(hipGraphLaunch(s->tail_exec[s->form], st));
   } else {
     ST_TRY(run_tail(s, /*advance_pos=*/0, st));
   }
@@ -1045,13 +1103,14 @@ int smoltts_lm_decode(SmolttsSession* s, int32_t n_frames, void* stream) {
   ST_REQUIRE(s->prefilled, SMOLTTS_E_STATE, "lm_decode: call smoltts_lm_prefill first");
   ST_REQUIRE(n_frames >= 0, SMOLTTS_E_INVALID, "lm_decode: n_frames < 0");
   hipStream_t st = (hipStream_t)stream;
+  pick_form(s);
   if (!graphs_enabled()) {
     for (int f = 0; f < n_frames; ++f) ST_TRY(run_decode_frame(s, st));
     return SMOLTTS_OK;
   }
-  if (!s->graph_ready) {
-    ST_TRY(capture_graph(st, &s->graph_exec, [&](hipStream_t cap) { return run_decode_frame(s, cap); }));
-    s->graph_ready = true;
+  if (!s->graph_ready[s->form]) {
+    ST_TRY(capture_graph(st, &s->graph_exec[s->form], [&](hipStream_t cap) { return run_decode_frame(s, cap); }));
+    s->graph_ready[s->form] = true;
   }
   // Bounded run-ahead: a frame is ~230 AQL packets, and nothing stops a caller from queueing hundreds of frames.  The
   // hardware queue holds 16K packets; the runtime copes with a full ring, but a profiler that rewrites every dispatch into
@@ -1068,11 +1127,11 @@ int smoltts_lm_decode(SmolttsSession* s, int32_t n_frames, void* stream) {
     const int want = n_frames < 4 ? n_frames : 4;
     if (want > s->multi_frames) {
       s->multi_frames = want;
-      if (s->multi_ready) { (void)hipGraphExecDestroy(s->multi_exec); s->multi_ready = false; }
+      drop_multi_graphs(s);
     }
   }
   ST_TRY(ensure_multi_graph(s, n_frames, st));
-  const int mf = s->multi_ready ? s->multi_frames : 1;
+  const int mf = s->multi_ready[s->form] ? s->multi_frames : 1;
   for (int f = 0; f < n_frames;) {
     if (s->flight_group > 0 && s->flight_count >= s->flight_group) {
       const int k = s->flight_cur;
@@ -1083,11 +1142,11 @@ int smoltts_lm_decode(SmolttsSession* s, int32_t n_frames, void* stream) {
       s->flight_count = 0;
     }
     if (mf > 1 && n_frames - f >= mf) {
-      ST_CHECK_HIP(hipGraphLaunch(s->multi_exec, st));
+      ST_CHECK_HIP(hipGraphLaunch(s->multi_exec[s->form], st));
       s->flight_count += mf;
       f += mf;
     } else {
-      ST_CHECK_HIP(hipGraphLaunch(s->graph_exec, st));
+      ST_CHECK_HIP(hipGraphLaunch(s->graph_exec[s->form], st));
       s->flight_count++;
       f++;
     }
@@ -1103,6 +1162,74 @@ int smoltts_session_set_sampling(SmolttsSession* s, float temp, float fast_temp,
   ST_REQUIRE(min_p < 1.0f, SMOLTTS_E_INVALID, "session_set_sampling: min_p must be < 1");
   s->temp = temp; s->fast_temp = fast_temp; s->min_p = min_p; s->seed = seed;
   drop_graphs(s);
+  return SMOLTTS_OK;
+}
+
+// Slot mode: per-slot entries (include/smoltts_hip.h).  The host copies the entries into the next area of a pinned ring and queues
+// one copy + one scatter launch on `stream`; it waits only for the upload that last used that area (an event), never for the stream.
+int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* temp_host,
+                                      const float* fast_temp_host, const float* min_p_host, const uint64_t* seed_host, void* stream) {
+  ST_REQUIRE(s && (n == 0 || (slots_host && temp_host && fast_temp_host && min_p_host && seed_host)), SMOLTTS_E_INVALID,
+             "session_set_slot_sampling: null argument");
+  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_sampling: %d entries, session holds %d slots", n, s->B);
+  for (int i = 0; i < n; ++i) {
+    ST_REQUIRE(slots_host[i] >= 0 && slots_host[i] < s->B, SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d out of range", slots_host[i]);
+    for (int j = 0; j < i; ++j)
+      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d listed twice", slots_host[i]);
+    ST_REQUIRE(temp_host[i] == temp_host[i] && fast_temp_host[i] == fast_temp_host[i] && min_p_host[i] >= 0.f && min_p_host[i] < 1.f,
+               SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d: temperatures must be numbers, 0 <= min_p < 1", slots_host[i]);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t B = s->B, area = B * sizeof(SmolttsSlotSampling) + B * sizeof(int);
+  if (!s->slot_mode) {  // enter slot mode: host mirror, pinned ring, events; every slot greedy with seed 0
+    s->h_slot = new (std::nothrow) SmolttsSlotSampling[B];
+    ST_REQUIRE(s->h_slot, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
+    memset(s->h_slot, 0, B * sizeof(SmolttsSlotSampling));
+    if (hipHostMalloc((void**)&s->h_slot_stage, area * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
+      s->h_slot_stage = nullptr;
+      delete[] s->h_slot;
+      s->h_slot = nullptr;
+      set_error("session_set_slot_sampling: hipHostMalloc failed");
+      return SMOLTTS_E_HIP;
+    }
+    for (int k = 0; k < STAGE_RING; ++k) {
+      if (hipEventCreateWithFlags(&s->slot_ev[k], hipEventDisableTiming) != hipSuccess) {
+        for (int j = 0; j <= k; ++j) {
+          if (j < k) (void)hipEventDestroy(s->slot_ev[j]);
+          s->slot_ev[j] = nullptr;
+        }
+        (void)hipHostFree(s->h_slot_stage);
+        s->h_slot_stage = nullptr;
+        delete[] s->h_slot;
+        s->h_slot = nullptr;
+        set_error("session_set_slot_sampling: hipEventCreate failed");
+        return SMOLTTS_E_HIP;  // (slot mode is not entered)
+      }
+    }
+    s->slot_tab = s->slot_tab_area;
+    ST_CHECK_HIP(hipMemsetAsync(s->slot_tab, 0, B * sizeof(SmolttsSlotSampling), st));
+    s->slot_mode = true;
+    drop_graphs(s);  // (the session-wide set: slot mode builds its own)
+  }
+  if (n == 0) return SMOLTTS_OK;
+  const int k = s->slot_next;
+  s->slot_next = (k + 1) % STAGE_RING;
+  if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
+  SmolttsSlotSampling* h = reinterpret_cast<SmolttsSlotSampling*>(s->h_slot_stage + (size_t)k * area);
+  int* hi = reinterpret_cast<int*>(h + B);
+  for (int i = 0; i < n; ++i) {
+    SmolttsSlotSampling en;
+    en.temp = temp_host[i]; en.fast_temp = fast_temp_host[i]; en.min_p = min_p_host[i]; en.reserved = 0; en.seed = seed_host[i];
+    h[i] = en;
+    hi[i] = slots_host[i];
+    s->h_slot[slots_host[i]] = en;
+  }
+  SmolttsSlotSampling* up = s->slot_tab_area + B;  // device upload area: the same layout as a ring area
+  ST_CHECK_HIP(hipMemcpyAsync(up, h, area, hipMemcpyHostToDevice, st));
+  ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
+  s->slot_ev_live[k] = true;
+  hipLaunchKernelGGL(slot_sampling_scatter_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->slot_tab);
+  ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }
 
@@ -1150,14 +1277,15 @@ int smoltts_session_set_frames_per_graph(SmolttsSession* s, int32_t n, void* str
   ST_REQUIRE(s, SMOLTTS_E_INVALID, "session_set_frames_per_graph: null session");
   ST_REQUIRE(n >= 0 && n <= 16, SMOLTTS_E_INVALID, "session_set_frames_per_graph: %d frames per graph (0..16)", n);
   if (s->multi_env) n = s->multi_frames;  // SMOLTTS_FRAMES_PER_GRAPH wins (a profiler run pins one frame per graph)
-  if (n != s->multi_frames && s->multi_ready) { (void)hipGraphExecDestroy(s->multi_exec); s->multi_ready = false; }
+  if (n != s->multi_frames) drop_multi_graphs(s);
   s->multi_frames = n;
   s->multi_fixed = n > 0;
   if (n > 0 && s->prefilled && graphs_enabled()) {
     hipStream_t st = (hipStream_t)stream;
-    if (!s->graph_ready) {
-      ST_TRY(capture_graph(st, &s->graph_exec, [&](hipStream_t cap) { return run_decode_frame(s, cap); }));
-      s->graph_ready = true;
+    pick_form(s);
+    if (!s->graph_ready[s->form]) {
+      ST_TRY(capture_graph(st, &s->graph_exec[s->form], [&](hipStream_t cap) { return run_decode_frame(s, cap); }));
+      s->graph_ready[s->form] = true;
     }
     ST_TRY(ensure_multi_graph(s, n, st));
   }

@@ -111,6 +111,7 @@ _EXPORTS = [
     "smoltts_mimi_encode_workspace_bytes", "smoltts_mimi_encode", "smoltts_mimi_session_set_option",
     "smoltts_resample_design", "smoltts_resampler_bytes", "smoltts_resampler_create", "smoltts_resampler_destroy",
     "smoltts_resampler_out_bytes", "smoltts_resampler_reset_slots", "smoltts_resample_chunk",
+    "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows",
 ]
 
 
@@ -167,6 +168,8 @@ def load_library(path: Optional[Path] = None):
     lib.smoltts_session_set_sampling.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_uint64]
     lib.smoltts_k_sample.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_void_p]
+    lib.smoltts_session_set_slot_sampling.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+    lib.smoltts_k_sample_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.smoltts_session_measure_duplicate.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.smoltts_session_margin_at.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.smoltts_session_drop_graph.argtypes = [C.c_void_p]
@@ -537,6 +540,20 @@ class LMSession:
         """temp / fast_temp <= 0: greedy (default). Takes effect from the next frame."""
         check(self.lib.smoltts_session_set_sampling(self.handle, float(temp), float(fast_temp), float(min_p), int(seed) & (2**64 - 1)),
               "smoltts_session_set_sampling")
+
+    def set_slot_sampling(self, slots: Sequence[int], temp: Sequence[float], fast_temp: Sequence[float], min_p: Sequence[float],
+                          seed: Sequence[int]) -> None:
+        """Per-slot sampling (slot mode, include/smoltts_hip.h): slot ``slots[i]`` samples its slow token at ``temp[i]`` and its
+        depth codes at ``fast_temp[i]`` (<= 0: greedy) with the effective cut ``min_p[i]`` and the request key of ``seed[i]``.  The
+        first call puts the session in slot mode for good (unlisted slots: greedy).  Queued on the current stream: the picks
+        behind it on that stream use the new entries; the host does not wait for the stream."""
+        n = len(slots)
+        if not (len(temp) == len(fast_temp) == len(min_p) == len(seed) == n):
+            raise ValueError("slot sampling: one value per slot in every list")
+        check(self.lib.smoltts_session_set_slot_sampling(
+            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_float * max(n, 1))(*[float(t) for t in temp]),
+            (C.c_float * max(n, 1))(*[float(t) for t in fast_temp]), (C.c_float * max(n, 1))(*[float(p) for p in min_p]),
+            (C.c_uint64 * max(n, 1))(*[int(x) & (2**64 - 1) for x in seed]), current_stream_ptr()), "smoltts_session_set_slot_sampling")
 
     def measure_duplicate(self, code: int = -1, n_filter: int = 0) -> None:
         """Measurement aid (this session only): issue every launch of one kernel class twice; -1 switches it off."""

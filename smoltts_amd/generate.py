@@ -22,7 +22,7 @@ from typing import Iterator, Any, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .config import GenerationSettings
+from .config import GenerationSettings, RequestSampling
 from .engine import LMEngine, LMSession, Resampler
 from .formats import ENC_OFF, parse_stream_format
 
@@ -44,6 +44,22 @@ def _apply_sampling(session: LMSession, settings: GenerationSettings) -> None:
     session.set_sampling(temp=settings.default_temp, fast_temp=max(fast, 0.0), min_p=settings.effective_min_p, seed=seed)
 
 
+def _apply_slot_sampling(session: LMSession, slots: Sequence[int], sampling: Sequence[RequestSampling]) -> None:
+    """Slot ``slots[i]`` samples with the resolved ``sampling[i]`` (slot mode; a greedy entry's seed is 0)."""
+    session.set_slot_sampling(list(slots), [r.temperature for r in sampling], [r.fast_temperature for r in sampling],
+                              [r.min_p for r in sampling], [r.seed or 0 for r in sampling])
+
+
+def resolve_sampling(sampling, settings: GenerationSettings, n: int) -> Optional[List[RequestSampling]]:
+    """``sampling=`` of the façade -> one resolved ``RequestSampling`` per utterance (None stays None: session-wide mode)."""
+    if sampling is None:
+        return None
+    items = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * n
+    if len(items) != n:
+        raise ValueError(f"sampling: {len(items)} entries for {n} inputs")
+    return [(r if r is not None else RequestSampling()).resolve(settings) for r in items]
+
+
 def _frame_to_token(engine: LMEngine, col: np.ndarray) -> VQToken:
     """lm/generate.py:143-159: audio codes exist only when the slow id is a semantic token."""
     tc, cfg = engine.token_config, engine.cfg
@@ -61,7 +77,10 @@ class BatchGenerator:
     utterance has stopped) per slot.  ``frames_per_sync`` > 1 lets the GPU run ahead."""
 
     def __init__(self, engine: LMEngine, prompts: Sequence[np.ndarray], generation_settings: GenerationSettings,
-                 audio_only: bool = True, frames_per_sync: int = 1, session: Optional[LMSession] = None):
+                 audio_only: bool = True, frames_per_sync: int = 1, session: Optional[LMSession] = None,
+                 sampling: Optional[Sequence[RequestSampling]] = None):
+        """``sampling``: one resolved ``RequestSampling`` per prompt (``resolve_sampling``): the session runs in slot mode with
+        them; None: every utterance samples with ``generation_settings`` (session-wide)."""
         self.engine = engine
         self.settings = generation_settings
         self.audio_only = audio_only
@@ -72,6 +91,10 @@ class BatchGenerator:
         self.session = session or LMSession(engine, self.B, max_seq=min(engine.cfg.max_seq_len, max_T + self.max_frames + 1),
                                             max_rows=sum(int(p.shape[1]) for p in prompts), max_frames=self.max_frames)
         _apply_sampling(self.session, generation_settings)
+        if sampling is not None:
+            if len(sampling) != self.B:
+                raise ValueError(f"sampling: {len(sampling)} entries for {self.B} prompts")
+            _apply_slot_sampling(self.session, range(self.B), sampling)
         self._prompts = list(prompts)
         self._started = False
         self._emitted = np.zeros(self.B, dtype=np.int64)

@@ -173,6 +173,32 @@ def argmax(logits: torch.Tensor, margin: Optional[torch.Tensor] = None) -> torch
     return ids
 
 
+def slot_sampling_table(temp, fast_temp, min_p, seed, device="cuda") -> torch.Tensor:
+    """Rows of ``SmolttsSlotSampling`` (temp, fast_temp, min_p, 0, seed: 24 bytes each) as a uint8 device tensor."""
+    import numpy as np
+
+    dt = np.dtype([("temp", "<f4"), ("fast_temp", "<f4"), ("min_p", "<f4"), ("reserved", "<u4"), ("seed", "<u8")])
+    n = len(temp)
+    a = np.zeros(n, dt)
+    a["temp"], a["fast_temp"], a["min_p"] = temp, fast_temp, min_p
+    a["seed"] = np.array([int(x) & (2**64 - 1) for x in seed], dtype=np.uint64)
+    return torch.from_numpy(a.view(np.uint8).copy()).to(device)
+
+
+def sample_rows(logits: torch.Tensor, table: torch.Tensor, frames: Optional[torch.Tensor] = None, step: int = 0) -> torch.Tensor:
+    """``smoltts_k_sample_rows``: row r picked with its own entry ``table`` row r (``slot_sampling_table``) and the request key at
+    frame ``frames[r]`` (None: r) and ``step`` (0: the entry's temp; > 0: fast_temp)."""
+    lib = E.load_library()
+    if table.dtype != torch.uint8 or table.numel() < 24 * logits.shape[0]:
+        raise ValueError("table: 24 bytes per row (slot_sampling_table)")
+    if frames is not None and (frames.dtype != torch.int32 or frames.numel() < logits.shape[0]):
+        raise ValueError("frames: int32, one per row")
+    ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    E.check(lib.smoltts_k_sample_rows(E.dptr(logits), logits.shape[0], logits.shape[1], logits.stride(0), E.dptr(table), E.dptr(frames),
+                                      int(step), E.dptr(ids), E.current_stream_ptr()), "smoltts_k_sample_rows")
+    return ids
+
+
 def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     lib = E.load_library()
     out = torch.empty_like(x)

@@ -38,22 +38,46 @@ class TTSCore:
             return int(voice)
         return 0
 
-    def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000"):
+    def _model_sampling(self, sampling):
+        """The model-only path: the request's sampling resolved against the façade's own defaults (its seed drawn here), or None
+        when the request names none (the façade's unchanged behaviour)."""
+        if sampling is None:
+            return None
+        from ..config import GenerationSettings
+
+        base = self.model._settings(None) if hasattr(self.model, "_settings") else GenerationSettings()
+        return sampling.resolve(base)
+
+    def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000", sampling=None):
+        """-> (bytes, media type, the seed the request sampled with or None)."""
+        used = None
         try:
             if self.scheduler is not None:
-                pcm = self.scheduler.synthesize(input_text, str(voice))
+                req = self.scheduler.submit(input_text, str(voice), stream=False, **({"sampling": sampling} if sampling is not None else {}))
+                used = getattr(req, "sampling", None)
+                pcm = np.concatenate(list(self.scheduler.iter_chunks(req)) or [np.zeros(0, np.float32)])
             else:
-                pcm = np.asarray(self.model(input_text, str(voice))).flatten()
+                used = self._model_sampling(sampling)
+                kw = {"sampling": used} if used is not None else {}
+                pcm = np.asarray(self.model(input_text, str(voice), **kw)).flatten()
         except ValueError as e:  # a request the engine refuses (e.g. a text too long for max_seq_len): the client's fault, not a 500
             raise HTTPException(status_code=400, detail=str(e))
-        return self.format_audio_chunk(pcm, response_format)
+        return (*self.format_audio_chunk(pcm, response_format), seed_used(used))
 
-    def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000"):
-        """Chunks as bytes: float32 at 24 kHz for ``pcm_24000``; otherwise the int16 / mu-law samples the model or scheduler
-        converted on the GPU (the format is passed on only when it is not ``pcm_24000``)."""
+    def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None):
+        """-> (chunks as bytes, the seed the request samples with or None).  Chunks: float32 at 24 kHz for ``pcm_24000``;
+        otherwise the int16 / mu-law samples the model or scheduler converted on the GPU (the format is passed on only when it is
+        not ``pcm_24000``).  The request is submitted here, before the first chunk is asked for."""
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
-        chunks = (self.scheduler.iter_chunks(self.scheduler.submit(input_text, str(voice), stream=True, **kw))
-                  if self.scheduler is not None else self.model.stream(input_text, str(voice), **kw))
+        if self.scheduler is not None:
+            req = self.scheduler.submit(input_text, str(voice), stream=True, **kw, **({"sampling": sampling} if sampling is not None else {}))
+            chunks, used = self.scheduler.iter_chunks(req), getattr(req, "sampling", None)
+        else:
+            used = self._model_sampling(sampling)
+            chunks = self.model.stream(input_text, str(voice), **kw, **({"sampling": used} if used is not None else {}))
+        return self._stream_bytes(chunks, kw), seed_used(used)
+
+    def _stream_bytes(self, chunks, kw):
         try:
             for chunk in chunks:
                 if chunk is not None:
@@ -86,14 +110,42 @@ class TTSCore:
         return pcm_to_wav_bytes(pcm_data, sample_rate), "audio/wav"
 
 
-class SpeechRequest(BaseModel):
+def seed_used(sampling) -> Optional[int]:
+    """The seed of a request that samples (its ``X-Seed``), or None: greedy, or no sampling known."""
+    if sampling is None or sampling.seed is None:
+        return None
+    known_greedy = sampling.temperature is not None and sampling.fast_temperature is not None and not sampling.is_sampled
+    return None if known_greedy else int(sampling.seed)
+
+
+def _seed_headers(seed: Optional[int]) -> dict:
+    return {} if seed is None else {"X-Seed": str(seed)}
+
+
+class SamplingFields(BaseModel):
+    """Per-request sampling (extension; the ElevenLabs body's ``seed``): omitted fields take the server's generation settings.
+    A sampled response carries ``X-Seed``: the seed it used, drawn by the server when the body names none."""
+    seed: Optional[int] = Field(default=None, ge=0, le=2**64 - 1)
+    temperature: Optional[float] = Field(default=None, ge=0, allow_inf_nan=False)
+    fast_temperature: Optional[float] = Field(default=None, ge=0, allow_inf_nan=False)
+    min_p: Optional[float] = Field(default=None, ge=0, lt=1)
+
+    def request_sampling(self):
+        if self.seed is None and self.temperature is None and self.fast_temperature is None and self.min_p is None:
+            return None
+        from ..config import RequestSampling
+
+        return RequestSampling(self.temperature, self.fast_temperature, self.min_p, self.seed)
+
+
+class SpeechRequest(SamplingFields):
     model: str = Field(default="tts-1-hd")
     input: str
     voice: Union[str, int] = Field(default="alloy")
     response_format: Literal["wav"] = Field(default="wav")
 
 
-class CreateSpeechRequest(BaseModel):
+class CreateSpeechRequest(SamplingFields):
     text: str
     model_id: Optional[str] = Field(default=None)
 
@@ -105,8 +157,8 @@ eleven_router = APIRouter(prefix="/v1", tags=["ElevenLabs"])
 @openai_router.post("/audio/speech")
 def openai_speech(item: SpeechRequest, http_request: Request):
     core = http_request.app.state.tts_core
-    audio, media_type = core.generate_audio(item.input, item.voice, item.response_format + "_24000")
-    return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"'})
+    audio, media_type, seed = core.generate_audio(item.input, item.voice, item.response_format + "_24000", sampling=item.request_sampling())
+    return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}")
@@ -114,10 +166,10 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
                                   output_format: Optional[str] = Query(None, description="pcm_<rate> | wav_<rate>")):
     core = http_request.app.state.tts_core
     fmt = output_format or "wav_24000"
-    content, media_type = core.generate_audio(item.text, voice_id, fmt)
+    content, media_type, seed = core.generate_audio(item.text, voice_id, fmt, sampling=item.request_sampling())
     return Response(content=content, media_type=media_type, headers={
         "Content-Disposition": f'attachment; filename="elevenlabs_speech.{fmt.split("_")[0]}"',
-        "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000"})
+        "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}/stream")
@@ -126,8 +178,9 @@ def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
     """pcm_24000: raw float32 (the reference's stream); pcm_<rate>: int16 little-endian; ulaw_8000: G.711 mu-law bytes."""
     core = http_request.app.state.tts_core
     kind, rate = output_format.split("_")
-    return StreamingResponse(core.stream_audio(item.text, voice=voice_id, output_format=output_format), media_type="audio/wav", headers={
-        "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate})
+    chunks, seed = core.stream_audio(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling())
+    return StreamingResponse(chunks, media_type="audio/wav", headers={
+        "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed)})
 
 
 @eleven_router.get("/stats")
@@ -182,7 +235,8 @@ def main():
 
     if args.gpus > 1:
         # this process stays off the GPUs: it parses HTTP and relays audio; every worker owns one GPU and one scheduler
-        sched = GpuPool(functools.partial(scheduler_from_settings, settings), devices=list(range(args.gpus)))
+        sched = GpuPool(functools.partial(scheduler_from_settings, settings), devices=list(range(args.gpus)),
+                        generation_settings=ServerSettings(**settings).generation.to_settings())
         model = None
     else:
         sched = scheduler_from_settings(settings)

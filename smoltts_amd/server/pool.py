@@ -30,6 +30,7 @@ class _PoolRequest:
     out: "queue.Queue" = field(default_factory=queue.Queue)  # np.ndarray chunks, then None (or an Exception)
     cancelled: bool = False
     closed: bool = False
+    sampling: object = None  # config.RequestSampling as sent to the worker (seed resolved here), or None
 
 
 def visible_device(index: int, inherited: Optional[str]) -> str:
@@ -87,7 +88,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
                 break
             if msg[0] == "submit":
                 _, rid, text, voice, stream, max_new_tokens = msg[:6]
-                extra = msg[6] if len(msg) > 6 else {}  # (output_format, only when the client set one)
+                extra = msg[6] if len(msg) > 6 else {}  # (output_format / sampling, only when set)
                 req = sched.submit(text, voice, stream=stream, max_new_tokens=max_new_tokens, **extra)
                 with lock:
                     live[rid] = req
@@ -106,17 +107,21 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
 
 class GpuPool:
     def __init__(self, factory: Callable[[], object], devices: Sequence[int], start_method: str = "spawn", ready_timeout: float = 600.0,
-                 respawn: bool = True):
+                 respawn: bool = True, generation_settings=None):
         """``factory``: picklable, called once in every worker to build its scheduler.  ``devices``: GPU indices, one
         worker each (an index may repeat: two replicas on one GPU).  ``start_method``: "spawn" or "forkserver" — never
         "fork": a forked copy of a process that has used the GPU is not usable.  ``respawn``: a worker that dies is replaced
-        (same GPU); its requests in flight are failed, later ones are served again by all workers."""
+        (same GPU); its requests in flight are failed, later ones are served again by all workers.
+        ``generation_settings``: what the workers' schedulers are configured with; then every request's sampling is resolved
+        here (``RequestSampling.resolve``) and sent along, so that a request samples the same on any worker.  Without it only a
+        request that names a ``sampling`` carries one (its seed drawn here when missing)."""
         if start_method not in ("spawn", "forkserver"):
             raise ValueError("start_method must be 'spawn' or 'forkserver'")
         if not devices:
             raise ValueError("no devices")
         self._ctx = mp.get_context(start_method)
         self._factory, self._ready_timeout, self._respawn = factory, ready_timeout, respawn
+        self._settings = generation_settings
         inherited = os.environ.get("HIP_VISIBLE_DEVICES")
         self._devices = [visible_device(d, inherited) for d in devices]
         started = [self._start_worker(i) for i in range(len(devices))]
@@ -160,11 +165,21 @@ class GpuPool:
 
     # ------------------------------------------------------------------ client side (the BatchScheduler interface)
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None) -> _PoolRequest:
+               output_format: Optional[str] = None, sampling=None) -> _PoolRequest:
         if output_format is not None:  # refused here, before a worker sees it
             from ..formats import parse_stream_format
 
             parse_stream_format(output_format)
+        if sampling is not None or self._settings is not None:  # the seed is drawn here: the same on whichever worker serves it
+            import dataclasses
+
+            from ..config import RequestSampling
+
+            sampling = sampling if sampling is not None else RequestSampling()
+            if self._settings is not None:
+                sampling = sampling.resolve(self._settings)
+            elif sampling.seed is None:
+                sampling = dataclasses.replace(sampling, seed=int.from_bytes(os.urandom(8), "little"))
         with self._lock:
             if self._closing:
                 raise RuntimeError("pool closed")
@@ -172,11 +187,12 @@ class GpuPool:
             if not alive:
                 raise RuntimeError("no GPU worker is alive")
             w = min(alive, key=lambda i: self._load[i])
-            req = _PoolRequest(next(self._ids), w)
+            req = _PoolRequest(next(self._ids), w, sampling=sampling)
             self._reqs[req.rid] = req
             self._load[w] += 1
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
-        self._req_qs[w].put(msg + ({"output_format": output_format},) if output_format is not None else msg)
+        extra = {k: v for k, v in (("output_format", output_format), ("sampling", sampling)) if v is not None}
+        self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
     def synthesize(self, text: str, voice: str = "heart", max_new_tokens: Optional[int] = None) -> np.ndarray:

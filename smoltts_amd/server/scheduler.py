@@ -47,6 +47,7 @@ class _Request:
     cancelled: bool = False  # set by the client side (cancel / an abandoned chunk iterator), honoured by the worker at its next look
     closed: bool = False  # the end marker (None or an exception) has been queued
     output_format: Optional[str] = None  # streaming: pcm_<rate> / ulaw_8000 converted on the GPU (None: float32 at 24 kHz)
+    sampling: object = None  # config.RequestSampling, resolved at submit (seed drawn there for a sampled request without one)
 
 
 @dataclass
@@ -87,6 +88,14 @@ class BatchScheduler:
         self.session = LMSession(tts.lm, max_batch, max_seq=tts.config.max_seq_len, max_rows=max(max_prompt_rows, max_batch),
                                  max_frames=self.max_frames)
         _apply_sampling(self.session, self.settings)
+        # per-request sampling: the session runs in slot mode, every slot with the configured settings until a request names its
+        # own; a request's entry is written on the frame stream before its frame 0 can be picked, a freed slot gets the default back
+        from ..config import RequestSampling
+
+        self._default_sampling = RequestSampling().resolve(self.settings, draw_seed=False)
+        self._slot_sampling: Dict[int, object] = {}  # the entry each slot has on the device
+        self._write_sampling({b: self._default_sampling for b in range(max_batch)})
+        torch.cuda.current_stream().synchronize()  # (the worker's frame stream is another one)
         self.session.set_frames_per_graph(min(max(frames_per_tick, 1), 8))  # a tick is one graph launch where it fits
         self._torch = torch
         self._pending: "queue.Queue[_Request]" = queue.Queue()
@@ -119,9 +128,14 @@ class BatchScheduler:
 
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None) -> _Request:
+               output_format: Optional[str] = None, sampling=None) -> _Request:
         """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
-        in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32."""
+        in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
+        ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
+        a seed gets one here.  The resolved value is ``request.sampling``; its seed replays the request."""
+        from ..config import RequestSampling
+
+        resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         if output_format is not None:
             from ..formats import ENC_OFF, parse_stream_format
 
@@ -134,7 +148,7 @@ class BatchScheduler:
         if self._draining:
             raise RuntimeError("scheduler is not running: shutting down")
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
-                       output_format=output_format)
+                       output_format=output_format, sampling=resolved)
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
@@ -273,6 +287,7 @@ class BatchScheduler:
                     self._retiring.append(r)
                     del self._active[slot]
                     self._free.append(slot)
+        freed = [b for b in self._free if self._slot_sampling[b] != self._default_sampling]  # handed back: the default again
         while self._free and (self._held is not None or not self._pending.empty()):
             req, self._held = (self._held, None) if self._held is not None else (self._pending.get_nowait(), None)
             if req.cancelled:
@@ -301,6 +316,9 @@ class BatchScheduler:
             rows += need
             req.slot = self._free.pop(0)
             new.append(req)
+        entries = {b: self._default_sampling for b in freed}
+        entries.update({r.slot: r.sampling for r in new})
+        self._write_sampling(entries)  # on the frame stream, ahead of the park / prefill of the new tenants
         if not new:
             return
         if side:
@@ -319,6 +337,16 @@ class BatchScheduler:
                 self._end(r, e)
             raise
         self._enter(new)
+
+    def _write_sampling(self, entries: Dict[int, object]) -> None:
+        """Slot b samples with ``entries[b]`` from the next pick on the current stream on (only changed entries are uploaded)."""
+        from ..generate import _apply_slot_sampling
+
+        todo = sorted(b for b, e in entries.items() if self._slot_sampling.get(b) != e)
+        if todo:
+            _apply_slot_sampling(self.session, todo, [entries[b] for b in todo])
+        for b in todo:
+            self._slot_sampling[b] = entries[b]
 
     def _prefill(self, new: List[_Request]) -> None:
         if self.prefill_chunk:

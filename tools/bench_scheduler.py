@@ -1,5 +1,6 @@
 """Sustained serving throughput of the continuous-batching scheduler (SURVEY.md §8d EOS variant): 128 requests with
-frame budgets U{64..384} (seed 1) through 32 slots, smoltts_byte_150m synthetic weights, greedy, blocking responses.
+frame budgets U{64..384} (seed 1) through 32 slots, smoltts_byte_150m synthetic weights, greedy (BENCH_TEMP=t: slow token sampled
+at t), blocking responses.
 
     python tools/bench_scheduler.py [n_requests] [frames_per_tick] [stream|block] [pool_workers]
 
@@ -42,7 +43,9 @@ def main():
         cfg.max_seq_len = int(os.environ.get("MAX_SEQ", cfg.max_seq_len))  # experiment: the session's KV stride
         tts = SmolTTS(state=synthetic_lm_state(cfg, seed=0), config=cfg, mimi_state=synthetic_mimi_state(seed=0))
         slots = int(os.environ.get("SLOTS", 32))
-        sched = BatchScheduler(tts, max_batch=slots, frames_per_tick=tick, generation_settings=GenerationSettings.greedy(max_new_tokens=400),
+        temp = float(os.environ.get("BENCH_TEMP", 0))  # > 0: every request samples its slow token at this temperature (server default)
+        gs = GenerationSettings(default_temp=temp, default_fast_temp=0.0, max_new_tokens=400) if temp > 0 else GenerationSettings.greedy(max_new_tokens=400)
+        sched = BatchScheduler(tts, max_batch=slots, frames_per_tick=tick, generation_settings=gs,
                                codec_products=int(os.environ.get("CODEC_PRODUCTS", 6)))  # experiment: 3 = SMOLTTS_MIMI_OPT_PRODUCTS
     for _ in range(max(n_pool, 1) * 2):
         sched.synthesize("warm up", max_new_tokens=8)
