@@ -299,6 +299,38 @@ int smoltts_session_kv_cache(SmolttsSession* s, void** k_dev, void** v_dev, uint
 /* int32 [max_batch]: where each slot's smallest gap occurred, frame * 64 + step (step 0 = slow id, i = depth code i-1). */
 int smoltts_session_margin_at(SmolttsSession* s, int32_t** margin_at_dev);
 
+/* (ABI 6) Voice prefixes: the slow KV rows of a prompt prefix (a cloned voice's speaker turns), computed once and copied into the
+ * slots of later requests, whose own turns are then prefilled from position P on.  A prefix slab is caller-owned device memory,
+ * 256-byte aligned, of smoltts_prefix_kv_bytes(): a header (SmolttsPrefixHeader, padded to 256 bytes), then K and V of positions
+ * [0, P) as [n_layer][K | V][n_kv_head][P][64] in the KV format it was saved from -- exactly the bytes the cache holds.  The same
+ * header is returned on the host by the save call; the install call checks that host copy against the session and the install
+ * kernel checks the slab's own header against it (a slab with another header is left out of the copy). */
+#define SMOLTTS_PREFIX_MAGIC 0x58464250u  /* "PBFX" */
+#define SMOLTTS_PREFIX_MAX_INSTALL 16     /* prefixes per install launch; more are installed by further launches */
+typedef struct SmolttsPrefixHeader {
+  uint32_t magic;       /* SMOLTTS_PREFIX_MAGIC */
+  int32_t n_positions;  /* P */
+  int32_t n_layer;
+  int32_t n_kv_head;
+  int32_t kv_format;    /* SMOLTTS_KV_* */
+  int32_t head_dim;     /* 64 */
+  uint64_t data_bytes;  /* bytes after the 256-byte header */
+} SmolttsPrefixHeader;
+/* Bytes of a prefix slab of n_positions positions (0 for bad arguments). */
+size_t smoltts_prefix_kv_bytes(const SmolttsEngine* e, int32_t n_positions, int32_t kv_format);
+/* Copy rows [0, n_positions) of `slot`'s slow KV cache (every layer and kv head) into prefix_dev, and the header in front of them;
+ * *header_host (may be NULL) receives the header.  Asynchronous on `stream`: the rows are those the stream has written by then. */
+int smoltts_session_save_prefix(SmolttsSession* s, int32_t slot, int32_t n_positions, void* prefix_dev,
+                                SmolttsPrefixHeader* header_host, void* stream);
+/* Write prefix prefix_dev_host[i] (header header_host[i], as returned by the save) into rows [0, P_i) of slot slots_host[i], for n
+ * distinct slots with any mix of prefixes and lengths: one launch per SMOLTTS_PREFIX_MAX_INSTALL prefixes, descriptors passed by
+ * value.  Rows >= P_i of those slots and every other slot are untouched.  Allocates, uploads and synchronises nothing (capturable).
+ * Refused (nothing launched): a null or misaligned pointer, a slot out of range or listed twice, a header of another kv format,
+ * layer or kv-head count, or P_i + 1 > max_seq.  The slots' position counters are not touched: the prompt rows that follow go
+ * in at row_pos P_i, ... (a prefill, a chunk, or smoltts_lm_park_slots + smoltts_lm_prefill_side) before the slots decode again. */
+int smoltts_session_install_prefix(SmolttsSession* s, const void* const* prefix_dev_host, const SmolttsPrefixHeader* header_host,
+                                   const int32_t* slots_host, int32_t n, void* stream);
+
 /* ------------------------------------------------------------------------------ Mimi decoder */
 #define SMOLTTS_MIMI_MAX_LAYERS 16
 

@@ -12,6 +12,10 @@ from typing import Dict, Iterator, List, Optional
 __version__ = "0.1.0"
 
 
+class NoEncoderError(ValueError):
+    """Voice cloning asked of a model whose Mimi checkpoint carries no encoder weights."""
+
+
 class SmolTTS:
     def __init__(self, model_id: Optional[str] = None, checkpoint_dir: Optional[str] = None,
                  mimi_checkpoint: Optional[str] = None, numerics=None, state=None, config=None, mimi_state=None,
@@ -51,13 +55,39 @@ class SmolTTS:
         self._codec_window = codec_window
         self._encoder = None
         self.sampling_rate = 24_000
+        self.voices: Dict[str, "np.ndarray"] = {}  # registered voice id -> speaker grid (add_voice)
         self.verbose = verbose  # print the reference's per-call timing lines (lm/generate.py:187-214)
         self.last_sampling = None  # resolved RequestSampling list of the last call that was given sampling= (seeds included)
         self.last_stats: dict = {}  # timing of the last generate_codes / __call__ (BatchGenerator.stats + codec_ms)
 
     # -- prompt (``_get_prompt``, __init__.py:120-151)
     def _get_prompt(self, input: str, voice: str, sysprompt=None):
+        """A registered voice id (``add_voice``) brings its speaker grid as the prompt's prefix; other names are presets, and
+        unknown ones fall back to speaker 0 as in the reference."""
+        if sysprompt is None and voice in self.voices:
+            sysprompt = self.voices[voice]
         return self.prompt_encoder.build_prompt(input, voice, sysprompt)
+
+    # -- registered (cloned) voices: a voice id names a speaker grid (``create_speaker``) wherever a voice is named
+    def add_voice(self, voice_id: str, speaker_grid) -> None:
+        """Register ``speaker_grid`` under ``voice_id``: ``tts(text, voice_id)`` and ``stream(text, voice_id)`` then condition
+        on it, exactly as ``speaker=speaker_grid`` does.  The façade computes the whole prompt every call (the serving
+        scheduler is the one that caches the speaker turns' KV rows)."""
+        import numpy as np
+
+        from .prompt import VOICE_MAP
+
+        if not isinstance(voice_id, str) or not voice_id or voice_id in VOICE_MAP:
+            raise ValueError(f"voice id {voice_id!r} is empty or names a preset voice")
+        g = np.asarray(speaker_grid)
+        if g.ndim != 2 or g.shape[0] != self.prompt_encoder.depth + 1 or g.shape[1] < 1:
+            raise ValueError(f"speaker grid must be ({self.prompt_encoder.depth + 1}, T>=1), got {g.shape}")
+        self.voices[voice_id] = np.ascontiguousarray(g.astype(np.int32))
+
+    def remove_voice(self, voice_id: str) -> None:
+        if voice_id not in self.voices:
+            raise KeyError(voice_id)
+        del self.voices[voice_id]
 
     def _settings(self, generation_settings):
         from .config import GenerationSettings
@@ -136,7 +166,7 @@ class SmolTTS:
 
         if self._encoder is None:
             if self._mimi_encoder_state is None:
-                raise ValueError("the Mimi checkpoint has no encoder.* weights: voice-clone prompts need the full kyutai/mimi model")
+                raise NoEncoderError("the Mimi checkpoint has no encoder.* weights: voice-clone prompts need the full kyutai/mimi model")
             self._encoder = MimiEncoder(self._mimi_encoder_state, num_codebooks=8, window=self._codec_window)
             self._mimi_encoder_state = None
         pcm = np.asarray(audio, dtype=np.float32).reshape(-1)

@@ -761,6 +761,101 @@ int check_offsets(const SmolttsLMConfig& c, const SmolttsLMWeights& w, size_t by
   return SMOLTTS_OK;
 }
 
+// ---- voice prefixes (smoltts_session_save_prefix / _install_prefix): rows [0, P) of a slot's slow KV cache in a caller-owned slab
+//   [SmolttsPrefixHeader, padded to PREFIX_HDR bytes][layer][K | V][kv head][P][64] in the session's KV dtype
+// Every (layer, K/V, kv head) run is contiguous in the slab and in the cache ([layer][slot][kv head][max_seq][64]), and its bytes
+// are a multiple of 128: a copy of 16-byte units.  One launch moves up to SMOLTTS_PREFIX_MAX_INSTALL runs sets; blockIdx.y picks
+// the (descriptor, run), blockIdx.x a PREFIX_BLOCK_BYTES piece of it, and each lane has PREFIX_UNROLL loads in flight before it stores.
+constexpr int PREFIX_HDR = 256;
+constexpr int PREFIX_THREADS = 256, PREFIX_UNROLL = 4;
+constexpr int PREFIX_BLOCK_BYTES = PREFIX_THREADS * PREFIX_UNROLL * 16;  // 16 KiB per workgroup
+
+struct PrefixDesc {
+  char* prefix;  // slab (header first)
+  int slot;
+  int n_positions;
+};
+
+struct PrefixCopyArgs {
+  char *kc, *vc;
+  uint64_t layer_bytes;  // bytes of one layer of the cache (all slots)
+  int n_kv_head, max_seq, row_bytes, runs;  // runs = n_layer * 2 * n_kv_head per descriptor
+  int n;
+  int to_cache;          // 1: slab -> cache (install), 0: cache -> slab (save; writes the header too)
+  SmolttsPrefixHeader header;  // save: the header written into the slab
+  PrefixDesc d[SMOLTTS_PREFIX_MAX_INSTALL];
+};
+
+__global__ __launch_bounds__(PREFIX_THREADS) void prefix_copy_kernel(PrefixCopyArgs a) {
+  const int d = blockIdx.y / a.runs, r = blockIdx.y % a.runs;
+  if (d >= a.n) return;
+  const PrefixDesc desc = a.d[d];
+  const int l = r / (2 * a.n_kv_head), kv = (r / a.n_kv_head) & 1, h = r % a.n_kv_head;
+  const uint64_t run_bytes = (uint64_t)desc.n_positions * a.row_bytes;
+  char* slab_run = desc.prefix + PREFIX_HDR + (uint64_t)r * run_bytes;
+  char* cache_run = (kv ? a.vc : a.kc) + (uint64_t)l * a.layer_bytes + ((uint64_t)desc.slot * a.n_kv_head + h) * a.max_seq * a.row_bytes;
+  if (a.to_cache) {
+    // the slab must carry the header the host validated (a slab paired with another slab's header copies nothing)
+    const SmolttsPrefixHeader* hd = reinterpret_cast<const SmolttsPrefixHeader*>(desc.prefix);
+    if (hd->magic != SMOLTTS_PREFIX_MAGIC || hd->n_positions != desc.n_positions) return;
+  } else if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    *reinterpret_cast<SmolttsPrefixHeader*>(desc.prefix) = a.header;
+  }
+  const uint4* src = reinterpret_cast<const uint4*>(a.to_cache ? slab_run : cache_run);
+  uint4* dst = reinterpret_cast<uint4*>(a.to_cache ? cache_run : slab_run);
+  const uint64_t units = run_bytes / 16;
+  const uint64_t base = (uint64_t)blockIdx.x * (PREFIX_BLOCK_BYTES / 16);
+  if (base >= units) return;  // (a shorter prefix of the launch)
+  if (base + PREFIX_BLOCK_BYTES / 16 <= units) {  // whole piece: every load issued before the first store
+    uint4 v[PREFIX_UNROLL];
+#pragma unroll
+    for (int k = 0; k < PREFIX_UNROLL; ++k) v[k] = src[base + k * PREFIX_THREADS + threadIdx.x];
+#pragma unroll
+    for (int k = 0; k < PREFIX_UNROLL; ++k) dst[base + k * PREFIX_THREADS + threadIdx.x] = v[k];
+  } else {  // the run's last piece
+    for (uint64_t u = base + threadIdx.x; u < units; u += PREFIX_THREADS) dst[u] = src[u];
+  }
+}
+
+size_t prefix_data_bytes(const SmolttsLMConfig& c, int n_positions, int kv_format) {
+  return (size_t)c.n_layer * 2 * c.n_kv_head * n_positions * 64 * (kv_format == SMOLTTS_KV_BF16 ? 2 : 4);
+}
+
+SmolttsPrefixHeader prefix_header(const SmolttsSession* s, int n_positions) {
+  const SmolttsLMConfig& c = s->e->cfg;
+  SmolttsPrefixHeader h;
+  memset(&h, 0, sizeof(h));
+  h.magic = SMOLTTS_PREFIX_MAGIC;
+  h.n_positions = n_positions;
+  h.n_layer = c.n_layer;
+  h.n_kv_head = c.n_kv_head;
+  h.kv_format = s->kv_format;
+  h.head_dim = 64;
+  h.data_bytes = prefix_data_bytes(c, n_positions, s->kv_format);
+  return h;
+}
+
+PrefixCopyArgs prefix_args(const SmolttsSession* s, int to_cache) {
+  const SmolttsLMConfig& c = s->e->cfg;
+  PrefixCopyArgs a;
+  memset(&a, 0, sizeof(a));
+  a.kc = s->kc; a.vc = s->vc;
+  a.row_bytes = 64 * (s->kv_format == SMOLTTS_KV_BF16 ? 2 : 4);
+  a.layer_bytes = (uint64_t)s->B * c.n_kv_head * s->max_seq * a.row_bytes;
+  a.n_kv_head = c.n_kv_head; a.max_seq = s->max_seq;
+  a.runs = c.n_layer * 2 * c.n_kv_head;
+  a.to_cache = to_cache;
+  return a;
+}
+
+int launch_prefix_copy(const PrefixCopyArgs& a, int max_positions, hipStream_t st) {
+  const uint64_t run_bytes = (uint64_t)max_positions * a.row_bytes;
+  const dim3 grid((unsigned)((run_bytes + PREFIX_BLOCK_BYTES - 1) / PREFIX_BLOCK_BYTES), (unsigned)(a.n * a.runs));
+  hipLaunchKernelGGL(prefix_copy_kernel, grid, dim3(PREFIX_THREADS), 0, st, a);
+  ST_CHECK_HIP(hipGetLastError());
+  return SMOLTTS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1313,6 +1408,65 @@ int smoltts_session_kv_cache(SmolttsSession* s, void** k_dev, void** v_dev, uint
 int smoltts_session_margin_at(SmolttsSession* s, int32_t** margin_at_dev) {
   ST_REQUIRE(s && margin_at_dev, SMOLTTS_E_INVALID, "session_margin_at: null argument");
   *margin_at_dev = s->margin_at;
+  return SMOLTTS_OK;
+}
+
+size_t smoltts_prefix_kv_bytes(const SmolttsEngine* e, int32_t n_positions, int32_t kv_format) {
+  if (!e || n_positions <= 0 || (kv_format != SMOLTTS_KV_F32 && kv_format != SMOLTTS_KV_BF16)) return 0;
+  return PREFIX_HDR + prefix_data_bytes(e->cfg, n_positions, kv_format);
+}
+
+int smoltts_session_save_prefix(SmolttsSession* s, int32_t slot, int32_t n_positions, void* prefix_dev,
+                                SmolttsPrefixHeader* header_host, void* stream) {
+  ST_REQUIRE(s && prefix_dev, SMOLTTS_E_INVALID, "session_save_prefix: null argument");
+  ST_REQUIRE(slot >= 0 && slot < s->B, SMOLTTS_E_INVALID, "session_save_prefix: slot %d out of range (%d slots)", slot, s->B);
+  ST_REQUIRE(n_positions > 0 && n_positions + 1 <= s->max_seq, SMOLTTS_E_CAPACITY,
+             "session_save_prefix: %d positions + 1 exceed max_seq %d", n_positions, s->max_seq);
+  ST_REQUIRE(((uintptr_t)prefix_dev & 255) == 0, SMOLTTS_E_INVALID, "session_save_prefix: slab not 256-byte aligned");
+  PrefixCopyArgs a = prefix_args(s, /*to_cache=*/0);
+  a.header = prefix_header(s, n_positions);
+  a.n = 1;
+  a.d[0] = PrefixDesc{(char*)prefix_dev, slot, n_positions};
+  ST_TRY(launch_prefix_copy(a, n_positions, (hipStream_t)stream));
+  if (header_host) *header_host = a.header;
+  return SMOLTTS_OK;
+}
+
+int smoltts_session_install_prefix(SmolttsSession* s, const void* const* prefix_dev_host, const SmolttsPrefixHeader* header_host,
+                                   const int32_t* slots_host, int32_t n, void* stream) {
+  ST_REQUIRE(s && prefix_dev_host && header_host && slots_host, SMOLTTS_E_INVALID, "session_install_prefix: null argument");
+  ST_REQUIRE(n > 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_install_prefix: %d prefixes, session holds %d slots", n, s->B);
+  const SmolttsLMConfig& c = s->e->cfg;
+  for (int i = 0; i < n; ++i) {
+    const SmolttsPrefixHeader& h = header_host[i];
+    ST_REQUIRE(prefix_dev_host[i] && ((uintptr_t)prefix_dev_host[i] & 255) == 0, SMOLTTS_E_INVALID,
+               "session_install_prefix: prefix %d is null or not 256-byte aligned", i);
+    ST_REQUIRE(slots_host[i] >= 0 && slots_host[i] < s->B, SMOLTTS_E_INVALID, "session_install_prefix: slot %d out of range (%d slots)",
+               slots_host[i], s->B);
+    for (int j = 0; j < i; ++j)
+      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_install_prefix: slot %d listed twice", slots_host[i]);
+    ST_REQUIRE(h.magic == SMOLTTS_PREFIX_MAGIC && h.head_dim == 64, SMOLTTS_E_INVALID, "session_install_prefix: prefix %d has no valid header", i);
+    ST_REQUIRE(h.kv_format == s->kv_format, SMOLTTS_E_INVALID, "session_install_prefix: prefix %d holds kv format %d, the session %d", i,
+               h.kv_format, s->kv_format);
+    ST_REQUIRE(h.n_layer == c.n_layer && h.n_kv_head == c.n_kv_head, SMOLTTS_E_INVALID,
+               "session_install_prefix: prefix %d is %d layers x %d kv heads, the session's model %d x %d", i, h.n_layer, h.n_kv_head,
+               c.n_layer, c.n_kv_head);
+    ST_REQUIRE(h.n_positions > 0 && h.n_positions + 1 <= s->max_seq, SMOLTTS_E_CAPACITY,
+               "session_install_prefix: prefix %d of %d positions + 1 exceeds max_seq %d", i, h.n_positions, s->max_seq);
+    ST_REQUIRE(h.data_bytes == prefix_data_bytes(c, h.n_positions, h.kv_format), SMOLTTS_E_INVALID,
+               "session_install_prefix: prefix %d header size mismatch", i);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int i0 = 0; i0 < n; i0 += SMOLTTS_PREFIX_MAX_INSTALL) {  // one launch per SMOLTTS_PREFIX_MAX_INSTALL prefixes
+    PrefixCopyArgs a = prefix_args(s, /*to_cache=*/1);
+    a.n = n - i0 < SMOLTTS_PREFIX_MAX_INSTALL ? n - i0 : SMOLTTS_PREFIX_MAX_INSTALL;
+    int pmax = 0;
+    for (int k = 0; k < a.n; ++k) {
+      a.d[k] = PrefixDesc{(char*)prefix_dev_host[i0 + k], slots_host[i0 + k], header_host[i0 + k].n_positions};
+      pmax = imax(pmax, a.d[k].n_positions);
+    }
+    ST_TRY(launch_prefix_copy(a, pmax, st));
+  }
   return SMOLTTS_OK;
 }
 

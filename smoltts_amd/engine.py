@@ -92,6 +92,11 @@ class MimiEncWeights(C.Structure):
                 ("in_proj", C.c_uint64 * 2), ("codebooks_t", C.c_uint64), ("codebooks", C.c_uint64), ("codebook_sq", C.c_uint64)]
 
 
+class PrefixHeader(C.Structure):
+    _fields_ = [("magic", C.c_uint32)] + [(n, C.c_int32) for n in ("n_positions", "n_layer", "n_kv_head", "kv_format", "head_dim")] + [
+        ("data_bytes", C.c_uint64)]
+
+
 PRO_NONE, PRO_RMSNORM, PRO_ELU, PRO_LAYERNORM = 0, 1, 2, 3
 KV_FORMATS = {"fp32": 0, "bf16": 1}  # SMOLTTS_KV_*
 EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_GELU, EPI_SCALE_RESID, EPI_QKV_ROPE = range(6)
@@ -112,6 +117,7 @@ _EXPORTS = [
     "smoltts_resample_design", "smoltts_resampler_bytes", "smoltts_resampler_create", "smoltts_resampler_destroy",
     "smoltts_resampler_out_bytes", "smoltts_resampler_reset_slots", "smoltts_resample_chunk",
     "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows",
+    "smoltts_prefix_kv_bytes", "smoltts_session_save_prefix", "smoltts_session_install_prefix",
 ]
 
 
@@ -212,6 +218,11 @@ def load_library(path: Optional[Path] = None):
     lib.smoltts_resampler_reset_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.smoltts_resample_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_void_p]
+    lib.smoltts_prefix_kv_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.smoltts_prefix_kv_bytes.restype = C.c_size_t
+    lib.smoltts_session_save_prefix.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(PrefixHeader), C.c_void_p]
+    lib.smoltts_session_install_prefix.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(PrefixHeader), C.POINTER(C.c_int32),
+                                                   C.c_int32, C.c_void_p]
     if lib.smoltts_abi_version() != 6:
         raise SmolttsError("libsmoltts_hip.so ABI version mismatch")
     if path is None:
@@ -281,8 +292,14 @@ def dptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else int(t.data_ptr())
 
 
-def _alloc_slab(nbytes: int, device) -> torch.Tensor:
+def _alloc_slab(nbytes: int, device, settle: bool = False) -> torch.Tensor:
+    """A zeroed, 256-byte aligned slab.  The zero fill is queued on the current stream.  ``settle``: wait for it here -- for a slab
+    that a C create call then initialises with plain hipMemcpy / hipMemset / a null-stream kernel, which are not ordered against
+    a non-blocking current stream (a serving thread's frame stream with ticks queued) and would otherwise be overwritten by a
+    late zero fill."""
     slab = torch.zeros(nbytes + 256, dtype=torch.uint8, device=device)
+    if settle:
+        torch.cuda.current_stream(device).synchronize()
     shift = (-slab.data_ptr()) % 256
     return slab[shift: shift + nbytes]
 
@@ -399,7 +416,7 @@ class LMSession:
         need = self.lib.smoltts_session_slab_bytes_kv(engine.handle, self.B, self.max_seq, self.max_rows, self.max_frames, kvf)
         if need == 0:
             raise SmolttsError("smoltts_session_slab_bytes returned 0 (bad sizes)")
-        self.slab = _alloc_slab(need, engine.device)
+        self.slab = _alloc_slab(need, engine.device, settle=True)
         h = C.c_void_p()
         check(self.lib.smoltts_session_create_kv(engine.handle, dptr(self.slab), need, self.B, self.max_seq, self.max_rows,
                                                  self.max_frames, kvf, C.byref(h)), "smoltts_session_create")
@@ -420,6 +437,7 @@ class LMSession:
         check(self.lib.smoltts_session_margin_at(h, C.byref(mp)), "smoltts_session_margin_at")
         self.margin_at = view(mp, self.B * 4, torch.int32, (self.B,))  # frame * 64 + step of each slot's smallest gap
         self._keep = None
+        self._keep_prefixes = None
         if os.environ.get("SMOLTTS_COMMIT_PICKS") == "0":  # A/B switches of tools/ (the ids are the same either way)
             self.use_commit_picks(False)
         if os.environ.get("SMOLTTS_SPLIT_ATTN") == "0":
@@ -459,15 +477,21 @@ class LMSession:
 
     # ---- prompt prefill beside the decode frames (include/smoltts_hip.h at smoltts_lm_park_slots): three steps, the first and the
     #      last on the stream the frames run on, the middle one on any other stream once the first has run
-    def side_park(self, prompts: Sequence[np.ndarray], slots: Sequence[int]):
+    def side_park(self, prompts: Sequence[np.ndarray], slots: Sequence[int], pos0: Optional[Sequence[int]] = None,
+                  prefixes: Optional[Sequence[Optional["PrefixKV"]]] = None):
         """Freeze the (idle) ``slots`` at their new prompts' last positions and upload the prompt rows; -> a handle for the two
-        steps that follow.  Call on the frame stream."""
+        steps that follow.  Call on the frame stream.  ``pos0[b]``: position of the first column of ``prompts[b]`` (default 0;
+        the slot parks at ``pos0 + T - 1``).  ``prefixes[b]`` (a ``PrefixKV`` or None): installed into the slot first, in one
+        launch for all of them; ``pos0`` then defaults to its ``P``."""
         slots = list(slots)
         if len(slots) != len(prompts) or len(set(slots)) != len(slots):
             raise ValueError("slots must be distinct and match prompts")
-        grid_d, rslot_d, rpos_d, last, n = self._rows(prompts, slots, [0] * len(prompts))
+        pos0 = self._prefix_pos0(prompts, prefixes, pos0)
+        grid_d, rslot_d, rpos_d, last, n = self._rows(prompts, slots, pos0)
+        if prefixes is not None and any(p is not None for p in prefixes):
+            self.install_prefix([p for p in prefixes if p is not None], [b for b, p in zip(slots, prefixes) if p is not None])
         slots_h = (C.c_int32 * len(slots))(*slots)
-        park_h = (C.c_int32 * len(slots))(*[int(np.asarray(g).shape[1]) - 1 for g in prompts])
+        park_h = (C.c_int32 * len(slots))(*[p0 + int(np.asarray(g).shape[1]) - 1 for g, p0 in zip(prompts, pos0)])
         check(self.lib.smoltts_lm_park_slots(self.handle, slots_h, park_h, len(slots), current_stream_ptr()), "smoltts_lm_park_slots")
         parked = torch.cuda.Event()
         parked.record(torch.cuda.current_stream())
@@ -518,23 +542,77 @@ class LMSession:
                                                     len(slots), current_stream_ptr()), "smoltts_lm_prefill_chunk")
 
     def prefill_chunked(self, prompts: Sequence[np.ndarray], slots: Optional[Sequence[int]] = None, stop_on_eos: bool = True,
-                        chunk: int = 128, between=None, defer_frame0: bool = False) -> None:
+                        chunk: int = 128, between=None, defer_frame0: bool = False, pos0: Optional[Sequence[int]] = None,
+                        prefixes: Optional[Sequence[Optional["PrefixKV"]]] = None) -> None:
         """The same result as ``prefill`` with at most ``chunk`` columns per utterance per call; ``between()`` runs
-        after every partial call (e.g. a few decode frames for the slots that are already speaking)."""
+        after every partial call (e.g. a few decode frames for the slots that are already speaking).  ``pos0[b]``: position
+        of the first column of ``prompts[b]`` (default 0).  ``prefixes[b]`` (a ``PrefixKV`` or None): installed into the slot
+        first, in one launch for all of them; ``pos0`` then defaults to its ``P``."""
         slots = list(range(len(prompts))) if slots is None else list(slots)
         prompts = [np.asarray(g) for g in prompts]
+        start = self._prefix_pos0(prompts, prefixes, pos0)
+        if prefixes is not None and any(p is not None for p in prefixes):
+            have = [i for i, p in enumerate(prefixes) if p is not None]
+            self.install_prefix([prefixes[i] for i in have], [slots[i] for i in have])
+            if between is not None and any(g.shape[1] > chunk for g in prompts):
+                # a tick may run before these slots' first prefill call: park them behind their prompts, where an idle slot's
+                # decode rows may scribble without harm (the installed rows stay as they are)
+                slots_h = (C.c_int32 * len(have))(*[slots[i] for i in have])
+                park_h = (C.c_int32 * len(have))(*[start[i] + int(prompts[i].shape[1]) - 1 for i in have])
+                check(self.lib.smoltts_lm_park_slots(self.handle, slots_h, park_h, len(have), current_stream_ptr()), "smoltts_lm_park_slots")
         done = [0] * len(prompts)
         while True:
             part = [i for i, g in enumerate(prompts) if g.shape[1] - done[i] > chunk]
             if not part:
                 break
             self.prefill([prompts[i][:, done[i]: done[i] + chunk] for i in part], [slots[i] for i in part], stop_on_eos,
-                         pos0=[done[i] for i in part], final=False)
+                         pos0=[start[i] + done[i] for i in part], final=False)
             for i in part:
                 done[i] += chunk
             if between is not None:
                 between()
-        self.prefill([g[:, d:] for g, d in zip(prompts, done)], slots, stop_on_eos, pos0=done, final=True, defer_frame0=defer_frame0)
+        self.prefill([g[:, d:] for g, d in zip(prompts, done)], slots, stop_on_eos, pos0=[p + d for p, d in zip(start, done)], final=True,
+                     defer_frame0=defer_frame0)
+
+    # ---- voice prefixes (include/smoltts_hip.h at smoltts_session_save_prefix)
+    @staticmethod
+    def _prefix_pos0(prompts, prefixes, pos0) -> List[int]:
+        if prefixes is not None and len(prefixes) != len(prompts):
+            raise ValueError("one prefix (or None) per prompt")
+        if pos0 is not None:
+            pos0 = [int(p) for p in pos0]
+            if len(pos0) != len(prompts):
+                raise ValueError("one pos0 per prompt")
+            if prefixes is not None and any(p is not None and p0 != p.n_positions for p, p0 in zip(prefixes, pos0)):
+                raise ValueError("pos0 of a prompt behind a prefix must be the prefix's length")
+            return pos0
+        return [0 if prefixes is None or p is None else p.n_positions for p in (prefixes or [None] * len(prompts))]
+
+    def save_prefix(self, slot: int, n_positions: int) -> "PrefixKV":
+        """Rows [0, n_positions) of ``slot``'s slow KV cache (as the current stream has written them by then) -> a ``PrefixKV``
+        that any session on this engine with the same kv dtype can install."""
+        pk = PrefixKV(self.engine, int(n_positions), self.kv_dtype)
+        hdr = PrefixHeader()
+        check(self.lib.smoltts_session_save_prefix(self.handle, int(slot), int(n_positions), dptr(pk.slab), C.byref(hdr),
+                                                   current_stream_ptr()), "smoltts_session_save_prefix")
+        pk.header = hdr
+        return pk
+
+    def install_prefix(self, prefixes: Sequence["PrefixKV"], slots: Sequence[int]) -> None:
+        """Copy ``prefixes[i]`` into rows [0, P_i) of slot ``slots[i]`` on the current stream (one launch per 16 prefixes; nothing
+        else of the session changes).  The prompt rows that follow must go in at pos0 = P_i before the slots decode again."""
+        slots = [int(b) for b in slots]
+        n = len(slots)
+        if n != len(prefixes) or n == 0:
+            raise ValueError("one slot per prefix, at least one")
+        for p in prefixes:
+            if p.header is None:
+                raise ValueError("prefix has not been saved")
+        ptrs = (C.c_void_p * n)(*[dptr(p.slab) for p in prefixes])
+        hdrs = (PrefixHeader * n)(*[p.header for p in prefixes])
+        check(self.lib.smoltts_session_install_prefix(self.handle, ptrs, hdrs, (C.c_int32 * n)(*slots), n, current_stream_ptr()),
+              "smoltts_session_install_prefix")
+        self._keep_prefixes = list(prefixes)  # alive until the stream has consumed them (freed slabs go back to torch's cache)
 
     def set_sampling(self, temp: float = 0.0, fast_temp: float = 0.0, min_p: float = 0.0, seed: int = 0) -> None:
         """temp / fast_temp <= 0: greedy (default). Takes effect from the next frame."""
@@ -616,6 +694,35 @@ class LMSession:
             torch.cuda.synchronize()
             self.lib.smoltts_session_destroy(self.handle)
             self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PrefixKV:
+    """The slow KV rows of positions [0, P) of one prompt prefix (a cloned voice's speaker turns), in a slab of its own
+    (``LMSession.save_prefix``): any session on the same engine with the same kv dtype installs it into a slot in one copy
+    (``LMSession.install_prefix``).  The slab is released with the object."""
+
+    def __init__(self, engine: LMEngine, n_positions: int, kv_dtype: str = "fp32"):
+        if kv_dtype not in KV_FORMATS:
+            raise ValueError(f"kv_dtype must be one of {sorted(KV_FORMATS)}, got {kv_dtype!r}")
+        self.engine, self.n_positions, self.kv_dtype = engine, int(n_positions), kv_dtype
+        nbytes = engine.lib.smoltts_prefix_kv_bytes(engine.handle, self.n_positions, KV_FORMATS[kv_dtype])
+        if nbytes == 0:
+            raise SmolttsError(f"smoltts_prefix_kv_bytes returned 0 (P={n_positions})")
+        self.slab = _alloc_slab(nbytes, engine.device)
+        self.header: Optional[PrefixHeader] = None  # set by the save (the host copy of the slab's header)
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.slab.numel())
+
+    def close(self):
+        self.slab = None
 
     def __del__(self):
         try:
@@ -749,7 +856,7 @@ class MimiSession:
         need = self.lib.smoltts_mimi_slab_bytes(engine.handle, max_batch, max_chunk_frames)
         if need == 0:
             raise SmolttsError("smoltts_mimi_slab_bytes returned 0 (bad sizes)")
-        self.slab = _alloc_slab(need, engine.device)
+        self.slab = _alloc_slab(need, engine.device, settle=True)
         h = C.c_void_p()
         check(self.lib.smoltts_mimi_session_create(engine.handle, dptr(self.slab), need, max_batch, max_chunk_frames, C.byref(h)),
               "smoltts_mimi_session_create")
@@ -832,7 +939,7 @@ class Resampler:
         need = self.lib.smoltts_resampler_bytes(max_batch)
         if need == 0:
             raise SmolttsError("smoltts_resampler_bytes returned 0 (bad sizes)")
-        self.slab = _alloc_slab(need, device)
+        self.slab = _alloc_slab(need, device, settle=True)
         h = C.c_void_p()
         check(self.lib.smoltts_resampler_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_resampler_create")
         self.handle = h

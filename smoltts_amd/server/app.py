@@ -11,7 +11,8 @@ from __future__ import annotations
 
 import argparse
 import json
-from typing import Literal, Optional, Union
+import threading
+from typing import Dict, List, Literal, Optional, Union
 
 import numpy as np
 from fastapi import APIRouter, FastAPI, HTTPException, Query, Request, Response
@@ -30,6 +31,72 @@ class TTSCore:
         self.model = model
         self.settings = settings
         self.scheduler = scheduler  # BatchScheduler: concurrent requests share the GPU batch
+        self.voices: Dict[str, dict] = {}  # cloned voices registered through this server: id -> {"name", "prompt_positions"}
+        self._voice_lock = threading.Lock()
+
+    # -- cloned voices (extension: ElevenLabs' voices/add with JSON + base64 WAV samples instead of multipart)
+    @property
+    def max_voices(self) -> int:
+        st = self.settings
+        v = st.get("max_voices") if isinstance(st, dict) else getattr(st, "max_voices", None)
+        return 64 if v is None else int(v)
+
+    def add_voice(self, name: str, samples: List[dict], system_prompt: Optional[str] = None) -> str:
+        """samples: [{"text", "audio": float32 at 24 kHz}] -> the new voice id.  ``ValueError``: a voice that cannot be served;
+        ``NoEncoderError``: no encoder weights; ``OverflowError``: max_voices reached."""
+        from .voices import new_voice_id
+
+        with self._voice_lock:
+            if len(self.voices) >= self.max_voices:
+                raise OverflowError(f"{len(self.voices)} voices registered: max_voices is {self.max_voices}")
+            voice_id = new_voice_id()
+            self.voices[voice_id] = {"name": name, "prompt_positions": None}  # (holds the place while the voice is computed)
+        try:
+            if self.scheduler is not None:
+                P = int(self.scheduler.add_voice(voice_id, samples=samples, system_prompt=system_prompt, name=name)["prompt_positions"])
+            else:
+                grid = self.model.create_speaker(samples, system_prompt=system_prompt)
+                P = int(grid.shape[1])
+                self._check_room(grid)
+                self.model.add_voice(voice_id, grid)
+        except BaseException:
+            with self._voice_lock:
+                self.voices.pop(voice_id, None)
+            raise
+        with self._voice_lock:
+            self.voices[voice_id]["prompt_positions"] = P
+        return voice_id
+
+    def _check_room(self, grid) -> None:
+        """The model-only path: a speaker prompt must leave room for an empty request and the frame budget (as the scheduler's)."""
+        m = self.model
+        if not all(hasattr(m, a) for a in ("prompt_encoder", "config", "_settings")):
+            return
+        P = int(grid.shape[1])
+        t_min = int(m.prompt_encoder.build_prompt("", "", grid).shape[1]) - P
+        max_new = m._settings(None).max_new_tokens or 0
+        if P + t_min + max_new + 2 > m.config.max_seq_len:
+            raise ValueError(f"speaker prompt of P={P} positions leaves no room for a request: P + {t_min} (an empty request) + "
+                             f"max_new_tokens {max_new} + 2 > max_seq_len {m.config.max_seq_len}")
+
+    def remove_voice(self, voice_id: str) -> None:
+        with self._voice_lock:
+            if voice_id not in self.voices or self.voices[voice_id]["prompt_positions"] is None:
+                raise KeyError(voice_id)
+            del self.voices[voice_id]
+        if self.scheduler is not None:
+            self.scheduler.remove_voice(voice_id)
+        else:
+            self.model.remove_voice(voice_id)
+
+    def list_voices(self) -> List[dict]:
+        from ..prompt import VOICES
+
+        out = [{"voice_id": v, "name": v, "category": "premade"} for v in VOICES]
+        with self._voice_lock:
+            out += [{"voice_id": k, "name": v["name"], "category": "cloned", "prompt_positions": v["prompt_positions"]}
+                    for k, v in self.voices.items() if v["prompt_positions"] is not None]
+        return out
 
     def resolve_speaker_id(self, voice: Union[str, int]) -> int:
         if isinstance(voice, int):
@@ -181,6 +248,61 @@ def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
     chunks, seed = core.stream_audio(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling())
     return StreamingResponse(chunks, media_type="audio/wav", headers={
         "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed)})
+
+
+class VoiceSample(BaseModel):
+    text: Optional[str] = None
+    audio: str  # base64 RIFF WAV: 16-bit PCM or 32-bit float (also WAVE_FORMAT_EXTENSIBLE), 8-48 kHz, any channel count
+
+
+class AddVoiceRequest(BaseModel):
+    name: str
+    samples: List[VoiceSample] = Field(min_length=1)
+    system_prompt: Optional[str] = None
+
+
+@eleven_router.post("/voices/add")
+def add_voice(item: AddVoiceRequest, http_request: Request):
+    """Clone a voice from reference recordings and their transcripts; the answer's ``voice_id`` names it on every speech route."""
+    from .. import NoEncoderError
+    from .voices import decode_sample_audio
+
+    core = http_request.app.state.tts_core
+    samples = []
+    for i, smp in enumerate(item.samples):
+        if not smp.text or not smp.text.strip():
+            raise HTTPException(status_code=400, detail=f"sample {i} has no text")
+        try:
+            samples.append({"text": smp.text, "audio": decode_sample_audio(smp.audio)})
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"sample {i}: {e}")
+    try:
+        voice_id = core.add_voice(item.name, samples, item.system_prompt)
+    except NoEncoderError as e:
+        raise HTTPException(status_code=501, detail=str(e))
+    except OverflowError as e:
+        raise HTTPException(status_code=409, detail=str(e))
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+    return {"voice_id": voice_id}
+
+
+@eleven_router.get("/voices")
+def list_voices(http_request: Request):
+    return {"voices": http_request.app.state.tts_core.list_voices()}
+
+
+@eleven_router.delete("/voices/{voice_id}")
+def delete_voice(voice_id: str, http_request: Request):
+    from ..prompt import VOICE_MAP
+
+    if voice_id in VOICE_MAP:
+        raise HTTPException(status_code=400, detail=f"{voice_id!r} is a premade voice")
+    try:
+        http_request.app.state.tts_core.remove_voice(voice_id)
+    except KeyError:
+        raise HTTPException(status_code=404, detail=f"no voice {voice_id!r}")
+    return {"status": "ok"}
 
 
 @eleven_router.get("/stats")

@@ -81,11 +81,28 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
             with lock:
                 live.pop(rid, None)
 
+    def control(msg) -> None:  # voice registry: the scheduler call blocks until its worker thread has done the GPU part
+        kind, rid = msg[:2]
+        try:
+            if kind == "encode_voice":
+                out = sched.encode_speaker(msg[2], system_prompt=msg[3])
+            elif kind == "add_voice":
+                out = sched.add_voice(msg[2], grid=msg[3], name=msg[4])
+            else:
+                sched.remove_voice(msg[2])
+                out = None
+            res_q.put((rid, "result", out))
+        except Exception as e:
+            res_q.put((rid, "error", (type(e).__name__, str(e))))
+
     try:
         while True:
             msg = req_q.get()
             if msg[0] == "close":
                 break
+            if msg[0] in ("encode_voice", "add_voice", "remove_voice"):
+                threading.Thread(target=control, args=(msg,), name=f"smoltts-voice-{msg[1]}", daemon=True).start()
+                continue
             if msg[0] == "submit":
                 _, rid, text, voice, stream, max_new_tokens = msg[:6]
                 extra = msg[6] if len(msg) > 6 else {}  # (output_format / sampling, only when set)
@@ -135,6 +152,8 @@ class GpuPool:
         self._restarts: List[int] = [0] * len(devices)
         self._ids = itertools.count()
         self._closing = False
+        self._voices: Dict[str, tuple] = {}  # registered voice id -> (speaker grid, name): replayed to a worker that replaces a dead one
+        self._voice_lock = threading.Lock()  # one registry change at a time
         for i, conn in enumerate(self._res):  # all workers up (weights loaded, kernels resident) before the first request is taken
             why = self._await_ready(conn, i)
             if why is not None:
@@ -218,6 +237,79 @@ class GpuPool:
             req.cancelled = True
             self._req_qs[req.worker].put(("cancel", req.rid))
 
+    # ------------------------------------------------------------------ registered voices (the parent stays off the GPU)
+    def add_voice(self, voice_id: str, samples=None, grid=None, system_prompt: Optional[str] = None, name: Optional[str] = None) -> dict:
+        """``BatchScheduler.add_voice`` on every worker: one worker encodes ``samples`` into a speaker grid, then the grid goes
+        to all of them, and the call returns once every one has acknowledged -- a request submitted afterwards finds the voice
+        wherever it lands.  The grid is kept here and replayed to a worker that replaces a dead one."""
+        if (samples is None) == (grid is None):
+            raise ValueError("pass samples or grid")
+        with self._voice_lock:
+            if grid is None:
+                w = self._pick_worker()
+                grid = self._await_control(self._control(w, ("encode_voice", samples, system_prompt)))
+            grid = np.ascontiguousarray(np.asarray(grid, dtype=np.int32))
+            reqs = [self._control(w, ("add_voice", voice_id, grid, name)) for w in self._alive()]
+            results = []
+            try:
+                for r in reqs:
+                    results.append(self._await_control(r))
+            except BaseException:
+                for w in self._alive():  # a partial registration is taken back where it was made
+                    try:
+                        self._await_control(self._control(w, ("remove_voice", voice_id)))
+                    except Exception:
+                        pass
+                raise
+            self._voices[voice_id] = (grid, name)
+            return results[0]
+
+    def remove_voice(self, voice_id: str) -> None:
+        """Forget a registered voice on every worker (``KeyError`` if there is none)."""
+        with self._voice_lock:
+            if voice_id not in self._voices:
+                raise KeyError(voice_id)
+            del self._voices[voice_id]
+            for r in [self._control(w, ("remove_voice", voice_id)) for w in self._alive()]:
+                try:
+                    self._await_control(r)
+                except KeyError:
+                    pass
+
+    def voices(self) -> Dict[str, dict]:
+        """Registered voices: id -> {"name", "prompt_positions"}."""
+        with self._voice_lock:
+            return {k: {"name": n, "prompt_positions": int(g.shape[1])} for k, (g, n) in self._voices.items()}
+
+    def _alive(self) -> List[int]:
+        with self._lock:
+            return [i for i, p in enumerate(self._procs) if not self._dead[i] and p.is_alive()]
+
+    def _pick_worker(self) -> int:
+        alive = self._alive()
+        if not alive:
+            raise RuntimeError("no GPU worker is alive")
+        with self._lock:
+            return min(alive, key=lambda i: self._load[i])
+
+    def _control(self, w: int, msg: tuple) -> _PoolRequest:
+        """Send a registry message to worker ``w``; its answer arrives through the request books like a request's end."""
+        with self._lock:
+            if self._closing:
+                raise RuntimeError("pool closed")
+            req = _PoolRequest(next(self._ids), w)
+            self._reqs[req.rid] = req
+            self._load[w] += 1
+        self._req_qs[w].put((msg[0], req.rid) + tuple(msg[1:]))
+        return req
+
+    @staticmethod
+    def _await_control(req: _PoolRequest):
+        item = req.out.get()
+        if isinstance(item, BaseException):
+            raise item
+        return item[1]
+
     def stats(self) -> dict:
         """Front-end view (``GET /v1/stats``): workers alive and requests in flight per worker."""
         with self._lock:
@@ -283,9 +375,27 @@ class GpuPool:
                     req.out.put(payload)
             elif kind == "end":
                 self._finish(req, None)
+            elif kind == "result":  # a registry message's answer
+                self._finish(req, ("result", payload))
             elif kind == "error":
                 name, msg = payload  # a refused request (ValueError) stays one: the HTTP layer answers 400 for it, 500 for the rest
-                self._finish(req, ValueError(msg) if name == "ValueError" else RuntimeError(f"{name}: {msg}"))
+                self._finish(req, _remote_error(name, msg))
+
+    def _replay_voices(self, w: int, q, conn) -> bool:
+        """Register the known voices on the new worker ``w`` (its pipe read here, before its dispatcher takes over)."""
+        for k, (grid, name) in list(self._voices.items()):
+            rid = next(self._ids)
+            q.put(("add_voice", rid, k, grid, name))
+            while True:
+                try:
+                    got, kind, _ = conn.recv()
+                except (EOFError, OSError):
+                    return False
+                if got == rid:
+                    break
+            if kind != "result":
+                return False
+        return True
 
     def _replace(self, w: int):
         """Start a new worker in place of the dead one; its result pipe, or None (not wanted, closing, or it keeps dying)."""
@@ -293,7 +403,7 @@ class GpuPool:
             return None
         self._restarts[w] += 1
         p, q, r = self._start_worker(w)
-        if self._await_ready(r, w) is not None or self._closing:
+        if self._await_ready(r, w) is not None or self._closing or not self._replay_voices(w, q, r):
             if p.is_alive():
                 p.terminate()
             return None
@@ -310,6 +420,17 @@ class GpuPool:
             p.join(timeout=10)
 
 
+def _remote_error(name: str, msg: str) -> Exception:
+    """A worker's exception, by kind: ValueError (and a missing encoder, one of them) stays a refusal, KeyError an unknown voice."""
+    if name == "NoEncoderError":
+        from .. import NoEncoderError
+
+        return NoEncoderError(msg)
+    if name == "KeyError":
+        return KeyError(msg)
+    return ValueError(msg) if name == "ValueError" else RuntimeError(f"{name}: {msg}")
+
+
 # ---------------------------------------------------------------------- factories (picklable: module-level callables)
 def scheduler_from_settings(settings):
     """What a worker of ``smoltts-server --gpus N`` builds: the model from the settings file (a ``ServerSettings`` or the
@@ -324,15 +445,19 @@ def scheduler_from_settings(settings):
 
 
 def synthetic_scheduler(model: str = "tiny", seed: int = 21, mimi_seed: int = 5, max_batch: int = 4, frames_per_tick: int = 2,
-                        max_new_tokens: int = 64):
-    """Seeded random weights at the named shapes (tests, rehearsals without a checkpoint); greedy."""
+                        max_new_tokens: int = 64, mimi_encoder: bool = False):
+    """Seeded random weights at the named shapes (tests, rehearsals without a checkpoint); greedy.  ``mimi_encoder``: the codec
+    also carries (seeded) encoder weights, so that voices can be cloned."""
     from .. import SmolTTS
-    from ..codec.synthetic import synthetic_mimi_state
+    from ..codec.synthetic import synthetic_mimi_encoder_state, synthetic_mimi_state
     from ..config import GenerationSettings
     from ..synthetic import named_config, synthetic_lm_state
     from .scheduler import BatchScheduler
 
     cfg = named_config(model)
-    tts = SmolTTS(state=synthetic_lm_state(cfg, seed=seed), config=cfg, mimi_state=synthetic_mimi_state(seed=mimi_seed))
+    mst = synthetic_mimi_state(seed=mimi_seed)
+    if mimi_encoder:
+        mst = {**mst, **synthetic_mimi_encoder_state(seed=mimi_seed)}
+    tts = SmolTTS(state=synthetic_lm_state(cfg, seed=seed), config=cfg, mimi_state=mst)
     return BatchScheduler(tts, max_batch=max_batch, frames_per_tick=frames_per_tick,
                           generation_settings=GenerationSettings.greedy(max_new_tokens=max_new_tokens))

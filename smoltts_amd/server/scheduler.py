@@ -48,6 +48,17 @@ class _Request:
     closed: bool = False  # the end marker (None or an exception) has been queued
     output_format: Optional[str] = None  # streaming: pcm_<rate> / ulaw_8000 converted on the GPU (None: float32 at 24 kHz)
     sampling: object = None  # config.RequestSampling, resolved at submit (seed drawn there for a sampled request without one)
+    voice_entry: object = None  # _Voice of a registered voice, taken at submit (a later remove_voice does not affect the request)
+    pos0: int = 0             # position of the prompt's first column: the voice's prefix length P for a registered voice
+    prefix: object = None     # engine.PrefixKV installed into the slot at admission (None: the whole prompt is prefilled)
+
+
+@dataclass
+class _Voice:
+    voice_id: str
+    grid: np.ndarray   # the speaker prompt grid (1 + n_fast, P)
+    prefix: object     # engine.PrefixKV: its KV rows, computed once
+    name: Optional[str] = None
 
 
 @dataclass
@@ -117,11 +128,15 @@ class BatchScheduler:
         self._deliveries: List[tuple] = []      # (event, pcm on the device, [(request, first sample, n samples, last?)]) in order
         self._snaps: List[tuple] = []           # snapshots of the output ring the host has not looked at yet (oldest first)
         self._tick_no = 0                       # ticks queued so far
-        self._counts = {"completed": 0, "cancelled": 0, "failed": 0, "frames_delivered": 0}
+        self._counts = {"completed": 0, "cancelled": 0, "failed": 0, "frames_delivered": 0, "prefix_installs": 0}
         self._dead: Optional[Exception] = None  # why the worker stopped
         self._draining = False
         self._held: Optional[_Request] = None   # next in line, waiting for room in a prefill call
         self._gpu_wait_s = 0.0                  # time the worker spent waiting for the GPU (small => the host is the limit)
+        self._voices: Dict[str, _Voice] = {}    # registered voices (add_voice); read by submit, written by the worker
+        self._jobs: "queue.Queue[dict]" = queue.Queue()  # voice registrations waiting for the worker
+        self._job = None                        # the registration in progress: {"job": ..., "steps": generator}
+        self._scratch = None                    # one-slot session the voices' prefixes are computed in (created on first use)
         self._t0 = time.time()
         self._thread = threading.Thread(target=self._run, name="smoltts-scheduler", daemon=True)
         self._thread.start()
@@ -148,7 +163,7 @@ class BatchScheduler:
         if self._draining:
             raise RuntimeError("scheduler is not running: shutting down")
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
-                       output_format=output_format, sampling=resolved)
+                       output_format=output_format, sampling=resolved, voice_entry=self._voices.get(voice))
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
@@ -181,6 +196,46 @@ class BatchScheduler:
         step costs the same with or without it.  Nothing more is delivered except the end marker."""
         req.cancelled = True
 
+    # ------------------------------------------------------------------ client side: registered voices
+    def add_voice(self, voice_id: str, samples=None, grid=None, system_prompt: Optional[str] = None, name: Optional[str] = None) -> dict:
+        """Register a cloned voice: ``samples`` (``SmolTTS.create_speaker`` input: [{"text", "audio" at 24 kHz}]) or a ready speaker
+        ``grid``.  The worker encodes the samples (Mimi encoder) and computes the speaker turns' KV rows once, between ticks, a
+        prefill chunk at a time; from then on a request naming ``voice_id`` gets those rows copied into its slot and prefills only
+        its own turns.  Blocks until the voice is usable; ``ValueError`` for a voice the engine cannot serve.
+        Returns {"voice_id", "prompt_positions"}."""
+        from ..prompt import VOICE_MAP
+
+        if (samples is None) == (grid is None):
+            raise ValueError("pass samples or grid")
+        if not isinstance(voice_id, str) or not voice_id or voice_id in VOICE_MAP:
+            raise ValueError(f"voice id {voice_id!r} is empty or names a preset voice")
+        return self._run_job({"voice_id": voice_id, "samples": samples, "grid": grid, "system_prompt": system_prompt, "name": name})
+
+    def encode_speaker(self, samples, system_prompt: Optional[str] = None) -> np.ndarray:
+        """The speaker grid of ``samples`` (``SmolTTS.create_speaker``), encoded on the worker thread between ticks."""
+        return self._run_job({"voice_id": None, "samples": samples, "grid": None, "system_prompt": system_prompt, "name": None})
+
+    def _run_job(self, job: dict):
+        job.update(done=threading.Event(), result=None, error=None)
+        if self._dead is not None or self._draining:
+            raise RuntimeError(f"scheduler is not running: {self._dead or 'shutting down'}")
+        self._jobs.put(job)
+        self._wake.set()
+        while not job["done"].wait(timeout=0.1):
+            if self._dead is not None and not job["done"].is_set():
+                raise RuntimeError(f"scheduler is not running: {self._dead}")
+        if job["error"] is not None:
+            raise job["error"]
+        return job["result"]
+
+    def remove_voice(self, voice_id: str) -> None:
+        """Forget a registered voice (``KeyError`` if there is none).  Requests already submitted for it keep its prefix."""
+        del self._voices[voice_id]
+
+    def voices(self) -> Dict[str, dict]:
+        """Registered voices: id -> {"name", "prompt_positions"}."""
+        return {k: {"name": v.name, "prompt_positions": int(v.grid.shape[1])} for k, v in list(self._voices.items())}
+
     def close(self, drain: bool = False, timeout: float = 300.0) -> None:
         """Stop the worker.  ``drain``: take no new requests but finish the ones in the books first (a server shutting down);
         otherwise requests in flight are answered with an error."""
@@ -193,7 +248,7 @@ class BatchScheduler:
         self._stop.set()
         self._wake.set()
         self._thread.join(timeout=30)
-        for name in ("_batch_codec", "_stream_codec", "_stream_rs"):
+        for name in ("_batch_codec", "_stream_codec", "_stream_rs", "_scratch"):
             if getattr(self, name) is not None:
                 getattr(self, name).close()
                 setattr(self, name, None)
@@ -295,9 +350,16 @@ class BatchScheduler:
                 continue
             if req.prompt is None:
                 try:
-                    req.prompt = self.tts._get_prompt(req.text, req.voice)
-                    if req.prompt.shape[1] + req.max_new_tokens + 2 > self.session.max_seq:
-                        raise ValueError("prompt + max_new_tokens exceed max_seq_len")
+                    v = req.voice_entry
+                    if v is not None:  # a registered voice: its speaker turns' KV rows are installed, its own turns prefilled at P
+                        P = int(v.grid.shape[1])
+                        req.prompt = self.tts.prompt_encoder.build_prompt(req.text, req.voice, v.grid)[:, P:]
+                        req.pos0, req.prefix = P, v.prefix
+                    else:
+                        req.prompt = self.tts._get_prompt(req.text, req.voice)
+                    if req.pos0 + req.prompt.shape[1] + req.max_new_tokens + 2 > self.session.max_seq:
+                        raise ValueError(f"prompt ({req.pos0} + {req.prompt.shape[1]} positions) + max_new_tokens ({req.max_new_tokens}) "
+                                         f"exceed max_seq_len ({self.session.max_seq})")
                     if min(req.prompt.shape[1], self.prefill_chunk or req.prompt.shape[1]) > self.session.max_rows:
                         raise ValueError("prompt exceeds the session's prefill workspace")
                 except Exception as e:  # bad request: answer it, keep serving
@@ -323,7 +385,12 @@ class BatchScheduler:
             return
         if side:
             try:
-                h = self.session.side_park([r.prompt for r in new], [r.slot for r in new])  # queued behind the ticks so far
+                if any(r.prefix is not None for r in new):  # the voices' prefix rows go in first, in one launch, then the park at P + T - 1
+                    h = self.session.side_park([r.prompt for r in new], [r.slot for r in new], pos0=[r.pos0 for r in new],
+                                               prefixes=[r.prefix for r in new])
+                    self._counts["prefix_installs"] += sum(1 for r in new if r.prefix is not None)
+                else:
+                    h = self.session.side_park([r.prompt for r in new], [r.slot for r in new])  # queued behind the ticks so far
             except Exception as e:
                 for r in new:
                     self._end(r, e)
@@ -349,6 +416,9 @@ class BatchScheduler:
             self._slot_sampling[b] = entries[b]
 
     def _prefill(self, new: List[_Request]) -> None:
+        if any(r.prefix is not None for r in new):
+            self._prefill_prefixed(new)
+            return
         if self.prefill_chunk:
             # long prompts (voice-clone speakers) enter in chunks; the slots already speaking get a tick in between
             def between():
@@ -361,6 +431,82 @@ class BatchScheduler:
         else:
             # frame 0 of the new slots comes out of the next tick's first frame (no separate tail for all slots)
             self.session.prefill([r.prompt for r in new], slots=[r.slot for r in new], stop_on_eos=True, defer_frame0=True)
+
+    def _prefill_prefixed(self, new: List[_Request]) -> None:
+        """In-line admission with registered voices among the requests: their prefixes are installed in one launch, then every
+        prompt (a registered voice's: its own turns only) is prefilled from its pos0."""
+        prefixes = [r.prefix for r in new]
+        pos0 = [r.pos0 for r in new]
+        if self.prefill_chunk:
+            def between():
+                if self._active:
+                    self._tick_and_snapshot()
+                    self._consume_snapshots(keep=1)
+
+            self.session.prefill_chunked([r.prompt for r in new], slots=[r.slot for r in new], stop_on_eos=True, chunk=self.prefill_chunk,
+                                         between=between, defer_frame0=True, pos0=pos0, prefixes=prefixes)
+        else:
+            self.session.install_prefix([p for p in prefixes if p is not None], [r.slot for r in new if r.prefix is not None])
+            self.session.prefill([r.prompt for r in new], slots=[r.slot for r in new], stop_on_eos=True, defer_frame0=True, pos0=pos0)
+        self._counts["prefix_installs"] += sum(1 for p in prefixes if p is not None)
+
+    # ------------------------------------------------------------------ worker: voice registrations
+    def _job_step(self) -> None:
+        """One step of the registration in progress (or of the next one waiting): the encode, then one prefill chunk of the
+        speaker grid per step; the worker runs a tick of the speaking slots between steps."""
+        if self._job is None:
+            if self._jobs.empty():
+                return
+            job = self._jobs.get_nowait()
+            self._job = {"job": job, "steps": self._voice_steps(job)}
+        job = self._job["job"]
+        try:
+            next(self._job["steps"])
+            return
+        except StopIteration:
+            pass
+        except Exception as e:  # (ValueError: a voice this engine cannot serve; the caller answers it, the worker goes on)
+            job["error"] = e
+        self._job = None
+        job["done"].set()
+
+    def _voice_steps(self, job):
+        from ..engine import LMSession, SmolttsError
+
+        grid = job["grid"]
+        if grid is None:
+            try:
+                grid = self.tts.create_speaker(job["samples"], job["system_prompt"])
+            except SmolttsError as e:  # the encoder refuses the audio (e.g. beyond its position limit): the client's input
+                raise ValueError(f"cannot encode the samples: {e}") from e
+            if job["voice_id"] is None:  # (encode_speaker)
+                job["result"] = grid
+                return
+            yield
+        grid = np.ascontiguousarray(np.asarray(grid, dtype=np.int32))
+        H = self.session.H
+        if grid.ndim != 2 or grid.shape[0] != H or grid.shape[1] < 1:
+            raise ValueError(f"speaker grid must be ({H}, P>=1), got {grid.shape}")
+        P = int(grid.shape[1])
+        cfg = self.tts.config
+        if grid[0].min() < 0 or grid[0].max() >= cfg.vocab_size or grid[1:].min() < 0 or grid[1:].max() >= cfg.codebook_size:
+            raise ValueError("speaker grid ids out of range")
+        T_min = int(self.tts.prompt_encoder.build_prompt("", job["voice_id"], grid).shape[1]) - P  # a request's own turns, empty text
+        if P + T_min + self.settings.max_new_tokens + 2 > self.session.max_seq:
+            raise ValueError(f"speaker prompt of P={P} positions leaves no room for a request: P + {T_min} (an empty request) + "
+                             f"max_new_tokens {self.settings.max_new_tokens} + 2 > max_seq_len {self.session.max_seq}")
+        chunk = self.prefill_chunk or 128
+        if self._scratch is None:
+            self._scratch = LMSession(self.tts.lm, 1, max_seq=self.session.max_seq, max_rows=chunk, max_frames=1,
+                                      kv_dtype=self.session.kv_dtype)
+        # the speaker grid alone, as non-final chunks (what a direct chunked prefill of the voice's prompts writes into a slot)
+        for a in range(0, P, chunk):
+            self._scratch.prefill([grid[:, a: a + chunk]], [0], pos0=[a], final=False)
+            if a + chunk < P:
+                yield
+        prefix = self._scratch.save_prefix(0, P)  # on the frame stream: every later install is queued behind it
+        self._voices[job["voice_id"]] = _Voice(job["voice_id"], grid, prefix, job["name"])
+        job["result"] = {"voice_id": job["voice_id"], "prompt_positions": P}
 
     # ------------------------------------------------------------------ worker: ticks and snapshots
     def _tick_and_snapshot(self) -> None:
@@ -675,10 +821,13 @@ class BatchScheduler:
             self._side_stream = torch.cuda.Stream()
             with torch.cuda.stream(compute):
                 while not self._stop.is_set():
+                    self._job_step()  # a voice registration: at most one prefill chunk between two ticks
                     self._admit()
                     if not self._active:
                         if self._side is not None:  # (its slots are the only ones taken: nothing to run beside)
                             self._side_advance()
+                            continue
+                        if self._job is not None or not self._jobs.empty():
                             continue
                         self._consume_snapshots(keep=0)
                         self._decode_finished(force=True)
@@ -720,12 +869,19 @@ class BatchScheduler:
         """Counters since start (served by ``GET /v1/stats``): requests by outcome, audio frames handed to clients, ticks,
         slots in use, queue length."""
         up = time.time() - self._t0
-        return dict(self._counts, ticks=self._tick_no, frames_per_tick=self.tick, slots=self.B, active=len(self._active),
+        return dict(self._counts, ticks=self._tick_no, frames_per_tick=self.tick, slots=self.B, active=len(self._active), voices=len(self._voices),
                     queued=self._pending.qsize(), awaiting_codec=len(self._finished) + sum(1 for j in self._codec_jobs if j is not None), uptime_s=up, gpu_wait_s=self._gpu_wait_s,
                     delivered_frames_per_s=self._counts["frames_delivered"] / up if up > 0 else 0.0)
 
     def _fail_all(self, e: Exception) -> None:
         self._dead = e
+        jobs = [self._job["job"]] if self._job is not None else []
+        self._job = None
+        while not self._jobs.empty():
+            jobs.append(self._jobs.get_nowait())
+        for job in jobs:
+            job["error"] = RuntimeError(f"scheduler is not running: {e}")
+            job["done"].set()
         if self._held is not None:
             self._end(self._held, e)
             self._held = None

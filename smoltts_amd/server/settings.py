@@ -1,7 +1,7 @@
 """The server's settings file, same schema and validation as the reference (server/settings.py:12-63): exactly one of
 ``model_id`` / ``checkpoint_dir``, a ``generation`` block (lm/generate.py:12-16) and a ``model_type`` block
 (lm/config.py:5-12).  Extensions of this build: ``mimi_checkpoint`` (the reference downloads kyutai/mimi; there is no
-network here), ``max_batch`` (slots per GPU), ``weight_format`` ("bf16" | "fp8").  ``model_id`` is accepted by the schema
+network here), ``max_batch`` (slots per GPU), ``weight_format`` ("bf16" | "fp8"), ``max_voices`` (cloned voices held at once).  ``model_id`` is accepted by the schema
 but cannot be resolved without network access; ``get_checkpoint_dir`` says so."""
 from __future__ import annotations
 
@@ -45,6 +45,9 @@ class ServerSettings(BaseModel):
     # (not in the reference's settings) bf16x3 products per operand pair in the codec's matrix-core kernels: 6 = fp32-grade (the
     # reference's codec runs fp32), 3 = the 2^-16-grade form: chunks 23 % faster, PCM RMS error 7e-7 (SMOLTTS_MIMI_OPT_PRODUCTS)
     codec_products: Literal[3, 6] = 6
+    # (extension) cloned voices a server holds at once (POST /v1/voices/add); each costs its speaker prompt's KV rows on every GPU,
+    # P x 20 KB at 150m (P: about 12.5 positions per second of reference audio, plus the transcripts)
+    max_voices: int = Field(default=64, ge=0)
 
     model_config = {"protected_namespaces": ()}
 
