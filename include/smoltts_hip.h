@@ -504,6 +504,41 @@ int smoltts_resampler_reset_slots(SmolttsResampler* r, const int32_t* slots_host
 int smoltts_resample_chunk(SmolttsResampler* r, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
                            const int32_t* valid_in_dev, void* out_dev, int64_t out_stride, int32_t* counts_dev, void* stream);
 
+/* ------------------------------------------------------------------------------ Speaking speed
+ * A pitch-preserving time stretch of the codec's 24 kHz fp32 PCM, chunk by chunk (smoltts_amd/csrc/tsm.hip, DESIGN.md
+ * section 11; the numpy model is smoltts_amd/tsm.py): WSOLA with hop L = 240, a periodic Hann of W = 480 and an integer-exact
+ * search over the lags [-192, 192], speed carried as speed_q = round(speed * 65536) in [16384, 262144].  Segment positions are
+ * integer functions of the int16 codes rint(clip(x, -1, 1) * 32767), so the output does not depend on how the input is chunked.
+ * A stream of N input samples gives exactly M = ceil(N 65536 / speed_q) output samples; speed_q 65536 is the identity and turns
+ * a slot off. */
+typedef struct SmolttsTsm SmolttsTsm;
+
+/* Device slab of a stretcher for max_batch slots (256-byte aligned, caller-owned): the window, each slot's speed, and two copies
+ * of each slot's stream state (2048 input samples of history, the open half-window, int64 counters).  Every slot starts off.
+ * create uploads the window synchronously. */
+size_t smoltts_tsm_bytes(int32_t max_batch);
+int smoltts_tsm_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsTsm** out);
+void smoltts_tsm_destroy(SmolttsTsm* t);
+/* Output samples per row that a call of n_in input samples needs (any speed, flush included). */
+size_t smoltts_tsm_out_samples(int32_t n_in);
+
+/* Start new streams in the listed slots (host arrays) at their speed_q (65536: the slot is off); the other slots' streams
+ * continue.  Stream-ordered. */
+int smoltts_tsm_reset_slots(SmolttsTsm* t, const int32_t* slots_host, const int32_t* speed_q_host, int32_t n_slots, void* stream);
+
+/* One launch for slots [0, batch): slot b consumes valid_in_dev[b] (clamped to [0, n_in]; NULL = n_in) samples of pcm_dev float
+ * [batch][pcm_stride]; last_dev[b] nonzero (NULL = none) ends the slot's stream with them and flushes it.  Slot b writes the
+ * output samples that became final in this call to out_dev float [batch][out_stride] (out_stride >= smoltts_tsm_out_samples(n_in))
+ * and their number to counts_dev[b]; slots that are off, or flushed before, write 0.  Calls on one stretcher must be ordered on
+ * one stream (the slot states alternate between their two copies). */
+int smoltts_tsm_chunk(SmolttsTsm* t, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
+                      const int32_t* valid_in_dev, const int32_t* last_dev, float* out_dev, int64_t out_stride,
+                      int32_t* counts_dev, void* stream);
+
+/* Tests and tools: slot's current state (k = next segment, p_{k-1}, input consumed, output emitted, flushed) into
+ * state_host[5]; synchronises the stream. */
+int smoltts_tsm_slot_state(SmolttsTsm* t, int32_t slot, int64_t* state_host, void* stream);
+
 /* --------------------------------------------------------------- operator-level test entry points */
 enum {  /* prologue applied to the activation operand */
   SMOLTTS_PRO_NONE = 0,

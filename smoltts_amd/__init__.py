@@ -150,12 +150,22 @@ class SmolTTS:
             print(f"Decoded {F_} frames to PCM in {self.last_stats['codec_ms']:.1f} ms")
         return pcm
 
-    def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None):
+    def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None,
+                 speed: Optional[float] = None):
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
-        (per-request temperature / min_p / seed, as in ``generate_codes``)."""
+        (per-request temperature / min_p / seed, as in ``generate_codes``).  ``speed`` (0.25 to 4.0; None / 1.0: unchanged):
+        the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples."""
+        from .tsm import parse_speed
+
+        sq = parse_speed(speed)  # a bad speed is refused before any work
         codes = self.generate_codes([input], [voice if voice is not None else "heart"], generation_settings,
                                     speakers=None if speaker is None else [speaker], sampling=sampling)[0]
-        return self.decode_codes(codes)
+        pcm = self.decode_codes(codes)
+        if sq is None:
+            return pcm
+        from .engine import stretch_pcm
+
+        return stretch_pcm(pcm, sq, self.lm.device)
 
     # -- voice-clone prompts (``create_speaker``, __init__.py:97-118)
     def encode_audio(self, audio) -> "np.ndarray":
@@ -189,7 +199,8 @@ class SmolTTS:
         return np.concatenate(turns, axis=1).astype(np.int32)
 
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
-               reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None) -> Iterator["np.ndarray"]:
+               reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None,
+               speed: Optional[float] = None) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -201,13 +212,17 @@ class SmolTTS:
         ``output_format``: ``pcm_8000`` / ``pcm_16000`` / ``pcm_22050`` / ``pcm_44100`` / ``pcm_48000`` (int16 chunks) or
         ``ulaw_8000`` (uint8 chunks), converted on the GPU chunk by chunk; over the utterance they concatenate to
         ``scipy.signal.resample_poly`` of the float32 stream, quantised (formats.py).  ``None`` / ``pcm_24000``: float32.
-        ``sampling``: a ``config.RequestSampling`` (as in ``generate_codes``); it is resolved when the generator starts."""
+        ``sampling``: a ``config.RequestSampling`` (as in ``generate_codes``); it is resolved when the generator starts.
+        ``speed`` (0.25 to 4.0; None / 1.0: unchanged): the stream is time-stretched on the GPU in front of the conversion; each
+        chunk holds the samples that became final with its frame (none for some frames: no chunk then)."""
         import numpy as np
 
         from .formats import parse_stream_format
+        from .tsm import parse_speed
 
         if output_format is not None:
             parse_stream_format(output_format)  # an unknown format is refused before any work
+        sq = parse_speed(speed)
 
         from .engine import LMSession, MimiSession
         from .generate import _apply_sampling, _apply_slot_sampling, resolve_sampling, stream_pcm
@@ -226,7 +241,7 @@ class SmolTTS:
             _apply_slot_sampling(sess, [0], resolved)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
-            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=output_format)
+            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=output_format, speed_q=sq)
         finally:
             msess.close()
             sess.close()

@@ -116,6 +116,8 @@ _EXPORTS = [
     "smoltts_mimi_encode_workspace_bytes", "smoltts_mimi_encode", "smoltts_mimi_session_set_option",
     "smoltts_resample_design", "smoltts_resampler_bytes", "smoltts_resampler_create", "smoltts_resampler_destroy",
     "smoltts_resampler_out_bytes", "smoltts_resampler_reset_slots", "smoltts_resample_chunk",
+    "smoltts_tsm_bytes", "smoltts_tsm_create", "smoltts_tsm_destroy", "smoltts_tsm_out_samples", "smoltts_tsm_reset_slots",
+    "smoltts_tsm_chunk", "smoltts_tsm_slot_state",
     "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows",
     "smoltts_prefix_kv_bytes", "smoltts_session_save_prefix", "smoltts_session_install_prefix",
 ]
@@ -218,6 +220,17 @@ def load_library(path: Optional[Path] = None):
     lib.smoltts_resampler_reset_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.smoltts_resample_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_void_p]
+    lib.smoltts_tsm_bytes.argtypes = [C.c_int32]
+    lib.smoltts_tsm_bytes.restype = C.c_size_t
+    lib.smoltts_tsm_out_samples.argtypes = [C.c_int32]
+    lib.smoltts_tsm_out_samples.restype = C.c_size_t
+    lib.smoltts_tsm_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.smoltts_tsm_destroy.argtypes = [C.c_void_p]
+    lib.smoltts_tsm_destroy.restype = None
+    lib.smoltts_tsm_reset_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.smoltts_tsm_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_void_p]
+    lib.smoltts_tsm_slot_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.smoltts_prefix_kv_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.smoltts_prefix_kv_bytes.restype = C.c_size_t
     lib.smoltts_session_save_prefix.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(PrefixHeader), C.c_void_p]
@@ -958,9 +971,11 @@ class Resampler:
         for b, p in zip(slots, parsed):
             self.formats[b] = p
 
-    def new_outputs(self, batch: int):
-        """Device buffers of one call: (bytes uint8 [batch, out_stride], counts int32 [batch, 2])."""
-        return (torch.empty(batch, self.out_stride, dtype=torch.uint8, device=self.device),
+    def new_outputs(self, batch: int, n_in: Optional[int] = None):
+        """Device buffers of one call: (bytes uint8 [batch, out_stride], counts int32 [batch, 2]); ``n_in``: size them for calls of
+        at most that many input samples instead of ``max_in``."""
+        stride = self.out_stride if n_in is None else int(self.lib.smoltts_resampler_out_bytes(n_in))
+        return (torch.empty(batch, stride, dtype=torch.uint8, device=self.device),
                 torch.empty(batch, 2, dtype=torch.int32, device=self.device))
 
     def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
@@ -968,7 +983,8 @@ class Resampler:
         ``valid``: device int32 [batch], the samples of each row that are real (the rest is not consumed)."""
         batch = pcm.shape[0]
         assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and batch <= self.B and 0 <= n_in <= min(self.max_in, pcm.shape[1])
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[0] >= batch and out.shape[1] >= self.out_stride
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[0] >= batch
+        assert out.shape[1] >= int(self.lib.smoltts_resampler_out_bytes(n_in))
         assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 2 * batch
         assert valid is None or (valid.dtype == torch.int32 and valid.is_contiguous() and valid.numel() >= batch)
         check(self.lib.smoltts_resample_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1],
@@ -996,3 +1012,92 @@ class Resampler:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------------- speaking speed
+class TimeStretcher:
+    """Per-slot pitch-preserving time stretch of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Speaking speed";
+    the numpy model is ``tsm.Stretcher``): one launch per call for every slot, each at its own speed.  Slots start off;
+    ``reset_slots`` starts a new stream in a slot at its ``speed_q`` (65536: off)."""
+
+    def __init__(self, device: torch.device, max_batch: int):
+        self.lib = load_library()
+        self.device, self.B = device, max_batch
+        need = self.lib.smoltts_tsm_bytes(max_batch)
+        if need == 0:
+            raise SmolttsError("smoltts_tsm_bytes returned 0 (bad sizes)")
+        self.slab = _alloc_slab(need, device, settle=True)
+        h = C.c_void_p()
+        check(self.lib.smoltts_tsm_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_tsm_create")
+        self.handle = h
+        self.speed_q = [65536] * max_batch
+
+    def out_samples(self, n_in: int) -> int:
+        """Output samples per row that a call of ``n_in`` input samples needs."""
+        return int(self.lib.smoltts_tsm_out_samples(int(n_in)))
+
+    def reset_slots(self, slots: Sequence[int], speed_q: Sequence[int]) -> None:
+        n = len(slots)
+        arr = lambda v: (C.c_int32 * n)(*[int(x) for x in v])  # noqa: E731
+        check(self.lib.smoltts_tsm_reset_slots(self.handle, arr(slots), arr(speed_q), n, current_stream_ptr()), "smoltts_tsm_reset_slots")
+        for b, q in zip(slots, speed_q):
+            self.speed_q[b] = int(q)
+
+    def new_outputs(self, batch: int, n_in: int):
+        """Device buffers of one call of at most ``n_in`` input samples: (fp32 [batch, out_samples(n_in)], counts int32 [batch])."""
+        return (torch.empty(batch, self.out_samples(n_in), dtype=torch.float32, device=self.device),
+                torch.empty(batch, dtype=torch.int32, device=self.device))
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
+              last: Optional[torch.Tensor] = None) -> None:
+        """Stretch ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream.
+        ``valid``: device int32 [batch], the samples of each row that are real; ``last``: device int32 [batch], nonzero where the
+        row's stream ends with this call (the slot flushes).  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
+        batch = pcm.shape[0]
+        assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and batch <= self.B and 0 <= n_in <= pcm.shape[1]
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= batch and out.shape[1] >= self.out_samples(n_in)
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= batch
+        for t in (valid, last):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= batch)
+        check(self.lib.smoltts_tsm_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(last), dptr(out),
+                                         out.shape[1], dptr(counts), current_stream_ptr()), "smoltts_tsm_chunk")
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s counters (synchronises the current stream): k (next segment), p_prev, n_in, n_out, ended."""
+        v = (C.c_int64 * 5)()
+        check(self.lib.smoltts_tsm_slot_state(self.handle, int(slot), v, current_stream_ptr()), "smoltts_tsm_slot_state")
+        return dict(zip(("k", "p_prev", "n_in", "n_out", "ended"), list(v)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize()
+            self.lib.smoltts_tsm_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device) -> np.ndarray:
+    """A whole utterance (float32 at 24 kHz) stretched on ``device`` (the model's) in one call with ``last`` set: exactly
+    ``tsm.out_length(len(pcm), speed_q)`` samples (``SmolTTS.__call__``).  Waits for the result.  ``speed_q == 65536`` returns
+    ``pcm`` untouched."""
+    pcm = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    if speed_q == 65536:
+        return pcm
+    with torch.cuda.device(device):
+        ts = TimeStretcher(device, 1)
+        try:
+            ts.reset_slots([0], [speed_q])
+            n = int(pcm.size)
+            x = torch.from_numpy(pcm).to(device)[None] if n else torch.zeros(1, 1, dtype=torch.float32, device=device)
+            out, counts = ts.new_outputs(1, n)
+            last = torch.ones(1, dtype=torch.int32, device=device)
+            ts.chunk(x, n, out, counts, last=last)
+            m = int(counts.cpu()[0])
+            return out[0, :m].cpu().numpy()
+        finally:
+            ts.close()

@@ -11,12 +11,14 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import threading
 from typing import Dict, List, Literal, Optional, Union
 
 import numpy as np
 from fastapi import APIRouter, FastAPI, HTTPException, Query, Request, Response
-from fastapi.responses import StreamingResponse
+from fastapi.exceptions import RequestValidationError
+from fastapi.responses import JSONResponse, StreamingResponse
 from pydantic import BaseModel, Field
 
 from ..formats import lin2ulaw
@@ -115,33 +117,38 @@ class TTSCore:
         base = self.model._settings(None) if hasattr(self.model, "_settings") else GenerationSettings()
         return sampling.resolve(base)
 
-    def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000", sampling=None):
-        """-> (bytes, media type, the seed the request sampled with or None)."""
+    def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000", sampling=None,
+                       speed: Optional[float] = None):
+        """-> (bytes, media type, the seed the request sampled with or None).  ``speed``: passed on only when it is not 1."""
         used = None
+        sp = _speed_kw(speed)
         try:
             if self.scheduler is not None:
-                req = self.scheduler.submit(input_text, str(voice), stream=False, **({"sampling": sampling} if sampling is not None else {}))
+                req = self.scheduler.submit(input_text, str(voice), stream=False, **({"sampling": sampling} if sampling is not None else {}), **sp)
                 used = getattr(req, "sampling", None)
                 pcm = np.concatenate(list(self.scheduler.iter_chunks(req)) or [np.zeros(0, np.float32)])
             else:
                 used = self._model_sampling(sampling)
                 kw = {"sampling": used} if used is not None else {}
-                pcm = np.asarray(self.model(input_text, str(voice), **kw)).flatten()
+                pcm = np.asarray(self.model(input_text, str(voice), **kw, **sp)).flatten()
         except ValueError as e:  # a request the engine refuses (e.g. a text too long for max_seq_len): the client's fault, not a 500
             raise HTTPException(status_code=400, detail=str(e))
         return (*self.format_audio_chunk(pcm, response_format), seed_used(used))
 
-    def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None):
+    def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
+                     speed: Optional[float] = None):
         """-> (chunks as bytes, the seed the request samples with or None).  Chunks: float32 at 24 kHz for ``pcm_24000``;
         otherwise the int16 / mu-law samples the model or scheduler converted on the GPU (the format is passed on only when it is
-        not ``pcm_24000``).  The request is submitted here, before the first chunk is asked for."""
+        not ``pcm_24000``).  The request is submitted here, before the first chunk is asked for.  ``speed``: passed on only when
+        it is not 1; the chunks are then the stretched stream (float32 for ``pcm_24000``)."""
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
+        sp = _speed_kw(speed)
         if self.scheduler is not None:
-            req = self.scheduler.submit(input_text, str(voice), stream=True, **kw, **({"sampling": sampling} if sampling is not None else {}))
+            req = self.scheduler.submit(input_text, str(voice), stream=True, **kw, **({"sampling": sampling} if sampling is not None else {}), **sp)
             chunks, used = self.scheduler.iter_chunks(req), getattr(req, "sampling", None)
         else:
             used = self._model_sampling(sampling)
-            chunks = self.model.stream(input_text, str(voice), **kw, **({"sampling": used} if used is not None else {}))
+            chunks = self.model.stream(input_text, str(voice), **kw, **({"sampling": used} if used is not None else {}), **sp)
         return self._stream_bytes(chunks, kw), seed_used(used)
 
     def _stream_bytes(self, chunks, kw):
@@ -177,6 +184,14 @@ class TTSCore:
         return pcm_to_wav_bytes(pcm_data, sample_rate), "audio/wav"
 
 
+def _speed_kw(speed) -> dict:
+    """``{"speed": speed}`` for a speed other than 1 (``ValueError`` out of range), else nothing: a request that names no speed
+    reaches the model exactly as before."""
+    from ..tsm import parse_speed
+
+    return {} if speed is None or parse_speed(speed) is None else {"speed": float(speed)}
+
+
 def seed_used(sampling) -> Optional[int]:
     """The seed of a request that samples (its ``X-Seed``), or None: greedy, or no sampling known."""
     if sampling is None or sampling.seed is None:
@@ -205,16 +220,33 @@ class SamplingFields(BaseModel):
         return RequestSampling(self.temperature, self.fast_temperature, self.min_p, self.seed)
 
 
+# speaking speed (OpenAI's ``speed``, ElevenLabs' ``voice_settings.speed``): pitch-preserving time stretch on the GPU (tsm.py);
+# an explicit null is speed 1, as an omitted field (such bodies were answered before speed was honoured, and still are)
+SpeedField = Field(default=None, ge=0.25, le=4.0, allow_inf_nan=False)
+
+
 class SpeechRequest(SamplingFields):
     model: str = Field(default="tts-1-hd")
     input: str
     voice: Union[str, int] = Field(default="alloy")
     response_format: Literal["wav"] = Field(default="wav")
+    speed: Optional[float] = SpeedField
+
+
+class VoiceSettings(BaseModel):
+    """ElevenLabs' ``voice_settings``: ``speed`` is honoured; the other fields (stability, similarity_boost, ...) are accepted
+    and ignored."""
+    speed: Optional[float] = SpeedField
 
 
 class CreateSpeechRequest(SamplingFields):
     text: str
     model_id: Optional[str] = Field(default=None)
+    voice_settings: Optional[VoiceSettings] = Field(default=None)
+
+    @property
+    def speed(self) -> Optional[float]:
+        return None if self.voice_settings is None else self.voice_settings.speed
 
 
 openai_router = APIRouter(prefix="/v1", tags=["OpenAI"])
@@ -224,7 +256,8 @@ eleven_router = APIRouter(prefix="/v1", tags=["ElevenLabs"])
 @openai_router.post("/audio/speech")
 def openai_speech(item: SpeechRequest, http_request: Request):
     core = http_request.app.state.tts_core
-    audio, media_type, seed = core.generate_audio(item.input, item.voice, item.response_format + "_24000", sampling=item.request_sampling())
+    audio, media_type, seed = core.generate_audio(item.input, item.voice, item.response_format + "_24000", sampling=item.request_sampling(),
+                                                  speed=item.speed)
     return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed)})
 
 
@@ -233,7 +266,7 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
                                   output_format: Optional[str] = Query(None, description="pcm_<rate> | wav_<rate>")):
     core = http_request.app.state.tts_core
     fmt = output_format or "wav_24000"
-    content, media_type, seed = core.generate_audio(item.text, voice_id, fmt, sampling=item.request_sampling())
+    content, media_type, seed = core.generate_audio(item.text, voice_id, fmt, sampling=item.request_sampling(), speed=item.speed)
     return Response(content=content, media_type=media_type, headers={
         "Content-Disposition": f'attachment; filename="elevenlabs_speech.{fmt.split("_")[0]}"',
         "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed)})
@@ -245,7 +278,8 @@ def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
     """pcm_24000: raw float32 (the reference's stream); pcm_<rate>: int16 little-endian; ulaw_8000: G.711 mu-law bytes."""
     core = http_request.app.state.tts_core
     kind, rate = output_format.split("_")
-    chunks, seed = core.stream_audio(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling())
+    chunks, seed = core.stream_audio(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling(),
+                                     speed=item.speed)
     return StreamingResponse(chunks, media_type="audio/wav", headers={
         "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed)})
 
@@ -312,6 +346,24 @@ def stats(http_request: Request):
     return sched.stats() if sched is not None and hasattr(sched, "stats") else {}
 
 
+def _finite(v):
+    if isinstance(v, float) and not math.isfinite(v):
+        return str(v)
+    if isinstance(v, dict):
+        return {k: _finite(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_finite(x) for x in v]
+    return v
+
+
+async def _validation_error(request, exc):
+    """FastAPI's 422 answer, also for a body with NaN / Infinity (a speed of NaN): the echoed input is written as a string
+    instead of failing the JSON encoding with a 500."""
+    from fastapi.encoders import jsonable_encoder
+
+    return JSONResponse(status_code=422, content={"detail": _finite(jsonable_encoder(exc.errors()))})
+
+
 def create_app(model=None, settings: Optional[dict] = None, scheduler=None) -> FastAPI:
     """``model``: a ``smoltts_amd.SmolTTS`` (or any object with ``__call__``/``stream``); ``scheduler``: an
     optional ``BatchScheduler`` so that concurrent requests are decoded together (handlers are plain
@@ -328,6 +380,7 @@ def create_app(model=None, settings: Optional[dict] = None, scheduler=None) -> F
                 scheduler.close()
 
     app = FastAPI(lifespan=lifespan)
+    app.add_exception_handler(RequestValidationError, _validation_error)
     app.include_router(openai_router)
     app.include_router(eleven_router)
     app.state.settings = settings

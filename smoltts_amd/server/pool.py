@@ -105,7 +105,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
                 continue
             if msg[0] == "submit":
                 _, rid, text, voice, stream, max_new_tokens = msg[:6]
-                extra = msg[6] if len(msg) > 6 else {}  # (output_format / sampling, only when set)
+                extra = msg[6] if len(msg) > 6 else {}  # (output_format / sampling / speed, only when set)
                 req = sched.submit(text, voice, stream=stream, max_new_tokens=max_new_tokens, **extra)
                 with lock:
                     live[rid] = req
@@ -184,11 +184,15 @@ class GpuPool:
 
     # ------------------------------------------------------------------ client side (the BatchScheduler interface)
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None, sampling=None) -> _PoolRequest:
+               output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None) -> _PoolRequest:
         if output_format is not None:  # refused here, before a worker sees it
             from ..formats import parse_stream_format
 
             parse_stream_format(output_format)
+        if speed is not None:  # (likewise; speed 1.0 is not passed on)
+            from ..tsm import parse_speed
+
+            speed = None if parse_speed(speed) is None else float(speed)
         if sampling is not None or self._settings is not None:  # the seed is drawn here: the same on whichever worker serves it
             import dataclasses
 
@@ -210,7 +214,7 @@ class GpuPool:
             self._reqs[req.rid] = req
             self._load[w] += 1
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
-        extra = {k: v for k, v in (("output_format", output_format), ("sampling", sampling)) if v is not None}
+        extra = {k: v for k, v in (("output_format", output_format), ("sampling", sampling), ("speed", speed)) if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 

@@ -51,6 +51,8 @@ class _Request:
     voice_entry: object = None  # _Voice of a registered voice, taken at submit (a later remove_voice does not affect the request)
     pos0: int = 0             # position of the prompt's first column: the voice's prefix length P for a registered voice
     prefix: object = None     # engine.PrefixKV installed into the slot at admission (None: the whole prompt is prefilled)
+    speed_q: Optional[int] = None  # speaking speed in Q16 (tsm.py), time-stretched on the GPU; None: speed 1, no stretch
+    stretch_in: list = field(default_factory=list)  # blocking requests with a speed: the utterance's PCM until its last pass
 
 
 @dataclass
@@ -66,6 +68,15 @@ class _CodecJob:
     req: _Request
     cols: np.ndarray  # (F, n_codebooks) int32 audio codes of the complete utterance
     done: int = 0     # frames already handed to the codec
+
+
+def _to_host(conv):
+    """Queue the host copies of a pass's converted outputs (``BatchScheduler._convert``; stages that did not run stay None)."""
+    return None if conv is None else tuple(t.to("cpu", non_blocking=True) if t is not None else None for t in conv)
+
+
+def _numpy(conv):
+    return None if conv is None else tuple(t.numpy() if t is not None else None for t in conv)
 
 
 class BatchScheduler:
@@ -124,6 +135,10 @@ class BatchScheduler:
         self._codec_wait = 0                    # ticks since the last pass while work was waiting
         self._stream_codec = None               # codec session whose slot b carries the stream of LM slot b (streaming requests)
         self._stream_rs = None                  # engine.Resampler beside it: slot b converts the stream of LM slot b when it has a format
+        self._stream_ts = None                  # engine.TimeStretcher in front of it: slot b stretches LM slot b's stream when it has a speed
+        self._block_ts = None                   # one-slot stretcher of the blocking requests' whole utterances
+        self._stretches: List[dict] = []        # blocking utterances with a speed, complete, being stretched (_poll_stretches)
+        self._stretch_flight = None             # the stretch call in flight: (event, host output, host counts, keep-alive, [(job, slot)])
         self._codec_age = [0] * max_batch       # codec passes each of its slots has seen since that slot's last reset
         self._deliveries: List[tuple] = []      # (event, pcm on the device, [(request, first sample, n samples, last?)]) in order
         self._snaps: List[tuple] = []           # snapshots of the output ring the host has not looked at yet (oldest first)
@@ -143,12 +158,17 @@ class BatchScheduler:
 
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None, sampling=None) -> _Request:
+               output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None) -> _Request:
         """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
         in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
-        a seed gets one here.  The resolved value is ``request.sampling``; its seed replays the request."""
+        a seed gets one here.  The resolved value is ``request.sampling``; its seed replays the request.
+        ``speed`` (0.25 to 4.0, ``ValueError`` otherwise; None / 1.0: unchanged): pitch-preserving time stretch on the GPU
+        (tsm.py).  A stream is stretched in its codec pass in front of the format conversion, a blocking utterance as a whole."""
         from ..config import RequestSampling
+        from ..tsm import parse_speed
+
+        speed_q = parse_speed(speed)
 
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         if output_format is not None:
@@ -163,7 +183,7 @@ class BatchScheduler:
         if self._draining:
             raise RuntimeError("scheduler is not running: shutting down")
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
-                       output_format=output_format, sampling=resolved, voice_entry=self._voices.get(voice))
+                       output_format=output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=speed_q)
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
@@ -243,12 +263,12 @@ class BatchScheduler:
             self._draining = True
             deadline = time.time() + timeout
             while (self._thread.is_alive() and time.time() < deadline and
-                   (self._active or self._side is not None or self._retiring or self._held is not None or not self._pending.empty() or self._codec_backlog() or self._deliveries)):
+                   (self._active or self._side is not None or self._retiring or self._held is not None or not self._pending.empty() or self._codec_backlog() or self._deliveries or self._stretches)):
                 time.sleep(0.01)
         self._stop.set()
         self._wake.set()
         self._thread.join(timeout=30)
-        for name in ("_batch_codec", "_stream_codec", "_stream_rs", "_scratch"):
+        for name in ("_batch_codec", "_stream_codec", "_stream_rs", "_stream_ts", "_block_ts", "_scratch"):
             if getattr(self, name) is not None:
                 getattr(self, name).close()
                 setattr(self, name, None)
@@ -286,8 +306,14 @@ class BatchScheduler:
                 self._stream_codec.reset()
             if self._stream_rs is None and any(r.output_format for r in new if r.stream):
                 from ..engine import Resampler
+                from ..tsm import out_bound
 
-                self._stream_rs = Resampler(self.session.engine.device, self.B, max(self.tick, 1) * 1920)  # every slot starts off
+                # (sized for the stretcher's output at speed 0.25; a pass without a speed sizes its buffers for the PCM alone)
+                self._stream_rs = Resampler(self.session.engine.device, self.B, out_bound(max(self.tick, 1) * 1920))  # every slot starts off
+            if self._stream_ts is None and any(r.speed_q for r in new if r.stream):
+                from ..engine import TimeStretcher
+
+                self._stream_ts = TimeStretcher(self.session.engine.device, self.B)  # every slot starts off
             if not self.overlap_stream_codec:  # (overlapped: the slot's stream restarts on the codec stream, right before the pass
                 self._stream_codec.reset_slots(streams)  # of the request's first tick and behind the previous tenant's last pass)
                 self._reset_formats([r for r in new if r.stream])
@@ -299,16 +325,22 @@ class BatchScheduler:
             self._active[r.slot] = r
 
     def _reset_formats(self, reqs: List[_Request]) -> None:
-        """Start the resampler streams of new streaming tenants (a slot without a format is switched off)."""
+        """Start the resampler and stretcher streams of new streaming tenants (a slot without a format / speed is switched off)."""
         if self._stream_rs is not None and reqs:
             self._stream_rs.reset_slots([r.slot for r in reqs], [r.output_format or "pcm_24000" for r in reqs])
+        if self._stream_ts is not None and reqs:
+            self._stream_ts.reset_slots([r.slot for r in reqs], [r.speed_q or 65536 for r in reqs])
 
-    def _convert(self, pcm, n_frames_d, reqs: List[_Request], tick_no: int):
-        """The resample launch of a stream codec pass (current stream, right behind the decode): slot b of a request in ``reqs``
-        consumes the samples of the frames the tick's frame counter ``n_frames_d`` (device) gives it; every other slot none.
-        Returns (bytes, counts) on the device, or None when no request of the pass has a format (no launch)."""
-        rs = self._stream_rs
-        if rs is None or not any(r.output_format for r in reqs):
+    def _convert(self, pcm, n_frames_d, done_d, reqs: List[_Request], tick_no: int):
+        """The stretch and resample launches of a stream codec pass (current stream, right behind the decode): slot b of a request
+        in ``reqs`` consumes the samples of the frames the tick's frame counter ``n_frames_d`` (device) gives it; every other slot
+        none.  A slot with a speed is stretched first, and ends its stream (flushes) in the tick where the host will see it finish,
+        derived from the same snapshot (``n_frames_d``, ``done_d``); the resampler then consumes the stretcher's output.  Returns
+        (bytes, counts, stretched, stretched counts) on the device, None for a stage that did not run, or None when neither ran."""
+        rs, ts = self._stream_rs, self._stream_ts
+        fmt = rs is not None and any(r.output_format for r in reqs)
+        spd = ts is not None and any(r.speed_q for r in reqs)
+        if not (fmt or spd):
             return None
         from ..engine import upload
 
@@ -319,10 +351,27 @@ class BatchScheduler:
             f0[r.slot] = (tick_no - r.first_tick) * self.tick
             cap[r.slot] = r.max_new_tokens + 1
         f0_d, cap_d = upload([f0, cap], self.session.engine.device)
-        valid = ((torch.minimum(n_frames_d.to(torch.int32), cap_d) - f0_d).clamp_(0, self.tick) * 1920).to(torch.int32)
-        out, counts = rs.new_outputs(self.B)
-        rs.chunk(pcm, self.tick * 1920, out, counts, valid=valid)
-        return out, counts
+        n_d = n_frames_d.to(torch.int32)
+        valid = ((torch.minimum(n_d, cap_d) - f0_d).clamp_(0, self.tick) * 1920).to(torch.int32)
+        n_in, src, rs_valid = self.tick * 1920, pcm, valid
+        ts_out = ts_counts = rs_out = rs_counts = None
+        if spd:
+            # the host's `finished` of _drain, on the device: done (with a frame) or the frame budget reached
+            last = ((((done_d != 0) & (n_d > 0)) | (n_d >= cap_d)) & (cap_d > 0)).to(torch.int32)
+            ts_out, ts_counts = ts.new_outputs(self.B, n_in)
+            ts.chunk(pcm, n_in, ts_out, ts_counts, valid=valid, last=last)
+            if fmt:  # the resampler reads the stretched rows, and the codec's rows of the slots without a speed
+                plain = [r.slot for r in reqs if r.output_format and not r.speed_q]
+                sped = np.zeros(self.B, np.int32)
+                sped[[r.slot for r in reqs if r.speed_q]] = 1
+                sped_d, plain_d = upload([sped, np.asarray(plain, np.int64)], self.session.engine.device)
+                if plain:
+                    ts_out[plain_d, :n_in] = pcm[plain_d]
+                src, rs_valid, n_in = ts_out, torch.where(sped_d != 0, ts_counts, valid), ts_out.shape[1]
+        if fmt:
+            rs_out, rs_counts = rs.new_outputs(self.B, n_in)
+            rs.chunk(src, n_in, rs_out, rs_counts, valid=rs_valid)
+        return rs_out, rs_counts, ts_out, ts_counts
 
     def _admit(self) -> None:
         if self._side is not None and self._side["state"] == "running":
@@ -542,7 +591,7 @@ class BatchScheduler:
             chunk = s.codes[torch.arange(self.B, device="cuda")[:, None], idx][:, :, -nq:].contiguous()
             pcm = torch.empty(self.B, self.tick * 1920, dtype=torch.float32, device="cuda")
             self._stream_codec.decode_chunk(chunk, 0, self.tick, pcm, code_offset=0)
-            conv = self._convert(pcm, s.n_frames, streaming, self._tick_no)
+            conv = self._convert(pcm, s.n_frames, s.done, streaming, self._tick_no)
         else:
             conv = None
         snap = (s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no, pcm, conv)
@@ -559,18 +608,18 @@ class BatchScheduler:
             # the host waits for the snapshot, then copies on the copy stream: a device-side wait would park a blocked barrier
             # packet in a second hardware queue for the whole tick, and the frame graphs' dependent launches get slower for it
             self._wait_event(ev)
-            stream_pass = self._launch_stream_codec(codes_d, n_d, tick_no) if self.overlap_stream_codec else None
+            stream_pass = self._launch_stream_codec(codes_d, n_d, done_d, tick_no) if self.overlap_stream_codec else None
             with torch.cuda.stream(self._copy_stream):
                 codes = codes_d.to("cpu", non_blocking=True)
                 n_frames = n_d.to("cpu", non_blocking=True)
                 done = done_d.to("cpu", non_blocking=True)
                 pcm = pcm_d.to("cpu", non_blocking=True) if pcm_d is not None else None
-                conv = tuple(t.to("cpu", non_blocking=True) for t in conv_d) if conv_d is not None else None
+                conv = _to_host(conv_d)
             self._sync_copies()
             self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), tick_no, None if pcm is None else pcm.numpy(), stream_pass,
-                        None if conv is None else tuple(t.numpy() for t in conv))
+                        _numpy(conv))
 
-    def _launch_stream_codec(self, codes_d, n_d, tick_no: int):
+    def _launch_stream_codec(self, codes_d, n_d, done_d, tick_no: int):
         """The codec pass of the streaming requests for tick ``tick_no``, on the codec stream, from the tick's snapshot of the
         output ring (the host has just seen that snapshot's event, so the next tick is running meanwhile).  Returns
         (pcm on the device, event, what to keep alive, converted bytes and counts on the device or None) or None when no stream was
@@ -603,10 +652,10 @@ class BatchScheduler:
             chunk = codes_d[torch.arange(self.B, device="cuda")[:, None], idx][:, :, -nq:].contiguous()
             pcm = torch.empty(self.B, self.tick * 1920, dtype=torch.float32, device="cuda")
             self._stream_codec.decode_chunk(chunk, 0, self.tick, pcm, code_offset=0)
-            conv = self._convert(pcm, n_d, alive, tick_no)
+            conv = self._convert(pcm, n_d, done_d, alive, tick_no)
             ev = torch.cuda.Event()
             ev.record(self._codec_stream)
-        return pcm, ev, (codes_d, n_d), conv  # (codes_d, n_d: kept alive until the pass has run)
+        return pcm, ev, (codes_d, n_d, done_d), conv  # (codes_d, n_d, done_d: kept alive until the pass has run)
 
     def _wait_event(self, ev) -> None:
         t = time.perf_counter()
@@ -658,8 +707,8 @@ class BatchScheduler:
                         r.stream_done = True
                         release(r)  # the end marker follows the last chunk, in _deliver
                     continue
-                if r.output_format and conv is not None and (k > 0 or finished):
-                    chunk = self._stream_rs.slot_bytes(conv[0], conv[1], slot, tail=finished, output_format=r.output_format)  # (the tail goes out with the last chunk)
+                if (r.output_format or r.speed_q) and conv is not None and (k > 0 or finished):
+                    chunk = self._converted(r, slot, conv, finished)
                     if chunk.size:
                         r.out.put(chunk)
                     self._counts["frames_delivered"] += max(k, 0)
@@ -777,8 +826,10 @@ class BatchScheduler:
         self._deliveries.append((ev, pcm, items, False, None, None))
 
     def _deliver(self, wait: bool) -> None:
-        """Hand finished codec passes to their requests, in order; ``wait``: block on the oldest one."""
+        """Hand finished codec passes to their requests, in order; ``wait``: block on the oldest one.  Finished stretches of
+        blocking utterances go out first (never waited for)."""
         torch = self._torch
+        self._poll_stretches()
         while self._deliveries:
             ev, pcm, items, _, _, conv = self._deliveries[0]
             wait = wait or any(d[3] for d in self._deliveries)  # a stream's first chunk is somewhere in the line: do not dawdle
@@ -789,23 +840,118 @@ class BatchScheduler:
                 self._wait_event(ev)
                 with torch.cuda.stream(self._copy_stream):
                     host = pcm.to("cpu", non_blocking=True)
-                    conv_h = tuple(t.to("cpu", non_blocking=True) for t in conv) if conv is not None else None
+                    conv_h = _to_host(conv)
                 self._sync_copies()
                 host = host.numpy()
-                conv_h = tuple(t.numpy() for t in conv_h) if conv_h is not None else None
+                conv_h = _numpy(conv_h)
             self._deliveries.pop(0)
             for r, b, n, fin in items:
-                if r.output_format and conv_h is not None:
-                    chunk = self._stream_rs.slot_bytes(conv_h[0], conv_h[1], b, tail=fin, output_format=r.output_format)  # (the tail goes out with the last chunk)
+                if r.stream and (r.output_format or r.speed_q) and conv_h is not None:
+                    chunk = self._converted(r, b, conv_h, fin)
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
                         self._counts["frames_delivered"] += n // 1920
+                elif not r.stream and r.speed_q:  # a blocking utterance with a speed: stretched whole once its last pass is in
+                    if n and not r.cancelled:
+                        r.stretch_in.append(host[b, :n].copy())
+                        self._counts["frames_delivered"] += n // 1920
+                    if fin and r.stretch_in and not r.cancelled:
+                        self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
+                        continue
                 elif n and not r.cancelled:
                     r.out.put(host[b, :n].copy())
                     self._counts["frames_delivered"] += n // 1920
                 if fin:
                     self._end(r)
             wait = False
+
+    def _converted(self, r: _Request, b: int, conv, last: bool) -> np.ndarray:
+        """Slot ``b``'s chunk of a stream pass from its host copy ``conv`` (``_convert``): the converted samples (with the
+        resampler's tail when ``last``), or the stretched float32 of a ``pcm_24000`` request with a speed."""
+        if r.output_format:
+            return self._stream_rs.slot_bytes(conv[0], conv[1], b, tail=last, output_format=r.output_format)  # (the tail goes out with the last chunk)
+        return conv[2][b, : int(conv[3][b])].copy()
+
+    STRETCH_SLOTS, STRETCH_PIECE = 16, 65536  # blocking utterances stretched side by side, input samples per slot and call
+
+    def _start_stretch(self, r: _Request) -> None:
+        """A blocking utterance with a speed is complete: it joins the stretch queue (``_poll_stretches`` runs it)."""
+        pcm = np.ascontiguousarray(np.concatenate(r.stretch_in), dtype=np.float32)
+        r.stretch_in = []
+        self._stretches.append({"req": r, "pcm": pcm, "pos": 0, "outs": [], "slot": -1})
+
+    def _poll_stretches(self) -> None:
+        """One step of the blocking utterances' stretches, never waited for.  Up to STRETCH_SLOTS utterances are stretched side by
+        side, one stretcher slot each, in calls of at most STRETCH_PIECE input samples per slot (a call at speed 0.25 is ~9 ms on
+        the GPU), queued on the stretch stream with an event.  A step collects the previous call once its event has fired (the
+        utterances that ended in it go out, each with its end marker) and queues the next one."""
+        from ..engine import TimeStretcher
+
+        torch = self._torch
+        fl = self._stretch_flight
+        if fl is not None:
+            ev, out_h, cnt_h, keep, ran = fl
+            if not ev.query():
+                return
+            out, cnt = out_h.numpy(), cnt_h.numpy()
+            for job, b in ran:
+                if cnt[b]:
+                    job["outs"].append(out[b, : int(cnt[b])].copy())
+            for job in [j for j, _ in ran if j["slot"] == -2]:
+                r = job["req"]
+                if not r.cancelled:
+                    r.out.put(np.concatenate(job["outs"]) if job["outs"] else np.zeros(0, np.float32))
+                self._end(r)
+                self._stretches.remove(job)
+            self._stretch_flight = None
+        for job in [j for j in self._stretches if j["req"].cancelled and j["slot"] == -1]:  # (a running one finishes)
+            self._end(job["req"])
+            self._stretches.remove(job)
+        if not self._stretches:
+            return
+        S, P = self.STRETCH_SLOTS, self.STRETCH_PIECE
+        dev = self.session.engine.device
+        with torch.cuda.stream(self._stretch_stream):
+            if self._block_ts is None:
+                self._block_ts = TimeStretcher(dev, S)
+            ts = self._block_ts
+            used = {j["slot"] for j in self._stretches if j["slot"] >= 0}
+            fresh = []
+            for job in self._stretches:
+                if job["slot"] == -1 and len(used) < S:
+                    job["slot"] = min(set(range(S)) - used)
+                    used.add(job["slot"])
+                    fresh.append(job)
+            if fresh:
+                ts.reset_slots([j["slot"] for j in fresh], [j["req"].speed_q for j in fresh])
+            running = [j for j in self._stretches if j["slot"] >= 0]
+            batch = max(j["slot"] for j in running) + 1
+            n_in = min(P, max(j["pcm"].size - j["pos"] for j in running))
+            x_h = torch.zeros(batch, max(n_in, 1), dtype=torch.float32).pin_memory()
+            ctl_h = torch.zeros(2, batch, dtype=torch.int32).pin_memory()  # valid, last
+            xn, ctl = x_h.numpy(), ctl_h.numpy()
+            ending = []
+            for job in running:
+                b, piece = job["slot"], job["pcm"][job["pos"]: job["pos"] + n_in]
+                xn[b, : piece.size] = piece
+                job["pos"] += piece.size
+                ctl[0, b] = piece.size
+                if job["pos"] >= job["pcm"].size:
+                    ctl[1, b] = 1
+                    ending.append(job)
+            x = x_h.to(dev, non_blocking=True)
+            ctl_d = ctl_h.to(dev, non_blocking=True)
+            out, cnt = ts.new_outputs(batch, n_in)
+            ts.chunk(x, n_in, out, cnt, valid=ctl_d[0], last=ctl_d[1])
+            out_h = torch.empty(out.shape, dtype=torch.float32).pin_memory()
+            cnt_h = torch.empty(cnt.shape, dtype=torch.int32).pin_memory()
+            out_h.copy_(out, non_blocking=True)
+            cnt_h.copy_(cnt, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._stretch_stream)
+        self._stretch_flight = (ev, out_h, cnt_h, (x_h, ctl_h, x, ctl_d, out, cnt), [(j, j["slot"]) for j in running])
+        for job in ending:
+            job["slot"] = -2  # (done once this call is collected; its slot is free for the next call)
 
     # ------------------------------------------------------------------ worker: main loop
     def _run(self) -> None:
@@ -819,6 +965,7 @@ class BatchScheduler:
             self._copy_stream = torch.cuda.Stream()
             self._codec_stream = torch.cuda.Stream()
             self._side_stream = torch.cuda.Stream()
+            self._stretch_stream = torch.cuda.Stream()  # blocking utterances' stretches (_start_stretch)
             with torch.cuda.stream(compute):
                 while not self._stop.is_set():
                     self._job_step()  # a voice registration: at most one prefill chunk between two ticks
@@ -833,6 +980,11 @@ class BatchScheduler:
                         self._decode_finished(force=True)
                         if self._deliveries or self._codec_backlog():
                             self._deliver(wait=not self._codec_backlog())  # keep the passes coming while there is codec work
+                            continue
+                        if self._stretches:  # only stretches in flight: look again shortly, or sooner for a new request
+                            self._poll_stretches()
+                            self._wake.wait(timeout=0.0005)
+                            self._wake.clear()
                             continue
                         self._wake.wait(timeout=0.05)  # idle: sleep until submit() (or close) without touching the queue
                         self._wake.clear()
@@ -897,5 +1049,9 @@ class BatchScheduler:
         self._retiring = []
         self._finished = []
         self._deliveries = []
+        for job in self._stretches:
+            self._end(job["req"], e)
+        self._stretches = []
+        self._stretch_flight = None
         while not self._pending.empty():
             self._end(self._pending.get_nowait(), e)

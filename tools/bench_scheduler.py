@@ -5,8 +5,11 @@ at t), blocking responses.
     python tools/bench_scheduler.py [n_requests] [frames_per_tick] [stream|block] [pool_workers]
 
 ``pool_workers`` > 0 puts the same load through the multi-GPU front-end (server/pool.py) with that many worker processes,
-all on GPU 0 here: what the relay between processes costs."""
+all on GPU 0 here: what the relay between processes costs.
+SPEED_HALF=s: every other request, streamed or blocking, asks for speaking speed s (time-stretched on the GPU); its frames are
+counted as the LM frames behind its samples (samples x s / 1920)."""
 import functools
+import os
 import sys
 import threading
 import time
@@ -55,17 +58,24 @@ def main():
 
 
     first_chunk_ms = []
+    half_speed = float(os.environ.get("SPEED_HALF", 0)) or None
 
 
     def worker(i):
         if streaming:
             t1 = time.perf_counter()
             n = 0
-            for j, chunk in enumerate(sched.iter_chunks(sched.submit(texts[i], "heart", stream=True, max_new_tokens=int(budgets[i])))):
+            sp = half_speed if half_speed and i % 2 else None
+            kw = {"speed": sp} if sp else {}
+            for j, chunk in enumerate(sched.iter_chunks(sched.submit(texts[i], "heart", stream=True, max_new_tokens=int(budgets[i]), **kw))):
                 if j == 0:
                     first_chunk_ms.append((time.perf_counter() - t1) * 1e3)
                 n += chunk.shape[0]
-            samples[i] = n
+            samples[i] = int(round(n * sp)) if sp else n
+        elif half_speed and i % 2:  # (blocking with a speed: the utterance is stretched after its last codec pass)
+            req = sched.submit(texts[i], "heart", max_new_tokens=int(budgets[i]), speed=half_speed)
+            n = sum(c.shape[0] for c in sched.iter_chunks(req))
+            samples[i] = int(round(n * half_speed))
         else:
             samples[i] = sched.synthesize(texts[i], "heart", max_new_tokens=int(budgets[i])).shape[0]
 
@@ -127,7 +137,8 @@ def main():
     frames = sum(samples) // 1920
     print(f"{n_req} {'streaming' if streaming else 'blocking'} requests, {frames} frames of audio in {dt:.2f} s -> {frames / dt:.0f} frames/s "
           f"({frames / dt / 12.5:.0f}x real time), tick {tick}" + (f", pool of {n_pool} worker processes" if n_pool else "")
-          + (f"; time to first chunk p50 {np.median(first_chunk_ms):.1f} ms (includes queueing for a slot)" if first_chunk_ms else ""))
+          + (f"; time to first chunk p50 {np.median(first_chunk_ms):.1f} ms (includes queueing for a slot)" if first_chunk_ms else "")
+          + (f"; every other request at speed {half_speed}" if half_speed else ""))
     if not n_pool:
         st1 = sched.stats()
         ticks = st1["ticks"] - st0["ticks"]
