@@ -16,6 +16,8 @@ import numpy as np
 import torch
 
 from .config import NumericsMode, RQTransformerModelArgs, TokenConfig
+from .formats import ENC_OFF, parse_stream_format
+from .tsm import out_bound
 from . import packing
 
 LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libsmoltts_hip.so"
@@ -961,8 +963,6 @@ class Resampler:
 
     def reset_slots(self, slots: Sequence[int], formats: Sequence[str]) -> None:
         """Start new streams in ``slots`` with their ``output_format`` (``pcm_24000``: the slot is not converted)."""
-        from .formats import parse_stream_format
-
         parsed = [parse_stream_format(f) for f in formats]
         n = len(slots)
         arr = lambda v: (C.c_int32 * n)(*v)  # noqa: E731
@@ -991,12 +991,10 @@ class Resampler:
                                               dptr(counts), current_stream_ptr()), "smoltts_resample_chunk")
 
     def slot_bytes(self, host_out: np.ndarray, host_counts: np.ndarray, b: int, tail: bool = False,
-                   output_format: Optional[str] = None) -> np.ndarray:
+                   enc: Optional[int] = None) -> np.ndarray:
         """Slot ``b``'s samples of a call, copied to the host: int16 for pcm_*, uint8 for ulaw_8000; with the tail if ``tail``.
-        ``output_format``: the format the call ran with, when the slot may have been restarted since (default: its current one)."""
-        from .formats import parse_stream_format
-
-        enc = self.formats[b][1] if output_format is None else parse_stream_format(output_format)[1]
+        ``enc``: the encoding the call ran with, when the slot may have been restarted since (default: its current one)."""
+        enc = self.formats[b][1] if enc is None else enc
         n = int(host_counts[b, 0]) + (int(host_counts[b, 1]) if tail else 0)
         width = 1 if enc == 2 else 2
         return host_out[b, : n * width].view(np.uint8 if enc == 2 else np.int16).copy()
@@ -1079,6 +1077,97 @@ class TimeStretcher:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------------- a stream's stages behind the codec
+class StreamConverter:
+    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch``: a slot with a speed is time-stretched
+    (``TimeStretcher``), then a slot with an output format is converted (``Resampler``, from the stretched samples where the
+    slot has a speed).  Each stage is created the first time a slot needs it.  ``n_in``: codec samples per slot and call; the
+    resampler takes up to the stretcher's output of that many."""
+
+    def __init__(self, device: torch.device, max_batch: int, n_in: int):
+        self.device, self.B, self.n_in = device, max_batch, n_in
+        self.rs: Optional[Resampler] = None
+        self.ts: Optional[TimeStretcher] = None
+
+    def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]]) -> None:
+        """Start new streams in ``slots`` on the current stream: ``formats[i]`` an ``output_format`` (None / ``pcm_24000``:
+        float32), ``speed_q[i]`` a Q16 speed (None / 65536: none).  A slot with neither is switched off."""
+        if not slots:
+            return
+        formats = [f or "pcm_24000" for f in formats]
+        speed_q = [q or 65536 for q in speed_q]
+        if self.rs is None and any(parse_stream_format(f)[1] != ENC_OFF for f in formats):
+            self.rs = Resampler(self.device, self.B, out_bound(self.n_in))
+        if self.ts is None and any(q != 65536 for q in speed_q):
+            self.ts = TimeStretcher(self.device, self.B)
+        if self.rs is not None:
+            self.rs.reset_slots(slots, formats)
+        if self.ts is not None:
+            self.ts.reset_slots(slots, speed_q)
+
+    def run(self, pcm: torch.Tensor, n_in: int, valid: torch.Tensor, last: Optional[torch.Tensor] = None,
+            slots: Optional[Sequence[int]] = None) -> Optional["StreamPass"]:
+        """Queue the stages for ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in]) on the current stream.
+        ``valid`` (device int32 [batch]): the samples of each row that are real; ``last`` (device int32 [batch], needed when a
+        slot has a speed): nonzero where the row's stream ends with this call.  ``slots``: the live streams (default: every
+        slot); the others consume what ``valid`` gives them and are never read.  None when no live slot converts: no launch."""
+        slots = range(self.B) if slots is None else slots
+        fmt = [b for b in slots if self.rs is not None and self.rs.formats[b][1] != ENC_OFF]
+        spd = [b for b in slots if self.ts is not None and self.ts.speed_q[b] != 65536]
+        if not (fmt or spd):
+            return None
+        batch = pcm.shape[0]
+        src, rs_valid = pcm, valid
+        out = counts = stretched = st_counts = None
+        if spd:
+            stretched, st_counts = self.ts.new_outputs(batch, n_in)
+            self.ts.chunk(pcm, n_in, stretched, st_counts, valid=valid, last=last)
+            src, rs_valid = stretched, st_counts
+            plain = [b for b in fmt if b not in spd]
+            if plain:  # one resample launch for all: the codec's rows of formatted slots without a speed join the stretched rows
+                sped = np.zeros(batch, np.int32)
+                sped[spd] = 1
+                sped_d, plain_d = upload([sped, np.asarray(plain, np.int64)], self.device)
+                stretched[plain_d, :n_in] = pcm[plain_d]
+                rs_valid = torch.where(sped_d != 0, st_counts, valid)
+            n_in = stretched.shape[1]
+        if fmt:
+            out, counts = self.rs.new_outputs(batch, n_in)
+            self.rs.chunk(src, n_in, out, counts, valid=rs_valid)
+        if not any(b not in fmt for b in spd):  # every stretched slot is converted: its float32 is not read
+            stretched = st_counts = None
+        return StreamPass(self.rs, [f[1] for f in self.rs.formats] if fmt else None, out, counts, stretched, st_counts)
+
+    def close(self):
+        for stage in (self.rs, self.ts):
+            if stage is not None:
+                stage.close()
+        self.rs = self.ts = None
+
+
+class StreamPass:
+    """The outputs of one ``StreamConverter.run``: on the device, then (``to_host``) on the host, read slot by slot (``chunk``).
+    It keeps the slots' encodings of its run: a slot may have been restarted by the time its chunk is read."""
+
+    def __init__(self, rs: Optional[Resampler], enc: Optional[List[int]], *device_outputs):
+        self.rs, self.enc = rs, enc
+        self.dev = device_outputs  # (bytes, counts, stretched fp32, stretched counts); None where not read
+        self.host = None
+
+    def to_host(self, stream) -> None:
+        """Queue the host copies on ``stream``; ``chunk`` reads them once ``stream`` has run them."""
+        with torch.cuda.stream(stream):
+            self.host = tuple(t.to("cpu", non_blocking=True) if t is not None else None for t in self.dev)
+
+    def chunk(self, b: int, last: bool) -> np.ndarray:
+        """Slot ``b``'s chunk: its converted samples (with the resampler's tail when ``last``), or the stretched float32 of a slot
+        with a speed and no format."""
+        out, counts, stretched, st_counts = (t.numpy() if t is not None else None for t in self.host)
+        if self.enc is not None and self.enc[b] != ENC_OFF:
+            return self.rs.slot_bytes(out, counts, b, tail=last, enc=self.enc[b])
+        return stretched[b, : int(st_counts[b])].copy()
 
 
 def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device) -> np.ndarray:

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .config import GenerationSettings, RequestSampling
-from .engine import LMEngine, LMSession, Resampler, TimeStretcher
+from .engine import LMEngine, LMSession, StreamConverter
 from .formats import ENC_OFF, parse_stream_format
 
 
@@ -244,25 +244,12 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     pcm_dev = torch.empty(1, 1920, dtype=torch.float32, device=dev)
     pcm_host = torch.empty(1, 1920, dtype=torch.float32).pin_memory()
     state_host = torch.zeros(2, dtype=torch.int32).pin_memory()  # n_frames[0], done[0]
-    rs = ts = rs_out = rs_counts = rs_out_host = rs_counts_host = None
-    rs_in = 1920
-    if speed_q is not None:
-        ts = TimeStretcher(dev, 1)
-        ts_out, ts_counts = ts.new_outputs(1, 1920)
-        ts_out_host = torch.empty(ts_out.shape, dtype=torch.float32).pin_memory()
-        ts_counts_host = torch.empty(ts_counts.shape, dtype=torch.int32).pin_memory()
-        rs_in = ts_out.shape[1]  # the resampler consumes the stretcher's output, up to 4x the frame at speed 0.25
-    if output_format is not None and parse_stream_format(output_format)[1] != ENC_OFF:
-        rs = Resampler(dev, 1, rs_in)
-        rs_out, rs_counts = rs.new_outputs(1)
-        rs_out_host = torch.empty(rs_out.shape, dtype=torch.uint8).pin_memory()
-        rs_counts_host = torch.empty(rs_counts.shape, dtype=torch.int32).pin_memory()
+    formatted = output_format is not None and parse_stream_format(output_format)[1] != ENC_OFF
+    conv = StreamConverter(dev, 1, 1920) if formatted or speed_q is not None else None
     with torch.cuda.stream(codec_stream):
         msession.reset()
-        if rs is not None:
-            rs.reset_slots([0], [output_format])
-        if ts is not None:
-            ts.reset_slots([0], [speed_q])
+        if conv is not None:
+            conv.reset_slots([0], [output_format], [speed_q])
     with torch.cuda.stream(lm_stream):
         s.prefill([prompt], stop_on_eos=stop_on_eos)  # frame 0
         ev = torch.cuda.Event()
@@ -277,35 +264,36 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
                     nxt = torch.cuda.Event()
                     nxt.record(lm_stream)
             ev.synchronize()  # frame f is in the output ring
-            if ts is not None:
-                yield from _stretch_step(s, msession, f, limit, codec_stream, pcm_dev, state_host, ts, ts_out, ts_counts, ts_out_host,
-                                         ts_counts_host, rs, rs_out, rs_counts, rs_out_host, rs_counts_host)
-                n, done = int(state_host[0]), int(state_host[1])
-                if n <= f:
-                    break
-            else:
-                with torch.cuda.stream(codec_stream):
+            out = None
+            with torch.cuda.stream(codec_stream):
+                if speed_q is None:
                     state_host[0:1].copy_(s.n_frames[0:1], non_blocking=True)
                     state_host[1:2].copy_(s.done[0:1], non_blocking=True)
-                    msession.decode_chunk(s.codes[:, f:f + 1], 0, 1, pcm_dev, code_offset=1)  # (decode_chunk writes frame f0 at pcm[:, 1920 f0:])
-                    if rs is not None:
-                        valid = (s.n_frames[0:1] > f).to(torch.int32) * 1920  # 0 once the slot has stopped: garbage is not consumed
-                        rs.chunk(pcm_dev, 1920, rs_out, rs_counts, valid=valid)
-                        rs_out_host.copy_(rs_out, non_blocking=True)
-                        rs_counts_host.copy_(rs_counts, non_blocking=True)
-                    else:
-                        pcm_host.copy_(pcm_dev, non_blocking=True)
-                codec_stream.synchronize()
-                n, done = int(state_host[0]), int(state_host[1])
-                if n <= f:  # the slot had stopped before this frame
-                    if rs is not None:  # (this call consumed nothing: its tail is that of the last frame)
-                        yield rs.slot_bytes(rs_out_host.numpy(), rs_counts_host.numpy(), 0, tail=True)
-                    break
-                last = bool(done and n == f + 1) or f + 1 >= limit
-                if rs is not None:
-                    yield rs.slot_bytes(rs_out_host.numpy(), rs_counts_host.numpy(), 0, tail=last)
+                    n_d, done_d = s.n_frames[0:1], s.done[0:1]
+                else:  # one device snapshot: the stretcher's `last` and the host's decision below come from the same values
+                    snap = torch.cat([s.n_frames[0:1], s.done[0:1]])
+                    state_host.copy_(snap, non_blocking=True)
+                    n_d, done_d = snap[0:1], snap[1:2]
+                msession.decode_chunk(s.codes[:, f:f + 1], 0, 1, pcm_dev, code_offset=1)  # (decode_chunk writes frame f0 at pcm[:, 1920 f0:])
+                if conv is not None:
+                    valid = (n_d > f).to(torch.int32) * 1920  # 0 once the slot has stopped: garbage is not consumed
+                    # the stream ends with this frame (done at it, or the frame limit), or had ended before it unseen by the host
+                    last = None if speed_q is None else ((n_d <= f) | ((done_d != 0) & (n_d == f + 1)) | (f + 1 >= limit)).to(torch.int32)
+                    out = conv.run(pcm_dev, 1920, valid, last)
+                    out.to_host(codec_stream)
                 else:
-                    yield pcm_host.numpy().reshape(-1).copy()
+                    pcm_host.copy_(pcm_dev, non_blocking=True)
+            codec_stream.synchronize()
+            n, done = int(state_host[0]), int(state_host[1])
+            if out is not None:
+                # (a call after the slot stopped consumed nothing: its tail is that of the last frame)
+                chunk = out.chunk(0, last=n <= f or bool(done and n == f + 1) or f + 1 >= limit)
+                if chunk.size or speed_q is None:  # (a stretched frame that finalised no sample yields nothing)
+                    yield chunk
+            if n <= f:  # the slot had stopped before this frame
+                break
+            if out is None:
+                yield pcm_host.numpy().reshape(-1).copy()
             if done and n == f + 1:
                 break
             if not overlap and f + 1 < limit:
@@ -319,38 +307,5 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     finally:
         lm_stream.synchronize()
         codec_stream.synchronize()
-        if rs is not None:
-            rs.close()
-        if ts is not None:
-            ts.close()
-
-
-def _stretch_step(s, msession, f: int, limit: int, codec_stream, pcm_dev, state_host, ts, ts_out, ts_counts, ts_out_host,
-                  ts_counts_host, rs, rs_out, rs_counts, rs_out_host, rs_counts_host):
-    """Frame f of ``stream_pcm`` with a speed: decode, stretch (and convert) on the codec stream; yields the chunk, if any.
-    ``valid`` and ``last`` come from one device snapshot of (n_frames, done), the one the host reads back in ``state_host``."""
-    with torch.cuda.stream(codec_stream):
-        snap = torch.cat([s.n_frames[0:1], s.done[0:1]])
-        state_host.copy_(snap, non_blocking=True)
-        msession.decode_chunk(s.codes[:, f:f + 1], 0, 1, pcm_dev, code_offset=1)
-        n_d, done_d = snap[0:1], snap[1:2]
-        valid = (n_d > f).to(torch.int32) * 1920
-        # the stream ends with this frame (done at it, or the frame limit), or had ended before it unseen by the host
-        last = ((n_d <= f) | ((done_d != 0) & (n_d == f + 1)) | (f + 1 >= limit)).to(torch.int32)
-        ts.chunk(pcm_dev, 1920, ts_out, ts_counts, valid=valid, last=last)
-        if rs is not None:
-            rs.chunk(ts_out, ts_out.shape[1], rs_out, rs_counts, valid=ts_counts)
-            rs_out_host.copy_(rs_out, non_blocking=True)
-            rs_counts_host.copy_(rs_counts, non_blocking=True)
-        else:
-            ts_out_host.copy_(ts_out, non_blocking=True)
-            ts_counts_host.copy_(ts_counts, non_blocking=True)
-    codec_stream.synchronize()
-    n, done = int(state_host[0]), int(state_host[1])
-    last = n <= f or bool(done and n == f + 1) or f + 1 >= limit
-    if rs is not None:
-        chunk = rs.slot_bytes(rs_out_host.numpy(), rs_counts_host.numpy(), 0, tail=last)
-    else:
-        chunk = ts_out_host.numpy()[0, : int(ts_counts_host[0])].copy()
-    if chunk.size:
-        yield chunk
+        if conv is not None:
+            conv.close()

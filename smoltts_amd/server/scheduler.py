@@ -11,10 +11,12 @@ between chunks.
 The loop is pipelined so that the GPU never waits for Python: tick k is queued, a device-side snapshot of the output ring
 is queued behind it, and *then* the host reads the snapshot of tick k-1 (on a copy stream) and does its bookkeeping while
 tick k runs.  A slot that finished in tick k-1 is therefore refilled in tick k+1 (one tick of that slot is the price).
-Codec work is queued on the same stream behind the ticks and its PCM is fetched on the copy stream when its event has
-fired: streaming requests share one codec session whose slots mirror the LM slots (every slot keeps its own stream
-position, ``smoltts_mimi_reset_slots`` starts a new stream in a slot) and are decoded together, one codec pass per tick; a
-blocking request is decoded when its utterance is complete, up to ``CODEC_BATCH`` finished utterances per codec pass.  A request's PCM is identical to what
+Codec work runs on a codec stream beside the ticks and its PCM is fetched on the copy stream when its event has fired:
+streaming requests share one codec session whose slots mirror the LM slots (every slot keeps its own stream position,
+``smoltts_mimi_reset_slots`` starts a new stream in a slot) and are decoded together, one codec pass per tick, launched once
+the host has seen that tick's snapshot (so beside the next tick); a stream with a speed or an output format is stretched
+and converted in the same pass (``engine.StreamConverter``).  A blocking request is decoded when its utterance is complete,
+up to ``CODEC_BATCH`` finished utterances per codec pass.  A request's PCM is identical to what
 ``SmolTTS.__call__`` / ``stream`` return for it alone.
 """
 from __future__ import annotations
@@ -70,25 +72,55 @@ class _CodecJob:
     done: int = 0     # frames already handed to the codec
 
 
-def _to_host(conv):
-    """Queue the host copies of a pass's converted outputs (``BatchScheduler._convert``; stages that did not run stay None)."""
-    return None if conv is None else tuple(t.to("cpu", non_blocking=True) if t is not None else None for t in conv)
+@dataclass
+class _Snapshot:
+    """Device-side copies of the output ring queued behind tick ``tick_no``, and the event that fires when they are taken."""
+    codes: object
+    n_frames: object
+    done: object
+    event: object
+    tick_no: int
 
 
-def _numpy(conv):
-    return None if conv is None else tuple(t.numpy() if t is not None else None for t in conv)
+@dataclass
+class _Delivery:
+    """A codec pass whose PCM goes out to its requests, in order, once ``event`` has fired (None: nothing to wait for)."""
+    event: object
+    pcm: object       # the pass's PCM on the device
+    items: list       # [(request, codec slot, samples, last?)]
+    urgent: bool = False  # a stream's first chunk is in it: handed out as soon as the pass is through
+    keep: object = None   # device tensors the pass reads, kept alive until it has run
+    conv: object = None   # engine.StreamPass: the stream conversion of the pass (None: float32 rows of ``pcm``)
+
+
+@dataclass
+class _StretchJob:
+    """A complete blocking utterance with a speed, stretched in pieces by ``_poll_stretches``."""
+    req: _Request
+    pcm: np.ndarray
+    pos: int = 0                                   # input samples handed to the stretcher so far
+    outs: list = field(default_factory=list)       # stretched pieces collected so far
+    state: str = "waiting"  # "waiting" for a stretcher slot, "running" in it, or "ending": its last piece is in the call in flight
+    slot: int = -1          # its stretcher slot while running or ending
+
+
+def stream_ends(n, done, cap):
+    """Whether a stream with frame budget ``cap`` is complete at a snapshot showing ``n`` frames and the ``done`` flag: the slot
+    has stopped with a frame, or the budget is reached.  Elementwise on numpy values and torch tensors alike: the host closes a
+    response with it and the device flushes the stretcher with it, from the same snapshot, so the two agree."""
+    return (done != 0) & (n > 0) | (n >= cap)
 
 
 class BatchScheduler:
     CODEC_BATCH, CODEC_CHUNK, CODEC_WAIT = 16, 64, 32  # slots, frames per slot and pass, LM frames a pass may wait for company
 
     def __init__(self, tts, max_batch: int = 32, frames_per_tick: int = 4, generation_settings=None, max_prompt_rows: int = 4096,
-                 prefill_chunk: Optional[int] = 128, overlap_stream_codec: bool = True, side_prefill: bool = True,
-                 side_prefill_min_active: Optional[int] = None, codec_products: int = 6):
+                 prefill_chunk: Optional[int] = 128, side_prefill: bool = True, side_prefill_min_active: Optional[int] = None,
+                 codec_products: int = 6):
         import torch
 
         from ..config import GenerationSettings
-        from ..engine import LMSession
+        from ..engine import LMSession, StreamConverter
         from ..generate import _apply_sampling
 
         self.tts = tts
@@ -96,9 +128,6 @@ class BatchScheduler:
         self.codec_products = codec_products  # SMOLTTS_MIMI_OPT_PRODUCTS of the codec sessions (6: fp32-grade)
         self.tick = frames_per_tick
         self.prefill_chunk = prefill_chunk  # columns per utterance per prefill call (None: whole prompts at once)
-        # streaming requests: the codec pass of tick k is launched on a second stream by the host once it has seen tick k finish
-        # (it waits for that anyway, to read the tick's snapshot), i.e. while tick k+1 runs -- instead of in line between the ticks
-        self.overlap_stream_codec = overlap_stream_codec
         # refills while most slots are speaking: the new prompts' KV rows are computed on a second stream beside the next tick
         # (LMSession.side_park / side_run / side_start) instead of in line between two ticks; the new tenants then start one
         # tick later.  With few slots speaking the in-line prefill answers sooner and stops nobody worth mentioning.
@@ -134,14 +163,14 @@ class BatchScheduler:
         self._codec_slot_age = [0] * self.CODEC_BATCH  # passes a slot has seen since its last restart
         self._codec_wait = 0                    # ticks since the last pass while work was waiting
         self._stream_codec = None               # codec session whose slot b carries the stream of LM slot b (streaming requests)
-        self._stream_rs = None                  # engine.Resampler beside it: slot b converts the stream of LM slot b when it has a format
-        self._stream_ts = None                  # engine.TimeStretcher in front of it: slot b stretches LM slot b's stream when it has a speed
-        self._block_ts = None                   # one-slot stretcher of the blocking requests' whole utterances
-        self._stretches: List[dict] = []        # blocking utterances with a speed, complete, being stretched (_poll_stretches)
-        self._stretch_flight = None             # the stretch call in flight: (event, host output, host counts, keep-alive, [(job, slot)])
+        # behind it, slot b stretches and converts LM slot b's stream when it has a speed / a format
+        self._stream_conv = StreamConverter(self.session.engine.device, max_batch, max(frames_per_tick, 1) * 1920)
+        self._block_ts = None                   # stretcher of the blocking requests' whole utterances
+        self._stretches: List[_StretchJob] = []  # blocking utterances with a speed, complete, being stretched (_poll_stretches)
+        self._stretch_flight = None             # the stretch call in flight: (event, host output, host counts, keep-alive, [jobs])
         self._codec_age = [0] * max_batch       # codec passes each of its slots has seen since that slot's last reset
-        self._deliveries: List[tuple] = []      # (event, pcm on the device, [(request, first sample, n samples, last?)]) in order
-        self._snaps: List[tuple] = []           # snapshots of the output ring the host has not looked at yet (oldest first)
+        self._deliveries: List[_Delivery] = []  # codec passes whose PCM has not been handed out yet, in order
+        self._snaps: List[_Snapshot] = []       # snapshots of the output ring the host has not looked at yet (oldest first)
         self._tick_no = 0                       # ticks queued so far
         self._counts = {"completed": 0, "cancelled": 0, "failed": 0, "frames_delivered": 0, "prefix_installs": 0}
         self._dead: Optional[Exception] = None  # why the worker stopped
@@ -268,10 +297,11 @@ class BatchScheduler:
         self._stop.set()
         self._wake.set()
         self._thread.join(timeout=30)
-        for name in ("_batch_codec", "_stream_codec", "_stream_rs", "_stream_ts", "_block_ts", "_scratch"):
+        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch"):
             if getattr(self, name) is not None:
                 getattr(self, name).close()
                 setattr(self, name, None)
+        self._stream_conv.close()
         self.session.close()
 
     # ------------------------------------------------------------------ worker: admission
@@ -296,51 +326,25 @@ class BatchScheduler:
         self._enter(sd["reqs"])
 
     def _enter(self, new: List[_Request]) -> None:
-        """Requests whose slots have just been armed: codec stream bookkeeping, first / last tick, into the active set."""
-        streams = [r.slot for r in new if r.stream]
-        if streams:
+        """Requests whose slots have just been armed: the streams' codec session, first / last tick, into the active set.  (A
+        slot's codec stream restarts in ``_launch_stream_codec``, right before the pass of the request's first tick.)"""
+        if self._stream_codec is None and any(r.stream for r in new):
             from ..engine import MimiSession
 
-            if self._stream_codec is None:
-                self._stream_codec = MimiSession(self.tts.codec, max_batch=self.B, max_chunk_frames=max(self.tick, 1), products=self.codec_products)
-                self._stream_codec.reset()
-            if self._stream_rs is None and any(r.output_format for r in new if r.stream):
-                from ..engine import Resampler
-                from ..tsm import out_bound
-
-                # (sized for the stretcher's output at speed 0.25; a pass without a speed sizes its buffers for the PCM alone)
-                self._stream_rs = Resampler(self.session.engine.device, self.B, out_bound(max(self.tick, 1) * 1920))  # every slot starts off
-            if self._stream_ts is None and any(r.speed_q for r in new if r.stream):
-                from ..engine import TimeStretcher
-
-                self._stream_ts = TimeStretcher(self.session.engine.device, self.B)  # every slot starts off
-            if not self.overlap_stream_codec:  # (overlapped: the slot's stream restarts on the codec stream, right before the pass
-                self._stream_codec.reset_slots(streams)  # of the request's first tick and behind the previous tenant's last pass)
-                self._reset_formats([r for r in new if r.stream])
-                for b in streams:
-                    self._codec_age[b] = 0
+            self._stream_codec = MimiSession(self.tts.codec, max_batch=self.B, max_chunk_frames=max(self.tick, 1), products=self.codec_products)
+            self._stream_codec.reset()
         for r in new:
             r.first_tick = self._tick_no
             r.last_tick = self._tick_no + -(-(r.max_new_tokens + 1) // self.tick) - 1  # ceil(frames / tick) ticks from first_tick on
             self._active[r.slot] = r
 
-    def _reset_formats(self, reqs: List[_Request]) -> None:
-        """Start the resampler and stretcher streams of new streaming tenants (a slot without a format / speed is switched off)."""
-        if self._stream_rs is not None and reqs:
-            self._stream_rs.reset_slots([r.slot for r in reqs], [r.output_format or "pcm_24000" for r in reqs])
-        if self._stream_ts is not None and reqs:
-            self._stream_ts.reset_slots([r.slot for r in reqs], [r.speed_q or 65536 for r in reqs])
-
     def _convert(self, pcm, n_frames_d, done_d, reqs: List[_Request], tick_no: int):
-        """The stretch and resample launches of a stream codec pass (current stream, right behind the decode): slot b of a request
-        in ``reqs`` consumes the samples of the frames the tick's frame counter ``n_frames_d`` (device) gives it; every other slot
-        none.  A slot with a speed is stretched first, and ends its stream (flushes) in the tick where the host will see it finish,
-        derived from the same snapshot (``n_frames_d``, ``done_d``); the resampler then consumes the stretcher's output.  Returns
-        (bytes, counts, stretched, stretched counts) on the device, None for a stage that did not run, or None when neither ran."""
-        rs, ts = self._stream_rs, self._stream_ts
-        fmt = rs is not None and any(r.output_format for r in reqs)
-        spd = ts is not None and any(r.speed_q for r in reqs)
-        if not (fmt or spd):
+        """The stream conversion of a codec pass (``engine.StreamConverter``, current stream, right behind the decode): slot b of
+        a request in ``reqs`` consumes the samples of the frames the tick's frame counter ``n_frames_d`` (device) gives it; every
+        other slot none.  A slot with a speed ends its stream (flushes) in the tick where the host will see it finish, by the
+        rule of ``_drain`` on the same snapshot (``n_frames_d``, ``done_d``).  Returns the ``engine.StreamPass``, or None when no
+        request in ``reqs`` has a format or a speed (then nothing is uploaded or launched)."""
+        if not any(r.output_format or r.speed_q for r in reqs):
             return None
         from ..engine import upload
 
@@ -353,25 +357,10 @@ class BatchScheduler:
         f0_d, cap_d = upload([f0, cap], self.session.engine.device)
         n_d = n_frames_d.to(torch.int32)
         valid = ((torch.minimum(n_d, cap_d) - f0_d).clamp_(0, self.tick) * 1920).to(torch.int32)
-        n_in, src, rs_valid = self.tick * 1920, pcm, valid
-        ts_out = ts_counts = rs_out = rs_counts = None
-        if spd:
-            # the host's `finished` of _drain, on the device: done (with a frame) or the frame budget reached
-            last = ((((done_d != 0) & (n_d > 0)) | (n_d >= cap_d)) & (cap_d > 0)).to(torch.int32)
-            ts_out, ts_counts = ts.new_outputs(self.B, n_in)
-            ts.chunk(pcm, n_in, ts_out, ts_counts, valid=valid, last=last)
-            if fmt:  # the resampler reads the stretched rows, and the codec's rows of the slots without a speed
-                plain = [r.slot for r in reqs if r.output_format and not r.speed_q]
-                sped = np.zeros(self.B, np.int32)
-                sped[[r.slot for r in reqs if r.speed_q]] = 1
-                sped_d, plain_d = upload([sped, np.asarray(plain, np.int64)], self.session.engine.device)
-                if plain:
-                    ts_out[plain_d, :n_in] = pcm[plain_d]
-                src, rs_valid, n_in = ts_out, torch.where(sped_d != 0, ts_counts, valid), ts_out.shape[1]
-        if fmt:
-            rs_out, rs_counts = rs.new_outputs(self.B, n_in)
-            rs.chunk(src, n_in, rs_out, rs_counts, valid=rs_valid)
-        return rs_out, rs_counts, ts_out, ts_counts
+        last = None
+        if any(r.speed_q for r in reqs):
+            last = (stream_ends(n_d, done_d, cap_d) & (cap_d > 0)).to(torch.int32)
+        return self._stream_conv.run(pcm, self.tick * 1920, valid, last, slots=[r.slot for r in reqs])
 
     def _admit(self) -> None:
         if self._side is not None and self._side["state"] == "running":
@@ -434,12 +423,10 @@ class BatchScheduler:
             return
         if side:
             try:
-                if any(r.prefix is not None for r in new):  # the voices' prefix rows go in first, in one launch, then the park at P + T - 1
-                    h = self.session.side_park([r.prompt for r in new], [r.slot for r in new], pos0=[r.pos0 for r in new],
-                                               prefixes=[r.prefix for r in new])
-                    self._counts["prefix_installs"] += sum(1 for r in new if r.prefix is not None)
-                else:
-                    h = self.session.side_park([r.prompt for r in new], [r.slot for r in new])  # queued behind the ticks so far
+                # queued behind the ticks so far; the voices' prefix rows go in first, in one launch, then the park at P + T - 1
+                h = self.session.side_park([r.prompt for r in new], [r.slot for r in new], pos0=[r.pos0 for r in new],
+                                           prefixes=[r.prefix for r in new])
+                self._counts["prefix_installs"] += sum(1 for r in new if r.prefix is not None)
             except Exception as e:
                 for r in new:
                     self._end(r, e)
@@ -465,9 +452,11 @@ class BatchScheduler:
             self._slot_sampling[b] = entries[b]
 
     def _prefill(self, new: List[_Request]) -> None:
-        if any(r.prefix is not None for r in new):
-            self._prefill_prefixed(new)
-            return
+        """In-line admission: the registered voices' prefixes are installed in one launch, then every prompt (a registered
+        voice's: its own turns only) is prefilled from its pos0.  Frame 0 of the new slots comes out of the next tick's first
+        frame (no separate tail for all slots)."""
+        prompts, slots = [r.prompt for r in new], [r.slot for r in new]
+        prefixes, pos0 = [r.prefix for r in new], [r.pos0 for r in new]
         if self.prefill_chunk:
             # long prompts (voice-clone speakers) enter in chunks; the slots already speaking get a tick in between
             def between():
@@ -475,28 +464,12 @@ class BatchScheduler:
                     self._tick_and_snapshot()
                     self._consume_snapshots(keep=1)
 
-            self.session.prefill_chunked([r.prompt for r in new], slots=[r.slot for r in new], stop_on_eos=True,
-                                         chunk=self.prefill_chunk, between=between, defer_frame0=True)
+            self.session.prefill_chunked(prompts, slots=slots, stop_on_eos=True, chunk=self.prefill_chunk, between=between,
+                                         defer_frame0=True, pos0=pos0, prefixes=prefixes)
         else:
-            # frame 0 of the new slots comes out of the next tick's first frame (no separate tail for all slots)
-            self.session.prefill([r.prompt for r in new], slots=[r.slot for r in new], stop_on_eos=True, defer_frame0=True)
-
-    def _prefill_prefixed(self, new: List[_Request]) -> None:
-        """In-line admission with registered voices among the requests: their prefixes are installed in one launch, then every
-        prompt (a registered voice's: its own turns only) is prefilled from its pos0."""
-        prefixes = [r.prefix for r in new]
-        pos0 = [r.pos0 for r in new]
-        if self.prefill_chunk:
-            def between():
-                if self._active:
-                    self._tick_and_snapshot()
-                    self._consume_snapshots(keep=1)
-
-            self.session.prefill_chunked([r.prompt for r in new], slots=[r.slot for r in new], stop_on_eos=True, chunk=self.prefill_chunk,
-                                         between=between, defer_frame0=True, pos0=pos0, prefixes=prefixes)
-        else:
-            self.session.install_prefix([p for p in prefixes if p is not None], [r.slot for r in new if r.prefix is not None])
-            self.session.prefill([r.prompt for r in new], slots=[r.slot for r in new], stop_on_eos=True, defer_frame0=True, pos0=pos0)
+            if any(p is not None for p in prefixes):  # (install_prefix refuses an empty list)
+                self.session.install_prefix([p for p in prefixes if p is not None], [r.slot for r in new if r.prefix is not None])
+            self.session.prefill(prompts, slots=slots, stop_on_eos=True, defer_frame0=True, pos0=pos0)
         self._counts["prefix_installs"] += sum(1 for p in prefixes if p is not None)
 
     # ------------------------------------------------------------------ worker: voice registrations
@@ -562,40 +535,10 @@ class BatchScheduler:
         """Queue one tick of frames and, behind it, a device-side copy of the output ring with an event: the host reads
         that copy later, while the following tick runs."""
         torch = self._torch
-        self.session.decode(self.tick)
         s = self.session
-        pcm = None
-        streaming = [] if self.overlap_stream_codec else [r for r in self._active.values() if r.stream]
-        if streaming:
-            # the frames this tick gives slot b sit at ring positions [f0_b, f0_b + tick): f0_b follows from the tick count
-            # alone while the request is alive (frames of a slot that has stopped are garbage here and never delivered)
-            f0 = np.zeros(self.B, np.int64)
-            for r in streaming:
-                f0[r.slot] = (self._tick_no - r.first_tick) * self.tick
-            # the pass runs over all slots; those without a stream (blocking requests, idle) decode garbage that nobody
-            # reads, but their stream position advances too: restart them before it would reach the codec's capacity
-            live = {r.slot for r in streaming}
-            cap = int(self.tts.codec.c_cfg.max_positions)
-            stale = [b for b in range(self.B) if b not in live and (self._codec_age[b] + 2) * 2 * self.tick > cap]
-            if stale:
-                self._stream_codec.reset_slots(stale)
-                for b in stale:
-                    self._codec_age[b] = 0
-            for b in range(self.B):
-                self._codec_age[b] += 1
-            from ..engine import upload
-
-            f0_d, = upload([f0], self.session.engine.device)
-            idx = (f0_d[:, None] + torch.arange(self.tick, device="cuda")[None]).clamp_(max=self.max_frames - 1)
-            nq = self.tts.config.num_codebooks
-            chunk = s.codes[torch.arange(self.B, device="cuda")[:, None], idx][:, :, -nq:].contiguous()
-            pcm = torch.empty(self.B, self.tick * 1920, dtype=torch.float32, device="cuda")
-            self._stream_codec.decode_chunk(chunk, 0, self.tick, pcm, code_offset=0)
-            conv = self._convert(pcm, s.n_frames, s.done, streaming, self._tick_no)
-        else:
-            conv = None
-        snap = (s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no, pcm, conv)
-        snap[3].record(torch.cuda.current_stream())
+        s.decode(self.tick)
+        snap = _Snapshot(s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no)
+        snap.event.record(torch.cuda.current_stream())
         self._snaps.append(snap)
         self._tick_no += 1
 
@@ -604,27 +547,24 @@ class BatchScheduler:
         only just been queued; its predecessor finished before that tick could start)."""
         torch = self._torch
         while len(self._snaps) > keep:
-            codes_d, n_d, done_d, ev, tick_no, pcm_d, conv_d = self._snaps.pop(0)
+            snap = self._snaps.pop(0)
             # the host waits for the snapshot, then copies on the copy stream: a device-side wait would park a blocked barrier
             # packet in a second hardware queue for the whole tick, and the frame graphs' dependent launches get slower for it
-            self._wait_event(ev)
-            stream_pass = self._launch_stream_codec(codes_d, n_d, done_d, tick_no) if self.overlap_stream_codec else None
+            self._wait_event(snap.event)
+            stream_pass = self._launch_stream_codec(snap)
             with torch.cuda.stream(self._copy_stream):
-                codes = codes_d.to("cpu", non_blocking=True)
-                n_frames = n_d.to("cpu", non_blocking=True)
-                done = done_d.to("cpu", non_blocking=True)
-                pcm = pcm_d.to("cpu", non_blocking=True) if pcm_d is not None else None
-                conv = _to_host(conv_d)
+                codes = snap.codes.to("cpu", non_blocking=True)
+                n_frames = snap.n_frames.to("cpu", non_blocking=True)
+                done = snap.done.to("cpu", non_blocking=True)
             self._sync_copies()
-            self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), tick_no, None if pcm is None else pcm.numpy(), stream_pass,
-                        _numpy(conv))
+            self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), snap.tick_no, stream_pass)
 
-    def _launch_stream_codec(self, codes_d, n_d, done_d, tick_no: int):
-        """The codec pass of the streaming requests for tick ``tick_no``, on the codec stream, from the tick's snapshot of the
-        output ring (the host has just seen that snapshot's event, so the next tick is running meanwhile).  Returns
-        (pcm on the device, event, what to keep alive, converted bytes and counts on the device or None) or None when no stream was
-        alive in that tick."""
+    def _launch_stream_codec(self, snap: _Snapshot) -> Optional[_Delivery]:
+        """The codec pass of the streaming requests for tick ``snap.tick_no``, on the codec stream, from the tick's snapshot of
+        the output ring (the host has just seen that snapshot's event, so the next tick is running meanwhile).  Returns the pass
+        as a delivery without items (``_drain`` adds them), or None when no stream was alive in that tick."""
         torch = self._torch
+        tick_no = snap.tick_no
         alive = [r for r in self._retiring + list(self._active.values())
                  if r.stream and r.first_tick <= tick_no <= r.last_tick and not r.closed and not r.stream_done]
         if not alive or self._stream_codec is None:
@@ -634,28 +574,33 @@ class BatchScheduler:
         with torch.cuda.stream(self._codec_stream):
             live = {r.slot for r in alive}
             cap = int(self.tts.codec.c_cfg.max_positions)
-            restart = [r.slot for r in alive if r.first_tick == tick_no]  # new streams start at position 0 ...
-            restart += [b for b in range(self.B) if b not in live and (self._codec_age[b] + 2) * 2 * self.tick > cap]  # ... idle slots before they overflow
+            new = [r for r in alive if r.first_tick == tick_no]  # new streams start at position 0 ...
+            restart = [r.slot for r in new]
+            # ... and the slots without a stream (blocking requests, idle), which decode garbage that nobody reads, before their
+            # stream position would reach the codec's capacity
+            restart += [b for b in range(self.B) if b not in live and (self._codec_age[b] + 2) * 2 * self.tick > cap]
             if restart:
                 self._stream_codec.reset_slots(sorted(set(restart)))
-                self._reset_formats([r for r in alive if r.first_tick == tick_no])
+                self._stream_conv.reset_slots([r.slot for r in new], [r.output_format for r in new], [r.speed_q for r in new])
                 for b in restart:
                     self._codec_age[b] = 0
             for b in range(self.B):
                 self._codec_age[b] += 1
+            # the frames this tick gives slot b sit at ring positions [f0_b, f0_b + tick): f0_b follows from the tick count
+            # alone while the request is alive (frames of a slot that has stopped are garbage here and never delivered)
             f0 = np.zeros(self.B, np.int64)
             for r in alive:
                 f0[r.slot] = (tick_no - r.first_tick) * self.tick
             f0_d, = upload([f0], self.session.engine.device)
             idx = (f0_d[:, None] + torch.arange(self.tick, device="cuda")[None]).clamp_(max=self.max_frames - 1)
             nq = self.tts.config.num_codebooks
-            chunk = codes_d[torch.arange(self.B, device="cuda")[:, None], idx][:, :, -nq:].contiguous()
+            chunk = snap.codes[torch.arange(self.B, device="cuda")[:, None], idx][:, :, -nq:].contiguous()
             pcm = torch.empty(self.B, self.tick * 1920, dtype=torch.float32, device="cuda")
             self._stream_codec.decode_chunk(chunk, 0, self.tick, pcm, code_offset=0)
-            conv = self._convert(pcm, n_d, done_d, alive, tick_no)
+            conv = self._convert(pcm, snap.n_frames, snap.done, alive, tick_no)
             ev = torch.cuda.Event()
             ev.record(self._codec_stream)
-        return pcm, ev, (codes_d, n_d, done_d), conv  # (codes_d, n_d, done_d: kept alive until the pass has run)
+        return _Delivery(ev, pcm, [], keep=snap, conv=conv)  # (the snapshot's tensors: kept alive until the pass has run)
 
     def _wait_event(self, ev) -> None:
         t = time.perf_counter()
@@ -667,8 +612,9 @@ class BatchScheduler:
         self._copy_stream.synchronize()
         self._gpu_wait_s += time.perf_counter() - t
 
-    def _drain(self, codes, n_frames, done, tick_no: int, pcm, stream_pass=None, conv=None) -> None:
-        stream_items = []  # overlapped codec pass of this tick: (request, pcm row, samples, last?) handed out by _deliver
+    def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery]) -> None:
+        stream_items = []  # the streams' share of this tick's codec pass: (request, pcm row, samples, last?) handed out by _deliver
+        urgent = False     # a stream's first chunk is among them
         nq = self.tts.config.num_codebooks
         tc = self.tts.token_config
 
@@ -693,33 +639,19 @@ class BatchScheduler:
                 self._end(r, RuntimeError("scheduler lost the last frames of a request"))
                 continue
             n = min(int(n_frames[slot]), r.max_new_tokens + 1)
-            finished = (bool(done[slot]) and int(n_frames[slot]) > 0) or n >= r.max_new_tokens + 1
+            finished = bool(stream_ends(n_frames[slot], done[slot], r.max_new_tokens + 1))
             if r.stream:
                 # streaming requests decode every frame (__init__.py:88-92); this tick's PCM of the slot starts at its frame
                 # r.emitted (== f0 of the tick: one codec frame per LM frame)
                 k = n - r.emitted
-                if self.overlap_stream_codec:
-                    if k > 0 or finished:
-                        assert k == 0 or (stream_pass is not None and r.emitted == (tick_no - r.first_tick) * self.tick), "stream bookkeeping out of step"
-                        stream_items.append((r, slot, max(k, 0) * 1920, finished, r.emitted == 0))
-                    r.emitted = n
-                    if finished:
-                        r.stream_done = True
-                        release(r)  # the end marker follows the last chunk, in _deliver
-                    continue
-                if (r.output_format or r.speed_q) and conv is not None and (k > 0 or finished):
-                    chunk = self._converted(r, slot, conv, finished)
-                    if chunk.size:
-                        r.out.put(chunk)
-                    self._counts["frames_delivered"] += max(k, 0)
-                elif k > 0:
-                    assert pcm is not None and r.emitted == (tick_no - r.first_tick) * self.tick, "stream bookkeeping out of step"
-                    r.out.put(pcm[slot, : k * 1920].copy())
-                    self._counts["frames_delivered"] += k
+                if k > 0 or finished:
+                    assert k == 0 or (stream_pass is not None and r.emitted == (tick_no - r.first_tick) * self.tick), "stream bookkeeping out of step"
+                    stream_items.append((r, slot, max(k, 0) * 1920, finished))
+                    urgent = urgent or r.emitted == 0
                 r.emitted = n
                 if finished:
-                    release(r)
-                    self._end(r)
+                    r.stream_done = True
+                    release(r)  # the end marker follows the last chunk, in _deliver
                 continue
             # blocking requests keep only frames whose slow id is a semantic token (generate_blocking, lm/generate.py:196-207)
             slow = codes[slot, r.emitted:n, 0]
@@ -732,9 +664,9 @@ class BatchScheduler:
                 release(r)
                 self._finished.append(r)
         if stream_items:
-            pcm_d, ev, keep, conv_d = stream_pass if stream_pass is not None else (None, None, None, None)
-            urgent = any(it[4] for it in stream_items)  # a first chunk: handed out as soon as the pass is through
-            self._deliveries.append((ev, pcm_d, [it[:4] for it in stream_items], urgent, keep, conv_d))
+            d = stream_pass or _Delivery(None, None, [])
+            d.items, d.urgent = stream_items, urgent
+            self._deliveries.append(d)
 
     # ------------------------------------------------------------------ worker: codec passes and delivery
     def _codec_backlog(self) -> bool:
@@ -764,7 +696,7 @@ class BatchScheduler:
             cols = np.concatenate(r.pending) if r.pending else np.zeros((0, nq), np.int32)
             r.pending = []
             if cols.shape[0] == 0:  # nothing to decode (every frame was non-semantic): just close the response, in order
-                self._deliveries.append((None, None, [(r, 0, 0, True)], False, None, None))
+                self._deliveries.append(_Delivery(None, None, [(r, 0, 0, True)]))
                 continue
             b = jobs.index(None)
             jobs[b] = _CodecJob(r, cols)
@@ -780,8 +712,7 @@ class BatchScheduler:
         self._codec_wait = 0
         # these passes depend on nothing the frame graphs produce on the device (their codes come from the host): they run on
         # the codec stream, beside the ticks
-        side = self._codec_stream if self.overlap_stream_codec else torch.cuda.current_stream()
-        with torch.cuda.stream(side):
+        with torch.cuda.stream(self._codec_stream):
             self._decode_finished_pass(jobs, occupied, nq)
 
     def _decode_finished_pass(self, jobs, occupied, nq) -> None:
@@ -823,7 +754,7 @@ class BatchScheduler:
             items.append((j.req, b, n[b] * 1920, fin))
             if fin:
                 jobs[b] = None
-        self._deliveries.append((ev, pcm, items, False, None, None))
+        self._deliveries.append(_Delivery(ev, pcm, items))
 
     def _deliver(self, wait: bool) -> None:
         """Hand finished codec passes to their requests, in order; ``wait``: block on the oldest one.  Finished stretches of
@@ -831,23 +762,23 @@ class BatchScheduler:
         torch = self._torch
         self._poll_stretches()
         while self._deliveries:
-            ev, pcm, items, _, _, conv = self._deliveries[0]
-            wait = wait or any(d[3] for d in self._deliveries)  # a stream's first chunk is somewhere in the line: do not dawdle
-            host = conv_h = None
-            if ev is not None:
-                if not (wait or ev.query()):
+            d = self._deliveries[0]
+            wait = wait or any(x.urgent for x in self._deliveries)  # a stream's first chunk is somewhere in the line: do not dawdle
+            host = None
+            if d.event is not None:
+                if not (wait or d.event.query()):
                     return
-                self._wait_event(ev)
+                self._wait_event(d.event)
                 with torch.cuda.stream(self._copy_stream):
-                    host = pcm.to("cpu", non_blocking=True)
-                    conv_h = _to_host(conv)
+                    host = d.pcm.to("cpu", non_blocking=True)
+                if d.conv is not None:
+                    d.conv.to_host(self._copy_stream)
                 self._sync_copies()
                 host = host.numpy()
-                conv_h = _numpy(conv_h)
             self._deliveries.pop(0)
-            for r, b, n, fin in items:
-                if r.stream and (r.output_format or r.speed_q) and conv_h is not None:
-                    chunk = self._converted(r, b, conv_h, fin)
+            for r, b, n, fin in d.items:
+                if r.stream and (r.output_format or r.speed_q) and d.conv is not None:
+                    chunk = d.conv.chunk(b, fin)  # (the tail goes out with the last chunk)
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
                         self._counts["frames_delivered"] += n // 1920
@@ -865,20 +796,13 @@ class BatchScheduler:
                     self._end(r)
             wait = False
 
-    def _converted(self, r: _Request, b: int, conv, last: bool) -> np.ndarray:
-        """Slot ``b``'s chunk of a stream pass from its host copy ``conv`` (``_convert``): the converted samples (with the
-        resampler's tail when ``last``), or the stretched float32 of a ``pcm_24000`` request with a speed."""
-        if r.output_format:
-            return self._stream_rs.slot_bytes(conv[0], conv[1], b, tail=last, output_format=r.output_format)  # (the tail goes out with the last chunk)
-        return conv[2][b, : int(conv[3][b])].copy()
-
     STRETCH_SLOTS, STRETCH_PIECE = 16, 65536  # blocking utterances stretched side by side, input samples per slot and call
 
     def _start_stretch(self, r: _Request) -> None:
         """A blocking utterance with a speed is complete: it joins the stretch queue (``_poll_stretches`` runs it)."""
         pcm = np.ascontiguousarray(np.concatenate(r.stretch_in), dtype=np.float32)
         r.stretch_in = []
-        self._stretches.append({"req": r, "pcm": pcm, "pos": 0, "outs": [], "slot": -1})
+        self._stretches.append(_StretchJob(r, pcm))
 
     def _poll_stretches(self) -> None:
         """One step of the blocking utterances' stretches, never waited for.  Up to STRETCH_SLOTS utterances are stretched side by
@@ -894,18 +818,18 @@ class BatchScheduler:
             if not ev.query():
                 return
             out, cnt = out_h.numpy(), cnt_h.numpy()
-            for job, b in ran:
-                if cnt[b]:
-                    job["outs"].append(out[b, : int(cnt[b])].copy())
-            for job in [j for j, _ in ran if j["slot"] == -2]:
-                r = job["req"]
+            for job in ran:
+                if cnt[job.slot]:
+                    job.outs.append(out[job.slot, : int(cnt[job.slot])].copy())
+            for job in [j for j in ran if j.state == "ending"]:
+                r = job.req
                 if not r.cancelled:
-                    r.out.put(np.concatenate(job["outs"]) if job["outs"] else np.zeros(0, np.float32))
+                    r.out.put(np.concatenate(job.outs) if job.outs else np.zeros(0, np.float32))
                 self._end(r)
                 self._stretches.remove(job)
             self._stretch_flight = None
-        for job in [j for j in self._stretches if j["req"].cancelled and j["slot"] == -1]:  # (a running one finishes)
-            self._end(job["req"])
+        for job in [j for j in self._stretches if j.req.cancelled and j.state == "waiting"]:  # (a running one finishes)
+            self._end(job.req)
             self._stretches.remove(job)
         if not self._stretches:
             return
@@ -915,28 +839,28 @@ class BatchScheduler:
             if self._block_ts is None:
                 self._block_ts = TimeStretcher(dev, S)
             ts = self._block_ts
-            used = {j["slot"] for j in self._stretches if j["slot"] >= 0}
+            used = {j.slot for j in self._stretches if j.state == "running"}
             fresh = []
             for job in self._stretches:
-                if job["slot"] == -1 and len(used) < S:
-                    job["slot"] = min(set(range(S)) - used)
-                    used.add(job["slot"])
+                if job.state == "waiting" and len(used) < S:
+                    job.state, job.slot = "running", min(set(range(S)) - used)
+                    used.add(job.slot)
                     fresh.append(job)
             if fresh:
-                ts.reset_slots([j["slot"] for j in fresh], [j["req"].speed_q for j in fresh])
-            running = [j for j in self._stretches if j["slot"] >= 0]
-            batch = max(j["slot"] for j in running) + 1
-            n_in = min(P, max(j["pcm"].size - j["pos"] for j in running))
+                ts.reset_slots([j.slot for j in fresh], [j.req.speed_q for j in fresh])
+            running = [j for j in self._stretches if j.state == "running"]
+            batch = max(j.slot for j in running) + 1
+            n_in = min(P, max(j.pcm.size - j.pos for j in running))
             x_h = torch.zeros(batch, max(n_in, 1), dtype=torch.float32).pin_memory()
             ctl_h = torch.zeros(2, batch, dtype=torch.int32).pin_memory()  # valid, last
             xn, ctl = x_h.numpy(), ctl_h.numpy()
             ending = []
             for job in running:
-                b, piece = job["slot"], job["pcm"][job["pos"]: job["pos"] + n_in]
+                b, piece = job.slot, job.pcm[job.pos: job.pos + n_in]
                 xn[b, : piece.size] = piece
-                job["pos"] += piece.size
+                job.pos += piece.size
                 ctl[0, b] = piece.size
-                if job["pos"] >= job["pcm"].size:
+                if job.pos >= job.pcm.size:
                     ctl[1, b] = 1
                     ending.append(job)
             x = x_h.to(dev, non_blocking=True)
@@ -949,9 +873,9 @@ class BatchScheduler:
             cnt_h.copy_(cnt, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._stretch_stream)
-        self._stretch_flight = (ev, out_h, cnt_h, (x_h, ctl_h, x, ctl_d, out, cnt), [(j, j["slot"]) for j in running])
+        self._stretch_flight = (ev, out_h, cnt_h, (x_h, ctl_h, x, ctl_d, out, cnt), running)
         for job in ending:
-            job["slot"] = -2  # (done once this call is collected; its slot is free for the next call)
+            job.state = "ending"  # (done once this call is collected; its slot is free for the next call)
 
     # ------------------------------------------------------------------ worker: main loop
     def _run(self) -> None:
@@ -992,18 +916,13 @@ class BatchScheduler:
                     self._tick_and_snapshot()          # tick k and its snapshot are queued ...
                     self._decode_finished(force=False)
                     self._deliver(wait=False)
-                    # ... while the host looks at what tick k-1 produced; unless a stream is still waiting for its first
-                    # chunk: then this tick is read as soon as it is done (first-audio latency before pipelining)
-                    first_chunk_due = any(r.stream and r.emitted == 0 for r in self._active.values())
-                    if self.overlap_stream_codec:
-                        # the codec pass of tick k-1 goes out now, beside tick k; reading tick k itself right away (keep=0) would
-                        # leave the GPU idle until the next tick is queued -- with an arrival every other tick that was ~10 % of
-                        # the wall time -- and would not bring the first chunk any earlier: it needs tick k finished either way
-                        self._consume_snapshots(keep=1)
-                        if any(d[3] for d in self._deliveries):
-                            self._deliver(wait=False)  # a first chunk: wait for its pass (the running tick leaves the host slack)
-                    else:
-                        self._consume_snapshots(keep=0 if first_chunk_due else 1)
+                    # ... while the host looks at what tick k-1 produced: the codec pass of tick k-1 goes out now, beside tick
+                    # k.  Reading tick k itself right away (keep=0) would leave the GPU idle until the next tick is queued --
+                    # with an arrival every other tick that was ~10 % of the wall time -- and would not bring a first chunk
+                    # any earlier: it needs tick k finished either way
+                    self._consume_snapshots(keep=1)
+                    if any(d.urgent for d in self._deliveries):
+                        self._deliver(wait=False)  # a first chunk: wait for its pass (the running tick leaves the host slack)
                     if self._side is not None and self._side["state"] == "parked":
                         self._side_advance()  # the tick before the park has been seen to finish: the side call runs beside this one
             self._fail_all(RuntimeError("scheduler closed"))  # requests still in flight when close() was called
@@ -1043,14 +962,14 @@ class BatchScheduler:
             self._end(r, e)
         self._codec_jobs = [None] * len(self._codec_jobs)
         for d in self._deliveries:
-            for r, _, _, _ in d[2]:
+            for r, _, _, _ in d.items:
                 self._end(r, e)
         self._active.clear()
         self._retiring = []
         self._finished = []
         self._deliveries = []
         for job in self._stretches:
-            self._end(job["req"], e)
+            self._end(job.req, e)
         self._stretches = []
         self._stretch_flight = None
         while not self._pending.empty():

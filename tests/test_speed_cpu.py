@@ -245,3 +245,21 @@ def test_null_speed_is_speed_one():
     assert c.post("/v1/text-to-speech/sky", json={"text": "x", "voice_settings": {"speed": None}}).status_code == 200
     assert c.post("/v1/text-to-speech/sky/stream", json={"text": "x", "voice_settings": None}).status_code == 200
     assert model.calls == [("call", None), ("call", None), ("stream", None)]
+
+
+def test_stream_end_rule_same_on_numpy_and_torch():
+    """The scheduler closes a stream on the host and flushes its stretcher on the device with ``stream_ends``: the two must
+    agree for every snapshot."""
+    import torch
+
+    from smoltts_amd.server.scheduler import stream_ends
+
+    n, done, cap = (a.ravel() for a in np.meshgrid(np.arange(8), np.arange(3), np.arange(7), indexing="ij"))
+    n, done, cap = n.astype(np.int32), done.astype(np.int32), cap.astype(np.int32)
+    host = stream_ends(n, done, cap)
+    dev = stream_ends(torch.from_numpy(n), torch.from_numpy(done), torch.from_numpy(cap))
+    assert host.dtype == np.bool_ and dev.dtype == torch.bool
+    assert np.array_equal(host, dev.numpy())
+    for i in range(n.size):  # one slot of a snapshot, as _drain reads it: stopped with a frame, or the budget reached
+        want = (bool(done[i]) and int(n[i]) > 0) or min(int(n[i]), int(cap[i])) >= int(cap[i])
+        assert bool(stream_ends(n[i], done[i], int(cap[i]))) == bool(host[i]) == want

@@ -217,8 +217,7 @@ def test_facade_stream_and_call_with_speed(tts, overlap, monkeypatch):
         tts(text, voice, generation_settings=gs, speed=5.0)
 
 
-@pytest.mark.parametrize("overlap", [True, False])
-def test_scheduler_speeds_and_formats(tts, overlap, monkeypatch):
+def test_scheduler_speeds_and_formats(tts, monkeypatch):
     from smoltts_amd.config import GenerationSettings
     from smoltts_amd.formats import lin2ulaw
     from smoltts_amd.server.scheduler import BatchScheduler
@@ -226,15 +225,14 @@ def test_scheduler_speeds_and_formats(tts, overlap, monkeypatch):
     reqs = [("first at one and a half", "heart", 9, 1.5, None), ("second slow and narrow", "sky", 12, 0.5, "pcm_16000"),
             ("third on the telephone", "nova", 7, 2.0, "ulaw_8000"), ("fourth stays plain", "bella", 10, None, "pcm_16000"),
             ("fifth refills a slot", "liam", 8, 4.0, None), ("sixth slow float", "heart", 6, 0.25, None)]
-    sched = BatchScheduler(tts, max_batch=4, frames_per_tick=2, generation_settings=GenerationSettings.greedy(max_new_tokens=300),
-                           overlap_stream_codec=overlap)
+    sched = BatchScheduler(tts, max_batch=4, frames_per_tick=2, generation_settings=GenerationSettings.greedy(max_new_tokens=300))
     try:
         # the references: the same requests without speed or format, float32 from this scheduler
         base = {t: np.concatenate(list(sched.iter_chunks(sched.submit(t, v, stream=True, max_new_tokens=n)))) for t, v, n, _, _ in reqs}
         plain_block = np.concatenate(list(sched.iter_chunks(sched.submit("a blocking one", "sky", max_new_tokens=11))))
         launches = _Launches(monkeypatch)
         again = np.concatenate(list(sched.iter_chunks(sched.submit(reqs[0][0], "heart", stream=True, max_new_tokens=9, speed=1.0))))
-        assert np.array_equal(again, base[reqs[0][0]]) and launches.n == 0 and sched._stream_ts is None
+        assert np.array_equal(again, base[reqs[0][0]]) and launches.n == 0 and sched._stream_conv.ts is None
         handles = [sched.submit(t, v, stream=True, max_new_tokens=n, speed=s, output_format=f) for t, v, n, s, f in reqs]
         blocking = sched.submit("a blocking one", "sky", max_new_tokens=11, speed=0.8)
         got = [np.concatenate(list(sched.iter_chunks(h))) for h in handles]

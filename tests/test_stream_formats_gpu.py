@@ -192,8 +192,7 @@ def test_facade_stream_output_format(tts, overlap):
         next(tts.stream("x", "sky", generation_settings=gs, output_format="flac_8000"))
 
 
-@pytest.mark.parametrize("overlap", [True, False])
-def test_scheduler_mixed_formats_match_the_facade(tts, overlap):
+def test_scheduler_mixed_formats_match_the_facade(tts):
     from smoltts_amd.config import GenerationSettings
     from smoltts_amd.server.scheduler import BatchScheduler
 
@@ -204,8 +203,7 @@ def test_scheduler_mixed_formats_match_the_facade(tts, overlap):
     for text, voice, n, fmt in reqs:
         gs = GenerationSettings.greedy(max_new_tokens=n)
         want.append(np.concatenate(list(tts.stream(text, voice, generation_settings=gs, output_format=fmt))))
-    sched = BatchScheduler(tts, max_batch=4, frames_per_tick=2, generation_settings=GenerationSettings.greedy(max_new_tokens=300),
-                           overlap_stream_codec=overlap)
+    sched = BatchScheduler(tts, max_batch=4, frames_per_tick=2, generation_settings=GenerationSettings.greedy(max_new_tokens=300))
     got = [None] * len(reqs)
     try:
         # one request is cancelled mid-stream: its slot is refilled, the others do not notice
