@@ -31,7 +31,10 @@ ARCH = "gfx950"
 # their first loads need in front of their argument struct; measured +2 % frames/s)
 PRODUCT_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 NAMED_VARIANTS = {"hooks": ["-DSMOLTTS_DEBUG_HOOKS"],  # event hooks + in-kernel cycle stamps for tools/
-                  "knobs": ["-DSMOLTTS_DBG_KNOBS"]}    # the experiment environment switches of tools/ (forced tiles, kernels off)
+                  "knobs": ["-DSMOLTTS_DBG_KNOBS"],    # the experiment environment switches of tools/ (forced tiles, kernels off)
+                  # gemm3_kernel / attn_wo_kernel fill their dynamic LDS with quiet NaN at entry: tests/test_attn_wo_matrix_gpu.py
+                  # requires the same output bytes as the product library (no LDS word is read before it is written)
+                  "lds_poison": ["-DSMOLTTS_DBG_LDS_POISON"]}
 
 
 def _hipcc() -> str:

@@ -84,6 +84,19 @@ constexpr int AWO_KERNARG_LINES = (0x38 + (int)sizeof(Gemm3Dev) - 1) / 64;  // a
 #define STAMP3(k) do { } while (0)
 #endif
 
+// Test builds only (python -m smoltts_amd.build --variant lds_poison): every word of the kernel's dynamic LDS starts as a quiet NaN
+// (0x7fc07fc0: a NaN as fp32 and as both of its bf16 halves), so that a word read before it is written shows up in an output instead
+// of whatever the previous workgroup left there.  Called by all threads at kernel entry; the barrier is the variant's own.
+__device__ __forceinline__ void lds_poison(float* smem, size_t bytes) {
+#ifdef SMOLTTS_DBG_LDS_POISON
+  uint32_t* s = reinterpret_cast<uint32_t*>(smem);
+  for (size_t i = threadIdx.x; i < bytes / 4; i += blockDim.x) s[i] = 0x7fc07fc0u;
+  __syncthreads();
+#else
+  (void)smem; (void)bytes;
+#endif
+}
+
 // Weight tiles are read once per launch by the one or two workgroups that own them: with
 // SMOLTTS_NT_W the loads carry the non-temporal hint (MI355X_MICROARCH.md 'nt-weights').
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -151,6 +164,7 @@ __global__ __launch_bounds__(512) void gemm3_kernel(const char* w_, const char* 
   const int mg = p.half_rows ? (blockIdx.y >> 1) : blockIdx.y;
   const bool row_on = !p.half_rows || ((r >> 3) == (int)(blockIdx.y & 1));  // this lane's row belongs to the workgroup
   const int nchunks = p.K >> 5;
+  lds_poison(smem, (size_t)nwaves * T * MT * 1024 + (size_t)MT * 16 * sizeof(float));  // (launch3_one's lds)
   constexpr bool kResid = EPI == SMOLTTS_EPI_RESID;
   constexpr bool kEmits = EPI == SMOLTTS_EPI_RESID || EPI == SMOLTTS_EPI_STORE;
   constexpr bool kRope = EPI == SMOLTTS_EPI_QKV_ROPE;
@@ -824,6 +838,7 @@ __global__ __launch_bounds__(768) void attn_wo_kernel(const char* w_, const floa
   const int nb = FULL ? NBF : ((nchunks + 2) / 3 < 1 ? 1 : ((nchunks + 2) / 3 > NB ? NB : (nchunks + 2) / 3));
   char* frag = reinterpret_cast<char*>(smem);  // [chunk][piece][q][row] x 16 B
   float4* red4 = reinterpret_cast<float4*>(frag + (size_t)nchunks * 3 * 4 * R * 16);  // [GEMM wave][tile][lane]
+  lds_poison(smem, (size_t)nchunks * 3 * 4 * R * 16 + (size_t)NB * T * 1024);  // (launch_attn_wo_g's lds)
   STAMP3(0);
 
   // Two kinds of waves, because a CU takes its operands in at ~64 B per clock whatever the waves do: the
@@ -1003,8 +1018,13 @@ static int launch_attn_wo_g(const Gemm3Dev& d, hipStream_t stream) {
              "gemm3: attention + wo: sizes out of the packed arguments' range");
   const int nb_full = ((nchunks == 8 * AWO_U || nchunks == 6 * AWO_U) && ntiles % T == 0) ? nchunks / AWO_U : 0;
   const int m_tiles = d.M | (d.pk_tiles << 16), heads_pos = d.n_q_heads | (d.n_kv_heads << 8) | (d.cache_len << 16) | (d.a_pos << 24);
-#define ST_AWO(TT, TWO_, PK_) \
-  do { if (nb_full == 8) ST_AWO_(TT, TWO_, PK_, 8); else if (nb_full == 6) ST_AWO_(TT, TWO_, PK_, 6); else ST_AWO_(TT, TWO_, PK_, 0); } while (0)
+  // (nb_full == 6 means K = 576, i.e. 9 query heads: groups of 1 or 3 only -- no <2|4, .., 6> form is instantiated)
+#define ST_AWO(TT, TWO_, PK_)                                                                            \
+  do {                                                                                                   \
+    if (nb_full == 8) ST_AWO_(TT, TWO_, PK_, 8);                                                         \
+    else if (nb_full == 6) ST_AWO_(TT, TWO_, PK_, ((G == 1 || G == 3) ? 6 : 0));                          \
+    else ST_AWO_(TT, TWO_, PK_, 0);                                                                      \
+  } while (0)
 #define ST_AWO_(TT, TWO_, PK_, FULL_)                                                                                                   \
   hipLaunchKernelGGL((attn_wo_kernel<G, TT, TWO_, W8, PK_, FULL_>), grid, block, lds, stream, d.w, (const float*)d.kc, (const float*)d.vc, \
                      PK_ ? d.pk_cand : d.aq, d.pk_table, m_tiles, d.N, d.K, heads_pos, d)

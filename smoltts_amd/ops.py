@@ -9,6 +9,7 @@ All of them run the HIP kernels; nothing here computes on the CPU.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -254,6 +255,44 @@ class Gemm3Args(C.Structure):
     ]
 
 
+class PickArgs(C.Structure):  # SmolttsPickArgs (include/smoltts_hip.h)
+    _fields_ = [
+        ("cand_dev", C.c_void_p), ("cand_tiles", C.c_int32), ("qkv_table_dev", C.c_void_p), ("rope_dev", C.c_void_p),
+        ("emb_dev", C.c_void_p), ("emb_row_offset", C.c_int32), ("ids_dev", C.c_void_p), ("ids_stride", C.c_int32),
+        ("margin_dev", C.c_void_p), ("margin_mask_dev", C.c_void_p), ("margin_at_dev", C.c_void_p), ("frames_dev", C.c_void_p),
+        ("step", C.c_int32),
+    ]
+
+
+@dataclass
+class Pick:
+    """The previous depth step's greedy pick in front of ``linear3``'s attention prologue (``SmolttsPickArgs``).
+    ``cand`` [M][tiles][4] from the head GEMM's ``cand_out``; ``table`` fp32 [rows][(Hq + 2 KV) * 64] (q | k | v before RoPE);
+    ``rope`` fp32 [pos][32][2]; ``emb`` bf16 [rows][K]; row = id + ``emb_row_offset``; ids land in ``ids[r * ids_stride]``;
+    ``margin`` / ``margin_mask`` / ``margin_at`` / ``frames`` / ``step``: the top-2 gap records of ``argmax``."""
+    cand: torch.Tensor
+    table: torch.Tensor
+    rope: torch.Tensor
+    emb: torch.Tensor
+    ids: torch.Tensor
+    ids_stride: int = 1
+    emb_row_offset: int = 0
+    margin: Optional[torch.Tensor] = None
+    margin_mask: Optional[torch.Tensor] = None
+    margin_at: Optional[torch.Tensor] = None
+    frames: Optional[torch.Tensor] = None
+    step: int = 0
+
+    def args(self) -> PickArgs:
+        k = PickArgs()
+        k.cand_dev, k.cand_tiles = E.dptr(self.cand), self.cand.shape[1]
+        k.qkv_table_dev, k.rope_dev, k.emb_dev, k.emb_row_offset = E.dptr(self.table), E.dptr(self.rope), E.dptr(self.emb), self.emb_row_offset
+        k.ids_dev, k.ids_stride = E.dptr(self.ids), self.ids_stride
+        k.margin_dev, k.margin_mask_dev = E.dptr(self.margin), E.dptr(self.margin_mask)
+        k.margin_at_dev, k.frames_dev, k.step = E.dptr(self.margin_at), E.dptr(self.frames), self.step
+        return k
+
+
 def pack_weight_fp8(w: torch.Tensor):
     """Row-major [N, K] -> (e4m3 T16x32 tiles, fp32 row scales) on the current GPU, and the dequantised matrix."""
     from .packing import quantize_fp8_rows
@@ -271,11 +310,13 @@ def linear3(x3: torch.Tensor, w_tiles: torch.Tensor, M: int, N: int, K: int, *, 
             n_q_heads: int = 0, n_kv_heads: int = 0, cache_len: int = 0, w_scale: Optional[torch.Tensor] = None,
             v_x3: Optional[torch.Tensor] = None, kv_format: int = 0, w_stream: bool = False,
             attn_q: Optional[torch.Tensor] = None, attn_pos: int = 0, cand_out: Optional[torch.Tensor] = None,
-            fp8_activations: bool = False):
+            fp8_activations: bool = False, pick: Optional[Pick] = None):
     """The bf16-MFMA GEMM over an X3 operand; returns the fp32 ``out`` tensor (None for SWIGLU).
     ``w_scale`` given: ``w_tiles`` are e4m3 tiles (``pack_weight_fp8``).
     ``attn_q`` given (EPI_RESID): ``x3`` may be None -- the operand is the attention of ``attn_q`` over keys 0..``attn_pos`` of
-    ``k_cache`` / ``v_cache`` (row r = slot r), worked out inside the launch (attn_wo_kernel)."""
+    ``k_cache`` / ``v_cache`` (row r = slot r), worked out inside the launch (attn_wo_kernel).
+    ``pick`` given (EPI_RESID, ``attn_pos`` >= 1): ``attn_q`` and ``resid`` are not read -- each row's q, newest K / V and residual
+    come from the table / embedding rows of its picked id (``Pick``), and the new K / V rows are written to the caches."""
     lib = E.load_library()
     lib.smoltts_k_gemm3.argtypes = [C.POINTER(Gemm3Args), C.c_void_p]
     if out is None and epilogue != E.EPI_SWIGLU:
@@ -299,5 +340,7 @@ def linear3(x3: torch.Tensor, w_tiles: torch.Tensor, M: int, N: int, K: int, *, 
     a.attn_q_dev, a.attn_pos = E.dptr(attn_q), int(attn_pos)
     a.fp8_activations = 1 if fp8_activations else 0  # fp8 weights, M >= 256: fp8 x fp8 MFMA on the activation's hi piece (not the parity path)
     a.cand_out_dev = E.dptr(cand_out)  # EPI_STORE: per (row, 16-column tile) (max, first column of it as int bits, runner-up, -)
+    pk = pick.args() if pick is not None else None  # (kept alive across the call)
+    a.pick = C.cast(C.pointer(pk), C.c_void_p) if pk is not None else None
     E.check(lib.smoltts_k_gemm3(C.byref(a), E.current_stream_ptr()), "smoltts_k_gemm3")
     return out
