@@ -539,6 +539,47 @@ int smoltts_tsm_chunk(SmolttsTsm* t, const float* pcm_dev, int64_t pcm_stride, i
  * state_host[5]; synchronises the stream. */
 int smoltts_tsm_slot_state(SmolttsTsm* t, int32_t slot, int64_t* state_host, void* stream);
 
+/* ------------------------------------------------------------------------------ FLAC
+ * Lossless framing of a stream (smoltts_amd/csrc/flac.hip; the numpy model and parity oracle is
+ * smoltts_amd/flac.py): RFC 9639 frames, mono, 16 bits, variable blocking (the coded number is the sample number of the block's
+ * first sample), subframes CONSTANT / FIXED 0..4 with partitioned Rice residuals / VERBATIM, fewest bits wins.  Every choice is
+ * an integer function of the int16 samples, so the bytes equal the model's.  A slot holds back at most 15 samples: with 16 or
+ * more pending, or any at its last call, it emits all of them as ceil(P / 4096) blocks sized as evenly as possible.  The stream
+ * header (fLaC + STREAMINFO) is the host's. */
+typedef struct SmolttsFlac SmolttsFlac;
+enum {
+  SMOLTTS_FLAC_OFF = 0,
+  SMOLTTS_FLAC_F32 = 1, /* the slot reads fp32 PCM, quantised as rint(clip(x, -1, 1) * 32767) */
+  SMOLTTS_FLAC_S16 = 2  /* the slot reads the resampler's int16 output */
+};
+
+/* Device slab of an encoder for max_batch slots (256-byte aligned, caller-owned): each slot's source and rate, and two copies of
+ * each slot's stream state (the int64 position, up to 15 pending samples).  Every slot starts off. */
+size_t smoltts_flac_bytes(int32_t max_batch);
+int smoltts_flac_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsFlac** out);
+void smoltts_flac_destroy(SmolttsFlac* f);
+/* For calls in which a slot reads at most n_max samples: the blocks a slot may emit, and the output row bytes (2 (n_max + 15)
+ * plus 20 per block: a frame of n samples takes at most 2 n + 17 bytes). */
+int32_t smoltts_flac_max_blocks(int32_t n_max);
+size_t smoltts_flac_out_bytes(int32_t n_max);
+
+/* Start new streams in the listed slots (host arrays) at their rate (8000, 16000, 22050, 24000, 44100, 48000) and source
+ * (SMOLTTS_FLAC_*; OFF switches the slot off); the other slots' streams continue.  Stream-ordered. */
+int smoltts_flac_reset_slots(SmolttsFlac* f, const int32_t* slots_host, const int32_t* rates_host, const int32_t* sources_host,
+                             int32_t n_slots, void* stream);
+
+/* One launch for slots [0, batch), no host read.  An F32 slot b consumes valid_in_dev[b] (clamped to [0, n_in]; NULL = n_in)
+ * samples of pcm_dev float [batch][pcm_stride]; an S16 slot consumes s16_counts_dev[2b] (+ s16_counts_dev[2b + 1] when it is
+ * last) little-endian int16 samples of s16_dev [batch][s16_stride bytes] (the resampler's bytes and counts of the same pass).
+ * last_dev[b] nonzero (NULL = none) ends the slot's stream with this call.  Slot b writes its frames to out_dev [batch]
+ * [out_stride] (out_stride >= smoltts_flac_out_bytes(n_max), n_max the most samples a slot of the call can read) and
+ * sizes_dev int32 [batch][max_blocks][2] = {byte offset in the row, bytes} per frame in order, {0, 0} past its last; slots
+ * that are off write {0, 0} only.  Calls on one encoder must be ordered on one stream (the states alternate between copies). */
+int smoltts_flac_chunk(SmolttsFlac* f, const float* pcm_dev, int64_t pcm_stride, int32_t n_in, const int32_t* valid_in_dev,
+                       const void* s16_dev, int64_t s16_stride, const int32_t* s16_counts_dev, int32_t batch,
+                       const int32_t* last_dev, void* out_dev, int64_t out_stride, int32_t* sizes_dev, int32_t max_blocks,
+                       void* stream);
+
 /* --------------------------------------------------------------- operator-level test entry points */
 enum {  /* prologue applied to the activation operand */
   SMOLTTS_PRO_NONE = 0,

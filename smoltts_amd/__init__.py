@@ -200,7 +200,7 @@ class SmolTTS:
 
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
                reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None,
-               speed: Optional[float] = None) -> Iterator["np.ndarray"]:
+               speed: Optional[float] = None, container: Optional[str] = None) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -214,14 +214,18 @@ class SmolTTS:
         ``scipy.signal.resample_poly`` of the float32 stream, quantised (formats.py).  ``None`` / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling`` (as in ``generate_codes``); it is resolved when the generator starts.
         ``speed`` (0.25 to 4.0; None / 1.0: unchanged): the stream is time-stretched on the GPU in front of the conversion; each
-        chunk holds the samples that became final with its frame (none for some frames: no chunk then)."""
+        chunk holds the samples that became final with its frame (none for some frames: no chunk then).
+        ``container``: ``"flac"`` frames the stream's 16-bit samples (``output_format`` ``pcm_<rate>``, the float32 of
+        ``pcm_24000`` quantised as rint(clip(x, -1, 1) * 32767)) as FLAC on the GPU: uint8 chunks, the stream header in front of
+        the first, which decode to exactly those samples (flac.py)."""
         import numpy as np
 
-        from .formats import parse_stream_format
+        from .formats import check_container, parse_stream_format
         from .tsm import parse_speed
 
         if output_format is not None:
             parse_stream_format(output_format)  # an unknown format is refused before any work
+        check_container(container, output_format)
         sq = parse_speed(speed)
 
         from .engine import LMSession, MimiSession
@@ -241,7 +245,8 @@ class SmolTTS:
             _apply_slot_sampling(sess, [0], resolved)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
-            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=output_format, speed_q=sq)
+            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=output_format, speed_q=sq,
+                                  container=container)
         finally:
             msess.close()
             sess.close()

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .config import NumericsMode, RQTransformerModelArgs, TokenConfig
-from .formats import ENC_OFF, parse_stream_format
+from .formats import ENC_OFF, check_container, parse_stream_format
 from .tsm import out_bound
 from . import packing
 
@@ -120,6 +120,8 @@ _EXPORTS = [
     "smoltts_resampler_out_bytes", "smoltts_resampler_reset_slots", "smoltts_resample_chunk",
     "smoltts_tsm_bytes", "smoltts_tsm_create", "smoltts_tsm_destroy", "smoltts_tsm_out_samples", "smoltts_tsm_reset_slots",
     "smoltts_tsm_chunk", "smoltts_tsm_slot_state",
+    "smoltts_flac_bytes", "smoltts_flac_create", "smoltts_flac_destroy", "smoltts_flac_max_blocks", "smoltts_flac_out_bytes",
+    "smoltts_flac_reset_slots", "smoltts_flac_chunk",
     "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows",
     "smoltts_prefix_kv_bytes", "smoltts_session_save_prefix", "smoltts_session_install_prefix",
 ]
@@ -233,6 +235,18 @@ def load_library(path: Optional[Path] = None):
     lib.smoltts_tsm_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.c_void_p, C.c_void_p]
     lib.smoltts_tsm_slot_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.smoltts_flac_bytes.argtypes = [C.c_int32]
+    lib.smoltts_flac_bytes.restype = C.c_size_t
+    lib.smoltts_flac_max_blocks.argtypes = [C.c_int32]
+    lib.smoltts_flac_max_blocks.restype = C.c_int32
+    lib.smoltts_flac_out_bytes.argtypes = [C.c_int32]
+    lib.smoltts_flac_out_bytes.restype = C.c_size_t
+    lib.smoltts_flac_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.smoltts_flac_destroy.argtypes = [C.c_void_p]
+    lib.smoltts_flac_destroy.restype = None
+    lib.smoltts_flac_reset_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.smoltts_flac_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
     lib.smoltts_prefix_kv_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.smoltts_prefix_kv_bytes.restype = C.c_size_t
     lib.smoltts_session_save_prefix.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(PrefixHeader), C.c_void_p]
@@ -1079,54 +1093,183 @@ class TimeStretcher:
             pass
 
 
+# ------------------------------------------------------------------------------- FLAC framing
+FLAC_OFF, FLAC_F32, FLAC_S16 = 0, 1, 2  # SMOLTTS_FLAC_*
+
+
+class FlacEncoder:
+    """Per-slot FLAC framing of streamed samples on the GPU (include/smoltts_hip.h, "FLAC"; the numpy model is
+    ``flac.StreamEncoder``): one launch per call for every slot, each reading fp32 PCM or the resampler's int16 at its own rate.
+    Slots start off; ``reset_slots`` starts a new stream in a slot.  The stream header (``flac.stream_header``) is the caller's."""
+
+    def __init__(self, device: torch.device, max_batch: int):
+        self.lib = load_library()
+        self.device, self.B = device, max_batch
+        need = self.lib.smoltts_flac_bytes(max_batch)
+        if need == 0:
+            raise SmolttsError("smoltts_flac_bytes returned 0 (bad sizes)")
+        self.slab = _alloc_slab(need, device, settle=True)
+        h = C.c_void_p()
+        check(self.lib.smoltts_flac_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_flac_create")
+        self.handle = h
+        self.source = [FLAC_OFF] * max_batch
+        self.rate = [0] * max_batch
+
+    def reset_slots(self, slots: Sequence[int], rates: Sequence[int], sources: Sequence[int]) -> None:
+        """Start new streams in ``slots`` at their rate and source (``FLAC_F32`` / ``FLAC_S16``; ``FLAC_OFF``: off)."""
+        n = len(slots)
+        arr = lambda v: (C.c_int32 * n)(*[int(x) for x in v])  # noqa: E731
+        check(self.lib.smoltts_flac_reset_slots(self.handle, arr(slots), arr(rates), arr(sources), n, current_stream_ptr()),
+              "smoltts_flac_reset_slots")
+        for b, r, src in zip(slots, rates, sources):
+            self.rate[b], self.source[b] = int(r), int(src)
+
+    def new_outputs(self, batch: int, n_max: int):
+        """Device buffers of one call in which a slot reads at most ``n_max`` samples: (bytes uint8 [batch, out_bytes],
+        sizes int32 [batch, max_blocks, 2])."""
+        blocks = int(self.lib.smoltts_flac_max_blocks(int(n_max)))
+        return (torch.empty(batch, int(self.lib.smoltts_flac_out_bytes(int(n_max))), dtype=torch.uint8, device=self.device),
+                torch.empty(batch, blocks, 2, dtype=torch.int32, device=self.device))
+
+    def chunk(self, batch: int, out: torch.Tensor, sizes: torch.Tensor, pcm: Optional[torch.Tensor] = None, n_in: int = 0,
+              valid: Optional[torch.Tensor] = None, s16: Optional[torch.Tensor] = None, s16_counts: Optional[torch.Tensor] = None,
+              last: Optional[torch.Tensor] = None) -> None:
+        """Frame the samples of slots [0, batch) on the current stream: F32 slots read ``n_in`` samples of ``pcm`` (device fp32
+        [batch, >= n_in]; ``valid``: device int32 [batch], the real ones), S16 slots the resampler's ``s16`` bytes (uint8
+        [batch, row]) and ``s16_counts`` (int32 [batch, 2]: finals, tail); ``last`` (device int32 [batch]) nonzero where the
+        stream ends with this call.  ``sizes[b, j]``: {offset, bytes} of slot b's frame j in ``out[b]``."""
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[0] >= batch
+        assert sizes.dtype == torch.int32 and sizes.is_contiguous() and sizes.shape[0] >= batch
+        if pcm is not None:
+            assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and 0 <= n_in <= pcm.shape[1] and pcm.shape[0] >= batch
+        if s16 is not None:
+            assert s16.dtype == torch.uint8 and s16.is_contiguous() and s16_counts is not None and s16_counts.is_contiguous()
+        for t in (valid, last):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= batch)
+        check(self.lib.smoltts_flac_chunk(self.handle, dptr(pcm), pcm.stride(0) if pcm is not None else 0, int(n_in), dptr(valid),
+                                          dptr(s16), s16.shape[1] if s16 is not None else 0, dptr(s16_counts), batch, dptr(last),
+                                          dptr(out), out.shape[1], dptr(sizes), sizes.shape[1], current_stream_ptr()),
+              "smoltts_flac_chunk")
+
+    @staticmethod
+    def slot_frames(host_out: np.ndarray, host_sizes: np.ndarray, b: int) -> List[bytes]:
+        """Slot ``b``'s frames of a call, in order, from the host copies of ``out`` and ``sizes``."""
+        frames = []
+        for off, n in host_sizes[b]:
+            if n <= 0:
+                break
+            frames.append(host_out[b, int(off):int(off) + int(n)].tobytes())
+        return frames
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize()
+            self.lib.smoltts_flac_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def flac_encode(samples: np.ndarray, sample_rate: int, device: torch.device) -> bytes:
+    """A whole utterance as one FLAC file, framed on ``device`` in one call with ``last`` set: float32 samples are quantised as
+    rint(clip(x, -1, 1) * 32767), int16 ones taken as they are.  The STREAMINFO carries the true total, the smallest and largest
+    frame and the MD5 of the samples (``SmolTTS.__call__``).  Waits for the result."""
+    from . import flac
+
+    x = np.asarray(samples).reshape(-1)
+    is_f32 = x.dtype != np.int16
+    x = np.ascontiguousarray(x, dtype=np.float32 if is_f32 else np.int16)
+    s16 = flac.quantize(x) if is_f32 else x
+    n = int(x.size)
+    with torch.cuda.device(device):
+        fe = FlacEncoder(device, 1)
+        try:
+            fe.reset_slots([0], [sample_rate], [FLAC_F32 if is_f32 else FLAC_S16])
+            last = torch.ones(1, dtype=torch.int32, device=device)
+            out, sizes = fe.new_outputs(1, n)
+            if is_f32:
+                pcm = torch.from_numpy(x).to(device)[None] if n else torch.zeros(1, 1, dtype=torch.float32, device=device)
+                fe.chunk(1, out, sizes, pcm=pcm, n_in=n, last=last)
+            else:
+                raw = torch.from_numpy(x.view(np.uint8).copy()).to(device)[None] if n else torch.zeros(1, 2, dtype=torch.uint8, device=device)
+                counts = torch.tensor([[n, 0]], dtype=torch.int32, device=device)
+                fe.chunk(1, out, sizes, s16=raw, s16_counts=counts, last=last)
+            frames = FlacEncoder.slot_frames(out.cpu().numpy(), sizes.cpu().numpy(), 0)
+        finally:
+            fe.close()
+    return flac.file_from_frames(frames, s16, sample_rate)
+
+
 # ------------------------------------------------------------------------------- a stream's stages behind the codec
 class StreamConverter:
     """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch``: a slot with a speed is time-stretched
     (``TimeStretcher``), then a slot with an output format is converted (``Resampler``, from the stretched samples where the
-    slot has a speed).  Each stage is created the first time a slot needs it.  ``n_in``: codec samples per slot and call; the
+    slot has a speed), then a slot with a FLAC container is framed (``FlacEncoder``, from the resampler's int16, or from the
+    float32 at 24 kHz).  Each stage is created the first time a slot needs it.  ``n_in``: codec samples per slot and call; the
     resampler takes up to the stretcher's output of that many."""
 
     def __init__(self, device: torch.device, max_batch: int, n_in: int):
         self.device, self.B, self.n_in = device, max_batch, n_in
         self.rs: Optional[Resampler] = None
         self.ts: Optional[TimeStretcher] = None
+        self.fl: Optional[FlacEncoder] = None
+        self.gen = [0] * max_batch           # streams started in each slot
+        self.head_owed = [-1] * max_batch    # the stream (gen) of the slot whose FLAC header has not been handed out yet
 
-    def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]]) -> None:
+    def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]],
+                    containers: Optional[Sequence[Optional[str]]] = None) -> None:
         """Start new streams in ``slots`` on the current stream: ``formats[i]`` an ``output_format`` (None / ``pcm_24000``:
-        float32), ``speed_q[i]`` a Q16 speed (None / 65536: none).  A slot with neither is switched off."""
+        float32), ``speed_q[i]`` a Q16 speed (None / 65536: none), ``containers[i]`` None or ``"flac"`` (FLAC frames of the
+        slot's 16-bit samples at its rate).  A slot with none of them is switched off."""
         if not slots:
             return
         formats = [f or "pcm_24000" for f in formats]
         speed_q = [q or 65536 for q in speed_q]
+        containers = [check_container(c, f) for c, f in zip(containers or [None] * len(slots), formats)]
         if self.rs is None and any(parse_stream_format(f)[1] != ENC_OFF for f in formats):
             self.rs = Resampler(self.device, self.B, out_bound(self.n_in))
         if self.ts is None and any(q != 65536 for q in speed_q):
             self.ts = TimeStretcher(self.device, self.B)
+        if self.fl is None and any(containers):
+            self.fl = FlacEncoder(self.device, self.B)
         if self.rs is not None:
             self.rs.reset_slots(slots, formats)
         if self.ts is not None:
             self.ts.reset_slots(slots, speed_q)
+        if self.fl is not None:
+            parsed = [parse_stream_format(f) for f in formats]
+            self.fl.reset_slots(slots, [p[0] for p in parsed],
+                                [FLAC_OFF if c is None else (FLAC_F32 if p[1] == ENC_OFF else FLAC_S16) for c, p in zip(containers, parsed)])
+        for b, c in zip(slots, containers):
+            self.gen[b] += 1
+            self.head_owed[b] = self.gen[b] if c else -1
 
     def run(self, pcm: torch.Tensor, n_in: int, valid: torch.Tensor, last: Optional[torch.Tensor] = None,
             slots: Optional[Sequence[int]] = None) -> Optional["StreamPass"]:
         """Queue the stages for ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in]) on the current stream.
         ``valid`` (device int32 [batch]): the samples of each row that are real; ``last`` (device int32 [batch], needed when a
-        slot has a speed): nonzero where the row's stream ends with this call.  ``slots``: the live streams (default: every
-        slot); the others consume what ``valid`` gives them and are never read.  None when no live slot converts: no launch."""
+        slot has a speed or a FLAC container): nonzero where the row's stream ends with this call.  ``slots``: the live streams
+        (default: every slot); the others consume what ``valid`` gives them and are never read.  None when no live slot
+        converts: no launch."""
         slots = range(self.B) if slots is None else slots
         fmt = [b for b in slots if self.rs is not None and self.rs.formats[b][1] != ENC_OFF]
         spd = [b for b in slots if self.ts is not None and self.ts.speed_q[b] != 65536]
-        if not (fmt or spd):
+        flc = [b for b in slots if self.fl is not None and self.fl.source[b] != FLAC_OFF]
+        if not (fmt or spd or flc):
             return None
         batch = pcm.shape[0]
         src, rs_valid = pcm, valid
-        out = counts = stretched = st_counts = None
+        out = counts = stretched = st_counts = fout = fsizes = None
         if spd:
             stretched, st_counts = self.ts.new_outputs(batch, n_in)
             self.ts.chunk(pcm, n_in, stretched, st_counts, valid=valid, last=last)
             src, rs_valid = stretched, st_counts
-            plain = [b for b in fmt if b not in spd]
-            if plain:  # one resample launch for all: the codec's rows of formatted slots without a speed join the stretched rows
+            plain = [b for b in fmt + flc if b not in spd]
+            if plain:  # one launch per stage for all: the codec's rows of slots without a speed join the stretched rows
                 sped = np.zeros(batch, np.int32)
                 sped[spd] = 1
                 sped_d, plain_d = upload([sped, np.asarray(plain, np.int64)], self.device)
@@ -1136,25 +1279,36 @@ class StreamConverter:
         if fmt:
             out, counts = self.rs.new_outputs(batch, n_in)
             self.rs.chunk(src, n_in, out, counts, valid=rs_valid)
-        if not any(b not in fmt for b in spd):  # every stretched slot is converted: its float32 is not read
+        if flc:
+            s16_max = out.shape[1] // 2 if out is not None and any(self.fl.source[b] == FLAC_S16 for b in flc) else 0
+            fout, fsizes = self.fl.new_outputs(batch, max(n_in, s16_max))
+            self.fl.chunk(batch, fout, fsizes, pcm=src, n_in=n_in, valid=rs_valid, s16=out if s16_max else None,
+                          s16_counts=counts if s16_max else None, last=last)
+        if not any(b not in fmt and b not in flc for b in spd):  # every stretched slot is converted: its float32 is not read
             stretched = st_counts = None
-        return StreamPass(self.rs, [f[1] for f in self.rs.formats] if fmt else None, out, counts, stretched, st_counts)
+        if fmt and all(b in flc for b in fmt):  # every converted slot is framed: its int16 is not read
+            out = counts = None
+        heads = {b: (self.gen[b], self.fl.rate[b]) for b in flc}
+        return StreamPass(self.rs, [f[1] for f in self.rs.formats] if fmt else None, out, counts, stretched, st_counts, fout, fsizes,
+                          conv=self, heads=heads)
 
     def close(self):
-        for stage in (self.rs, self.ts):
+        for stage in (self.rs, self.ts, self.fl):
             if stage is not None:
                 stage.close()
-        self.rs = self.ts = None
+        self.rs = self.ts = self.fl = None
 
 
 class StreamPass:
     """The outputs of one ``StreamConverter.run``: on the device, then (``to_host``) on the host, read slot by slot (``chunk``).
     It keeps the slots' encodings of its run: a slot may have been restarted by the time its chunk is read."""
 
-    def __init__(self, rs: Optional[Resampler], enc: Optional[List[int]], *device_outputs):
+    def __init__(self, rs: Optional[Resampler], enc: Optional[List[int]], *device_outputs, conv: Optional[StreamConverter] = None,
+                 heads: Optional[Dict[int, tuple]] = None):
         self.rs, self.enc = rs, enc
-        self.dev = device_outputs  # (bytes, counts, stretched fp32, stretched counts); None where not read
+        self.dev = device_outputs  # (bytes, counts, stretched fp32, stretched counts, flac bytes, flac sizes); None where not read
         self.host = None
+        self.conv, self.heads = conv, heads or {}  # FLAC slots of the run: (stream gen, rate) of each
 
     def to_host(self, stream) -> None:
         """Queue the host copies on ``stream``; ``chunk`` reads them once ``stream`` has run them."""
@@ -1162,9 +1316,18 @@ class StreamPass:
             self.host = tuple(t.to("cpu", non_blocking=True) if t is not None else None for t in self.dev)
 
     def chunk(self, b: int, last: bool) -> np.ndarray:
-        """Slot ``b``'s chunk: its converted samples (with the resampler's tail when ``last``), or the stretched float32 of a slot
-        with a speed and no format."""
-        out, counts, stretched, st_counts = (t.numpy() if t is not None else None for t in self.host)
+        """Slot ``b``'s chunk: its FLAC frames as uint8 (behind the stream header on the stream's first chunk), its converted
+        samples (with the resampler's tail when ``last``), or the stretched float32 of a slot with a speed and no format."""
+        out, counts, stretched, st_counts, fout, fsizes = (t.numpy() if t is not None else None for t in self.host)
+        if b in self.heads:
+            from .flac import stream_header
+
+            data = b"".join(FlacEncoder.slot_frames(fout, fsizes, b))
+            gen, rate = self.heads[b]
+            if self.conv.head_owed[b] == gen:
+                self.conv.head_owed[b] = -1
+                data = stream_header(rate) + data
+            return np.frombuffer(data, dtype=np.uint8).copy()
         if self.enc is not None and self.enc[b] != ENC_OFF:
             return self.rs.slot_bytes(out, counts, b, tail=last, enc=self.enc[b])
         return stretched[b, : int(st_counts[b])].copy()

@@ -27,6 +27,21 @@ def parse_stream_format(fmt: str) -> Tuple[int, int]:
     raise ValueError(f"unsupported stream output_format {fmt!r}: supported are {', '.join((NATIVE_FORMAT,) + STREAM_FORMATS)}")
 
 
+CONTAINERS = ("flac",)
+
+
+def check_container(container, output_format=None):
+    """A stream's ``container`` (None, or ``"flac"``: lossless FLAC framing of its 16-bit samples, flac.py) for ``output_format``
+    (None / ``pcm_<rate>``; FLAC frames PCM only).  Returns it; ``ValueError`` for anything else."""
+    if container is None:
+        return None
+    if container not in CONTAINERS:
+        raise ValueError(f"unsupported container {container!r}: supported are {', '.join(CONTAINERS)}")
+    if output_format is not None and parse_stream_format(output_format)[1] == ENC_ULAW:
+        raise ValueError(f"container {container!r} frames 16-bit PCM, not {output_format}")
+    return container
+
+
 def lin2ulaw(s16: np.ndarray) -> np.ndarray:
     """G.711 mu-law of 16-bit samples: Sun's ``linear2ulaw`` on the full 16-bit value (bias 0x84, clip 32635), no 14-bit cut."""
     s = np.asarray(s16, dtype=np.int32)

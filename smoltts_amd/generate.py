@@ -209,7 +209,8 @@ def generate_blocking(model: LMEngine, prompt: np.ndarray, generation_settings: 
 
 
 def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bool = True, max_frames: Optional[int] = None,
-               overlap: bool = True, output_format: Optional[str] = None, speed_q: Optional[int] = None) -> Iterator[np.ndarray]:
+               overlap: bool = True, output_format: Optional[str] = None, speed_q: Optional[int] = None,
+               container: Optional[str] = None) -> Iterator[np.ndarray]:
     """One utterance in slot 0 of ``session`` -> one 1920-sample float32 chunk per generated frame, as the reference's
     ``SmolTTS.stream`` yields them (mlx_inference/src/smoltts_mlx/__init__.py:83-95: every frame of ``SingleBatchGenerator`` through
     ``codec.decode_step``), the terminating ``<|im_end|>`` frame included.
@@ -230,7 +231,11 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     (``engine.TimeStretcher``) on the codec stream in front of the resampler, which then consumes the stretcher's output.  The end
     of the stream is derived on the device from the same snapshot of the frame counter and ``done`` that the host reads, and the
     stretcher flushes with it.  A chunk holds the samples that became final with its frame; a frame that finalised none yields
-    nothing."""
+    nothing.
+
+    ``container`` (``"flac"``): the stream's 16-bit samples (the converted ones, or the float32 quantised) are framed as FLAC on
+    the codec stream behind the other stages (``engine.FlacEncoder``): uint8 chunks, the stream header in front of the first;
+    the end of the stream is derived on the device as for a speed."""
     if speed_q is not None and speed_q == 65536:
         speed_q = None
     s = session
@@ -245,11 +250,12 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     pcm_host = torch.empty(1, 1920, dtype=torch.float32).pin_memory()
     state_host = torch.zeros(2, dtype=torch.int32).pin_memory()  # n_frames[0], done[0]
     formatted = output_format is not None and parse_stream_format(output_format)[1] != ENC_OFF
-    conv = StreamConverter(dev, 1, 1920) if formatted or speed_q is not None else None
+    ends_on_device = speed_q is not None or container is not None  # a stage that must see the end of the stream
+    conv = StreamConverter(dev, 1, 1920) if formatted or ends_on_device else None
     with torch.cuda.stream(codec_stream):
         msession.reset()
         if conv is not None:
-            conv.reset_slots([0], [output_format], [speed_q])
+            conv.reset_slots([0], [output_format], [speed_q], [container])
     with torch.cuda.stream(lm_stream):
         s.prefill([prompt], stop_on_eos=stop_on_eos)  # frame 0
         ev = torch.cuda.Event()
@@ -266,7 +272,7 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
             ev.synchronize()  # frame f is in the output ring
             out = None
             with torch.cuda.stream(codec_stream):
-                if speed_q is None:
+                if not ends_on_device:
                     state_host[0:1].copy_(s.n_frames[0:1], non_blocking=True)
                     state_host[1:2].copy_(s.done[0:1], non_blocking=True)
                     n_d, done_d = s.n_frames[0:1], s.done[0:1]
@@ -278,7 +284,7 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
                 if conv is not None:
                     valid = (n_d > f).to(torch.int32) * 1920  # 0 once the slot has stopped: garbage is not consumed
                     # the stream ends with this frame (done at it, or the frame limit), or had ended before it unseen by the host
-                    last = None if speed_q is None else ((n_d <= f) | ((done_d != 0) & (n_d == f + 1)) | (f + 1 >= limit)).to(torch.int32)
+                    last = None if not ends_on_device else ((n_d <= f) | ((done_d != 0) & (n_d == f + 1)) | (f + 1 >= limit)).to(torch.int32)
                     out = conv.run(pcm_dev, 1920, valid, last)
                     out.to_host(codec_stream)
                 else:
@@ -288,7 +294,7 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
             if out is not None:
                 # (a call after the slot stopped consumed nothing: its tail is that of the last frame)
                 chunk = out.chunk(0, last=n <= f or bool(done and n == f + 1) or f + 1 >= limit)
-                if chunk.size or speed_q is None:  # (a stretched frame that finalised no sample yields nothing)
+                if chunk.size or not ends_on_device:  # (a stretched frame that finalised no sample yields nothing)
                     yield chunk
             if n <= f:  # the slot had stopped before this frame
                 break

@@ -136,12 +136,15 @@ class TTSCore:
         return (*self.format_audio_chunk(pcm, response_format), seed_used(used))
 
     def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
-                     speed: Optional[float] = None):
+                     speed: Optional[float] = None, container: Optional[str] = None):
         """-> (chunks as bytes, the seed the request samples with or None).  Chunks: float32 at 24 kHz for ``pcm_24000``;
         otherwise the int16 / mu-law samples the model or scheduler converted on the GPU (the format is passed on only when it is
         not ``pcm_24000``).  The request is submitted here, before the first chunk is asked for.  ``speed``: passed on only when
-        it is not 1; the chunks are then the stretched stream (float32 for ``pcm_24000``)."""
+        it is not 1; the chunks are then the stretched stream (float32 for ``pcm_24000``).  ``container`` ``"flac"``: the
+        chunks are the stream's FLAC bytes (framed on the GPU), the stream header in front of the first."""
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
+        if container is not None:
+            kw["container"] = container
         sp = _speed_kw(speed)
         if self.scheduler is not None:
             req = self.scheduler.submit(input_text, str(voice), stream=True, **kw, **({"sampling": sampling} if sampling is not None else {}), **sp)
@@ -229,7 +232,7 @@ class SpeechRequest(SamplingFields):
     model: str = Field(default="tts-1-hd")
     input: str
     voice: Union[str, int] = Field(default="alloy")
-    response_format: Literal["wav"] = Field(default="wav")
+    response_format: Literal["wav", "flac", "pcm"] = Field(default="wav")
     speed: Optional[float] = SpeedField
 
 
@@ -253,9 +256,52 @@ openai_router = APIRouter(prefix="/v1", tags=["OpenAI"])
 eleven_router = APIRouter(prefix="/v1", tags=["ElevenLabs"])
 
 
+def _pcm16_bytes(chunks):
+    """float32 chunks (bytes) -> int16 little-endian bytes, rint(clip(x, -1, 1) * 32767) as on the blocking route."""
+    try:
+        for b in chunks:
+            x = np.frombuffer(b, dtype=np.float32)
+            yield np.rint(np.clip(x, -1.0, 1.0) * np.float32(32767.0)).astype("<i2").tobytes()
+    finally:
+        chunks.close()
+
+
+def _answer_first(chunks):
+    """Pull the first chunk before the response starts, so that a request the engine refuses (e.g. a text too long for
+    max_seq_len) is answered 400 with its reason, as on the blocking route; then the whole stream."""
+    try:
+        first = next(chunks)
+    except StopIteration:
+        return iter(())
+    except ValueError as e:
+        chunks.close()
+        raise HTTPException(status_code=400, detail=str(e))
+
+    def body():
+        yield first
+        yield from chunks
+
+    return body()
+
+
 @openai_router.post("/audio/speech")
 def openai_speech(item: SpeechRequest, http_request: Request):
+    """``wav``: the whole utterance at 24 kHz.  ``flac`` and ``pcm`` stream at 24 kHz (chunked): FLAC framed on the GPU, or
+    int16 little-endian samples."""
     core = http_request.app.state.tts_core
+    if item.response_format != "wav":
+        container = "flac" if item.response_format == "flac" else None
+        try:
+            chunks, seed = core.stream_audio(item.input, item.voice, "pcm_24000", sampling=item.request_sampling(), speed=item.speed,
+                                             container=container)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        if container is None:
+            chunks = _pcm16_bytes(chunks)
+        media_type = "audio/flac" if container else "audio/x-pcm"
+        return StreamingResponse(_answer_first(chunks), media_type=media_type, headers={
+            "Content-Disposition": f'attachment; filename="speech.{item.response_format}"', "X-Sample-Rate": "24000",
+            **_seed_headers(seed)})
     audio, media_type, seed = core.generate_audio(item.input, item.voice, item.response_format + "_24000", sampling=item.request_sampling(),
                                                   speed=item.speed)
     return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed)})

@@ -184,11 +184,18 @@ class GpuPool:
 
     # ------------------------------------------------------------------ client side (the BatchScheduler interface)
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None) -> _PoolRequest:
+               output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
+               container: Optional[str] = None) -> _PoolRequest:
         if output_format is not None:  # refused here, before a worker sees it
             from ..formats import parse_stream_format
 
             parse_stream_format(output_format)
+        if container is not None:  # (likewise)
+            from ..formats import check_container
+
+            if not stream:
+                raise ValueError("container applies to streaming requests")
+            check_container(container, output_format)
         if speed is not None:  # (likewise; speed 1.0 is not passed on)
             from ..tsm import parse_speed
 
@@ -214,7 +221,8 @@ class GpuPool:
             self._reqs[req.rid] = req
             self._load[w] += 1
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
-        extra = {k: v for k, v in (("output_format", output_format), ("sampling", sampling), ("speed", speed)) if v is not None}
+        extra = {k: v for k, v in (("output_format", output_format), ("sampling", sampling), ("speed", speed), ("container", container))
+                 if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 

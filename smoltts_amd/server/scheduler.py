@@ -55,6 +55,7 @@ class _Request:
     prefix: object = None     # engine.PrefixKV installed into the slot at admission (None: the whole prompt is prefilled)
     speed_q: Optional[int] = None  # speaking speed in Q16 (tsm.py), time-stretched on the GPU; None: speed 1, no stretch
     stretch_in: list = field(default_factory=list)  # blocking requests with a speed: the utterance's PCM until its last pass
+    container: Optional[str] = None  # streaming: "flac" frames the stream's 16-bit samples on the GPU (uint8 chunks)
 
 
 @dataclass
@@ -187,17 +188,27 @@ class BatchScheduler:
 
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None) -> _Request:
+               output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
+               container: Optional[str] = None) -> _Request:
         """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
         in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
         a seed gets one here.  The resolved value is ``request.sampling``; its seed replays the request.
         ``speed`` (0.25 to 4.0, ``ValueError`` otherwise; None / 1.0: unchanged): pitch-preserving time stretch on the GPU
-        (tsm.py).  A stream is stretched in its codec pass in front of the format conversion, a blocking utterance as a whole."""
+        (tsm.py).  A stream is stretched in its codec pass in front of the format conversion, a blocking utterance as a whole.
+        ``container`` (streaming only, ``ValueError`` otherwise): ``"flac"`` frames the stream's 16-bit samples (of its
+        ``pcm_<rate>``, 24 kHz by default) as FLAC in the same pass, behind the other stages: uint8 chunks, the stream header in
+        front of the first."""
         from ..config import RequestSampling
         from ..tsm import parse_speed
 
         speed_q = parse_speed(speed)
+        if container is not None:
+            from ..formats import check_container
+
+            if not stream:
+                raise ValueError("container applies to streaming requests")
+            check_container(container, output_format)
 
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         if output_format is not None:
@@ -212,7 +223,8 @@ class BatchScheduler:
         if self._draining:
             raise RuntimeError("scheduler is not running: shutting down")
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
-                       output_format=output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=speed_q)
+                       output_format=output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=speed_q,
+                       container=container)
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
@@ -344,7 +356,7 @@ class BatchScheduler:
         other slot none.  A slot with a speed ends its stream (flushes) in the tick where the host will see it finish, by the
         rule of ``_drain`` on the same snapshot (``n_frames_d``, ``done_d``).  Returns the ``engine.StreamPass``, or None when no
         request in ``reqs`` has a format or a speed (then nothing is uploaded or launched)."""
-        if not any(r.output_format or r.speed_q for r in reqs):
+        if not any(r.output_format or r.speed_q or r.container for r in reqs):
             return None
         from ..engine import upload
 
@@ -358,7 +370,7 @@ class BatchScheduler:
         n_d = n_frames_d.to(torch.int32)
         valid = ((torch.minimum(n_d, cap_d) - f0_d).clamp_(0, self.tick) * 1920).to(torch.int32)
         last = None
-        if any(r.speed_q for r in reqs):
+        if any(r.speed_q or r.container for r in reqs):
             last = (stream_ends(n_d, done_d, cap_d) & (cap_d > 0)).to(torch.int32)
         return self._stream_conv.run(pcm, self.tick * 1920, valid, last, slots=[r.slot for r in reqs])
 
@@ -581,7 +593,8 @@ class BatchScheduler:
             restart += [b for b in range(self.B) if b not in live and (self._codec_age[b] + 2) * 2 * self.tick > cap]
             if restart:
                 self._stream_codec.reset_slots(sorted(set(restart)))
-                self._stream_conv.reset_slots([r.slot for r in new], [r.output_format for r in new], [r.speed_q for r in new])
+                self._stream_conv.reset_slots([r.slot for r in new], [r.output_format for r in new], [r.speed_q for r in new],
+                                              [r.container for r in new])
                 for b in restart:
                     self._codec_age[b] = 0
             for b in range(self.B):
@@ -777,7 +790,7 @@ class BatchScheduler:
                 host = host.numpy()
             self._deliveries.pop(0)
             for r, b, n, fin in d.items:
-                if r.stream and (r.output_format or r.speed_q) and d.conv is not None:
+                if r.stream and (r.output_format or r.speed_q or r.container) and d.conv is not None:
                     chunk = d.conv.chunk(b, fin)  # (the tail goes out with the last chunk)
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)

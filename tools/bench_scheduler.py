@@ -7,7 +7,9 @@ at t), blocking responses.
 ``pool_workers`` > 0 puts the same load through the multi-GPU front-end (server/pool.py) with that many worker processes,
 all on GPU 0 here: what the relay between processes costs.
 SPEED_HALF=s: every other request, streamed or blocking, asks for speaking speed s (time-stretched on the GPU); its frames are
-counted as the LM frames behind its samples (samples x s / 1920)."""
+counted as the LM frames behind its samples (samples x s / 1920).
+STREAM_FLAC=1: every streamed request asks for FLAC framing (container="flac", framed on the GPU); its frames are counted from
+the request's LM frames."""
 import functools
 import os
 import sys
@@ -53,12 +55,14 @@ def main():
     for _ in range(max(n_pool, 1) * 2):
         sched.synthesize("warm up", max_new_tokens=8)
     if streaming:
-        list(sched.iter_chunks(sched.submit("warm up the stream path", "heart", stream=True, max_new_tokens=8)))
+        wkw = {"container": "flac"} if os.environ.get("STREAM_FLAC", "0") == "1" else {}
+        list(sched.iter_chunks(sched.submit("warm up the stream path", "heart", stream=True, max_new_tokens=8, **wkw)))
     samples = [0] * n_req
 
 
     first_chunk_ms = []
     half_speed = float(os.environ.get("SPEED_HALF", 0)) or None
+    use_flac = os.environ.get("STREAM_FLAC", "0") == "1"
 
 
     def worker(i):
@@ -67,11 +71,17 @@ def main():
             n = 0
             sp = half_speed if half_speed and i % 2 else None
             kw = {"speed": sp} if sp else {}
-            for j, chunk in enumerate(sched.iter_chunks(sched.submit(texts[i], "heart", stream=True, max_new_tokens=int(budgets[i]), **kw))):
+            if use_flac:
+                kw["container"] = "flac"
+            req = sched.submit(texts[i], "heart", stream=True, max_new_tokens=int(budgets[i]), **kw)
+            for j, chunk in enumerate(sched.iter_chunks(req)):
                 if j == 0:
                     first_chunk_ms.append((time.perf_counter() - t1) * 1e3)
                 n += chunk.shape[0]
-            samples[i] = int(round(n * sp)) if sp else n
+            if use_flac:
+                samples[i] = int(req.emitted) * 1920
+            else:
+                samples[i] = int(round(n * sp)) if sp else n
         elif half_speed and i % 2:  # (blocking with a speed: the utterance is stretched after its last codec pass)
             req = sched.submit(texts[i], "heart", max_new_tokens=int(budgets[i]), speed=half_speed)
             n = sum(c.shape[0] for c in sched.iter_chunks(req))
