@@ -580,6 +580,47 @@ int smoltts_flac_chunk(SmolttsFlac* f, const float* pcm_dev, int64_t pcm_stride,
                        const int32_t* last_dev, void* out_dev, int64_t out_stride, int32_t* sizes_dev, int32_t max_blocks,
                        void* stream);
 
+/* ------------------------------------------------------------------------------ Seam
+ * The segments of a long text joined into one stream on the codec's 24 kHz fp32 PCM (smoltts_amd/csrc/seam.hip, DESIGN.md
+ * section 13; the numpy model is smoltts_amd/seam.py).  Blocks of 240 samples from a segment's start are silent when
+ * max|x| < 2^-8.  A segment that is not the stream's first drops leading silent blocks (at most 1 s); one that is not the
+ * stream's last holds back trailing silent blocks (at most 1 s) and, at its end, replaces the held run of r samples by its first
+ * min(r, G) samples and G - min(r, G) zeros, G the seam's pause.  The first segment may open with `lead` zeros and the last
+ * close with G zeros.  The output does not depend on how a segment is cut into calls. */
+typedef struct SmolttsSeam SmolttsSeam;
+enum {  /* segment flags of smoltts_seam_reset_slots */
+  SMOLTTS_SEAM_FIRST = 1,  /* the stream's first segment: its head is kept, `lead` zeros go in front of it */
+  SMOLTTS_SEAM_FINAL = 2,  /* the stream's last segment: its tail is kept, G zeros follow it */
+  SMOLTTS_SEAM_OFF = 4     /* switch the slot off */
+};
+
+/* Device slab of a seam stage for max_batch slots (256-byte aligned, caller-owned): two copies of each slot's state (counters and
+ * 24576 samples of history).  Every slot starts off; create clears the slab synchronously. */
+size_t smoltts_seam_bytes(int32_t max_batch);
+int smoltts_seam_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsSeam** out);
+void smoltts_seam_destroy(SmolttsSeam* s);
+/* Output samples per row that a call of n_in input samples needs when no open slot owes more than max_zeros zeros (its lead
+ * plus its pause, as given to smoltts_seam_reset_slots; at most 480000). */
+size_t smoltts_seam_out_samples(int32_t n_in, int32_t max_zeros);
+
+/* Open a segment in each listed slot (host arrays): its pause G in samples (0..240000), its flags (SMOLTTS_SEAM_*) and, for a
+ * FIRST segment, the zeros in front of it (lead_host may be NULL: none).  The other slots continue.  Stream-ordered. */
+int smoltts_seam_reset_slots(SmolttsSeam* s, const int32_t* slots_host, const int32_t* pause_host, const int32_t* flags_host,
+                             const int32_t* lead_host, int32_t n_slots, void* stream);
+
+/* One launch for slots [0, batch): slot b consumes valid_in_dev[b] (clamped to [0, n_in]; NULL = n_in) samples of pcm_dev float
+ * [batch][pcm_stride]; seg_end_dev[b] nonzero ends the slot's segment with them, last_dev[b] nonzero ends the stream (a held run
+ * is then released unchanged); either may be NULL.  max_zeros: the most zeros (lead + pause) any open slot owes.  Slot b writes
+ * the samples that became final in this call to out_dev float [batch][out_stride] (out_stride >= smoltts_seam_out_samples(n_in,
+ * max_zeros)) and their number to counts_dev[b]; slots without an open segment write 0.  Calls on one seam stage must be
+ * ordered on one stream (the slot states alternate between their copies). */
+int smoltts_seam_chunk(SmolttsSeam* s, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
+                       const int32_t* valid_in_dev, const int32_t* seg_end_dev, const int32_t* last_dev, int32_t max_zeros,
+                       float* out_dev, int64_t out_stride, int32_t* counts_dev, void* stream);
+
+/* Tests and tools: slot's state (n_in, judged, ec, head, open, lead, pause, flags) into state_host[8]; synchronises the stream. */
+int smoltts_seam_slot_state(SmolttsSeam* s, int32_t slot, int64_t* state_host, void* stream);
+
 /* --------------------------------------------------------------- operator-level test entry points */
 enum {  /* prologue applied to the activation operand */
   SMOLTTS_PRO_NONE = 0,

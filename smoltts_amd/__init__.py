@@ -58,6 +58,8 @@ class SmolTTS:
         self.voices: Dict[str, "np.ndarray"] = {}  # registered voice id -> speaker grid (add_voice)
         self.verbose = verbose  # print the reference's per-call timing lines (lm/generate.py:187-214)
         self.last_sampling = None  # resolved RequestSampling list of the last call that was given sampling= (seeds included)
+        self._seam = None  # engine.SeamJoiner of the blocking segmented calls (made on first use)
+        self.last_segments: list = []  # per segment of the last segmented call: text, prompt, codes, seed
         self.last_stats: dict = {}  # timing of the last generate_codes / __call__ (BatchGenerator.stats + codec_ms)
 
     # -- prompt (``_get_prompt``, __init__.py:120-151)
@@ -102,18 +104,22 @@ class SmolTTS:
         generation settings, and a sampled entry without a seed draws one (see ``last_sampling``).  The inputs then sample
         independently, each with the request key of its seed: the same seed gives the same codes whatever the
         other inputs are, as long as the batch selects the same kernel variants.  None: every input samples with the settings."""
+        voices = voices or ["heart"] * len(inputs)
+        speakers = speakers or [None] * len(inputs)
+        prompts = [self._get_prompt(t, v, sp) for t, v, sp in zip(inputs, voices, speakers)]
+        return self.generate_prompt_codes(prompts, generation_settings, sampling)
+
+    def generate_prompt_codes(self, prompts, generation_settings=None, sampling=None):
+        """``generate_codes`` of ready prompt grids ((1 + depth, T) each: ``build_prompt``, ``longform.chain_prompt``)."""
         import numpy as np
 
         from .generate import BatchGenerator, resolve_sampling
 
-        voices = voices or ["heart"] * len(inputs)
-        speakers = speakers or [None] * len(inputs)
-        prompts = [self._get_prompt(t, v, sp) for t, v, sp in zip(inputs, voices, speakers)]
         settings = self._settings(generation_settings)
-        resolved = resolve_sampling(sampling, settings, len(inputs))
+        resolved = resolve_sampling(sampling, settings, len(prompts))
         self.last_sampling = resolved  # what the call sampled with, seeds included (None: the settings, session-wide)
         gen = BatchGenerator(self.lm, prompts, settings, frames_per_sync=16, sampling=resolved)
-        cols: List[list] = [[] for _ in inputs]
+        cols: List[list] = [[] for _ in prompts]
         for row in gen:
             for b, tok in enumerate(row):
                 if tok is not None and tok.audio_codes is not None:
@@ -151,16 +157,23 @@ class SmolTTS:
         return pcm
 
     def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None,
-                 speed: Optional[float] = None):
+                 speed: Optional[float] = None, segment=False):
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
         (per-request temperature / min_p / seed, as in ``generate_codes``).  ``speed`` (0.25 to 4.0; None / 1.0: unchanged):
-        the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples."""
+        the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
+        ``segment`` (True, a dict or a ``longform.SegmentOptions``): a long text is spoken as chained segments (``longform``),
+        one after another, each decoded as its own utterance and joined on the GPU (``seam``) before the stretch; a text that is
+        one segment without break tags takes the plain path.  ``last_segments`` then lists each segment's text, seed and codes."""
         from .tsm import parse_speed
 
         sq = parse_speed(speed)  # a bad speed is refused before any work
-        codes = self.generate_codes([input], [voice if voice is not None else "heart"], generation_settings,
-                                    speakers=None if speaker is None else [speaker], sampling=sampling)[0]
-        pcm = self.decode_codes(codes)
+        plan = self._segment_plan(input, segment)
+        if plan is not None:
+            pcm = self._call_segmented(plan, voice if voice is not None else "heart", speaker, generation_settings, sampling)
+        else:
+            codes = self.generate_codes([input], [voice if voice is not None else "heart"], generation_settings,
+                                        speakers=None if speaker is None else [speaker], sampling=sampling)[0]
+            pcm = self.decode_codes(codes)
         if sq is None:
             return pcm
         from .engine import stretch_pcm
@@ -200,7 +213,7 @@ class SmolTTS:
 
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
                reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None,
-               speed: Optional[float] = None, container: Optional[str] = None) -> Iterator["np.ndarray"]:
+               speed: Optional[float] = None, container: Optional[str] = None, segment=False) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -217,7 +230,9 @@ class SmolTTS:
         chunk holds the samples that became final with its frame (none for some frames: no chunk then).
         ``container``: ``"flac"`` frames the stream's 16-bit samples (``output_format`` ``pcm_<rate>``, the float32 of
         ``pcm_24000`` quantised as rint(clip(x, -1, 1) * 32767)) as FLAC on the GPU: uint8 chunks, the stream header in front of
-        the first, which decode to exactly those samples (flac.py)."""
+        the first, which decode to exactly those samples (flac.py).
+        ``segment`` (as in ``__call__``): a long text streams segment after segment in slot 0, each one's codec output through
+        the seam stage in front of the stream's other stages, which run on across the segments: one stream (one FLAC header)."""
         import numpy as np
 
         from .formats import check_container, parse_stream_format
@@ -227,6 +242,11 @@ class SmolTTS:
             parse_stream_format(output_format)  # an unknown format is refused before any work
         check_container(container, output_format)
         sq = parse_speed(speed)
+        plan = self._segment_plan(input, segment)
+        if plan is not None:
+            yield from self._stream_segmented(plan, voice if voice is not None else "0", generation_settings, overlap,
+                                              reference_upsample, output_format, sampling, sq, container)
+            return
 
         from .engine import LMSession, MimiSession
         from .generate import _apply_sampling, _apply_slot_sampling, resolve_sampling, stream_pcm
@@ -250,3 +270,120 @@ class SmolTTS:
         finally:
             msess.close()
             sess.close()
+
+    # -- long texts as chained segments (``longform``, ``seam``)
+    def _segment_plan(self, input: str, segment):
+        """(options, segments) of a segmented request, or None where the plain path runs (``segment`` off, or one segment
+        without break tags)."""
+        from .longform import needs_segments, segment_options, split_text
+
+        opts = segment_options(segment)
+        if opts is None:
+            return None
+        segs = split_text(input, opts.max_bytes)
+        if not segs:
+            raise ValueError("the text has nothing to speak")
+        return (opts, segs) if needs_segments(segs) else None
+
+    def _segment_setup(self, plan, voice: str, speaker, generation_settings, sampling):
+        """-> (settings, prefix, per-segment (settings, sampling) factory, pauses, lead, trail)."""
+        import dataclasses
+        import os
+
+        from .generate import resolve_sampling
+        from .longform import segment_seed, voice_prefix
+        from .seam import pause_samples
+
+        opts, segs = plan
+        settings = self._settings(generation_settings)
+        if speaker is None and voice in self.voices:
+            speaker = self.voices[voice]
+        prefix = voice_prefix(self.prompt_encoder, voice, speaker)
+        resolved = resolve_sampling(sampling, settings, 1)
+        self.last_sampling = resolved
+        base = settings.seed if settings.seed is not None else int.from_bytes(os.urandom(8), "little")
+
+        def per_segment(k: int):
+            if resolved is not None:
+                return settings, [dataclasses.replace(resolved[0], seed=segment_seed(resolved[0].seed, k))]
+            return dataclasses.replace(settings, seed=segment_seed(base, k)), None
+
+        pauses = [pause_samples(s.pause_after_s if s.pause_after_s is not None else opts.pause_s) for s in segs[:-1]]
+        return settings, prefix, per_segment, pauses, pause_samples(segs[0].pause_before_s), pause_samples(segs[-1].pause_after_s)
+
+    def _chain(self, plan, prefix, k: int, prev, settings):
+        from .longform import chain_prompt
+
+        opts, segs = plan
+        max_new = settings.max_new_tokens if settings.max_new_tokens is not None else self.config.max_seq_len
+        if opts.context == "previous" and prev is not None:
+            return chain_prompt(self.prompt_encoder, prefix, segs[k].text, prev[0], prev[1], max_new, self.config.max_seq_len)
+        return chain_prompt(self.prompt_encoder, prefix, segs[k].text, max_new_tokens=max_new, max_seq=self.config.max_seq_len)
+
+    def _call_segmented(self, plan, voice, speaker, generation_settings, sampling):
+        from .engine import seam_join
+
+        opts, segs = plan
+        settings, prefix, per_segment, pauses, lead, trail = self._segment_setup(plan, voice, speaker, generation_settings, sampling)
+        pcms, prev, info = [], None, []
+        resolved = self.last_sampling
+        for k, seg in enumerate(segs):
+            st_k, samp_k = per_segment(k)
+            prompt = self._chain(plan, prefix, k, prev, settings)
+            codes = self.generate_prompt_codes([prompt], st_k, samp_k)[0]
+            pcms.append(self.decode_codes(codes))
+            info.append({"text": seg.text, "prompt": prompt, "codes": codes,
+                         "seed": samp_k[0].seed if samp_k is not None else st_k.seed})
+            prev = (seg.text, codes)
+        self.last_sampling = resolved
+        self.last_segments = info
+        if self._seam is None:
+            from .engine import SeamJoiner
+
+            self._seam = SeamJoiner(self.lm.device, 1)
+        return seam_join(pcms, pauses, self.lm.device, lead=lead, trail=trail, joiner=self._seam)
+
+    def _stream_segmented(self, plan, voice, generation_settings, overlap, reference_upsample, output_format, sampling, sq,
+                          container):
+        import numpy as np
+        import torch
+
+        from .engine import SEAM_FINAL, SEAM_FIRST, LMSession, MimiSession, StreamConverter
+        from .generate import _apply_sampling, _apply_slot_sampling, _frame_to_token, stream_pcm
+
+        opts, segs = plan
+        settings, prefix, per_segment, pauses, lead, trail = self._segment_setup(plan, voice, None, generation_settings, sampling)
+        max_new = settings.max_new_tokens if settings.max_new_tokens is not None else self.config.max_seq_len
+        dev = self.lm.device
+        conv = StreamConverter(dev, 1, 1920, seam=True)
+        msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
+        info, prev = [], None
+        self.last_segments = info
+        try:
+            conv.reset_slots([0], [output_format], [sq], [container])
+            for k, seg in enumerate(segs):
+                final = k == len(segs) - 1
+                prompt = self._chain(plan, prefix, k, prev, settings)
+                st_k, samp_k = per_segment(k)
+                T = int(prompt.shape[1])
+                sess = LMSession(self.lm, 1, max_seq=min(self.config.max_seq_len, T + max_new + 2), max_rows=T, max_frames=max_new + 1)
+                try:
+                    _apply_sampling(sess, st_k)
+                    if samp_k is not None:
+                        _apply_slot_sampling(sess, [0], samp_k)
+                    conv.start_segments([0], [trail if final else pauses[k]],
+                                        [(SEAM_FIRST if k == 0 else 0) | (SEAM_FINAL if final else 0)], [lead])
+                    yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, conv=conv, final=final)
+                    codes_all, n_frames, _, _ = sess.fetch()
+                    cols = [t.audio_codes[0, :, 0] for t in (_frame_to_token(self.lm, codes_all[0, f]) for f in range(int(n_frames[0])))
+                            if t.audio_codes is not None]
+                    codes = (np.stack(cols, axis=1).astype(np.uint32) if cols else np.zeros((self.config.num_codebooks, 0), np.uint32))
+                finally:
+                    sess.close()
+                info.append({"text": seg.text, "prompt": prompt, "codes": codes,
+                             "seed": samp_k[0].seed if samp_k is not None else st_k.seed})
+                prev = (seg.text, codes)
+        finally:
+            torch.cuda.synchronize(dev)
+            msess.close()
+            conv.close()

@@ -122,6 +122,8 @@ _EXPORTS = [
     "smoltts_tsm_chunk", "smoltts_tsm_slot_state",
     "smoltts_flac_bytes", "smoltts_flac_create", "smoltts_flac_destroy", "smoltts_flac_max_blocks", "smoltts_flac_out_bytes",
     "smoltts_flac_reset_slots", "smoltts_flac_chunk",
+    "smoltts_seam_bytes", "smoltts_seam_create", "smoltts_seam_destroy", "smoltts_seam_out_samples", "smoltts_seam_reset_slots",
+    "smoltts_seam_chunk", "smoltts_seam_slot_state",
     "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows",
     "smoltts_prefix_kv_bytes", "smoltts_session_save_prefix", "smoltts_session_install_prefix",
 ]
@@ -235,6 +237,17 @@ def load_library(path: Optional[Path] = None):
     lib.smoltts_tsm_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.c_void_p, C.c_void_p]
     lib.smoltts_tsm_slot_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.smoltts_seam_bytes.argtypes = [C.c_int32]
+    lib.smoltts_seam_bytes.restype = C.c_size_t
+    lib.smoltts_seam_out_samples.argtypes = [C.c_int32, C.c_int32]
+    lib.smoltts_seam_out_samples.restype = C.c_size_t
+    lib.smoltts_seam_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.smoltts_seam_destroy.argtypes = [C.c_void_p]
+    lib.smoltts_seam_destroy.restype = None
+    lib.smoltts_seam_reset_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.smoltts_seam_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.smoltts_seam_slot_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.smoltts_flac_bytes.argtypes = [C.c_int32]
     lib.smoltts_flac_bytes.restype = C.c_size_t
     lib.smoltts_flac_max_blocks.argtypes = [C.c_int32]
@@ -1093,6 +1106,113 @@ class TimeStretcher:
             pass
 
 
+# ------------------------------------------------------------------------------- long texts: the seam between segments
+SEAM_FIRST, SEAM_FINAL, SEAM_OFF = 1, 2, 4  # SMOLTTS_SEAM_*
+
+
+class SeamJoiner:
+    """Per-slot joining of a long text's segments on the GPU (include/smoltts_hip.h, "Seam"; the numpy model is
+    ``seam.SeamState``): one launch per call for every slot.  Slots start off; ``start_segments`` opens a segment in a slot with
+    its pause and flags (``SEAM_FIRST`` / ``SEAM_FINAL``; ``SEAM_OFF`` switches the slot off)."""
+
+    def __init__(self, device: torch.device, max_batch: int):
+        self.lib = load_library()
+        self.device, self.B = device, max_batch
+        need = self.lib.smoltts_seam_bytes(max_batch)
+        if need == 0:
+            raise SmolttsError("smoltts_seam_bytes returned 0 (bad sizes)")
+        self.slab = _alloc_slab(need, device, settle=True)
+        h = C.c_void_p()
+        check(self.lib.smoltts_seam_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_seam_create")
+        self.handle = h
+        self.on = [False] * max_batch  # the slot's stream is segmented (it stays on between its segments)
+        self.zeros = [0] * max_batch   # zeros the slot's open segment owes at most (its lead and its pause)
+
+    def out_samples(self, n_in: int) -> int:
+        """Output samples per row of a call of ``n_in`` input samples, for the segments open now."""
+        return int(self.lib.smoltts_seam_out_samples(int(n_in), max(self.zeros)))
+
+    def start_segments(self, slots: Sequence[int], pauses: Sequence[int], flags: Sequence[int],
+                       leads: Optional[Sequence[int]] = None) -> None:
+        """Open a segment in each of ``slots`` on the current stream: its pause G (samples), flags, and the zeros in front of a
+        ``SEAM_FIRST`` segment (``leads``)."""
+        n = len(slots)
+        if not n:
+            return
+        arr = lambda v: (C.c_int32 * n)(*[int(x) for x in v])  # noqa: E731
+        check(self.lib.smoltts_seam_reset_slots(self.handle, arr(slots), arr(pauses), arr(flags), arr(leads or [0] * n), n,
+                                                current_stream_ptr()), "smoltts_seam_reset_slots")
+        for b, p, f, ld in zip(slots, pauses, flags, leads or [0] * n):
+            self.on[b] = not (int(f) & SEAM_OFF)
+            self.zeros[b] = (int(p) + (int(ld) if int(f) & SEAM_FIRST else 0)) if self.on[b] else 0
+
+    def new_outputs(self, batch: int, n_in: int):
+        """Device buffers of one call of at most ``n_in`` input samples: (fp32 [batch, out_samples(n_in)], counts int32 [batch])."""
+        return (torch.empty(batch, self.out_samples(n_in), dtype=torch.float32, device=self.device),
+                torch.empty(batch, dtype=torch.int32, device=self.device))
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
+              seg_end: Optional[torch.Tensor] = None, last: Optional[torch.Tensor] = None) -> None:
+        """Join ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream.
+        ``valid``: device int32 [batch], the real samples of each row; ``seg_end`` / ``last``: device int32 [batch], nonzero where
+        the row's segment / stream ends with this call.  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
+        batch = pcm.shape[0]
+        assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and batch <= self.B and 0 <= n_in <= pcm.shape[1]
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= batch and out.shape[1] >= self.out_samples(n_in)
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= batch
+        for t in (valid, seg_end, last):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= batch)
+        check(self.lib.smoltts_seam_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(seg_end), dptr(last),
+                                          max(self.zeros), dptr(out), out.shape[1], dptr(counts), current_stream_ptr()),
+              "smoltts_seam_chunk")
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s state (synchronises the current stream): n_in, judged, ec, head, open, lead, pause, flags."""
+        v = (C.c_int64 * 8)()
+        check(self.lib.smoltts_seam_slot_state(self.handle, int(slot), v, current_stream_ptr()), "smoltts_seam_slot_state")
+        return dict(zip(("n_in", "judged", "ec", "head", "open", "lead", "pause", "flags"), list(v)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize()
+            self.lib.smoltts_seam_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: torch.device, lead: int = 0, trail: int = 0,
+              joiner: Optional[SeamJoiner] = None) -> np.ndarray:
+    """Whole segments (float32 at 24 kHz) joined on ``device`` by the seam rule, one call per segment with its end set: what
+    ``seam.join`` computes (``SmolTTS.__call__`` with ``segment``).  ``pauses[k]``: the seam after segment k, in samples.
+    ``joiner``: a caller's ``SeamJoiner`` whose slot 0 is used (default: one made for the call).  Waits for the result."""
+    segs = [np.ascontiguousarray(np.asarray(s, dtype=np.float32).reshape(-1)) for s in segments]
+    if len(pauses) != max(len(segs) - 1, 0):
+        raise ValueError("one pause per seam")
+    out = []
+    with torch.cuda.device(device):
+        sj = joiner if joiner is not None else SeamJoiner(device, 1)
+        try:
+            end = torch.ones(1, dtype=torch.int32, device=device)
+            for k, x in enumerate(segs):
+                final = k == len(segs) - 1
+                sj.start_segments([0], [trail if final else pauses[k]], [(SEAM_FIRST if k == 0 else 0) | (SEAM_FINAL if final else 0)],
+                                  [lead])
+                n = int(x.size)
+                xd = torch.from_numpy(x).to(device)[None] if n else torch.zeros(1, 1, dtype=torch.float32, device=device)
+                y, cnt = sj.new_outputs(1, n)
+                sj.chunk(xd, n, y, cnt, seg_end=end, last=end if final else None)
+                out.append(y[0, :int(cnt.cpu()[0])].cpu().numpy())
+        finally:
+            if joiner is None:
+                sj.close()
+    return np.concatenate(out) if out else np.zeros(0, np.float32)
+
+
 # ------------------------------------------------------------------------------- FLAC framing
 FLAC_OFF, FLAC_F32, FLAC_S16 = 0, 1, 2  # SMOLTTS_FLAC_*
 
@@ -1210,13 +1330,16 @@ class StreamConverter:
     (``TimeStretcher``), then a slot with an output format is converted (``Resampler``, from the stretched samples where the
     slot has a speed), then a slot with a FLAC container is framed (``FlacEncoder``, from the resampler's int16, or from the
     float32 at 24 kHz).  Each stage is created the first time a slot needs it.  ``n_in``: codec samples per slot and call; the
-    resampler takes up to the stretcher's output of that many."""
+    resampler takes up to the stretcher's output of that many.  ``seam``: the converter joins long texts' segments
+    (``start_segments``): a segmented slot goes through the seam stage (``SeamJoiner``) first, and the other stages read its
+    output, their state carried from segment to segment."""
 
-    def __init__(self, device: torch.device, max_batch: int, n_in: int):
+    def __init__(self, device: torch.device, max_batch: int, n_in: int, seam: bool = False):
         self.device, self.B, self.n_in = device, max_batch, n_in
         self.rs: Optional[Resampler] = None
         self.ts: Optional[TimeStretcher] = None
         self.fl: Optional[FlacEncoder] = None
+        self.sj: Optional[SeamJoiner] = SeamJoiner(device, max_batch) if seam else None
         self.gen = [0] * max_batch           # streams started in each slot
         self.head_owed = [-1] * max_batch    # the stream (gen) of the slot whose FLAC header has not been handed out yet
 
@@ -1244,24 +1367,52 @@ class StreamConverter:
             parsed = [parse_stream_format(f) for f in formats]
             self.fl.reset_slots(slots, [p[0] for p in parsed],
                                 [FLAC_OFF if c is None else (FLAC_F32 if p[1] == ENC_OFF else FLAC_S16) for c, p in zip(containers, parsed)])
+        if self.sj is not None:
+            self.sj.start_segments(slots, [0] * len(slots), [SEAM_OFF] * len(slots))
         for b, c in zip(slots, containers):
             self.gen[b] += 1
             self.head_owed[b] = self.gen[b] if c else -1
 
+    def start_segments(self, slots: Sequence[int], pauses: Sequence[int], flags: Sequence[int],
+                       leads: Optional[Sequence[int]] = None) -> None:
+        """Open the next segment of the segmented streams in ``slots`` (``SeamJoiner.start_segments``), after ``reset_slots``
+        started the streams; the other stages' state is kept."""
+        if self.sj is None:
+            self.sj = SeamJoiner(self.device, self.B)
+        self.sj.start_segments(slots, pauses, flags, leads)
+
     def run(self, pcm: torch.Tensor, n_in: int, valid: torch.Tensor, last: Optional[torch.Tensor] = None,
-            slots: Optional[Sequence[int]] = None) -> Optional["StreamPass"]:
+            slots: Optional[Sequence[int]] = None, seg_end: Optional[torch.Tensor] = None) -> Optional["StreamPass"]:
         """Queue the stages for ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in]) on the current stream.
         ``valid`` (device int32 [batch]): the samples of each row that are real; ``last`` (device int32 [batch], needed when a
         slot has a speed or a FLAC container): nonzero where the row's stream ends with this call.  ``slots``: the live streams
         (default: every slot); the others consume what ``valid`` gives them and are never read.  None when no live slot
-        converts: no launch."""
+        converts: no launch.  ``seg_end`` (device int32 [batch], needed when a slot is segmented): nonzero where the row's
+        segment ends with this call."""
         slots = range(self.B) if slots is None else slots
         fmt = [b for b in slots if self.rs is not None and self.rs.formats[b][1] != ENC_OFF]
         spd = [b for b in slots if self.ts is not None and self.ts.speed_q[b] != 65536]
         flc = [b for b in slots if self.fl is not None and self.fl.source[b] != FLAC_OFF]
-        if not (fmt or spd or flc):
+        smd = [b for b in slots if self.sj is not None and self.sj.on[b]]
+        if not (fmt or spd or flc or smd):
             return None
         batch = pcm.shape[0]
+        joined = j_counts = None
+        if smd:  # the seam stage first; the rows of slots that are not segmented join its output as they are
+            joined, j_counts = self.sj.new_outputs(batch, n_in)
+            self.sj.chunk(pcm, n_in, joined, j_counts, valid=valid, seg_end=seg_end, last=last)
+            plain = [b for b in fmt + spd + flc if b not in smd]
+            if plain:
+                segd = np.zeros(batch, np.int32)
+                segd[smd] = 1
+                segd_d, plain_d = upload([segd, np.asarray(plain, np.int64)], self.device)
+                joined[plain_d, :n_in] = pcm[plain_d]
+                valid = torch.where(segd_d != 0, j_counts, valid)
+            else:
+                valid = j_counts
+            pcm, n_in = joined, joined.shape[1]
+            if self.rs is not None and self.rs.max_in < out_bound(n_in):  # (the stages behind read the seam's wider rows)
+                self.rs.max_in = out_bound(n_in)
         src, rs_valid = pcm, valid
         out = counts = stretched = st_counts = fout = fsizes = None
         if spd:
@@ -1288,15 +1439,17 @@ class StreamConverter:
             stretched = st_counts = None
         if fmt and all(b in flc for b in fmt):  # every converted slot is framed: its int16 is not read
             out = counts = None
+        if not any(b not in fmt and b not in flc and b not in spd for b in smd):  # every joined slot goes on: its float32 is not read
+            joined = j_counts = None
         heads = {b: (self.gen[b], self.fl.rate[b]) for b in flc}
         return StreamPass(self.rs, [f[1] for f in self.rs.formats] if fmt else None, out, counts, stretched, st_counts, fout, fsizes,
-                          conv=self, heads=heads)
+                          joined, j_counts, conv=self, heads=heads, stretched_slots=set(spd))
 
     def close(self):
-        for stage in (self.rs, self.ts, self.fl):
+        for stage in (self.rs, self.ts, self.fl, self.sj):
             if stage is not None:
                 stage.close()
-        self.rs = self.ts = self.fl = None
+        self.rs = self.ts = self.fl = self.sj = None
 
 
 class StreamPass:
@@ -1304,9 +1457,11 @@ class StreamPass:
     It keeps the slots' encodings of its run: a slot may have been restarted by the time its chunk is read."""
 
     def __init__(self, rs: Optional[Resampler], enc: Optional[List[int]], *device_outputs, conv: Optional[StreamConverter] = None,
-                 heads: Optional[Dict[int, tuple]] = None):
+                 heads: Optional[Dict[int, tuple]] = None, stretched_slots=None):
         self.rs, self.enc = rs, enc
-        self.dev = device_outputs  # (bytes, counts, stretched fp32, stretched counts, flac bytes, flac sizes); None where not read
+        # (bytes, counts, stretched fp32, stretched counts, flac bytes, flac sizes[, joined fp32, joined counts]); None where not read
+        self.dev = device_outputs
+        self.stretched_slots = stretched_slots
         self.host = None
         self.conv, self.heads = conv, heads or {}  # FLAC slots of the run: (stream gen, rate) of each
 
@@ -1318,7 +1473,7 @@ class StreamPass:
     def chunk(self, b: int, last: bool) -> np.ndarray:
         """Slot ``b``'s chunk: its FLAC frames as uint8 (behind the stream header on the stream's first chunk), its converted
         samples (with the resampler's tail when ``last``), or the stretched float32 of a slot with a speed and no format."""
-        out, counts, stretched, st_counts, fout, fsizes = (t.numpy() if t is not None else None for t in self.host)
+        out, counts, stretched, st_counts, fout, fsizes, *rest = (t.numpy() if t is not None else None for t in self.host)
         if b in self.heads:
             from .flac import stream_header
 
@@ -1330,6 +1485,8 @@ class StreamPass:
             return np.frombuffer(data, dtype=np.uint8).copy()
         if self.enc is not None and self.enc[b] != ENC_OFF:
             return self.rs.slot_bytes(out, counts, b, tail=last, enc=self.enc[b])
+        if rest and rest[0] is not None and (self.stretched_slots is None or b not in self.stretched_slots):
+            return rest[0][b, : int(rest[1][b])].copy()  # a segmented slot with no other stage: the joined float32
         return stretched[b, : int(st_counts[b])].copy()
 
 

@@ -210,7 +210,7 @@ def generate_blocking(model: LMEngine, prompt: np.ndarray, generation_settings: 
 
 def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bool = True, max_frames: Optional[int] = None,
                overlap: bool = True, output_format: Optional[str] = None, speed_q: Optional[int] = None,
-               container: Optional[str] = None) -> Iterator[np.ndarray]:
+               container: Optional[str] = None, conv: Optional[StreamConverter] = None, final: bool = True) -> Iterator[np.ndarray]:
     """One utterance in slot 0 of ``session`` -> one 1920-sample float32 chunk per generated frame, as the reference's
     ``SmolTTS.stream`` yields them (mlx_inference/src/smoltts_mlx/__init__.py:83-95: every frame of ``SingleBatchGenerator`` through
     ``codec.decode_step``), the terminating ``<|im_end|>`` frame included.
@@ -235,7 +235,12 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
 
     ``container`` (``"flac"``): the stream's 16-bit samples (the converted ones, or the float32 quantised) are framed as FLAC on
     the codec stream behind the other stages (``engine.FlacEncoder``): uint8 chunks, the stream header in front of the first;
-    the end of the stream is derived on the device as for a speed."""
+    the end of the stream is derived on the device as for a speed.
+
+    ``conv``: the utterance is one segment of a long text (``longform``): the caller's ``StreamConverter(seam=True)``, with the
+    stream's stages started in slot 0 and this segment opened (``start_segments``), converts it and is not closed here; the
+    format, speed and container arguments are then ignored.  The end of the utterance, derived on the device, is the seam's end
+    of segment, and the end of the stream only where ``final``; the resampler's tail follows the final segment only."""
     if speed_q is not None and speed_q == 65536:
         speed_q = None
     s = session
@@ -249,12 +254,14 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     pcm_dev = torch.empty(1, 1920, dtype=torch.float32, device=dev)
     pcm_host = torch.empty(1, 1920, dtype=torch.float32).pin_memory()
     state_host = torch.zeros(2, dtype=torch.int32).pin_memory()  # n_frames[0], done[0]
+    own = conv is None
     formatted = output_format is not None and parse_stream_format(output_format)[1] != ENC_OFF
-    ends_on_device = speed_q is not None or container is not None  # a stage that must see the end of the stream
-    conv = StreamConverter(dev, 1, 1920) if formatted or ends_on_device else None
+    ends_on_device = speed_q is not None or container is not None or not own  # a stage that must see the end of the stream
+    if own:
+        conv = StreamConverter(dev, 1, 1920) if formatted or ends_on_device else None
     with torch.cuda.stream(codec_stream):
         msession.reset()
-        if conv is not None:
+        if conv is not None and own:
             conv.reset_slots([0], [output_format], [speed_q], [container])
     with torch.cuda.stream(lm_stream):
         s.prefill([prompt], stop_on_eos=stop_on_eos)  # frame 0
@@ -285,7 +292,10 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
                     valid = (n_d > f).to(torch.int32) * 1920  # 0 once the slot has stopped: garbage is not consumed
                     # the stream ends with this frame (done at it, or the frame limit), or had ended before it unseen by the host
                     last = None if not ends_on_device else ((n_d <= f) | ((done_d != 0) & (n_d == f + 1)) | (f + 1 >= limit)).to(torch.int32)
-                    out = conv.run(pcm_dev, 1920, valid, last)
+                    seg_end = None
+                    if not own:  # a segment: it ends where an utterance would; the stream only with the final one
+                        seg_end, last = last, (last if final else None)
+                    out = conv.run(pcm_dev, 1920, valid, last, seg_end=seg_end)
                     out.to_host(codec_stream)
                 else:
                     pcm_host.copy_(pcm_dev, non_blocking=True)
@@ -293,7 +303,7 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
             n, done = int(state_host[0]), int(state_host[1])
             if out is not None:
                 # (a call after the slot stopped consumed nothing: its tail is that of the last frame)
-                chunk = out.chunk(0, last=n <= f or bool(done and n == f + 1) or f + 1 >= limit)
+                chunk = out.chunk(0, last=final and (n <= f or bool(done and n == f + 1) or f + 1 >= limit))
                 if chunk.size or not ends_on_device:  # (a stretched frame that finalised no sample yields nothing)
                     yield chunk
             if n <= f:  # the slot had stopped before this frame
@@ -313,5 +323,5 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     finally:
         lm_stream.synchronize()
         codec_stream.synchronize()
-        if conv is not None:
+        if conv is not None and own:
             conv.close()

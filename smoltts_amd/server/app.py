@@ -35,6 +35,37 @@ class TTSCore:
         self.scheduler = scheduler  # BatchScheduler: concurrent requests share the GPU batch
         self.voices: Dict[str, dict] = {}  # cloned voices registered through this server: id -> {"name", "prompt_positions"}
         self._voice_lock = threading.Lock()
+        self.segments = 0  # segments of the segmented requests that completed (long_text="segment")
+        self._segments_lock = threading.Lock()
+
+    def _setting(self, name: str, default):
+        st = self.settings
+        v = st.get(name) if isinstance(st, dict) else getattr(st, name, None)
+        return default if v is None else v
+
+    @property
+    def long_text(self) -> str:
+        return self._setting("long_text", "refuse")
+
+    def _segment_kw(self, text: str) -> dict:
+        """``{"segment": options}`` in ``long_text="segment"`` mode (nothing otherwise, so that the model sees the calls it saw
+        before); a text over ``max_input_chars`` or with a bad break tag is the client's fault (ValueError).  ``"_n"``: the segments
+        the request speaks (0: an unsegmented one), counted once it has completed; the caller takes it out."""
+        if self.long_text != "segment":
+            return {}
+        from ..longform import needs_segments, split_text
+
+        limit = int(self._setting("max_input_chars", 5000))
+        if len(text) > limit:
+            raise ValueError(f"input has {len(text)} characters; max_input_chars is {limit}")
+        opts = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
+        segs = split_text(text, opts["max_bytes"])
+        return {"segment": opts, "_n": len(segs) if needs_segments(segs) else 0}
+
+    def _count_segments(self, n: int) -> None:
+        if n:
+            with self._segments_lock:
+                self.segments += n
 
     # -- cloned voices (extension: ElevenLabs' voices/add with JSON + base64 WAV samples instead of multipart)
     @property
@@ -123,6 +154,8 @@ class TTSCore:
         used = None
         sp = _speed_kw(speed)
         try:
+            sp.update(self._segment_kw(input_text))
+            n_seg = sp.pop("_n", 0)
             if self.scheduler is not None:
                 req = self.scheduler.submit(input_text, str(voice), stream=False, **({"sampling": sampling} if sampling is not None else {}), **sp)
                 used = getattr(req, "sampling", None)
@@ -133,6 +166,7 @@ class TTSCore:
                 pcm = np.asarray(self.model(input_text, str(voice), **kw, **sp)).flatten()
         except ValueError as e:  # a request the engine refuses (e.g. a text too long for max_seq_len): the client's fault, not a 500
             raise HTTPException(status_code=400, detail=str(e))
+        self._count_segments(n_seg)
         return (*self.format_audio_chunk(pcm, response_format), seed_used(used))
 
     def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
@@ -146,19 +180,22 @@ class TTSCore:
         if container is not None:
             kw["container"] = container
         sp = _speed_kw(speed)
+        sp.update(self._segment_kw(input_text))
+        n_seg = sp.pop("_n", 0)
         if self.scheduler is not None:
             req = self.scheduler.submit(input_text, str(voice), stream=True, **kw, **({"sampling": sampling} if sampling is not None else {}), **sp)
             chunks, used = self.scheduler.iter_chunks(req), getattr(req, "sampling", None)
         else:
             used = self._model_sampling(sampling)
             chunks = self.model.stream(input_text, str(voice), **kw, **({"sampling": used} if used is not None else {}), **sp)
-        return self._stream_bytes(chunks, kw), seed_used(used)
+        return self._stream_bytes(chunks, kw, n_seg), seed_used(used)
 
-    def _stream_bytes(self, chunks, kw):
+    def _stream_bytes(self, chunks, kw, n_seg: int = 0):
         try:
             for chunk in chunks:
                 if chunk is not None:
                     yield (np.asarray(chunk, dtype=np.float32) if not kw else np.ascontiguousarray(chunk)).tobytes()
+            self._count_segments(n_seg)  # (the stream is through)
         finally:
             chunks.close()  # a client that went away mid-stream: the scheduler takes its slot back (BatchScheduler.cancel)
 
@@ -324,8 +361,11 @@ def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
     """pcm_24000: raw float32 (the reference's stream); pcm_<rate>: int16 little-endian; ulaw_8000: G.711 mu-law bytes."""
     core = http_request.app.state.tts_core
     kind, rate = output_format.split("_")
-    chunks, seed = core.stream_audio(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling(),
-                                     speed=item.speed)
+    try:
+        chunks, seed = core.stream_audio(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling(),
+                                         speed=item.speed)
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
     return StreamingResponse(chunks, media_type="audio/wav", headers={
         "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed)})
 
@@ -388,8 +428,12 @@ def delete_voice(voice_id: str, http_request: Request):
 @eleven_router.get("/stats")
 def stats(http_request: Request):
     """Not in the reference: serving counters (requests by outcome, frames delivered, slots in use) of the scheduler or pool."""
-    sched = http_request.app.state.tts_core.scheduler
-    return sched.stats() if sched is not None and hasattr(sched, "stats") else {}
+    core = http_request.app.state.tts_core
+    sched = core.scheduler
+    out = sched.stats() if sched is not None and hasattr(sched, "stats") else {}
+    if core.long_text == "segment":
+        out = {**out, "segments": core.segments}  # segments of completed segmented requests
+    return out
 
 
 def _finite(v):

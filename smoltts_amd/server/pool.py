@@ -185,7 +185,18 @@ class GpuPool:
     # ------------------------------------------------------------------ client side (the BatchScheduler interface)
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
-               container: Optional[str] = None) -> _PoolRequest:
+               container: Optional[str] = None, segment=None) -> _PoolRequest:
+        """``segment``: as ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
+        if segment is not None and segment is not False:  # refused here, before a worker sees it
+            import dataclasses
+
+            from ..longform import segment_options, split_text
+
+            opts = segment_options(segment)
+            split_text(text, opts.max_bytes)  # (a bad break tag is the caller's ValueError)
+            segment = dataclasses.asdict(opts)
+        else:
+            segment = None
         if output_format is not None:  # refused here, before a worker sees it
             from ..formats import parse_stream_format
 
@@ -221,7 +232,8 @@ class GpuPool:
             self._reqs[req.rid] = req
             self._load[w] += 1
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
-        extra = {k: v for k, v in (("output_format", output_format), ("sampling", sampling), ("speed", speed), ("container", container))
+        extra = {k: v for k, v in (("output_format", output_format), ("sampling", sampling), ("speed", speed), ("container", container),
+                                                     ("segment", segment))
                  if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req

@@ -56,6 +56,16 @@ class _Request:
     speed_q: Optional[int] = None  # speaking speed in Q16 (tsm.py), time-stretched on the GPU; None: speed 1, no stretch
     stretch_in: list = field(default_factory=list)  # blocking requests with a speed: the utterance's PCM until its last pass
     container: Optional[str] = None  # streaming: "flac" frames the stream's 16-bit samples on the GPU (uint8 chunks)
+    # a long text as chained segments (longform.py): the request keeps its slot from its first segment to its last
+    segs: object = None          # the segments (None: one utterance)
+    seg_opts: object = None      # longform.SegmentOptions
+    seg_k: int = 0               # the segment in the slot now
+    seg_sampling: object = None  # the sampling of segment seg_k (its seed is seed_k)
+    seg_prev: object = None      # (text, (n_codebooks, F) codes) of the segment before seg_k: its context
+    seg_cols: list = field(default_factory=list)  # semantic code columns of segment seg_k so far
+    seg_pcm: dict = field(default_factory=dict)   # blocking: segment -> its PCM pieces from the codec
+    seg_done: int = 0            # blocking: segments whose PCM is complete
+    parent: object = None        # blocking: the segmented request whose segment seg_k this codec job decodes
 
 
 @dataclass
@@ -173,7 +183,9 @@ class BatchScheduler:
         self._deliveries: List[_Delivery] = []  # codec passes whose PCM has not been handed out yet, in order
         self._snaps: List[_Snapshot] = []       # snapshots of the output ring the host has not looked at yet (oldest first)
         self._tick_no = 0                       # ticks queued so far
-        self._counts = {"completed": 0, "cancelled": 0, "failed": 0, "frames_delivered": 0, "prefix_installs": 0}
+        self._counts = {"completed": 0, "cancelled": 0, "failed": 0, "frames_delivered": 0, "prefix_installs": 0, "segments": 0}
+        self._refills: List[_Request] = []      # segmented requests whose slot waits for their next segment's prompt
+        self._block_seam = None                 # seam stage of the blocking segmented requests (engine.SeamJoiner, 1 slot)
         self._dead: Optional[Exception] = None  # why the worker stopped
         self._draining = False
         self._held: Optional[_Request] = None   # next in line, waiting for room in a prefill call
@@ -189,7 +201,7 @@ class BatchScheduler:
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
-               container: Optional[str] = None) -> _Request:
+               container: Optional[str] = None, segment=None) -> _Request:
         """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
         in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
@@ -198,11 +210,25 @@ class BatchScheduler:
         (tsm.py).  A stream is stretched in its codec pass in front of the format conversion, a blocking utterance as a whole.
         ``container`` (streaming only, ``ValueError`` otherwise): ``"flac"`` frames the stream's 16-bit samples (of its
         ``pcm_<rate>``, 24 kHz by default) as FLAC in the same pass, behind the other stages: uint8 chunks, the stream header in
-        front of the first."""
+        front of the first.
+        ``segment`` (True, a dict or a ``longform.SegmentOptions``): a long text is spoken as chained segments in one slot, kept
+        from the first segment to the last; each segment's end, seen in a snapshot, refills the slot with the next chained
+        prompt.  A stream runs through the seam stage in front of its other stages (one stream); a blocking request decodes
+        each segment as its own codec job and joins them on the GPU.  A text that is one segment without break tags is an
+        ordinary request."""
         from ..config import RequestSampling
+        from ..longform import needs_segments, segment_options, split_text
         from ..tsm import parse_speed
 
         speed_q = parse_speed(speed)
+        opts = segment_options(segment)
+        segs = None
+        if opts is not None:
+            segs = split_text(text, opts.max_bytes)
+            if not segs:
+                raise ValueError("the text has nothing to speak")
+            if not needs_segments(segs):
+                segs = None
         if container is not None:
             from ..formats import check_container
 
@@ -225,6 +251,8 @@ class BatchScheduler:
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
                        output_format=output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=speed_q,
                        container=container)
+        if segs is not None:
+            req.segs, req.seg_opts, req.seg_sampling = segs, opts, resolved
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
@@ -256,6 +284,8 @@ class BatchScheduler:
         request that is still queued never starts.  The slot itself simply keeps decoding until it is restarted — a batch
         step costs the same with or without it.  Nothing more is delivered except the end marker."""
         req.cancelled = True
+        for part in list(req.seg_pcm.get("parts", [])):
+            part.cancelled = True
 
     # ------------------------------------------------------------------ client side: registered voices
     def add_voice(self, voice_id: str, samples=None, grid=None, system_prompt: Optional[str] = None, name: Optional[str] = None) -> dict:
@@ -304,12 +334,12 @@ class BatchScheduler:
             self._draining = True
             deadline = time.time() + timeout
             while (self._thread.is_alive() and time.time() < deadline and
-                   (self._active or self._side is not None or self._retiring or self._held is not None or not self._pending.empty() or self._codec_backlog() or self._deliveries or self._stretches)):
+                   (self._active or self._side is not None or self._retiring or self._refills or self._held is not None or not self._pending.empty() or self._codec_backlog() or self._deliveries or self._stretches)):
                 time.sleep(0.01)
         self._stop.set()
         self._wake.set()
         self._thread.join(timeout=30)
-        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch"):
+        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch", "_block_seam"):
             if getattr(self, name) is not None:
                 getattr(self, name).close()
                 setattr(self, name, None)
@@ -356,7 +386,7 @@ class BatchScheduler:
         other slot none.  A slot with a speed ends its stream (flushes) in the tick where the host will see it finish, by the
         rule of ``_drain`` on the same snapshot (``n_frames_d``, ``done_d``).  Returns the ``engine.StreamPass``, or None when no
         request in ``reqs`` has a format or a speed (then nothing is uploaded or launched)."""
-        if not any(r.output_format or r.speed_q or r.container for r in reqs):
+        if not any(r.output_format or r.speed_q or r.container or r.segs is not None for r in reqs):
             return None
         from ..engine import upload
 
@@ -369,10 +399,18 @@ class BatchScheduler:
         f0_d, cap_d = upload([f0, cap], self.session.engine.device)
         n_d = n_frames_d.to(torch.int32)
         valid = ((torch.minimum(n_d, cap_d) - f0_d).clamp_(0, self.tick) * 1920).to(torch.int32)
-        last = None
-        if any(r.speed_q or r.container for r in reqs):
+        last = seg_end = None
+        if any(r.segs is not None for r in reqs):
+            # a segmented stream: its segment ends where an utterance would; the stream ends with its final segment only
+            fin = np.zeros(self.B, np.int32)
+            for r in reqs:
+                fin[r.slot] = r.segs is None or r.seg_k == len(r.segs) - 1
+            fin_d, = upload([fin], self.session.engine.device)
+            ends = stream_ends(n_d, done_d, cap_d) & (cap_d > 0)
+            seg_end, last = ends.to(torch.int32), (ends & (fin_d != 0)).to(torch.int32)
+        elif any(r.speed_q or r.container for r in reqs):
             last = (stream_ends(n_d, done_d, cap_d) & (cap_d > 0)).to(torch.int32)
-        return self._stream_conv.run(pcm, self.tick * 1920, valid, last, slots=[r.slot for r in reqs])
+        return self._stream_conv.run(pcm, self.tick * 1920, valid, last, slots=[r.slot for r in reqs], seg_end=seg_end)
 
     def _admit(self) -> None:
         if self._side is not None and self._side["state"] == "running":
@@ -382,26 +420,34 @@ class BatchScheduler:
         side = self.side_prefill and self._side is None and len(self._active) >= self.side_min_active
         if self._side is not None:
             return  # one refill at a time: the next arrivals wait for it (at most a tick)
-        if self._held is not None or not self._pending.empty():
+        if self._held is not None or not self._pending.empty() or self._refills:
             # A request that ends by its frame budget ends in a tick known since its admission.  Once that tick is queued the
             # slot can take its next tenant straight away: the prefill is queued behind the tick, and the snapshots (device-side
             # copies queued behind their ticks) still show the old tenant's last frames when the host gets to them.
             for slot, r in list(self._active.items()):
-                if r.last_tick < self._tick_no and not r.cancelled:
+                if r.last_tick < self._tick_no and not r.cancelled and r.segs is None:  # (a segmented one keeps its slot)
                     r.retired = True
                     self._retiring.append(r)
                     del self._active[slot]
                     self._free.append(slot)
         freed = [b for b in self._free if self._slot_sampling[b] != self._default_sampling]  # handed back: the default again
-        while self._free and (self._held is not None or not self._pending.empty()):
-            req, self._held = (self._held, None) if self._held is not None else (self._pending.get_nowait(), None)
+        while self._refills or (self._free and (self._held is not None or not self._pending.empty())):
+            refill = bool(self._refills)  # a segmented request's next segment: its slot is its own, it goes first
+            if refill:
+                req = self._refills.pop(0)
+            else:
+                req, self._held = (self._held, None) if self._held is not None else (self._pending.get_nowait(), None)
             if req.cancelled:
+                if refill:
+                    self._free.append(req.slot)
                 self._end(req)
                 continue
             if req.prompt is None:
                 try:
                     v = req.voice_entry
-                    if v is not None:  # a registered voice: its speaker turns' KV rows are installed, its own turns prefilled at P
+                    if req.segs is not None:
+                        self._segment_prompt(req)
+                    elif v is not None:  # a registered voice: its speaker turns' KV rows are installed, its own turns prefilled at P
                         P = int(v.grid.shape[1])
                         req.prompt = self.tts.prompt_encoder.build_prompt(req.text, req.voice, v.grid)[:, P:]
                         req.pos0, req.prefix = P, v.prefix
@@ -413,23 +459,26 @@ class BatchScheduler:
                     if min(req.prompt.shape[1], self.prefill_chunk or req.prompt.shape[1]) > self.session.max_rows:
                         raise ValueError("prompt exceeds the session's prefill workspace")
                 except Exception as e:  # bad request: answer it, keep serving
+                    if refill:
+                        self._free.append(req.slot)
                     self._end(req, e)
                     continue
             need = req.prompt.shape[1] if side else min(req.prompt.shape[1], self.prefill_chunk or req.prompt.shape[1])
             if side and need > self.session.max_rows:
                 side = False if not new else side  # a prompt too long for one side call goes in line, in chunks (alone)
                 if new:
-                    self._held = req
+                    self._hold(req, refill)
                     break
                 need = min(req.prompt.shape[1], self.prefill_chunk or req.prompt.shape[1])
             if new and rows + need > self.session.max_rows:  # no room in this call: first in line next time
-                self._held = req
+                self._hold(req, refill)
                 break
             rows += need
-            req.slot = self._free.pop(0)
+            if not refill:
+                req.slot = self._free.pop(0)
             new.append(req)
         entries = {b: self._default_sampling for b in freed}
-        entries.update({r.slot: r.sampling for r in new})
+        entries.update({r.slot: (r.seg_sampling if r.segs is not None else r.sampling) for r in new})
         self._write_sampling(entries)  # on the frame stream, ahead of the park / prefill of the new tenants
         if not new:
             return
@@ -452,6 +501,53 @@ class BatchScheduler:
                 self._end(r, e)
             raise
         self._enter(new)
+
+    def _hold(self, req: _Request, refill: bool) -> None:
+        if refill:
+            self._refills.insert(0, req)
+        else:
+            self._held = req
+
+    def _segment_prompt(self, req: _Request) -> None:
+        """Segment ``req.seg_k``'s chained prompt (longform.chain_prompt); a registered voice's prefix rows are installed for
+        every segment and only the turns after them are prefilled."""
+        from ..longform import chain_prompt, voice_prefix
+
+        enc = self.tts.prompt_encoder
+        v = req.voice_entry
+        prefix = voice_prefix(enc, req.voice, v.grid if v is not None else self.tts.voices.get(req.voice))
+        prev = req.seg_prev if req.seg_opts.context == "previous" and req.seg_prev is not None else (None, None)
+        prompt = chain_prompt(enc, prefix, req.segs[req.seg_k].text, *prev, max_new_tokens=req.max_new_tokens,
+                              max_seq=self.session.max_seq)
+        if v is not None:
+            P = int(v.grid.shape[1])
+            req.prompt, req.pos0, req.prefix = prompt[:, P:], P, v.prefix
+        else:
+            req.prompt = prompt
+
+    def _next_segment(self, r: _Request, cols: np.ndarray) -> None:
+        """Segment r.seg_k has ended (seen in a snapshot): its codes become the next one's context and the slot, still the
+        request's, waits in ``_refills`` for the next chained prompt."""
+        import dataclasses
+
+        from ..longform import segment_seed
+
+        r.seg_prev = (r.segs[r.seg_k].text, cols.T.copy())
+        r.seg_k += 1
+        r.seg_sampling = dataclasses.replace(r.sampling, seed=segment_seed(r.sampling.seed, r.seg_k))
+        r.prompt, r.emitted, r.seg_cols = None, 0, []
+        del self._active[r.slot]
+        self._refills.append(r)
+
+    def _seam_args(self, r: _Request):
+        """(pause, flags, lead) of the seam stage for segment r.seg_k, in samples."""
+        from ..engine import SEAM_FINAL, SEAM_FIRST
+        from ..seam import pause_samples
+
+        k, segs, final = r.seg_k, r.segs, r.seg_k == len(r.segs) - 1
+        pause = pause_samples(segs[-1].pause_after_s) if final else pause_samples(
+            segs[k].pause_after_s if segs[k].pause_after_s is not None else r.seg_opts.pause_s)
+        return pause, (SEAM_FIRST if k == 0 else 0) | (SEAM_FINAL if final else 0), pause_samples(segs[0].pause_before_s)
 
     def _write_sampling(self, entries: Dict[int, object]) -> None:
         """Slot b samples with ``entries[b]`` from the next pick on the current stream on (only changed entries are uploaded)."""
@@ -593,8 +689,15 @@ class BatchScheduler:
             restart += [b for b in range(self.B) if b not in live and (self._codec_age[b] + 2) * 2 * self.tick > cap]
             if restart:
                 self._stream_codec.reset_slots(sorted(set(restart)))
-                self._stream_conv.reset_slots([r.slot for r in new], [r.output_format for r in new], [r.speed_q for r in new],
-                                              [r.container for r in new])
+                # (a segmented stream's later segments restart the codec only: its other stages run on)
+                fresh = [r for r in new if r.segs is None or r.seg_k == 0]
+                self._stream_conv.reset_slots([r.slot for r in fresh], [r.output_format for r in fresh],
+                                              [r.speed_q for r in fresh], [r.container for r in fresh])
+                segd = [r for r in new if r.segs is not None]
+                if segd:
+                    args = [self._seam_args(r) for r in segd]
+                    self._stream_conv.start_segments([r.slot for r in segd], [a[0] for a in args], [a[1] for a in args],
+                                                     [a[2] for a in args])
                 for b in restart:
                     self._codec_age[b] = 0
             for b in range(self.B):
@@ -653,16 +756,26 @@ class BatchScheduler:
                 continue
             n = min(int(n_frames[slot]), r.max_new_tokens + 1)
             finished = bool(stream_ends(n_frames[slot], done[slot], r.max_new_tokens + 1))
+            seg_more = r.segs is not None and r.seg_k + 1 < len(r.segs)  # a segment follows this one
             if r.stream:
                 # streaming requests decode every frame (__init__.py:88-92); this tick's PCM of the slot starts at its frame
                 # r.emitted (== f0 of the tick: one codec frame per LM frame)
                 k = n - r.emitted
+                if r.segs is not None and k > 0:  # the next segment's context: this one's semantic frames
+                    slow = codes[slot, r.emitted:n, 0]
+                    keep = (slow >= tc.semantic_start_id) & (slow <= tc.semantic_end_id)
+                    r.seg_cols.append(codes[slot, r.emitted:n][keep][:, -nq:].astype(np.int32))
                 if k > 0 or finished:
                     assert k == 0 or (stream_pass is not None and r.emitted == (tick_no - r.first_tick) * self.tick), "stream bookkeeping out of step"
-                    stream_items.append((r, slot, max(k, 0) * 1920, finished))
+                    stream_items.append((r, slot, max(k, 0) * 1920, finished and not seg_more))
                     urgent = urgent or r.emitted == 0
                 r.emitted = n
                 if finished:
+                    if r.segs is not None:
+                        self._counts["segments"] += 1
+                    if seg_more:
+                        self._next_segment(r, np.concatenate(r.seg_cols) if r.seg_cols else np.zeros((0, nq), np.int32))
+                        continue
                     r.stream_done = True
                     release(r)  # the end marker follows the last chunk, in _deliver
                 continue
@@ -673,6 +786,20 @@ class BatchScheduler:
             r.emitted = n
             if cols.shape[0]:
                 r.pending.append(cols)
+            if finished and r.segs is not None:  # a segment of a blocking segmented request: its own codec job
+                self._counts["segments"] += 1
+                seg_cols = np.concatenate(r.pending) if r.pending else np.zeros((0, nq), np.int32)
+                part = _Request(r.text, r.voice, False, r.max_new_tokens, pending=[seg_cols], seg_k=r.seg_k, parent=r,
+                                cancelled=r.cancelled)
+                r.seg_pcm.setdefault("parts", []).append(part)
+                r.seg_pcm[r.seg_k] = []
+                r.pending = []
+                self._finished.append(part)
+                if seg_more:
+                    self._next_segment(r, seg_cols)
+                else:
+                    release(r)  # its end marker follows the joined audio (_part_done)
+                continue
             if finished:
                 release(r)
                 self._finished.append(r)
@@ -790,7 +917,14 @@ class BatchScheduler:
                 host = host.numpy()
             self._deliveries.pop(0)
             for r, b, n, fin in d.items:
-                if r.stream and (r.output_format or r.speed_q or r.container) and d.conv is not None:
+                if r.parent is not None:  # a segment of a blocking segmented request
+                    if n and not r.cancelled:
+                        r.parent.seg_pcm[r.seg_k].append(host[b, :n].copy())
+                        self._counts["frames_delivered"] += n // 1920
+                    if fin:
+                        self._part_done(r)
+                    continue
+                if r.stream and (r.output_format or r.speed_q or r.container or r.segs is not None) and d.conv is not None:
                     chunk = d.conv.chunk(b, fin)  # (the tail goes out with the last chunk)
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
@@ -808,6 +942,36 @@ class BatchScheduler:
                 if fin:
                     self._end(r)
             wait = False
+
+    def _part_done(self, part: _Request) -> None:
+        """A segment's PCM of a blocking segmented request is complete; once all are, they are joined on the GPU (engine.seam_join)
+        and go out, stretched first when the request has a speed."""
+        from ..engine import SeamJoiner, seam_join
+        from ..seam import pause_samples
+
+        r = part.parent
+        r.seg_done += 1
+        if r.cancelled:
+            self._end(r)
+            return
+        if r.seg_done < len(r.segs):
+            return
+        torch = self._torch
+        pcms = [np.concatenate(r.seg_pcm[k]) if r.seg_pcm[k] else np.zeros(0, np.float32) for k in range(len(r.segs))]
+        pauses = [pause_samples(s.pause_after_s if s.pause_after_s is not None else r.seg_opts.pause_s) for s in r.segs[:-1]]
+        dev = self.session.engine.device
+        with torch.cuda.stream(self._stretch_stream):
+            if self._block_seam is None:
+                self._block_seam = SeamJoiner(dev, 1)
+            pcm = seam_join(pcms, pauses, dev, lead=pause_samples(r.segs[0].pause_before_s),
+                            trail=pause_samples(r.segs[-1].pause_after_s), joiner=self._block_seam)
+        r.seg_pcm = {}
+        if r.speed_q:
+            r.stretch_in = [pcm]
+            self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
+            return
+        r.out.put(pcm)
+        self._end(r)
 
     STRETCH_SLOTS, STRETCH_PIECE = 16, 65536  # blocking utterances stretched side by side, input samples per slot and call
 
@@ -918,6 +1082,8 @@ class BatchScheduler:
                         if self._deliveries or self._codec_backlog():
                             self._deliver(wait=not self._codec_backlog())  # keep the passes coming while there is codec work
                             continue
+                        if self._refills:  # a segmented request's next segment: admitted at the top of the loop
+                            continue
                         if self._stretches:  # only stretches in flight: look again shortly, or sooner for a new request
                             self._poll_stretches()
                             self._wake.wait(timeout=0.0005)
@@ -944,6 +1110,10 @@ class BatchScheduler:
 
     def _end(self, r: _Request, e: Optional[Exception] = None) -> None:
         """Queue the end marker of a request (exactly once)."""
+        if r.parent is not None:  # a segment's codec job: the segmented request ends, not its part
+            if r.cancelled or e is not None:
+                self._end(r.parent, e)
+            return
         if not r.closed:
             r.closed = True
             self._counts["failed" if e is not None else ("cancelled" if r.cancelled else "completed")] += 1
@@ -971,7 +1141,8 @@ class BatchScheduler:
             self._held = None
         side = self._side["reqs"] if self._side is not None else []
         self._side = None
-        for r in list(self._active.values()) + side + self._retiring + self._finished + [j.req for j in self._codec_jobs if j is not None]:
+        for r in (list(self._active.values()) + side + self._retiring + self._refills + self._finished +
+                  [j.req for j in self._codec_jobs if j is not None]):
             self._end(r, e)
         self._codec_jobs = [None] * len(self._codec_jobs)
         for d in self._deliveries:
@@ -979,6 +1150,7 @@ class BatchScheduler:
                 self._end(r, e)
         self._active.clear()
         self._retiring = []
+        self._refills = []
         self._finished = []
         self._deliveries = []
         for job in self._stretches:

@@ -1,7 +1,8 @@
 """The server's settings file, same schema and validation as the reference (server/settings.py:12-63): exactly one of
 ``model_id`` / ``checkpoint_dir``, a ``generation`` block (lm/generate.py:12-16) and a ``model_type`` block
 (lm/config.py:5-12).  Extensions of this build: ``mimi_checkpoint`` (the reference downloads kyutai/mimi; there is no
-network here), ``max_batch`` (slots per GPU), ``weight_format`` ("bf16" | "fp8"), ``max_voices`` (cloned voices held at once).  ``model_id`` is accepted by the schema
+network here), ``max_batch`` (slots per GPU), ``weight_format`` ("bf16" | "fp8"), ``max_voices`` (cloned voices held at once),
+``long_text`` / ``segment_max_bytes`` / ``seam_pause_ms`` / ``max_input_chars`` (long texts as chained segments).  ``model_id`` is accepted by the schema
 but cannot be resolved without network access; ``get_checkpoint_dir`` says so."""
 from __future__ import annotations
 
@@ -48,6 +49,13 @@ class ServerSettings(BaseModel):
     # (extension) cloned voices a server holds at once (POST /v1/voices/add); each costs its speaker prompt's KV rows on every GPU,
     # P x 20 KB at 150m (P: about 12.5 positions per second of reference audio, plus the transcripts)
     max_voices: int = Field(default=64, ge=0)
+    # (extension) a text too long for one prompt: "refuse" answers 400 as before; "segment" speaks it as chained sentence segments
+    # of at most segment_max_bytes UTF-8 bytes joined on the GPU with seam_pause_ms between them, break tags honoured
+    # (longform.py); inputs over max_input_chars are then refused with 400.
+    long_text: Literal["refuse", "segment"] = "refuse"
+    segment_max_bytes: int = Field(default=300, ge=16, le=1000)
+    seam_pause_ms: int = Field(default=250, ge=0, le=3000)
+    max_input_chars: int = Field(default=5000, ge=1)
 
     model_config = {"protected_namespaces": ()}
 
