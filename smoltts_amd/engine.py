@@ -9,8 +9,10 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
+from dataclasses import dataclass, replace
+from functools import cached_property
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -970,31 +972,71 @@ def resample_design(out_rate: int):
     return taps, up.value, down.value, half.value
 
 
-class Resampler:
+class _Stage:
+    """What the stages behind the codec share: a slab of ``smoltts_<C_NAME>_bytes(max_batch)`` bytes that the handle of
+    ``smoltts_<C_NAME>_create`` lives in, destroyed by ``close`` once the device is idle, and the checks of a ``chunk`` call."""
+
+    C_NAME = ""
+
+    def __init__(self, device: torch.device, max_batch: int):
+        self.lib = load_library()
+        self.device, self.B = device, max_batch
+        need = getattr(self.lib, f"smoltts_{self.C_NAME}_bytes")(max_batch)
+        if need == 0:
+            raise SmolttsError(f"smoltts_{self.C_NAME}_bytes returned 0 (bad sizes)")
+        self.slab = _alloc_slab(need, device, settle=True)
+        h = C.c_void_p()
+        check(getattr(self.lib, f"smoltts_{self.C_NAME}_create")(dptr(self.slab), need, max_batch, C.byref(h)),
+              f"smoltts_{self.C_NAME}_create")
+        self.handle = h
+
+    @staticmethod
+    def _ints(v: Sequence[int]):
+        """``v`` as a host int32 array for the C calls."""
+        return (C.c_int32 * len(v))(*[int(x) for x in v])
+
+    def _check(self, batch: int, pcm: Optional[torch.Tensor], n_in: int, out: torch.Tensor, dtype, width: int,
+               counts: torch.Tensor, per_row: int, *controls: Optional[torch.Tensor]) -> None:
+        """``pcm``: device fp32 [>= batch, >= n_in] with unit-stride rows (None: not read); ``out``: contiguous ``dtype``
+        [>= batch, >= width]; ``counts``: contiguous int32 of ``per_row`` entries per row; ``controls``: None or contiguous
+        device int32 [>= batch]."""
+        assert batch <= self.B and out.dtype == dtype and out.is_contiguous() and out.shape[0] >= batch and out.shape[1] >= width
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.shape[0] >= batch and counts.numel() >= per_row * batch
+        assert pcm is None or (pcm.dtype == torch.float32 and pcm.stride(1) == 1 and pcm.shape[0] >= batch and 0 <= n_in <= pcm.shape[1])
+        for t in controls:
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= batch)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize()
+            getattr(self.lib, f"smoltts_{self.C_NAME}_destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Resampler(_Stage):
     """Per-slot conversion of streamed 24 kHz fp32 PCM to ``pcm_<rate>`` int16 / ``ulaw_8000`` bytes on the GPU
     (include/smoltts_hip.h, "Streamed output formats"): one launch per call for every slot, each at its own format.  Slots
     start off; ``reset_slots`` starts a new stream in a slot with its format."""
 
+    C_NAME = "resampler"
+
     def __init__(self, device: torch.device, max_batch: int, max_in: int):
-        self.lib = load_library()
-        self.device, self.B, self.max_in = device, max_batch, max_in
-        need = self.lib.smoltts_resampler_bytes(max_batch)
-        if need == 0:
-            raise SmolttsError("smoltts_resampler_bytes returned 0 (bad sizes)")
-        self.slab = _alloc_slab(need, device, settle=True)
-        h = C.c_void_p()
-        check(self.lib.smoltts_resampler_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_resampler_create")
-        self.handle = h
+        super().__init__(device, max_batch)
         self.out_stride = int(self.lib.smoltts_resampler_out_bytes(max_in))
         self.formats = [(24000, 0)] * max_batch  # (rate, SMOLTTS_RESAMPLE_*) per slot
 
     def reset_slots(self, slots: Sequence[int], formats: Sequence[str]) -> None:
         """Start new streams in ``slots`` with their ``output_format`` (``pcm_24000``: the slot is not converted)."""
         parsed = [parse_stream_format(f) for f in formats]
-        n = len(slots)
-        arr = lambda v: (C.c_int32 * n)(*v)  # noqa: E731
-        check(self.lib.smoltts_resampler_reset_slots(self.handle, arr(slots), arr([p[0] for p in parsed]), arr([p[1] for p in parsed]), n,
-                                                     current_stream_ptr()), "smoltts_resampler_reset_slots")
+        check(self.lib.smoltts_resampler_reset_slots(self.handle, self._ints(slots), self._ints([p[0] for p in parsed]),
+                                                     self._ints([p[1] for p in parsed]), len(slots), current_stream_ptr()),
+              "smoltts_resampler_reset_slots")
         for b, p in zip(slots, parsed):
             self.formats[b] = p
 
@@ -1009,11 +1051,7 @@ class Resampler:
         """Convert ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream;
         ``valid``: device int32 [batch], the samples of each row that are real (the rest is not consumed)."""
         batch = pcm.shape[0]
-        assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and batch <= self.B and 0 <= n_in <= min(self.max_in, pcm.shape[1])
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[0] >= batch
-        assert out.shape[1] >= int(self.lib.smoltts_resampler_out_bytes(n_in))
-        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 2 * batch
-        assert valid is None or (valid.dtype == torch.int32 and valid.is_contiguous() and valid.numel() >= batch)
+        self._check(batch, pcm, n_in, out, torch.uint8, int(self.lib.smoltts_resampler_out_bytes(n_in)), counts, 2, valid)
         check(self.lib.smoltts_resample_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1],
                                               dptr(counts), current_stream_ptr()), "smoltts_resample_chunk")
 
@@ -1026,47 +1064,22 @@ class Resampler:
         width = 1 if enc == 2 else 2
         return host_out[b, : n * width].view(np.uint8 if enc == 2 else np.int16).copy()
 
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize()
-            self.lib.smoltts_resampler_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ------------------------------------------------------------------------------- speaking speed
-class TimeStretcher:
+class TimeStretcher(_Stage):
     """Per-slot pitch-preserving time stretch of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Speaking speed";
     the numpy model is ``tsm.Stretcher``): one launch per call for every slot, each at its own speed.  Slots start off;
     ``reset_slots`` starts a new stream in a slot at its ``speed_q`` (65536: off)."""
 
-    def __init__(self, device: torch.device, max_batch: int):
-        self.lib = load_library()
-        self.device, self.B = device, max_batch
-        need = self.lib.smoltts_tsm_bytes(max_batch)
-        if need == 0:
-            raise SmolttsError("smoltts_tsm_bytes returned 0 (bad sizes)")
-        self.slab = _alloc_slab(need, device, settle=True)
-        h = C.c_void_p()
-        check(self.lib.smoltts_tsm_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_tsm_create")
-        self.handle = h
-        self.speed_q = [65536] * max_batch
+    C_NAME = "tsm"
 
     def out_samples(self, n_in: int) -> int:
         """Output samples per row that a call of ``n_in`` input samples needs."""
         return int(self.lib.smoltts_tsm_out_samples(int(n_in)))
 
     def reset_slots(self, slots: Sequence[int], speed_q: Sequence[int]) -> None:
-        n = len(slots)
-        arr = lambda v: (C.c_int32 * n)(*[int(x) for x in v])  # noqa: E731
-        check(self.lib.smoltts_tsm_reset_slots(self.handle, arr(slots), arr(speed_q), n, current_stream_ptr()), "smoltts_tsm_reset_slots")
-        for b, q in zip(slots, speed_q):
-            self.speed_q[b] = int(q)
+        check(self.lib.smoltts_tsm_reset_slots(self.handle, self._ints(slots), self._ints(speed_q), len(slots), current_stream_ptr()),
+              "smoltts_tsm_reset_slots")
 
     def new_outputs(self, batch: int, n_in: int):
         """Device buffers of one call of at most ``n_in`` input samples: (fp32 [batch, out_samples(n_in)], counts int32 [batch])."""
@@ -1079,11 +1092,7 @@ class TimeStretcher:
         ``valid``: device int32 [batch], the samples of each row that are real; ``last``: device int32 [batch], nonzero where the
         row's stream ends with this call (the slot flushes).  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
         batch = pcm.shape[0]
-        assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and batch <= self.B and 0 <= n_in <= pcm.shape[1]
-        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= batch and out.shape[1] >= self.out_samples(n_in)
-        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= batch
-        for t in (valid, last):
-            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= batch)
+        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, last)
         check(self.lib.smoltts_tsm_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(last), dptr(out),
                                          out.shape[1], dptr(counts), current_stream_ptr()), "smoltts_tsm_chunk")
 
@@ -1093,40 +1102,50 @@ class TimeStretcher:
         check(self.lib.smoltts_tsm_slot_state(self.handle, int(slot), v, current_stream_ptr()), "smoltts_tsm_slot_state")
         return dict(zip(("k", "p_prev", "n_in", "n_out", "ended"), list(v)))
 
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize()
-            self.lib.smoltts_tsm_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
+def _whole_row(stage: _Stage, x: np.ndarray, launch):
+    """A whole utterance through slot 0 of ``stage``: ``x`` (host, contiguous) goes up as the device row [1, n] (one zero sample
+    when empty), and ``launch(row, n, out, counts)`` queues the stage's call into ``stage.new_outputs(1, n)``.  Waits, and
+    returns the output row cut to its count, or for FLAC (counts: frame sizes [1, blocks, 2]) the row's frames."""
+    n = int(x.size)
+    row = torch.from_numpy(x).to(stage.device)[None] if n else torch.zeros(1, 1, dtype=torch.from_numpy(x).dtype, device=stage.device)
+    out, counts = stage.new_outputs(1, n)
+    launch(row, n, out, counts)
+    if counts.dim() == 1:
+        return out[0, :int(counts.cpu()[0])].cpu().numpy()
+    return FlacEncoder.slot_frames(out.cpu().numpy(), counts.cpu().numpy(), 0)
+
+
+def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device) -> np.ndarray:
+    """A whole utterance (float32 at 24 kHz) stretched on ``device`` (the model's) in one call with ``last`` set: exactly
+    ``tsm.out_length(len(pcm), speed_q)`` samples (``SmolTTS.__call__``).  Waits for the result.  ``speed_q == 65536`` returns
+    ``pcm`` untouched."""
+    pcm = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    if speed_q == 65536:
+        return pcm
+    with torch.cuda.device(device):
+        ts = TimeStretcher(device, 1)
         try:
-            self.close()
-        except Exception:
-            pass
+            ts.reset_slots([0], [speed_q])
+            return _whole_row(ts, pcm, lambda x, n, out, cnt: ts.chunk(x, n, out, cnt, last=torch.ones(1, dtype=torch.int32, device=device)))
+        finally:
+            ts.close()
 
 
 # ------------------------------------------------------------------------------- long texts: the seam between segments
 SEAM_FIRST, SEAM_FINAL, SEAM_OFF = 1, 2, 4  # SMOLTTS_SEAM_*
 
 
-class SeamJoiner:
+class SeamJoiner(_Stage):
     """Per-slot joining of a long text's segments on the GPU (include/smoltts_hip.h, "Seam"; the numpy model is
     ``seam.SeamState``): one launch per call for every slot.  Slots start off; ``start_segments`` opens a segment in a slot with
     its pause and flags (``SEAM_FIRST`` / ``SEAM_FINAL``; ``SEAM_OFF`` switches the slot off)."""
 
+    C_NAME = "seam"
+
     def __init__(self, device: torch.device, max_batch: int):
-        self.lib = load_library()
-        self.device, self.B = device, max_batch
-        need = self.lib.smoltts_seam_bytes(max_batch)
-        if need == 0:
-            raise SmolttsError("smoltts_seam_bytes returned 0 (bad sizes)")
-        self.slab = _alloc_slab(need, device, settle=True)
-        h = C.c_void_p()
-        check(self.lib.smoltts_seam_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_seam_create")
-        self.handle = h
-        self.on = [False] * max_batch  # the slot's stream is segmented (it stays on between its segments)
-        self.zeros = [0] * max_batch   # zeros the slot's open segment owes at most (its lead and its pause)
+        super().__init__(device, max_batch)
+        self.zeros = [0] * max_batch  # zeros the slot's open segment owes at most (its lead and its pause)
 
     def out_samples(self, n_in: int) -> int:
         """Output samples per row of a call of ``n_in`` input samples, for the segments open now."""
@@ -1139,12 +1158,11 @@ class SeamJoiner:
         n = len(slots)
         if not n:
             return
-        arr = lambda v: (C.c_int32 * n)(*[int(x) for x in v])  # noqa: E731
-        check(self.lib.smoltts_seam_reset_slots(self.handle, arr(slots), arr(pauses), arr(flags), arr(leads or [0] * n), n,
-                                                current_stream_ptr()), "smoltts_seam_reset_slots")
-        for b, p, f, ld in zip(slots, pauses, flags, leads or [0] * n):
-            self.on[b] = not (int(f) & SEAM_OFF)
-            self.zeros[b] = (int(p) + (int(ld) if int(f) & SEAM_FIRST else 0)) if self.on[b] else 0
+        leads = leads or [0] * n
+        check(self.lib.smoltts_seam_reset_slots(self.handle, self._ints(slots), self._ints(pauses), self._ints(flags), self._ints(leads),
+                                                n, current_stream_ptr()), "smoltts_seam_reset_slots")
+        for b, p, f, ld in zip(slots, pauses, flags, leads):
+            self.zeros[b] = 0 if int(f) & SEAM_OFF else int(p) + (int(ld) if int(f) & SEAM_FIRST else 0)
 
     def new_outputs(self, batch: int, n_in: int):
         """Device buffers of one call of at most ``n_in`` input samples: (fp32 [batch, out_samples(n_in)], counts int32 [batch])."""
@@ -1157,11 +1175,7 @@ class SeamJoiner:
         ``valid``: device int32 [batch], the real samples of each row; ``seg_end`` / ``last``: device int32 [batch], nonzero where
         the row's segment / stream ends with this call.  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
         batch = pcm.shape[0]
-        assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and batch <= self.B and 0 <= n_in <= pcm.shape[1]
-        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= batch and out.shape[1] >= self.out_samples(n_in)
-        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= batch
-        for t in (valid, seg_end, last):
-            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= batch)
+        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, seg_end, last)
         check(self.lib.smoltts_seam_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(seg_end), dptr(last),
                                           max(self.zeros), dptr(out), out.shape[1], dptr(counts), current_stream_ptr()),
               "smoltts_seam_chunk")
@@ -1171,18 +1185,6 @@ class SeamJoiner:
         v = (C.c_int64 * 8)()
         check(self.lib.smoltts_seam_slot_state(self.handle, int(slot), v, current_stream_ptr()), "smoltts_seam_slot_state")
         return dict(zip(("n_in", "judged", "ec", "head", "open", "lead", "pause", "flags"), list(v)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize()
-            self.lib.smoltts_seam_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: torch.device, lead: int = 0, trail: int = 0,
@@ -1202,11 +1204,7 @@ def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: tor
                 final = k == len(segs) - 1
                 sj.start_segments([0], [trail if final else pauses[k]], [(SEAM_FIRST if k == 0 else 0) | (SEAM_FINAL if final else 0)],
                                   [lead])
-                n = int(x.size)
-                xd = torch.from_numpy(x).to(device)[None] if n else torch.zeros(1, 1, dtype=torch.float32, device=device)
-                y, cnt = sj.new_outputs(1, n)
-                sj.chunk(xd, n, y, cnt, seg_end=end, last=end if final else None)
-                out.append(y[0, :int(cnt.cpu()[0])].cpu().numpy())
+                out.append(_whole_row(sj, x, lambda xd, n, y, cnt: sj.chunk(xd, n, y, cnt, seg_end=end, last=end if final else None)))
         finally:
             if joiner is None:
                 sj.close()
@@ -1217,32 +1215,17 @@ def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: tor
 FLAC_OFF, FLAC_F32, FLAC_S16 = 0, 1, 2  # SMOLTTS_FLAC_*
 
 
-class FlacEncoder:
+class FlacEncoder(_Stage):
     """Per-slot FLAC framing of streamed samples on the GPU (include/smoltts_hip.h, "FLAC"; the numpy model is
     ``flac.StreamEncoder``): one launch per call for every slot, each reading fp32 PCM or the resampler's int16 at its own rate.
     Slots start off; ``reset_slots`` starts a new stream in a slot.  The stream header (``flac.stream_header``) is the caller's."""
 
-    def __init__(self, device: torch.device, max_batch: int):
-        self.lib = load_library()
-        self.device, self.B = device, max_batch
-        need = self.lib.smoltts_flac_bytes(max_batch)
-        if need == 0:
-            raise SmolttsError("smoltts_flac_bytes returned 0 (bad sizes)")
-        self.slab = _alloc_slab(need, device, settle=True)
-        h = C.c_void_p()
-        check(self.lib.smoltts_flac_create(dptr(self.slab), need, max_batch, C.byref(h)), "smoltts_flac_create")
-        self.handle = h
-        self.source = [FLAC_OFF] * max_batch
-        self.rate = [0] * max_batch
+    C_NAME = "flac"
 
     def reset_slots(self, slots: Sequence[int], rates: Sequence[int], sources: Sequence[int]) -> None:
         """Start new streams in ``slots`` at their rate and source (``FLAC_F32`` / ``FLAC_S16``; ``FLAC_OFF``: off)."""
-        n = len(slots)
-        arr = lambda v: (C.c_int32 * n)(*[int(x) for x in v])  # noqa: E731
-        check(self.lib.smoltts_flac_reset_slots(self.handle, arr(slots), arr(rates), arr(sources), n, current_stream_ptr()),
-              "smoltts_flac_reset_slots")
-        for b, r, src in zip(slots, rates, sources):
-            self.rate[b], self.source[b] = int(r), int(src)
+        check(self.lib.smoltts_flac_reset_slots(self.handle, self._ints(slots), self._ints(rates), self._ints(sources), len(slots),
+                                                current_stream_ptr()), "smoltts_flac_reset_slots")
 
     def new_outputs(self, batch: int, n_max: int):
         """Device buffers of one call in which a slot reads at most ``n_max`` samples: (bytes uint8 [batch, out_bytes],
@@ -1258,14 +1241,9 @@ class FlacEncoder:
         [batch, >= n_in]; ``valid``: device int32 [batch], the real ones), S16 slots the resampler's ``s16`` bytes (uint8
         [batch, row]) and ``s16_counts`` (int32 [batch, 2]: finals, tail); ``last`` (device int32 [batch]) nonzero where the
         stream ends with this call.  ``sizes[b, j]``: {offset, bytes} of slot b's frame j in ``out[b]``."""
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[0] >= batch
-        assert sizes.dtype == torch.int32 and sizes.is_contiguous() and sizes.shape[0] >= batch
-        if pcm is not None:
-            assert pcm.dtype == torch.float32 and pcm.stride(1) == 1 and 0 <= n_in <= pcm.shape[1] and pcm.shape[0] >= batch
+        self._check(batch, pcm, n_in, out, torch.uint8, 0, sizes, 0, valid, last)
         if s16 is not None:
             assert s16.dtype == torch.uint8 and s16.is_contiguous() and s16_counts is not None and s16_counts.is_contiguous()
-        for t in (valid, last):
-            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= batch)
         check(self.lib.smoltts_flac_chunk(self.handle, dptr(pcm), pcm.stride(0) if pcm is not None else 0, int(n_in), dptr(valid),
                                           dptr(s16), s16.shape[1] if s16 is not None else 0, dptr(s16_counts), batch, dptr(last),
                                           dptr(out), out.shape[1], dptr(sizes), sizes.shape[1], current_stream_ptr()),
@@ -1281,18 +1259,6 @@ class FlacEncoder:
             frames.append(host_out[b, int(off):int(off) + int(n)].tobytes())
         return frames
 
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize()
-            self.lib.smoltts_flac_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def flac_encode(samples: np.ndarray, sample_rate: int, device: torch.device) -> bytes:
     """A whole utterance as one FLAC file, framed on ``device`` in one call with ``last`` set: float32 samples are quantised as
@@ -1304,35 +1270,78 @@ def flac_encode(samples: np.ndarray, sample_rate: int, device: torch.device) -> 
     is_f32 = x.dtype != np.int16
     x = np.ascontiguousarray(x, dtype=np.float32 if is_f32 else np.int16)
     s16 = flac.quantize(x) if is_f32 else x
-    n = int(x.size)
     with torch.cuda.device(device):
         fe = FlacEncoder(device, 1)
         try:
             fe.reset_slots([0], [sample_rate], [FLAC_F32 if is_f32 else FLAC_S16])
             last = torch.ones(1, dtype=torch.int32, device=device)
-            out, sizes = fe.new_outputs(1, n)
             if is_f32:
-                pcm = torch.from_numpy(x).to(device)[None] if n else torch.zeros(1, 1, dtype=torch.float32, device=device)
-                fe.chunk(1, out, sizes, pcm=pcm, n_in=n, last=last)
-            else:
-                raw = torch.from_numpy(x.view(np.uint8).copy()).to(device)[None] if n else torch.zeros(1, 2, dtype=torch.uint8, device=device)
-                counts = torch.tensor([[n, 0]], dtype=torch.int32, device=device)
-                fe.chunk(1, out, sizes, s16=raw, s16_counts=counts, last=last)
-            frames = FlacEncoder.slot_frames(out.cpu().numpy(), sizes.cpu().numpy(), 0)
+                frames = _whole_row(fe, x, lambda row, n, out, sizes: fe.chunk(1, out, sizes, pcm=row, n_in=n, last=last))
+            else:  # (the int16 row read as the resampler's bytes, all of it final)
+                frames = _whole_row(fe, x, lambda row, n, out, sizes: fe.chunk(
+                    1, out, sizes, s16=row.view(torch.uint8), s16_counts=torch.tensor([[n, 0]], dtype=torch.int32, device=device), last=last))
         finally:
             fe.close()
     return flac.file_from_frames(frames, s16, sample_rate)
 
 
 # ------------------------------------------------------------------------------- a stream's stages behind the codec
+STAGES = ("seam", "stretch", "resample", "flac")  # the stages of a pass, in launch order
+
+
+@dataclass(frozen=True)
+class SlotRoute:
+    """What a slot's stream goes through behind the codec (``StreamConverter``): its format (rate, SMOLTTS_RESAMPLE_*), its Q16
+    speed, FLAC framing, whether it is segmented (``start_segments``), its stream generation in the slot and whether its FLAC
+    stream header is still owed.  A restarted slot gets a new record: a pass keeps the records of its run."""
+    rate: int = 24000
+    enc: int = ENC_OFF
+    speed_q: int = 65536
+    flac: bool = False
+    segmented: bool = False
+    gen: int = 0
+    head_owed: bool = False
+
+    @cached_property
+    def stages(self) -> Tuple[str, ...]:
+        """The stages the slot goes through, in launch order."""
+        return tuple(s for s, on in zip(STAGES, (self.segmented, self.speed_q != 65536, self.enc != ENC_OFF, self.flac)) if on)
+
+
+class PassPlan(NamedTuple):
+    stages: List[str]                 # the stages to launch, in order
+    rows: Dict[str, List[int]]        # the live slots each of them serves
+    through: Dict[str, List[int]]     # float stage (seam, stretch) -> the live slots it does not serve that a later stage does
+    source: Dict[int, Optional[str]]  # live slot -> the last stage it goes through (None: its codec rows are its output)
+    host: List[str]                   # the stages whose outputs are copied to the host: the sources of the live slots
+    routes: Dict[int, SlotRoute]      # live slot -> its route when planned
+
+
+def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
+    """The plan of one converter pass over the live slots' routes (``{slot: SlotRoute}``, in slot order); no device involved."""
+    rows = {s: [] for s in STAGES}
+    through = {"seam": [], "stretch": []}
+    source = {}
+    for b, r in routes.items():
+        path = r.stages
+        source[b] = path[-1] if path else None
+        for s in path:
+            rows[s].append(b)
+        for s in through:
+            if path and s not in path and STAGES.index(path[-1]) > STAGES.index(s):
+                through[s].append(b)
+    stages = [s for s in STAGES if rows[s]]
+    return PassPlan(stages, {s: rows[s] for s in stages}, {s: through[s] for s in through if rows[s]}, source,
+                    [s for s in stages if s in source.values()], routes)
+
+
 class StreamConverter:
-    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch``: a slot with a speed is time-stretched
-    (``TimeStretcher``), then a slot with an output format is converted (``Resampler``, from the stretched samples where the
-    slot has a speed), then a slot with a FLAC container is framed (``FlacEncoder``, from the resampler's int16, or from the
-    float32 at 24 kHz).  Each stage is created the first time a slot needs it.  ``n_in``: codec samples per slot and call; the
-    resampler takes up to the stretcher's output of that many.  ``seam``: the converter joins long texts' segments
-    (``start_segments``): a segmented slot goes through the seam stage (``SeamJoiner``) first, and the other stages read its
-    output, their state carried from segment to segment."""
+    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``STAGES``): a
+    segmented slot (``start_segments``) is joined by the seam stage (``SeamJoiner``), a slot with a speed is time-stretched
+    (``TimeStretcher``), a slot with an output format is converted (``Resampler``), and a slot with a FLAC container is framed
+    (``FlacEncoder``, from the resampler's int16, or from the float32 at 24 kHz); each stage reads the output of the one in
+    front, and the state of the stages behind the seam carries from segment to segment.  Each stage is created the first time
+    a slot needs it (``seam``: the seam stage at once).  ``n_in``: codec samples per slot and call."""
 
     def __init__(self, device: torch.device, max_batch: int, n_in: int, seam: bool = False):
         self.device, self.B, self.n_in = device, max_batch, n_in
@@ -1340,8 +1349,8 @@ class StreamConverter:
         self.ts: Optional[TimeStretcher] = None
         self.fl: Optional[FlacEncoder] = None
         self.sj: Optional[SeamJoiner] = SeamJoiner(device, max_batch) if seam else None
-        self.gen = [0] * max_batch           # streams started in each slot
-        self.head_owed = [-1] * max_batch    # the stream (gen) of the slot whose FLAC header has not been handed out yet
+        self.routes = [SlotRoute()] * max_batch
+        self._plan: Optional[PassPlan] = None  # the last pass's plan
 
     def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]],
                     containers: Optional[Sequence[Optional[str]]] = None) -> None:
@@ -1351,27 +1360,28 @@ class StreamConverter:
         if not slots:
             return
         formats = [f or "pcm_24000" for f in formats]
-        speed_q = [q or 65536 for q in speed_q]
-        containers = [check_container(c, f) for c, f in zip(containers or [None] * len(slots), formats)]
-        if self.rs is None and any(parse_stream_format(f)[1] != ENC_OFF for f in formats):
+        routes = []
+        for b, f, q, c in zip(slots, formats, speed_q, containers or [None] * len(slots)):
+            rate, enc = parse_stream_format(f)
+            flac = check_container(c, f) is not None
+            routes.append(SlotRoute(rate, enc, q or 65536, flac, segmented=False, gen=self.routes[b].gen + 1, head_owed=flac))
+        if self.rs is None and any(r.enc != ENC_OFF for r in routes):
             self.rs = Resampler(self.device, self.B, out_bound(self.n_in))
-        if self.ts is None and any(q != 65536 for q in speed_q):
+        if self.ts is None and any(r.speed_q != 65536 for r in routes):
             self.ts = TimeStretcher(self.device, self.B)
-        if self.fl is None and any(containers):
+        if self.fl is None and any(r.flac for r in routes):
             self.fl = FlacEncoder(self.device, self.B)
         if self.rs is not None:
             self.rs.reset_slots(slots, formats)
         if self.ts is not None:
-            self.ts.reset_slots(slots, speed_q)
+            self.ts.reset_slots(slots, [r.speed_q for r in routes])
         if self.fl is not None:
-            parsed = [parse_stream_format(f) for f in formats]
-            self.fl.reset_slots(slots, [p[0] for p in parsed],
-                                [FLAC_OFF if c is None else (FLAC_F32 if p[1] == ENC_OFF else FLAC_S16) for c, p in zip(containers, parsed)])
+            self.fl.reset_slots(slots, [r.rate for r in routes],
+                                [FLAC_OFF if not r.flac else (FLAC_F32 if r.enc == ENC_OFF else FLAC_S16) for r in routes])
         if self.sj is not None:
             self.sj.start_segments(slots, [0] * len(slots), [SEAM_OFF] * len(slots))
-        for b, c in zip(slots, containers):
-            self.gen[b] += 1
-            self.head_owed[b] = self.gen[b] if c else -1
+        for b, r in zip(slots, routes):
+            self.routes[b] = r
 
     def start_segments(self, slots: Sequence[int], pauses: Sequence[int], flags: Sequence[int],
                        leads: Optional[Sequence[int]] = None) -> None:
@@ -1380,70 +1390,66 @@ class StreamConverter:
         if self.sj is None:
             self.sj = SeamJoiner(self.device, self.B)
         self.sj.start_segments(slots, pauses, flags, leads)
+        for b, f in zip(slots, flags):
+            self.routes[b] = replace(self.routes[b], segmented=not int(f) & SEAM_OFF)
+
+    def converts(self, b: int) -> bool:
+        """Whether slot ``b``'s stream goes through a stage: its chunks are ``StreamPass.chunk``'s, not the codec's float32."""
+        return bool(self.routes[b].stages)
+
+    def plan(self, slots: Sequence[int]) -> PassPlan:
+        """The plan of a pass over the live ``slots``: the last one again while they and their routes stay the same."""
+        p, slots = self._plan, tuple(slots)
+        if p is None or tuple(p.routes) != slots or any(self.routes[b] is not r for b, r in p.routes.items()):
+            p = self._plan = plan_pass({b: self.routes[b] for b in slots})
+        return p
+
+    def ends(self, slots: Sequence[int]):
+        """The end markers a pass over ``slots`` needs: (``last``: some slot has a speed, FLAC or segments; ``seg_end``: some
+        slot has segments)."""
+        stages = self.plan(slots).stages
+        return any(s in stages for s in ("seam", "stretch", "flac")), "seam" in stages
+
+    def _through(self, plan: PassPlan, stage: str, out: torch.Tensor, counts: torch.Tensor, pcm: torch.Tensor, n_in: int,
+                 valid: torch.Tensor) -> torch.Tensor:
+        """After a float stage: its rows of the slots it passes through (``plan.through``) take the ``pcm`` it read, so that the
+        stages behind serve all slots in one launch each; returns the valid counts of its rows."""
+        plain = plan.through[stage]
+        if not plain:
+            return counts
+        served = np.zeros(out.shape[0], np.int32)
+        served[plan.rows[stage]] = 1
+        served_d, plain_d = upload([served, np.asarray(plain, np.int64)], self.device)
+        out[plain_d, :n_in] = pcm[plain_d]
+        return torch.where(served_d != 0, counts, valid)
 
     def run(self, pcm: torch.Tensor, n_in: int, valid: torch.Tensor, last: Optional[torch.Tensor] = None,
             slots: Optional[Sequence[int]] = None, seg_end: Optional[torch.Tensor] = None) -> Optional["StreamPass"]:
         """Queue the stages for ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in]) on the current stream.
-        ``valid`` (device int32 [batch]): the samples of each row that are real; ``last`` (device int32 [batch], needed when a
-        slot has a speed or a FLAC container): nonzero where the row's stream ends with this call.  ``slots``: the live streams
+        ``valid`` (device int32 [batch]): the samples of each row that are real; ``last`` / ``seg_end`` (device int32 [batch],
+        needed as ``ends`` says): nonzero where the row's stream / segment ends with this call.  ``slots``: the live streams
         (default: every slot); the others consume what ``valid`` gives them and are never read.  None when no live slot
-        converts: no launch.  ``seg_end`` (device int32 [batch], needed when a slot is segmented): nonzero where the row's
-        segment ends with this call."""
-        slots = range(self.B) if slots is None else slots
-        fmt = [b for b in slots if self.rs is not None and self.rs.formats[b][1] != ENC_OFF]
-        spd = [b for b in slots if self.ts is not None and self.ts.speed_q[b] != 65536]
-        flc = [b for b in slots if self.fl is not None and self.fl.source[b] != FLAC_OFF]
-        smd = [b for b in slots if self.sj is not None and self.sj.on[b]]
-        if not (fmt or spd or flc or smd):
+        converts: no launch."""
+        plan = self.plan(range(self.B) if slots is None else slots)
+        if not plan.stages:
             return None
-        batch = pcm.shape[0]
-        joined = j_counts = None
-        if smd:  # the seam stage first; the rows of slots that are not segmented join its output as they are
-            joined, j_counts = self.sj.new_outputs(batch, n_in)
-            self.sj.chunk(pcm, n_in, joined, j_counts, valid=valid, seg_end=seg_end, last=last)
-            plain = [b for b in fmt + spd + flc if b not in smd]
-            if plain:
-                segd = np.zeros(batch, np.int32)
-                segd[smd] = 1
-                segd_d, plain_d = upload([segd, np.asarray(plain, np.int64)], self.device)
-                joined[plain_d, :n_in] = pcm[plain_d]
-                valid = torch.where(segd_d != 0, j_counts, valid)
-            else:
-                valid = j_counts
-            pcm, n_in = joined, joined.shape[1]
-            if self.rs is not None and self.rs.max_in < out_bound(n_in):  # (the stages behind read the seam's wider rows)
-                self.rs.max_in = out_bound(n_in)
-        src, rs_valid = pcm, valid
-        out = counts = stretched = st_counts = fout = fsizes = None
-        if spd:
-            stretched, st_counts = self.ts.new_outputs(batch, n_in)
-            self.ts.chunk(pcm, n_in, stretched, st_counts, valid=valid, last=last)
-            src, rs_valid = stretched, st_counts
-            plain = [b for b in fmt + flc if b not in spd]
-            if plain:  # one launch per stage for all: the codec's rows of slots without a speed join the stretched rows
-                sped = np.zeros(batch, np.int32)
-                sped[spd] = 1
-                sped_d, plain_d = upload([sped, np.asarray(plain, np.int64)], self.device)
-                stretched[plain_d, :n_in] = pcm[plain_d]
-                rs_valid = torch.where(sped_d != 0, st_counts, valid)
-            n_in = stretched.shape[1]
-        if fmt:
-            out, counts = self.rs.new_outputs(batch, n_in)
-            self.rs.chunk(src, n_in, out, counts, valid=rs_valid)
-        if flc:
-            s16_max = out.shape[1] // 2 if out is not None and any(self.fl.source[b] == FLAC_S16 for b in flc) else 0
-            fout, fsizes = self.fl.new_outputs(batch, max(n_in, s16_max))
-            self.fl.chunk(batch, fout, fsizes, pcm=src, n_in=n_in, valid=rs_valid, s16=out if s16_max else None,
-                          s16_counts=counts if s16_max else None, last=last)
-        if not any(b not in fmt and b not in flc for b in spd):  # every stretched slot is converted: its float32 is not read
-            stretched = st_counts = None
-        if fmt and all(b in flc for b in fmt):  # every converted slot is framed: its int16 is not read
-            out = counts = None
-        if not any(b not in fmt and b not in flc and b not in spd for b in smd):  # every joined slot goes on: its float32 is not read
-            joined = j_counts = None
-        heads = {b: (self.gen[b], self.fl.rate[b]) for b in flc}
-        return StreamPass(self.rs, [f[1] for f in self.rs.formats] if fmt else None, out, counts, stretched, st_counts, fout, fsizes,
-                          joined, j_counts, conv=self, heads=heads, stretched_slots=set(spd))
+        batch, outs = pcm.shape[0], {}
+        if "seam" in plan.stages:  # (each float stage's rows, counts and width are what the stages behind it read)
+            out, counts = outs["seam"] = self.sj.new_outputs(batch, n_in)
+            self.sj.chunk(pcm, n_in, out, counts, valid=valid, seg_end=seg_end, last=last)
+            valid, pcm, n_in = self._through(plan, "seam", out, counts, pcm, n_in, valid), out, out.shape[1]
+        if "stretch" in plan.stages:
+            out, counts = outs["stretch"] = self.ts.new_outputs(batch, n_in)
+            self.ts.chunk(pcm, n_in, out, counts, valid=valid, last=last)
+            valid, pcm, n_in = self._through(plan, "stretch", out, counts, pcm, n_in, valid), out, out.shape[1]
+        if "resample" in plan.stages:
+            out, counts = outs["resample"] = self.rs.new_outputs(batch, n_in)
+            self.rs.chunk(pcm, n_in, out, counts, valid=valid)
+        if "flac" in plan.stages:
+            s16, s16_counts = outs["resample"] if any(plan.routes[b].enc != ENC_OFF for b in plan.rows["flac"]) else (None, None)
+            fout, fsizes = outs["flac"] = self.fl.new_outputs(batch, max(n_in, s16.shape[1] // 2 if s16 is not None else 0))
+            self.fl.chunk(batch, fout, fsizes, pcm=pcm, n_in=n_in, valid=valid, s16=s16, s16_counts=s16_counts, last=last)
+        return StreamPass(self, {s: outs[s] for s in plan.host}, plan)
 
     def close(self):
         for stage in (self.rs, self.ts, self.fl, self.sj):
@@ -1454,59 +1460,37 @@ class StreamConverter:
 
 class StreamPass:
     """The outputs of one ``StreamConverter.run``: on the device, then (``to_host``) on the host, read slot by slot (``chunk``).
-    It keeps the slots' encodings of its run: a slot may have been restarted by the time its chunk is read."""
+    It reads each slot by the plan of its run: a slot may have been restarted by the time its chunk is read."""
 
-    def __init__(self, rs: Optional[Resampler], enc: Optional[List[int]], *device_outputs, conv: Optional[StreamConverter] = None,
-                 heads: Optional[Dict[int, tuple]] = None, stretched_slots=None):
-        self.rs, self.enc = rs, enc
-        # (bytes, counts, stretched fp32, stretched counts, flac bytes, flac sizes[, joined fp32, joined counts]); None where not read
-        self.dev = device_outputs
-        self.stretched_slots = stretched_slots
+    def __init__(self, conv: StreamConverter, dev: Dict[str, tuple], plan: PassPlan):
+        self.conv, self.rs = conv, conv.rs
+        self.dev = dev    # source stage -> its (output, counts) on the device
+        self.plan = plan
         self.host = None
-        self.conv, self.heads = conv, heads or {}  # FLAC slots of the run: (stream gen, rate) of each
+
+    def converts(self, b: int) -> bool:
+        """Whether slot ``b`` was converted in the run (its chunk is ``chunk(b, ...)``)."""
+        return self.plan.source.get(b) is not None
 
     def to_host(self, stream) -> None:
         """Queue the host copies on ``stream``; ``chunk`` reads them once ``stream`` has run them."""
         with torch.cuda.stream(stream):
-            self.host = tuple(t.to("cpu", non_blocking=True) if t is not None else None for t in self.dev)
+            self.host = {s: tuple(t.to("cpu", non_blocking=True) for t in ts) for s, ts in self.dev.items()}
 
     def chunk(self, b: int, last: bool) -> np.ndarray:
-        """Slot ``b``'s chunk: its FLAC frames as uint8 (behind the stream header on the stream's first chunk), its converted
-        samples (with the resampler's tail when ``last``), or the stretched float32 of a slot with a speed and no format."""
-        out, counts, stretched, st_counts, fout, fsizes, *rest = (t.numpy() if t is not None else None for t in self.host)
-        if b in self.heads:
+        """Slot ``b``'s chunk from its source stage: its FLAC frames as uint8 (behind the stream header on the stream's first
+        chunk), its converted samples (with the resampler's tail when ``last``), or the stretched / joined float32."""
+        route, source = self.plan.routes[b], self.plan.source[b]
+        out, counts = (t.numpy() for t in self.host[source])
+        if source == "flac":
             from .flac import stream_header
 
-            data = b"".join(FlacEncoder.slot_frames(fout, fsizes, b))
-            gen, rate = self.heads[b]
-            if self.conv.head_owed[b] == gen:
-                self.conv.head_owed[b] = -1
-                data = stream_header(rate) + data
+            data = b"".join(FlacEncoder.slot_frames(out, counts, b))
+            now = self.conv.routes[b]
+            if now.head_owed and now.gen == route.gen:
+                self.conv.routes[b] = replace(now, head_owed=False)
+                data = stream_header(route.rate) + data
             return np.frombuffer(data, dtype=np.uint8).copy()
-        if self.enc is not None and self.enc[b] != ENC_OFF:
-            return self.rs.slot_bytes(out, counts, b, tail=last, enc=self.enc[b])
-        if rest and rest[0] is not None and (self.stretched_slots is None or b not in self.stretched_slots):
-            return rest[0][b, : int(rest[1][b])].copy()  # a segmented slot with no other stage: the joined float32
-        return stretched[b, : int(st_counts[b])].copy()
-
-
-def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device) -> np.ndarray:
-    """A whole utterance (float32 at 24 kHz) stretched on ``device`` (the model's) in one call with ``last`` set: exactly
-    ``tsm.out_length(len(pcm), speed_q)`` samples (``SmolTTS.__call__``).  Waits for the result.  ``speed_q == 65536`` returns
-    ``pcm`` untouched."""
-    pcm = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
-    if speed_q == 65536:
-        return pcm
-    with torch.cuda.device(device):
-        ts = TimeStretcher(device, 1)
-        try:
-            ts.reset_slots([0], [speed_q])
-            n = int(pcm.size)
-            x = torch.from_numpy(pcm).to(device)[None] if n else torch.zeros(1, 1, dtype=torch.float32, device=device)
-            out, counts = ts.new_outputs(1, n)
-            last = torch.ones(1, dtype=torch.int32, device=device)
-            ts.chunk(x, n, out, counts, last=last)
-            m = int(counts.cpu()[0])
-            return out[0, :m].cpu().numpy()
-        finally:
-            ts.close()
+        if source == "resample":
+            return self.rs.slot_bytes(out, counts, b, tail=last, enc=route.enc)
+        return out[b, : int(counts[b])].copy()

@@ -24,7 +24,6 @@ import torch
 
 from .config import GenerationSettings, RequestSampling
 from .engine import LMEngine, LMSession, StreamConverter
-from .formats import ENC_OFF, parse_stream_format
 
 
 @dataclass
@@ -255,14 +254,14 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     pcm_host = torch.empty(1, 1920, dtype=torch.float32).pin_memory()
     state_host = torch.zeros(2, dtype=torch.int32).pin_memory()  # n_frames[0], done[0]
     own = conv is None
-    formatted = output_format is not None and parse_stream_format(output_format)[1] != ENC_OFF
-    ends_on_device = speed_q is not None or container is not None or not own  # a stage that must see the end of the stream
     if own:
-        conv = StreamConverter(dev, 1, 1920) if formatted or ends_on_device else None
+        conv = StreamConverter(dev, 1, 1920)  # (its stages are made by reset_slots, as the stream needs them)
     with torch.cuda.stream(codec_stream):
         msession.reset()
-        if conv is not None and own:
+        if own:
             conv.reset_slots([0], [output_format], [speed_q], [container])
+    converted = conv.converts(0)
+    ends_on_device, segmented = conv.ends([0])  # a stage must see the end of the stream / of the segment
     with torch.cuda.stream(lm_stream):
         s.prefill([prompt], stop_on_eos=stop_on_eos)  # frame 0
         ev = torch.cuda.Event()
@@ -288,12 +287,12 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
                     state_host.copy_(snap, non_blocking=True)
                     n_d, done_d = snap[0:1], snap[1:2]
                 msession.decode_chunk(s.codes[:, f:f + 1], 0, 1, pcm_dev, code_offset=1)  # (decode_chunk writes frame f0 at pcm[:, 1920 f0:])
-                if conv is not None:
+                if converted:
                     valid = (n_d > f).to(torch.int32) * 1920  # 0 once the slot has stopped: garbage is not consumed
                     # the stream ends with this frame (done at it, or the frame limit), or had ended before it unseen by the host
                     last = None if not ends_on_device else ((n_d <= f) | ((done_d != 0) & (n_d == f + 1)) | (f + 1 >= limit)).to(torch.int32)
                     seg_end = None
-                    if not own:  # a segment: it ends where an utterance would; the stream only with the final one
+                    if segmented:  # a segment: it ends where an utterance would; the stream only with the final one
                         seg_end, last = last, (last if final else None)
                     out = conv.run(pcm_dev, 1920, valid, last, seg_end=seg_end)
                     out.to_host(codec_stream)
@@ -323,5 +322,5 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     finally:
         lm_stream.synchronize()
         codec_stream.synchronize()
-        if conv is not None and own:
+        if own:
             conv.close()

@@ -384,9 +384,10 @@ class BatchScheduler:
         """The stream conversion of a codec pass (``engine.StreamConverter``, current stream, right behind the decode): slot b of
         a request in ``reqs`` consumes the samples of the frames the tick's frame counter ``n_frames_d`` (device) gives it; every
         other slot none.  A slot with a speed ends its stream (flushes) in the tick where the host will see it finish, by the
-        rule of ``_drain`` on the same snapshot (``n_frames_d``, ``done_d``).  Returns the ``engine.StreamPass``, or None when no
-        request in ``reqs`` has a format or a speed (then nothing is uploaded or launched)."""
-        if not any(r.output_format or r.speed_q or r.container or r.segs is not None for r in reqs):
+        rule of ``_drain`` on the same snapshot (``n_frames_d``, ``done_d``).  Returns the ``engine.StreamPass``, or None when the
+        converter converts no slot of ``reqs`` (then nothing is uploaded or launched)."""
+        conv, slots = self._stream_conv, [r.slot for r in reqs]
+        if not any(conv.converts(b) for b in slots):
             return None
         from ..engine import upload
 
@@ -400,7 +401,8 @@ class BatchScheduler:
         n_d = n_frames_d.to(torch.int32)
         valid = ((torch.minimum(n_d, cap_d) - f0_d).clamp_(0, self.tick) * 1920).to(torch.int32)
         last = seg_end = None
-        if any(r.segs is not None for r in reqs):
+        needs_last, segmented = conv.ends(slots)
+        if segmented:
             # a segmented stream: its segment ends where an utterance would; the stream ends with its final segment only
             fin = np.zeros(self.B, np.int32)
             for r in reqs:
@@ -408,9 +410,9 @@ class BatchScheduler:
             fin_d, = upload([fin], self.session.engine.device)
             ends = stream_ends(n_d, done_d, cap_d) & (cap_d > 0)
             seg_end, last = ends.to(torch.int32), (ends & (fin_d != 0)).to(torch.int32)
-        elif any(r.speed_q or r.container for r in reqs):
+        elif needs_last:
             last = (stream_ends(n_d, done_d, cap_d) & (cap_d > 0)).to(torch.int32)
-        return self._stream_conv.run(pcm, self.tick * 1920, valid, last, slots=[r.slot for r in reqs], seg_end=seg_end)
+        return conv.run(pcm, self.tick * 1920, valid, last, slots=slots, seg_end=seg_end)
 
     def _admit(self) -> None:
         if self._side is not None and self._side["state"] == "running":
@@ -924,7 +926,7 @@ class BatchScheduler:
                     if fin:
                         self._part_done(r)
                     continue
-                if r.stream and (r.output_format or r.speed_q or r.container or r.segs is not None) and d.conv is not None:
+                if r.stream and d.conv is not None and d.conv.converts(b):
                     chunk = d.conv.chunk(b, fin)  # (the tail goes out with the last chunk)
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
