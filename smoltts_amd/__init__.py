@@ -164,21 +164,21 @@ class SmolTTS:
         ``segment`` (True, a dict or a ``longform.SegmentOptions``): a long text is spoken as chained segments (``longform``),
         one after another, each decoded as its own utterance and joined on the GPU (``seam``) before the stretch; a text that is
         one segment without break tags takes the plain path.  ``last_segments`` then lists each segment's text, seed and codes."""
-        from .tsm import parse_speed
+        from .request import parse_request
 
-        sq = parse_speed(speed)  # a bad speed is refused before any work
-        plan = self._segment_plan(input, segment)
-        if plan is not None:
-            pcm = self._call_segmented(plan, voice if voice is not None else "heart", speaker, generation_settings, sampling)
+        req = parse_request(input, speed=speed, segment=segment)  # a bad request is refused before any work
+        voice = voice if voice is not None else "heart"
+        if req.plan is not None:
+            pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling)
         else:
-            codes = self.generate_codes([input], [voice if voice is not None else "heart"], generation_settings,
-                                        speakers=None if speaker is None else [speaker], sampling=sampling)[0]
+            codes = self.generate_codes([input], [voice], generation_settings, speakers=None if speaker is None else [speaker],
+                                        sampling=sampling)[0]
             pcm = self.decode_codes(codes)
-        if sq is None:
+        if req.speed_q is None:
             return pcm
         from .engine import stretch_pcm
 
-        return stretch_pcm(pcm, sq, self.lm.device)
+        return stretch_pcm(pcm, req.speed_q, self.lm.device)
 
     # -- voice-clone prompts (``create_speaker``, __init__.py:97-118)
     def encode_audio(self, audio) -> "np.ndarray":
@@ -235,154 +235,110 @@ class SmolTTS:
         the seam stage in front of the stream's other stages, which run on across the segments: one stream (one FLAC header)."""
         import numpy as np
 
-        from .formats import check_container, parse_stream_format
-        from .tsm import parse_speed
+        from .engine import MimiSession
+        from .generate import resolve_sampling, stream_pcm
+        from .request import parse_request
 
-        if output_format is not None:
-            parse_stream_format(output_format)  # an unknown format is refused before any work
-        check_container(container, output_format)
-        sq = parse_speed(speed)
-        plan = self._segment_plan(input, segment)
-        if plan is not None:
-            yield from self._stream_segmented(plan, voice if voice is not None else "0", generation_settings, overlap,
-                                              reference_upsample, output_format, sampling, sq, container)
+        req = parse_request(input, stream=True, output_format=output_format, speed=speed, container=container, segment=segment)
+        voice = voice if voice is not None else "0"
+        if req.plan is not None:
+            yield from self._stream_segmented(req, voice, generation_settings, overlap, reference_upsample, sampling)
             return
-
-        from .engine import LMSession, MimiSession
-        from .generate import _apply_sampling, _apply_slot_sampling, resolve_sampling, stream_pcm
-
-        prompt = np.asarray(self._get_prompt(input, voice if voice is not None else "0"))
+        prompt = np.asarray(self._get_prompt(input, voice))
         if prompt.ndim == 3:
             prompt = prompt[0]
         settings = self._settings(generation_settings)
-        max_new = settings.max_new_tokens if settings.max_new_tokens is not None else self.config.max_seq_len
-        T = int(prompt.shape[1])
-        sess = LMSession(self.lm, 1, max_seq=min(self.config.max_seq_len, T + max_new + 2), max_rows=T, max_frames=max_new + 1)
-        _apply_sampling(sess, settings)
-        resolved = resolve_sampling(sampling, settings, 1)
-        self.last_sampling = resolved
-        if resolved is not None:
-            _apply_slot_sampling(sess, [0], resolved)
+        self.last_sampling = resolve_sampling(sampling, settings, 1)
+        sess = self._stream_session(prompt, settings, self.last_sampling)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
-            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=output_format, speed_q=sq,
-                                  container=container)
+            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=req.output_format,
+                                  speed_q=req.speed_q, container=req.container)
         finally:
             msess.close()
             sess.close()
 
+    def _max_new(self, settings) -> int:
+        return settings.max_new_tokens if settings.max_new_tokens is not None else self.config.max_seq_len
+
+    def _stream_session(self, prompt, settings, sampling):
+        """The one-slot ``LMSession`` a stream of ``prompt`` runs in, sampling with ``settings``, or slot 0 with the resolved
+        ``sampling`` list when there is one."""
+        from .engine import LMSession
+        from .generate import _apply_sampling, _apply_slot_sampling
+
+        max_new, T = self._max_new(settings), int(prompt.shape[1])
+        sess = LMSession(self.lm, 1, max_seq=min(self.config.max_seq_len, T + max_new + 2), max_rows=T, max_frames=max_new + 1)
+        _apply_sampling(sess, settings)
+        if sampling is not None:
+            _apply_slot_sampling(sess, [0], sampling)
+        return sess
+
     # -- long texts as chained segments (``longform``, ``seam``; DESIGN.md section 13)
-    def _segment_plan(self, input: str, segment):
-        """(options, segments) of a segmented request, or None where the plain path runs (``segment`` off, or one segment
-        without break tags)."""
-        from .longform import needs_segments, segment_options, split_text
-
-        opts = segment_options(segment)
-        if opts is None:
-            return None
-        segs = split_text(input, opts.max_bytes)
-        if not segs:
-            raise ValueError("the text has nothing to speak")
-        return (opts, segs) if needs_segments(segs) else None
-
-    def _segment_setup(self, plan, voice: str, speaker, generation_settings, sampling):
-        """-> (settings, prefix, per-segment (settings, sampling) factory, pauses, lead, trail)."""
+    def _segments(self, plan, voice: str, speaker, generation_settings, sampling):
+        """Segment after segment of ``plan``: (k, its ``last_segments`` entry with its prompt, its settings, its sampling list or
+        None).  The caller stores the segment's ``"codes"`` in the entry before it asks for the next one, which they condition."""
         import dataclasses
         import os
 
         from .generate import resolve_sampling
-        from .longform import segment_seed, voice_prefix
-        from .seam import pause_samples
+        from .longform import voice_prefix
 
-        opts, segs = plan
         settings = self._settings(generation_settings)
-        if speaker is None and voice in self.voices:
-            speaker = self.voices[voice]
-        prefix = voice_prefix(self.prompt_encoder, voice, speaker)
+        prefix = voice_prefix(self.prompt_encoder, voice, speaker if speaker is not None else self.voices.get(voice))
         resolved = resolve_sampling(sampling, settings, 1)
         self.last_sampling = resolved
-        base = settings.seed if settings.seed is not None else int.from_bytes(os.urandom(8), "little")
-
-        def per_segment(k: int):
-            if resolved is not None:
-                return settings, [dataclasses.replace(resolved[0], seed=segment_seed(resolved[0].seed, k))]
-            return dataclasses.replace(settings, seed=segment_seed(base, k)), None
-
-        pauses = [pause_samples(s.pause_after_s if s.pause_after_s is not None else opts.pause_s) for s in segs[:-1]]
-        return settings, prefix, per_segment, pauses, pause_samples(segs[0].pause_before_s), pause_samples(segs[-1].pause_after_s)
-
-    def _chain(self, plan, prefix, k: int, prev, settings):
-        from .longform import chain_prompt
-
-        opts, segs = plan
-        max_new = settings.max_new_tokens if settings.max_new_tokens is not None else self.config.max_seq_len
-        if opts.context == "previous" and prev is not None:
-            return chain_prompt(self.prompt_encoder, prefix, segs[k].text, prev[0], prev[1], max_new, self.config.max_seq_len)
-        return chain_prompt(self.prompt_encoder, prefix, segs[k].text, max_new_tokens=max_new, max_seq=self.config.max_seq_len)
+        # segment k samples with segment_seed(seed, k): the request's seed, or the settings' (drawn here when they have none)
+        if resolved is not None:
+            base = resolved[0]
+        else:
+            base = settings if settings.seed is not None else dataclasses.replace(settings, seed=int.from_bytes(os.urandom(8), "little"))
+        self.last_segments = info = []
+        for k, seg in enumerate(plan.segs):
+            prev = (info[-1]["text"], info[-1]["codes"]) if info else None
+            samp = plan.sampling(k, base)
+            info.append({"text": seg.text, "prompt": plan.prompt(k, self.prompt_encoder, prefix, prev, self._max_new(settings),
+                                                                 self.config.max_seq_len),
+                         "codes": None, "seed": samp.seed})
+            yield (k, info[-1], settings, [samp]) if resolved is not None else (k, info[-1], samp, None)
+        self.last_sampling = resolved  # (generate_prompt_codes sets it per segment)
 
     def _call_segmented(self, plan, voice, speaker, generation_settings, sampling):
-        from .engine import seam_join
+        from .engine import SeamJoiner, seam_join
 
-        opts, segs = plan
-        settings, prefix, per_segment, pauses, lead, trail = self._segment_setup(plan, voice, speaker, generation_settings, sampling)
-        pcms, prev, info = [], None, []
-        resolved = self.last_sampling
-        for k, seg in enumerate(segs):
-            st_k, samp_k = per_segment(k)
-            prompt = self._chain(plan, prefix, k, prev, settings)
-            codes = self.generate_prompt_codes([prompt], st_k, samp_k)[0]
-            pcms.append(self.decode_codes(codes))
-            info.append({"text": seg.text, "prompt": prompt, "codes": codes,
-                         "seed": samp_k[0].seed if samp_k is not None else st_k.seed})
-            prev = (seg.text, codes)
-        self.last_sampling = resolved
-        self.last_segments = info
+        pcms = []
+        for _, seg, st_k, samp_k in self._segments(plan, voice, speaker, generation_settings, sampling):
+            seg["codes"] = self.generate_prompt_codes([seg["prompt"]], st_k, samp_k)[0]
+            pcms.append(self.decode_codes(seg["codes"]))
         if self._seam is None:
-            from .engine import SeamJoiner
-
             self._seam = SeamJoiner(self.lm.device, 1)
-        return seam_join(pcms, pauses, self.lm.device, lead=lead, trail=trail, joiner=self._seam)
+        return seam_join(pcms, plan.pauses, self.lm.device, lead=plan.lead, trail=plan.trail, joiner=self._seam)
 
-    def _stream_segmented(self, plan, voice, generation_settings, overlap, reference_upsample, output_format, sampling, sq,
-                          container):
+    def _stream_segmented(self, req, voice, generation_settings, overlap, reference_upsample, sampling):
         import numpy as np
         import torch
 
-        from .engine import SEAM_FINAL, SEAM_FIRST, LMSession, MimiSession, StreamConverter
-        from .generate import _apply_sampling, _apply_slot_sampling, _frame_to_token, stream_pcm
+        from .engine import MimiSession, StreamConverter
+        from .generate import semantic_columns, stream_pcm
 
-        opts, segs = plan
-        settings, prefix, per_segment, pauses, lead, trail = self._segment_setup(plan, voice, None, generation_settings, sampling)
-        max_new = settings.max_new_tokens if settings.max_new_tokens is not None else self.config.max_seq_len
+        plan = req.plan
         dev = self.lm.device
         conv = StreamConverter(dev, 1, 1920, seam=True)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
-        info, prev = [], None
-        self.last_segments = info
         try:
-            conv.reset_slots([0], [output_format], [sq], [container])
-            for k, seg in enumerate(segs):
-                final = k == len(segs) - 1
-                prompt = self._chain(plan, prefix, k, prev, settings)
-                st_k, samp_k = per_segment(k)
-                T = int(prompt.shape[1])
-                sess = LMSession(self.lm, 1, max_seq=min(self.config.max_seq_len, T + max_new + 2), max_rows=T, max_frames=max_new + 1)
+            conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container])
+            for k, seg, st_k, samp_k in self._segments(plan, voice, None, generation_settings, sampling):
+                final = k == len(plan.segs) - 1
+                sess = self._stream_session(seg["prompt"], st_k, samp_k)
                 try:
-                    _apply_sampling(sess, st_k)
-                    if samp_k is not None:
-                        _apply_slot_sampling(sess, [0], samp_k)
-                    conv.start_segments([0], [trail if final else pauses[k]],
-                                        [(SEAM_FIRST if k == 0 else 0) | (SEAM_FINAL if final else 0)], [lead])
-                    yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, conv=conv, final=final)
+                    pause, flags, lead = plan.seam_args(k)
+                    conv.start_segments([0], [pause], [flags], [lead])
+                    yield from stream_pcm(sess, msess, seg["prompt"], stop_on_eos=True, overlap=overlap, conv=conv, final=final)
                     codes_all, n_frames, _, _ = sess.fetch()
-                    cols = [t.audio_codes[0, :, 0] for t in (_frame_to_token(self.lm, codes_all[0, f]) for f in range(int(n_frames[0])))
-                            if t.audio_codes is not None]
-                    codes = (np.stack(cols, axis=1).astype(np.uint32) if cols else np.zeros((self.config.num_codebooks, 0), np.uint32))
+                    seg["codes"] = semantic_columns(codes_all[0, :int(n_frames[0])], self.token_config,
+                                                    self.config.num_codebooks).T.astype(np.uint32)
                 finally:
                     sess.close()
-                info.append({"text": seg.text, "prompt": prompt, "codes": codes,
-                             "seed": samp_k[0].seed if samp_k is not None else st_k.seed})
-                prev = (seg.text, codes)
         finally:
             torch.cuda.synchronize(dev)
             msess.close()

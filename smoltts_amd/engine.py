@@ -19,6 +19,7 @@ import torch
 
 from .config import NumericsMode, RQTransformerModelArgs, TokenConfig
 from .formats import ENC_OFF, check_container, parse_stream_format
+from .seam import segment_flags
 from .tsm import out_bound
 from . import packing
 
@@ -1202,8 +1203,7 @@ def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: tor
             end = torch.ones(1, dtype=torch.int32, device=device)
             for k, x in enumerate(segs):
                 final = k == len(segs) - 1
-                sj.start_segments([0], [trail if final else pauses[k]], [(SEAM_FIRST if k == 0 else 0) | (SEAM_FINAL if final else 0)],
-                                  [lead])
+                sj.start_segments([0], [trail if final else pauses[k]], [segment_flags(k, len(segs))], [lead])
                 out.append(_whole_row(sj, x, lambda xd, n, y, cnt: sj.chunk(xd, n, y, cnt, seg_end=end, last=end if final else None)))
         finally:
             if joiner is None:

@@ -71,6 +71,14 @@ def _frame_to_token(engine: LMEngine, col: np.ndarray) -> VQToken:
     return VQToken(semantic_code=slow, audio_codes=audio, vq_tensor=vq)
 
 
+def semantic_columns(rows: np.ndarray, token_config, n_codebooks: int) -> np.ndarray:
+    """Output-ring rows (F, 1 + n_fast) -> the audio codes (F', n_codebooks) int32 of the frames whose slow id is a semantic
+    token, the frames ``generate_blocking`` keeps (lm/generate.py:196-207): the last ``n_codebooks`` ids of each."""
+    slow = rows[:, 0]
+    keep = (slow >= token_config.semantic_start_id) & (slow <= token_config.semantic_end_id)
+    return rows[keep][:, -n_codebooks:].astype(np.int32)
+
+
 class BatchGenerator:
     """Frames for B utterances; ``next()`` returns a list with one VQToken (or None once the
     utterance has stopped) per slot.  ``frames_per_sync`` > 1 lets the GPU run ahead."""

@@ -24,15 +24,17 @@ The segmentation rule, which is the definition:
    replaced by a space (a word longer than ``max_bytes``, cut at a character boundary, comes back with a space in it).
 
 A seam without a tag has ``pause_after_s`` None: the caller's default pause (0.25 s) applies.  A text without a tag that fits in
-one segment comes back as one segment, and the façade then takes the unsegmented path.
+one segment comes back as one segment, and the front ends then take the unsegmented path (``SegmentPlan.create`` is None).
 """
 from __future__ import annotations
 
 import re
-from dataclasses import dataclass
-from typing import List, NamedTuple, Optional
+from dataclasses import dataclass, replace
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
+
+from .seam import pause_samples, segment_flags
 
 MAX_TAG_S = 3.0       # one break tag (ElevenLabs' limit)
 MAX_PAUSE_S = 10.0    # the pauses of consecutive tags at one seam, summed
@@ -214,3 +216,49 @@ def voice_prefix(encoder, voice: str, sysprompt: Optional[np.ndarray] = None) ->
     from .prompt import VOICE_MAP
 
     return encoder.encode_text_turn("system", f"<|speaker:{VOICE_MAP.get(voice, 0)}|>")
+
+
+@dataclass(frozen=True)
+class SegmentPlan:
+    """A segmented request's segments and what follows from them, for every front end: segment k's prompt, seam arguments and
+    sampling, and the blocking join's pauses, lead and trail (all in samples at 24 kHz)."""
+    opts: SegmentOptions
+    segs: Tuple[Segment, ...]
+
+    @classmethod
+    def create(cls, text: str, opts: SegmentOptions) -> Optional["SegmentPlan"]:
+        """The plan of ``text``, or None where the plain path runs (one segment without break tags)."""
+        segs = split_text(text, opts.max_bytes)
+        if not segs:
+            raise ValueError("the text has nothing to speak")
+        return cls(opts, tuple(segs)) if needs_segments(segs) else None
+
+    @property
+    def pauses(self) -> List[int]:
+        """The seam after every segment but the last: its break tags, or the default pause."""
+        return [pause_samples(s.pause_after_s if s.pause_after_s is not None else self.opts.pause_s) for s in self.segs[:-1]]
+
+    @property
+    def lead(self) -> int:
+        return pause_samples(self.segs[0].pause_before_s)
+
+    @property
+    def trail(self) -> int:
+        return pause_samples(self.segs[-1].pause_after_s)
+
+    def seam_args(self, k: int) -> Tuple[int, int, int]:
+        """(pause, flags, lead) that open segment k in the seam stage."""
+        n = len(self.segs)
+        return (self.trail if k == n - 1 else self.pauses[k]), segment_flags(k, n), self.lead
+
+    def prompt(self, k: int, encoder, prefix: np.ndarray, prev: Optional[Tuple[str, np.ndarray]], max_new_tokens: int,
+               max_seq: int) -> np.ndarray:
+        """Segment k's prompt: ``prev`` (segment k - 1's text and codes, None for segment 0) is its context unless the options
+        say ``context="none"``."""
+        ctx = prev if prev is not None and self.opts.context == "previous" else (None, None)
+        return chain_prompt(encoder, prefix, self.segs[k].text, *ctx, max_new_tokens=max_new_tokens, max_seq=max_seq)
+
+    @staticmethod
+    def sampling(k: int, base):
+        """Segment k's copy of ``base`` (a resolved ``RequestSampling``, or ``GenerationSettings``) with ``segment_seed``."""
+        return replace(base, seed=segment_seed(base.seed, k))

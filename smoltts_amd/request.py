@@ -1,0 +1,39 @@
+"""One parse of a speech request's options, shared by every front end (``SmolTTS``, ``BatchScheduler``, ``GpuPool``, the HTTP
+core): the checks and their ``ValueError`` messages live here once, and the front ends only route the normalised values."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+from .formats import ENC_OFF, check_container, parse_stream_format
+from .longform import SegmentOptions, SegmentPlan, segment_options
+from .tsm import parse_speed
+
+
+@dataclass(frozen=True)
+class SpeechOptions:
+    output_format: Optional[str]     # pcm_<rate> / ulaw_8000 converted on the GPU; None: the codec's float32 at 24 kHz
+    speed: Optional[float]           # the speed asked for, None at speed 1
+    speed_q: Optional[int]           # the same in Q16 (tsm.py)
+    container: Optional[str]         # "flac", or None
+    segment: Optional[SegmentOptions]
+    plan: Optional[SegmentPlan]      # None: the plain path (no segment options, or a text that is one plain segment)
+
+
+def parse_request(text: str = "", stream: bool = False, output_format: Optional[str] = None, speed: Optional[float] = None,
+                  container: Optional[str] = None, segment=None) -> SpeechOptions:
+    """A request's options checked and normalised; ``ValueError`` for anything a front end refuses.  ``output_format`` and
+    ``container`` apply to streaming requests only."""
+    speed_q = parse_speed(speed)
+    if output_format is not None:
+        if not stream:
+            raise ValueError("output_format applies to streaming requests")
+        if parse_stream_format(output_format)[1] == ENC_OFF:
+            output_format = None
+    if container is not None:
+        if not stream:
+            raise ValueError("container applies to streaming requests")
+        check_container(container, output_format)
+    opts = segment_options(segment)
+    plan = SegmentPlan.create(text, opts) if opts is not None else None
+    return SpeechOptions(output_format, None if speed_q is None else float(speed), speed_q, container, opts, plan)

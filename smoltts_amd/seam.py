@@ -34,6 +34,11 @@ HIST = 24_576  # input samples a slot carries (a held run and a partial block: <
 FIRST, FINAL = 1, 2  # segment flags (SMOLTTS_SEAM_FIRST / _FINAL)
 
 
+def segment_flags(k: int, n: int) -> int:
+    """The flags of segment k of a stream of n segments."""
+    return (FIRST if k == 0 else 0) | (FINAL if k == n - 1 else 0)
+
+
 def pause_samples(seconds: Optional[float]) -> int:
     """A pause in seconds -> samples at 24 kHz (rounded to nearest)."""
     return 0 if seconds is None else int(round(float(seconds) * RATE))
@@ -117,7 +122,7 @@ def join(segments: Sequence[np.ndarray], pauses: Sequence[int], lead: int = 0, t
     out: List[np.ndarray] = []
     for k, s in enumerate(segs):
         final = k == len(segs) - 1
-        st.start(trail if final else int(pauses[k]), (FIRST if k == 0 else 0) | (FINAL if final else 0), lead)
+        st.start(trail if final else int(pauses[k]), segment_flags(k, len(segs)), lead)
         sizes = list(chunks[k]) if chunks is not None else [s.size]
         assert sum(sizes) == s.size
         i = 0

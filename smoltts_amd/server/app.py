@@ -13,7 +13,7 @@ import argparse
 import json
 import math
 import threading
-from typing import Dict, List, Literal, Optional, Union
+from typing import Dict, List, Literal, Optional, Tuple, Union
 
 import numpy as np
 from fastapi import APIRouter, FastAPI, HTTPException, Query, Request, Response
@@ -47,20 +47,24 @@ class TTSCore:
     def long_text(self) -> str:
         return self._setting("long_text", "refuse")
 
-    def _segment_kw(self, text: str) -> dict:
-        """``{"segment": options}`` in ``long_text="segment"`` mode (nothing otherwise, so that the model sees the calls it saw
-        before); a text over ``max_input_chars`` or with a bad break tag is the client's fault (ValueError).  ``"_n"``: the segments
-        the request speaks (0: an unsegmented one), counted once it has completed; the caller takes it out."""
-        if self.long_text != "segment":
-            return {}
-        from ..longform import needs_segments, split_text
+    def _request_kw(self, text: str, speed: Optional[float]) -> Tuple[dict, int]:
+        """(kwargs, segments): ``{"speed": speed}`` for a speed other than 1 and ``{"segment": options}`` in ``long_text="segment"``
+        mode, nothing otherwise, so that the model sees the calls it saw before; a bad speed, a text over ``max_input_chars`` or
+        with a bad break tag is the client's fault (ValueError).  The segments the request speaks (0: an unsegmented one) are
+        counted once it has completed."""
+        from ..request import parse_request
 
-        limit = int(self._setting("max_input_chars", 5000))
-        if len(text) > limit:
-            raise ValueError(f"input has {len(text)} characters; max_input_chars is {limit}")
-        opts = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
-        segs = split_text(text, opts["max_bytes"])
-        return {"segment": opts, "_n": len(segs) if needs_segments(segs) else 0}
+        seg = None
+        if self.long_text == "segment":
+            limit = int(self._setting("max_input_chars", 5000))
+            if len(text) > limit:
+                raise ValueError(f"input has {len(text)} characters; max_input_chars is {limit}")
+            seg = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
+        p = parse_request(text, speed=speed, segment=seg)
+        kw = {} if p.speed is None else {"speed": p.speed}
+        if seg is not None:
+            kw["segment"] = seg
+        return kw, len(p.plan.segs) if p.plan is not None else 0
 
     def _count_segments(self, n: int) -> None:
         if n:
@@ -152,10 +156,8 @@ class TTSCore:
                        speed: Optional[float] = None):
         """-> (bytes, media type, the seed the request sampled with or None).  ``speed``: passed on only when it is not 1."""
         used = None
-        sp = _speed_kw(speed)
         try:
-            sp.update(self._segment_kw(input_text))
-            n_seg = sp.pop("_n", 0)
+            sp, n_seg = self._request_kw(input_text, speed)
             if self.scheduler is not None:
                 req = self.scheduler.submit(input_text, str(voice), stream=False, **({"sampling": sampling} if sampling is not None else {}), **sp)
                 used = getattr(req, "sampling", None)
@@ -179,9 +181,7 @@ class TTSCore:
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
         if container is not None:
             kw["container"] = container
-        sp = _speed_kw(speed)
-        sp.update(self._segment_kw(input_text))
-        n_seg = sp.pop("_n", 0)
+        sp, n_seg = self._request_kw(input_text, speed)
         if self.scheduler is not None:
             req = self.scheduler.submit(input_text, str(voice), stream=True, **kw, **({"sampling": sampling} if sampling is not None else {}), **sp)
             chunks, used = self.scheduler.iter_chunks(req), getattr(req, "sampling", None)
@@ -222,14 +222,6 @@ class TTSCore:
             s16 = np.rint(np.clip(pcm_data, -1.0, 1.0) * 32767).astype(np.int16)
             return (s16.tobytes(), "audio/x-pcm") if kind == "pcm" else (lin2ulaw(s16).tobytes(), "audio/basic")  # ulaw: G.711 of the int16
         return pcm_to_wav_bytes(pcm_data, sample_rate), "audio/wav"
-
-
-def _speed_kw(speed) -> dict:
-    """``{"speed": speed}`` for a speed other than 1 (``ValueError`` out of range), else nothing: a request that names no speed
-    reaches the model exactly as before."""
-    from ..tsm import parse_speed
-
-    return {} if speed is None or parse_speed(speed) is None else {"speed": float(speed)}
 
 
 def seed_used(sampling) -> Optional[int]:

@@ -106,7 +106,11 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
             if msg[0] == "submit":
                 _, rid, text, voice, stream, max_new_tokens = msg[:6]
                 extra = msg[6] if len(msg) > 6 else {}  # (output_format / sampling / speed, only when set)
-                req = sched.submit(text, voice, stream=stream, max_new_tokens=max_new_tokens, **extra)
+                try:
+                    req = sched.submit(text, voice, stream=stream, max_new_tokens=max_new_tokens, **extra)
+                except Exception as e:  # a refused request is that request's error; the worker goes on serving
+                    res_q.put((rid, "error", (type(e).__name__, str(e))))
+                    continue
                 with lock:
                     live[rid] = req
                 threading.Thread(target=pump, args=(rid, req), name=f"smoltts-pump-{rid}", daemon=True).start()
@@ -186,31 +190,10 @@ class GpuPool:
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
                container: Optional[str] = None, segment=None) -> _PoolRequest:
-        """``segment``: as ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
-        if segment is not None and segment is not False:  # refused here, before a worker sees it
-            import dataclasses
+        """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
+        from ..request import parse_request
 
-            from ..longform import segment_options, split_text
-
-            opts = segment_options(segment)
-            split_text(text, opts.max_bytes)  # (a bad break tag is the caller's ValueError)
-            segment = dataclasses.asdict(opts)
-        else:
-            segment = None
-        if output_format is not None:  # refused here, before a worker sees it
-            from ..formats import parse_stream_format
-
-            parse_stream_format(output_format)
-        if container is not None:  # (likewise)
-            from ..formats import check_container
-
-            if not stream:
-                raise ValueError("container applies to streaming requests")
-            check_container(container, output_format)
-        if speed is not None:  # (likewise; speed 1.0 is not passed on)
-            from ..tsm import parse_speed
-
-            speed = None if parse_speed(speed) is None else float(speed)
+        p = parse_request(text, stream, output_format, speed, container, segment)  # refused here, before a worker sees it
         if sampling is not None or self._settings is not None:  # the seed is drawn here: the same on whichever worker serves it
             import dataclasses
 
@@ -232,9 +215,8 @@ class GpuPool:
             self._reqs[req.rid] = req
             self._load[w] += 1
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
-        extra = {k: v for k, v in (("output_format", output_format), ("sampling", sampling), ("speed", speed), ("container", container),
-                                                     ("segment", segment))
-                 if v is not None}
+        extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
+                                   ("container", p.container), ("segment", p.segment)) if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 

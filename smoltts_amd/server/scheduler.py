@@ -56,16 +56,25 @@ class _Request:
     speed_q: Optional[int] = None  # speaking speed in Q16 (tsm.py), time-stretched on the GPU; None: speed 1, no stretch
     stretch_in: list = field(default_factory=list)  # blocking requests with a speed: the utterance's PCM until its last pass
     container: Optional[str] = None  # streaming: "flac" frames the stream's 16-bit samples on the GPU (uint8 chunks)
-    # a long text as chained segments (longform.py): the request keeps its slot from its first segment to its last
-    segs: object = None          # the segments (None: one utterance)
-    seg_opts: object = None      # longform.SegmentOptions
-    seg_k: int = 0               # the segment in the slot now
-    seg_sampling: object = None  # the sampling of segment seg_k (its seed is seed_k)
-    seg_prev: object = None      # (text, (n_codebooks, F) codes) of the segment before seg_k: its context
-    seg_cols: list = field(default_factory=list)  # semantic code columns of segment seg_k so far
-    seg_pcm: dict = field(default_factory=dict)   # blocking: segment -> its PCM pieces from the codec
-    seg_done: int = 0            # blocking: segments whose PCM is complete
-    parent: object = None        # blocking: the segmented request whose segment seg_k this codec job decodes
+    seg: Optional["_Segmented"] = None  # a long text as chained segments (None: one utterance)
+    part_of: object = None    # (request, k): this codec job decodes segment k of a blocking segmented request
+
+
+@dataclass
+class _Segmented:
+    """A long text's progress (longform.SegmentPlan): the request keeps its slot from its first segment to its last."""
+    plan: object              # longform.SegmentPlan
+    sampling: object          # the sampling of segment k (its seed is seed_k)
+    k: int = 0                # the segment in the slot now
+    prev: object = None       # (text, (n_codebooks, F) codes) of segment k - 1: segment k's context
+    cols: list = field(default_factory=list)   # streaming: semantic code columns of segment k so far
+    pcm: list = field(default_factory=list)    # blocking: per segment, its PCM pieces from the codec
+    parts: list = field(default_factory=list)  # blocking: the segments' codec jobs
+    done: int = 0             # blocking: segments whose PCM is complete
+
+    @property
+    def final(self) -> bool:
+        return self.k == len(self.plan.segs) - 1
 
 
 @dataclass
@@ -217,42 +226,17 @@ class BatchScheduler:
         each segment as its own codec job and joins them on the GPU.  A text that is one segment without break tags is an
         ordinary request."""
         from ..config import RequestSampling
-        from ..longform import needs_segments, segment_options, split_text
-        from ..tsm import parse_speed
+        from ..request import parse_request
 
-        speed_q = parse_speed(speed)
-        opts = segment_options(segment)
-        segs = None
-        if opts is not None:
-            segs = split_text(text, opts.max_bytes)
-            if not segs:
-                raise ValueError("the text has nothing to speak")
-            if not needs_segments(segs):
-                segs = None
-        if container is not None:
-            from ..formats import check_container
-
-            if not stream:
-                raise ValueError("container applies to streaming requests")
-            check_container(container, output_format)
-
+        p = parse_request(text, stream, output_format, speed, container, segment)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
-        if output_format is not None:
-            from ..formats import ENC_OFF, parse_stream_format
-
-            if not stream:
-                raise ValueError("output_format applies to streaming requests")
-            if parse_stream_format(output_format)[1] == ENC_OFF:
-                output_format = None
         if self._dead is not None:  # the worker is gone (engine failure or close): nobody would ever answer
             raise RuntimeError(f"scheduler is not running: {self._dead}")
         if self._draining:
             raise RuntimeError("scheduler is not running: shutting down")
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
-                       output_format=output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=speed_q,
-                       container=container)
-        if segs is not None:
-            req.segs, req.seg_opts, req.seg_sampling = segs, opts, resolved
+                       output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=p.speed_q,
+                       container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None)
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
@@ -284,7 +268,7 @@ class BatchScheduler:
         request that is still queued never starts.  The slot itself simply keeps decoding until it is restarted — a batch
         step costs the same with or without it.  Nothing more is delivered except the end marker."""
         req.cancelled = True
-        for part in list(req.seg_pcm.get("parts", [])):
+        for part in list(req.seg.parts) if req.seg is not None else []:
             part.cancelled = True
 
     # ------------------------------------------------------------------ client side: registered voices
@@ -406,7 +390,7 @@ class BatchScheduler:
             # a segmented stream: its segment ends where an utterance would; the stream ends with its final segment only
             fin = np.zeros(self.B, np.int32)
             for r in reqs:
-                fin[r.slot] = r.segs is None or r.seg_k == len(r.segs) - 1
+                fin[r.slot] = r.seg is None or r.seg.final
             fin_d, = upload([fin], self.session.engine.device)
             ends = stream_ends(n_d, done_d, cap_d) & (cap_d > 0)
             seg_end, last = ends.to(torch.int32), (ends & (fin_d != 0)).to(torch.int32)
@@ -427,7 +411,7 @@ class BatchScheduler:
             # slot can take its next tenant straight away: the prefill is queued behind the tick, and the snapshots (device-side
             # copies queued behind their ticks) still show the old tenant's last frames when the host gets to them.
             for slot, r in list(self._active.items()):
-                if r.last_tick < self._tick_no and not r.cancelled and r.segs is None:  # (a segmented one keeps its slot)
+                if r.last_tick < self._tick_no and not r.cancelled and r.seg is None:  # (a segmented one keeps its slot)
                     r.retired = True
                     self._retiring.append(r)
                     del self._active[slot]
@@ -446,15 +430,19 @@ class BatchScheduler:
                 continue
             if req.prompt is None:
                 try:
-                    v = req.voice_entry
-                    if req.segs is not None:
-                        self._segment_prompt(req)
-                    elif v is not None:  # a registered voice: its speaker turns' KV rows are installed, its own turns prefilled at P
-                        P = int(v.grid.shape[1])
-                        req.prompt = self.tts.prompt_encoder.build_prompt(req.text, req.voice, v.grid)[:, P:]
-                        req.pos0, req.prefix = P, v.prefix
+                    v, sg, enc = req.voice_entry, req.seg, self.tts.prompt_encoder
+                    if sg is not None:  # segment k's chained prompt
+                        from ..longform import voice_prefix
+
+                        prefix = voice_prefix(enc, req.voice, v.grid if v is not None else self.tts.voices.get(req.voice))
+                        prompt = sg.plan.prompt(sg.k, enc, prefix, sg.prev, req.max_new_tokens, self.session.max_seq)
                     else:
-                        req.prompt = self.tts._get_prompt(req.text, req.voice)
+                        prompt = enc.build_prompt(req.text, req.voice, v.grid) if v is not None else self.tts._get_prompt(req.text, req.voice)
+                    if v is not None:  # a registered voice: its speaker turns' KV rows are installed, its own turns prefilled at P
+                        P = int(v.grid.shape[1])
+                        req.prompt, req.pos0, req.prefix = prompt[:, P:], P, v.prefix
+                    else:
+                        req.prompt = prompt
                     if req.pos0 + req.prompt.shape[1] + req.max_new_tokens + 2 > self.session.max_seq:
                         raise ValueError(f"prompt ({req.pos0} + {req.prompt.shape[1]} positions) + max_new_tokens ({req.max_new_tokens}) "
                                          f"exceed max_seq_len ({self.session.max_seq})")
@@ -480,7 +468,7 @@ class BatchScheduler:
                 req.slot = self._free.pop(0)
             new.append(req)
         entries = {b: self._default_sampling for b in freed}
-        entries.update({r.slot: (r.seg_sampling if r.segs is not None else r.sampling) for r in new})
+        entries.update({r.slot: (r.seg.sampling if r.seg is not None else r.sampling) for r in new})
         self._write_sampling(entries)  # on the frame stream, ahead of the park / prefill of the new tenants
         if not new:
             return
@@ -510,46 +498,16 @@ class BatchScheduler:
         else:
             self._held = req
 
-    def _segment_prompt(self, req: _Request) -> None:
-        """Segment ``req.seg_k``'s chained prompt (longform.chain_prompt); a registered voice's prefix rows are installed for
-        every segment and only the turns after them are prefilled."""
-        from ..longform import chain_prompt, voice_prefix
-
-        enc = self.tts.prompt_encoder
-        v = req.voice_entry
-        prefix = voice_prefix(enc, req.voice, v.grid if v is not None else self.tts.voices.get(req.voice))
-        prev = req.seg_prev if req.seg_opts.context == "previous" and req.seg_prev is not None else (None, None)
-        prompt = chain_prompt(enc, prefix, req.segs[req.seg_k].text, *prev, max_new_tokens=req.max_new_tokens,
-                              max_seq=self.session.max_seq)
-        if v is not None:
-            P = int(v.grid.shape[1])
-            req.prompt, req.pos0, req.prefix = prompt[:, P:], P, v.prefix
-        else:
-            req.prompt = prompt
-
     def _next_segment(self, r: _Request, cols: np.ndarray) -> None:
-        """Segment r.seg_k has ended (seen in a snapshot): its codes become the next one's context and the slot, still the
-        request's, waits in ``_refills`` for the next chained prompt."""
-        import dataclasses
-
-        from ..longform import segment_seed
-
-        r.seg_prev = (r.segs[r.seg_k].text, cols.T.copy())
-        r.seg_k += 1
-        r.seg_sampling = dataclasses.replace(r.sampling, seed=segment_seed(r.sampling.seed, r.seg_k))
-        r.prompt, r.emitted, r.seg_cols = None, 0, []
+        """Segment k has ended (seen in a snapshot): its codes become the next one's context and the slot, still the request's,
+        waits in ``_refills`` for the next chained prompt."""
+        sg = r.seg
+        sg.prev = (sg.plan.segs[sg.k].text, cols.T.copy())
+        sg.k += 1
+        sg.sampling, sg.cols = sg.plan.sampling(sg.k, r.sampling), []
+        r.prompt, r.emitted = None, 0
         del self._active[r.slot]
         self._refills.append(r)
-
-    def _seam_args(self, r: _Request):
-        """(pause, flags, lead) of the seam stage for segment r.seg_k, in samples."""
-        from ..engine import SEAM_FINAL, SEAM_FIRST
-        from ..seam import pause_samples
-
-        k, segs, final = r.seg_k, r.segs, r.seg_k == len(r.segs) - 1
-        pause = pause_samples(segs[-1].pause_after_s) if final else pause_samples(
-            segs[k].pause_after_s if segs[k].pause_after_s is not None else r.seg_opts.pause_s)
-        return pause, (SEAM_FIRST if k == 0 else 0) | (SEAM_FINAL if final else 0), pause_samples(segs[0].pause_before_s)
 
     def _write_sampling(self, entries: Dict[int, object]) -> None:
         """Slot b samples with ``entries[b]`` from the next pick on the current stream on (only changed entries are uploaded)."""
@@ -692,14 +650,13 @@ class BatchScheduler:
             if restart:
                 self._stream_codec.reset_slots(sorted(set(restart)))
                 # (a segmented stream's later segments restart the codec only: its other stages run on)
-                fresh = [r for r in new if r.segs is None or r.seg_k == 0]
+                fresh = [r for r in new if r.seg is None or r.seg.k == 0]
                 self._stream_conv.reset_slots([r.slot for r in fresh], [r.output_format for r in fresh],
                                               [r.speed_q for r in fresh], [r.container for r in fresh])
-                segd = [r for r in new if r.segs is not None]
+                segd = [r for r in new if r.seg is not None]
                 if segd:
-                    args = [self._seam_args(r) for r in segd]
-                    self._stream_conv.start_segments([r.slot for r in segd], [a[0] for a in args], [a[1] for a in args],
-                                                     [a[2] for a in args])
+                    pauses, flags, leads = zip(*(r.seg.plan.seam_args(r.seg.k) for r in segd))
+                    self._stream_conv.start_segments([r.slot for r in segd], pauses, flags, leads)
                 for b in restart:
                     self._codec_age[b] = 0
             for b in range(self.B):
@@ -731,6 +688,8 @@ class BatchScheduler:
         self._gpu_wait_s += time.perf_counter() - t
 
     def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery]) -> None:
+        from ..generate import semantic_columns
+
         stream_items = []  # the streams' share of this tick's codec pass: (request, pcm row, samples, last?) handed out by _deliver
         urgent = False     # a stream's first chunk is among them
         nq = self.tts.config.num_codebooks
@@ -758,43 +717,38 @@ class BatchScheduler:
                 continue
             n = min(int(n_frames[slot]), r.max_new_tokens + 1)
             finished = bool(stream_ends(n_frames[slot], done[slot], r.max_new_tokens + 1))
-            seg_more = r.segs is not None and r.seg_k + 1 < len(r.segs)  # a segment follows this one
+            seg_more = r.seg is not None and not r.seg.final  # a segment follows this one
             if r.stream:
                 # streaming requests decode every frame (__init__.py:88-92); this tick's PCM of the slot starts at its frame
                 # r.emitted (== f0 of the tick: one codec frame per LM frame)
                 k = n - r.emitted
-                if r.segs is not None and k > 0:  # the next segment's context: this one's semantic frames
-                    slow = codes[slot, r.emitted:n, 0]
-                    keep = (slow >= tc.semantic_start_id) & (slow <= tc.semantic_end_id)
-                    r.seg_cols.append(codes[slot, r.emitted:n][keep][:, -nq:].astype(np.int32))
+                if r.seg is not None and k > 0:  # the next segment's context: this one's semantic frames
+                    r.seg.cols.append(semantic_columns(codes[slot, r.emitted:n], tc, nq))
                 if k > 0 or finished:
                     assert k == 0 or (stream_pass is not None and r.emitted == (tick_no - r.first_tick) * self.tick), "stream bookkeeping out of step"
                     stream_items.append((r, slot, max(k, 0) * 1920, finished and not seg_more))
                     urgent = urgent or r.emitted == 0
                 r.emitted = n
                 if finished:
-                    if r.segs is not None:
+                    if r.seg is not None:
                         self._counts["segments"] += 1
                     if seg_more:
-                        self._next_segment(r, np.concatenate(r.seg_cols) if r.seg_cols else np.zeros((0, nq), np.int32))
+                        self._next_segment(r, np.concatenate(r.seg.cols) if r.seg.cols else np.zeros((0, nq), np.int32))
                         continue
                     r.stream_done = True
                     release(r)  # the end marker follows the last chunk, in _deliver
                 continue
             # blocking requests keep only frames whose slow id is a semantic token (generate_blocking, lm/generate.py:196-207)
-            slow = codes[slot, r.emitted:n, 0]
-            keep = (slow >= tc.semantic_start_id) & (slow <= tc.semantic_end_id)
-            cols = codes[slot, r.emitted:n][keep][:, -nq:].astype(np.int32)
+            cols = semantic_columns(codes[slot, r.emitted:n], tc, nq)
             r.emitted = n
             if cols.shape[0]:
                 r.pending.append(cols)
-            if finished and r.segs is not None:  # a segment of a blocking segmented request: its own codec job
+            if finished and r.seg is not None:  # a segment of a blocking segmented request: its own codec job
                 self._counts["segments"] += 1
                 seg_cols = np.concatenate(r.pending) if r.pending else np.zeros((0, nq), np.int32)
-                part = _Request(r.text, r.voice, False, r.max_new_tokens, pending=[seg_cols], seg_k=r.seg_k, parent=r,
-                                cancelled=r.cancelled)
-                r.seg_pcm.setdefault("parts", []).append(part)
-                r.seg_pcm[r.seg_k] = []
+                part = _Request(r.text, r.voice, False, r.max_new_tokens, pending=[seg_cols], part_of=(r, r.seg.k), cancelled=r.cancelled)
+                r.seg.parts.append(part)
+                r.seg.pcm.append([])
                 r.pending = []
                 self._finished.append(part)
                 if seg_more:
@@ -919,9 +873,10 @@ class BatchScheduler:
                 host = host.numpy()
             self._deliveries.pop(0)
             for r, b, n, fin in d.items:
-                if r.parent is not None:  # a segment of a blocking segmented request
+                if r.part_of is not None:  # a segment of a blocking segmented request
                     if n and not r.cancelled:
-                        r.parent.seg_pcm[r.seg_k].append(host[b, :n].copy())
+                        parent, k = r.part_of
+                        parent.seg.pcm[k].append(host[b, :n].copy())
                         self._counts["frames_delivered"] += n // 1920
                     if fin:
                         self._part_done(r)
@@ -949,25 +904,23 @@ class BatchScheduler:
         """A segment's PCM of a blocking segmented request is complete; once all are, they are joined on the GPU (engine.seam_join)
         and go out, stretched first when the request has a speed."""
         from ..engine import SeamJoiner, seam_join
-        from ..seam import pause_samples
 
-        r = part.parent
-        r.seg_done += 1
+        r = part.part_of[0]
+        sg = r.seg
+        sg.done += 1
         if r.cancelled:
             self._end(r)
             return
-        if r.seg_done < len(r.segs):
+        if sg.done < len(sg.plan.segs):
             return
         torch = self._torch
-        pcms = [np.concatenate(r.seg_pcm[k]) if r.seg_pcm[k] else np.zeros(0, np.float32) for k in range(len(r.segs))]
-        pauses = [pause_samples(s.pause_after_s if s.pause_after_s is not None else r.seg_opts.pause_s) for s in r.segs[:-1]]
+        pcms = [np.concatenate(p) if p else np.zeros(0, np.float32) for p in sg.pcm]
         dev = self.session.engine.device
         with torch.cuda.stream(self._stretch_stream):
             if self._block_seam is None:
                 self._block_seam = SeamJoiner(dev, 1)
-            pcm = seam_join(pcms, pauses, dev, lead=pause_samples(r.segs[0].pause_before_s),
-                            trail=pause_samples(r.segs[-1].pause_after_s), joiner=self._block_seam)
-        r.seg_pcm = {}
+            pcm = seam_join(pcms, sg.plan.pauses, dev, lead=sg.plan.lead, trail=sg.plan.trail, joiner=self._block_seam)
+        sg.pcm = []
         if r.speed_q:
             r.stretch_in = [pcm]
             self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
@@ -1112,9 +1065,9 @@ class BatchScheduler:
 
     def _end(self, r: _Request, e: Optional[Exception] = None) -> None:
         """Queue the end marker of a request (exactly once)."""
-        if r.parent is not None:  # a segment's codec job: the segmented request ends, not its part
+        if r.part_of is not None:  # a segment's codec job: the segmented request ends, not its part
             if r.cancelled or e is not None:
-                self._end(r.parent, e)
+                self._end(r.part_of[0], e)
             return
         if not r.closed:
             r.closed = True

@@ -33,6 +33,8 @@ class EchoScheduler:
         if text == "__raise__":
             r.out.put(ValueError("bad request"))
             return r
+        if text == "__refuse__":  # refused by submit itself, as BatchScheduler.submit refuses a bad request
+            raise ValueError("refused at submit")
 
         def run():
             n = len(text) if max_new_tokens is None else min(len(text), max_new_tokens)

@@ -3,8 +3,8 @@ the server's long_text settings with a stand-in model."""
 import numpy as np
 import pytest
 
-from smoltts_amd.longform import (SEED_STEP, Segment, SegmentOptions, chain_prompt, needs_segments, segment_options, segment_seed,
-                                  split_text, voice_prefix)
+from smoltts_amd.longform import (SEED_STEP, Segment, SegmentOptions, SegmentPlan, chain_prompt, needs_segments, segment_options,
+                                  segment_seed, split_text, voice_prefix)
 from smoltts_amd import seam
 from smoltts_amd.seam import BLOCK, D, H, THRESH, SeamState
 
@@ -128,6 +128,43 @@ def test_segment_seed():
     assert segment_seed(12345, 0) == 12345
     assert segment_seed(12345, 1) == (12345 + 0x9E3779B97F4A7C15) % 2**64
     assert segment_seed(2**64 - 1, 2) == (2**64 - 1 + 2 * SEED_STEP) % 2**64
+
+
+def test_segment_plan_numbers():
+    from smoltts_amd.config import GenerationSettings, RequestSampling
+
+    text = '<break time="0.5s"/> One two. <break time="1s"/> Three four. Five six. <break time="250ms"/>'
+    plan = SegmentPlan.create(text, SegmentOptions(max_bytes=12, pause_s=0.2))
+    assert [s.text for s in plan.segs] == ["One two.", "Three four.", "Five six."]
+    assert plan.pauses == [24000, 4800] and plan.lead == 12000 and plan.trail == 6000
+    assert [plan.seam_args(k) for k in range(3)] == [(24000, seam.FIRST, 12000), (4800, 0, 12000), (6000, seam.FINAL, 12000)]
+    want = [5, 11400714819323198490, 4354685564936845359]
+    assert [plan.sampling(k, RequestSampling(temperature=0.5, seed=5)) for k in range(3)] == [
+        RequestSampling(temperature=0.5, seed=s) for s in want]
+    gs = GenerationSettings(max_new_tokens=7, seed=5)
+    assert [plan.sampling(k, gs) for k in range(3)] == [GenerationSettings(max_new_tokens=7, seed=s) for s in want]
+    assert seam.segment_flags(0, 1) == seam.FIRST | seam.FINAL
+
+
+def test_segment_plan_prompt_follows_the_context_option(encoder):
+    pre = voice_prefix(encoder, "heart")
+    codes = np.arange(8 * 3, dtype=np.uint32).reshape(8, 3) % 50
+    for context in ("previous", "none"):
+        plan = SegmentPlan.create("First. Second.", SegmentOptions(max_bytes=8, context=context))
+        assert plan.prompt(0, encoder, pre, None, 100, 2048).tolist() == chain_prompt(encoder, pre, "First.").tolist()
+        got = plan.prompt(1, encoder, pre, ("First.", codes), 100, 2048)
+        want = chain_prompt(encoder, pre, "Second.", *(("First.", codes) if context == "previous" else (None, None)), 100, 2048)
+        np.testing.assert_array_equal(got, want)
+
+
+def test_segment_plan_is_none_exactly_without_segments():
+    texts = ["Hello there.", "One. Two. Three.", 'Hi. <break time="1s"/>', '<break time="1s"/> Hi.', "a" * 40, "x\ny",
+             'Hi <break time="0s"/> there']
+    for opts in (SegmentOptions(), SegmentOptions(max_bytes=8)):
+        for t in texts:
+            assert (SegmentPlan.create(t, opts) is None) == (not needs_segments(split_text(t, opts.max_bytes))), (t, opts)
+    with pytest.raises(ValueError, match="nothing to speak"):
+        SegmentPlan.create(' <break time="1s"/> ', SegmentOptions())
 
 
 # ---------------------------------------------------------------------------------------------------- numpy seam model

@@ -60,6 +60,20 @@ def test_pool_routes_relays_and_balances():
         pool.submit("after close")
 
 
+def test_pool_answers_a_submit_the_worker_refuses():
+    from smoltts_amd.server.pool import GpuPool
+
+    pool = GpuPool(make_echo, devices=[0, 1], ready_timeout=120)
+    try:
+        for _ in range(2):  # (whichever worker takes it)
+            with pytest.raises(ValueError, match="refused at submit"):
+                pool.synthesize("__refuse__")
+        assert pool.synthesize("ok").shape == (8,)  # the workers keep serving
+        assert pool.stats() == {"workers": 2, "alive": 2, "in_flight": [0, 0], "restarts": [0, 0]}
+    finally:
+        pool.close()
+
+
 def test_pool_cancel_and_worker_death():
     from smoltts_amd.server.pool import GpuPool
 
