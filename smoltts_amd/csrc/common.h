@@ -40,6 +40,26 @@ void set_error(const char* fmt, ...);
     if (_r != SMOLTTS_OK) return _r;                                                      \
   } while (0)
 
+// a slot index of a session or stage that holds B slots
+inline int check_slot(const char* what, int slot, int B) {
+  ST_REQUIRE(slot >= 0 && slot < B, SMOLTTS_E_INVALID, "%s: slot %d out of range", what, slot);
+  return SMOLTTS_OK;
+}
+
+// Caller-owned device slabs: a layout is written once, as a sequence of take() calls, and run twice -- over a null base to
+// measure the slab, over the slab itself to assign the pointers -- so the size and the pointers cannot disagree.
+inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+struct Carver {
+  char* base;  // null: measure only
+  size_t off;  // bytes taken so far: the next region's offset, in the end the slab's size
+  template <typename T>
+  T* take(size_t n) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off = align_up(off + n * sizeof(T));
+    return p;
+  }
+};
+
 // Per-device "first time" flags of the launchers: a kernel's MaxDynamicSharedMemorySize attribute and the CU count are
 // properties of a DEVICE, so a process that moves to a second GPU must set / read them again there.
 struct PerDevice {

@@ -12,9 +12,9 @@
 // partitions of order 8 - l), where the group picks its k.  The winner is packed by an exclusive scan of per-sample code
 // lengths and 32-bit atomicOr into a zeroed LDS bit buffer; its CRC-16 is the XOR of per-lane segment CRCs, each multiplied by
 // x^(8 bytes behind the segment) mod 0x8005 (CRC with init 0 and no xorout is linear).
-#include <new>
+#include "stage.h"
 
-#include "common.h"
+using namespace smoltts;
 
 namespace {
 
@@ -427,7 +427,6 @@ __global__ __launch_bounds__(kT) void flac_kernel(const float* __restrict__ pcm,
   }
 }
 
-constexpr int kResetMax = 16;
 struct ResetArgs {
   int32_t n;
   int32_t slot[kResetMax];
@@ -448,8 +447,6 @@ __global__ __launch_bounds__(64) void flac_reset_kernel(ResetArgs a, FlacCfg* cf
   }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int rate_code(int rate) {
   for (const RateCode& r : kRateCodes)
     if (r.rate == rate) return r.code;
@@ -463,18 +460,21 @@ int blocks_for(int64_t n_max) { return (int)((n_max + kHold + kMaxN - 1) / kMaxN
 struct SmolttsFlac {
   int B;
   FlacCfg* cfg_dev;
-  FlacState* st[2];
+  PingPong<FlacState> st;
   FlacCfg* cfg_host;  // mirror of cfg_dev (sizes the grid)
-  unsigned parity;    // st[parity] holds the slots' current state
 };
 
-using namespace smoltts;
+static size_t carve(SmolttsFlac* f, char* base) {
+  Carver cv{base, 0};
+  f->cfg_dev = cv.take<FlacCfg>(f->B);
+  f->st.carve(cv, f->B);
+  return cv.off;
+}
 
 extern "C" {
 
 size_t smoltts_flac_bytes(int32_t max_batch) {
-  if (max_batch <= 0) return 0;
-  return align256(sizeof(FlacCfg) * max_batch) + 2 * align256(sizeof(FlacState) * max_batch);
+  return stage_bytes<SmolttsFlac>(max_batch);
 }
 
 int32_t smoltts_flac_max_blocks(int32_t n_max) {
@@ -488,18 +488,9 @@ size_t smoltts_flac_out_bytes(int32_t n_max) {
 }
 
 int smoltts_flac_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsFlac** out) {
-  ST_REQUIRE(slab_dev && out && max_batch > 0, SMOLTTS_E_INVALID, "flac_create: bad argument");
-  ST_REQUIRE(((uintptr_t)slab_dev & 255) == 0, SMOLTTS_E_INVALID, "flac_create: slab must be 256-byte aligned");
-  const size_t need = smoltts_flac_bytes(max_batch);
-  ST_REQUIRE(slab_bytes >= need, SMOLTTS_E_CAPACITY, "flac_create: slab has %zu bytes, %zu needed", slab_bytes, need);
-  char* p = (char*)slab_dev;
-  SmolttsFlac* f = new (std::nothrow) SmolttsFlac;
-  ST_REQUIRE(f, SMOLTTS_E_INVALID, "flac_create: out of host memory");
-  f->B = max_batch;
-  f->cfg_dev = (FlacCfg*)p;
-  f->st[0] = (FlacState*)(p + align256(sizeof(FlacCfg) * max_batch));
-  f->st[1] = (FlacState*)((char*)f->st[0] + align256(sizeof(FlacState) * max_batch));
-  f->parity = 0;
+  SmolttsFlac* f = nullptr;
+  size_t need = 0;
+  ST_TRY(stage_create("flac_create", slab_dev, slab_bytes, max_batch, out, &f, &need));
   f->cfg_host = static_cast<FlacCfg*>(calloc((size_t)max_batch, sizeof(FlacCfg)));
   if (!f->cfg_host) {
     delete f;
@@ -525,41 +516,30 @@ void smoltts_flac_destroy(SmolttsFlac* f) {
 int smoltts_flac_reset_slots(SmolttsFlac* f, const int32_t* slots_host, const int32_t* rates_host, const int32_t* sources_host,
                              int32_t n_slots, void* stream) {
   ST_REQUIRE(f && slots_host && rates_host && sources_host && n_slots > 0, SMOLTTS_E_INVALID, "flac_reset_slots: bad argument");
-  for (int i0 = 0; i0 < n_slots; i0 += kResetMax) {
-    ResetArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = n_slots - i0 < kResetMax ? n_slots - i0 : kResetMax;
-    for (int i = 0; i < a.n; ++i) {
-      const int b = slots_host[i0 + i], src = sources_host[i0 + i], rate = rates_host[i0 + i];
-      ST_REQUIRE(b >= 0 && b < f->B, SMOLTTS_E_INVALID, "flac_reset_slots: slot %d out of range", b);
-      ST_REQUIRE(src == SMOLTTS_FLAC_OFF || src == SMOLTTS_FLAC_F32 || src == SMOLTTS_FLAC_S16, SMOLTTS_E_INVALID,
-                 "flac_reset_slots: unknown source %d", src);
-      FlacCfg c;
-      memset(&c, 0, sizeof(c));
-      c.src = src;
-      if (src != SMOLTTS_FLAC_OFF) {
-        c.rate_code = rate_code(rate);
-        ST_REQUIRE(c.rate_code > 0, SMOLTTS_E_INVALID, "flac_reset_slots: unsupported rate %d", rate);
-      }
-      a.slot[i] = b;
-      a.cfg[i] = c;
+  auto fill = [&](ResetArgs& a, int i, int k) -> int {
+    const int src = sources_host[k], rate = rates_host[k];
+    ST_REQUIRE(src == SMOLTTS_FLAC_OFF || src == SMOLTTS_FLAC_F32 || src == SMOLTTS_FLAC_S16, SMOLTTS_E_INVALID,
+               "flac_reset_slots: unknown source %d", src);
+    FlacCfg& c = a.cfg[i];  // (zeroed)
+    c.src = src;
+    if (src != SMOLTTS_FLAC_OFF) {
+      c.rate_code = rate_code(rate);
+      ST_REQUIRE(c.rate_code > 0, SMOLTTS_E_INVALID, "flac_reset_slots: unsupported rate %d", rate);
     }
+    return SMOLTTS_OK;
+  };
+  return reset_in_groups<ResetArgs>("flac_reset_slots", f->B, slots_host, n_slots, fill, [&](const ResetArgs& a) {
     for (int i = 0; i < a.n; ++i) f->cfg_host[a.slot[i]] = a.cfg[i];
-    hipLaunchKernelGGL(flac_reset_kernel, dim3(a.n), dim3(64), 0, (hipStream_t)stream, a, f->cfg_dev, f->st[0], f->st[1]);
-    ST_CHECK_HIP(hipGetLastError());
-  }
-  return SMOLTTS_OK;
+    hipLaunchKernelGGL(flac_reset_kernel, dim3(a.n), dim3(64), 0, (hipStream_t)stream, a, f->cfg_dev, f->st.half[0], f->st.half[1]);
+  });
 }
 
 int smoltts_flac_chunk(SmolttsFlac* f, const float* pcm_dev, int64_t pcm_stride, int32_t n_in, const int32_t* valid_in_dev,
                        const void* s16_dev, int64_t s16_stride, const int32_t* s16_counts_dev, int32_t batch,
                        const int32_t* last_dev, void* out_dev, int64_t out_stride, int32_t* sizes_dev, int32_t max_blocks,
                        void* stream) {
-  ST_REQUIRE(f && out_dev && sizes_dev, SMOLTTS_E_INVALID, "flac_chunk: null argument");
-  ST_REQUIRE(batch > 0 && batch <= f->B, SMOLTTS_E_INVALID, "flac_chunk: batch %d (1..%d)", batch, f->B);
   // a slot whose source is not given this call reads nothing; the grid and rows cover the most any other slot can read
-  ST_REQUIRE(!pcm_dev || (n_in >= 0 && pcm_stride >= n_in), SMOLTTS_E_INVALID, "flac_chunk: n_in %d, pcm_stride %lld", n_in,
-             (long long)pcm_stride);
+  ST_TRY(check_chunk("flac_chunk", f, out_dev && sizes_dev, batch, pcm_dev != nullptr, n_in, pcm_stride));
   ST_REQUIRE(!s16_dev || (s16_counts_dev && s16_stride >= 0), SMOLTTS_E_INVALID, "flac_chunk: int16 samples without counts");
   int64_t n_max = 0;
   for (int b = 0; b < batch; ++b) {
@@ -571,12 +551,11 @@ int smoltts_flac_chunk(SmolttsFlac* f, const float* pcm_dev, int64_t pcm_stride,
   ST_REQUIRE(max_blocks >= blocks_for(n_max), SMOLTTS_E_CAPACITY, "flac_chunk: max_blocks %d < %d", max_blocks, blocks_for(n_max));
   ST_REQUIRE(out_stride >= (int64_t)smoltts_flac_out_bytes((int32_t)n_max), SMOLTTS_E_CAPACITY, "flac_chunk: out_stride %lld < %zu bytes",
              (long long)out_stride, smoltts_flac_out_bytes((int32_t)n_max));
-  const unsigned p = f->parity;
   hipLaunchKernelGGL(flac_kernel, dim3(max_blocks, f->B), dim3(kT), 0, (hipStream_t)stream, pcm_dev, pcm_stride, n_in, valid_in_dev,
-                     (const uint8_t*)s16_dev, s16_stride, s16_counts_dev, batch, last_dev, f->cfg_dev, f->st[p], f->st[p ^ 1],
+                     (const uint8_t*)s16_dev, s16_stride, s16_counts_dev, batch, last_dev, f->cfg_dev, f->st.cur(), f->st.next(),
                      (uint8_t*)out_dev, out_stride, sizes_dev, max_blocks);
   ST_CHECK_HIP(hipGetLastError());
-  f->parity = p ^ 1;
+  f->st.flip();
   return SMOLTTS_OK;
 }
 

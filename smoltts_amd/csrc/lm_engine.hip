@@ -116,22 +116,9 @@ struct SmolttsSession {
 
 namespace {
 
-size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
-struct Carver {
-  char* base;
-  size_t off;
-  template <typename T>
-  T* take(size_t n) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off = align_up(off + n * sizeof(T));
-    return p;
-  }
-};
-
 int imax(int a, int b) { return a > b ? a : b; }
 
-void carve(SmolttsSession* s, char* base, size_t* total) {
+size_t carve(SmolttsSession* s, char* base) {
   const SmolttsLMConfig& c = s->e->cfg;
   Carver cv{base, 0};
   const size_t B = s->B, R = s->max_rows, H = 1 + c.n_fast;
@@ -183,7 +170,7 @@ void carve(SmolttsSession* s, char* base, size_t* total) {
   // slot mode only (smoltts_session_set_slot_sampling): the table, then the upload area (B entries, B slot numbers) -- the
   // tail of the slab, in use once the session enters slot mode
   s->slot_tab_area = cv.take<SmolttsSlotSampling>(2 * B + (B * sizeof(int) + sizeof(SmolttsSlotSampling) - 1) / sizeof(SmolttsSlotSampling));
-  *total = cv.off;
+  return cv.off;
 }
 
 __global__ void init_state_kernel(int B, int n_fast, int* iota, int* fastpos, int* pos, int* frames, int* done, int* mask,
@@ -673,6 +660,41 @@ void drop_graphs(SmolttsSession* s) {
   drop_multi_graphs(s);
 }
 
+void set_stop_on_eos(SmolttsSession* s, int stop_on_eos) {
+  if (s->stop_on_eos != stop_on_eos) drop_graphs(s);  // the flag is baked into the captured commit nodes
+  s->stop_on_eos = stop_on_eos;
+}
+
+// The slot list of an entry call and the list beside it: every slot's last prompt row, or (`positions`) its parking position
+int check_slot_lists(const char* what, const SmolttsSession* s, const int32_t* slots_host, const int32_t* second_host, int n_slots,
+                     int second_limit, bool positions = false) {
+  ST_REQUIRE(n_slots > 0 && n_slots <= s->B, SMOLTTS_E_CAPACITY, "%s: %d slots, session holds %d", what, n_slots, s->B);
+  for (int i = 0; i < n_slots; ++i) {
+    ST_TRY(check_slot(what, slots_host[i], s->B));
+    const int v = second_host[i];
+    ST_REQUIRE(v >= 0 && v < second_limit, SMOLTTS_E_INVALID,
+               positions ? "%s: position %d outside the cache (%d)" : "%s: last_row %d out of range", what, v, second_limit);
+  }
+  return SMOLTTS_OK;
+}
+
+// KV rows of n_rows prompt rows, through the prefill workspace of the session given (the side call passes its shadow session)
+int prefill_rows(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_slot_dev, const int32_t* row_pos_dev, int n_rows,
+                 hipStream_t st) {
+  ST_TRY(embed_rows(s, grid_dev, n_rows, s->xr, st));
+  return run_slow_layers(s, s->xr, s->qr, n_rows, row_pos_dev, row_slot_dev, /*publish_hidden=*/false, st);
+}
+
+// The staged slots (stage_upload) become live at their last prompt column; their first decode frame recomputes that column's row
+int arm_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos_dev, int n_slots, hipStream_t st) {
+  hipLaunchKernelGGL(slot_start_kernel, dim3((s->B + 63) / 64), dim3(64), 0, st, s->B, 1 + s->e->cfg.n_fast, n_slots, s->stage_slots,
+                     s->stage_last, row_pos_dev, grid_dev, s->pos, s->frames, s->done, s->margin, s->cur_col, s->salt);
+  ST_CHECK_HIP(hipGetLastError());
+  ST_TRY(launch_commit_embed(s, /*do_commit=*/0, 0, st));  // mask = !done; embed every slot's (new) current column
+  s->prefilled = true;
+  return SMOLTTS_OK;
+}
+
 // The form of the frame launches: bit 0 = some slot samples its slow token, bit 1 = some slot samples its depth codes.  Outside
 // slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
 // point that launches or captures picks, after the last change of the table.
@@ -958,9 +980,7 @@ size_t smoltts_session_slab_bytes_kv(const SmolttsEngine* e, int32_t max_batch, 
   tmp.e = const_cast<SmolttsEngine*>(e);
   tmp.kv_format = kv_format;
   tmp.B = max_batch; tmp.max_seq = max_seq; tmp.max_rows = max_rows; tmp.max_frames = max_frames;
-  size_t total = 0;
-  carve(&tmp, nullptr, &total);
-  return total;
+  return carve(&tmp, nullptr);
 }
 
 int smoltts_session_create(SmolttsEngine* e, void* slab_dev, size_t slab_bytes, int32_t max_batch, int32_t max_seq,
@@ -991,8 +1011,7 @@ int smoltts_session_create_kv(SmolttsEngine* e, void* slab_dev, size_t slab_byte
   s->fuse_depth_attn = true;
   s->fuse_pick = true;
   s->kv_format = kv_format;
-  size_t total = 0;
-  carve(s, (char*)slab_dev, &total);
+  carve(s, (char*)slab_dev);
   if (hipHostMalloc((void**)&s->h_stage, sizeof(int) * 2 * max_batch * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
     delete s;
     set_error("session_create: hipHostMalloc failed");
@@ -1057,23 +1076,17 @@ int smoltts_lm_prefill(SmolttsSession* s, const int32_t* grid_dev, const int32_t
   ST_REQUIRE(s && grid_dev && row_slot_dev && row_pos_dev && slots_host && last_row_host, SMOLTTS_E_INVALID,
              "lm_prefill: null argument");
   ST_REQUIRE(n_rows > 0 && n_rows <= s->max_rows, SMOLTTS_E_CAPACITY, "lm_prefill: %d rows, session holds %d", n_rows, s->max_rows);
-  ST_REQUIRE(n_slots > 0 && n_slots <= s->B, SMOLTTS_E_CAPACITY, "lm_prefill: %d slots, session holds %d", n_slots, s->B);
-  for (int i = 0; i < n_slots; ++i) {
-    ST_REQUIRE(slots_host[i] >= 0 && slots_host[i] < s->B, SMOLTTS_E_INVALID, "lm_prefill: slot %d out of range", slots_host[i]);
-    ST_REQUIRE(last_row_host[i] >= 0 && last_row_host[i] < n_rows, SMOLTTS_E_INVALID, "lm_prefill: last_row %d out of range", last_row_host[i]);
-  }
+  ST_TRY(check_slot_lists("lm_prefill", s, slots_host, last_row_host, n_slots, n_rows));
   hipStream_t st = (hipStream_t)stream;
   const SmolttsEngine* e = s->e;
   const SmolttsLMConfig& c = e->cfg;
-  if (s->stop_on_eos != stop_on_eos) drop_graphs(s);  // the flag is baked into the captured commit nodes
-  s->stop_on_eos = stop_on_eos;
+  set_stop_on_eos(s, stop_on_eos);
   pick_form(s);
   ST_TRY(stage_upload(s, slots_host, last_row_host, n_slots, st));
   hipLaunchKernelGGL(slot_reset_kernel, dim3((s->B + 63) / 64), dim3(64), 0, st, s->B, n_slots, s->stage_slots, s->stage_last,
                      row_pos_dev, s->pos, s->frames, s->done, s->mask, s->margin, s->salt);
   ST_CHECK_HIP(hipGetLastError());
-  ST_TRY(embed_rows(s, grid_dev, n_rows, s->xr, st));
-  ST_TRY(run_slow_layers(s, s->xr, s->qr, n_rows, row_pos_dev, row_slot_dev, /*publish_hidden=*/false, st));
+  ST_TRY(prefill_rows(s, grid_dev, row_slot_dev, row_pos_dev, n_rows, st));
   hipLaunchKernelGGL(scatter_last_kernel, dim3(n_slots), dim3(256), 0, st, s->xr, s->stage_slots, s->stage_last, c.dim, s->xt);
   ST_CHECK_HIP(hipGetLastError());
   {  // publish the slow hidden rows of all B slots (rows of slots not being started are masked at commit)
@@ -1100,18 +1113,13 @@ int smoltts_lm_prefill_chunk(SmolttsSession* s, const int32_t* grid_dev, const i
   ST_REQUIRE(s && grid_dev && row_slot_dev && row_pos_dev && slots_host && last_row_host, SMOLTTS_E_INVALID,
              "lm_prefill_chunk: null argument");
   ST_REQUIRE(n_rows > 0 && n_rows <= s->max_rows, SMOLTTS_E_CAPACITY, "lm_prefill_chunk: %d rows, session holds %d", n_rows, s->max_rows);
-  ST_REQUIRE(n_slots > 0 && n_slots <= s->B, SMOLTTS_E_CAPACITY, "lm_prefill_chunk: %d slots, session holds %d", n_slots, s->B);
-  for (int i = 0; i < n_slots; ++i) {
-    ST_REQUIRE(slots_host[i] >= 0 && slots_host[i] < s->B, SMOLTTS_E_INVALID, "lm_prefill_chunk: slot %d out of range", slots_host[i]);
-    ST_REQUIRE(last_row_host[i] >= 0 && last_row_host[i] < n_rows, SMOLTTS_E_INVALID, "lm_prefill_chunk: last_row %d out of range", last_row_host[i]);
-  }
+  ST_TRY(check_slot_lists("lm_prefill_chunk", s, slots_host, last_row_host, n_slots, n_rows));
   hipStream_t st = (hipStream_t)stream;
   ST_TRY(stage_upload(s, slots_host, last_row_host, n_slots, st));
   hipLaunchKernelGGL(slot_park_kernel, dim3((s->B + 63) / 64), dim3(64), 0, st, s->B, n_slots, s->stage_slots, s->stage_last, row_pos_dev,
                      s->pos, s->done, s->mask);
   ST_CHECK_HIP(hipGetLastError());
-  ST_TRY(embed_rows(s, grid_dev, n_rows, s->xr, st));
-  ST_TRY(run_slow_layers(s, s->xr, s->qr, n_rows, row_pos_dev, row_slot_dev, /*publish_hidden=*/false, st));
+  ST_TRY(prefill_rows(s, grid_dev, row_slot_dev, row_pos_dev, n_rows, st));
   return launch_commit_embed(s, /*do_commit=*/0, 0, st);  // the prompt rows went through x3n / ssq: re-publish the decode rows
 }
 
@@ -1121,24 +1129,13 @@ int smoltts_lm_prefill_deferred(SmolttsSession* s, const int32_t* grid_dev, cons
   ST_REQUIRE(s && grid_dev && row_slot_dev && row_pos_dev && slots_host && last_row_host, SMOLTTS_E_INVALID,
              "lm_prefill_deferred: null argument");
   ST_REQUIRE(n_rows > 0 && n_rows <= s->max_rows, SMOLTTS_E_CAPACITY, "lm_prefill_deferred: %d rows, session holds %d", n_rows, s->max_rows);
-  ST_REQUIRE(n_slots > 0 && n_slots <= s->B, SMOLTTS_E_CAPACITY, "lm_prefill_deferred: %d slots, session holds %d", n_slots, s->B);
-  for (int i = 0; i < n_slots; ++i) {
-    ST_REQUIRE(slots_host[i] >= 0 && slots_host[i] < s->B, SMOLTTS_E_INVALID, "lm_prefill_deferred: slot %d out of range", slots_host[i]);
-    ST_REQUIRE(last_row_host[i] >= 0 && last_row_host[i] < n_rows, SMOLTTS_E_INVALID, "lm_prefill_deferred: last_row %d out of range", last_row_host[i]);
-  }
+  ST_TRY(check_slot_lists("lm_prefill_deferred", s, slots_host, last_row_host, n_slots, n_rows));
   hipStream_t st = (hipStream_t)stream;
-  if (s->stop_on_eos != stop_on_eos) drop_graphs(s);  // the flag is baked into the captured commit nodes
-  s->stop_on_eos = stop_on_eos;
+  set_stop_on_eos(s, stop_on_eos);
   ST_TRY(stage_upload(s, slots_host, last_row_host, n_slots, st));
   // KV rows of the whole prompt (the last column's row is recomputed by the first decode frame, identically)
-  ST_TRY(embed_rows(s, grid_dev, n_rows, s->xr, st));
-  ST_TRY(run_slow_layers(s, s->xr, s->qr, n_rows, row_pos_dev, row_slot_dev, /*publish_hidden=*/false, st));
-  hipLaunchKernelGGL(slot_start_kernel, dim3((s->B + 63) / 64), dim3(64), 0, st, s->B, 1 + s->e->cfg.n_fast, n_slots, s->stage_slots,
-                     s->stage_last, row_pos_dev, grid_dev, s->pos, s->frames, s->done, s->margin, s->cur_col, s->salt);
-  ST_CHECK_HIP(hipGetLastError());
-  ST_TRY(launch_commit_embed(s, /*do_commit=*/0, 0, st));  // mask = !done; embed every slot's (new) current column
-  s->prefilled = true;
-  return SMOLTTS_OK;
+  ST_TRY(prefill_rows(s, grid_dev, row_slot_dev, row_pos_dev, n_rows, st));
+  return arm_slots(s, grid_dev, row_pos_dev, n_slots, st);
 }
 
 // ---- prompt prefill beside the decode frames (serving: the refill of a slot no longer stops the other slots' ticks)
@@ -1148,11 +1145,7 @@ int smoltts_lm_prefill_deferred(SmolttsSession* s, const int32_t* grid_dev, cons
 // decode rows write at the parking position T-1 (rewritten by the tenant's first frame) and read garbage nobody keeps.
 int smoltts_lm_park_slots(SmolttsSession* s, const int32_t* slots_host, const int32_t* pos_host, int32_t n_slots, void* stream) {
   ST_REQUIRE(s && slots_host && pos_host, SMOLTTS_E_INVALID, "lm_park_slots: null argument");
-  ST_REQUIRE(n_slots > 0 && n_slots <= s->B, SMOLTTS_E_CAPACITY, "lm_park_slots: %d slots, session holds %d", n_slots, s->B);
-  for (int i = 0; i < n_slots; ++i) {
-    ST_REQUIRE(slots_host[i] >= 0 && slots_host[i] < s->B, SMOLTTS_E_INVALID, "lm_park_slots: slot %d out of range", slots_host[i]);
-    ST_REQUIRE(pos_host[i] >= 0 && pos_host[i] < s->max_seq, SMOLTTS_E_INVALID, "lm_park_slots: position %d outside the cache (%d)", pos_host[i], s->max_seq);
-  }
+  ST_TRY(check_slot_lists("lm_park_slots", s, slots_host, pos_host, n_slots, s->max_seq, /*positions=*/true));
   hipStream_t st = (hipStream_t)stream;
   ST_TRY(stage_upload(s, slots_host, pos_host, n_slots, st));
   hipLaunchKernelGGL(slot_parkpos_kernel, dim3((s->B + 63) / 64), dim3(64), 0, st, s->B, n_slots, s->stage_slots, s->stage_last, s->pos, s->done, s->mask);
@@ -1169,28 +1162,17 @@ int smoltts_lm_prefill_side(SmolttsSession* s, const int32_t* grid_dev, const in
   side.split_attn = false;  // (the key-split attention's records and tickets belong to the frames)
   side.dup_code = -1;
   hipStream_t st = (hipStream_t)stream;
-  ST_TRY(embed_rows(&side, grid_dev, n_rows, side.xr, st));
-  return run_slow_layers(&side, side.xr, side.qr, n_rows, row_pos_dev, row_slot_dev, /*publish_hidden=*/false, st);
+  return prefill_rows(&side, grid_dev, row_slot_dev, row_pos_dev, n_rows, st);
 }
 
 int smoltts_lm_start_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos_dev, const int32_t* slots_host,
                            const int32_t* last_row_host, int32_t n_slots, int32_t stop_on_eos, void* stream) {
   ST_REQUIRE(s && grid_dev && row_pos_dev && slots_host && last_row_host, SMOLTTS_E_INVALID, "lm_start_slots: null argument");
-  ST_REQUIRE(n_slots > 0 && n_slots <= s->B, SMOLTTS_E_CAPACITY, "lm_start_slots: %d slots, session holds %d", n_slots, s->B);
-  for (int i = 0; i < n_slots; ++i) {
-    ST_REQUIRE(slots_host[i] >= 0 && slots_host[i] < s->B, SMOLTTS_E_INVALID, "lm_start_slots: slot %d out of range", slots_host[i]);
-    ST_REQUIRE(last_row_host[i] >= 0 && last_row_host[i] < s->max_rows, SMOLTTS_E_INVALID, "lm_start_slots: last_row %d out of range", last_row_host[i]);
-  }
+  ST_TRY(check_slot_lists("lm_start_slots", s, slots_host, last_row_host, n_slots, s->max_rows));
   hipStream_t st = (hipStream_t)stream;
-  if (s->stop_on_eos != stop_on_eos) drop_graphs(s);  // the flag is baked into the captured commit nodes
-  s->stop_on_eos = stop_on_eos;
+  set_stop_on_eos(s, stop_on_eos);
   ST_TRY(stage_upload(s, slots_host, last_row_host, n_slots, st));
-  hipLaunchKernelGGL(slot_start_kernel, dim3((s->B + 63) / 64), dim3(64), 0, st, s->B, 1 + s->e->cfg.n_fast, n_slots, s->stage_slots,
-                     s->stage_last, row_pos_dev, grid_dev, s->pos, s->frames, s->done, s->margin, s->cur_col, s->salt);
-  ST_CHECK_HIP(hipGetLastError());
-  ST_TRY(launch_commit_embed(s, /*do_commit=*/0, 0, st));  // mask = !done; embed every slot's (new) current column
-  s->prefilled = true;
-  return SMOLTTS_OK;
+  return arm_slots(s, grid_dev, row_pos_dev, n_slots, st);
 }
 
 int smoltts_lm_decode(SmolttsSession* s, int32_t n_frames, void* stream) {
@@ -1268,7 +1250,7 @@ int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_ho
              "session_set_slot_sampling: null argument");
   ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_sampling: %d entries, session holds %d slots", n, s->B);
   for (int i = 0; i < n; ++i) {
-    ST_REQUIRE(slots_host[i] >= 0 && slots_host[i] < s->B, SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d out of range", slots_host[i]);
+    ST_TRY(check_slot("session_set_slot_sampling", slots_host[i], s->B));
     for (int j = 0; j < i; ++j)
       ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d listed twice", slots_host[i]);
     ST_REQUIRE(temp_host[i] == temp_host[i] && fast_temp_host[i] == fast_temp_host[i] && min_p_host[i] >= 0.f && min_p_host[i] < 1.f,

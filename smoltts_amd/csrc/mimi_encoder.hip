@@ -24,7 +24,6 @@ constexpr int RATIO[NSTAGE] = {4, 5, 6, 8};
 constexpr int D = MIMI_D, HEADS = MIMI_HEADS, FF = MIMI_FF, CB_DIM = 256, CB_SIZE = 2048;
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 struct Plan {
   int T[NSTAGE + 1];  // rows entering stage i (T[0] = samples); T[4] = 25 Hz rows
@@ -38,12 +37,8 @@ struct Plan {
 };
 
 void make_plan(Plan& p, int n_samples, int n_layers, bool extra_right, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t n_floats) {
-    float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off = align_up(off + n_floats * sizeof(float));
-    return r;
-  };
+  Carver cv{base, 0};
+  auto take = [&](size_t n_floats) { return cv.take<float>(n_floats); };
   p.T[0] = n_samples;
   for (int i = 0; i < NSTAGE; ++i) {
     const int r = RATIO[i], C = 64 << i;
@@ -69,7 +64,7 @@ void make_plan(Plan& p, int n_samples, int n_layers, bool extra_right, char* bas
   p.dots = take((size_t)p.F * CB_SIZE);
   p.row_pos = reinterpret_cast<int*>(take(T4));
   p.row_slot = reinterpret_cast<int*>(take(T4));
-  p.total = off;
+  p.total = cv.off;
 }
 
 __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expm1f(v); }

@@ -73,20 +73,7 @@ struct SmolttsMimiSession {
 
 namespace {
 
-size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
-struct Carver {
-  char* base;
-  size_t off;
-  template <typename T>
-  T* take(size_t n) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off = align_up(off + n * sizeof(T));
-    return p;
-  }
-};
-
-void carve(SmolttsMimiSession* s, char* base, size_t* total) {
+size_t carve(SmolttsMimiSession* s, char* base) {
   Carver cv{base, 0};
   const size_t B = s->B, F = s->chunk, R = B * 2 * F;
   const SmolttsMimiConfig& c = s->m->cfg;
@@ -117,7 +104,7 @@ void carve(SmolttsMimiSession* s, char* base, size_t* total) {
   s->kv3_layer = F >= 16 ? SMOLTTS_KV3_BYTES(B, HEADS, c.max_positions) : 0;
   s->kc3 = s->kv3_layer ? cv.take<char>(s->kv3_layer * c.n_layers) : nullptr;
   s->vc3 = s->kv3_layer ? cv.take<char>(s->kv3_layer * c.n_layers) : nullptr;
-  *total = cv.off;
+  return cv.off;
 }
 
 // e[b][f] = sum_q table[q][code[b][f][q]]  (rvq.py:118-131,179-186 with output_proj folded in),
@@ -284,9 +271,7 @@ size_t smoltts_mimi_slab_bytes(const SmolttsMimi* m, int32_t max_batch, int32_t 
   memset(&tmp, 0, sizeof(tmp));
   tmp.m = const_cast<SmolttsMimi*>(m);
   tmp.B = max_batch; tmp.chunk = max_chunk_frames;
-  size_t total = 0;
-  carve(&tmp, nullptr, &total);
-  return total;
+  return carve(&tmp, nullptr);
 }
 
 int smoltts_mimi_session_create(SmolttsMimi* m, void* slab_dev, size_t slab_bytes, int32_t max_batch,
@@ -300,8 +285,7 @@ int smoltts_mimi_session_create(SmolttsMimi* m, void* slab_dev, size_t slab_byte
   ST_REQUIRE(s, SMOLTTS_E_INVALID, "mimi_session_create: out of host memory");
   memset(s, 0, sizeof(*s));
   s->m = m; s->B = max_batch; s->chunk = max_chunk_frames;
-  size_t total = 0;
-  carve(s, (char*)slab_dev, &total);
+  carve(s, (char*)slab_dev);
   s->pos_host = static_cast<int*>(calloc((size_t)max_batch, sizeof(int)));
   // (the piece caches are read in whole 32-position blocks: positions not written yet get zero weights and must hold finite values)
   if (s->pos_host == nullptr || hipMemset(s->zero_begin, 0, s->zero_bytes) != hipSuccess ||
@@ -348,7 +332,7 @@ int smoltts_mimi_reset_slots(SmolttsMimiSession* s, const int32_t* slots_host, i
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_slots; ++i) {
     const int b = slots_host[i];
-    ST_REQUIRE(b >= 0 && b < s->B, SMOLTTS_E_INVALID, "mimi_reset_slots: slot %d out of range", b);
+    ST_TRY(check_slot("mimi_reset_slots", b, s->B));
     ST_CHECK_HIP(hipMemsetAsync(s->carry[0] + (size_t)b * D, 0, D * sizeof(float), st));
     ST_CHECK_HIP(hipMemsetAsync(s->carry[1] + (size_t)b * D, 0, D * sizeof(float), st));
     ST_CHECK_HIP(hipMemsetAsync(s->pos_dev + b, 0, sizeof(int), st));

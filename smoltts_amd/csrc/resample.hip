@@ -10,9 +10,9 @@
 // depend on where the chunk boundaries fall.
 #include <math.h>
 
-#include <new>
+#include "stage.h"
 
-#include "common.h"
+using namespace smoltts;
 
 namespace {
 
@@ -107,8 +107,7 @@ __global__ __launch_bounds__(kTile) void resample_kernel(const float* __restrict
   const int64_t N0 = si->n_in, M0 = si->n_out;
   int n = 0;
   if (b < batch && c.enc != SMOLTTS_RESAMPLE_OFF) {
-    n = valid ? valid[b] : n_in;
-    n = n < 0 ? 0 : (n > n_in ? n_in : n);
+    n = valid_count(valid, b, n_in);
   }
   const int64_t N1 = N0 + n;
   const float* x = pcm + (int64_t)(b < batch ? b : 0) * pcm_stride;
@@ -179,7 +178,6 @@ __global__ __launch_bounds__(kTile) void resample_kernel(const float* __restrict
   }
 }
 
-constexpr int kResetMax = 16;
 struct ResetArgs {
   int32_t n;
   int32_t slot[kResetMax];
@@ -200,8 +198,6 @@ __global__ __launch_bounds__(64) void resample_reset_kernel(ResetArgs a, SlotCfg
   }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t taps_count() {
   size_t n = 0;
   for (const RateSpec& s : kSpecs) n += (size_t)s.up * taps_per_phase(s);
@@ -213,14 +209,20 @@ size_t taps_count() {
 struct SmolttsResampler {
   int B;
   SlotCfg* cfg_dev;
-  SlotState* st[2];
+  PingPong<SlotState> st;
   double* taps_dev;
   int tap_off[kRates];
   SlotCfg* cfg_host;  // mirror of cfg_dev (sizes the grid)
-  unsigned parity;    // st[parity] holds the slots' current state
 };
 
-using namespace smoltts;
+// the slab: the constant tap tables, then what create clears (every slot off, every stream empty)
+static size_t carve(SmolttsResampler* r, char* base) {
+  Carver cv{base, 0};
+  r->taps_dev = cv.take<double>(taps_count());
+  r->cfg_dev = cv.take<SlotCfg>(r->B);
+  r->st.carve(cv, r->B);
+  return cv.off;
+}
 
 extern "C" {
 
@@ -240,8 +242,7 @@ int smoltts_resample_design(int32_t out_rate, double* taps, int32_t cap, int32_t
 }
 
 size_t smoltts_resampler_bytes(int32_t max_batch) {
-  if (max_batch <= 0) return 0;
-  return align256(taps_count() * sizeof(double)) + align256(sizeof(SlotCfg) * max_batch) + 2 * align256(sizeof(SlotState) * max_batch);
+  return stage_bytes<SmolttsResampler>(max_batch);
 }
 
 size_t smoltts_resampler_out_bytes(int32_t n_in) {
@@ -255,20 +256,9 @@ size_t smoltts_resampler_out_bytes(int32_t n_in) {
 }
 
 int smoltts_resampler_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsResampler** out) {
-  ST_REQUIRE(slab_dev && out && max_batch > 0, SMOLTTS_E_INVALID, "resampler_create: bad argument");
-  ST_REQUIRE(((uintptr_t)slab_dev & 255) == 0, SMOLTTS_E_INVALID, "resampler_create: slab must be 256-byte aligned");
-  const size_t need = smoltts_resampler_bytes(max_batch);
-  ST_REQUIRE(slab_bytes >= need, SMOLTTS_E_CAPACITY, "resampler_create: slab has %zu bytes, %zu needed", slab_bytes, need);
-  char* p = (char*)slab_dev;
-  const size_t taps_bytes = align256(taps_count() * sizeof(double));
-  SmolttsResampler* r = new (std::nothrow) SmolttsResampler;
-  ST_REQUIRE(r, SMOLTTS_E_INVALID, "resampler_create: out of host memory");
-  r->B = max_batch;
-  r->taps_dev = (double*)p;
-  r->cfg_dev = (SlotCfg*)(p + taps_bytes);
-  r->st[0] = (SlotState*)(p + taps_bytes + align256(sizeof(SlotCfg) * max_batch));
-  r->st[1] = (SlotState*)((char*)r->st[0] + align256(sizeof(SlotState) * max_batch));
-  r->parity = 0;
+  SmolttsResampler* r = nullptr;
+  size_t need = 0;
+  ST_TRY(stage_create("resampler_create", slab_dev, slab_bytes, max_batch, out, &r, &need));
   r->cfg_host = static_cast<SlotCfg*>(calloc((size_t)max_batch, sizeof(SlotCfg)));
   // polyphase tables: phase ph of a rate holds h[ph], h[ph + up], h[ph + 2 up], ... (zero past the filter's end)
   double* host = static_cast<double*>(calloc(taps_count(), sizeof(double)));
@@ -291,7 +281,7 @@ int smoltts_resampler_create(void* slab_dev, size_t slab_bytes, int32_t max_batc
     off += (size_t)s.up * L;
   }
   const bool ok = hipMemcpy(r->taps_dev, host, taps_count() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemset(r->cfg_dev, 0, need - taps_bytes) == hipSuccess;  // every slot off, every stream empty
+                  hipMemset(r->cfg_dev, 0, need - ((char*)r->cfg_dev - (char*)slab_dev)) == hipSuccess;  // every slot off, every stream empty
   free(host);
   free(h);
   if (!ok) {
@@ -313,43 +303,33 @@ void smoltts_resampler_destroy(SmolttsResampler* r) {
 int smoltts_resampler_reset_slots(SmolttsResampler* r, const int32_t* slots_host, const int32_t* out_rates_host,
                                   const int32_t* encodings_host, int32_t n_slots, void* stream) {
   ST_REQUIRE(r && slots_host && out_rates_host && encodings_host && n_slots > 0, SMOLTTS_E_INVALID, "resampler_reset_slots: bad argument");
-  for (int i0 = 0; i0 < n_slots; i0 += kResetMax) {
-    ResetArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = n_slots - i0 < kResetMax ? n_slots - i0 : kResetMax;
-    for (int i = 0; i < a.n; ++i) {
-      const int b = slots_host[i0 + i], enc = encodings_host[i0 + i], rate = out_rates_host[i0 + i];
-      ST_REQUIRE(b >= 0 && b < r->B, SMOLTTS_E_INVALID, "resampler_reset_slots: slot %d out of range", b);
-      ST_REQUIRE(enc == SMOLTTS_RESAMPLE_OFF || enc == SMOLTTS_RESAMPLE_S16 || enc == SMOLTTS_RESAMPLE_ULAW, SMOLTTS_E_INVALID,
-                 "resampler_reset_slots: unknown encoding %d", enc);
-      SlotCfg c;
-      memset(&c, 0, sizeof(c));
-      c.enc = enc;
-      if (enc != SMOLTTS_RESAMPLE_OFF) {
-        const int k = spec_index(rate);
-        ST_REQUIRE(k >= 0, SMOLTTS_E_INVALID, "resampler_reset_slots: unsupported output rate %d", rate);
-        ST_REQUIRE(enc != SMOLTTS_RESAMPLE_ULAW || rate == 8000, SMOLTTS_E_INVALID, "resampler_reset_slots: mu-law is 8 kHz only");
-        c.up = kSpecs[k].up;
-        c.down = kSpecs[k].down;
-        c.half_len = half_len_of(kSpecs[k]);
-        c.tap_off = r->tap_off[k];
-        c.taps_per_phase = taps_per_phase(kSpecs[k]);
-      }
-      a.slot[i] = b;
-      a.cfg[i] = c;
+  auto fill = [&](ResetArgs& a, int i, int k) -> int {
+    const int enc = encodings_host[k], rate = out_rates_host[k];
+    ST_REQUIRE(enc == SMOLTTS_RESAMPLE_OFF || enc == SMOLTTS_RESAMPLE_S16 || enc == SMOLTTS_RESAMPLE_ULAW, SMOLTTS_E_INVALID,
+               "resampler_reset_slots: unknown encoding %d", enc);
+    SlotCfg& c = a.cfg[i];  // (zeroed)
+    c.enc = enc;
+    if (enc != SMOLTTS_RESAMPLE_OFF) {
+      const int s = spec_index(rate);
+      ST_REQUIRE(s >= 0, SMOLTTS_E_INVALID, "resampler_reset_slots: unsupported output rate %d", rate);
+      ST_REQUIRE(enc != SMOLTTS_RESAMPLE_ULAW || rate == 8000, SMOLTTS_E_INVALID, "resampler_reset_slots: mu-law is 8 kHz only");
+      c.up = kSpecs[s].up;
+      c.down = kSpecs[s].down;
+      c.half_len = half_len_of(kSpecs[s]);
+      c.tap_off = r->tap_off[s];
+      c.taps_per_phase = taps_per_phase(kSpecs[s]);
     }
+    return SMOLTTS_OK;
+  };
+  return reset_in_groups<ResetArgs>("resampler_reset_slots", r->B, slots_host, n_slots, fill, [&](const ResetArgs& a) {
     for (int i = 0; i < a.n; ++i) r->cfg_host[a.slot[i]] = a.cfg[i];
-    hipLaunchKernelGGL(resample_reset_kernel, dim3(a.n), dim3(kHist), 0, (hipStream_t)stream, a, r->cfg_dev, r->st[0], r->st[1]);
-    ST_CHECK_HIP(hipGetLastError());
-  }
-  return SMOLTTS_OK;
+    hipLaunchKernelGGL(resample_reset_kernel, dim3(a.n), dim3(kHist), 0, (hipStream_t)stream, a, r->cfg_dev, r->st.half[0], r->st.half[1]);
+  });
 }
 
 int smoltts_resample_chunk(SmolttsResampler* r, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
                            const int32_t* valid_in_dev, void* out_dev, int64_t out_stride, int32_t* counts_dev, void* stream) {
-  ST_REQUIRE(r && pcm_dev && out_dev && counts_dev, SMOLTTS_E_INVALID, "resample_chunk: null argument");
-  ST_REQUIRE(batch > 0 && batch <= r->B, SMOLTTS_E_INVALID, "resample_chunk: batch %d (1..%d)", batch, r->B);
-  ST_REQUIRE(n_in >= 0 && pcm_stride >= n_in, SMOLTTS_E_INVALID, "resample_chunk: n_in %d, pcm_stride %lld", n_in, (long long)pcm_stride);
+  ST_TRY(check_chunk("resample_chunk", r, pcm_dev && out_dev && counts_dev, batch, true, n_in, pcm_stride));
   // the grid covers the most outputs any listed slot can emit in this call, at its own rate and encoding
   int64_t most = 0, row = 0;
   for (int b = 0; b < batch; ++b) {
@@ -362,11 +342,10 @@ int smoltts_resample_chunk(SmolttsResampler* r, const float* pcm_dev, int64_t pc
   }
   ST_REQUIRE(out_stride >= row, SMOLTTS_E_CAPACITY, "resample_chunk: out_stride %lld < %lld bytes", (long long)out_stride, (long long)row);
   const int tiles = most > 0 ? (int)((most + kTile - 1) / kTile) : 1;
-  const unsigned p = r->parity;
   hipLaunchKernelGGL(resample_kernel, dim3(tiles, r->B), dim3(kTile), 0, (hipStream_t)stream, pcm_dev, pcm_stride, batch, n_in,
-                     valid_in_dev, r->cfg_dev, r->taps_dev, r->st[p], r->st[p ^ 1], (uint8_t*)out_dev, out_stride, counts_dev);
+                     valid_in_dev, r->cfg_dev, r->taps_dev, r->st.cur(), r->st.next(), (uint8_t*)out_dev, out_stride, counts_dev);
   ST_CHECK_HIP(hipGetLastError());
-  r->parity = p ^ 1;
+  r->st.flip();
   return SMOLTTS_OK;
 }
 

@@ -7,9 +7,9 @@
 // unchanged in front of a non-silent block, and at the segment's end replaces the held run of r samples by its first min(r, G)
 // samples and G - min(r, G) zeros.  So one call's output is always zeros(lead) ++ segment[e0, ec) ++ zeros(z1): the state is
 // three positions (judged, ec, n_in) and the samples [ec, n_in) that are still held or undecided.
-#include <new>
+#include "stage.h"
 
-#include "common.h"
+using namespace smoltts;
 
 namespace {
 
@@ -152,7 +152,6 @@ __global__ __launch_bounds__(kThreads) void seam_kernel(const float* __restrict_
   }
 }
 
-constexpr int kResetMax = 16;
 struct ResetArgs {
   int32_t n;
   int32_t slot[kResetMax];
@@ -177,23 +176,23 @@ __global__ void seam_reset_kernel(ResetArgs a, SeamState* st0, SeamState* st1) {
   }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 struct SmolttsSeam {
   int B;
-  SeamState* st[2];
-  unsigned parity;  // st[parity] holds the slots' current state
+  PingPong<SeamState> st;
 };
 
-using namespace smoltts;
+static size_t carve(SmolttsSeam* r, char* base) {
+  Carver cv{base, 0};
+  r->st.carve(cv, r->B);
+  return cv.off;
+}
 
 extern "C" {
 
 size_t smoltts_seam_bytes(int32_t max_batch) {
-  if (max_batch <= 0) return 0;
-  return 2 * align256(sizeof(SeamState) * max_batch);
+  return stage_bytes<SmolttsSeam>(max_batch);
 }
 
 size_t smoltts_seam_out_samples(int32_t n_in, int32_t max_zeros) {
@@ -203,16 +202,9 @@ size_t smoltts_seam_out_samples(int32_t n_in, int32_t max_zeros) {
 }
 
 int smoltts_seam_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsSeam** out) {
-  ST_REQUIRE(slab_dev && out && max_batch > 0, SMOLTTS_E_INVALID, "seam_create: bad argument");
-  ST_REQUIRE(((uintptr_t)slab_dev & 255) == 0, SMOLTTS_E_INVALID, "seam_create: slab must be 256-byte aligned");
-  const size_t need = smoltts_seam_bytes(max_batch);
-  ST_REQUIRE(slab_bytes >= need, SMOLTTS_E_CAPACITY, "seam_create: slab has %zu bytes, %zu needed", slab_bytes, need);
-  SmolttsSeam* r = new (std::nothrow) SmolttsSeam;
-  ST_REQUIRE(r, SMOLTTS_E_INVALID, "seam_create: out of host memory");
-  r->B = max_batch;
-  r->st[0] = (SeamState*)slab_dev;
-  r->st[1] = (SeamState*)((char*)slab_dev + align256(sizeof(SeamState) * max_batch));
-  r->parity = 0;
+  SmolttsSeam* r = nullptr;
+  size_t need = 0;
+  ST_TRY(stage_create("seam_create", slab_dev, slab_bytes, max_batch, out, &r, &need));
   if (hipMemset(slab_dev, 0, need) != hipSuccess) {  // every slot off
     delete r;
     set_error("seam_create: hipMemset failed");
@@ -229,48 +221,39 @@ void smoltts_seam_destroy(SmolttsSeam* r) {
 int smoltts_seam_reset_slots(SmolttsSeam* r, const int32_t* slots_host, const int32_t* pause_host, const int32_t* flags_host,
                              const int32_t* lead_host, int32_t n_slots, void* stream) {
   ST_REQUIRE(r && slots_host && pause_host && flags_host && n_slots > 0, SMOLTTS_E_INVALID, "seam_reset_slots: bad argument");
-  for (int i0 = 0; i0 < n_slots; i0 += kResetMax) {
-    ResetArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = n_slots - i0 < kResetMax ? n_slots - i0 : kResetMax;
-    for (int i = 0; i < a.n; ++i) {
-      const int b = slots_host[i0 + i], p = pause_host[i0 + i], f = flags_host[i0 + i], ld = lead_host ? lead_host[i0 + i] : 0;
-      ST_REQUIRE(b >= 0 && b < r->B, SMOLTTS_E_INVALID, "seam_reset_slots: slot %d out of range", b);
-      ST_REQUIRE(p >= 0 && p <= kMaxPause && ld >= 0 && ld <= kMaxPause, SMOLTTS_E_INVALID,
-                 "seam_reset_slots: pause %d / lead %d outside [0, %d]", p, ld, kMaxPause);
-      ST_REQUIRE((f & ~(SMOLTTS_SEAM_FIRST | SMOLTTS_SEAM_FINAL | SMOLTTS_SEAM_OFF)) == 0, SMOLTTS_E_INVALID,
-                 "seam_reset_slots: bad flags %d", f);
-      a.slot[i] = b;
-      a.pause[i] = p;
-      a.flags[i] = f;
-      a.lead[i] = ld;
-    }
-    hipLaunchKernelGGL(seam_reset_kernel, dim3(a.n), dim3(64), 0, (hipStream_t)stream, a, r->st[0], r->st[1]);
-    ST_CHECK_HIP(hipGetLastError());
-  }
-  return SMOLTTS_OK;
+  auto fill = [&](ResetArgs& a, int i, int k) -> int {
+    const int p = pause_host[k], f = flags_host[k], ld = lead_host ? lead_host[k] : 0;
+    ST_REQUIRE(p >= 0 && p <= kMaxPause && ld >= 0 && ld <= kMaxPause, SMOLTTS_E_INVALID,
+               "seam_reset_slots: pause %d / lead %d outside [0, %d]", p, ld, kMaxPause);
+    ST_REQUIRE((f & ~(SMOLTTS_SEAM_FIRST | SMOLTTS_SEAM_FINAL | SMOLTTS_SEAM_OFF)) == 0, SMOLTTS_E_INVALID,
+               "seam_reset_slots: bad flags %d", f);
+    a.pause[i] = p;
+    a.flags[i] = f;
+    a.lead[i] = ld;
+    return SMOLTTS_OK;
+  };
+  return reset_in_groups<ResetArgs>("seam_reset_slots", r->B, slots_host, n_slots, fill, [&](const ResetArgs& a) {
+    hipLaunchKernelGGL(seam_reset_kernel, dim3(a.n), dim3(64), 0, (hipStream_t)stream, a, r->st.half[0], r->st.half[1]);
+  });
 }
 
 int smoltts_seam_chunk(SmolttsSeam* r, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
                        const int32_t* valid_in_dev, const int32_t* seg_end_dev, const int32_t* last_dev, int32_t max_zeros,
                        float* out_dev, int64_t out_stride, int32_t* counts_dev, void* stream) {
-  ST_REQUIRE(r && pcm_dev && out_dev && counts_dev, SMOLTTS_E_INVALID, "seam_chunk: null argument");
-  ST_REQUIRE(batch > 0 && batch <= r->B, SMOLTTS_E_INVALID, "seam_chunk: batch %d (1..%d)", batch, r->B);
-  ST_REQUIRE(n_in >= 0 && pcm_stride >= n_in, SMOLTTS_E_INVALID, "seam_chunk: n_in %d, pcm_stride %lld", n_in, (long long)pcm_stride);
+  ST_TRY(check_chunk("seam_chunk", r, pcm_dev && out_dev && counts_dev, batch, true, n_in, pcm_stride));
   ST_REQUIRE(max_zeros >= 0 && max_zeros <= 2 * kMaxPause, SMOLTTS_E_INVALID, "seam_chunk: max_zeros %d", max_zeros);
   const int64_t need = (int64_t)smoltts_seam_out_samples(n_in, max_zeros);
   ST_REQUIRE(out_stride >= need, SMOLTTS_E_CAPACITY, "seam_chunk: out_stride %lld < %lld samples", (long long)out_stride, (long long)need);
-  const unsigned p = r->parity;
   hipLaunchKernelGGL(seam_kernel, dim3(r->B), dim3(kThreads), 0, (hipStream_t)stream, pcm_dev, pcm_stride, batch, n_in,
-                     valid_in_dev, seg_end_dev, last_dev, r->st[p], r->st[p ^ 1], out_dev, out_stride, counts_dev);
+                     valid_in_dev, seg_end_dev, last_dev, r->st.cur(), r->st.next(), out_dev, out_stride, counts_dev);
   ST_CHECK_HIP(hipGetLastError());
-  r->parity = p ^ 1;
+  r->st.flip();
   return SMOLTTS_OK;
 }
 
 int smoltts_seam_slot_state(SmolttsSeam* r, int32_t slot, int64_t* state_host, void* stream) {
   ST_REQUIRE(r && state_host && slot >= 0 && slot < r->B, SMOLTTS_E_INVALID, "seam_slot_state: bad argument");
-  const SeamState* s = r->st[r->parity] + slot;
+  const SeamState* s = r->st.cur() + slot;
   int64_t v[3];
   int32_t w[5];
   ST_CHECK_HIP(hipMemcpyAsync(v, &s->n_in, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));

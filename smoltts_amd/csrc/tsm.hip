@@ -8,9 +8,9 @@
 // then ola[n] = w[n + L] x[p_k + L + n].  p_{-1} = -L (the first L outputs are (w[n] + w[n + L]) x[n]), p_0 = 0.
 // Segment k is computed once the input holds a_k + kDelta + W samples and (k + 1) L <= ceil(N 65536 / speed_q); a flush (last)
 // reads zeros past the end N and computes segments while k L < M = ceil(N 65536 / speed_q), cutting the output at M.
-#include <new>
+#include "stage.h"
 
-#include "common.h"
+using namespace smoltts;
 
 namespace {
 
@@ -76,8 +76,7 @@ __global__ __launch_bounds__(kThreads) void tsm_kernel(const float* __restrict__
     }
     return;
   }
-  int n = valid ? valid[b] : n_in;
-  n = n < 0 ? 0 : (n > n_in ? n_in : n);
+  const int n = valid_count(valid, b, n_in);
   const int fl = last ? (last[b] != 0) : 0;
   const int64_t N0 = si->n_in, N1 = N0 + n;
   const int64_t mcap = (N1 * kQOne + sq - 1) / sq;  // M of the input so far
@@ -169,7 +168,6 @@ __global__ __launch_bounds__(kThreads) void tsm_kernel(const float* __restrict__
   }
 }
 
-constexpr int kResetMax = 16;
 struct ResetArgs {
   int32_t n;
   int32_t slot[kResetMax];
@@ -192,25 +190,28 @@ __global__ __launch_bounds__(kThreads) void tsm_reset_kernel(ResetArgs a, int32_
   }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 struct SmolttsTsm {
   int B;
   float* win_dev;
   int32_t* cfg_dev;
-  TsmState* st[2];
-  unsigned parity;    // st[parity] holds the slots' current state
+  PingPong<TsmState> st;
 };
 
-using namespace smoltts;
+// the slab: the constant window, then what create clears (every slot off)
+static size_t carve(SmolttsTsm* r, char* base) {
+  Carver cv{base, 0};
+  r->win_dev = cv.take<float>(W);
+  r->cfg_dev = cv.take<int32_t>(r->B);
+  r->st.carve(cv, r->B);
+  return cv.off;
+}
 
 extern "C" {
 
 size_t smoltts_tsm_bytes(int32_t max_batch) {
-  if (max_batch <= 0) return 0;
-  return align256(sizeof(float) * W) + align256(sizeof(int32_t) * max_batch) + 2 * align256(sizeof(TsmState) * max_batch);
+  return stage_bytes<SmolttsTsm>(max_batch);
 }
 
 size_t smoltts_tsm_out_samples(int32_t n_in) {
@@ -221,24 +222,13 @@ size_t smoltts_tsm_out_samples(int32_t n_in) {
 }
 
 int smoltts_tsm_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsTsm** out) {
-  ST_REQUIRE(slab_dev && out && max_batch > 0, SMOLTTS_E_INVALID, "tsm_create: bad argument");
-  ST_REQUIRE(((uintptr_t)slab_dev & 255) == 0, SMOLTTS_E_INVALID, "tsm_create: slab must be 256-byte aligned");
-  const size_t need = smoltts_tsm_bytes(max_batch);
-  ST_REQUIRE(slab_bytes >= need, SMOLTTS_E_CAPACITY, "tsm_create: slab has %zu bytes, %zu needed", slab_bytes, need);
-  char* p = (char*)slab_dev;
-  const size_t win_bytes = align256(sizeof(float) * W);
-  SmolttsTsm* r = new (std::nothrow) SmolttsTsm;
-  ST_REQUIRE(r, SMOLTTS_E_INVALID, "tsm_create: out of host memory");
-  r->B = max_batch;
-  r->win_dev = (float*)p;
-  r->cfg_dev = (int32_t*)(p + win_bytes);
-  r->st[0] = (TsmState*)(p + win_bytes + align256(sizeof(int32_t) * max_batch));
-  r->st[1] = (TsmState*)((char*)r->st[0] + align256(sizeof(TsmState) * max_batch));
-  r->parity = 0;
+  SmolttsTsm* r = nullptr;
+  size_t need = 0;
+  ST_TRY(stage_create("tsm_create", slab_dev, slab_bytes, max_batch, out, &r, &need));
   float w[W];
   for (int n = 0; n < W; ++n) w[n] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)n / (double)W));  // periodic Hann, fp64 -> fp32
   const bool ok = hipMemcpy(r->win_dev, w, sizeof(w), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemset(r->cfg_dev, 0, need - win_bytes) == hipSuccess;  // every slot off
+                  hipMemset(r->cfg_dev, 0, need - ((char*)r->cfg_dev - (char*)slab_dev)) == hipSuccess;  // every slot off
   if (!ok) {
     delete r;
     set_error("tsm_create: hipMemcpy / hipMemset failed");
@@ -254,43 +244,34 @@ void smoltts_tsm_destroy(SmolttsTsm* r) {
 
 int smoltts_tsm_reset_slots(SmolttsTsm* r, const int32_t* slots_host, const int32_t* speed_q_host, int32_t n_slots, void* stream) {
   ST_REQUIRE(r && slots_host && speed_q_host && n_slots > 0, SMOLTTS_E_INVALID, "tsm_reset_slots: bad argument");
-  for (int i0 = 0; i0 < n_slots; i0 += kResetMax) {
-    ResetArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = n_slots - i0 < kResetMax ? n_slots - i0 : kResetMax;
-    for (int i = 0; i < a.n; ++i) {
-      const int b = slots_host[i0 + i], sq = speed_q_host[i0 + i];
-      ST_REQUIRE(b >= 0 && b < r->B, SMOLTTS_E_INVALID, "tsm_reset_slots: slot %d out of range", b);
-      ST_REQUIRE(sq == kQOne || (sq >= 16384 && sq <= 262144), SMOLTTS_E_INVALID,
-                 "tsm_reset_slots: speed_q %d outside [16384, 262144]", sq);
-      a.slot[i] = b;
-      a.sq[i] = sq == kQOne ? 0 : sq;  // speed 1: the slot is off
-    }
-    hipLaunchKernelGGL(tsm_reset_kernel, dim3(a.n), dim3(kThreads), 0, (hipStream_t)stream, a, r->cfg_dev, r->st[0], r->st[1]);
-    ST_CHECK_HIP(hipGetLastError());
-  }
-  return SMOLTTS_OK;
+  auto fill = [&](ResetArgs& a, int i, int k) -> int {
+    const int sq = speed_q_host[k];
+    ST_REQUIRE(sq == kQOne || (sq >= 16384 && sq <= 262144), SMOLTTS_E_INVALID,
+               "tsm_reset_slots: speed_q %d outside [16384, 262144]", sq);
+    a.sq[i] = sq == kQOne ? 0 : sq;  // speed 1: the slot is off
+    return SMOLTTS_OK;
+  };
+  return reset_in_groups<ResetArgs>("tsm_reset_slots", r->B, slots_host, n_slots, fill, [&](const ResetArgs& a) {
+    hipLaunchKernelGGL(tsm_reset_kernel, dim3(a.n), dim3(kThreads), 0, (hipStream_t)stream, a, r->cfg_dev, r->st.half[0], r->st.half[1]);
+  });
 }
 
 int smoltts_tsm_chunk(SmolttsTsm* r, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
                       const int32_t* valid_in_dev, const int32_t* last_dev, float* out_dev, int64_t out_stride,
                       int32_t* counts_dev, void* stream) {
-  ST_REQUIRE(r && pcm_dev && out_dev && counts_dev, SMOLTTS_E_INVALID, "tsm_chunk: null argument");
-  ST_REQUIRE(batch > 0 && batch <= r->B, SMOLTTS_E_INVALID, "tsm_chunk: batch %d (1..%d)", batch, r->B);
-  ST_REQUIRE(n_in >= 0 && pcm_stride >= n_in, SMOLTTS_E_INVALID, "tsm_chunk: n_in %d, pcm_stride %lld", n_in, (long long)pcm_stride);
+  ST_TRY(check_chunk("tsm_chunk", r, pcm_dev && out_dev && counts_dev, batch, true, n_in, pcm_stride));
   const int64_t need = (int64_t)smoltts_tsm_out_samples(n_in);
   ST_REQUIRE(out_stride >= need, SMOLTTS_E_CAPACITY, "tsm_chunk: out_stride %lld < %lld samples", (long long)out_stride, (long long)need);
-  const unsigned p = r->parity;
   hipLaunchKernelGGL(tsm_kernel, dim3(r->B), dim3(kThreads), 0, (hipStream_t)stream, pcm_dev, pcm_stride, batch, n_in, valid_in_dev,
-                     last_dev, r->cfg_dev, r->win_dev, r->st[p], r->st[p ^ 1], out_dev, out_stride, counts_dev);
+                     last_dev, r->cfg_dev, r->win_dev, r->st.cur(), r->st.next(), out_dev, out_stride, counts_dev);
   ST_CHECK_HIP(hipGetLastError());
-  r->parity = p ^ 1;
+  r->st.flip();
   return SMOLTTS_OK;
 }
 
 int smoltts_tsm_slot_state(SmolttsTsm* r, int32_t slot, int64_t* state_host, void* stream) {
   ST_REQUIRE(r && state_host && slot >= 0 && slot < r->B, SMOLTTS_E_INVALID, "tsm_slot_state: bad argument");
-  const TsmState* s = r->st[r->parity] + slot;
+  const TsmState* s = r->st.cur() + slot;
   int64_t v[4];
   int32_t ended = 0;
   ST_CHECK_HIP(hipMemcpyAsync(v, &s->k, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
