@@ -621,6 +621,48 @@ int smoltts_seam_chunk(SmolttsSeam* s, const float* pcm_dev, int64_t pcm_stride,
 /* Tests and tools: slot's state (n_in, judged, ec, head, open, lead, pause, flags) into state_host[8]; synchronises the stream. */
 int smoltts_seam_slot_state(SmolttsSeam* s, int32_t slot, int64_t* state_host, void* stream);
 
+/* ------------------------------------------------------------------------------ Loudness
+ * Per-slot loudness normalisation of the codec's 24 kHz fp32 PCM by the ITU-R BS.1770-4 meter (smoltts_amd/csrc/loudness.hip,
+ * DESIGN.md section 14; the numpy model, reproduced bit for bit, is smoltts_amd/loudness.py).  A stream's gain is piecewise
+ * linear between knots at 2400-sample hop boundaries, on a grid of 1/64 dB within +-20 dB; both knots of a hop are fixed from
+ * the samples in front of it, so a slot emits exactly the samples it reads.  The output does not depend on how a stream is cut
+ * into calls. */
+typedef struct SmolttsLoudness SmolttsLoudness;
+
+/* Device slab of a loudness stage for max_batch slots (256-byte aligned, caller-owned): two copies of each slot's state and the
+ * stage's tables.  tables_host: smoltts_loudness_table_doubles() doubles (loudness.Tables.packed: the filters' coefficients, the
+ * 240-step transition matrix, the absolute gate, the ceiling, the knots' gains and their squares); the device computes no
+ * power or logarithm.  Every slot starts off; create clears the slab and uploads the tables synchronously. */
+size_t smoltts_loudness_bytes(int32_t max_batch);
+int32_t smoltts_loudness_table_doubles(void);
+int smoltts_loudness_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, const double* tables_host, int32_t n_tables,
+                            SmolttsLoudness** out);
+void smoltts_loudness_destroy(SmolttsLoudness* s);
+
+/* Start a new stream in each listed slot (host arrays): its target as the mean square that reads the target loudness (0 switches
+ * the slot off; at most 1) and its first knot in 1/64 dB (-1280..1280; start_knot_host may be NULL: 0).  The other slots
+ * continue.  Stream-ordered. */
+int smoltts_loudness_reset_slots(SmolttsLoudness* s, const int32_t* slots_host, const double* target_power_host,
+                                 const int32_t* start_knot_host, int32_t n_slots, void* stream);
+
+/* One launch for slots [0, batch): slot b consumes valid_in_dev[b] (clamped to [0, n_in]; NULL = n_in) samples of pcm_dev float
+ * [batch][pcm_stride] and writes as many to out_dev float [batch][out_stride] (out_stride >= n_in), their number to
+ * counts_dev[b]; slots that are off write 0.  Calls on one stage must be ordered on one stream. */
+int smoltts_loudness_chunk(SmolttsLoudness* s, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
+                           const int32_t* valid_in_dev, float* out_dev, int64_t out_stride, int32_t* counts_dev, void* stream);
+
+/* A whole utterance of n samples measured in one launch (no slot involved): every complete hop's energy to hops_dev (room for
+ * hops_len >= n / 2400 doubles), and result_dev[4] = {gated mean power, 0 when no block passes the absolute gate or n < 9600;
+ * max |x|; blocks past the absolute gate; blocks past both gates}.  smoltts_loudness_scale: out = float(x * gain). */
+int smoltts_loudness_measure(SmolttsLoudness* s, const float* pcm_dev, int32_t n, double* hops_dev, int64_t hops_len,
+                             double* result_dev, void* stream);
+int smoltts_loudness_scale(const float* pcm_dev, int64_t n, double gain, float* out_dev, void* stream);
+
+/* Tests and tools: slot's state; ints_host[4] = pos, the open hop's two knots, on; values_host[531] = the filter's three states
+ * (start, running, zero-state pass), the open sub-block's and hop's energies, the last three hop energies, the peak, the target
+ * power, the ring of 512 block powers.  Synchronises the stream. */
+int smoltts_loudness_slot_state(SmolttsLoudness* s, int32_t slot, int64_t* ints_host, double* values_host, void* stream);
+
 /* --------------------------------------------------------------- operator-level test entry points */
 enum {  /* prologue applied to the activation operand */
   SMOLTTS_PRO_NONE = 0,

@@ -60,6 +60,7 @@ class SmolTTS:
         self.last_sampling = None  # resolved RequestSampling list of the last call that was given sampling= (seeds included)
         self._seam = None  # engine.SeamJoiner of the blocking segmented calls (made on first use)
         self.last_segments: list = []  # per segment of the last segmented call: text, prompt, codes, seed
+        self.last_loudness_gain_db = None  # gain of the last call that was given loudness=
         self.last_stats: dict = {}  # timing of the last generate_codes / __call__ (BatchGenerator.stats + codec_ms)
 
     # -- prompt (``_get_prompt``, __init__.py:120-151)
@@ -157,16 +158,19 @@ class SmolTTS:
         return pcm
 
     def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None,
-                 speed: Optional[float] = None, segment=False):
+                 speed: Optional[float] = None, segment=False, loudness: Optional[float] = None):
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
         (per-request temperature / min_p / seed, as in ``generate_codes``).  ``speed`` (0.25 to 4.0; None / 1.0: unchanged):
         the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
         ``segment`` (True, a dict or a ``longform.SegmentOptions``): a long text is spoken as chained segments (``longform``),
         one after another, each decoded as its own utterance and joined on the GPU (``seam``) before the stretch; a text that is
-        one segment without break tags takes the plain path.  ``last_segments`` then lists each segment's text, seed and codes."""
+        one segment without break tags takes the plain path.  ``last_segments`` then lists each segment's text, seed and codes.
+        ``loudness`` (a target in LUFS, -40 to -5; None: the level is left alone): the utterance's BS.1770-4 integrated loudness
+        is measured on the GPU and one gain brings it to the target, capped where its peak would pass -1 dBFS (``loudness.py``),
+        behind the seam join and in front of the stretch; ``last_loudness_gain_db`` is the gain applied."""
         from .request import parse_request
 
-        req = parse_request(input, speed=speed, segment=segment)  # a bad request is refused before any work
+        req = parse_request(input, speed=speed, segment=segment, loudness=loudness)  # a bad request is refused before any work
         voice = voice if voice is not None else "heart"
         if req.plan is not None:
             pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling)
@@ -174,6 +178,12 @@ class SmolTTS:
             codes = self.generate_codes([input], [voice], generation_settings, speakers=None if speaker is None else [speaker],
                                         sampling=sampling)[0]
             pcm = self.decode_codes(codes)
+        if req.loudness is not None:
+            from .engine import loudness_normalize
+            from .loudness import gain_db
+
+            pcm, g = loudness_normalize(pcm, req.loudness, self.lm.device, with_gain=True)
+            self.last_loudness_gain_db = gain_db(g)
         if req.speed_q is None:
             return pcm
         from .engine import stretch_pcm
@@ -213,7 +223,8 @@ class SmolTTS:
 
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
                reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None,
-               speed: Optional[float] = None, container: Optional[str] = None, segment=False) -> Iterator["np.ndarray"]:
+               speed: Optional[float] = None, container: Optional[str] = None, segment=False,
+               loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -232,14 +243,18 @@ class SmolTTS:
         ``pcm_24000`` quantised as rint(clip(x, -1, 1) * 32767)) as FLAC on the GPU: uint8 chunks, the stream header in front of
         the first, which decode to exactly those samples (flac.py).
         ``segment`` (as in ``__call__``): a long text streams segment after segment in slot 0, each one's codec output through
-        the seam stage in front of the stream's other stages, which run on across the segments: one stream (one FLAC header)."""
+        the seam stage in front of the stream's other stages, which run on across the segments: one stream (one FLAC header).
+        ``loudness`` (as in ``__call__``): the stream is levelled causally on the GPU behind the seam and in front of the
+        stretch, by a gain that moves towards the target at 5 dB/s at most, from ``loudness_start_gain_db`` (default 0); every
+        frame's samples still leave with the frame (``loudness.StreamState``)."""
         import numpy as np
 
         from .engine import MimiSession
         from .generate import resolve_sampling, stream_pcm
         from .request import parse_request
 
-        req = parse_request(input, stream=True, output_format=output_format, speed=speed, container=container, segment=segment)
+        req = parse_request(input, stream=True, output_format=output_format, speed=speed, container=container, segment=segment,
+                            loudness=loudness, loudness_start_gain_db=loudness_start_gain_db)
         voice = voice if voice is not None else "0"
         if req.plan is not None:
             yield from self._stream_segmented(req, voice, generation_settings, overlap, reference_upsample, sampling)
@@ -253,7 +268,8 @@ class SmolTTS:
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
             yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=req.output_format,
-                                  speed_q=req.speed_q, container=req.container)
+                                  speed_q=req.speed_q, container=req.container, loudness=req.loudness,
+                                  start_gain_db=req.start_gain_db)
         finally:
             msess.close()
             sess.close()
@@ -326,7 +342,7 @@ class SmolTTS:
         conv = StreamConverter(dev, 1, 1920, seam=True)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
-            conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container])
+            conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container], [req.loudness], [req.start_gain_db])
             for k, seg, st_k, samp_k in self._segments(plan, voice, None, generation_settings, sampling):
                 final = k == len(plan.segs) - 1
                 sess = self._stream_session(seg["prompt"], st_k, samp_k)

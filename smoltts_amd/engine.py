@@ -127,6 +127,9 @@ _EXPORTS = [
     "smoltts_flac_reset_slots", "smoltts_flac_chunk",
     "smoltts_seam_bytes", "smoltts_seam_create", "smoltts_seam_destroy", "smoltts_seam_out_samples", "smoltts_seam_reset_slots",
     "smoltts_seam_chunk", "smoltts_seam_slot_state",
+    "smoltts_loudness_bytes", "smoltts_loudness_table_doubles", "smoltts_loudness_create", "smoltts_loudness_destroy",
+    "smoltts_loudness_reset_slots", "smoltts_loudness_chunk", "smoltts_loudness_measure", "smoltts_loudness_scale",
+    "smoltts_loudness_slot_state",
     "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows",
     "smoltts_prefix_kv_bytes", "smoltts_session_save_prefix", "smoltts_session_install_prefix",
 ]
@@ -251,6 +254,18 @@ def load_library(path: Optional[Path] = None):
     lib.smoltts_seam_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.smoltts_seam_slot_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.smoltts_loudness_bytes.argtypes = [C.c_int32]
+    lib.smoltts_loudness_bytes.restype = C.c_size_t
+    lib.smoltts_loudness_table_doubles.argtypes = []
+    lib.smoltts_loudness_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.smoltts_loudness_destroy.argtypes = [C.c_void_p]
+    lib.smoltts_loudness_destroy.restype = None
+    lib.smoltts_loudness_reset_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.smoltts_loudness_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_void_p]
+    lib.smoltts_loudness_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.smoltts_loudness_scale.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]
+    lib.smoltts_loudness_slot_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.smoltts_flac_bytes.argtypes = [C.c_int32]
     lib.smoltts_flac_bytes.restype = C.c_size_t
     lib.smoltts_flac_max_blocks.argtypes = [C.c_int32]
@@ -987,9 +1002,13 @@ class _Stage:
             raise SmolttsError(f"smoltts_{self.C_NAME}_bytes returned 0 (bad sizes)")
         self.slab = _alloc_slab(need, device, settle=True)
         h = C.c_void_p()
-        check(getattr(self.lib, f"smoltts_{self.C_NAME}_create")(dptr(self.slab), need, max_batch, C.byref(h)),
+        check(getattr(self.lib, f"smoltts_{self.C_NAME}_create")(dptr(self.slab), need, max_batch, *self._create_args(), C.byref(h)),
               f"smoltts_{self.C_NAME}_create")
         self.handle = h
+
+    def _create_args(self) -> tuple:
+        """What the stage's create call takes between ``max_batch`` and the handle."""
+        return ()
 
     @staticmethod
     def _ints(v: Sequence[int]):
@@ -1211,6 +1230,114 @@ def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: tor
     return np.concatenate(out) if out else np.zeros(0, np.float32)
 
 
+# ------------------------------------------------------------------------------- loudness
+class LoudnessNormalizer(_Stage):
+    """Per-slot loudness normalisation of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Loudness"; the numpy
+    model is ``loudness.StreamState``): one launch per call for every slot, each towards its own target.  A slot emits exactly
+    the samples it reads.  Slots start off; ``reset_slots`` starts a new stream in a slot (target None: off)."""
+
+    C_NAME = "loudness"
+
+    def _create_args(self) -> tuple:
+        from .loudness import tables
+
+        self._tables = tables().packed()  # (read by the create call only)
+        assert self._tables.size == self.lib.smoltts_loudness_table_doubles()
+        return self._tables.ctypes.data, int(self._tables.size)
+
+    def reset_slots(self, slots: Sequence[int], targets: Sequence[Optional[float]],
+                    start_gain_db: Optional[Sequence[Optional[float]]] = None) -> None:
+        """Start new streams in ``slots`` towards their ``targets`` (LUFS; None: the slot is off) from their first knots
+        (``start_gain_db``, default 0 dB)."""
+        from .loudness import knot_of_db, target_power
+
+        n = len(slots)
+        if not n:
+            return
+        power = (C.c_double * n)(*[0.0 if t is None else target_power(t) for t in targets])
+        knots = self._ints([knot_of_db(g or 0.0) for g in (start_gain_db or [0.0] * n)])
+        check(self.lib.smoltts_loudness_reset_slots(self.handle, self._ints(slots), power, knots, n, current_stream_ptr()),
+              "smoltts_loudness_reset_slots")
+
+    def new_outputs(self, batch: int, n_in: int):
+        """Device buffers of one call of at most ``n_in`` input samples: (fp32 [batch, n_in], counts int32 [batch])."""
+        return (torch.empty(batch, max(int(n_in), 1), dtype=torch.float32, device=self.device),
+                torch.empty(batch, dtype=torch.int32, device=self.device))
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
+        """Normalise ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current
+        stream.  ``valid``: device int32 [batch], the real samples of each row.  ``counts[b]``: the samples slot b wrote to
+        ``out[b]`` (its valid ones; 0 for a slot that is off)."""
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.float32, n_in, counts, 1, valid)
+        check(self.lib.smoltts_loudness_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1],
+                                              dptr(counts), current_stream_ptr()), "smoltts_loudness_chunk")
+
+    def measure(self, row: torch.Tensor, n: int) -> Tuple[float, float]:
+        """(gated mean power, peak) of the whole utterance ``row[:n]`` (device fp32, contiguous); waits for the result."""
+        hops = torch.empty(n // 2400 + 1, dtype=torch.float64, device=self.device)
+        res = torch.empty(4, dtype=torch.float64, device=self.device)
+        check(self.lib.smoltts_loudness_measure(self.handle, dptr(row), int(n), dptr(hops), hops.numel(), dptr(res), current_stream_ptr()),
+              "smoltts_loudness_measure")
+        p, peak = res.cpu().numpy()[:2]
+        return float(p), float(peak)
+
+    def scale(self, row: torch.Tensor, n: int, gain: float, out: torch.Tensor) -> None:
+        """``out[:n] = float32(row[:n] * gain)`` on the current stream."""
+        check(self.lib.smoltts_loudness_scale(dptr(row), int(n), float(gain), dptr(out), current_stream_ptr()), "smoltts_loudness_scale")
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s state (synchronises the current stream), in the layout of ``loudness.StreamState.state``, with
+        ``on`` and ``ptarget``."""
+        ints, v = (C.c_int64 * 4)(), np.zeros(19 + 512, np.float64)
+        check(self.lib.smoltts_loudness_slot_state(self.handle, int(slot), ints, v.ctypes.data, current_stream_ptr()),
+              "smoltts_loudness_slot_state")
+        return {"pos": int(ints[0]), "ka": int(ints[1]), "kb": int(ints[2]), "on": int(ints[3]), "peak": np.float32(v[17]),
+                "ptarget": float(v[18]), "filter": v[:17].copy(), "ring": v[19:].copy()}
+
+
+def _loudness_whole(pcm: np.ndarray, device: torch.device, target: Optional[float]):
+    """(power, peak, gain, output or None) of a whole utterance on ``device``: measured in one launch, and with a ``target``
+    scaled by the blocking rule's gain in a second one."""
+    from .loudness import static_gain
+
+    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    with torch.cuda.device(device):
+        ln = LoudnessNormalizer(device, 1)
+        try:
+            seen = {}
+
+            def launch(row, n, out, counts):
+                seen["p"], seen["peak"] = ln.measure(row, n) if n else (0.0, 0.0)
+                seen["g"] = 1.0 if target is None else static_gain(target, seen["p"], seen["peak"])
+                ln.scale(row, n, seen["g"], out)
+                counts.fill_(n)
+
+            y = _whole_row(ln, x, launch)
+        finally:
+            ln.close()
+    return seen["p"], seen["peak"], seen["g"], (x if seen["g"] == 1.0 else y)
+
+
+def measure_loudness(pcm: np.ndarray, device: torch.device) -> Tuple[float, float]:
+    """(integrated loudness in LUFS by BS.1770-4, -inf when no block passes the absolute gate or the utterance is shorter than
+    400 ms; peak) of a whole utterance (float32 at 24 kHz), measured on ``device``: ``loudness.measure``.  Waits."""
+    from .loudness import lufs_of_power
+
+    p, peak, _, _ = _loudness_whole(pcm, device, None)
+    return lufs_of_power(p), peak
+
+
+def loudness_normalize(pcm: np.ndarray, target: float, device: torch.device, with_gain: bool = False):
+    """A whole utterance (float32 at 24 kHz) brought to ``target`` LUFS on ``device`` by one gain, capped so that its peak
+    stays at -1 dBFS: ``loudness.normalize`` (``SmolTTS.__call__``).  An utterance that measures nothing comes back
+    unchanged.  ``with_gain``: -> (samples, the gain applied).  Waits for the result."""
+    from .loudness import check_target
+
+    _, _, g, y = _loudness_whole(pcm, device, check_target(target))
+    return (y, g) if with_gain else y
+
+
 # ------------------------------------------------------------------------------- FLAC framing
 FLAC_OFF, FLAC_F32, FLAC_S16 = 0, 1, 2  # SMOLTTS_FLAC_*
 
@@ -1286,7 +1413,9 @@ def flac_encode(samples: np.ndarray, sample_rate: int, device: torch.device) -> 
 
 
 # ------------------------------------------------------------------------------- a stream's stages behind the codec
-STAGES = ("seam", "stretch", "resample", "flac")  # the stages of a pass, in launch order
+STAGES = ("seam", "stretch", "resample", "flac")  # the stages every build has had, in launch order
+LAUNCH_ORDER = ("seam", "loudness", "stretch", "resample", "flac")  # the stages of a pass, in launch order
+FLOAT_STAGES = ("seam", "loudness", "stretch")  # fp32 in, fp32 out: the stages behind read their rows
 
 
 @dataclass(frozen=True)
@@ -1301,17 +1430,20 @@ class SlotRoute:
     segmented: bool = False
     gen: int = 0
     head_owed: bool = False
+    loudness: Optional[float] = None  # target in LUFS (None: the slot never enters the loudness stage)
+    start_gain_db: float = 0.0        # its stream's first knot
 
     @cached_property
     def stages(self) -> Tuple[str, ...]:
         """The stages the slot goes through, in launch order."""
-        return tuple(s for s, on in zip(STAGES, (self.segmented, self.speed_q != 65536, self.enc != ENC_OFF, self.flac)) if on)
+        on = (self.segmented, self.loudness is not None, self.speed_q != 65536, self.enc != ENC_OFF, self.flac)
+        return tuple(s for s, o in zip(LAUNCH_ORDER, on) if o)
 
 
 class PassPlan(NamedTuple):
     stages: List[str]                 # the stages to launch, in order
     rows: Dict[str, List[int]]        # the live slots each of them serves
-    through: Dict[str, List[int]]     # float stage (seam, stretch) -> the live slots it does not serve that a later stage does
+    through: Dict[str, List[int]]     # float stage (seam, loudness, stretch) -> the live slots it does not serve that a later stage does
     source: Dict[int, Optional[str]]  # live slot -> the last stage it goes through (None: its codec rows are its output)
     host: List[str]                   # the stages whose outputs are copied to the host: the sources of the live slots
     routes: Dict[int, SlotRoute]      # live slot -> its route when planned
@@ -1319,8 +1451,8 @@ class PassPlan(NamedTuple):
 
 def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
     """The plan of one converter pass over the live slots' routes (``{slot: SlotRoute}``, in slot order); no device involved."""
-    rows = {s: [] for s in STAGES}
-    through = {"seam": [], "stretch": []}
+    rows = {s: [] for s in LAUNCH_ORDER}
+    through = {s: [] for s in FLOAT_STAGES}
     source = {}
     for b, r in routes.items():
         path = r.stages
@@ -1328,9 +1460,9 @@ def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
         for s in path:
             rows[s].append(b)
         for s in through:
-            if path and s not in path and STAGES.index(path[-1]) > STAGES.index(s):
+            if path and s not in path and LAUNCH_ORDER.index(path[-1]) > LAUNCH_ORDER.index(s):
                 through[s].append(b)
-    stages = [s for s in STAGES if rows[s]]
+    stages = [s for s in LAUNCH_ORDER if rows[s]]
     return PassPlan(stages, {s: rows[s] for s in stages}, {s: through[s] for s in through if rows[s]}, source,
                     [s for s in stages if s in source.values()], routes)
 
@@ -1349,22 +1481,31 @@ class StreamConverter:
         self.ts: Optional[TimeStretcher] = None
         self.fl: Optional[FlacEncoder] = None
         self.sj: Optional[SeamJoiner] = SeamJoiner(device, max_batch) if seam else None
+        self.ln: Optional[LoudnessNormalizer] = None
         self.routes = [SlotRoute()] * max_batch
         self._plan: Optional[PassPlan] = None  # the last pass's plan
 
     def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]],
-                    containers: Optional[Sequence[Optional[str]]] = None) -> None:
+                    containers: Optional[Sequence[Optional[str]]] = None, loudness: Optional[Sequence[Optional[float]]] = None,
+                    start_gain_db: Optional[Sequence[Optional[float]]] = None) -> None:
         """Start new streams in ``slots`` on the current stream: ``formats[i]`` an ``output_format`` (None / ``pcm_24000``:
         float32), ``speed_q[i]`` a Q16 speed (None / 65536: none), ``containers[i]`` None or ``"flac"`` (FLAC frames of the
-        slot's 16-bit samples at its rate).  A slot with none of them is switched off."""
+        slot's 16-bit samples at its rate), ``loudness[i]`` a target in LUFS (None: none) reached from ``start_gain_db[i]``.
+        A slot with none of them is switched off."""
         if not slots:
             return
         formats = [f or "pcm_24000" for f in formats]
         routes = []
-        for b, f, q, c in zip(slots, formats, speed_q, containers or [None] * len(slots)):
+        none = [None] * len(slots)
+        for b, f, q, c, lt, sg in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none):
             rate, enc = parse_stream_format(f)
             flac = check_container(c, f) is not None
-            routes.append(SlotRoute(rate, enc, q or 65536, flac, segmented=False, gen=self.routes[b].gen + 1, head_owed=flac))
+            routes.append(SlotRoute(rate, enc, q or 65536, flac, segmented=False, gen=self.routes[b].gen + 1, head_owed=flac,
+                                    loudness=lt, start_gain_db=sg or 0.0))
+        if self.ln is None and any(r.loudness is not None for r in routes):
+            self.ln = LoudnessNormalizer(self.device, self.B)
+        if self.ln is not None:
+            self.ln.reset_slots(slots, [r.loudness for r in routes], [r.start_gain_db for r in routes])
         if self.rs is None and any(r.enc != ENC_OFF for r in routes):
             self.rs = Resampler(self.device, self.B, out_bound(self.n_in))
         if self.ts is None and any(r.speed_q != 65536 for r in routes):
@@ -1438,6 +1579,10 @@ class StreamConverter:
             out, counts = outs["seam"] = self.sj.new_outputs(batch, n_in)
             self.sj.chunk(pcm, n_in, out, counts, valid=valid, seg_end=seg_end, last=last)
             valid, pcm, n_in = self._through(plan, "seam", out, counts, pcm, n_in, valid), out, out.shape[1]
+        if "loudness" in plan.stages:
+            out, counts = outs["loudness"] = self.ln.new_outputs(batch, n_in)
+            self.ln.chunk(pcm, n_in, out, counts, valid=valid)
+            valid, pcm, n_in = self._through(plan, "loudness", out, counts, pcm, n_in, valid), out, out.shape[1]
         if "stretch" in plan.stages:
             out, counts = outs["stretch"] = self.ts.new_outputs(batch, n_in)
             self.ts.chunk(pcm, n_in, out, counts, valid=valid, last=last)
@@ -1452,10 +1597,10 @@ class StreamConverter:
         return StreamPass(self, {s: outs[s] for s in plan.host}, plan)
 
     def close(self):
-        for stage in (self.rs, self.ts, self.fl, self.sj):
+        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln):
             if stage is not None:
                 stage.close()
-        self.rs = self.ts = self.fl = self.sj = None
+        self.rs = self.ts = self.fl = self.sj = self.ln = None
 
 
 class StreamPass:

@@ -217,7 +217,8 @@ def generate_blocking(model: LMEngine, prompt: np.ndarray, generation_settings: 
 
 def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bool = True, max_frames: Optional[int] = None,
                overlap: bool = True, output_format: Optional[str] = None, speed_q: Optional[int] = None,
-               container: Optional[str] = None, conv: Optional[StreamConverter] = None, final: bool = True) -> Iterator[np.ndarray]:
+               container: Optional[str] = None, conv: Optional[StreamConverter] = None, final: bool = True,
+               loudness: Optional[float] = None, start_gain_db: Optional[float] = None) -> Iterator[np.ndarray]:
     """One utterance in slot 0 of ``session`` -> one 1920-sample float32 chunk per generated frame, as the reference's
     ``SmolTTS.stream`` yields them (mlx_inference/src/smoltts_mlx/__init__.py:83-95: every frame of ``SingleBatchGenerator`` through
     ``codec.decode_step``), the terminating ``<|im_end|>`` frame included.
@@ -244,6 +245,10 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     the codec stream behind the other stages (``engine.FlacEncoder``): uint8 chunks, the stream header in front of the first;
     the end of the stream is derived on the device as for a speed.
 
+    ``loudness`` (a target in LUFS, ``loudness.py``; None: no launch): every frame's PCM goes through the loudness stage
+    (``engine.LoudnessNormalizer``) in front of the stretch, from the first knot ``start_gain_db``; a frame's 1920 samples come
+    out with the frame.
+
     ``conv``: the utterance is one segment of a long text (``longform``): the caller's ``StreamConverter(seam=True)``, with the
     stream's stages started in slot 0 and this segment opened (``start_segments``), converts it and is not closed here; the
     format, speed and container arguments are then ignored.  The end of the utterance, derived on the device, is the seam's end
@@ -267,7 +272,7 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     with torch.cuda.stream(codec_stream):
         msession.reset()
         if own:
-            conv.reset_slots([0], [output_format], [speed_q], [container])
+            conv.reset_slots([0], [output_format], [speed_q], [container], [loudness], [start_gain_db])
     converted = conv.converts(0)
     ends_on_device, segmented = conv.ends([0])  # a stage must see the end of the stream / of the segment
     with torch.cuda.stream(lm_stream):
@@ -311,7 +316,8 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
             if out is not None:
                 # (a call after the slot stopped consumed nothing: its tail is that of the last frame)
                 chunk = out.chunk(0, last=final and (n <= f or bool(done and n == f + 1) or f + 1 >= limit))
-                if chunk.size or not ends_on_device:  # (a stretched frame that finalised no sample yields nothing)
+                # (a stretched frame that finalised no sample yields nothing, nor does a float stage fed no sample)
+                if chunk.size or (not ends_on_device and chunk.dtype != np.float32):
                     yield chunk
             if n <= f:  # the slot had stopped before this frame
                 break

@@ -7,6 +7,7 @@ from typing import Optional
 
 from .formats import ENC_OFF, check_container, parse_stream_format
 from .longform import SegmentOptions, SegmentPlan, segment_options
+from .loudness import check_start_gain, check_target
 from .tsm import parse_speed
 
 
@@ -18,12 +19,15 @@ class SpeechOptions:
     container: Optional[str]         # "flac", or None
     segment: Optional[SegmentOptions]
     plan: Optional[SegmentPlan]      # None: the plain path (no segment options, or a text that is one plain segment)
+    loudness: Optional[float] = None  # target in LUFS (loudness.py), None: the level is left as it is
+    start_gain_db: float = 0.0        # a stream's first gain knot
 
 
 def parse_request(text: str = "", stream: bool = False, output_format: Optional[str] = None, speed: Optional[float] = None,
-                  container: Optional[str] = None, segment=None) -> SpeechOptions:
+                  container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
+                  loudness_start_gain_db: Optional[float] = None) -> SpeechOptions:
     """A request's options checked and normalised; ``ValueError`` for anything a front end refuses.  ``output_format`` and
-    ``container`` apply to streaming requests only."""
+    ``container`` apply to streaming requests only, as does ``loudness_start_gain_db``, which needs a ``loudness``."""
     speed_q = parse_speed(speed)
     if output_format is not None:
         if not stream:
@@ -36,4 +40,8 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
         check_container(container, output_format)
     opts = segment_options(segment)
     plan = SegmentPlan.create(text, opts) if opts is not None else None
-    return SpeechOptions(output_format, None if speed_q is None else float(speed), speed_q, container, opts, plan)
+    target = check_target(loudness)
+    if loudness_start_gain_db is not None and (target is None or not stream):
+        raise ValueError("loudness_start_gain_db applies to streaming requests with a loudness")
+    return SpeechOptions(output_format, None if speed_q is None else float(speed), speed_q, container, opts, plan, target,
+                         check_start_gain(loudness_start_gain_db))

@@ -47,10 +47,11 @@ class TTSCore:
     def long_text(self) -> str:
         return self._setting("long_text", "refuse")
 
-    def _request_kw(self, text: str, speed: Optional[float]) -> Tuple[dict, int]:
-        """(kwargs, segments): ``{"speed": speed}`` for a speed other than 1 and ``{"segment": options}`` in ``long_text="segment"``
-        mode, nothing otherwise, so that the model sees the calls it saw before; a bad speed, a text over ``max_input_chars`` or
-        with a bad break tag is the client's fault (ValueError).  The segments the request speaks (0: an unsegmented one) are
+    def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False) -> Tuple[dict, int]:
+        """(kwargs, segments): ``{"speed": speed}`` for a speed other than 1, ``{"segment": options}`` in ``long_text="segment"``
+        mode and ``{"loudness": target}`` for a ``LoudnessFields`` body (or the server's ``loudness`` setting) that names one,
+        nothing otherwise, so that the model sees the calls it saw before; a bad speed or loudness, a text over
+        ``max_input_chars`` or with a bad break tag is the client's fault (ValueError).  The segments the request speaks (0: an unsegmented one) are
         counted once it has completed."""
         from ..request import parse_request
 
@@ -60,8 +61,13 @@ class TTSCore:
             if len(text) > limit:
                 raise ValueError(f"input has {len(text)} characters; max_input_chars is {limit}")
             seg = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
-        p = parse_request(text, speed=speed, segment=seg)
+        target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
+        p = parse_request(text, stream=stream, speed=speed, segment=seg, loudness=target, loudness_start_gain_db=start)
         kw = {} if p.speed is None else {"speed": p.speed}
+        if p.loudness is not None:
+            kw["loudness"] = p.loudness
+            if start is not None:
+                kw["loudness_start_gain_db"] = start
         if seg is not None:
             kw["segment"] = seg
         return kw, len(p.plan.segs) if p.plan is not None else 0
@@ -153,26 +159,31 @@ class TTSCore:
         return sampling.resolve(base)
 
     def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000", sampling=None,
-                       speed: Optional[float] = None):
-        """-> (bytes, media type, the seed the request sampled with or None).  ``speed``: passed on only when it is not 1."""
+                       speed: Optional[float] = None, loudness=None, info: Optional[dict] = None):
+        """-> (bytes, media type, the seed the request sampled with or None).  ``speed``: passed on only when it is not 1.
+        ``loudness``: the body's ``LoudnessFields``; ``info["loudness_gain_db"]`` is then the gain the utterance was given."""
         used = None
         try:
-            sp, n_seg = self._request_kw(input_text, speed)
+            sp, n_seg = self._request_kw(input_text, speed, loudness)
             if self.scheduler is not None:
                 req = self.scheduler.submit(input_text, str(voice), stream=False, **({"sampling": sampling} if sampling is not None else {}), **sp)
                 used = getattr(req, "sampling", None)
                 pcm = np.concatenate(list(self.scheduler.iter_chunks(req)) or [np.zeros(0, np.float32)])
+                gain = getattr(req, "loudness_gain_db", None)
             else:
                 used = self._model_sampling(sampling)
                 kw = {"sampling": used} if used is not None else {}
                 pcm = np.asarray(self.model(input_text, str(voice), **kw, **sp)).flatten()
+                gain = getattr(self.model, "last_loudness_gain_db", None)
+            if info is not None and "loudness" in sp:
+                info["loudness_gain_db"] = gain
         except ValueError as e:  # a request the engine refuses (e.g. a text too long for max_seq_len): the client's fault, not a 500
             raise HTTPException(status_code=400, detail=str(e))
         self._count_segments(n_seg)
         return (*self.format_audio_chunk(pcm, response_format), seed_used(used))
 
     def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
-                     speed: Optional[float] = None, container: Optional[str] = None):
+                     speed: Optional[float] = None, container: Optional[str] = None, loudness=None):
         """-> (chunks as bytes, the seed the request samples with or None).  Chunks: float32 at 24 kHz for ``pcm_24000``;
         otherwise the int16 / mu-law samples the model or scheduler converted on the GPU (the format is passed on only when it is
         not ``pcm_24000``).  The request is submitted here, before the first chunk is asked for.  ``speed``: passed on only when
@@ -181,7 +192,7 @@ class TTSCore:
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
         if container is not None:
             kw["container"] = container
-        sp, n_seg = self._request_kw(input_text, speed)
+        sp, n_seg = self._request_kw(input_text, speed, loudness, stream=True)
         if self.scheduler is not None:
             req = self.scheduler.submit(input_text, str(voice), stream=True, **kw, **({"sampling": sampling} if sampling is not None else {}), **sp)
             chunks, used = self.scheduler.iter_chunks(req), getattr(req, "sampling", None)
@@ -236,6 +247,11 @@ def _seed_headers(seed: Optional[int]) -> dict:
     return {} if seed is None else {"X-Seed": str(seed)}
 
 
+def _gain_headers(info: dict) -> dict:
+    g = info.get("loudness_gain_db")
+    return {} if g is None else {"X-Loudness-Gain-Db": f"{g:.2f}"}
+
+
 class SamplingFields(BaseModel):
     """Per-request sampling (extension; the ElevenLabs body's ``seed``): omitted fields take the server's generation settings.
     A sampled response carries ``X-Seed``: the seed it used, drawn by the server when the body names none."""
@@ -257,7 +273,19 @@ class SamplingFields(BaseModel):
 SpeedField = Field(default=None, ge=0.25, le=4.0, allow_inf_nan=False)
 
 
-class SpeechRequest(SamplingFields):
+class LoudnessFields(BaseModel):
+    """Loudness normalisation (extension): ``loudness`` is a target in LUFS (-40 to -5, 400 otherwise; BS.1770-4, measured and
+    applied on the GPU: loudness.py).  Omitted: the server's ``loudness`` setting; null: off.  A blocking response carries
+    ``X-Loudness-Gain-Db``.  ``loudness_start_gain_db`` (streams only, within +-20): the gain a stream starts from."""
+    loudness: Optional[float] = Field(default=None, allow_inf_nan=False)
+    loudness_start_gain_db: Optional[float] = Field(default=None, allow_inf_nan=False)
+
+    def resolve(self, default):
+        """(target or None, start gain or None): the body's field where it names one (null: off), else the server's default."""
+        return (self.loudness if "loudness" in self.model_fields_set else default), self.loudness_start_gain_db
+
+
+class SpeechRequest(SamplingFields, LoudnessFields):
     model: str = Field(default="tts-1-hd")
     input: str
     voice: Union[str, int] = Field(default="alloy")
@@ -271,7 +299,7 @@ class VoiceSettings(BaseModel):
     speed: Optional[float] = SpeedField
 
 
-class CreateSpeechRequest(SamplingFields):
+class CreateSpeechRequest(SamplingFields, LoudnessFields):
     text: str
     model_id: Optional[str] = Field(default=None)
     voice_settings: Optional[VoiceSettings] = Field(default=None)
@@ -322,7 +350,7 @@ def openai_speech(item: SpeechRequest, http_request: Request):
         container = "flac" if item.response_format == "flac" else None
         try:
             chunks, seed = core.stream_audio(item.input, item.voice, "pcm_24000", sampling=item.request_sampling(), speed=item.speed,
-                                             container=container)
+                                             container=container, loudness=item)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         if container is None:
@@ -331,9 +359,11 @@ def openai_speech(item: SpeechRequest, http_request: Request):
         return StreamingResponse(_answer_first(chunks), media_type=media_type, headers={
             "Content-Disposition": f'attachment; filename="speech.{item.response_format}"', "X-Sample-Rate": "24000",
             **_seed_headers(seed)})
+    info: dict = {}
     audio, media_type, seed = core.generate_audio(item.input, item.voice, item.response_format + "_24000", sampling=item.request_sampling(),
-                                                  speed=item.speed)
-    return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed)})
+                                                  speed=item.speed, loudness=item, info=info)
+    return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed),
+                                                           **_gain_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}")
@@ -341,10 +371,12 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
                                   output_format: Optional[str] = Query(None, description="pcm_<rate> | wav_<rate>")):
     core = http_request.app.state.tts_core
     fmt = output_format or "wav_24000"
-    content, media_type, seed = core.generate_audio(item.text, voice_id, fmt, sampling=item.request_sampling(), speed=item.speed)
+    info: dict = {}
+    content, media_type, seed = core.generate_audio(item.text, voice_id, fmt, sampling=item.request_sampling(), speed=item.speed,
+                                                    loudness=item, info=info)
     return Response(content=content, media_type=media_type, headers={
         "Content-Disposition": f'attachment; filename="elevenlabs_speech.{fmt.split("_")[0]}"',
-        "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed)})
+        "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed), **_gain_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}/stream")
@@ -355,7 +387,7 @@ def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
     kind, rate = output_format.split("_")
     try:
         chunks, seed = core.stream_audio(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling(),
-                                         speed=item.speed)
+                                         speed=item.speed, loudness=item)
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return StreamingResponse(chunks, media_type="audio/wav", headers={

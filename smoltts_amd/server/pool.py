@@ -31,6 +31,7 @@ class _PoolRequest:
     cancelled: bool = False
     closed: bool = False
     sampling: object = None  # config.RequestSampling as sent to the worker (seed resolved here), or None
+    loudness_gain_db: Optional[float] = None  # a blocking request with a loudness: the gain applied (known at its end)
 
 
 def visible_device(index: int, inherited: Optional[str]) -> str:
@@ -74,7 +75,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
         try:
             for chunk in sched.iter_chunks(req):
                 res_q.put((rid, "chunk", np.ascontiguousarray(chunk)))  # float32, or int16 / uint8 for a streamed output_format
-            res_q.put((rid, "end", None))
+            res_q.put((rid, "end", getattr(req, "loudness_gain_db", None)))
         except Exception as e:
             res_q.put((rid, "error", (type(e).__name__, str(e))))
         finally:
@@ -189,11 +190,12 @@ class GpuPool:
     # ------------------------------------------------------------------ client side (the BatchScheduler interface)
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
-               container: Optional[str] = None, segment=None) -> _PoolRequest:
+               container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
+               loudness_start_gain_db: Optional[float] = None) -> _PoolRequest:
         """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
         from ..request import parse_request
 
-        p = parse_request(text, stream, output_format, speed, container, segment)  # refused here, before a worker sees it
+        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db)  # refused here, before a worker sees it
         if sampling is not None or self._settings is not None:  # the seed is drawn here: the same on whichever worker serves it
             import dataclasses
 
@@ -216,7 +218,8 @@ class GpuPool:
             self._load[w] += 1
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
         extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
-                                   ("container", p.container), ("segment", p.segment)) if v is not None}
+                                   ("container", p.container), ("segment", p.segment), ("loudness", p.loudness),
+                                   ("loudness_start_gain_db", loudness_start_gain_db)) if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
@@ -380,6 +383,7 @@ class GpuPool:
                 if not req.cancelled:
                     req.out.put(payload)
             elif kind == "end":
+                req.loudness_gain_db = payload
                 self._finish(req, None)
             elif kind == "result":  # a registry message's answer
                 self._finish(req, ("result", payload))

@@ -58,6 +58,9 @@ class _Request:
     container: Optional[str] = None  # streaming: "flac" frames the stream's 16-bit samples on the GPU (uint8 chunks)
     seg: Optional["_Segmented"] = None  # a long text as chained segments (None: one utterance)
     part_of: object = None    # (request, k): this codec job decodes segment k of a blocking segmented request
+    loudness: Optional[float] = None  # target in LUFS (loudness.py): a stream is levelled in its codec pass, a blocking utterance whole
+    start_gain_db: float = 0.0        # streaming: the loudness stage's first knot
+    loudness_gain_db: Optional[float] = None  # blocking: the gain that was applied (set before the audio goes out)
 
 
 @dataclass
@@ -210,7 +213,8 @@ class BatchScheduler:
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
-               container: Optional[str] = None, segment=None) -> _Request:
+               container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
+               loudness_start_gain_db: Optional[float] = None) -> _Request:
         """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
         in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
@@ -224,11 +228,15 @@ class BatchScheduler:
         from the first segment to the last; each segment's end, seen in a snapshot, refills the slot with the next chained
         prompt.  A stream runs through the seam stage in front of its other stages (one stream); a blocking request decodes
         each segment as its own codec job and joins them on the GPU.  A text that is one segment without break tags is an
-        ordinary request."""
+        ordinary request.
+        ``loudness`` (a target in LUFS, -40 to -5, ``ValueError`` otherwise; None: the level is left alone): BS.1770-4 loudness
+        normalisation on the GPU (loudness.py).  A stream is levelled causally in its codec pass, behind the seam and in front of
+        the stretch, from ``loudness_start_gain_db`` (streaming only; default 0); a blocking utterance is measured whole and
+        given one gain (``request.loudness_gain_db``), behind the seam join and in front of the stretch."""
         from ..config import RequestSampling
         from ..request import parse_request
 
-        p = parse_request(text, stream, output_format, speed, container, segment)
+        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         if self._dead is not None:  # the worker is gone (engine failure or close): nobody would ever answer
             raise RuntimeError(f"scheduler is not running: {self._dead}")
@@ -236,7 +244,8 @@ class BatchScheduler:
             raise RuntimeError("scheduler is not running: shutting down")
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
                        output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=p.speed_q,
-                       container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None)
+                       container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None,
+                       loudness=p.loudness, start_gain_db=p.start_gain_db)
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
@@ -652,7 +661,8 @@ class BatchScheduler:
                 # (a segmented stream's later segments restart the codec only: its other stages run on)
                 fresh = [r for r in new if r.seg is None or r.seg.k == 0]
                 self._stream_conv.reset_slots([r.slot for r in fresh], [r.output_format for r in fresh],
-                                              [r.speed_q for r in fresh], [r.container for r in fresh])
+                                              [r.speed_q for r in fresh], [r.container for r in fresh],
+                                              [r.loudness for r in fresh], [r.start_gain_db for r in fresh])
                 segd = [r for r in new if r.seg is not None]
                 if segd:
                     pauses, flags, leads = zip(*(r.seg.plan.seam_args(r.seg.k) for r in segd))
@@ -886,13 +896,17 @@ class BatchScheduler:
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
                         self._counts["frames_delivered"] += n // 1920
-                elif not r.stream and r.speed_q:  # a blocking utterance with a speed: stretched whole once its last pass is in
+                elif not r.stream and (r.speed_q or r.loudness is not None):
+                    # a blocking utterance with a speed or a loudness target: levelled and stretched whole once its last pass is in
                     if n and not r.cancelled:
                         r.stretch_in.append(host[b, :n].copy())
                         self._counts["frames_delivered"] += n // 1920
                     if fin and r.stretch_in and not r.cancelled:
-                        self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
-                        continue
+                        r.stretch_in = [self._level(r, np.concatenate(r.stretch_in))]
+                        if r.speed_q:
+                            self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
+                            continue
+                        r.out.put(r.stretch_in.pop())
                 elif n and not r.cancelled:
                     r.out.put(host[b, :n].copy())
                     self._counts["frames_delivered"] += n // 1920
@@ -921,12 +935,26 @@ class BatchScheduler:
                 self._block_seam = SeamJoiner(dev, 1)
             pcm = seam_join(pcms, sg.plan.pauses, dev, lead=sg.plan.lead, trail=sg.plan.trail, joiner=self._block_seam)
         sg.pcm = []
+        pcm = self._level(r, pcm)
         if r.speed_q:
             r.stretch_in = [pcm]
             self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
             return
         r.out.put(pcm)
         self._end(r)
+
+    def _level(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
+        """A complete blocking utterance (joined, not yet stretched): with a loudness target it is measured and scaled whole on
+        the GPU (engine.loudness_normalize: two launches, waited for here as the seam join is)."""
+        if r.loudness is None:
+            return pcm
+        from ..engine import loudness_normalize
+        from ..loudness import gain_db
+
+        with self._torch.cuda.stream(self._stretch_stream):
+            pcm, g = loudness_normalize(pcm, r.loudness, self.session.engine.device, with_gain=True)
+        r.loudness_gain_db = gain_db(g)
+        return pcm
 
     STRETCH_SLOTS, STRETCH_PIECE = 16, 65536  # blocking utterances stretched side by side, input samples per slot and call
 

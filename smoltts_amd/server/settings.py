@@ -56,6 +56,9 @@ class ServerSettings(BaseModel):
     segment_max_bytes: int = Field(default=300, ge=16, le=1000)
     seam_pause_ms: int = Field(default=250, ge=0, le=3000)
     max_input_chars: int = Field(default=5000, ge=1)
+    # (extension) the loudness target in LUFS of requests whose body names none (loudness.py); null: the level is
+    # left as the model gives it
+    loudness: Optional[float] = Field(default=None, ge=-40.0, le=-5.0)
 
     model_config = {"protected_namespaces": ()}
 
