@@ -893,6 +893,33 @@ int smoltts_k_sample_rows(const float* logits_dev, int32_t n_rows, int32_t n_col
 int smoltts_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, int32_t n_rows,
                         int32_t dim, float eps, float* out_dev, void* stream);
 
+/* Test entries of the Mimi decoder's fused stages (the kernels smoltts_mimi_decode_chunk runs, with the caller's buffers).
+ *
+ * Resnet block of a SEANet stage (128 channels): out[b][t] = ELU(x + conv_k1(ELU(conv_k3(ELU(x)))))[b][t], t < n_rows, causal.
+ * x_dev / out_dev point at row 0 of slot 0, channel-last fp32, slot b at + b * x_bstride / o_bstride floats; the two rows in
+ * front of every slot's x rows are read (the previous call's last two rows, zeros at a stream's start), nothing in front of
+ * out_dev's rows is written.  w2_w3_dev / w3_w3_dev: W3 tiles of the GEMM forms [C/2][3C] (k = tap * C + channel) and [C][C/2]. */
+int smoltts_k_seanet_resblock(int32_t channels, int32_t batch, int32_t n_rows, const float* x_dev, int64_t x_bstride,
+                              const void* w2_w3_dev, const float* b2_dev, const void* w3_w3_dev, const float* b3_dev, float* out_dev,
+                              int64_t o_bstride, int32_t b3_products, void* stream);
+
+/* Last SEANet stage: ConvTranspose1d (128 -> 64, stride 4, kernel 8) + resnet block (64 -> 32 -> 64) + ELU + Conv1d k3 (64 -> 1):
+ * pcm[b][4 t + j], t < n_rows, from in[b][t] = ELU(previous stage), channel-last with two halo rows in front of every slot's rows as
+ * above.  slot_pos_dev[b] == 0 marks a stream's start: everything in front of the slot's row 0 is the convolutions' zero padding
+ * (and its halo rows must be zero); otherwise the halo rows are data.  wt_w3_dev: W3 tiles of the ConvTranspose's GEMM form
+ * [256 = j * 64 + channel][256 = (row t-1 | row t) x 128], bt_dev its bias repeated per phase [256]; final_w_dev fp32 [3][64]. */
+int smoltts_k_seanet_last(int32_t batch, int32_t n_rows, const float* in_dev, int64_t in_bstride, const void* wt_w3_dev,
+                          const float* bt_dev, const void* w2_w3_dev, const float* b2_dev, const void* w3_w3_dev, const float* b3_dev,
+                          const float* final_w_dev, float final_b, float* pcm_dev, int64_t pcm_stride, const int32_t* slot_pos_dev,
+                          int32_t b3_products, void* stream);
+
+/* RVQ decode + up-sampling: e[b][f] = sum_q table[q][clamp(codes[b][f][code_offset + q], 0, 2047)] (table fp32 [nq][2048][512]),
+ * tx[b][2 f + r] = e[f] * upw[r] + e[f - 1] * upw[r + 2] (upw fp32 [4][512]), e[-1] = carry_in_dev[b] (NULL: zero, the stateless
+ * mode); carry_out_dev[b] = e[n_frames - 1].  tx_dev is [batch][2 n_frames][512]. */
+int smoltts_k_rvq_upsample(const int32_t* codes_dev, int64_t codes_stride, int32_t frame_stride, int32_t code_offset, int32_t nq,
+                           int32_t batch, int32_t n_frames, const float* table_dev, const float* upw_dev, const float* carry_in_dev,
+                           float* carry_out_dev, float* tx_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

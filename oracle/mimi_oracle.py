@@ -2,7 +2,7 @@
 
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import it.
 
-Restates, in plain fp32 PyTorch on CPU, the reference chain ``MimiModel._decode_frame``
+Restates, in plain fp32 (or, on request, float64) PyTorch on CPU, the reference chain ``MimiModel._decode_frame``
 (mlx_inference/src/smoltts_mlx/codec/mimi.py:73-104):
 
 * RVQ decode       codec/rvq.py:41-52 (embed = embed_sum / max(cluster_usage, 1e-5)), :118-131
@@ -63,8 +63,11 @@ def _causal_convtr1d(x: Tensor, w: Tensor, b: Optional[Tensor], stride: int, gro
 
 
 class MimiDecodeOracle:
-    def __init__(self, state: Dict[str, Tensor], num_codebooks: int = 8, window: int = 0):
-        self.st = {k: v.float() for k, v in state.items()}
+    def __init__(self, state: Dict[str, Tensor], num_codebooks: int = 8, window: int = 0, dtype: torch.dtype = torch.float32):
+        """``dtype`` = torch.float64: the weights, the RoPE angles and every intermediate are float64 (the yardstick the strict
+        GPU tests measure both the kernels and this oracle's own fp32 form against); the default computes what it always did."""
+        self.dt = dtype
+        self.st = {k: v.to(dtype) for k, v in state.items()}
         self.nq = num_codebooks
         self.window = window
         self.n_layers = 1 + max(
@@ -98,8 +101,8 @@ class MimiDecodeOracle:
     def _rope_half(self, x: Tensor, pos: Tensor) -> Tensor:
         """nn.RoPE(traditional=False): pairs (j, j+hd/2); x (B,H,T,hd), pos (T,)."""
         hd = x.shape[-1]
-        inv = 1.0 / (10000.0 ** (torch.arange(0, hd, 2).float() / hd))
-        ang = pos.float()[:, None] * inv[None]  # T, hd/2
+        inv = 1.0 / (10000.0 ** (torch.arange(0, hd, 2).to(self.dt) / hd))
+        ang = pos.to(self.dt)[:, None] * inv[None]  # T, hd/2
         c, s = torch.cos(ang), torch.sin(ang)
         x1, x2 = x[..., : hd // 2], x[..., hd // 2 :]
         return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
@@ -147,10 +150,31 @@ class MimiDecodeOracle:
         x = F.elu(x)  # layer 13
         return _causal_conv1d(x, g("14.conv.weight"), g("14.conv.bias"))
 
+    @torch.no_grad()
+    def seanet_stages(self, x: Tensor) -> Dict[str, Tensor]:
+        """``seanet`` with its stage outputs, channel-last (B, rows, C): "conv0", then per ratio i = 1..4 "convtr{i}" (the raw
+        ConvTranspose output = the resnet block's input) and "res{i}" (the block's output x + y, before the next ELU), and
+        "pcm" (B, 1, 960 T) == ``seanet(x)``: a test that finds a wrong sample can name the stage where the error starts."""
+        g = lambda k: self.st["decoder.layers." + k]
+        out: Dict[str, Tensor] = {}
+        x = _causal_conv1d(x, g("0.conv.weight"), g("0.conv.bias"))
+        out["conv0"] = x.transpose(1, 2)
+        li = 1
+        for i, r in enumerate(RATIOS, 1):
+            x = _causal_convtr1d(F.elu(x), g(f"{li + 1}.conv.weight"), g(f"{li + 1}.conv.bias"), stride=r)
+            out[f"convtr{i}"] = x.transpose(1, 2)
+            y = _causal_conv1d(F.elu(x), g(f"{li + 2}.block.1.conv.weight"), g(f"{li + 2}.block.1.conv.bias"))
+            y = _causal_conv1d(F.elu(y), g(f"{li + 2}.block.3.conv.weight"), g(f"{li + 2}.block.3.conv.bias"))
+            x = x + y
+            out[f"res{i}"] = x.transpose(1, 2)
+            li += 3
+        out["pcm"] = _causal_conv1d(F.elu(x), g("14.conv.weight"), g("14.conv.bias"))
+        return out
+
     # -- mimi.py:73-104
     @torch.no_grad()
     def decode(self, codes: Tensor, upsample_call_frames: Optional[int] = None) -> Tensor:
-        """codes (B, nq, F) int -> pcm (B, 1, 1920 F) float32.  ``upsample_call_frames`` = c: the PCM a stream of
+        """codes (B, nq, F) int -> pcm (B, 1, 1920 F) in the oracle's dtype.  ``upsample_call_frames`` = c: the PCM a stream of
         ``decode_step`` calls of c frames each yields in the reference (mimi.py:73-77: ``self.upsample`` on the call's frames
         alone, i.e. taps 2, 3 of a call's last frame never reach the next call's first two rows)."""
         e = self.rvq_decode(codes.long())
@@ -168,8 +192,8 @@ class MimiDecodeOracle:
         e0 = self.rvq_decode(codes.long())
         e1 = self.upsample(e0)
         e2 = self.transformer(e1.transpose(1, 2))
-        pcm = self.seanet(e2.transpose(1, 2))
-        return {"rvq": e0.transpose(1, 2), "upsample": e1.transpose(1, 2), "transformer": e2, "pcm": pcm}
+        stages = self.seanet_stages(e2.transpose(1, 2))
+        return {"rvq": e0.transpose(1, 2), "upsample": e1.transpose(1, 2), "transformer": e2, **stages}
 
 
 # =============================================================================================

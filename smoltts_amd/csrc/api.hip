@@ -2,6 +2,7 @@
 #include <stdarg.h>
 
 #include "common.h"
+#include "mimi_common.h"
 
 namespace smoltts {
 static thread_local char g_err[1024] = "";
@@ -88,6 +89,43 @@ int smoltts_k_sample_rows(const float* logits_dev, int32_t n_rows, int32_t n_col
 int smoltts_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, int32_t n_rows, int32_t dim, float eps,
                         float* out_dev, void* stream) {
   return launch_layernorm(x_dev, w_dev, b_dev, n_rows, dim, eps, out_dev, (hipStream_t)stream);
+}
+
+int smoltts_k_seanet_resblock(int32_t channels, int32_t batch, int32_t n_rows, const float* x_dev, int64_t x_bstride,
+                              const void* w2_w3_dev, const float* b2_dev, const void* w3_w3_dev, const float* b3_dev, float* out_dev,
+                              int64_t o_bstride, int32_t b3_products, void* stream) {
+  MimiResblockArgs a;
+  memset(&a, 0, sizeof(a));
+  a.channels = channels; a.batch = batch; a.T = n_rows;
+  a.x = x_dev; a.x_bstride = x_bstride;
+  a.w2 = w2_w3_dev; a.b2 = b2_dev; a.w3 = w3_w3_dev; a.b3 = b3_dev;
+  a.out = out_dev; a.o_bstride = o_bstride;
+  a.b3_products = b3_products;
+  return launch_seanet_resblock(a, (hipStream_t)stream);
+}
+
+int smoltts_k_seanet_last(int32_t batch, int32_t n_rows, const float* in_dev, int64_t in_bstride, const void* wt_w3_dev,
+                          const float* bt_dev, const void* w2_w3_dev, const float* b2_dev, const void* w3_w3_dev, const float* b3_dev,
+                          const float* final_w_dev, float final_b, float* pcm_dev, int64_t pcm_stride, const int32_t* slot_pos_dev,
+                          int32_t b3_products, void* stream) {
+  ST_REQUIRE(pcm_stride >= 4 * (int64_t)n_rows, SMOLTTS_E_INVALID, "k_seanet_last: pcm_stride %lld < 4 * %d rows", (long long)pcm_stride,
+             n_rows);
+  MimiLastStageArgs a;
+  memset(&a, 0, sizeof(a));
+  a.batch = batch; a.T = n_rows;
+  a.in = in_dev; a.in_bstride = in_bstride;
+  a.wt = wt_w3_dev; a.bt = bt_dev; a.w2 = w2_w3_dev; a.b2 = b2_dev; a.w3 = w3_w3_dev; a.b3 = b3_dev;
+  a.final_w = final_w_dev; a.final_b = final_b;
+  a.pcm = pcm_dev; a.pcm_stride = pcm_stride;
+  a.slot_pos = slot_pos_dev; a.b3_products = b3_products;
+  return launch_seanet_last(a, (hipStream_t)stream);
+}
+
+int smoltts_k_rvq_upsample(const int32_t* codes_dev, int64_t codes_stride, int32_t frame_stride, int32_t code_offset, int32_t nq,
+                           int32_t batch, int32_t n_frames, const float* table_dev, const float* upw_dev, const float* carry_in_dev,
+                           float* carry_out_dev, float* tx_dev, void* stream) {
+  return launch_rvq_upsample(codes_dev, codes_stride, frame_stride, code_offset, nq, batch, n_frames, table_dev, upw_dev, carry_in_dev,
+                             carry_out_dev, tx_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

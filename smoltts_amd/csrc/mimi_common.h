@@ -55,6 +55,10 @@ struct MimiLastStageArgs {
 };
 int launch_seanet_last(const MimiLastStageArgs& a, hipStream_t st);
 
+// RVQ gather (output_proj folded into the table) + depthwise up-sampling -> tx[batch][2 n_frames][512] (mimi_engine.hip).
+int launch_rvq_upsample(const int* codes, int64_t codes_stride, int frame_stride, int code_offset, int nq, int batch, int n_frames,
+                        const float* table, const float* upw, const float* carry_in, float* carry_out, float* tx, hipStream_t st);
+
 inline SmolttsGemmArgs mimi_gemm_f32(const void* w, const float* x, long ldx, int M, int N, int K, const void* w3 = nullptr) {
   SmolttsGemmArgs a;
   memset(&a, 0, sizeof(a));

@@ -173,6 +173,17 @@ __global__ __launch_bounds__(256) void halo_shift_kernel(HaloDesc d) {
 
 namespace smoltts {
 
+int launch_rvq_upsample(const int* codes, int64_t codes_stride, int frame_stride, int code_offset, int nq, int batch, int n_frames,
+                        const float* table, const float* upw, const float* carry_in, float* carry_out, float* tx, hipStream_t st) {
+  ST_REQUIRE(codes && table && upw && carry_out && tx && batch > 0 && batch <= 65535 && n_frames > 0 && nq > 0 && code_offset >= 0 &&
+                 frame_stride >= nq + code_offset,
+             SMOLTTS_E_INVALID, "rvq_upsample: null, empty or inconsistent argument");
+  hipLaunchKernelGGL(rvq_upsample_kernel, dim3(n_frames, batch), dim3(128), 0, st, codes, (long)codes_stride, frame_stride, code_offset, nq,
+                     n_frames, table, upw, carry_in, carry_out, tx);
+  ST_CHECK_HIP(hipGetLastError());
+  return SMOLTTS_OK;
+}
+
 int launch_mimi_rows(int n_rows, int rows_per_slot, int pos0, int* row_pos, int* row_slot, hipStream_t st, const int* slot_pos) {
   hipLaunchKernelGGL(mimi_rows_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, st, n_rows, rows_per_slot, pos0, slot_pos, row_pos, row_slot);
   ST_CHECK_HIP(hipGetLastError());
@@ -385,10 +396,10 @@ static int decode_chunk_impl(SmolttsMimiSession* s, const int32_t* codes_dev, in
   const int F = n_frames, Tt = 2 * F, R = batch * Tt;
 
   // 1. RVQ gather (+ folded output_proj) and depthwise upsample -> transformer rows tx[b][2F][512]
-  hipLaunchKernelGGL(rvq_upsample_kernel, dim3(F, batch), dim3(128), 0, st, codes_dev, (long)codes_stride, frame_stride, code_offset,
-                     c.num_codebooks, F, (const float*)(A + m->w.rvq_table), (const float*)(A + m->w.upsample_w),
-                     s->stateless_upsample ? (const float*)nullptr : (const float*)s->carry[s->parity], s->carry[s->parity ^ 1], s->tx);
-  ST_CHECK_HIP(hipGetLastError());
+  ST_TRY(launch_rvq_upsample(codes_dev, codes_stride, frame_stride, code_offset, c.num_codebooks, batch, F, (const float*)(A + m->w.rvq_table),
+                             (const float*)(A + m->w.upsample_w),
+                             s->stateless_upsample ? (const float*)nullptr : (const float*)s->carry[s->parity], s->carry[s->parity ^ 1],
+                             s->tx, st));
   ST_TRY(launch_mimi_rows(R, Tt, 0, s->row_pos, s->row_slot, st, s->pos_dev));
 
   // 2. decoder transformer (transformer.py:109-131); the last layer writes straight into conv0's input

@@ -132,6 +132,7 @@ _EXPORTS = [
     "smoltts_loudness_slot_state",
     "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows",
     "smoltts_prefix_kv_bytes", "smoltts_session_save_prefix", "smoltts_session_install_prefix",
+    "smoltts_k_seanet_resblock", "smoltts_k_seanet_last", "smoltts_k_rvq_upsample",
 ]
 
 
@@ -185,6 +186,10 @@ def load_library(path: Optional[Path] = None):
     lib.smoltts_k_embed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]
     lib.smoltts_k_argmax.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.smoltts_k_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+    lib.smoltts_k_seanet_resblock.argtypes = [C.c_int32] * 3 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_void_p]
+    lib.smoltts_k_seanet_last.argtypes = [C.c_int32] * 2 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_float, C.c_void_p, C.c_int64,
+                                                                                                      C.c_void_p, C.c_int32, C.c_void_p]
+    lib.smoltts_k_rvq_upsample.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 6
     lib.smoltts_session_set_sampling.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_uint64]
     lib.smoltts_k_sample.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_void_p]

@@ -208,6 +208,58 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e
     return out
 
 
+# ------------------------------------------------------------------------------- fused stages of the Mimi decoder
+def seanet_resblock(xbuf: torch.Tensor, T: int, w2_w3: torch.Tensor, b2: torch.Tensor, w3_w3: torch.Tensor, b3: torch.Tensor,
+                    out: torch.Tensor, out_lead: int = 0, b3_products: int = 6) -> torch.Tensor:
+    """``smoltts_k_seanet_resblock`` (csrc/seanet.hip): ``xbuf`` fp32 [slots, 2 + rows, C] holds two halo rows, then the raw block
+    input (rows >= T; only [0, T) are read); ELU(x + conv_k1(ELU(conv_k3(ELU(x))))) of those T rows goes to
+    ``out[:, out_lead : out_lead + T]`` (fp32 [slots, out_lead + rows', C]).  ``w2_w3`` / ``w3_w3``: ``pack_weight_w3`` of the
+    ``conv_as_gemm`` matrices [C/2, 3C] and [C, C/2]."""
+    lib = E.load_library()
+    S, rows, Cn = xbuf.shape
+    assert xbuf.dtype == out.dtype == torch.float32 and xbuf.stride(2) == 1 and xbuf.stride(1) == Cn and out.stride(2) == 1 and out.stride(1) == Cn
+    assert out.shape[0] == S and out.shape[2] == Cn and 0 < T <= rows - 2 and out_lead + T <= out.shape[1]
+    E.check(lib.smoltts_k_seanet_resblock(Cn, S, T, xbuf.data_ptr() + 4 * 2 * Cn, xbuf.stride(0), E.dptr(w2_w3), E.dptr(b2), E.dptr(w3_w3),
+                                          E.dptr(b3), out.data_ptr() + 4 * out_lead * Cn, out.stride(0), b3_products, E.current_stream_ptr()),
+            "smoltts_k_seanet_resblock")
+    return out
+
+
+def seanet_last(inbuf: torch.Tensor, T: int, wt_w3: torch.Tensor, bt: torch.Tensor, w2_w3: torch.Tensor, b2: torch.Tensor,
+                w3_w3: torch.Tensor, b3: torch.Tensor, final_w: torch.Tensor, final_b: float, slot_pos: torch.Tensor, pcm: torch.Tensor,
+                b3_products: int = 6) -> torch.Tensor:
+    """``smoltts_k_seanet_last`` (csrc/seanet_last.hip): ``inbuf`` fp32 [slots, 2 + rows, 128] = two halo rows, then ELU(stage-3
+    output); the 4 T samples of every slot go to ``pcm[:, : 4 T]`` (fp32 [slots, >= 4 T]).  ``slot_pos`` int32 [slots]: 0 = the slot's
+    stream starts with this call (its halo rows must be zero).  Weights: ``pack_weight_w3`` of ``conv_as_gemm`` of the ConvTranspose
+    ([256, 256], bias repeated: [256]) and of the block's convs ([32, 192], [64, 32]); ``final_w`` fp32 [3 * 64] tap-major."""
+    lib = E.load_library()
+    S, rows, Cn = inbuf.shape
+    assert inbuf.dtype == pcm.dtype == torch.float32 and Cn == 128 and inbuf.stride(2) == 1 and inbuf.stride(1) == Cn and pcm.stride(1) == 1
+    assert pcm.shape[0] == S and 0 < T <= rows - 2 and 4 * T <= pcm.shape[1] and slot_pos.dtype == torch.int32 and slot_pos.numel() >= S
+    assert bt.numel() == 256 and final_w.numel() == 192
+    E.check(lib.smoltts_k_seanet_last(S, T, inbuf.data_ptr() + 4 * 2 * Cn, inbuf.stride(0), E.dptr(wt_w3), E.dptr(bt), E.dptr(w2_w3), E.dptr(b2),
+                                      E.dptr(w3_w3), E.dptr(b3), E.dptr(final_w), float(final_b), E.dptr(pcm), pcm.stride(0), E.dptr(slot_pos),
+                                      b3_products, E.current_stream_ptr()), "smoltts_k_seanet_last")
+    return pcm
+
+
+def rvq_upsample(codes: torch.Tensor, f0: int, n_frames: int, nq: int, table: torch.Tensor, upw: torch.Tensor,
+                 carry_in: Optional[torch.Tensor], carry_out: torch.Tensor, code_offset: int = 0) -> torch.Tensor:
+    """``smoltts_k_rvq_upsample`` (csrc/mimi_engine.hip): frames [f0, f0 + n_frames) of ``codes`` (int32 [slots, F, row], row >=
+    code_offset + nq) -> the decoder transformer's input rows fp32 [slots, 2 n_frames, 512].  ``table`` fp32 [nq, 2048, 512] (codebooks
+    with the output projection folded in), ``upw`` fp32 [4, 512]; ``carry_in`` [slots, 512] = the embedding of frame f0 - 1 (None: no
+    predecessor), ``carry_out`` receives that of the call's last frame."""
+    lib = E.load_library()
+    S, F, row = codes.shape
+    assert codes.dtype == torch.int32 and codes.is_contiguous() and 0 <= f0 and n_frames > 0 and f0 + n_frames <= F
+    assert tuple(table.shape) == (nq, 2048, 512) and table.is_contiguous() and tuple(upw.shape) == (4, 512) and upw.is_contiguous()
+    assert carry_out.numel() >= S * 512 and (carry_in is None or carry_in.numel() >= S * 512)
+    tx = torch.empty(S, 2 * n_frames, 512, dtype=torch.float32, device=codes.device)
+    E.check(lib.smoltts_k_rvq_upsample(codes.data_ptr() + 4 * f0 * row, F * row, row, code_offset, nq, S, n_frames, E.dptr(table), E.dptr(upw),
+                                       E.dptr(carry_in), E.dptr(carry_out), E.dptr(tx), E.current_stream_ptr()), "smoltts_k_rvq_upsample")
+    return tx
+
+
 # ------------------------------------------------------------------------------- X3 / bf16-MFMA path
 def x3_bytes(rows: int, K: int) -> int:
     return (rows + 15) // 16 * 16 * K * 6
