@@ -286,6 +286,37 @@ typedef struct SmolttsSlotSampling {
 int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* temp_host,
                                       const float* fast_temp_host, const float* min_p_host, const uint64_t* seed_host, void* stream);
 
+/* (ABI 6, additive) Per-slot filters of the sampled picks: top_k, top_p and a windowed repetition penalty, beside the slot's
+ * SmolttsSlotSampling entry.  They apply to a row only when that row is sampled (temp > 0 for the slow token, fast_temp > 0 for the
+ * depth codes: the rule min_p follows); a greedy row ignores them.  On the fp32 logits x of the row, in this order:
+ *   1. penalty r > 1 over a window of W frames: the ids this step produced in the request's last min(W, frame counter) frames
+ *      (step 0: the slow id, step i: depth code i - 1; read from the session's codes array, so the history restarts with the frame
+ *      counter) get x' = x * inv_penalty if x > 0, else x * penalty -- one rounded fp32 multiply; the row maximum is the penalised one;
+ *   2. top_k > 0: keep the columns with x' >= the k-th largest x' (duplicates counted, ties kept);
+ *   3. 0 < top_p < 1, on the columns top_k kept: z = (x' - max) * (1 / temp), p = exp(z); keep column j iff the mass of the kept
+ *      columns with z > z_j is < top_p * total (a threshold: ties stand or fall together);
+ *   4. min_p and the Gumbel key of the request as before.
+ * An all-zero entry is off, and a slot whose entry is off picks exactly what it picks without the table.  The thresholds are
+ * found by bisection with order-independent (integer-valued) reductions: the ids do not depend on the slot or the batch.
+ * Host model: smoltts_amd/sampling.py (filtered_keys / filtered_pick). */
+typedef struct SmolttsSlotFilters {
+  float top_p;        /* <= 0 or >= 1: off */
+  int32_t top_k;      /* <= 0 or >= columns: off */
+  float penalty;      /* <= 1: off */
+  float inv_penalty;  /* fp32(1 / penalty) */
+  int32_t window;     /* frames of history, 1 .. 64; <= 0: off */
+  int32_t reserved[3];
+} SmolttsSlotFilters;
+#define SMOLTTS_FILTER_MAX_WINDOW 64
+#define SMOLTTS_FILTER_MAX_PENALTY 1000.0f /* what this entry accepts; the public interface (config.RequestSampling) stops at 10 */
+
+/* Set the filter entries of slots_host[0 .. n): top_p in [0, 1] (0 and 1: off), top_k >= 0 (0: off), penalty 0 or in
+ * [1, SMOLTTS_FILTER_MAX_PENALTY] (0 and 1: off), window in [0, 64] (0: penalty off).  Uploaded like the sampling entries (pinned
+ * ring, no host wait, ordered on `stream`); the first call of either kind puts the session in slot mode.  "Some slot's entry is on"
+ * is one more bit of the graph form: while every entry is off, the frames launch exactly the kernels they launch without this table. */
+int smoltts_session_set_slot_filters(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* top_p_host,
+                                     const int32_t* top_k_host, const float* penalty_host, const int32_t* window_host, void* stream);
+
 /* Device pointers to the session's results (valid for the session's lifetime):
  *   codes      int32 [max_batch][max_frames][1 + n_fast]   emitted columns (slow id, codes)
  *   n_frames   int32 [max_batch]                            frames emitted so far per slot
@@ -889,6 +920,12 @@ int smoltts_k_sample(const float* logits_dev, int32_t n_rows, int32_t n_cols, in
  * session) and the request key of slot mode with frame frames_dev[r] (NULL: r); ids_dev[r] receives the pick. */
 int smoltts_k_sample_rows(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const SmolttsSlotSampling* table_dev,
                           const int32_t* frames_dev, int32_t step, int32_t* ids_dev, void* stream);
+
+/* (ABI 6, additive) smoltts_k_sample_rows with row r's filters filters_dev[r] and an explicit history: history_dev [n_rows][64]
+ * int32, newest first, of which row r's first min(history_len_dev[r], its window) ids are penalised. */
+int smoltts_k_sample_rows_filtered(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const SmolttsSlotSampling* table_dev,
+                                   const SmolttsSlotFilters* filters_dev, const int32_t* frames_dev, const int32_t* history_dev,
+                                   const int32_t* history_len_dev, int32_t step, int32_t* ids_dev, void* stream);
 
 int smoltts_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, int32_t n_rows,
                         int32_t dim, float eps, float* out_dev, void* stream);

@@ -177,10 +177,17 @@ class GenerationSettings:
     # and the draw is plain categorical over logits / temp.  "intended": the rule the code was taken from (MLX examples):
     # keep tokens with p >= min_p * p_max.  The drop-in default is what the reference does.
     min_p_mode: str = "reference"
+    # extension: the defaults of the per-request filters of sampled rows (``RequestSampling``; all off)
+    top_p: float = 1.0
+    top_k: int = 0
+    repetition_penalty: float = 1.0
+    repetition_window: int = 16
 
     def __post_init__(self):
         if self.min_p_mode not in ("reference", "intended"):
             raise ValueError(f"min_p_mode must be 'reference' or 'intended', got {self.min_p_mode!r}")
+        RequestSampling(top_p=self.top_p, top_k=self.top_k, repetition_penalty=self.repetition_penalty,
+                        repetition_window=self.repetition_window)  # the same ranges
 
     @property
     def effective_min_p(self) -> float:
@@ -202,12 +209,21 @@ class RequestSampling:
     """Sampling of one request (per-request settings of the server and the façade).  ``None`` fields take the server's or
     caller's ``GenerationSettings``: ``temperature`` <- ``default_temp``, ``fast_temperature`` <- ``default_fast_temp``,
     ``min_p`` <- ``min_p`` (then through that settings' ``min_p_mode``, ``effective_min_p``).  ``seed`` (0 .. 2**64 - 1) keys the
-    request's draws: the same seed gives the same ids in any slot of any batch ("per-request sampling")."""
+    request's draws: the same seed gives the same ids in any slot of any batch ("per-request sampling").
+
+    Filters of the sampled picks, ``None`` <- the settings' field of the same name: ``top_p`` (0 < p <= 1; 1 =
+    off), ``top_k`` (>= 0; 0 = off), ``repetition_penalty`` (1 .. 10; 1 = off) over the ids the same step produced in the
+    request's last ``repetition_window`` (1 .. 64) frames.  They act only where the request samples: a greedy slow token or
+    greedy depth codes ignore them."""
 
     temperature: Optional[float] = None
     fast_temperature: Optional[float] = None
     min_p: Optional[float] = None
     seed: Optional[int] = None
+    top_p: Optional[float] = None
+    top_k: Optional[int] = None
+    repetition_penalty: Optional[float] = None
+    repetition_window: Optional[int] = None
 
     def __post_init__(self):
         import math
@@ -220,6 +236,20 @@ class RequestSampling:
             raise ValueError(f"min_p must be in [0, 1), got {self.min_p!r}")
         if self.seed is not None and not (0 <= int(self.seed) < 2**64):
             raise ValueError(f"seed must be in [0, 2**64), got {self.seed!r}")
+        if self.top_p is not None and not (0 < self.top_p <= 1):
+            raise ValueError(f"top_p must be in (0, 1], got {self.top_p!r}")
+        if self.top_k is not None and not (isinstance(self.top_k, int) and not isinstance(self.top_k, bool) and 0 <= self.top_k < 2**31):
+            raise ValueError(f"top_k must be an integer >= 0, got {self.top_k!r}")
+        if self.repetition_penalty is not None and not (1 <= self.repetition_penalty <= 10):
+            raise ValueError(f"repetition_penalty must be in [1, 10], got {self.repetition_penalty!r}")
+        w = self.repetition_window
+        if w is not None and not (isinstance(w, int) and not isinstance(w, bool) and 1 <= w <= 64):
+            raise ValueError(f"repetition_window must be an integer in [1, 64], got {w!r}")
+
+    @property
+    def filters_on(self) -> bool:
+        """Whether some filter of a resolved entry is on (it still acts only on the picks that sample)."""
+        return (self.top_p is not None and self.top_p < 1) or bool(self.top_k) or (self.repetition_penalty or 1.0) > 1
 
     @property
     def is_sampled(self) -> bool:
@@ -234,7 +264,9 @@ class RequestSampling:
         t = float(self.temperature if self.temperature is not None else settings.default_temp)
         ft = float(self.fast_temperature if self.fast_temperature is not None else max(fast_default, 0.0))
         cut = GenerationSettings(min_p=self.min_p if self.min_p is not None else settings.min_p, min_p_mode=settings.min_p_mode).effective_min_p
-        out = RequestSampling(max(t, 0.0), max(ft, 0.0), cut, self.seed)
+        pick = lambda name: getattr(self, name) if getattr(self, name) is not None else getattr(settings, name)
+        out = RequestSampling(max(t, 0.0), max(ft, 0.0), cut, self.seed, float(pick("top_p")), int(pick("top_k")),
+                              float(pick("repetition_penalty")), int(pick("repetition_window")))
         if out.seed is None and draw_seed and out.is_sampled:
             out.seed = int.from_bytes(os.urandom(8), "little")
         return out

@@ -49,10 +49,91 @@ struct ArgmaxScratch {  // LDS of one call; a workgroup that makes several calls
   int id;
 };
 
+// ---- per-request filters of a sampled row (SmolttsSlotFilters, include/smoltts_hip.h; host model: smoltts_amd/sampling.py) ----
+// Order: repetition penalty -> top_k -> top_p -> min_p -> Gumbel key.  Both thresholds are found by bisection over an
+// order-preserving integer image of the floats (32 rounds for top_k over the penalised logits, 31 for top_p over -z >= 0), one
+// workgroup reduction per round.  Every reduced value is an exact integer (counts; masses quantised to multiples of 2^-40 and
+// summed in fp64, exact up to 2^53), so the sums do not depend on the order, the lane or the launch geometry.
+struct FilterScratch {  // LDS of the filter rounds: two slots used in turn, so that one barrier per round is enough
+  double m[2][4];
+  int c[2][4];
+};
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, true); }
+template <bool ROWS32>
+__device__ __forceinline__ uint32_t swap_u32(uint32_t x, int lane) {  // the value of lane ^ 16 (ROWS32: lane ^ 32), as top2_swap
+  const bool upper = (lane & (ROWS32 ? 32 : 16)) != 0;
+  if (ROWS32) {
+    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return upper ? r[0] : r[1];
+  }
+  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+  return upper ? r[0] : r[1];
+}
+// Wave sums on the VALU (the butterfly of cand_pick_wave): every lane returns the total.
+__device__ __forceinline__ int wave_sum_i32(int x, int lane) {
+  x += (int)dpp_u32<0xB1>(x);
+  x += (int)dpp_u32<0x4E>(x);
+  x += (int)dpp_u32<0x141>(x);
+  x += (int)dpp_u32<0x140>(x);
+  x += (int)swap_u32<false>(x, lane);
+  x += (int)swap_u32<true>(x, lane);
+  return x;
+}
+#define ST_F64_STEP(FETCH)                                                         \
+  {                                                                                \
+    const uint64_t b_ = (uint64_t)__double_as_longlong(x);                         \
+    const uint32_t lo_ = FETCH((uint32_t)b_), hi_ = FETCH((uint32_t)(b_ >> 32));   \
+    x += __longlong_as_double((long long)(((uint64_t)hi_ << 32) | lo_));           \
+  }
+__device__ __forceinline__ double wave_sum_f64(double x, int lane) {  // exact for the integer-valued masses: any order gives the same bits
+#define ST_SWAP16(V) swap_u32<false>((V), lane)
+#define ST_SWAP32(V) swap_u32<true>((V), lane)
+  ST_F64_STEP(dpp_u32<0xB1>)
+  ST_F64_STEP(dpp_u32<0x4E>)
+  ST_F64_STEP(dpp_u32<0x141>)
+  ST_F64_STEP(dpp_u32<0x140>)
+  ST_F64_STEP(ST_SWAP16)
+  ST_F64_STEP(ST_SWAP32)
+#undef ST_SWAP16
+#undef ST_SWAP32
+  return x;
+}
+#undef ST_F64_STEP
+__device__ __forceinline__ int wg_sum_i32(int x, FilterScratch& F, int round, int lane, int wave) {
+  x = wave_sum_i32(x, lane);
+  int* sh = F.c[round & 1];
+  if (lane == 0) sh[wave] = x;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__device__ __forceinline__ double wg_sum_f64(double x, FilterScratch& F, int round, int lane, int wave) {
+  x = wave_sum_f64(x, lane);
+  double* sh = F.m[round & 1];
+  if (lane == 0) sh[wave] = x;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// Order-preserving image of a float (a > b <=> ord_key(a) > ord_key(b); -0 and +0 share one key)
+__device__ __forceinline__ uint32_t ord_key(float x) {
+  uint32_t b = __float_as_uint(x);
+  if (x == 0.f) b = 0;
+  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+// z <= 0 -> the bits of -z (sign cleared: one image for both zeros): a smaller image is a larger z
+__device__ __forceinline__ uint32_t nz_bits(float z) { return __float_as_uint(z) & 0x7FFFFFFFu; }
+// mass of a column: exp(z) rounded down to a multiple of 2^-40, held as the integer it is a multiple of (exact in fp32)
+__device__ __forceinline__ float mass_q(float z) { return floorf(expf(z) * 0x1p40f); }
+__device__ __forceinline__ float penalised(float x, float r, float inv_r) { return x > 0.f ? x * inv_r : x * r; }
+
 // One workgroup of exactly 256 threads picks the id of logits row `row` (n_cols entries); every thread returns it.
 // `r`: the row's index into margin / margin_mask / the sampling arrays.  Greedy rows update margin[r] / margin_at[r].
+// FILTERS: the instantiation that reads sa.filters (slot mode's sampled forms; `F` is its LDS).  A row whose entry is off, and
+// every greedy row, takes one uniform branch and then the instructions of the plain instantiation.
+template <bool FILTERS = false>
 __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_vec, int r, float* margin, const int* margin_mask,
-                                          const SampleArgs& sa, ArgmaxScratch& S) {
+                                          const SampleArgs& sa, ArgmaxScratch& S, FilterScratch* F = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the row's sampling parameters (uniform in the workgroup: scalar loads, no divergence)
   float temp = sa.temp, min_p = sa.min_p;
@@ -64,6 +145,68 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     min_p = temp > 0.f ? en.min_p : 0.f;
     seed = en.seed;
     key_slot = 0;
+  }
+  const bool vec = (n_cols & 3) == 0 && ld_vec && n_cols <= 8 * 1024;
+  // the row's filters (uniform).  History id h sits in lane h of every wave: the loops over it read it with v_readlane.
+  int top_k = 0, hn = 0, hid = -1;
+  float top_p = 0.f, pen = 1.f, inv_pen = 1.f;
+  bool fon = false;
+  uint32_t vmask = 0;                      // vector path: bit i * 4 + c = column tid * 4 + i * 1024 + c is in the history
+  uint64_t pm0 = 0, pm1 = 0, pm2 = 0, pm3 = 0;  // scalar path: bit c of pm[g] = column tid + 256 * (g * 64 + c) is
+  if constexpr (FILTERS) {
+    if (sa.filters && temp > 0.f) {
+      const SmolttsSlotFilters fe = sa.filters[r];
+      top_k = fe.top_k > 0 && fe.top_k < n_cols ? fe.top_k : 0;
+      top_p = fe.top_p > 0.f && fe.top_p < 1.f ? fe.top_p : 0.f;
+      if (fe.penalty > 1.f && fe.window > 0 && sa.hist) {
+        const int w = fe.window < 64 ? fe.window : 64;
+        int f = 0;
+        if (sa.hist_len) {
+          hn = sa.hist_len[r];
+        } else {
+          f = sa.frames ? sa.frames[r] : 0;
+          hn = f < sa.hist_frames ? f : sa.hist_frames;
+        }
+        hn = hn < w ? hn : w;
+        if (hn < 0) hn = 0;
+        if (lane < hn) hid = sa.hist[(long)r * sa.hist_slot_stride + (long)(sa.hist_len ? lane : f - 1 - lane) * sa.hist_frame_stride];
+        pen = fe.penalty; inv_pen = fe.inv_penalty;
+        for (int h = 0; h < hn; ++h) {
+          const int id = __builtin_amdgcn_readlane(hid, h);
+          if ((unsigned)id >= (unsigned)n_cols) continue;
+          if (vec) {
+            if (((id >> 2) & 255) == tid) vmask |= 1u << (((id >> 10) << 2) | (id & 3));
+          } else if ((id & 255) == tid) {
+            const int c = id >> 8;
+            if ((c >> 6) == 0) pm0 |= 1ull << (c & 63);
+            if ((c >> 6) == 1) pm1 |= 1ull << (c & 63);
+            if ((c >> 6) == 2) pm2 |= 1ull << (c & 63);
+            if ((c >> 6) == 3) pm3 |= 1ull << (c & 63);
+          }
+        }
+      }
+      fon = top_k > 0 || top_p > 0.f || hn > 0;
+    }
+  }
+  // scalar path of a filtered row: BODY(value after the penalty, column), columns ascending within a thread
+#define ST_SGROUP(PM, G, BODY)                                          \
+  for (int c_ = 0; c_ < 64; ++c_) {                                     \
+    const int j_ = tid + 256 * ((G) * 64 + c_);                         \
+    if (j_ >= n_cols) break;                                            \
+    float x_ = row[j_];                                                 \
+    if (((PM) >> c_) & 1) x_ = penalised(x_, pen, inv_pen);             \
+    BODY(x_, j_)                                                        \
+  }
+#define ST_SCOLS(BODY)                                                                       \
+  {                                                                                          \
+    ST_SGROUP(pm0, 0, BODY) ST_SGROUP(pm1, 1, BODY) ST_SGROUP(pm2, 2, BODY) ST_SGROUP(pm3, 3, BODY) \
+    for (int j_ = tid + 65536; j_ < n_cols; j_ += 256) {                                     \
+      float x_ = row[j_];                                                                    \
+      bool hit_ = false;                                                                     \
+      for (int h_ = 0; h_ < hn; ++h_) hit_ |= __builtin_amdgcn_readlane(hid, h_) == j_;      \
+      if (hit_) x_ = penalised(x_, pen, inv_pen);                                            \
+      BODY(x_, j_)                                                                           \
+    }                                                                                        \
   }
   Top2 t{-INFINITY, 0x7fffffff, -INFINITY};
 #define ST_TAKE(V, J)                                                                               \
@@ -77,7 +220,6 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
   }
   // the whole row in one round trip: up to 8 float4 per thread, all requested before the first compare (a scalar loop is a
   // chain of n_cols / 256 dependent L2 latencies: 8 for a 2048-entry codebook); kept for the sampling pass
-  const bool vec = (n_cols & 3) == 0 && ld_vec && n_cols <= 8 * 1024;
   float4 v[8];
   if (vec) {
 #pragma unroll
@@ -85,11 +227,24 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
       const int j = tid * 4 + i * 1024;
       v[i] = j < n_cols ? *reinterpret_cast<const float4*>(row + j) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
     }
+    if constexpr (FILTERS) {
+      if (vmask) {  // the penalty, patched into the row registers before the first pass
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          if ((vmask >> (i * 4)) & 1) v[i].x = penalised(v[i].x, pen, inv_pen);
+          if ((vmask >> (i * 4 + 1)) & 1) v[i].y = penalised(v[i].y, pen, inv_pen);
+          if ((vmask >> (i * 4 + 2)) & 1) v[i].z = penalised(v[i].z, pen, inv_pen);
+          if ((vmask >> (i * 4 + 3)) & 1) v[i].w = penalised(v[i].w, pen, inv_pen);
+        }
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int j = tid * 4 + i * 1024;
       if (j < n_cols) { ST_TAKE(v[i].x, j) ST_TAKE(v[i].y, j + 1) ST_TAKE(v[i].z, j + 2) ST_TAKE(v[i].w, j + 3) }
     }
+  } else if (FILTERS && fon) {
+    ST_SCOLS(ST_TAKE)
   } else {
     for (int j = tid; j < n_cols; j += 256) ST_TAKE(row[j], j)
   }
@@ -108,25 +263,95 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     if (!sa.table && sa.salt) seed += 0x9E3779B97F4A7C15ULL * (uint64_t)sa.salt[r];
     const float inv_t = 1.0f / temp;
     const float cut = min_p > 0.f ? logf(min_p) : -INFINITY;
+    // the filters' thresholds: a column stays iff ord_key(x') >= tk (top_k) and nz_bits(z) <= wu (top_p)
+    uint32_t tk = 0, wu = 0x7FFFFFFFu;
+    if constexpr (FILTERS) {
+      int round = 0;
+      if (top_k > 0) {  // tk = the image of the k-th largest value: the largest image that at least k columns reach
+        for (int bit = 31; bit >= 0; --bit) {
+          const uint32_t cand = tk | (1u << bit);
+          int c = 0;
+#define ST_CNT(V, J) c += ord_key(V) >= cand;
+          if (vec) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              if (tid * 4 + i * 1024 < n_cols) { ST_CNT(v[i].x, 0) ST_CNT(v[i].y, 0) ST_CNT(v[i].z, 0) ST_CNT(v[i].w, 0) }
+            }
+          } else {
+            ST_SCOLS(ST_CNT)
+          }
+#undef ST_CNT
+          if (wg_sum_i32(c, *F, round++, lane, wave) >= top_k) tk = cand;
+        }
+        if (vec) {  // the columns top_k removes leave the row registers
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            if (ord_key(v[i].x) < tk) v[i].x = -INFINITY;
+            if (ord_key(v[i].y) < tk) v[i].y = -INFINITY;
+            if (ord_key(v[i].z) < tk) v[i].z = -INFINITY;
+            if (ord_key(v[i].w) < tk) v[i].w = -INFINITY;
+          }
+        }
+      }
+      if (top_p > 0.f) {  // wu = the largest image whose strictly-more-probable mass is below top_p * total
+        float fq[32];     // vector path: the columns' masses (an absent column's is 0)
+        double s = 0.0;
+#define ST_MASS(V, J) if (ord_key(V) >= tk) s += (double)mass_q(((V) - a.v1) * inv_t);
+        if (vec) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            fq[i * 4] = mass_q((v[i].x - a.v1) * inv_t); fq[i * 4 + 1] = mass_q((v[i].y - a.v1) * inv_t);
+            fq[i * 4 + 2] = mass_q((v[i].z - a.v1) * inv_t); fq[i * 4 + 3] = mass_q((v[i].w - a.v1) * inv_t);
+            s += ((double)fq[i * 4] + (double)fq[i * 4 + 1]) + ((double)fq[i * 4 + 2] + (double)fq[i * 4 + 3]);
+          }
+        } else {
+          ST_SCOLS(ST_MASS)
+        }
+#undef ST_MASS
+        const double P = (double)top_p * wg_sum_f64(s, *F, round++, lane, wave);
+        wu = 0;
+        for (int bit = 30; bit >= 0; --bit) {
+          const uint32_t cand = wu | (1u << bit);
+          double m = 0.0;
+#define ST_ABOVE(V, Q) if (nz_bits(((V) - a.v1) * inv_t) < cand) m += (double)(Q);
+#define ST_ABOVE_S(V, J) if (ord_key(V) >= tk) ST_ABOVE(V, mass_q(((V) - a.v1) * inv_t))
+          if (vec) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              ST_ABOVE(v[i].x, fq[i * 4]) ST_ABOVE(v[i].y, fq[i * 4 + 1]) ST_ABOVE(v[i].z, fq[i * 4 + 2]) ST_ABOVE(v[i].w, fq[i * 4 + 3])
+            }
+          } else {
+            ST_SCOLS(ST_ABOVE_S)
+          }
+#undef ST_ABOVE_S
+#undef ST_ABOVE
+          if (wg_sum_f64(m, *F, round++, lane, wave) < P) wu = cand;
+        }
+      }
+    }
     Top2 k{-INFINITY, 0x7fffffff, -INFINITY};
 #define ST_KEY(V, J)                                                  \
   {                                                                   \
     const float z = ((V) - a.v1) * inv_t; /* <= 0 */                  \
-    if (z >= cut) {                                                   \
+    if (z >= cut && (!FILTERS || nz_bits(z) <= wu)) {                 \
       const float u = uniform01(seed, key_slot, frame, sa.step, (J)); \
       const float key = z - logf(-logf(u));                           \
       if (key > k.v1) { k.v1 = key; k.i1 = (J); }                     \
     }                                                                 \
   }
+#define ST_KEY_S(V, J) if (ord_key(V) >= tk) ST_KEY(V, J)
     if (vec) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int j = tid * 4 + i * 1024;
         if (j < n_cols) { ST_KEY(v[i].x, j) ST_KEY(v[i].y, j + 1) ST_KEY(v[i].z, j + 2) ST_KEY(v[i].w, j + 3) }
       }
+    } else if (FILTERS && fon) {
+      ST_SCOLS(ST_KEY_S)
     } else {
       for (int j = tid; j < n_cols; j += 256) ST_KEY(row[j], j)
     }
+#undef ST_KEY_S
 #undef ST_KEY
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -139,6 +364,8 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     const Top2 w = top2_merge(top2_merge(S.sh2[0], S.sh2[1]), top2_merge(S.sh2[2], S.sh2[3]));
     a.i1 = w.i1;
   }
+#undef ST_SCOLS
+#undef ST_SGROUP
   if (a.i1 < 0 || a.i1 >= n_cols) a.i1 = 0;  // all-NaN row: stay inside the tables
   if (tid == 0) {
     if (temp <= 0.f && margin && (margin_mask == nullptr || margin_mask[r])) {

@@ -201,6 +201,17 @@ struct SampleArgs {
   // slot mode, or null: row r's own temperature (step 0: temp, else fast_temp), min_p and seed replace the fields above, and a
   // sampled row draws with the request key (seed unsalted, slot 0: argmax_dev.h)
   const SmolttsSlotSampling* table;
+  // per-row filters of the sampled rows (slot mode), or null: top_k / top_p / repetition penalty (argmax_dev.h).  Read only by
+  // the FILTERS instantiations of the picking kernels, which a launcher selects when this pointer is set.
+  const SmolttsSlotFilters* filters;
+  // the penalty's history of row r, newest first: entry h = hist[r * hist_slot_stride + fi * hist_frame_stride] with
+  //   hist_len == null (a session's codes array, offset to this step's column): fi = frames[r] - 1 - h, h < min(window, frames[r], hist_frames)
+  //   hist_len != null (explicit lists):                                        fi = h,                 h < min(window, hist_len[r])
+  const int32_t* hist;
+  int64_t hist_slot_stride;
+  int32_t hist_frame_stride;
+  int32_t hist_frames;
+  const int32_t* hist_len;
 };
 
 // Launchers implemented across the .hip files (all asynchronous on `stream`).

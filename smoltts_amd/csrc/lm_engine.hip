@@ -73,23 +73,29 @@ struct SmolttsSession {
   hipEvent_t stage_ev[8];      // recorded behind the async copies out of each area
   bool stage_ev_live[8];
   int stage_next;
-  // captured graphs, one set per form (GRAPH_FORMS: which picks sample; index 0 outside slot mode), each created when first needed
-  hipGraphExec_t graph_exec[4];   // one decode frame (slow step + tail)
-  bool graph_ready[4];
-  hipGraphExec_t tail_exec[4];    // the tail alone (slow head + depth steps + commit) as run after a prefill
-  bool tail_ready[4];
-  hipGraphExec_t multi_exec[4];   // `multi_frames` consecutive decode frames in one graph (fewer graph launches per tick / chunk)
-  bool multi_ready[4];
+  // captured graphs, one set per form (GRAPH_FORMS: which picks sample, and whether some slot filters; index 0 outside slot mode),
+  // each created when first needed
+  hipGraphExec_t graph_exec[8];   // one decode frame (slow step + tail)
+  bool graph_ready[8];
+  hipGraphExec_t tail_exec[8];    // the tail alone (slow head + depth steps + commit) as run after a prefill
+  bool tail_ready[8];
+  hipGraphExec_t multi_exec[8];   // `multi_frames` consecutive decode frames in one graph (fewer graph launches per tick / chunk)
+  bool multi_ready[8];
   int form;                       // the form the next launches are built / replayed in (pick_form)
   // slot mode (smoltts_session_set_slot_sampling): per-slot sampling entries
   bool slot_mode;
   SmolttsSlotSampling* slot_tab;      // [B] read by the picks; null until slot mode
   SmolttsSlotSampling* slot_tab_area; // where it is carved (the slab's tail): [B] table, [B] upload entries, [B] upload slots
   SmolttsSlotSampling* h_slot;        // host mirror of the table: chooses the graph form
-  char* h_slot_stage;                 // STAGE_RING pinned areas of B entries + B slots, used in turn
+  char* h_slot_stage;                 // STAGE_RING pinned areas (B entries + B slots of each table), used in turn
   hipEvent_t slot_ev[STAGE_RING];
   bool slot_ev_live[STAGE_RING];
   int slot_next;
+  // ... and per-slot filter entries (smoltts_session_set_slot_filters): uploaded through the same ring (each area holds a
+  // filter part behind its sampling part)
+  SmolttsSlotFilters* filt_tab;       // [B] read by the sampled picks of slot mode; all zero = off
+  SmolttsSlotFilters* filt_tab_area;  // [B] table, [B] upload entries, [B] upload slots
+  bool* h_filt_on;                    // host mirror: which slots' entries are on (chooses the graph form)
   int flight_limit;            // SMOLTTS_MAX_FRAMES_IN_FLIGHT as read at creation (0 = unbounded)
   int multi_frames;            // frames per multi-frame graph (1 = single-frame graphs only): SMOLTTS_FRAMES_PER_GRAPH, else
                                // smoltts_session_set_frames_per_graph, else min(n_frames, 4) of the largest decode call so far
@@ -170,6 +176,7 @@ size_t carve(SmolttsSession* s, char* base) {
   // slot mode only (smoltts_session_set_slot_sampling): the table, then the upload area (B entries, B slot numbers) -- the
   // tail of the slab, in use once the session enters slot mode
   s->slot_tab_area = cv.take<SmolttsSlotSampling>(2 * B + (B * sizeof(int) + sizeof(SmolttsSlotSampling) - 1) / sizeof(SmolttsSlotSampling));
+  s->filt_tab_area = cv.take<SmolttsSlotFilters>(2 * B + (B * sizeof(int) + sizeof(SmolttsSlotFilters) - 1) / sizeof(SmolttsSlotFilters));
   return cv.off;
 }
 
@@ -188,6 +195,11 @@ __global__ void init_state_kernel(int B, int n_fast, int* iota, int* fastpos, in
 
 // Slot mode: table[slots[i]] = entries[i] for the n entries of one upload (distinct slots)
 __global__ void slot_sampling_scatter_kernel(int n, const SmolttsSlotSampling* entries, const int* slots, SmolttsSlotSampling* table) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) table[slots[i]] = entries[i];
+}
+
+__global__ void slot_filters_scatter_kernel(int n, const SmolttsSlotFilters* entries, const int* slots, SmolttsSlotFilters* table) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) table[slots[i]] = entries[i];
 }
@@ -270,6 +282,8 @@ struct CommitArgs {
                      // interrupted launch, a caller's odd count) can invert a later launch's "who arrived last" decision
 };
 
+// FILTERS: the instantiation whose picks read SampleArgs.filters (slot mode's sampled forms)
+template <bool FILTERS>
 __global__ __launch_bounds__(256) void commit_embed_kernel(CommitArgs a, EmbedTables t, float* xt, EmitDev emit) {
   __shared__ int s_col[64];
   __shared__ float sh4[4];
@@ -304,8 +318,14 @@ __global__ __launch_bounds__(256) void commit_embed_kernel(CommitArgs a, EmbedTa
     if (c_slow) id_slow = s_id[0];
     if (c_last) id_last = s_id[1];
   }
-  if (a.slow_logits && !c_slow) id_slow = argmax_row(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0]);
-  if (a.last_logits && !c_last) id_last = argmax_row(a.last_logits + (long)b * a.last_cols, a.last_cols, (a.last_cols & 3) == 0, b, a.margin, a.mask, a.last_sa, s_pick[1]);
+  if constexpr (FILTERS) {
+    __shared__ FilterScratch s_filt[2];
+    if (a.slow_logits && !c_slow) id_slow = argmax_row<true>(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0], &s_filt[0]);
+    if (a.last_logits && !c_last) id_last = argmax_row<true>(a.last_logits + (long)b * a.last_cols, a.last_cols, (a.last_cols & 3) == 0, b, a.margin, a.mask, a.last_sa, s_pick[1], &s_filt[1]);
+  } else {
+    if (a.slow_logits && !c_slow) id_slow = argmax_row(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0]);
+    if (a.last_logits && !c_last) id_last = argmax_row(a.last_logits + (long)b * a.last_cols, a.last_cols, (a.last_cols & 3) == 0, b, a.margin, a.mask, a.last_sa, s_pick[1]);
+  }
   int f = 0;
   bool live = false;
   if (tid < 64) { f = a.frames[b]; live = a.do_commit && a.mask[b]; }
@@ -465,7 +485,13 @@ bool fast_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & 2)
 SampleArgs pick_args(const SmolttsSession* s, int step) {
   if (s->slot_mode) {
     const bool sampled = step == 0 ? slow_sampled(s) : fast_sampled(s);
-    return SampleArgs{0.f, 0.f, 0, step, 0, s->frames, nullptr, s->margin_at, sampled ? s->slot_tab : nullptr};
+    SampleArgs sa{0.f, 0.f, 0, step, 0, s->frames, nullptr, s->margin_at, sampled ? s->slot_tab : nullptr};
+    if (sampled && (s->form & 4)) {  // the filters of the sampled rows; the penalty's history: this step's column of the slot's emitted frames
+      sa.filters = s->filt_tab;
+      sa.hist = s->codes + step; sa.hist_slot_stride = (int64_t)s->max_frames * (1 + s->e->cfg.n_fast);
+      sa.hist_frame_stride = 1 + s->e->cfg.n_fast; sa.hist_frames = s->max_frames;
+    }
+    return sa;
   }
   if (step == 0) return SampleArgs{s->temp, s->min_p, s->seed, 0, 0, s->frames, s->salt, s->margin_at, nullptr};
   return SampleArgs{s->fast_temp, s->fast_temp > 0.f ? s->min_p : 0.f, s->seed, step, 0, s->frames, s->salt, s->margin_at, nullptr};
@@ -497,7 +523,10 @@ int launch_commit_embed(SmolttsSession* s, int do_commit, int advance_pos, hipSt
     if (commit_cand_last(s)) { a.last_cand = s->cand; a.last_tiles = (c.codebook_size + 15) / 16; }
   }
   const EmitDev em{s->x3n, gamma_at(e, e->w.layers[0].attn_norm), nullptr, nullptr, s->ssq};
-  hipLaunchKernelGGL(commit_embed_kernel, dim3(s->B), dim3(256), 0, st, a, embed_tables(e), s->xt, em);
+  if (picks && (a.slow_sa.filters || a.last_sa.filters))
+    hipLaunchKernelGGL(commit_embed_kernel<true>, dim3(s->B), dim3(256), 0, st, a, embed_tables(e), s->xt, em);
+  else
+    hipLaunchKernelGGL(commit_embed_kernel<false>, dim3(s->B), dim3(256), 0, st, a, embed_tables(e), s->xt, em);
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }
@@ -648,12 +677,12 @@ int stage_upload(SmolttsSession* s, const int32_t* slots_host, const int32_t* la
 }
 
 void drop_multi_graphs(SmolttsSession* s) {
-  for (int f = 0; f < 4; ++f)
+  for (int f = 0; f < 8; ++f)
     if (s->multi_ready[f]) { (void)hipGraphExecDestroy(s->multi_exec[f]); s->multi_ready[f] = false; }
 }
 
 void drop_graphs(SmolttsSession* s) {
-  for (int f = 0; f < 4; ++f) {
+  for (int f = 0; f < 8; ++f) {
     if (s->graph_ready[f]) { (void)hipGraphExecDestroy(s->graph_exec[f]); s->graph_ready[f] = false; }
     if (s->tail_ready[f]) { (void)hipGraphExecDestroy(s->tail_exec[f]); s->tail_ready[f] = false; }
   }
@@ -695,13 +724,15 @@ int arm_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos
   return SMOLTTS_OK;
 }
 
-// The form of the frame launches: bit 0 = some slot samples its slow token, bit 1 = some slot samples its depth codes.  Outside
+// The form of the frame launches: bit 0 = some slot samples its slow token, bit 1 = some slot samples its depth codes, bit 2 = some
+// slot's filter entry is on (the sampled picks are then the FILTERS instantiations; without it they are the parent's kernels).  Outside
 // slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
 // point that launches or captures picks, after the last change of the table.
 void pick_form(SmolttsSession* s) {
   int f = 0;
   if (s->slot_mode)
-    for (int b = 0; b < s->B; ++b) f |= (s->h_slot[b].temp > 0.f ? 1 : 0) | (s->h_slot[b].fast_temp > 0.f ? 2 : 0);
+    for (int b = 0; b < s->B; ++b) f |= (s->h_slot[b].temp > 0.f ? 1 : 0) | (s->h_slot[b].fast_temp > 0.f ? 2 : 0) | (s->h_filt_on[b] ? 4 : 0);
+  if ((f & 3) == 0) f = 0;  // nothing samples: the filters have nothing to act on
   s->form = f;
 }
 
@@ -1067,6 +1098,7 @@ void smoltts_session_destroy(SmolttsSession* s) {
     if (s->slot_ev[k]) (void)hipEventDestroy(s->slot_ev[k]);
   if (s->h_slot_stage) (void)hipHostFree(s->h_slot_stage);
   delete[] s->h_slot;
+  delete[] s->h_filt_on;
   delete s;
 }
 
@@ -1242,6 +1274,53 @@ int smoltts_session_set_sampling(SmolttsSession* s, float temp, float fast_temp,
   return SMOLTTS_OK;
 }
 
+namespace {
+size_t slot_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotSampling) + sizeof(int)); }
+size_t filt_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotFilters) + sizeof(int)); }
+size_t ring_area_bytes(const SmolttsSession* s) { return slot_area_bytes(s) + filt_area_bytes(s); }
+
+// Enter slot mode (first per-slot call of either kind): host mirror, pinned ring, events; every slot greedy with seed 0 and
+// its filters off
+int enter_slot_mode(SmolttsSession* s, hipStream_t st) {
+  if (s->slot_mode) return SMOLTTS_OK;
+  const size_t B = s->B;
+  s->h_slot = new (std::nothrow) SmolttsSlotSampling[B];
+  ST_REQUIRE(s->h_slot, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
+  memset(s->h_slot, 0, B * sizeof(SmolttsSlotSampling));
+  delete[] s->h_filt_on;
+  s->h_filt_on = new (std::nothrow) bool[B]();
+  ST_REQUIRE(s->h_filt_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
+  if (hipHostMalloc((void**)&s->h_slot_stage, ring_area_bytes(s) * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
+    s->h_slot_stage = nullptr;
+    delete[] s->h_slot;
+    s->h_slot = nullptr;
+    set_error("session_set_slot_sampling: hipHostMalloc failed");
+    return SMOLTTS_E_HIP;
+  }
+  for (int k = 0; k < STAGE_RING; ++k) {
+    if (hipEventCreateWithFlags(&s->slot_ev[k], hipEventDisableTiming) != hipSuccess) {
+      for (int j = 0; j <= k; ++j) {
+        if (j < k) (void)hipEventDestroy(s->slot_ev[j]);
+        s->slot_ev[j] = nullptr;
+      }
+      (void)hipHostFree(s->h_slot_stage);
+      s->h_slot_stage = nullptr;
+      delete[] s->h_slot;
+      s->h_slot = nullptr;
+      set_error("session_set_slot_sampling: hipEventCreate failed");
+      return SMOLTTS_E_HIP;  // (slot mode is not entered)
+    }
+  }
+  s->slot_tab = s->slot_tab_area;
+  s->filt_tab = s->filt_tab_area;
+  ST_CHECK_HIP(hipMemsetAsync(s->slot_tab, 0, B * sizeof(SmolttsSlotSampling), st));
+  ST_CHECK_HIP(hipMemsetAsync(s->filt_tab, 0, B * sizeof(SmolttsSlotFilters), st));
+  s->slot_mode = true;
+  drop_graphs(s);  // (the session-wide set: slot mode builds its own)
+  return SMOLTTS_OK;
+}
+}  // namespace
+
 // Slot mode: per-slot entries (include/smoltts_hip.h).  The host copies the entries into the next area of a pinned ring and queues
 // one copy + one scatter launch on `stream`; it waits only for the upload that last used that area (an event), never for the stream.
 int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* temp_host,
@@ -1257,42 +1336,14 @@ int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_ho
                SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d: temperatures must be numbers, 0 <= min_p < 1", slots_host[i]);
   }
   hipStream_t st = (hipStream_t)stream;
-  const size_t B = s->B, area = B * sizeof(SmolttsSlotSampling) + B * sizeof(int);
-  if (!s->slot_mode) {  // enter slot mode: host mirror, pinned ring, events; every slot greedy with seed 0
-    s->h_slot = new (std::nothrow) SmolttsSlotSampling[B];
-    ST_REQUIRE(s->h_slot, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
-    memset(s->h_slot, 0, B * sizeof(SmolttsSlotSampling));
-    if (hipHostMalloc((void**)&s->h_slot_stage, area * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
-      s->h_slot_stage = nullptr;
-      delete[] s->h_slot;
-      s->h_slot = nullptr;
-      set_error("session_set_slot_sampling: hipHostMalloc failed");
-      return SMOLTTS_E_HIP;
-    }
-    for (int k = 0; k < STAGE_RING; ++k) {
-      if (hipEventCreateWithFlags(&s->slot_ev[k], hipEventDisableTiming) != hipSuccess) {
-        for (int j = 0; j <= k; ++j) {
-          if (j < k) (void)hipEventDestroy(s->slot_ev[j]);
-          s->slot_ev[j] = nullptr;
-        }
-        (void)hipHostFree(s->h_slot_stage);
-        s->h_slot_stage = nullptr;
-        delete[] s->h_slot;
-        s->h_slot = nullptr;
-        set_error("session_set_slot_sampling: hipEventCreate failed");
-        return SMOLTTS_E_HIP;  // (slot mode is not entered)
-      }
-    }
-    s->slot_tab = s->slot_tab_area;
-    ST_CHECK_HIP(hipMemsetAsync(s->slot_tab, 0, B * sizeof(SmolttsSlotSampling), st));
-    s->slot_mode = true;
-    drop_graphs(s);  // (the session-wide set: slot mode builds its own)
-  }
+  const size_t B = s->B;
+  ST_TRY(enter_slot_mode(s, st));
   if (n == 0) return SMOLTTS_OK;
   const int k = s->slot_next;
   s->slot_next = (k + 1) % STAGE_RING;
   if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
-  SmolttsSlotSampling* h = reinterpret_cast<SmolttsSlotSampling*>(s->h_slot_stage + (size_t)k * area);
+  const size_t area = slot_area_bytes(s);
+  SmolttsSlotSampling* h = reinterpret_cast<SmolttsSlotSampling*>(s->h_slot_stage + (size_t)k * ring_area_bytes(s));
   int* hi = reinterpret_cast<int*>(h + B);
   for (int i = 0; i < n; ++i) {
     SmolttsSlotSampling en;
@@ -1306,6 +1357,52 @@ int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_ho
   ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
   s->slot_ev_live[k] = true;
   hipLaunchKernelGGL(slot_sampling_scatter_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->slot_tab);
+  ST_CHECK_HIP(hipGetLastError());
+  return SMOLTTS_OK;
+}
+
+// The filter entries of slot mode, uploaded like the sampling entries (the filter part of the next ring area, one copy + one
+// scatter launch on `stream`).  Whether any entry is on is a bit of the graph form (pick_form): no graph is dropped here.
+int smoltts_session_set_slot_filters(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* top_p_host,
+                                     const int32_t* top_k_host, const float* penalty_host, const int32_t* window_host, void* stream) {
+  ST_REQUIRE(s && (n == 0 || (slots_host && top_p_host && top_k_host && penalty_host && window_host)), SMOLTTS_E_INVALID,
+             "session_set_slot_filters: null argument");
+  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_filters: %d entries, session holds %d slots", n, s->B);
+  for (int i = 0; i < n; ++i) {
+    ST_TRY(check_slot("session_set_slot_filters", slots_host[i], s->B));
+    for (int j = 0; j < i; ++j)
+      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_filters: slot %d listed twice", slots_host[i]);
+    const float r = penalty_host[i];
+    ST_REQUIRE(top_p_host[i] >= 0.f && top_p_host[i] <= 1.f && top_k_host[i] >= 0 && (r == 0.f || (r >= 1.f && r <= SMOLTTS_FILTER_MAX_PENALTY)) &&
+                   window_host[i] >= 0 && window_host[i] <= SMOLTTS_FILTER_MAX_WINDOW,
+               SMOLTTS_E_INVALID, "session_set_slot_filters: slot %d: 0 <= top_p <= 1, top_k >= 0, penalty 0 or in [1, %g], 0 <= window <= %d",
+               slots_host[i], (double)SMOLTTS_FILTER_MAX_PENALTY, SMOLTTS_FILTER_MAX_WINDOW);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t B = s->B;
+  ST_TRY(enter_slot_mode(s, st));
+  if (n == 0) return SMOLTTS_OK;
+  const int k = s->slot_next;
+  s->slot_next = (k + 1) % STAGE_RING;
+  if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
+  SmolttsSlotFilters* h = reinterpret_cast<SmolttsSlotFilters*>(s->h_slot_stage + (size_t)k * ring_area_bytes(s) + slot_area_bytes(s));
+  int* hi = reinterpret_cast<int*>(h + B);
+  for (int i = 0; i < n; ++i) {
+    SmolttsSlotFilters en;
+    memset(&en, 0, sizeof(en));
+    const float r = penalty_host[i];
+    en.top_p = top_p_host[i] < 1.f ? top_p_host[i] : 0.f;
+    en.top_k = top_k_host[i];
+    if (r > 1.f && window_host[i] > 0) { en.penalty = r; en.inv_penalty = 1.0f / r; en.window = window_host[i]; }
+    h[i] = en;
+    hi[i] = slots_host[i];
+    s->h_filt_on[slots_host[i]] = en.top_p > 0.f || en.top_k > 0 || en.window > 0;
+  }
+  SmolttsSlotFilters* up = s->filt_tab_area + B;  // device upload area: the same layout as the ring area's filter part
+  ST_CHECK_HIP(hipMemcpyAsync(up, h, filt_area_bytes(s), hipMemcpyHostToDevice, st));
+  ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
+  s->slot_ev_live[k] = true;
+  hipLaunchKernelGGL(slot_filters_scatter_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->filt_tab);
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }

@@ -36,13 +36,21 @@ int launch_embed(const int32_t* cols, int n_rows, int n_code_rows, const void* t
 // Row pick (argmax_dev.h) + optionally the next depth step's input: the embedding row of the picked code
 // (lm/generate.py:134-140: fast_embeddings(code + i*codebook_size)) as fp32 residual row (+ X3 operand / sums of squares when a
 // GEMM consumes it), and / or the precomputed layer-0 q | k | v of that row (QkvGather: no wqkv launch in the next step).
+// FILTERS: the instantiation whose pick reads SampleArgs.filters (launched only when that pointer is set)
+template <bool FILTERS>
 __global__ __launch_bounds__(256) void argmax_kernel(const float* logits, int n_cols, long ld, int* ids, int ids_stride,
                                                      float* margin, const int* margin_mask, const uint16_t* emb,
                                                      int emb_row_offset, int dim, float* xnext, EmitDev emit, SampleArgs sa, QkvGather qg) {
   __shared__ ArgmaxScratch S;
   __shared__ float sh4[4];
   const int r = blockIdx.x, tid = threadIdx.x;
-  const int id = argmax_row(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S);
+  int id;
+  if constexpr (FILTERS) {
+    __shared__ FilterScratch F;
+    id = argmax_row<true>(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S, &F);
+  } else {
+    id = argmax_row(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S);
+  }
   if (tid == 0) ids[(long)r * ids_stride] = id;
   if (emb == nullptr) return;
   const long erow = (long)id + emb_row_offset;
@@ -77,6 +85,8 @@ int launch_argmax(const float* logits, int n_rows, int n_cols, int64_t ld, int32
                   const EmitArgs* emit, const SampleArgs* sample, hipStream_t stream, const QkvGather* qkv) {
   SampleArgs sa{0.f, 0.f, 0, 0, 0, nullptr, nullptr, nullptr};
   if (sample) sa = *sample;
+  ST_REQUIRE(sa.filters == nullptr || (sa.table && (sa.hist == nullptr || (sa.hist_frame_stride > 0 && sa.hist_frames > 0))), SMOLTTS_E_INVALID,
+             "argmax: filters need the per-row table and a history layout");
   EmitDev e{nullptr, nullptr, nullptr, nullptr, nullptr};
   if (emit && emb) e = EmitDev{(char*)emit->x3a, emit->gamma_a, (char*)emit->x3b, emit->gamma_b, emit->ssq};
   QkvGather qg;
@@ -86,8 +96,12 @@ int launch_argmax(const float* logits, int n_rows, int n_cols, int64_t ld, int32
   ST_REQUIRE(emb == nullptr || (xnext && dim % 4 == 0), SMOLTTS_E_INVALID, "argmax: bad gather arguments");
   ST_REQUIRE(qg.table == nullptr || (qg.rope && qg.q_out && qg.kc && qg.vc && qg.pos >= 0 && qg.pos < qg.cache_len), SMOLTTS_E_INVALID,
              "argmax: bad q|k|v gather arguments");
-  hipLaunchKernelGGL(argmax_kernel, dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, ids, ids_stride, margin,
-                     margin_mask, (const uint16_t*)emb, emb_row_offset, dim, xnext, e, sa, qg);
+  if (sa.filters)
+    hipLaunchKernelGGL(argmax_kernel<true>, dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, ids, ids_stride, margin,
+                       margin_mask, (const uint16_t*)emb, emb_row_offset, dim, xnext, e, sa, qg);
+  else
+    hipLaunchKernelGGL(argmax_kernel<false>, dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, ids, ids_stride, margin,
+                       margin_mask, (const uint16_t*)emb, emb_row_offset, dim, xnext, e, sa, qg);
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }

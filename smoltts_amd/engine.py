@@ -130,7 +130,7 @@ _EXPORTS = [
     "smoltts_loudness_bytes", "smoltts_loudness_table_doubles", "smoltts_loudness_create", "smoltts_loudness_destroy",
     "smoltts_loudness_reset_slots", "smoltts_loudness_chunk", "smoltts_loudness_measure", "smoltts_loudness_scale",
     "smoltts_loudness_slot_state",
-    "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows",
+    "smoltts_session_set_slot_sampling", "smoltts_k_sample_rows", "smoltts_session_set_slot_filters", "smoltts_k_sample_rows_filtered",
     "smoltts_prefix_kv_bytes", "smoltts_session_save_prefix", "smoltts_session_install_prefix",
     "smoltts_k_seanet_resblock", "smoltts_k_seanet_last", "smoltts_k_rvq_upsample",
 ]
@@ -195,6 +195,8 @@ def load_library(path: Optional[Path] = None):
                                      C.c_int32, C.c_void_p, C.c_void_p]
     lib.smoltts_session_set_slot_sampling.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
     lib.smoltts_k_sample_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.smoltts_session_set_slot_filters.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+    lib.smoltts_k_sample_rows_filtered.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_void_p]
     lib.smoltts_session_measure_duplicate.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.smoltts_session_margin_at.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.smoltts_session_drop_graph.argtypes = [C.c_void_p]
@@ -474,6 +476,7 @@ class LMSession:
         kvf = KV_FORMATS[kv_dtype]
         self.engine, self.lib = engine, engine.lib
         self.B = max_batch
+        self.filtered_slots = set()  # slots whose filter entry on the device is on (set_slot_filters)
         self.max_seq = max_seq or engine.cfg.max_seq_len
         self.max_rows = max(max_rows, max_batch)
         self.max_frames = max_frames
@@ -697,6 +700,21 @@ class LMSession:
             self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_float * max(n, 1))(*[float(t) for t in temp]),
             (C.c_float * max(n, 1))(*[float(t) for t in fast_temp]), (C.c_float * max(n, 1))(*[float(p) for p in min_p]),
             (C.c_uint64 * max(n, 1))(*[int(x) & (2**64 - 1) for x in seed]), current_stream_ptr()), "smoltts_session_set_slot_sampling")
+
+    def set_slot_filters(self, slots: Sequence[int], top_p: Sequence[float], top_k: Sequence[int], penalty: Sequence[float],
+                         window: Sequence[int]) -> None:
+        """Per-slot filters of the sampled picks (``smoltts_session_set_slot_filters``): slot ``slots[i]`` keeps its ``top_k[i]``
+        largest logits (0: off), then the ``top_p[i]`` nucleus (0 or 1: off), after the repetition penalty ``penalty[i]`` (0 or
+        1: off) over the ids of its last ``window[i]`` frames.  Queued on the current stream like ``set_slot_sampling``."""
+        n = len(slots)
+        if not (len(top_p) == len(top_k) == len(penalty) == len(window) == n):
+            raise ValueError("slot filters: one value per slot in every list")
+        check(self.lib.smoltts_session_set_slot_filters(
+            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_float * max(n, 1))(*[float(p) for p in top_p]),
+            (C.c_int32 * max(n, 1))(*[int(k) for k in top_k]), (C.c_float * max(n, 1))(*[float(r) for r in penalty]),
+            (C.c_int32 * max(n, 1))(*[int(w) for w in window]), current_stream_ptr()), "smoltts_session_set_slot_filters")
+        for b, p, k, r, w in zip(slots, top_p, top_k, penalty, window):
+            (self.filtered_slots.add if (0 < p < 1 or k > 0 or (r > 1 and w > 0)) else self.filtered_slots.discard)(int(b))
 
     def measure_duplicate(self, code: int = -1, n_filter: int = 0) -> None:
         """Measurement aid (this session only): issue every launch of one kernel class twice; -1 switches it off."""

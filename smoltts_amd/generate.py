@@ -47,6 +47,15 @@ def _apply_slot_sampling(session: LMSession, slots: Sequence[int], sampling: Seq
     """Slot ``slots[i]`` samples with the resolved ``sampling[i]`` (slot mode; a greedy entry's seed is 0)."""
     session.set_slot_sampling(list(slots), [r.temperature for r in sampling], [r.fast_temperature for r in sampling],
                               [r.min_p for r in sampling], [r.seed or 0 for r in sampling])
+    # the slots' filter entries: uploaded where one is on, or where the slot's previous tenant left one on (cleared)
+    slots, sampling = list(slots), list(sampling)
+    todo = [i for i, (b, r) in enumerate(zip(slots, sampling)) if r.filters_on or b in session.filtered_slots]
+    if todo:
+        on = [sampling[i].filters_on for i in todo]
+        session.set_slot_filters([slots[i] for i in todo], [sampling[i].top_p if o else 0.0 for i, o in zip(todo, on)],
+                                 [sampling[i].top_k if o else 0 for i, o in zip(todo, on)],
+                                 [sampling[i].repetition_penalty if o else 0.0 for i, o in zip(todo, on)],
+                                 [sampling[i].repetition_window if o else 0 for i, o in zip(todo, on)])
 
 
 def resolve_sampling(sampling, settings: GenerationSettings, n: int) -> Optional[List[RequestSampling]]:

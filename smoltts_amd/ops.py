@@ -200,6 +200,47 @@ def sample_rows(logits: torch.Tensor, table: torch.Tensor, frames: Optional[torc
     return ids
 
 
+def slot_filter_table(top_p, top_k, penalty, window, device="cuda") -> torch.Tensor:
+    """Rows of ``SmolttsSlotFilters`` (top_p, top_k, penalty, fp32(1 / penalty), window, 0, 0, 0: 32 bytes each) as a uint8 device
+    tensor, normalised as ``smoltts_session_set_slot_filters`` does (top_p >= 1 -> 0; penalty <= 1 or window 0 -> all three 0)."""
+    import numpy as np
+
+    dt = np.dtype([("top_p", "<f4"), ("top_k", "<i4"), ("penalty", "<f4"), ("inv_penalty", "<f4"), ("window", "<i4"), ("reserved", "<i4", 3)])
+    a = np.zeros(len(top_p), dt)
+    tp = np.asarray(top_p, np.float32)
+    a["top_p"] = np.where(tp < 1, tp, 0)
+    a["top_k"] = top_k
+    r, w = np.asarray(penalty, np.float32), np.asarray(window, np.int32)
+    on = (r > 1) & (w > 0)
+    a["penalty"] = np.where(on, r, 0)
+    a["inv_penalty"] = np.where(on, np.float32(1.0) / np.where(on, r, np.float32(1.0)), 0).astype(np.float32)
+    a["window"] = np.where(on, w, 0)
+    return torch.from_numpy(a.view(np.uint8).copy()).to(device)
+
+
+def sample_rows_filtered(logits: torch.Tensor, table: torch.Tensor, filters: torch.Tensor, history: torch.Tensor, history_len: torch.Tensor,
+                         frames: Optional[torch.Tensor] = None, step: int = 0) -> torch.Tensor:
+    """``smoltts_k_sample_rows_filtered``: ``sample_rows`` with row r's filters ``filters`` row r (``slot_filter_table``) and its
+    explicit history: the first ``min(history_len[r], window)`` ids of ``history[r]`` (int32 [rows, 64], newest first)."""
+    lib = E.load_library()
+    R = logits.shape[0]
+    if table.dtype != torch.uint8 or table.numel() < 24 * R:
+        raise ValueError("table: 24 bytes per row (slot_sampling_table)")
+    if filters.dtype != torch.uint8 or filters.numel() < 32 * R:
+        raise ValueError("filters: 32 bytes per row (slot_filter_table)")
+    if history.dtype != torch.int32 or tuple(history.shape) != (R, 64) or not history.is_contiguous():
+        raise ValueError("history: contiguous int32 [rows, 64]")
+    if history_len.dtype != torch.int32 or history_len.numel() < R:
+        raise ValueError("history_len: int32, one per row")
+    if frames is not None and (frames.dtype != torch.int32 or frames.numel() < R):
+        raise ValueError("frames: int32, one per row")
+    ids = torch.empty(R, dtype=torch.int32, device=logits.device)
+    E.check(lib.smoltts_k_sample_rows_filtered(E.dptr(logits), R, logits.shape[1], logits.stride(0), E.dptr(table), E.dptr(filters),
+                                               E.dptr(frames), E.dptr(history), E.dptr(history_len), int(step), E.dptr(ids),
+                                               E.current_stream_ptr()), "smoltts_k_sample_rows_filtered")
+    return ids
+
+
 def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     lib = E.load_library()
     out = torch.empty_like(x)

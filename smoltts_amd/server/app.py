@@ -259,13 +259,21 @@ class SamplingFields(BaseModel):
     temperature: Optional[float] = Field(default=None, ge=0, allow_inf_nan=False)
     fast_temperature: Optional[float] = Field(default=None, ge=0, allow_inf_nan=False)
     min_p: Optional[float] = Field(default=None, ge=0, lt=1)
+    # filters of the sampled picks: accepted on a request that resolves to greedy too, where they have no effect
+    top_p: Optional[float] = Field(default=None, gt=0, le=1)
+    top_k: Optional[int] = Field(default=None, ge=0, lt=2**31)
+    repetition_penalty: Optional[float] = Field(default=None, ge=1, le=10)
+    repetition_window: Optional[int] = Field(default=None, ge=1, le=64)
 
     def request_sampling(self):
-        if self.seed is None and self.temperature is None and self.fast_temperature is None and self.min_p is None:
+        fields = (self.seed, self.temperature, self.fast_temperature, self.min_p, self.top_p, self.top_k, self.repetition_penalty,
+                  self.repetition_window)
+        if all(v is None for v in fields):
             return None
         from ..config import RequestSampling
 
-        return RequestSampling(self.temperature, self.fast_temperature, self.min_p, self.seed)
+        return RequestSampling(self.temperature, self.fast_temperature, self.min_p, self.seed, self.top_p, self.top_k,
+                               self.repetition_penalty, self.repetition_window)
 
 
 # speaking speed (OpenAI's ``speed``, ElevenLabs' ``voice_settings.speed``): pitch-preserving time stretch on the GPU (tsm.py);

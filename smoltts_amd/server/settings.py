@@ -29,10 +29,16 @@ class GenerationBlock(BaseModel):
     # extension: "reference" = what lm/utils/samplers.py:22-28 computes (its threshold never removes a token, so the draw is
     # categorical over logits / temp); "intended" = keep p >= min_p * p_max.  The drop-in default is the reference's behaviour.
     min_p_mode: Literal["reference", "intended"] = "reference"
+    # extension: the filters of sampled picks that a request's body does not name (config.RequestSampling); all off
+    top_p: float = Field(default=1.0, gt=0, le=1)
+    top_k: int = Field(default=0, ge=0, lt=2**31)
+    repetition_penalty: float = Field(default=1.0, ge=1, le=10)
+    repetition_window: int = Field(default=16, ge=1, le=64)
 
     def to_settings(self) -> _GenerationSettings:
         return _GenerationSettings(default_temp=self.default_temp, default_fast_temp=self.default_fast_temp, min_p=self.min_p,
-                                   max_new_tokens=self.max_new_tokens, min_p_mode=self.min_p_mode)
+                                   max_new_tokens=self.max_new_tokens, min_p_mode=self.min_p_mode, top_p=self.top_p, top_k=self.top_k,
+                                   repetition_penalty=self.repetition_penalty, repetition_window=self.repetition_window)
 
 
 class ServerSettings(BaseModel):
