@@ -246,13 +246,23 @@ class SmolTTS:
         the seam stage in front of the stream's other stages, which run on across the segments: one stream (one FLAC header).
         ``loudness`` (as in ``__call__``): the stream is levelled causally on the GPU behind the seam and in front of the
         stretch, by a gain that moves towards the target at 5 dB/s at most, from ``loudness_start_gain_db`` (default 0); every
-        frame's samples still leave with the frame (``loudness.StreamState``)."""
+        frame's samples still leave with the frame (``loudness.StreamState``).
+        ``input`` may be an iterator or generator of strings (or UTF-8 ``bytes``, cut anywhere) in place of a string: text that is
+        still being written.  It implies ``segment=True`` (or the options given), is cut by ``longform.IncrementalSplitter``
+        and spoken segment after segment while the text is pulled: before segment k starts, just enough text is pulled to have
+        it whole and to know whether anything follows it, so the stream is that of the joined text with ``segment``.
+        ``longform.FLUSH`` as an item speaks the buffered remainder without waiting for its sentence to end."""
         import numpy as np
 
         from .engine import MimiSession
         from .generate import resolve_sampling, stream_pcm
         from .request import parse_request
 
+        if not isinstance(input, (str, bytes)):
+            yield from self._stream_incremental(iter(input), voice if voice is not None else "0", generation_settings, overlap,
+                                                reference_upsample, output_format, sampling, speed, container, segment, loudness,
+                                                loudness_start_gain_db)
+            return
         req = parse_request(input, stream=True, output_format=output_format, speed=speed, container=container, segment=segment,
                             loudness=loudness, loudness_start_gain_db=loudness_start_gain_db)
         voice = voice if voice is not None else "0"
@@ -330,21 +340,55 @@ class SmolTTS:
             self._seam = SeamJoiner(self.lm.device, 1)
         return seam_join(pcms, plan.pauses, self.lm.device, lead=plan.lead, trail=plan.trail, joiner=self._seam)
 
-    def _stream_segmented(self, req, voice, generation_settings, overlap, reference_upsample, sampling):
+    def _stream_incremental(self, texts, voice, generation_settings, overlap, reference_upsample, output_format, sampling, speed,
+                            container, segment, loudness, loudness_start_gain_db):
+        """``stream`` of a text that ``texts`` yields in pieces: the segmented stream of a plan that grows as the text is pulled."""
+        from .longform import FLUSH, GrowingPlan, IncrementalSplitter, segment_options
+        from .request import parse_request
+
+        req = parse_request("", stream=True, output_format=output_format, speed=speed, container=container, loudness=loudness,
+                            loudness_start_gain_db=loudness_start_gain_db)
+        opts = segment_options(segment or True)
+        plan, splitter = GrowingPlan(opts), IncrementalSplitter(opts)
+
+        def pull(k: int) -> bool:
+            """Pull text until segment k is whole and it is known whether it is the last; False: there is no segment k."""
+            while not plan.closed and (len(plan.segs) <= k or (len(plan.segs) == k + 1 and not splitter.pending)):
+                try:
+                    piece = next(texts)
+                except StopIteration:
+                    plan.extend(splitter.close())
+                    plan.close()
+                    break
+                plan.extend(splitter.flush() if piece is FLUSH else splitter.feed(piece))
+            return k < len(plan.segs)
+
+        if not pull(0):
+            raise ValueError("the text has nothing to speak")
+        yield from self._stream_segmented(req, voice, generation_settings, overlap, reference_upsample, sampling, plan, pull)
+
+    def _stream_segmented(self, req, voice, generation_settings, overlap, reference_upsample, sampling, plan=None, pull=None):
+        """``plan`` / ``pull``: a ``longform.GrowingPlan`` in place of the request's, and what completes its segment k."""
         import numpy as np
         import torch
 
         from .engine import MimiSession, StreamConverter
         from .generate import semantic_columns, stream_pcm
 
-        plan = req.plan
+        plan = plan if plan is not None else req.plan
         dev = self.lm.device
         conv = StreamConverter(dev, 1, 1920, seam=True)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
             conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container], [req.loudness], [req.start_gain_db])
-            for k, seg, st_k, samp_k in self._segments(plan, voice, None, generation_settings, sampling):
-                final = k == len(plan.segs) - 1
+            segments = self._segments(plan, voice, None, generation_settings, sampling)
+            for k in range(1 << 30):
+                if pull(k) if pull is not None else k < len(plan.segs):
+                    _, seg, st_k, samp_k = next(segments)  # (it walks the plan's list, which has grown by now)
+                else:
+                    next(segments, None)  # (its epilogue)
+                    break
+                final = plan.final(k) if pull is not None else k == len(plan.segs) - 1
                 sess = self._stream_session(seg["prompt"], st_k, samp_k)
                 try:
                     pause, flags, lead = plan.seam_args(k)

@@ -15,7 +15,8 @@ codec's 24 kHz fp32 PCM, block by block.  The rule, which is the definition:
   The head of the first segment and the tail of the last are otherwise never touched.
 
 Every cut falls inside samples below the threshold, so the step at a cut is below 2^-8; there are no fades.  The output does not
-depend on how a segment is cut into calls.  A stream of one segment is never given to this stage.
+depend on how a segment is cut into calls.  A whole text of one segment is never given to this stage; a text fed in pieces
+(``longform.IncrementalSplitter``) always is, and a single segment passes through it unchanged.
 """
 from __future__ import annotations
 

@@ -10,8 +10,10 @@ lacks: those formats answer 501 instead of being half-implemented.
 from __future__ import annotations
 
 import argparse
+import asyncio
 import json
 import math
+import queue
 import threading
 from typing import Dict, List, Literal, Optional, Tuple, Union
 
@@ -201,6 +203,40 @@ class TTSCore:
             chunks = self.model.stream(input_text, str(voice), **kw, **({"sampling": used} if used is not None else {}), **sp)
         return self._stream_bytes(chunks, kw, n_seg), seed_used(used)
 
+    def open_input_stream(self, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
+                          speed: Optional[float] = None, container: Optional[str] = None, loudness=None):
+        """A stream whose text arrives in pieces -> (an ``InputStream``, the seed it samples with or None).  Behind a scheduler
+        or pool it is ``submit_incremental``; a bare model streams from an iterator (``SmolTTS.stream(text_iter)``), which pulls
+        the text as it speaks.  The segment options are the settings' ``segment_max_bytes`` / ``seam_pause_ms`` whatever
+        ``long_text`` says (a text fed in pieces is always spoken in segments); ``idle_timeout_s`` and ``flush_after_s`` are
+        the settings' too.  ``ValueError``: options the engine refuses."""
+        from ..request import parse_request
+
+        kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
+        if container is not None:
+            kw["container"] = container
+        target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
+        p = parse_request("", stream=True, speed=speed, loudness=target, loudness_start_gain_db=start, **kw)
+        sp = {} if p.speed is None else {"speed": p.speed}
+        if p.loudness is not None:
+            sp["loudness"] = p.loudness
+            if start is not None:
+                sp["loudness_start_gain_db"] = start
+        sp["segment"] = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
+        if self.scheduler is not None:
+            req = self.scheduler.submit_incremental(str(voice), **kw, **({"sampling": sampling} if sampling is not None else {}), **sp,
+                                                    idle_timeout_s=float(self._setting("idle_timeout_s", 10.0)),
+                                                    flush_after_s=self._setting("flush_after_s", None))
+            used = getattr(req, "sampling", None)
+            return InputStream(req.feed, req.flush, req.close, req.cancel, self._stream_bytes(self.scheduler.iter_chunks(req), kw)), seed_used(used)
+        from ..longform import FLUSH
+
+        used = self._model_sampling(sampling)
+        texts: "queue.Queue" = queue.Queue()  # pieces, FLUSH marks, then None
+        chunks = self.model.stream(iter(texts.get, None), str(voice), **kw, **({"sampling": used} if used is not None else {}), **sp)
+        end = lambda: texts.put(None)  # (a bare model cannot be interrupted: it speaks what it has pulled, then ends)
+        return InputStream(texts.put, lambda: texts.put(FLUSH), end, end, self._stream_bytes(chunks, kw)), seed_used(used)
+
     def _stream_bytes(self, chunks, kw, n_seg: int = 0):
         try:
             for chunk in chunks:
@@ -233,6 +269,14 @@ class TTSCore:
             s16 = np.rint(np.clip(pcm_data, -1.0, 1.0) * 32767).astype(np.int16)
             return (s16.tobytes(), "audio/x-pcm") if kind == "pcm" else (lin2ulaw(s16).tobytes(), "audio/basic")  # ulaw: G.711 of the int16
         return pcm_to_wav_bytes(pcm_data, sample_rate), "audio/wav"
+
+
+class InputStream:
+    """The two ends of a stream fed in pieces: ``feed(text)`` / ``flush()`` / ``close()`` for the text, ``chunks`` (a generator
+    of bytes, blocking) for the audio; closing ``chunks`` early cancels the request."""
+
+    def __init__(self, feed, flush, close, cancel, chunks):
+        self.feed, self.flush, self.close, self.cancel, self.chunks = feed, flush, close, cancel, chunks
 
 
 def seed_used(sampling) -> Optional[int]:
@@ -399,6 +443,137 @@ def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return StreamingResponse(chunks, media_type="audio/wav", headers={
+        "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed)})
+
+
+class StreamInputOptions(SamplingFields, LoudnessFields):
+    """The first line of a ``stream-input`` body: the ``/stream`` body without its ``text``."""
+    model_id: Optional[str] = Field(default=None)
+    voice_settings: Optional[VoiceSettings] = Field(default=None)
+
+    @property
+    def speed(self) -> Optional[float]:
+        return None if self.voice_settings is None else self.voice_settings.speed
+
+
+class _DuplexResponse(StreamingResponse):
+    """A streamed response whose handler is still reading the request body: it does not listen on ``receive`` for the client's
+    disconnect, as ``StreamingResponse`` does below ASGI 2.4 (it would take body messages away from the reader, which sees a
+    disconnect itself)."""
+
+    async def __call__(self, scope, receive, send) -> None:
+        try:
+            await self.stream_response(send)
+        except OSError:
+            pass  # (the client went away: the body iterator has been closed)
+
+
+async def _ndjson(body):
+    """The lines of a newline-delimited JSON body, as they arrive: one parsed value per non-empty line (``ValueError`` for a line
+    that is not JSON); the last line needs no newline."""
+    buf = b""
+    async for part in body:
+        buf += part
+        while b"\n" in buf:
+            line, buf = buf.split(b"\n", 1)
+            if line.strip():
+                yield json.loads(line)
+    if buf.strip():
+        yield json.loads(buf)
+
+
+def _input_line(obj) -> Tuple[str, Optional[str]]:
+    """A line behind the first: ``{"text": "..."}`` or ``{"flush": true}`` -> ("text", the text) / ("flush", None)."""
+    if isinstance(obj, dict) and set(obj) == {"text"} and isinstance(obj["text"], str):
+        return "text", obj["text"]
+    if isinstance(obj, dict) and set(obj) == {"flush"} and obj["flush"] is True:
+        return "flush", None
+    raise ValueError('a line must be {"text": "..."} or {"flush": true}')
+
+
+@eleven_router.post("/text-to-speech/{voice_id}/stream-input")
+async def stream_input_tts(voice_id: str, http_request: Request, output_format: StreamFormat = "pcm_24000"):
+    """Text in as it is written, audio out as it is spoken (for a language model in front of the synthesiser).  The body is
+    newline-delimited JSON, read as it arrives: the first line holds the options of the ``/stream`` body without ``text``
+    (``{}`` for none), every later line is ``{"text": "..."}`` -- a piece of the text, cut anywhere -- or ``{"flush": true}``,
+    which speaks what is buffered without waiting for its sentence to end; the end of the body ends the text.  The response is
+    the chunked audio of ``/stream``, one stream for the whole text (``BatchScheduler.submit_incremental``).  A line that cannot
+    be read answers 422 while no audio has gone out; after that it ends the stream."""
+    from pydantic import ValidationError
+
+    core = http_request.app.state.tts_core
+    kind, rate = output_format.split("_")
+    lines = _ndjson(http_request.stream())
+    try:
+        first = await lines.__anext__()
+        item = StreamInputOptions.model_validate(first)
+    except StopAsyncIteration:
+        raise HTTPException(status_code=422, detail="the body is empty: its first line holds the options")
+    except ValidationError as e:
+        raise HTTPException(status_code=422, detail=_finite(json.loads(e.json(include_url=False, include_context=False))))
+    except ValueError as e:
+        raise HTTPException(status_code=422, detail=f"line 1: {e}")
+    try:
+        stream, seed = core.open_input_stream(voice_id, output_format, sampling=item.request_sampling(), speed=item.speed, loudness=item)
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+    loop = asyncio.get_running_loop()
+    out: asyncio.Queue = asyncio.Queue()  # bytes, then None or an exception
+
+    def pump():  # the chunk iterator blocks: it runs in a thread of its own
+        end = None
+        try:
+            for b in stream.chunks:
+                loop.call_soon_threadsafe(out.put_nowait, b)
+        except Exception as e:
+            end = e
+        loop.call_soon_threadsafe(out.put_nowait, end)
+
+    threading.Thread(target=pump, name="smoltts-stream-input", daemon=True).start()
+
+    async def read_text():
+        n = 1
+        try:
+            while True:
+                n += 1
+                try:
+                    obj = await lines.__anext__()
+                except StopAsyncIteration:
+                    break
+                what, text = _input_line(obj)
+                stream.feed(text) if what == "text" else stream.flush()
+        except Exception as e:  # a line that cannot be read, or text the engine refuses (a bad break tag): the request ends
+            stream.cancel()
+            raise ValueError(f"line {n}: {e}") if isinstance(e, ValueError) else e
+        stream.close()
+
+    reader = asyncio.ensure_future(read_text())
+    getter = asyncio.ensure_future(out.get())
+    while not getter.done():
+        await asyncio.wait({getter} if reader.done() else {getter, reader}, return_when=asyncio.FIRST_COMPLETED)
+        if reader.done() and reader.exception() is not None and not getter.done():
+            getter.cancel()
+            e = reader.exception()
+            raise HTTPException(status_code=422 if isinstance(e, ValueError) else 500, detail=str(e))
+    head = getter.result()
+    if isinstance(head, ValueError):  # a request the engine refuses (as on /stream)
+        raise HTTPException(status_code=400, detail=str(head))
+
+    async def body():
+        item = head
+        try:
+            while item is not None and not isinstance(item, Exception):
+                yield item
+                item = await out.get()
+        finally:
+            if item is not None:  # the client went away, or the engine failed: stop working for the request
+                stream.cancel()
+            if not reader.done():
+                reader.cancel()
+            elif not reader.cancelled():
+                reader.exception()  # (a bad line behind the first chunk has ended the stream: there is nobody left to tell)
+
+    return _DuplexResponse(body(), media_type="audio/wav", headers={
         "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed)})
 
 

@@ -34,6 +34,27 @@ class _PoolRequest:
     loudness_gain_db: Optional[float] = None  # a blocking request with a loudness: the gain applied (known at its end)
 
 
+@dataclass
+class _PoolIncrementalRequest(_PoolRequest):
+    """``GpuPool.submit_incremental``'s handle: the text calls travel to the worker that owns the request, in order."""
+    pool: object = None
+
+    def feed(self, text) -> None:
+        self.pool._inc(self, "feed", text)
+
+    def flush(self) -> None:
+        self.pool._inc(self, "flush")
+
+    def close(self) -> None:
+        self.pool._inc(self, "close")
+
+    def cancel(self) -> None:
+        self.pool.cancel(self)
+
+    def __iter__(self):
+        return self.pool.iter_chunks(self)
+
+
 def visible_device(index: int, inherited: Optional[str]) -> str:
     """The ``HIP_VISIBLE_DEVICES`` value of the worker for GPU ``index``: an entry of the mask this process runs under, if
     there is one (indices are relative to it), else the index itself."""
@@ -115,6 +136,26 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
                 with lock:
                     live[rid] = req
                 threading.Thread(target=pump, args=(rid, req), name=f"smoltts-pump-{rid}", daemon=True).start()
+            elif msg[0] == "submit_incremental":
+                _, rid, voice, max_new_tokens, extra = msg
+                try:
+                    req = sched.submit_incremental(voice, max_new_tokens=max_new_tokens, **extra)
+                except Exception as e:
+                    res_q.put((rid, "error", (type(e).__name__, str(e))))
+                    continue
+                with lock:
+                    live[rid] = req
+                threading.Thread(target=pump, args=(rid, req), name=f"smoltts-pump-{rid}", daemon=True).start()
+            elif msg[0] in ("feed", "flush", "close_text"):
+                with lock:
+                    req = live.get(msg[1])
+                if req is None:
+                    continue
+                try:
+                    req.feed(msg[2]) if msg[0] == "feed" else (req.flush() if msg[0] == "flush" else req.close())
+                except Exception as e:  # text the engine refuses (a bad break tag): the request ends with that error
+                    res_q.put((msg[1], "error", (type(e).__name__, str(e))))
+                    sched.cancel(req)
             elif msg[0] == "cancel":
                 with lock:
                     req = live.get(msg[1])
@@ -196,7 +237,47 @@ class GpuPool:
         from ..request import parse_request
 
         p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db)  # refused here, before a worker sees it
-        if sampling is not None or self._settings is not None:  # the seed is drawn here: the same on whichever worker serves it
+        sampling = self._resolve_sampling(sampling)
+        req = self._new_request(sampling)
+        w = req.worker
+        msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
+        extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
+                                   ("container", p.container), ("segment", p.segment), ("loudness", p.loudness),
+                                   ("loudness_start_gain_db", loudness_start_gain_db)) if v is not None}
+        self._req_qs[w].put(msg + (extra,) if extra else msg)
+        return req
+
+    def submit_incremental(self, voice: str = "heart", max_new_tokens: Optional[int] = None, output_format: Optional[str] = None,
+                           sampling=None, speed: Optional[float] = None, container: Optional[str] = None, segment=True,
+                           loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
+                           idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None) -> _PoolIncrementalRequest:
+        """As ``BatchScheduler.submit_incremental``: the request lives in one slot of one worker, and ``feed`` / ``flush`` /
+        ``close`` / ``cancel`` of the handle go to that worker over its queue, in the order they were called.  Text the worker
+        refuses (a bad break tag) ends the stream with that ``ValueError`` instead of raising from ``feed``."""
+        from ..longform import segment_options
+        from ..request import parse_request
+
+        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db)
+        opts = segment_options(True if segment is None or segment is False else segment)
+        sampling = self._resolve_sampling(sampling)
+        req = self._new_request(sampling, _PoolIncrementalRequest, pool=self)
+        extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
+                                   ("container", p.container), ("segment", opts), ("loudness", p.loudness),
+                                   ("loudness_start_gain_db", loudness_start_gain_db), ("idle_timeout_s", idle_timeout_s),
+                                   ("flush_after_s", flush_after_s)) if v is not None}
+        self._req_qs[req.worker].put(("submit_incremental", req.rid, voice, max_new_tokens, extra))
+        return req
+
+    def _inc(self, req: _PoolIncrementalRequest, what: str, text=None) -> None:
+        if req.closed or req.cancelled:
+            if what == "feed":
+                raise ValueError("the request has ended")
+            return
+        self._req_qs[req.worker].put(("feed", req.rid, text) if what == "feed" else ("flush" if what == "flush" else "close_text", req.rid))
+
+    def _resolve_sampling(self, sampling):
+        """A request's sampling as it travels: the seed is drawn here, the same on whichever worker serves it."""
+        if sampling is not None or self._settings is not None:
             import dataclasses
 
             from ..config import RequestSampling
@@ -206,6 +287,10 @@ class GpuPool:
                 sampling = sampling.resolve(self._settings)
             elif sampling.seed is None:
                 sampling = dataclasses.replace(sampling, seed=int.from_bytes(os.urandom(8), "little"))
+        return sampling
+
+    def _new_request(self, sampling, cls=_PoolRequest, **kw) -> _PoolRequest:
+        """A request in the books of the worker with the fewest in flight."""
         with self._lock:
             if self._closing:
                 raise RuntimeError("pool closed")
@@ -213,14 +298,9 @@ class GpuPool:
             if not alive:
                 raise RuntimeError("no GPU worker is alive")
             w = min(alive, key=lambda i: self._load[i])
-            req = _PoolRequest(next(self._ids), w, sampling=sampling)
+            req = cls(next(self._ids), w, sampling=sampling, **kw)
             self._reqs[req.rid] = req
             self._load[w] += 1
-        msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
-        extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
-                                   ("container", p.container), ("segment", p.segment), ("loudness", p.loudness),
-                                   ("loudness_start_gain_db", loudness_start_gain_db)) if v is not None}
-        self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
     def synthesize(self, text: str, voice: str = "heart", max_new_tokens: Optional[int] = None) -> np.ndarray:

@@ -61,6 +61,7 @@ class _Request:
     loudness: Optional[float] = None  # target in LUFS (loudness.py): a stream is levelled in its codec pass, a blocking utterance whole
     start_gain_db: float = 0.0        # streaming: the loudness stage's first knot
     loudness_gain_db: Optional[float] = None  # blocking: the gain that was applied (set before the audio goes out)
+    inc: Optional["_Incremental"] = None  # a stream whose text is fed in pieces (submit_incremental)
 
 
 @dataclass
@@ -77,7 +78,50 @@ class _Segmented:
 
     @property
     def final(self) -> bool:
-        return self.k == len(self.plan.segs) - 1
+        """No segment follows the one in the slot (a plan that grows: and none can)."""
+        grows = getattr(self.plan, "final", None)
+        return grows(self.k) if grows is not None else self.k == len(self.plan.segs) - 1
+
+
+@dataclass
+class _Incremental:
+    """The text side of a request fed in pieces.  The client's calls run the splitter under ``lock`` and leave its segments in
+    ``inbox``; the worker alone moves them into the request's plan (``_ingest``), so that a tick's codec pass and its
+    bookkeeping see one and the same plan."""
+    splitter: object                      # longform.IncrementalSplitter
+    idle_timeout_s: float
+    flush_after_s: Optional[float]
+    lock: object = field(default_factory=threading.Lock)
+    inbox: list = field(default_factory=list)
+    close_asked: bool = False             # close() was called (or the idle timeout did it): the inbox holds the last segments
+    last_input: float = 0.0               # time.monotonic() of the last feed
+    parked_at: float = 0.0                # ... and of the park, while parked
+    state: str = "waiting"                # "waiting" for its first segment (no slot yet), then "admitted"
+
+
+@dataclass
+class IncrementalRequest(_Request):
+    """What ``submit_incremental`` returns: ``feed`` / ``flush`` / ``close`` for the text, iteration for the chunks, ``cancel``."""
+    sched: object = None
+
+    def feed(self, text) -> None:
+        """More text (``str``, or ``bytes`` of UTF-8 cut anywhere).  ``ValueError``: a bad break tag, or text after ``close``
+        (an idle timeout closes too)."""
+        self.sched._inc_text(self, "feed", text)
+
+    def flush(self) -> None:
+        """Speak what is buffered now, without waiting for its sentence to end."""
+        self.sched._inc_text(self, "flush")
+
+    def close(self) -> None:
+        """The text is complete: what is buffered is its last segment."""
+        self.sched._inc_text(self, "close")
+
+    def cancel(self) -> None:
+        self.sched.cancel(self)
+
+    def __iter__(self):
+        return self.sched.iter_chunks(self)
 
 
 @dataclass
@@ -195,8 +239,12 @@ class BatchScheduler:
         self._deliveries: List[_Delivery] = []  # codec passes whose PCM has not been handed out yet, in order
         self._snaps: List[_Snapshot] = []       # snapshots of the output ring the host has not looked at yet (oldest first)
         self._tick_no = 0                       # ticks queued so far
-        self._counts = {"completed": 0, "cancelled": 0, "failed": 0, "frames_delivered": 0, "prefix_installs": 0, "segments": 0}
+        self._counts = {"completed": 0, "cancelled": 0, "failed": 0, "frames_delivered": 0, "prefix_installs": 0, "segments": 0,
+                        "idle_timeouts": 0}
         self._refills: List[_Request] = []      # segmented requests whose slot waits for their next segment's prompt
+        self._parked: List[_Request] = []       # ... and incremental ones whose slot waits for text that has not arrived yet
+        self._incs: List[_Request] = []         # the incremental requests alive (worker side)
+        self._inc_new: "queue.Queue[_Request]" = queue.Queue()  # ... and those the worker has not seen yet
         self._block_seam = None                 # seam stage of the blocking segmented requests (engine.SeamJoiner, 1 slot)
         self._dead: Optional[Exception] = None  # why the worker stopped
         self._draining = False
@@ -252,6 +300,78 @@ class BatchScheduler:
             self._end(req, RuntimeError(f"scheduler is not running: {self._dead}"))
         return req
 
+    def submit_incremental(self, voice: str = "heart", max_new_tokens: Optional[int] = None, output_format: Optional[str] = None,
+                           sampling=None, speed: Optional[float] = None, container: Optional[str] = None, segment=True,
+                           loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
+                           idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None) -> IncrementalRequest:
+        """A stream whose text is not known yet: ``request.feed(text)`` as it arrives, ``request.close()`` at its end, the
+        chunks by iterating the request (or ``iter_chunks``).  The options are those of ``submit(stream=True, segment=...)``
+        (``segment``: True, a dict or a ``SegmentOptions``; it cannot be off).
+
+        The text is cut by ``longform.IncrementalSplitter`` into the segments ``SegmentPlan.create`` gives the whole text, each
+        handed over once no later input can change it, and spoken as a segmented stream whose segment list grows: the request
+        takes its slot with its first segment and keeps it to its end.  When ``close()`` arrives before the last segment is
+        opened, the stream is byte for byte that of ``submit(whole_text, stream=True, segment=...)``.
+
+        *Latency over closing silence.*  Whether a segment is the last is not known while text may follow, and no segment
+        waits to find out: segment k is opened as soon as it exists, as a segment with a seam behind it.  When the text is then
+        closed with nothing behind segment k, the stream ends with it the way a stream's last segment ends: the seam stage's
+        ``last`` marker releases its held trailing silence unchanged (``seam.SeamState.push(..., last=True)`` is the definition),
+        and break tags behind the segment are dropped (they would have been the stream's trailing silence).
+
+        *Parking.*  A slot whose segment ends before more text has arrived keeps its slot, its stage states and its conditioning
+        context and takes no decode work -- the state of a segmented slot between two of its segments -- until a segment
+        arrives.  The segment that ended has had its seam (its held silence cut or padded to the pause); a ``close()`` without
+        more text then only flushes the stream's other stages.  A slot parked for ``idle_timeout_s`` without input is closed
+        as if ``close()`` had been called.  ``cancel`` while parked frees the slot at once.
+
+        ``flush_after_s`` (None: off): when no text has arrived for that long and the buffered text has not reached a sentence
+        end, it is spoken as a segment of its own.  Such a segment is not one of the whole text's: the stream then differs
+        from the whole text's."""
+        from ..config import RequestSampling
+        from ..longform import GrowingPlan, IncrementalSplitter, segment_options
+        from ..request import parse_request
+
+        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db)
+        opts = segment_options(True if segment is None or segment is False else segment)
+        if not float(idle_timeout_s) > 0.0 or (flush_after_s is not None and not float(flush_after_s) > 0.0):
+            raise ValueError("idle_timeout_s and flush_after_s must be positive")
+        resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
+        if self._dead is not None or self._draining:
+            raise RuntimeError(f"scheduler is not running: {self._dead or 'shutting down'}")
+        req = IncrementalRequest("", voice, True, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
+                                 output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice),
+                                 speed_q=p.speed_q, container=p.container, seg=_Segmented(GrowingPlan(opts), resolved),
+                                 loudness=p.loudness, start_gain_db=p.start_gain_db, sched=self,
+                                 inc=_Incremental(IncrementalSplitter(opts), float(idle_timeout_s),
+                                                  None if flush_after_s is None else float(flush_after_s),
+                                                  last_input=time.monotonic()))
+        self._inc_new.put(req)
+        self._wake.set()
+        if self._dead is not None:
+            self._end(req, RuntimeError(f"scheduler is not running: {self._dead}"))
+        return req
+
+    def _inc_text(self, req: _Request, what: str, text=None) -> None:
+        """The client's ``feed`` / ``flush`` / ``close``: the splitter runs here, its segments wait for the worker."""
+        inc = req.inc
+        if self._dead is not None:
+            raise RuntimeError(f"scheduler is not running: {self._dead}")
+        with inc.lock:
+            if inc.close_asked:
+                if what == "feed":
+                    raise ValueError("the request's text is closed")
+                return
+            if what == "feed":
+                inc.inbox.extend(inc.splitter.feed(text))
+                inc.last_input = time.monotonic()
+            elif what == "flush":
+                inc.inbox.extend(inc.splitter.flush())
+            else:
+                inc.inbox.extend(inc.splitter.close())
+                inc.close_asked = True
+        self._wake.set()
+
     def synthesize(self, text: str, voice: str = "heart", max_new_tokens: Optional[int] = None) -> np.ndarray:
         """Blocking: float32 PCM of the whole utterance."""
         return np.concatenate(list(self.iter_chunks(self.submit(text, voice, False, max_new_tokens))) or [np.zeros(0, np.float32)])
@@ -279,6 +399,8 @@ class BatchScheduler:
         req.cancelled = True
         for part in list(req.seg.parts) if req.seg is not None else []:
             part.cancelled = True
+        if req.inc is not None:
+            self._wake.set()  # (a parked one is in no tick's books: the worker frees its slot when it looks at the text side)
 
     # ------------------------------------------------------------------ client side: registered voices
     def add_voice(self, voice_id: str, samples=None, grid=None, system_prompt: Optional[str] = None, name: Optional[str] = None) -> dict:
@@ -327,7 +449,7 @@ class BatchScheduler:
             self._draining = True
             deadline = time.time() + timeout
             while (self._thread.is_alive() and time.time() < deadline and
-                   (self._active or self._side is not None or self._retiring or self._refills or self._held is not None or not self._pending.empty() or self._codec_backlog() or self._deliveries or self._stretches)):
+                   (self._active or self._side is not None or self._retiring or self._refills or self._parked or self._held is not None or not self._pending.empty() or self._codec_backlog() or self._deliveries or self._stretches)):
                 time.sleep(0.01)
         self._stop.set()
         self._wake.set()
@@ -501,6 +623,82 @@ class BatchScheduler:
             raise
         self._enter(new)
 
+    def _ingest(self) -> None:
+        """The text side of the incremental requests, once per turn of the loop: segments the clients' calls left move into the
+        plans (nothing else changes a plan, so a tick's codec pass and its bookkeeping agree on which segment is final), a
+        request with its first segment joins the queue, a parked one with a new segment goes back to the refills, and one whose
+        text has ended while parked is flushed and closed.  Idle timeout and early flush are decided here too."""
+        while not self._inc_new.empty():
+            self._incs.append(self._inc_new.get_nowait())
+        if not self._incs:
+            return
+        now = time.monotonic()
+        for r in list(self._incs):
+            inc, sg = r.inc, r.seg
+            parked = r in self._parked
+            if r.cancelled and not r.closed and (parked or inc.state == "waiting"):
+                if parked:
+                    self._free.append(r.slot)
+                    self._parked.remove(r)
+                self._end(r)
+            if r.closed:
+                self._incs.remove(r)
+                continue
+            try:
+                with inc.lock:
+                    if not inc.close_asked:
+                        if parked and (self._draining or now - max(inc.last_input, inc.parked_at) >= inc.idle_timeout_s):
+                            inc.inbox.extend(inc.splitter.close())  # a stalled client does not pin a slot
+                            inc.close_asked = True
+                            self._counts["idle_timeouts"] += not self._draining
+                        elif inc.flush_after_s is not None and inc.splitter.pending and now - inc.last_input >= inc.flush_after_s:
+                            inc.inbox.extend(inc.splitter.flush())
+                    segs, inc.inbox, closing = inc.inbox, [], inc.close_asked
+            except ValueError as e:  # (the remainder held a bad break tag)
+                segs, closing = [], True
+                inc.close_asked = True
+                if inc.state == "waiting":
+                    self._end(r, e)
+                    self._incs.remove(r)
+                    continue
+            if segs:
+                sg.plan.extend(segs)
+            if closing:
+                sg.plan.close()
+            if inc.state == "waiting":
+                if sg.plan.segs:
+                    inc.state = "admitted"
+                    self._pending.put(r)
+                elif closing:
+                    self._end(r, ValueError("the text has nothing to speak"))
+                    self._incs.remove(r)
+            elif parked and sg.k < len(sg.plan.segs):
+                self._parked.remove(r)
+                self._refills.append(r)
+            elif parked and closing:
+                self._parked.remove(r)
+                self._flush_parked(r)
+
+    def _flush_parked(self, r: _Request) -> None:
+        """A parked stream ends: one pass of its stages behind the seam with no samples and the ``last`` marker (the stretcher's
+        and the FLAC encoder's flush, the resampler's tail), on the codec stream behind the passes so far; its end marker
+        follows that chunk and the slot is free (a next tenant's stages are reset behind this pass)."""
+        from ..engine import upload
+
+        torch = self._torch
+        n = self.tick * 1920
+        with torch.cuda.stream(self._codec_stream):
+            none, last = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32)
+            last[r.slot] = 1
+            none_d, last_d = upload([none, last], self.session.engine.device)
+            pcm = torch.zeros(self.B, n, dtype=torch.float32, device="cuda")
+            conv = self._stream_conv.run(pcm, n, none_d, last_d, slots=[r.slot], seg_end=none_d)
+            ev = torch.cuda.Event()
+            ev.record(self._codec_stream)
+        self._deliveries.append(_Delivery(ev, pcm, [(r, r.slot, 0, True)], urgent=True, keep=(none_d, last_d), conv=conv))
+        r.stream_done = True
+        self._free.append(r.slot)
+
     def _hold(self, req: _Request, refill: bool) -> None:
         if refill:
             self._refills.insert(0, req)
@@ -509,14 +707,19 @@ class BatchScheduler:
 
     def _next_segment(self, r: _Request, cols: np.ndarray) -> None:
         """Segment k has ended (seen in a snapshot): its codes become the next one's context and the slot, still the request's,
-        waits in ``_refills`` for the next chained prompt."""
+        waits in ``_refills`` for the next chained prompt -- or, where the next segment's text has not arrived yet (an
+        incremental request), in ``_parked`` for that."""
         sg = r.seg
         sg.prev = (sg.plan.segs[sg.k].text, cols.T.copy())
         sg.k += 1
         sg.sampling, sg.cols = sg.plan.sampling(sg.k, r.sampling), []
         r.prompt, r.emitted = None, 0
         del self._active[r.slot]
-        self._refills.append(r)
+        if sg.k < len(sg.plan.segs):
+            self._refills.append(r)
+        else:
+            r.inc.parked_at = time.monotonic()
+            self._parked.append(r)
 
     def _write_sampling(self, entries: Dict[int, object]) -> None:
         """Slot b samples with ``entries[b]`` from the next pick on the current stream on (only changed entries are uploaded)."""
@@ -1053,6 +1256,7 @@ class BatchScheduler:
             with torch.cuda.stream(compute):
                 while not self._stop.is_set():
                     self._job_step()  # a voice registration: at most one prefill chunk between two ticks
+                    self._ingest()
                     self._admit()
                     if not self._active:
                         if self._side is not None:  # (its slots are the only ones taken: nothing to run beside)
@@ -1107,7 +1311,7 @@ class BatchScheduler:
         slots in use, queue length."""
         up = time.time() - self._t0
         return dict(self._counts, ticks=self._tick_no, frames_per_tick=self.tick, slots=self.B, active=len(self._active), voices=len(self._voices),
-                    queued=self._pending.qsize(), awaiting_codec=len(self._finished) + sum(1 for j in self._codec_jobs if j is not None), uptime_s=up, gpu_wait_s=self._gpu_wait_s,
+                    queued=self._pending.qsize(), parked=len(self._parked), awaiting_codec=len(self._finished) + sum(1 for j in self._codec_jobs if j is not None), uptime_s=up, gpu_wait_s=self._gpu_wait_s,
                     delivered_frames_per_s=self._counts["frames_delivered"] / up if up > 0 else 0.0)
 
     def _fail_all(self, e: Exception) -> None:
@@ -1124,7 +1328,9 @@ class BatchScheduler:
             self._held = None
         side = self._side["reqs"] if self._side is not None else []
         self._side = None
-        for r in (list(self._active.values()) + side + self._retiring + self._refills + self._finished +
+        while not self._inc_new.empty():
+            self._incs.append(self._inc_new.get_nowait())
+        for r in (list(self._active.values()) + side + self._retiring + self._refills + self._parked + self._incs + self._finished +
                   [j.req for j in self._codec_jobs if j is not None]):
             self._end(r, e)
         self._codec_jobs = [None] * len(self._codec_jobs)
@@ -1134,6 +1340,8 @@ class BatchScheduler:
         self._active.clear()
         self._retiring = []
         self._refills = []
+        self._parked = []
+        self._incs = []
         self._finished = []
         self._deliveries = []
         for job in self._stretches:

@@ -2,7 +2,8 @@
 ``model_id`` / ``checkpoint_dir``, a ``generation`` block (lm/generate.py:12-16) and a ``model_type`` block
 (lm/config.py:5-12).  Extensions of this build: ``mimi_checkpoint`` (the reference downloads kyutai/mimi; there is no
 network here), ``max_batch`` (slots per GPU), ``weight_format`` ("bf16" | "fp8"), ``max_voices`` (cloned voices held at once),
-``long_text`` / ``segment_max_bytes`` / ``seam_pause_ms`` / ``max_input_chars`` (long texts as chained segments).  ``model_id`` is accepted by the schema
+``long_text`` / ``segment_max_bytes`` / ``seam_pause_ms`` / ``max_input_chars`` (long texts as chained segments),
+``idle_timeout_s`` / ``flush_after_s`` (text fed in pieces).  ``model_id`` is accepted by the schema
 but cannot be resolved without network access; ``get_checkpoint_dir`` says so."""
 from __future__ import annotations
 
@@ -65,6 +66,12 @@ class ServerSettings(BaseModel):
     # (extension) the loudness target in LUFS of requests whose body names none (loudness.py); null: the level is
     # left as the model gives it
     loudness: Optional[float] = Field(default=None, ge=-40.0, le=-5.0)
+
+    # (extension) requests whose text is fed in pieces (POST .../stream-input): a slot that has waited this long for
+    # text is closed as if its text had ended; with flush_after_s, text that has stopped arriving short of a sentence end for that
+    # long is spoken as it is
+    idle_timeout_s: float = Field(default=10.0, gt=0, allow_inf_nan=False)
+    flush_after_s: Optional[float] = Field(default=None, gt=0, allow_inf_nan=False)
 
     model_config = {"protected_namespaces": ()}
 
