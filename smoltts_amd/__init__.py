@@ -30,7 +30,8 @@ class SmolTTS:
 
         from .checkpoint import load_checkpoint, load_mimi_state
         from .config import NumericsMode, TokenConfig
-        from .engine import LMEngine, MimiEngine
+        from .lm import LMEngine
+        from .mimi import MimiEngine
         from .prompt import PromptEncoder
         from .tokenizer import load_tokenizer
 
@@ -58,7 +59,7 @@ class SmolTTS:
         self.voices: Dict[str, "np.ndarray"] = {}  # registered voice id -> speaker grid (add_voice)
         self.verbose = verbose  # print the reference's per-call timing lines (lm/generate.py:187-214)
         self.last_sampling = None  # resolved RequestSampling list of the last call that was given sampling= (seeds included)
-        self._seam = None  # engine.SeamJoiner of the blocking segmented calls (made on first use)
+        self._seam = None  # stages.SeamJoiner of the blocking segmented calls (made on first use)
         self.last_segments: list = []  # per segment of the last segmented call: text, prompt, codes, seed
         self.last_loudness_gain_db = None  # gain of the last call that was given loudness=
         self.last_stats: dict = {}  # timing of the last generate_codes / __call__ (BatchGenerator.stats + codec_ms)
@@ -140,7 +141,7 @@ class SmolTTS:
         import numpy as np
         import torch
 
-        from .engine import MimiSession
+        from .mimi import MimiSession
 
         F_ = int(codes.shape[1])
         if F_ == 0:
@@ -179,14 +180,14 @@ class SmolTTS:
                                         sampling=sampling)[0]
             pcm = self.decode_codes(codes)
         if req.loudness is not None:
-            from .engine import loudness_normalize
+            from .stages import loudness_normalize
             from .loudness import gain_db
 
             pcm, g = loudness_normalize(pcm, req.loudness, self.lm.device, with_gain=True)
             self.last_loudness_gain_db = gain_db(g)
         if req.speed_q is None:
             return pcm
-        from .engine import stretch_pcm
+        from .stages import stretch_pcm
 
         return stretch_pcm(pcm, req.speed_q, self.lm.device)
 
@@ -195,7 +196,7 @@ class SmolTTS:
         """24 kHz mono float PCM (any shape, flattened) -> (n_codebooks, F) uint32 Mimi codes (``codec.encode``)."""
         import numpy as np
 
-        from .engine import MimiEncoder
+        from .mimi import MimiEncoder
 
         if self._encoder is None:
             if self._mimi_encoder_state is None:
@@ -254,7 +255,7 @@ class SmolTTS:
         ``longform.FLUSH`` as an item speaks the buffered remainder without waiting for its sentence to end."""
         import numpy as np
 
-        from .engine import MimiSession
+        from .mimi import MimiSession
         from .generate import resolve_sampling, stream_pcm
         from .request import parse_request
 
@@ -290,7 +291,7 @@ class SmolTTS:
     def _stream_session(self, prompt, settings, sampling):
         """The one-slot ``LMSession`` a stream of ``prompt`` runs in, sampling with ``settings``, or slot 0 with the resolved
         ``sampling`` list when there is one."""
-        from .engine import LMSession
+        from .lm import LMSession
         from .generate import _apply_sampling, _apply_slot_sampling
 
         max_new, T = self._max_new(settings), int(prompt.shape[1])
@@ -330,7 +331,7 @@ class SmolTTS:
         self.last_sampling = resolved  # (generate_prompt_codes sets it per segment)
 
     def _call_segmented(self, plan, voice, speaker, generation_settings, sampling):
-        from .engine import SeamJoiner, seam_join
+        from .stages import SeamJoiner, seam_join
 
         pcms = []
         for _, seg, st_k, samp_k in self._segments(plan, voice, speaker, generation_settings, sampling):
@@ -372,7 +373,8 @@ class SmolTTS:
         import numpy as np
         import torch
 
-        from .engine import MimiSession, StreamConverter
+        from .mimi import MimiSession
+        from .route import StreamConverter
         from .generate import semantic_columns, stream_pcm
 
         plan = plan if plan is not None else req.plan

@@ -2,7 +2,7 @@
 
 ``python -m smoltts_amd.build`` or ``build_library()``; ``__graft_entry__.build()`` calls this.
 hipcc cross-compiles without a GPU.  The product never falls back to anything else: if the
-library is missing, ``smoltts_amd.engine.load_library`` raises.
+library is missing, ``smoltts_amd.abi.load_library`` raises.
 
 The product library (``csrc/libsmoltts_hip.so``) is always compiled with exactly ``PRODUCT_FLAGS``: its objects carry a
 record of the flags they were built with and are rebuilt when that record differs.  Experiments that need other flags

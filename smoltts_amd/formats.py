@@ -2,7 +2,7 @@
 
 A streamed ``output_format`` is ``pcm_<rate>`` (16-bit little-endian PCM) at 8000 / 16000 / 22050 / 44100 / 48000 Hz or
 ``ulaw_8000`` (G.711 mu-law); ``pcm_24000`` is the codec's own float32 stream and is not converted.  The conversion of streamed
-chunks runs on the GPU (``engine.Resampler``, csrc/resample.hip); the host mu-law here serves the blocking route, which
+chunks runs on the GPU (``stages.Resampler``, csrc/resample.hip); the host mu-law here serves the blocking route, which
 resamples whole signals on the host.
 """
 from __future__ import annotations
@@ -11,7 +11,8 @@ from typing import Tuple
 
 import numpy as np
 
-ENC_OFF, ENC_S16, ENC_ULAW = 0, 1, 2  # SMOLTTS_RESAMPLE_*
+from .abi import RESAMPLE_OFF as ENC_OFF, RESAMPLE_S16 as ENC_S16, RESAMPLE_ULAW as ENC_ULAW
+
 STREAM_RATES = (8000, 16000, 22050, 44100, 48000)
 STREAM_FORMATS = tuple(f"pcm_{r}" for r in STREAM_RATES) + ("ulaw_8000",)
 NATIVE_FORMAT = "pcm_24000"

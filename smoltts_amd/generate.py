@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from .config import GenerationSettings, RequestSampling
-from .engine import LMEngine, LMSession, StreamConverter
+from .lm import LMEngine, LMSession
+from .route import StreamConverter
 
 
 @dataclass
@@ -240,22 +241,22 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     last one is not a frame: a stopped slot is frozen (smoltts_lm_decode).
 
     ``output_format`` (``pcm_<rate>`` / ``ulaw_8000``, formats.py): every chunk is converted on the codec stream right behind its
-    decode (``engine.Resampler``) and leaves as int16 / uint8 samples -- the outputs that became final with it; the resampler's
+    decode (``stages.Resampler``) and leaves as int16 / uint8 samples -- the outputs that became final with it; the resampler's
     tail (<= 20 samples) follows the last chunk.  A frame the slot did not produce is not fed to the resampler (its valid count is
     taken from the device's frame counter), so the tail is that of the last real frame.  ``None`` / ``pcm_24000``: float32.
 
     ``speed_q`` (``tsm.speed_q``; None or 65536: no stretch, no launch): every frame's PCM goes through the time stretch
-    (``engine.TimeStretcher``) on the codec stream in front of the resampler, which then consumes the stretcher's output.  The end
+    (``stages.TimeStretcher``) on the codec stream in front of the resampler, which then consumes the stretcher's output.  The end
     of the stream is derived on the device from the same snapshot of the frame counter and ``done`` that the host reads, and the
     stretcher flushes with it.  A chunk holds the samples that became final with its frame; a frame that finalised none yields
     nothing.
 
     ``container`` (``"flac"``): the stream's 16-bit samples (the converted ones, or the float32 quantised) are framed as FLAC on
-    the codec stream behind the other stages (``engine.FlacEncoder``): uint8 chunks, the stream header in front of the first;
+    the codec stream behind the other stages (``stages.FlacEncoder``): uint8 chunks, the stream header in front of the first;
     the end of the stream is derived on the device as for a speed.
 
     ``loudness`` (a target in LUFS, ``loudness.py``; None: no launch): every frame's PCM goes through the loudness stage
-    (``engine.LoudnessNormalizer``) in front of the stretch, from the first knot ``start_gain_db``; a frame's 1920 samples come
+    (``stages.LoudnessNormalizer``) in front of the stretch, from the first knot ``start_gain_db``; a frame's 1920 samples come
     out with the frame.
 
     ``conv``: the utterance is one segment of a long text (``longform``): the caller's ``StreamConverter(seam=True)``, with the

@@ -14,8 +14,15 @@ from typing import Optional
 
 import torch
 
-from . import engine as E
+from . import abi as E
+from .abi import Gemm3Args, PickArgs, SlotFilters, SlotSampling
+from .device import current_stream_ptr, dptr
 from .packing import tile_t16x32, tile_w3
+
+
+def _k(name: str, *args) -> None:
+    """``name(*args, current stream)`` of the library, checked."""
+    E.check(getattr(E.load_library(), name)(*args, current_stream_ptr()), name)
 
 
 def pack_weight(w: torch.Tensor, fp32: bool = False) -> torch.Tensor:
@@ -44,45 +51,42 @@ def linear(x: torch.Tensor, w_tiles: torch.Tensor, N: int, *, w_fp32: bool = Fal
            k_cache3: Optional[torch.Tensor] = None, v_cache3: Optional[torch.Tensor] = None, b3_products: int = 6) -> torch.Tensor:
     """``w3`` (``pack_weight_w3`` of the same fp32 matrix): many-row calls run the bf16x3-split kernel (gemm_b3.hip).
     ``k_cache3`` / ``v_cache3`` (``kv3_cache``): EPI_QKV_ROPE also writes the K / V rows as bf16x3 pieces (``attention_rows3``)."""
-    lib = E.load_library()
     M = x.shape[0] if M is None else M
     K = x.shape[1] if K is None else K
     out_cols = N // 2 if epilogue == E.EPI_SWIGLU else (n_q_heads * 64 if epilogue == E.EPI_QKV_ROPE else N)
     if out is None:
         out = torch.empty(M, out_cols, dtype=torch.float32, device=x.device)
     a = E.GemmArgs()
-    a.w_dev, a.w_is_fp32, a.x_dev = E.dptr(w_tiles), int(w_fp32), E.dptr(x)
+    a.w_dev, a.w_is_fp32, a.x_dev = dptr(w_tiles), int(w_fp32), dptr(x)
     a.ldx = x.stride(0) if ldx is None else ldx
     a.x_bstride, a.rows_per_batch, a.M, a.N, a.K = x_bstride, rows_per_batch, M, N, K
-    a.prologue, a.epilogue, a.gamma_dev, a.eps = prologue, epilogue, E.dptr(gamma), eps
-    a.bias_dev, a.scale_dev, a.resid_dev = E.dptr(bias), E.dptr(scale), E.dptr(resid)
+    a.prologue, a.epilogue, a.gamma_dev, a.eps = prologue, epilogue, dptr(gamma), eps
+    a.bias_dev, a.scale_dev, a.resid_dev = dptr(bias), dptr(scale), dptr(resid)
     a.ldr, a.r_bstride = ldr, r_bstride
-    a.out_dev = E.dptr(out)
+    a.out_dev = dptr(out)
     a.ldo = (out.stride(0) if out.dim() == 2 else out_cols) if ldo is None else ldo
     a.o_bstride = o_bstride
-    a.elu_out, a.raw_out_dev, a.raw_bstride = int(elu_out), E.dptr(raw_out), raw_bstride
-    a.rope_dev, a.row_pos_dev, a.row_slot_dev = E.dptr(rope), E.dptr(row_pos), E.dptr(row_slot)
-    a.k_cache_dev, a.v_cache_dev = E.dptr(k_cache), E.dptr(v_cache)
+    a.elu_out, a.raw_out_dev, a.raw_bstride = int(elu_out), dptr(raw_out), raw_bstride
+    a.rope_dev, a.row_pos_dev, a.row_slot_dev = dptr(rope), dptr(row_pos), dptr(row_slot)
+    a.k_cache_dev, a.v_cache_dev = dptr(k_cache), dptr(v_cache)
     a.n_q_heads, a.n_kv_heads, a.cache_len = n_q_heads, n_kv_heads, cache_len
-    a.w3_dev = E.dptr(w3)
-    a.splitk_ws_dev, a.splitk_ws_floats = E.dptr(splitk_ws), (splitk_ws.numel() if splitk_ws is not None else 0)
-    a.beta_dev, a.ln_scratch_dev = E.dptr(beta), E.dptr(ln_scratch)
-    a.k_cache3_dev, a.v_cache3_dev = E.dptr(k_cache3), E.dptr(v_cache3)
+    a.w3_dev = dptr(w3)
+    a.splitk_ws_dev, a.splitk_ws_floats = dptr(splitk_ws), (splitk_ws.numel() if splitk_ws is not None else 0)
+    a.beta_dev, a.ln_scratch_dev = dptr(beta), dptr(ln_scratch)
+    a.k_cache3_dev, a.v_cache3_dev = dptr(k_cache3), dptr(v_cache3)
     a.b3_products = b3_products
-    E.check(lib.smoltts_k_gemm(C.byref(a), E.current_stream_ptr()), "smoltts_k_gemm")
+    _k("smoltts_k_gemm", C.byref(a))
     return out
 
 
 def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, row_pos: torch.Tensor,
               row_slot: torch.Tensor, n_q_heads: int, window: int = 0, out_x3: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q [rows, Hq*64]; caches [slots, KV, cache_len, 64] fp32 or bf16; -> [rows, Hq*64] (and the X3 operand if given)."""
-    lib = E.load_library()
     n_kv, cache_len = k_cache.shape[1], k_cache.shape[2]
     assert k_cache.dtype == v_cache.dtype and k_cache.dtype in (torch.float32, torch.bfloat16)
     out = torch.empty_like(q)
-    E.check(lib.smoltts_k_attention_kv(E.dptr(q), E.dptr(k_cache), E.dptr(v_cache), E.dptr(row_pos), E.dptr(row_slot),
-                                       q.shape[0], n_q_heads, n_kv, cache_len, window, E.dptr(out), E.dptr(out_x3),
-                                       1 if k_cache.dtype == torch.bfloat16 else 0, E.current_stream_ptr()), "smoltts_k_attention_kv")
+    _k("smoltts_k_attention_kv", dptr(q), dptr(k_cache), dptr(v_cache), dptr(row_pos), dptr(row_slot), q.shape[0], n_q_heads, n_kv,
+       cache_len, window, dptr(out), dptr(out_x3), 1 if k_cache.dtype == torch.bfloat16 else 0)
     return out
 
 
@@ -127,11 +131,9 @@ def kv3_encode(values: torch.Tensor, is_v: bool) -> torch.Tensor:
 def attention_rows3(q: torch.Tensor, k_cache3: torch.Tensor, v_cache3: torch.Tensor, row_pos: torch.Tensor, row_slot: torch.Tensor,
                     rows_per_slot: int, n_heads: int, cache_len: int, window: int = 0) -> torch.Tensor:
     """Attention of ``rows_per_slot`` (a multiple of 32) consecutive positions per slot over bf16x3 piece caches (attn_rows3_kernel)."""
-    lib = E.load_library()
     out = torch.empty_like(q)
-    E.check(lib.smoltts_k_attention_rows3(E.dptr(q), E.dptr(k_cache3), E.dptr(v_cache3), E.dptr(row_pos), E.dptr(row_slot), q.shape[0],
-                                          rows_per_slot, n_heads, cache_len, window, E.dptr(out), E.current_stream_ptr()),
-            "smoltts_k_attention_rows3")
+    _k("smoltts_k_attention_rows3", dptr(q), dptr(k_cache3), dptr(v_cache3), dptr(row_pos), dptr(row_slot), q.shape[0], rows_per_slot,
+       n_heads, cache_len, window, dptr(out))
     return out
 
 
@@ -142,35 +144,28 @@ def attention_split(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
                     n_q_heads: int, scratch, window: int = 0, out_x3: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``attention`` with the keys of every (row, kv head) pair on two workgroups (rows x kv heads <= 128, cache_len > 128).
     ``scratch`` = (part fp32 [SPLIT_PART_FLOATS], ticket int32 [SPLIT_TICKETS] zeroed once and then left alone)."""
-    lib = E.load_library()
     n_kv, cache_len = k_cache.shape[1], k_cache.shape[2]
     part, ticket = scratch
     assert part.numel() >= SPLIT_PART_FLOATS and ticket.numel() >= SPLIT_TICKETS and ticket.dtype == torch.int32
     out = torch.empty_like(q)
-    E.check(lib.smoltts_k_attention_split(E.dptr(q), E.dptr(k_cache), E.dptr(v_cache), E.dptr(row_pos), E.dptr(row_slot),
-                                          q.shape[0], n_q_heads, n_kv, cache_len, window, E.dptr(out), E.dptr(out_x3),
-                                          1 if k_cache.dtype == torch.bfloat16 else 0, E.dptr(part), E.dptr(ticket),
-                                          E.current_stream_ptr()), "smoltts_k_attention_split")
+    _k("smoltts_k_attention_split", dptr(q), dptr(k_cache), dptr(v_cache), dptr(row_pos), dptr(row_slot), q.shape[0], n_q_heads, n_kv,
+       cache_len, window, dptr(out), dptr(out_x3), 1 if k_cache.dtype == torch.bfloat16 else 0, dptr(part), dptr(ticket))
     return out
 
 
 def embed(cols: torch.Tensor, text_emb: torch.Tensor, cb_emb: torch.Tensor, codebook_size: int, cb_first_offset: int = 0,
           mask_mode: int = 0, sem_start: int = 320, sem_end: int = 2367) -> torch.Tensor:
     """cols int32 [rows, 1+n]; bf16 tables; -> fp32 [rows, dim]."""
-    lib = E.load_library()
     rows, dim = cols.shape[0], text_emb.shape[1]
     x = torch.empty(rows, dim, dtype=torch.float32, device=cols.device)
-    E.check(lib.smoltts_k_embed(E.dptr(cols), rows, cols.shape[1] - 1, E.dptr(text_emb), E.dptr(cb_emb), dim, codebook_size,
-                                cb_first_offset, mask_mode, sem_start, sem_end, E.dptr(x), E.current_stream_ptr()),
-            "smoltts_k_embed")
+    _k("smoltts_k_embed", dptr(cols), rows, cols.shape[1] - 1, dptr(text_emb), dptr(cb_emb), dim, codebook_size, cb_first_offset,
+       mask_mode, sem_start, sem_end, dptr(x))
     return x
 
 
 def argmax(logits: torch.Tensor, margin: Optional[torch.Tensor] = None) -> torch.Tensor:
-    lib = E.load_library()
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    E.check(lib.smoltts_k_argmax(E.dptr(logits), logits.shape[0], logits.shape[1], logits.stride(0), E.dptr(ids), 1,
-                                 E.dptr(margin), E.current_stream_ptr()), "smoltts_k_argmax")
+    _k("smoltts_k_argmax", dptr(logits), logits.shape[0], logits.shape[1], logits.stride(0), dptr(ids), 1, dptr(margin))
     return ids
 
 
@@ -178,9 +173,7 @@ def slot_sampling_table(temp, fast_temp, min_p, seed, device="cuda") -> torch.Te
     """Rows of ``SmolttsSlotSampling`` (temp, fast_temp, min_p, 0, seed: 24 bytes each) as a uint8 device tensor."""
     import numpy as np
 
-    dt = np.dtype([("temp", "<f4"), ("fast_temp", "<f4"), ("min_p", "<f4"), ("reserved", "<u4"), ("seed", "<u8")])
-    n = len(temp)
-    a = np.zeros(n, dt)
+    a = np.zeros(len(temp), np.dtype(SlotSampling))
     a["temp"], a["fast_temp"], a["min_p"] = temp, fast_temp, min_p
     a["seed"] = np.array([int(x) & (2**64 - 1) for x in seed], dtype=np.uint64)
     return torch.from_numpy(a.view(np.uint8).copy()).to(device)
@@ -189,14 +182,13 @@ def slot_sampling_table(temp, fast_temp, min_p, seed, device="cuda") -> torch.Te
 def sample_rows(logits: torch.Tensor, table: torch.Tensor, frames: Optional[torch.Tensor] = None, step: int = 0) -> torch.Tensor:
     """``smoltts_k_sample_rows``: row r picked with its own entry ``table`` row r (``slot_sampling_table``) and the request key at
     frame ``frames[r]`` (None: r) and ``step`` (0: the entry's temp; > 0: fast_temp)."""
-    lib = E.load_library()
-    if table.dtype != torch.uint8 or table.numel() < 24 * logits.shape[0]:
+    if table.dtype != torch.uint8 or table.numel() < C.sizeof(SlotSampling) * logits.shape[0]:
         raise ValueError("table: 24 bytes per row (slot_sampling_table)")
     if frames is not None and (frames.dtype != torch.int32 or frames.numel() < logits.shape[0]):
         raise ValueError("frames: int32, one per row")
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    E.check(lib.smoltts_k_sample_rows(E.dptr(logits), logits.shape[0], logits.shape[1], logits.stride(0), E.dptr(table), E.dptr(frames),
-                                      int(step), E.dptr(ids), E.current_stream_ptr()), "smoltts_k_sample_rows")
+    _k("smoltts_k_sample_rows", dptr(logits), logits.shape[0], logits.shape[1], logits.stride(0), dptr(table), dptr(frames), int(step),
+       dptr(ids))
     return ids
 
 
@@ -205,8 +197,7 @@ def slot_filter_table(top_p, top_k, penalty, window, device="cuda") -> torch.Ten
     tensor, normalised as ``smoltts_session_set_slot_filters`` does (top_p >= 1 -> 0; penalty <= 1 or window 0 -> all three 0)."""
     import numpy as np
 
-    dt = np.dtype([("top_p", "<f4"), ("top_k", "<i4"), ("penalty", "<f4"), ("inv_penalty", "<f4"), ("window", "<i4"), ("reserved", "<i4", 3)])
-    a = np.zeros(len(top_p), dt)
+    a = np.zeros(len(top_p), np.dtype(SlotFilters))
     tp = np.asarray(top_p, np.float32)
     a["top_p"] = np.where(tp < 1, tp, 0)
     a["top_k"] = top_k
@@ -222,11 +213,10 @@ def sample_rows_filtered(logits: torch.Tensor, table: torch.Tensor, filters: tor
                          frames: Optional[torch.Tensor] = None, step: int = 0) -> torch.Tensor:
     """``smoltts_k_sample_rows_filtered``: ``sample_rows`` with row r's filters ``filters`` row r (``slot_filter_table``) and its
     explicit history: the first ``min(history_len[r], window)`` ids of ``history[r]`` (int32 [rows, 64], newest first)."""
-    lib = E.load_library()
     R = logits.shape[0]
-    if table.dtype != torch.uint8 or table.numel() < 24 * R:
+    if table.dtype != torch.uint8 or table.numel() < C.sizeof(SlotSampling) * R:
         raise ValueError("table: 24 bytes per row (slot_sampling_table)")
-    if filters.dtype != torch.uint8 or filters.numel() < 32 * R:
+    if filters.dtype != torch.uint8 or filters.numel() < C.sizeof(SlotFilters) * R:
         raise ValueError("filters: 32 bytes per row (slot_filter_table)")
     if history.dtype != torch.int32 or tuple(history.shape) != (R, 64) or not history.is_contiguous():
         raise ValueError("history: contiguous int32 [rows, 64]")
@@ -235,17 +225,14 @@ def sample_rows_filtered(logits: torch.Tensor, table: torch.Tensor, filters: tor
     if frames is not None and (frames.dtype != torch.int32 or frames.numel() < R):
         raise ValueError("frames: int32, one per row")
     ids = torch.empty(R, dtype=torch.int32, device=logits.device)
-    E.check(lib.smoltts_k_sample_rows_filtered(E.dptr(logits), R, logits.shape[1], logits.stride(0), E.dptr(table), E.dptr(filters),
-                                               E.dptr(frames), E.dptr(history), E.dptr(history_len), int(step), E.dptr(ids),
-                                               E.current_stream_ptr()), "smoltts_k_sample_rows_filtered")
+    _k("smoltts_k_sample_rows_filtered", dptr(logits), R, logits.shape[1], logits.stride(0), dptr(table), dptr(filters), dptr(frames),
+       dptr(history), dptr(history_len), int(step), dptr(ids))
     return ids
 
 
 def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
-    lib = E.load_library()
     out = torch.empty_like(x)
-    E.check(lib.smoltts_k_layernorm(E.dptr(x), E.dptr(w), E.dptr(b), x.shape[0], x.shape[1], eps, E.dptr(out),
-                                    E.current_stream_ptr()), "smoltts_k_layernorm")
+    _k("smoltts_k_layernorm", dptr(x), dptr(w), dptr(b), x.shape[0], x.shape[1], eps, dptr(out))
     return out
 
 
@@ -256,13 +243,11 @@ def seanet_resblock(xbuf: torch.Tensor, T: int, w2_w3: torch.Tensor, b2: torch.T
     input (rows >= T; only [0, T) are read); ELU(x + conv_k1(ELU(conv_k3(ELU(x))))) of those T rows goes to
     ``out[:, out_lead : out_lead + T]`` (fp32 [slots, out_lead + rows', C]).  ``w2_w3`` / ``w3_w3``: ``pack_weight_w3`` of the
     ``conv_as_gemm`` matrices [C/2, 3C] and [C, C/2]."""
-    lib = E.load_library()
     S, rows, Cn = xbuf.shape
     assert xbuf.dtype == out.dtype == torch.float32 and xbuf.stride(2) == 1 and xbuf.stride(1) == Cn and out.stride(2) == 1 and out.stride(1) == Cn
     assert out.shape[0] == S and out.shape[2] == Cn and 0 < T <= rows - 2 and out_lead + T <= out.shape[1]
-    E.check(lib.smoltts_k_seanet_resblock(Cn, S, T, xbuf.data_ptr() + 4 * 2 * Cn, xbuf.stride(0), E.dptr(w2_w3), E.dptr(b2), E.dptr(w3_w3),
-                                          E.dptr(b3), out.data_ptr() + 4 * out_lead * Cn, out.stride(0), b3_products, E.current_stream_ptr()),
-            "smoltts_k_seanet_resblock")
+    _k("smoltts_k_seanet_resblock", Cn, S, T, xbuf.data_ptr() + 4 * 2 * Cn, xbuf.stride(0), dptr(w2_w3), dptr(b2), dptr(w3_w3), dptr(b3),
+       out.data_ptr() + 4 * out_lead * Cn, out.stride(0), b3_products)
     return out
 
 
@@ -273,14 +258,12 @@ def seanet_last(inbuf: torch.Tensor, T: int, wt_w3: torch.Tensor, bt: torch.Tens
     output); the 4 T samples of every slot go to ``pcm[:, : 4 T]`` (fp32 [slots, >= 4 T]).  ``slot_pos`` int32 [slots]: 0 = the slot's
     stream starts with this call (its halo rows must be zero).  Weights: ``pack_weight_w3`` of ``conv_as_gemm`` of the ConvTranspose
     ([256, 256], bias repeated: [256]) and of the block's convs ([32, 192], [64, 32]); ``final_w`` fp32 [3 * 64] tap-major."""
-    lib = E.load_library()
     S, rows, Cn = inbuf.shape
     assert inbuf.dtype == pcm.dtype == torch.float32 and Cn == 128 and inbuf.stride(2) == 1 and inbuf.stride(1) == Cn and pcm.stride(1) == 1
     assert pcm.shape[0] == S and 0 < T <= rows - 2 and 4 * T <= pcm.shape[1] and slot_pos.dtype == torch.int32 and slot_pos.numel() >= S
     assert bt.numel() == 256 and final_w.numel() == 192
-    E.check(lib.smoltts_k_seanet_last(S, T, inbuf.data_ptr() + 4 * 2 * Cn, inbuf.stride(0), E.dptr(wt_w3), E.dptr(bt), E.dptr(w2_w3), E.dptr(b2),
-                                      E.dptr(w3_w3), E.dptr(b3), E.dptr(final_w), float(final_b), E.dptr(pcm), pcm.stride(0), E.dptr(slot_pos),
-                                      b3_products, E.current_stream_ptr()), "smoltts_k_seanet_last")
+    _k("smoltts_k_seanet_last", S, T, inbuf.data_ptr() + 4 * 2 * Cn, inbuf.stride(0), dptr(wt_w3), dptr(bt), dptr(w2_w3), dptr(b2),
+       dptr(w3_w3), dptr(b3), dptr(final_w), float(final_b), dptr(pcm), pcm.stride(0), dptr(slot_pos), b3_products)
     return pcm
 
 
@@ -290,14 +273,13 @@ def rvq_upsample(codes: torch.Tensor, f0: int, n_frames: int, nq: int, table: to
     code_offset + nq) -> the decoder transformer's input rows fp32 [slots, 2 n_frames, 512].  ``table`` fp32 [nq, 2048, 512] (codebooks
     with the output projection folded in), ``upw`` fp32 [4, 512]; ``carry_in`` [slots, 512] = the embedding of frame f0 - 1 (None: no
     predecessor), ``carry_out`` receives that of the call's last frame."""
-    lib = E.load_library()
     S, F, row = codes.shape
     assert codes.dtype == torch.int32 and codes.is_contiguous() and 0 <= f0 and n_frames > 0 and f0 + n_frames <= F
     assert tuple(table.shape) == (nq, 2048, 512) and table.is_contiguous() and tuple(upw.shape) == (4, 512) and upw.is_contiguous()
     assert carry_out.numel() >= S * 512 and (carry_in is None or carry_in.numel() >= S * 512)
     tx = torch.empty(S, 2 * n_frames, 512, dtype=torch.float32, device=codes.device)
-    E.check(lib.smoltts_k_rvq_upsample(codes.data_ptr() + 4 * f0 * row, F * row, row, code_offset, nq, S, n_frames, E.dptr(table), E.dptr(upw),
-                                       E.dptr(carry_in), E.dptr(carry_out), E.dptr(tx), E.current_stream_ptr()), "smoltts_k_rvq_upsample")
+    _k("smoltts_k_rvq_upsample", codes.data_ptr() + 4 * f0 * row, F * row, row, code_offset, nq, S, n_frames, dptr(table), dptr(upw),
+       dptr(carry_in), dptr(carry_out), dptr(tx))
     return tx
 
 
@@ -321,40 +303,12 @@ def x3_to_float(buf: torch.Tensor, rows: int, K: int) -> torch.Tensor:
 def x3_pack(x: torch.Tensor, gamma_a: Optional[torch.Tensor] = None, gamma_b: Optional[torch.Tensor] = None,
             two: bool = False):
     """fp32 rows on the GPU -> (X3 of x*gamma_a, X3 of x*gamma_b or None, ssq [rows, K/16])."""
-    lib = E.load_library()
     rows, K = x.shape
     a = x3_alloc(rows, K)
     b = x3_alloc(rows, K) if two else None
     ssq = torch.zeros(rows, K // 16, dtype=torch.float32, device=x.device)
-    lib.smoltts_k_x3_pack.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6
-    E.check(lib.smoltts_k_x3_pack(E.dptr(x), x.stride(0), rows, K, E.dptr(a), E.dptr(gamma_a), E.dptr(b), E.dptr(gamma_b),
-                                  E.dptr(ssq), E.current_stream_ptr()), "smoltts_k_x3_pack")
+    _k("smoltts_k_x3_pack", dptr(x), x.stride(0), rows, K, dptr(a), dptr(gamma_a), dptr(b), dptr(gamma_b), dptr(ssq))
     return a, b, ssq
-
-
-class Gemm3Args(C.Structure):
-    _fields_ = [
-        ("w_dev", C.c_void_p), ("x3_dev", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-        ("epilogue", C.c_int32), ("ssq_in_dev", C.c_void_p), ("eps", C.c_float), ("bias_dev", C.c_void_p),
-        ("resid_dev", C.c_void_p), ("out_dev", C.c_void_p), ("ldo", C.c_int64), ("x3_out_dev", C.c_void_p),
-        ("emit_a_dev", C.c_void_p), ("gamma_a_dev", C.c_void_p), ("emit_b_dev", C.c_void_p), ("gamma_b_dev", C.c_void_p),
-        ("ssq_out_dev", C.c_void_p), ("rope_dev", C.c_void_p), ("row_pos_dev", C.c_void_p), ("row_slot_dev", C.c_void_p),
-        ("k_cache_dev", C.c_void_p), ("v_cache_dev", C.c_void_p), ("n_q_heads", C.c_int32), ("n_kv_heads", C.c_int32),
-        ("cache_len", C.c_int32), ("w_format", C.c_int32), ("w_scale_dev", C.c_void_p), ("v_x3_dev", C.c_void_p),
-        ("kv_format", C.c_int32),
-        ("w_stream", C.c_int32),
-        ("attn_q_dev", C.c_void_p), ("attn_pos", C.c_int32),
-        ("cand_out_dev", C.c_void_p), ("pick", C.c_void_p), ("fp8_activations", C.c_int32),
-    ]
-
-
-class PickArgs(C.Structure):  # SmolttsPickArgs (include/smoltts_hip.h)
-    _fields_ = [
-        ("cand_dev", C.c_void_p), ("cand_tiles", C.c_int32), ("qkv_table_dev", C.c_void_p), ("rope_dev", C.c_void_p),
-        ("emb_dev", C.c_void_p), ("emb_row_offset", C.c_int32), ("ids_dev", C.c_void_p), ("ids_stride", C.c_int32),
-        ("margin_dev", C.c_void_p), ("margin_mask_dev", C.c_void_p), ("margin_at_dev", C.c_void_p), ("frames_dev", C.c_void_p),
-        ("step", C.c_int32),
-    ]
 
 
 @dataclass
@@ -378,11 +332,11 @@ class Pick:
 
     def args(self) -> PickArgs:
         k = PickArgs()
-        k.cand_dev, k.cand_tiles = E.dptr(self.cand), self.cand.shape[1]
-        k.qkv_table_dev, k.rope_dev, k.emb_dev, k.emb_row_offset = E.dptr(self.table), E.dptr(self.rope), E.dptr(self.emb), self.emb_row_offset
-        k.ids_dev, k.ids_stride = E.dptr(self.ids), self.ids_stride
-        k.margin_dev, k.margin_mask_dev = E.dptr(self.margin), E.dptr(self.margin_mask)
-        k.margin_at_dev, k.frames_dev, k.step = E.dptr(self.margin_at), E.dptr(self.frames), self.step
+        k.cand_dev, k.cand_tiles = dptr(self.cand), self.cand.shape[1]
+        k.qkv_table_dev, k.rope_dev, k.emb_dev, k.emb_row_offset = dptr(self.table), dptr(self.rope), dptr(self.emb), self.emb_row_offset
+        k.ids_dev, k.ids_stride = dptr(self.ids), self.ids_stride
+        k.margin_dev, k.margin_mask_dev = dptr(self.margin), dptr(self.margin_mask)
+        k.margin_at_dev, k.frames_dev, k.step = dptr(self.margin_at), dptr(self.frames), self.step
         return k
 
 
@@ -410,30 +364,28 @@ def linear3(x3: torch.Tensor, w_tiles: torch.Tensor, M: int, N: int, K: int, *, 
     ``k_cache`` / ``v_cache`` (row r = slot r), worked out inside the launch (attn_wo_kernel).
     ``pick`` given (EPI_RESID, ``attn_pos`` >= 1): ``attn_q`` and ``resid`` are not read -- each row's q, newest K / V and residual
     come from the table / embedding rows of its picked id (``Pick``), and the new K / V rows are written to the caches."""
-    lib = E.load_library()
-    lib.smoltts_k_gemm3.argtypes = [C.POINTER(Gemm3Args), C.c_void_p]
     if out is None and epilogue != E.EPI_SWIGLU:
         cols = n_q_heads * 64 if epilogue == E.EPI_QKV_ROPE else N
         out = torch.zeros(M, cols, dtype=torch.float32, device=w_tiles.device)
     a = Gemm3Args()
-    a.w_dev, a.x3_dev, a.M, a.N, a.K, a.epilogue = E.dptr(w_tiles), E.dptr(x3), M, N, K, epilogue
-    a.ssq_in_dev, a.eps, a.bias_dev, a.resid_dev = E.dptr(ssq_in), eps, E.dptr(bias), E.dptr(resid)
-    a.out_dev = E.dptr(out)
+    a.w_dev, a.x3_dev, a.M, a.N, a.K, a.epilogue = dptr(w_tiles), dptr(x3), M, N, K, epilogue
+    a.ssq_in_dev, a.eps, a.bias_dev, a.resid_dev = dptr(ssq_in), eps, dptr(bias), dptr(resid)
+    a.out_dev = dptr(out)
     a.ldo = out.stride(0) if out is not None else 0
-    a.x3_out_dev = E.dptr(x3_out)
-    a.emit_a_dev, a.gamma_a_dev, a.emit_b_dev, a.gamma_b_dev = E.dptr(emit_a), E.dptr(gamma_a), E.dptr(emit_b), E.dptr(gamma_b)
-    a.ssq_out_dev = E.dptr(ssq_out)
-    a.rope_dev, a.row_pos_dev, a.row_slot_dev = E.dptr(rope), E.dptr(row_pos), E.dptr(row_slot)
-    a.k_cache_dev, a.v_cache_dev = E.dptr(k_cache), E.dptr(v_cache)
+    a.x3_out_dev = dptr(x3_out)
+    a.emit_a_dev, a.gamma_a_dev, a.emit_b_dev, a.gamma_b_dev = dptr(emit_a), dptr(gamma_a), dptr(emit_b), dptr(gamma_b)
+    a.ssq_out_dev = dptr(ssq_out)
+    a.rope_dev, a.row_pos_dev, a.row_slot_dev = dptr(rope), dptr(row_pos), dptr(row_slot)
+    a.k_cache_dev, a.v_cache_dev = dptr(k_cache), dptr(v_cache)
     a.n_q_heads, a.n_kv_heads, a.cache_len = n_q_heads, n_kv_heads, cache_len
-    a.w_format, a.w_scale_dev = (1, E.dptr(w_scale)) if w_scale is not None else (0, None)
-    a.v_x3_dev = E.dptr(v_x3)
+    a.w_format, a.w_scale_dev = (1, dptr(w_scale)) if w_scale is not None else (0, None)
+    a.v_x3_dev = dptr(v_x3)
     a.kv_format = int(kv_format)
     a.w_stream = 1 if w_stream else 0
-    a.attn_q_dev, a.attn_pos = E.dptr(attn_q), int(attn_pos)
+    a.attn_q_dev, a.attn_pos = dptr(attn_q), int(attn_pos)
     a.fp8_activations = 1 if fp8_activations else 0  # fp8 weights, M >= 256: fp8 x fp8 MFMA on the activation's hi piece (not the parity path)
-    a.cand_out_dev = E.dptr(cand_out)  # EPI_STORE: per (row, 16-column tile) (max, first column of it as int bits, runner-up, -)
+    a.cand_out_dev = dptr(cand_out)  # EPI_STORE: per (row, 16-column tile) (max, first column of it as int bits, runner-up, -)
     pk = pick.args() if pick is not None else None  # (kept alive across the call)
-    a.pick = C.cast(C.pointer(pk), C.c_void_p) if pk is not None else None
-    E.check(lib.smoltts_k_gemm3(C.byref(a), E.current_stream_ptr()), "smoltts_k_gemm3")
+    a.pick = C.pointer(pk) if pk is not None else None
+    _k("smoltts_k_gemm3", C.byref(a))
     return out

@@ -1,0 +1,244 @@
+"""What a stream goes through behind its codec decode: the per-slot route, the plan of a pass over the live slots, and the
+converter that runs the stages (stages.py) by that plan."""
+from __future__ import annotations
+
+from dataclasses import dataclass, replace
+from functools import cached_property
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .abi import FLAC_F32, FLAC_OFF, FLAC_S16, SEAM_OFF
+from .device import upload
+from .formats import ENC_OFF, check_container, parse_stream_format
+from .stages import FlacEncoder, LoudnessNormalizer, Resampler, SeamJoiner, TimeStretcher
+from .tsm import out_bound
+
+
+STAGES = ("seam", "stretch", "resample", "flac")  # the stages every build has had, in launch order
+LAUNCH_ORDER = ("seam", "loudness", "stretch", "resample", "flac")  # the stages of a pass, in launch order
+FLOAT_STAGES = ("seam", "loudness", "stretch")  # fp32 in, fp32 out: the stages behind read their rows
+
+
+@dataclass(frozen=True)
+class SlotRoute:
+    """What a slot's stream goes through behind the codec (``StreamConverter``): its format (rate, SMOLTTS_RESAMPLE_*), its Q16
+    speed, FLAC framing, whether it is segmented (``start_segments``), its stream generation in the slot and whether its FLAC
+    stream header is still owed.  A restarted slot gets a new record: a pass keeps the records of its run."""
+    rate: int = 24000
+    enc: int = ENC_OFF
+    speed_q: int = 65536
+    flac: bool = False
+    segmented: bool = False
+    gen: int = 0
+    head_owed: bool = False
+    loudness: Optional[float] = None  # target in LUFS (None: the slot never enters the loudness stage)
+    start_gain_db: float = 0.0        # its stream's first knot
+
+    @cached_property
+    def stages(self) -> Tuple[str, ...]:
+        """The stages the slot goes through, in launch order."""
+        on = (self.segmented, self.loudness is not None, self.speed_q != 65536, self.enc != ENC_OFF, self.flac)
+        return tuple(s for s, o in zip(LAUNCH_ORDER, on) if o)
+
+
+class PassPlan(NamedTuple):
+    stages: List[str]                 # the stages to launch, in order
+    rows: Dict[str, List[int]]        # the live slots each of them serves
+    through: Dict[str, List[int]]     # float stage (seam, loudness, stretch) -> the live slots it does not serve that a later stage does
+    source: Dict[int, Optional[str]]  # live slot -> the last stage it goes through (None: its codec rows are its output)
+    host: List[str]                   # the stages whose outputs are copied to the host: the sources of the live slots
+    routes: Dict[int, SlotRoute]      # live slot -> its route when planned
+
+
+def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
+    """The plan of one converter pass over the live slots' routes (``{slot: SlotRoute}``, in slot order); no device involved."""
+    rows = {s: [] for s in LAUNCH_ORDER}
+    through = {s: [] for s in FLOAT_STAGES}
+    source = {}
+    for b, r in routes.items():
+        path = r.stages
+        source[b] = path[-1] if path else None
+        for s in path:
+            rows[s].append(b)
+        for s in through:
+            if path and s not in path and LAUNCH_ORDER.index(path[-1]) > LAUNCH_ORDER.index(s):
+                through[s].append(b)
+    stages = [s for s in LAUNCH_ORDER if rows[s]]
+    return PassPlan(stages, {s: rows[s] for s in stages}, {s: through[s] for s in through if rows[s]}, source,
+                    [s for s in stages if s in source.values()], routes)
+
+
+class StreamConverter:
+    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``STAGES``): a
+    segmented slot (``start_segments``) is joined by the seam stage (``SeamJoiner``), a slot with a speed is time-stretched
+    (``TimeStretcher``), a slot with an output format is converted (``Resampler``), and a slot with a FLAC container is framed
+    (``FlacEncoder``, from the resampler's int16, or from the float32 at 24 kHz); each stage reads the output of the one in
+    front, and the state of the stages behind the seam carries from segment to segment.  Each stage is created the first time
+    a slot needs it (``seam``: the seam stage at once).  ``n_in``: codec samples per slot and call."""
+
+    def __init__(self, device: torch.device, max_batch: int, n_in: int, seam: bool = False):
+        self.device, self.B, self.n_in = device, max_batch, n_in
+        self.rs: Optional[Resampler] = None
+        self.ts: Optional[TimeStretcher] = None
+        self.fl: Optional[FlacEncoder] = None
+        self.sj: Optional[SeamJoiner] = SeamJoiner(device, max_batch) if seam else None
+        self.ln: Optional[LoudnessNormalizer] = None
+        self.routes = [SlotRoute()] * max_batch
+        self._plan: Optional[PassPlan] = None  # the last pass's plan
+
+    def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]],
+                    containers: Optional[Sequence[Optional[str]]] = None, loudness: Optional[Sequence[Optional[float]]] = None,
+                    start_gain_db: Optional[Sequence[Optional[float]]] = None) -> None:
+        """Start new streams in ``slots`` on the current stream: ``formats[i]`` an ``output_format`` (None / ``pcm_24000``:
+        float32), ``speed_q[i]`` a Q16 speed (None / 65536: none), ``containers[i]`` None or ``"flac"`` (FLAC frames of the
+        slot's 16-bit samples at its rate), ``loudness[i]`` a target in LUFS (None: none) reached from ``start_gain_db[i]``.
+        A slot with none of them is switched off."""
+        if not slots:
+            return
+        formats = [f or "pcm_24000" for f in formats]
+        routes = []
+        none = [None] * len(slots)
+        for b, f, q, c, lt, sg in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none):
+            rate, enc = parse_stream_format(f)
+            flac = check_container(c, f) is not None
+            routes.append(SlotRoute(rate, enc, q or 65536, flac, segmented=False, gen=self.routes[b].gen + 1, head_owed=flac,
+                                    loudness=lt, start_gain_db=sg or 0.0))
+        if self.ln is None and any(r.loudness is not None for r in routes):
+            self.ln = LoudnessNormalizer(self.device, self.B)
+        if self.ln is not None:
+            self.ln.reset_slots(slots, [r.loudness for r in routes], [r.start_gain_db for r in routes])
+        if self.rs is None and any(r.enc != ENC_OFF for r in routes):
+            self.rs = Resampler(self.device, self.B, out_bound(self.n_in))
+        if self.ts is None and any(r.speed_q != 65536 for r in routes):
+            self.ts = TimeStretcher(self.device, self.B)
+        if self.fl is None and any(r.flac for r in routes):
+            self.fl = FlacEncoder(self.device, self.B)
+        if self.rs is not None:
+            self.rs.reset_slots(slots, formats)
+        if self.ts is not None:
+            self.ts.reset_slots(slots, [r.speed_q for r in routes])
+        if self.fl is not None:
+            self.fl.reset_slots(slots, [r.rate for r in routes],
+                                [FLAC_OFF if not r.flac else (FLAC_F32 if r.enc == ENC_OFF else FLAC_S16) for r in routes])
+        if self.sj is not None:
+            self.sj.start_segments(slots, [0] * len(slots), [SEAM_OFF] * len(slots))
+        for b, r in zip(slots, routes):
+            self.routes[b] = r
+
+    def start_segments(self, slots: Sequence[int], pauses: Sequence[int], flags: Sequence[int],
+                       leads: Optional[Sequence[int]] = None) -> None:
+        """Open the next segment of the segmented streams in ``slots`` (``SeamJoiner.start_segments``), after ``reset_slots``
+        started the streams; the other stages' state is kept."""
+        if self.sj is None:
+            self.sj = SeamJoiner(self.device, self.B)
+        self.sj.start_segments(slots, pauses, flags, leads)
+        for b, f in zip(slots, flags):
+            self.routes[b] = replace(self.routes[b], segmented=not int(f) & SEAM_OFF)
+
+    def converts(self, b: int) -> bool:
+        """Whether slot ``b``'s stream goes through a stage: its chunks are ``StreamPass.chunk``'s, not the codec's float32."""
+        return bool(self.routes[b].stages)
+
+    def plan(self, slots: Sequence[int]) -> PassPlan:
+        """The plan of a pass over the live ``slots``: the last one again while they and their routes stay the same."""
+        p, slots = self._plan, tuple(slots)
+        if p is None or tuple(p.routes) != slots or any(self.routes[b] is not r for b, r in p.routes.items()):
+            p = self._plan = plan_pass({b: self.routes[b] for b in slots})
+        return p
+
+    def ends(self, slots: Sequence[int]):
+        """The end markers a pass over ``slots`` needs: (``last``: some slot has a speed, FLAC or segments; ``seg_end``: some
+        slot has segments)."""
+        stages = self.plan(slots).stages
+        return any(s in stages for s in ("seam", "stretch", "flac")), "seam" in stages
+
+    def _through(self, plan: PassPlan, stage: str, out: torch.Tensor, counts: torch.Tensor, pcm: torch.Tensor, n_in: int,
+                 valid: torch.Tensor) -> torch.Tensor:
+        """After a float stage: its rows of the slots it passes through (``plan.through``) take the ``pcm`` it read, so that the
+        stages behind serve all slots in one launch each; returns the valid counts of its rows."""
+        plain = plan.through[stage]
+        if not plain:
+            return counts
+        served = np.zeros(out.shape[0], np.int32)
+        served[plan.rows[stage]] = 1
+        served_d, plain_d = upload([served, np.asarray(plain, np.int64)], self.device)
+        out[plain_d, :n_in] = pcm[plain_d]
+        return torch.where(served_d != 0, counts, valid)
+
+    def run(self, pcm: torch.Tensor, n_in: int, valid: torch.Tensor, last: Optional[torch.Tensor] = None,
+            slots: Optional[Sequence[int]] = None, seg_end: Optional[torch.Tensor] = None) -> Optional["StreamPass"]:
+        """Queue the stages for ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in]) on the current stream.
+        ``valid`` (device int32 [batch]): the samples of each row that are real; ``last`` / ``seg_end`` (device int32 [batch],
+        needed as ``ends`` says): nonzero where the row's stream / segment ends with this call.  ``slots``: the live streams
+        (default: every slot); the others consume what ``valid`` gives them and are never read.  None when no live slot
+        converts: no launch."""
+        plan = self.plan(range(self.B) if slots is None else slots)
+        if not plan.stages:
+            return None
+        batch, outs = pcm.shape[0], {}
+        if "seam" in plan.stages:  # (each float stage's rows, counts and width are what the stages behind it read)
+            out, counts = outs["seam"] = self.sj.new_outputs(batch, n_in)
+            self.sj.chunk(pcm, n_in, out, counts, valid=valid, seg_end=seg_end, last=last)
+            valid, pcm, n_in = self._through(plan, "seam", out, counts, pcm, n_in, valid), out, out.shape[1]
+        if "loudness" in plan.stages:
+            out, counts = outs["loudness"] = self.ln.new_outputs(batch, n_in)
+            self.ln.chunk(pcm, n_in, out, counts, valid=valid)
+            valid, pcm, n_in = self._through(plan, "loudness", out, counts, pcm, n_in, valid), out, out.shape[1]
+        if "stretch" in plan.stages:
+            out, counts = outs["stretch"] = self.ts.new_outputs(batch, n_in)
+            self.ts.chunk(pcm, n_in, out, counts, valid=valid, last=last)
+            valid, pcm, n_in = self._through(plan, "stretch", out, counts, pcm, n_in, valid), out, out.shape[1]
+        if "resample" in plan.stages:
+            out, counts = outs["resample"] = self.rs.new_outputs(batch, n_in)
+            self.rs.chunk(pcm, n_in, out, counts, valid=valid)
+        if "flac" in plan.stages:
+            s16, s16_counts = outs["resample"] if any(plan.routes[b].enc != ENC_OFF for b in plan.rows["flac"]) else (None, None)
+            fout, fsizes = outs["flac"] = self.fl.new_outputs(batch, max(n_in, s16.shape[1] // 2 if s16 is not None else 0))
+            self.fl.chunk(batch, fout, fsizes, pcm=pcm, n_in=n_in, valid=valid, s16=s16, s16_counts=s16_counts, last=last)
+        return StreamPass(self, {s: outs[s] for s in plan.host}, plan)
+
+    def close(self):
+        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln):
+            if stage is not None:
+                stage.close()
+        self.rs = self.ts = self.fl = self.sj = self.ln = None
+
+
+class StreamPass:
+    """The outputs of one ``StreamConverter.run``: on the device, then (``to_host``) on the host, read slot by slot (``chunk``).
+    It reads each slot by the plan of its run: a slot may have been restarted by the time its chunk is read."""
+
+    def __init__(self, conv: StreamConverter, dev: Dict[str, tuple], plan: PassPlan):
+        self.conv, self.rs = conv, conv.rs
+        self.dev = dev    # source stage -> its (output, counts) on the device
+        self.plan = plan
+        self.host = None
+
+    def converts(self, b: int) -> bool:
+        """Whether slot ``b`` was converted in the run (its chunk is ``chunk(b, ...)``)."""
+        return self.plan.source.get(b) is not None
+
+    def to_host(self, stream) -> None:
+        """Queue the host copies on ``stream``; ``chunk`` reads them once ``stream`` has run them."""
+        with torch.cuda.stream(stream):
+            self.host = {s: tuple(t.to("cpu", non_blocking=True) for t in ts) for s, ts in self.dev.items()}
+
+    def chunk(self, b: int, last: bool) -> np.ndarray:
+        """Slot ``b``'s chunk from its source stage: its FLAC frames as uint8 (behind the stream header on the stream's first
+        chunk), its converted samples (with the resampler's tail when ``last``), or the stretched / joined float32."""
+        route, source = self.plan.routes[b], self.plan.source[b]
+        out, counts = (t.numpy() for t in self.host[source])
+        if source == "flac":
+            from .flac import stream_header
+
+            data = b"".join(FlacEncoder.slot_frames(out, counts, b))
+            now = self.conv.routes[b]
+            if now.head_owed and now.gen == route.gen:
+                self.conv.routes[b] = replace(now, head_owed=False)
+                data = stream_header(route.rate) + data
+            return np.frombuffer(data, dtype=np.uint8).copy()
+        if source == "resample":
+            return self.rs.slot_bytes(out, counts, b, tail=last, enc=route.enc)
+        return out[b, : int(counts[b])].copy()

@@ -15,7 +15,7 @@ Codec work runs on a codec stream beside the ticks and its PCM is fetched on the
 streaming requests share one codec session whose slots mirror the LM slots (every slot keeps its own stream position,
 ``smoltts_mimi_reset_slots`` starts a new stream in a slot) and are decoded together, one codec pass per tick, launched once
 the host has seen that tick's snapshot (so beside the next tick); a stream with a speed or an output format is stretched
-and converted in the same pass (``engine.StreamConverter``).  A blocking request is decoded when its utterance is complete,
+and converted in the same pass (``route.StreamConverter``).  A blocking request is decoded when its utterance is complete,
 up to ``CODEC_BATCH`` finished utterances per codec pass.  A request's PCM is identical to what
 ``SmolTTS.__call__`` / ``stream`` return for it alone.
 """
@@ -52,7 +52,7 @@ class _Request:
     sampling: object = None  # config.RequestSampling, resolved at submit (seed drawn there for a sampled request without one)
     voice_entry: object = None  # _Voice of a registered voice, taken at submit (a later remove_voice does not affect the request)
     pos0: int = 0             # position of the prompt's first column: the voice's prefix length P for a registered voice
-    prefix: object = None     # engine.PrefixKV installed into the slot at admission (None: the whole prompt is prefilled)
+    prefix: object = None     # lm.PrefixKV installed into the slot at admission (None: the whole prompt is prefilled)
     speed_q: Optional[int] = None  # speaking speed in Q16 (tsm.py), time-stretched on the GPU; None: speed 1, no stretch
     stretch_in: list = field(default_factory=list)  # blocking requests with a speed: the utterance's PCM until its last pass
     container: Optional[str] = None  # streaming: "flac" frames the stream's 16-bit samples on the GPU (uint8 chunks)
@@ -128,7 +128,7 @@ class IncrementalRequest(_Request):
 class _Voice:
     voice_id: str
     grid: np.ndarray   # the speaker prompt grid (1 + n_fast, P)
-    prefix: object     # engine.PrefixKV: its KV rows, computed once
+    prefix: object     # lm.PrefixKV: its KV rows, computed once
     name: Optional[str] = None
 
 
@@ -157,7 +157,7 @@ class _Delivery:
     items: list       # [(request, codec slot, samples, last?)]
     urgent: bool = False  # a stream's first chunk is in it: handed out as soon as the pass is through
     keep: object = None   # device tensors the pass reads, kept alive until it has run
-    conv: object = None   # engine.StreamPass: the stream conversion of the pass (None: float32 rows of ``pcm``)
+    conv: object = None   # route.StreamPass: the stream conversion of the pass (None: float32 rows of ``pcm``)
 
 
 @dataclass
@@ -187,7 +187,8 @@ class BatchScheduler:
         import torch
 
         from ..config import GenerationSettings
-        from ..engine import LMSession, StreamConverter
+        from ..lm import LMSession
+        from ..route import StreamConverter
         from ..generate import _apply_sampling
 
         self.tts = tts
@@ -245,7 +246,7 @@ class BatchScheduler:
         self._parked: List[_Request] = []       # ... and incremental ones whose slot waits for text that has not arrived yet
         self._incs: List[_Request] = []         # the incremental requests alive (worker side)
         self._inc_new: "queue.Queue[_Request]" = queue.Queue()  # ... and those the worker has not seen yet
-        self._block_seam = None                 # seam stage of the blocking segmented requests (engine.SeamJoiner, 1 slot)
+        self._block_seam = None                 # seam stage of the blocking segmented requests (stages.SeamJoiner, 1 slot)
         self._dead: Optional[Exception] = None  # why the worker stopped
         self._draining = False
         self._held: Optional[_Request] = None   # next in line, waiting for room in a prefill call
@@ -486,7 +487,7 @@ class BatchScheduler:
         """Requests whose slots have just been armed: the streams' codec session, first / last tick, into the active set.  (A
         slot's codec stream restarts in ``_launch_stream_codec``, right before the pass of the request's first tick.)"""
         if self._stream_codec is None and any(r.stream for r in new):
-            from ..engine import MimiSession
+            from ..mimi import MimiSession
 
             self._stream_codec = MimiSession(self.tts.codec, max_batch=self.B, max_chunk_frames=max(self.tick, 1), products=self.codec_products)
             self._stream_codec.reset()
@@ -496,15 +497,15 @@ class BatchScheduler:
             self._active[r.slot] = r
 
     def _convert(self, pcm, n_frames_d, done_d, reqs: List[_Request], tick_no: int):
-        """The stream conversion of a codec pass (``engine.StreamConverter``, current stream, right behind the decode): slot b of
+        """The stream conversion of a codec pass (``route.StreamConverter``, current stream, right behind the decode): slot b of
         a request in ``reqs`` consumes the samples of the frames the tick's frame counter ``n_frames_d`` (device) gives it; every
         other slot none.  A slot with a speed ends its stream (flushes) in the tick where the host will see it finish, by the
-        rule of ``_drain`` on the same snapshot (``n_frames_d``, ``done_d``).  Returns the ``engine.StreamPass``, or None when the
+        rule of ``_drain`` on the same snapshot (``n_frames_d``, ``done_d``).  Returns the ``route.StreamPass``, or None when the
         converter converts no slot of ``reqs`` (then nothing is uploaded or launched)."""
         conv, slots = self._stream_conv, [r.slot for r in reqs]
         if not any(conv.converts(b) for b in slots):
             return None
-        from ..engine import upload
+        from ..device import upload
 
         torch = self._torch
         f0 = np.zeros(self.B, np.int32)
@@ -683,7 +684,7 @@ class BatchScheduler:
         """A parked stream ends: one pass of its stages behind the seam with no samples and the ``last`` marker (the stretcher's
         and the FLAC encoder's flush, the resampler's tail), on the codec stream behind the passes so far; its end marker
         follows that chunk and the slot is free (a next tenant's stages are reset behind this pass)."""
-        from ..engine import upload
+        from ..device import upload
 
         torch = self._torch
         n = self.tick * 1920
@@ -773,7 +774,8 @@ class BatchScheduler:
         job["done"].set()
 
     def _voice_steps(self, job):
-        from ..engine import LMSession, SmolttsError
+        from ..abi import SmolttsError
+        from ..lm import LMSession
 
         grid = job["grid"]
         if grid is None:
@@ -849,7 +851,7 @@ class BatchScheduler:
                  if r.stream and r.first_tick <= tick_no <= r.last_tick and not r.closed and not r.stream_done]
         if not alive or self._stream_codec is None:
             return None
-        from ..engine import upload
+        from ..device import upload
 
         with torch.cuda.stream(self._codec_stream):
             live = {r.slot for r in alive}
@@ -988,7 +990,8 @@ class BatchScheduler:
         is queued when the pool is full, when work has waited long enough — CODEC_WAIT frames of LM ticks while the LM batch is busy (wide
         passes cost half as much per frame as narrow ones), one tick otherwise — or when nothing else is going on; its PCM
         goes out chunk by chunk through _deliver."""
-        from ..engine import MimiSession, upload
+        from ..device import upload
+        from ..mimi import MimiSession
 
         torch = self._torch
         jobs = self._codec_jobs
@@ -1025,7 +1028,8 @@ class BatchScheduler:
             self._decode_finished_pass(jobs, occupied, nq)
 
     def _decode_finished_pass(self, jobs, occupied, nq) -> None:
-        from ..engine import MimiSession, upload
+        from ..device import upload
+        from ..mimi import MimiSession
 
         torch = self._torch
         if self._batch_codec is None:
@@ -1118,9 +1122,9 @@ class BatchScheduler:
             wait = False
 
     def _part_done(self, part: _Request) -> None:
-        """A segment's PCM of a blocking segmented request is complete; once all are, they are joined on the GPU (engine.seam_join)
+        """A segment's PCM of a blocking segmented request is complete; once all are, they are joined on the GPU (stages.seam_join)
         and go out, stretched first when the request has a speed."""
-        from ..engine import SeamJoiner, seam_join
+        from ..stages import SeamJoiner, seam_join
 
         r = part.part_of[0]
         sg = r.seg
@@ -1148,10 +1152,10 @@ class BatchScheduler:
 
     def _level(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
         """A complete blocking utterance (joined, not yet stretched): with a loudness target it is measured and scaled whole on
-        the GPU (engine.loudness_normalize: two launches, waited for here as the seam join is)."""
+        the GPU (stages.loudness_normalize: two launches, waited for here as the seam join is)."""
         if r.loudness is None:
             return pcm
-        from ..engine import loudness_normalize
+        from ..stages import loudness_normalize
         from ..loudness import gain_db
 
         with self._torch.cuda.stream(self._stretch_stream):
@@ -1172,7 +1176,7 @@ class BatchScheduler:
         side, one stretcher slot each, in calls of at most STRETCH_PIECE input samples per slot (a call at speed 0.25 is ~9 ms on
         the GPU), queued on the stretch stream with an event.  A step collects the previous call once its event has fired (the
         utterances that ended in it go out, each with its end marker) and queues the next one."""
-        from ..engine import TimeStretcher
+        from ..stages import TimeStretcher
 
         torch = self._torch
         fl = self._stretch_flight

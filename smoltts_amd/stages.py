@@ -1,0 +1,426 @@
+"""The stages behind the codec, one class per C stage (resampler, time stretch, seam, loudness, FLAC), and their
+whole-utterance helpers."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .abi import FLAC_F32, FLAC_S16, RESAMPLE_ULAW, SEAM_FIRST, SEAM_OFF, SmolttsError, check, load_library
+from .device import ClosesOnDel, _alloc_slab, current_stream_ptr, dptr
+from .formats import parse_stream_format
+from .seam import segment_flags
+
+
+# ------------------------------------------------------------------------------- streamed output formats
+def resample_design(out_rate: int):
+    """(taps float64 [2 half_len + 1], up, down, half_len) of ``out_rate``: scipy.signal.resample_poly's default filter, designed
+    on the host by the library (no device needed).  Raises SmolttsError for an unsupported rate."""
+    lib = load_library()
+    up, down, half = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.smoltts_resample_design(int(out_rate), None, 0, C.byref(up), C.byref(down), C.byref(half)), "smoltts_resample_design")
+    taps = np.zeros(2 * half.value + 1, np.float64)
+    check(lib.smoltts_resample_design(int(out_rate), taps.ctypes.data, taps.size, C.byref(up), C.byref(down), C.byref(half)),
+          "smoltts_resample_design")
+    return taps, up.value, down.value, half.value
+
+
+class _Stage(ClosesOnDel):
+    """What the stages behind the codec share: a slab of ``smoltts_<C_NAME>_bytes(max_batch)`` bytes that the handle of
+    ``smoltts_<C_NAME>_create`` lives in, destroyed by ``close`` once the device is idle, and the checks of a ``chunk`` call."""
+
+    C_NAME = ""
+
+    def __init__(self, device: torch.device, max_batch: int):
+        self.lib = load_library()
+        self.device, self.B = device, max_batch
+        need = getattr(self.lib, f"smoltts_{self.C_NAME}_bytes")(max_batch)
+        if need == 0:
+            raise SmolttsError(f"smoltts_{self.C_NAME}_bytes returned 0 (bad sizes)")
+        self.slab = _alloc_slab(need, device, settle=True)
+        h = C.c_void_p()
+        check(getattr(self.lib, f"smoltts_{self.C_NAME}_create")(dptr(self.slab), need, max_batch, *self._create_args(), C.byref(h)),
+              f"smoltts_{self.C_NAME}_create")
+        self.handle = h
+
+    def _create_args(self) -> tuple:
+        """What the stage's create call takes between ``max_batch`` and the handle."""
+        return ()
+
+    def _call(self, suffix: str, *args) -> None:
+        """``smoltts_<C_NAME>_<suffix>(handle, *args, current stream)``, checked."""
+        name = f"smoltts_{self.C_NAME}_{suffix}"
+        check(getattr(self.lib, name)(self.handle, *args, current_stream_ptr()), name)
+
+    def out_samples(self, n_in: int) -> int:
+        """Output samples per row that a call of ``n_in`` input samples needs."""
+        return int(getattr(self.lib, f"smoltts_{self.C_NAME}_out_samples")(int(n_in)))
+
+    def new_outputs(self, batch: int, n_in: int):
+        """Device buffers of one call of at most ``n_in`` input samples: (fp32 [batch, out_samples(n_in)], counts int32 [batch])."""
+        return (torch.empty(batch, self.out_samples(n_in), dtype=torch.float32, device=self.device),
+                torch.empty(batch, dtype=torch.int32, device=self.device))
+
+    @staticmethod
+    def _ints(v: Sequence[int]):
+        """``v`` as a host int32 array for the C calls."""
+        return (C.c_int32 * len(v))(*[int(x) for x in v])
+
+    def _check(self, batch: int, pcm: Optional[torch.Tensor], n_in: int, out: torch.Tensor, dtype, width: int,
+               counts: torch.Tensor, per_row: int, *controls: Optional[torch.Tensor]) -> None:
+        """``pcm``: device fp32 [>= batch, >= n_in] with unit-stride rows (None: not read); ``out``: contiguous ``dtype``
+        [>= batch, >= width]; ``counts``: contiguous int32 of ``per_row`` entries per row; ``controls``: None or contiguous
+        device int32 [>= batch]."""
+        assert batch <= self.B and out.dtype == dtype and out.is_contiguous() and out.shape[0] >= batch and out.shape[1] >= width
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.shape[0] >= batch and counts.numel() >= per_row * batch
+        assert pcm is None or (pcm.dtype == torch.float32 and pcm.stride(1) == 1 and pcm.shape[0] >= batch and 0 <= n_in <= pcm.shape[1])
+        for t in controls:
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= batch)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize()
+            getattr(self.lib, f"smoltts_{self.C_NAME}_destroy")(self.handle)
+            self.handle = None
+
+
+class Resampler(_Stage):
+    """Per-slot conversion of streamed 24 kHz fp32 PCM to ``pcm_<rate>`` int16 / ``ulaw_8000`` bytes on the GPU
+    (include/smoltts_hip.h, "Streamed output formats"): one launch per call for every slot, each at its own format.  Slots
+    start off; ``reset_slots`` starts a new stream in a slot with its format."""
+
+    C_NAME = "resampler"
+
+    def __init__(self, device: torch.device, max_batch: int, max_in: int):
+        super().__init__(device, max_batch)
+        self.out_stride = int(self.lib.smoltts_resampler_out_bytes(max_in))
+        self.formats = [(24000, 0)] * max_batch  # (rate, SMOLTTS_RESAMPLE_*) per slot
+
+    def reset_slots(self, slots: Sequence[int], formats: Sequence[str]) -> None:
+        """Start new streams in ``slots`` with their ``output_format`` (``pcm_24000``: the slot is not converted)."""
+        parsed = [parse_stream_format(f) for f in formats]
+        self._call("reset_slots", self._ints(slots), self._ints([p[0] for p in parsed]), self._ints([p[1] for p in parsed]), len(slots))
+        for b, p in zip(slots, parsed):
+            self.formats[b] = p
+
+    def new_outputs(self, batch: int, n_in: Optional[int] = None):
+        """Device buffers of one call: (bytes uint8 [batch, out_stride], counts int32 [batch, 2]); ``n_in``: size them for calls of
+        at most that many input samples instead of ``max_in``."""
+        stride = self.out_stride if n_in is None else int(self.lib.smoltts_resampler_out_bytes(n_in))
+        return (torch.empty(batch, stride, dtype=torch.uint8, device=self.device),
+                torch.empty(batch, 2, dtype=torch.int32, device=self.device))
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
+        """Convert ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream;
+        ``valid``: device int32 [batch], the samples of each row that are real (the rest is not consumed)."""
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.uint8, int(self.lib.smoltts_resampler_out_bytes(n_in)), counts, 2, valid)
+        check(self.lib.smoltts_resample_chunk(self.handle, dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1],
+                                              dptr(counts), current_stream_ptr()), "smoltts_resample_chunk")
+
+    def slot_bytes(self, host_out: np.ndarray, host_counts: np.ndarray, b: int, tail: bool = False,
+                   enc: Optional[int] = None) -> np.ndarray:
+        """Slot ``b``'s samples of a call, copied to the host: int16 for pcm_*, uint8 for ulaw_8000; with the tail if ``tail``.
+        ``enc``: the encoding the call ran with, when the slot may have been restarted since (default: its current one)."""
+        enc = self.formats[b][1] if enc is None else enc
+        n = int(host_counts[b, 0]) + (int(host_counts[b, 1]) if tail else 0)
+        width = 1 if enc == RESAMPLE_ULAW else 2
+        return host_out[b, : n * width].view(np.uint8 if enc == RESAMPLE_ULAW else np.int16).copy()
+
+
+# ------------------------------------------------------------------------------- speaking speed
+class TimeStretcher(_Stage):
+    """Per-slot pitch-preserving time stretch of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Speaking speed";
+    the numpy model is ``tsm.Stretcher``): one launch per call for every slot, each at its own speed.  Slots start off;
+    ``reset_slots`` starts a new stream in a slot at its ``speed_q`` (65536: off)."""
+
+    C_NAME = "tsm"
+
+    def reset_slots(self, slots: Sequence[int], speed_q: Sequence[int]) -> None:
+        self._call("reset_slots", self._ints(slots), self._ints(speed_q), len(slots))
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
+              last: Optional[torch.Tensor] = None) -> None:
+        """Stretch ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream.
+        ``valid``: device int32 [batch], the samples of each row that are real; ``last``: device int32 [batch], nonzero where the
+        row's stream ends with this call (the slot flushes).  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, last)
+        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(last), dptr(out), out.shape[1], dptr(counts))
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s counters (synchronises the current stream): k (next segment), p_prev, n_in, n_out, ended."""
+        v = (C.c_int64 * 5)()
+        self._call("slot_state", int(slot), v)
+        return dict(zip(("k", "p_prev", "n_in", "n_out", "ended"), list(v)))
+
+
+def _whole_row(stage: _Stage, x: np.ndarray, launch):
+    """A whole utterance through slot 0 of ``stage``: ``x`` (host, contiguous) goes up as the device row [1, n] (one zero sample
+    when empty), and ``launch(row, n, out, counts)`` queues the stage's call into ``stage.new_outputs(1, n)``.  Waits, and
+    returns the output row cut to its count, or for FLAC (counts: frame sizes [1, blocks, 2]) the row's frames."""
+    n = int(x.size)
+    row = torch.from_numpy(x).to(stage.device)[None] if n else torch.zeros(1, 1, dtype=torch.from_numpy(x).dtype, device=stage.device)
+    out, counts = stage.new_outputs(1, n)
+    launch(row, n, out, counts)
+    if counts.dim() == 1:
+        return out[0, :int(counts.cpu()[0])].cpu().numpy()
+    return FlacEncoder.slot_frames(out.cpu().numpy(), counts.cpu().numpy(), 0)
+
+
+def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device) -> np.ndarray:
+    """A whole utterance (float32 at 24 kHz) stretched on ``device`` (the model's) in one call with ``last`` set: exactly
+    ``tsm.out_length(len(pcm), speed_q)`` samples (``SmolTTS.__call__``).  Waits for the result.  ``speed_q == 65536`` returns
+    ``pcm`` untouched."""
+    pcm = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    if speed_q == 65536:
+        return pcm
+    with torch.cuda.device(device):
+        ts = TimeStretcher(device, 1)
+        try:
+            ts.reset_slots([0], [speed_q])
+            return _whole_row(ts, pcm, lambda x, n, out, cnt: ts.chunk(x, n, out, cnt, last=torch.ones(1, dtype=torch.int32, device=device)))
+        finally:
+            ts.close()
+
+
+# ------------------------------------------------------------------------------- long texts: the seam between segments
+class SeamJoiner(_Stage):
+    """Per-slot joining of a long text's segments on the GPU (include/smoltts_hip.h, "Seam"; the numpy model is
+    ``seam.SeamState``): one launch per call for every slot.  Slots start off; ``start_segments`` opens a segment in a slot with
+    its pause and flags (``SEAM_FIRST`` / ``SEAM_FINAL``; ``SEAM_OFF`` switches the slot off)."""
+
+    C_NAME = "seam"
+
+    def __init__(self, device: torch.device, max_batch: int):
+        super().__init__(device, max_batch)
+        self.zeros = [0] * max_batch  # zeros the slot's open segment owes at most (its lead and its pause)
+
+    def out_samples(self, n_in: int) -> int:
+        """Output samples per row of a call of ``n_in`` input samples, for the segments open now."""
+        return int(self.lib.smoltts_seam_out_samples(int(n_in), max(self.zeros)))
+
+    def start_segments(self, slots: Sequence[int], pauses: Sequence[int], flags: Sequence[int],
+                       leads: Optional[Sequence[int]] = None) -> None:
+        """Open a segment in each of ``slots`` on the current stream: its pause G (samples), flags, and the zeros in front of a
+        ``SEAM_FIRST`` segment (``leads``)."""
+        n = len(slots)
+        if not n:
+            return
+        leads = leads or [0] * n
+        self._call("reset_slots", self._ints(slots), self._ints(pauses), self._ints(flags), self._ints(leads), n)
+        for b, p, f, ld in zip(slots, pauses, flags, leads):
+            self.zeros[b] = 0 if int(f) & SEAM_OFF else int(p) + (int(ld) if int(f) & SEAM_FIRST else 0)
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
+              seg_end: Optional[torch.Tensor] = None, last: Optional[torch.Tensor] = None) -> None:
+        """Join ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream.
+        ``valid``: device int32 [batch], the real samples of each row; ``seg_end`` / ``last``: device int32 [batch], nonzero where
+        the row's segment / stream ends with this call.  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, seg_end, last)
+        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(seg_end), dptr(last), max(self.zeros), dptr(out),
+                   out.shape[1], dptr(counts))
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s state (synchronises the current stream): n_in, judged, ec, head, open, lead, pause, flags."""
+        v = (C.c_int64 * 8)()
+        self._call("slot_state", int(slot), v)
+        return dict(zip(("n_in", "judged", "ec", "head", "open", "lead", "pause", "flags"), list(v)))
+
+
+def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: torch.device, lead: int = 0, trail: int = 0,
+              joiner: Optional[SeamJoiner] = None) -> np.ndarray:
+    """Whole segments (float32 at 24 kHz) joined on ``device`` by the seam rule, one call per segment with its end set: what
+    ``seam.join`` computes (``SmolTTS.__call__`` with ``segment``).  ``pauses[k]``: the seam after segment k, in samples.
+    ``joiner``: a caller's ``SeamJoiner`` whose slot 0 is used (default: one made for the call).  Waits for the result."""
+    segs = [np.ascontiguousarray(np.asarray(s, dtype=np.float32).reshape(-1)) for s in segments]
+    if len(pauses) != max(len(segs) - 1, 0):
+        raise ValueError("one pause per seam")
+    out = []
+    with torch.cuda.device(device):
+        sj = joiner if joiner is not None else SeamJoiner(device, 1)
+        try:
+            end = torch.ones(1, dtype=torch.int32, device=device)
+            for k, x in enumerate(segs):
+                final = k == len(segs) - 1
+                sj.start_segments([0], [trail if final else pauses[k]], [segment_flags(k, len(segs))], [lead])
+                out.append(_whole_row(sj, x, lambda xd, n, y, cnt: sj.chunk(xd, n, y, cnt, seg_end=end, last=end if final else None)))
+        finally:
+            if joiner is None:
+                sj.close()
+    return np.concatenate(out) if out else np.zeros(0, np.float32)
+
+
+# ------------------------------------------------------------------------------- loudness
+class LoudnessNormalizer(_Stage):
+    """Per-slot loudness normalisation of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Loudness"; the numpy
+    model is ``loudness.StreamState``): one launch per call for every slot, each towards its own target.  A slot emits exactly
+    the samples it reads.  Slots start off; ``reset_slots`` starts a new stream in a slot (target None: off)."""
+
+    C_NAME = "loudness"
+
+    def _create_args(self) -> tuple:
+        from .loudness import tables
+
+        self._tables = tables().packed()  # (read by the create call only)
+        assert self._tables.size == self.lib.smoltts_loudness_table_doubles()
+        return self._tables.ctypes.data, int(self._tables.size)
+
+    def reset_slots(self, slots: Sequence[int], targets: Sequence[Optional[float]],
+                    start_gain_db: Optional[Sequence[Optional[float]]] = None) -> None:
+        """Start new streams in ``slots`` towards their ``targets`` (LUFS; None: the slot is off) from their first knots
+        (``start_gain_db``, default 0 dB)."""
+        from .loudness import knot_of_db, target_power
+
+        n = len(slots)
+        if not n:
+            return
+        power = (C.c_double * n)(*[0.0 if t is None else target_power(t) for t in targets])
+        knots = self._ints([knot_of_db(g or 0.0) for g in (start_gain_db or [0.0] * n)])
+        self._call("reset_slots", self._ints(slots), power, knots, n)
+
+    def out_samples(self, n_in: int) -> int:
+        """A slot emits what it reads (one sample of room for an empty call)."""
+        return max(int(n_in), 1)
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
+        """Normalise ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current
+        stream.  ``valid``: device int32 [batch], the real samples of each row.  ``counts[b]``: the samples slot b wrote to
+        ``out[b]`` (its valid ones; 0 for a slot that is off)."""
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.float32, n_in, counts, 1, valid)
+        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1], dptr(counts))
+
+    def measure(self, row: torch.Tensor, n: int) -> Tuple[float, float]:
+        """(gated mean power, peak) of the whole utterance ``row[:n]`` (device fp32, contiguous); waits for the result."""
+        hops = torch.empty(n // 2400 + 1, dtype=torch.float64, device=self.device)
+        res = torch.empty(4, dtype=torch.float64, device=self.device)
+        self._call("measure", dptr(row), int(n), dptr(hops), hops.numel(), dptr(res))
+        p, peak = res.cpu().numpy()[:2]
+        return float(p), float(peak)
+
+    def scale(self, row: torch.Tensor, n: int, gain: float, out: torch.Tensor) -> None:
+        """``out[:n] = float32(row[:n] * gain)`` on the current stream."""
+        check(self.lib.smoltts_loudness_scale(dptr(row), int(n), float(gain), dptr(out), current_stream_ptr()), "smoltts_loudness_scale")
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s state (synchronises the current stream), in the layout of ``loudness.StreamState.state``, with
+        ``on`` and ``ptarget``."""
+        ints, v = (C.c_int64 * 4)(), np.zeros(19 + 512, np.float64)
+        self._call("slot_state", int(slot), ints, v.ctypes.data)
+        return {"pos": int(ints[0]), "ka": int(ints[1]), "kb": int(ints[2]), "on": int(ints[3]), "peak": np.float32(v[17]),
+                "ptarget": float(v[18]), "filter": v[:17].copy(), "ring": v[19:].copy()}
+
+
+def _loudness_whole(pcm: np.ndarray, device: torch.device, target: Optional[float]):
+    """(power, peak, gain, output or None) of a whole utterance on ``device``: measured in one launch, and with a ``target``
+    scaled by the blocking rule's gain in a second one."""
+    from .loudness import static_gain
+
+    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    with torch.cuda.device(device):
+        ln = LoudnessNormalizer(device, 1)
+        try:
+            seen = {}
+
+            def launch(row, n, out, counts):
+                seen["p"], seen["peak"] = ln.measure(row, n) if n else (0.0, 0.0)
+                seen["g"] = 1.0 if target is None else static_gain(target, seen["p"], seen["peak"])
+                ln.scale(row, n, seen["g"], out)
+                counts.fill_(n)
+
+            y = _whole_row(ln, x, launch)
+        finally:
+            ln.close()
+    return seen["p"], seen["peak"], seen["g"], (x if seen["g"] == 1.0 else y)
+
+
+def measure_loudness(pcm: np.ndarray, device: torch.device) -> Tuple[float, float]:
+    """(integrated loudness in LUFS by BS.1770-4, -inf when no block passes the absolute gate or the utterance is shorter than
+    400 ms; peak) of a whole utterance (float32 at 24 kHz), measured on ``device``: ``loudness.measure``.  Waits."""
+    from .loudness import lufs_of_power
+
+    p, peak, _, _ = _loudness_whole(pcm, device, None)
+    return lufs_of_power(p), peak
+
+
+def loudness_normalize(pcm: np.ndarray, target: float, device: torch.device, with_gain: bool = False):
+    """A whole utterance (float32 at 24 kHz) brought to ``target`` LUFS on ``device`` by one gain, capped so that its peak
+    stays at -1 dBFS: ``loudness.normalize`` (``SmolTTS.__call__``).  An utterance that measures nothing comes back
+    unchanged.  ``with_gain``: -> (samples, the gain applied).  Waits for the result."""
+    from .loudness import check_target
+
+    _, _, g, y = _loudness_whole(pcm, device, check_target(target))
+    return (y, g) if with_gain else y
+
+
+# ------------------------------------------------------------------------------- FLAC framing
+class FlacEncoder(_Stage):
+    """Per-slot FLAC framing of streamed samples on the GPU (include/smoltts_hip.h, "FLAC"; the numpy model is
+    ``flac.StreamEncoder``): one launch per call for every slot, each reading fp32 PCM or the resampler's int16 at its own rate.
+    Slots start off; ``reset_slots`` starts a new stream in a slot.  The stream header (``flac.stream_header``) is the caller's."""
+
+    C_NAME = "flac"
+
+    def reset_slots(self, slots: Sequence[int], rates: Sequence[int], sources: Sequence[int]) -> None:
+        """Start new streams in ``slots`` at their rate and source (``FLAC_F32`` / ``FLAC_S16``; ``FLAC_OFF``: off)."""
+        self._call("reset_slots", self._ints(slots), self._ints(rates), self._ints(sources), len(slots))
+
+    def new_outputs(self, batch: int, n_max: int):
+        """Device buffers of one call in which a slot reads at most ``n_max`` samples: (bytes uint8 [batch, out_bytes],
+        sizes int32 [batch, max_blocks, 2])."""
+        blocks = int(self.lib.smoltts_flac_max_blocks(int(n_max)))
+        return (torch.empty(batch, int(self.lib.smoltts_flac_out_bytes(int(n_max))), dtype=torch.uint8, device=self.device),
+                torch.empty(batch, blocks, 2, dtype=torch.int32, device=self.device))
+
+    def chunk(self, batch: int, out: torch.Tensor, sizes: torch.Tensor, pcm: Optional[torch.Tensor] = None, n_in: int = 0,
+              valid: Optional[torch.Tensor] = None, s16: Optional[torch.Tensor] = None, s16_counts: Optional[torch.Tensor] = None,
+              last: Optional[torch.Tensor] = None) -> None:
+        """Frame the samples of slots [0, batch) on the current stream: F32 slots read ``n_in`` samples of ``pcm`` (device fp32
+        [batch, >= n_in]; ``valid``: device int32 [batch], the real ones), S16 slots the resampler's ``s16`` bytes (uint8
+        [batch, row]) and ``s16_counts`` (int32 [batch, 2]: finals, tail); ``last`` (device int32 [batch]) nonzero where the
+        stream ends with this call.  ``sizes[b, j]``: {offset, bytes} of slot b's frame j in ``out[b]``."""
+        self._check(batch, pcm, n_in, out, torch.uint8, 0, sizes, 0, valid, last)
+        if s16 is not None:
+            assert s16.dtype == torch.uint8 and s16.is_contiguous() and s16_counts is not None and s16_counts.is_contiguous()
+        self._call("chunk", dptr(pcm), pcm.stride(0) if pcm is not None else 0, int(n_in), dptr(valid), dptr(s16),
+                   s16.shape[1] if s16 is not None else 0, dptr(s16_counts), batch, dptr(last), dptr(out), out.shape[1], dptr(sizes),
+                   sizes.shape[1])
+
+    @staticmethod
+    def slot_frames(host_out: np.ndarray, host_sizes: np.ndarray, b: int) -> List[bytes]:
+        """Slot ``b``'s frames of a call, in order, from the host copies of ``out`` and ``sizes``."""
+        frames = []
+        for off, n in host_sizes[b]:
+            if n <= 0:
+                break
+            frames.append(host_out[b, int(off):int(off) + int(n)].tobytes())
+        return frames
+
+
+def flac_encode(samples: np.ndarray, sample_rate: int, device: torch.device) -> bytes:
+    """A whole utterance as one FLAC file, framed on ``device`` in one call with ``last`` set: float32 samples are quantised as
+    rint(clip(x, -1, 1) * 32767), int16 ones taken as they are.  The STREAMINFO carries the true total, the smallest and largest
+    frame and the MD5 of the samples (``SmolTTS.__call__``).  Waits for the result."""
+    from . import flac
+
+    x = np.asarray(samples).reshape(-1)
+    is_f32 = x.dtype != np.int16
+    x = np.ascontiguousarray(x, dtype=np.float32 if is_f32 else np.int16)
+    s16 = flac.quantize(x) if is_f32 else x
+    with torch.cuda.device(device):
+        fe = FlacEncoder(device, 1)
+        try:
+            fe.reset_slots([0], [sample_rate], [FLAC_F32 if is_f32 else FLAC_S16])
+            last = torch.ones(1, dtype=torch.int32, device=device)
+            if is_f32:
+                frames = _whole_row(fe, x, lambda row, n, out, sizes: fe.chunk(1, out, sizes, pcm=row, n_in=n, last=last))
+            else:  # (the int16 row read as the resampler's bytes, all of it final)
+                frames = _whole_row(fe, x, lambda row, n, out, sizes: fe.chunk(
+                    1, out, sizes, s16=row.view(torch.uint8), s16_counts=torch.tensor([[n, 0]], dtype=torch.int32, device=device), last=last))
+        finally:
+            fe.close()
+    return flac.file_from_frames(frames, s16, sample_rate)

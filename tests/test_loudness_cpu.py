@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 from scipy.signal import lfilter
 
-from smoltts_amd import engine, loudness as L
+from smoltts_amd import engine, loudness as L, route
 from smoltts_amd.formats import parse_stream_format
 from smoltts_amd.request import parse_request
 
@@ -230,7 +230,7 @@ def test_converter_makes_no_loudness_stage_until_a_slot_asks(monkeypatch):
         def close(self):
             pass
 
-    monkeypatch.setattr(engine, "LoudnessNormalizer", Stage)
+    monkeypatch.setattr(route, "LoudnessNormalizer", Stage)
     conv = engine.StreamConverter(torch_device(), 4, 1920)
     conv.reset_slots([0, 1], [None, None], [None, None])
     assert made == [] and not conv.converts(0)

@@ -6,12 +6,12 @@ import pytest
 import torch
 
 from smoltts_amd import engine
+from smoltts_amd.abi import E_CAPACITY, E_INVALID
 from smoltts_amd.engine import dptr
 from smoltts_amd.formats import ENC_S16
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_CAPACITY = -1, -4  # include/smoltts_hip.h
 B = 4
 
 

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from smoltts_amd import engine
+from smoltts_amd import engine, route
 from smoltts_amd.formats import ENC_OFF, parse_stream_format
 
 FORMATS = ("pcm_24000", "pcm_16000", "ulaw_8000")
@@ -122,11 +122,11 @@ def _stand_ins(monkeypatch, log):
         Stage.slot_frames = staticmethod(slot_frames)
         return Stage
 
-    monkeypatch.setattr(engine, "SeamJoiner", stage("seam", 16, 7))
-    monkeypatch.setattr(engine, "TimeStretcher", stage("stretch", 32, 5))
-    monkeypatch.setattr(engine, "Resampler", stage("resample"))
-    monkeypatch.setattr(engine, "FlacEncoder", stage("flac"))
-    monkeypatch.setattr(engine, "upload", lambda arrays, device: [torch.from_numpy(np.ascontiguousarray(a)) for a in arrays])
+    monkeypatch.setattr(route, "SeamJoiner", stage("seam", 16, 7))
+    monkeypatch.setattr(route, "TimeStretcher", stage("stretch", 32, 5))
+    monkeypatch.setattr(route, "Resampler", stage("resample"))
+    monkeypatch.setattr(route, "FlacEncoder", stage("flac"))
+    monkeypatch.setattr(route, "upload", lambda arrays, device: [torch.from_numpy(np.ascontiguousarray(a)) for a in arrays])
 
 
 def test_run_executes_the_plan_and_the_pass_keeps_its_routes(monkeypatch):
