@@ -694,6 +694,42 @@ int smoltts_loudness_scale(const float* pcm_dev, int64_t n, double gain, float* 
  * power, the ring of 512 block powers.  Synchronises the stream. */
 int smoltts_loudness_slot_state(SmolttsLoudness* s, int32_t slot, int64_t* ints_host, double* values_host, void* stream);
 
+/* ------------------------------------------------------------------------------ Watermark
+ * A keyed spread-spectrum mark added to the codec's 24 kHz fp32 PCM (smoltts_amd/csrc/watermark.hip; the
+ * numpy model, reproduced bit for bit, and the detector are smoltts_amd/watermark.py).  Chips of +-1 on a period of 15360
+ * samples, scaled per 480-sample block by gain * sqrt(mean square of the block in front), shaped by a 65-tap band-pass
+ * (500-3400 Hz) and added in fp64.  A block's gain comes from the block in front of it, so a slot emits exactly the samples it
+ * reads.  The output does not depend on how a stream is cut into calls.  One key per stage. */
+typedef struct SmolttsWatermark SmolttsWatermark;
+
+/* Device slab of a watermark stage for max_batch slots (256-byte aligned, caller-owned): two copies of each slot's state and the
+ * stage's tables.  tables_host: smoltts_watermark_table_doubles() doubles (watermark.Watermark.packed: the 65 taps, then the
+ * key's 15360 chips as +1.0 / -1.0); the device hashes nothing.  Every slot starts off; create clears the slab and uploads the
+ * tables synchronously. */
+size_t smoltts_watermark_bytes(int32_t max_batch);
+int32_t smoltts_watermark_table_doubles(void);
+int smoltts_watermark_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, const double* tables_host, int32_t n_tables,
+                             SmolttsWatermark** out);
+void smoltts_watermark_destroy(SmolttsWatermark* s);
+
+/* Start a new stream in each listed slot (host arrays) at its gain 10^(strength_db / 20) (0 switches the slot off; at most 1).
+ * The other slots continue.  Stream-ordered. */
+int smoltts_watermark_reset_slots(SmolttsWatermark* s, const int32_t* slots_host, const double* gain_host, int32_t n_slots,
+                                  void* stream);
+
+/* One launch for slots [0, batch): slot b consumes valid_in_dev[b] (clamped to [0, n_in]; NULL = n_in) samples of pcm_dev float
+ * [batch][pcm_stride] and writes as many to out_dev float [batch][out_stride] (out_stride >= n_in), their number to
+ * counts_dev[b]; slots that are off write 0 and leave their rows alone.  Calls on one stage must be ordered on one stream. */
+int smoltts_watermark_chunk(SmolttsWatermark* s, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
+                            const int32_t* valid_in_dev, float* out_dev, int64_t out_stride, int32_t* counts_dev, void* stream);
+
+/* A whole utterance of n samples marked from position 0 at `gain` in one launch (no slot involved): the samples a stream gives. */
+int smoltts_watermark_embed(SmolttsWatermark* s, const float* pcm_dev, int32_t n, double gain, float* out_dev, void* stream);
+
+/* Tests and tools: slot's state; ints_host[2] = pos, on; values_host[5] = the open sub-block's sum, the open block's folded
+ * sub-blocks, the open and the previous block's gain, the slot's gain.  Synchronises the stream. */
+int smoltts_watermark_slot_state(SmolttsWatermark* s, int32_t slot, int64_t* ints_host, double* values_host, void* stream);
+
 /* --------------------------------------------------------------- operator-level test entry points */
 enum {  /* prologue applied to the activation operand */
   SMOLTTS_PRO_NONE = 0,

@@ -19,14 +19,21 @@ class NoEncoderError(ValueError):
 class SmolTTS:
     def __init__(self, model_id: Optional[str] = None, checkpoint_dir: Optional[str] = None,
                  mimi_checkpoint: Optional[str] = None, numerics=None, state=None, config=None, mimi_state=None,
-                 codec_window: int = 0, weight_format: str = "bf16", verbose: bool = False):
+                 codec_window: int = 0, weight_format: str = "bf16", verbose: bool = False, watermark=None):
         """``checkpoint_dir``: config.json + tokenizer.json + model.safetensors | model.pth (reference
         layouts).  ``mimi_checkpoint``: the Hugging Face kyutai/mimi ``model.safetensors`` (or its
         directory).  ``state``/``config``/``mimi_state`` allow in-memory (e.g. synthetic) weights.
         ``model_id`` (Hugging Face download in the reference) needs network access and is refused.
         ``weight_format="fp8"`` stores the Linears as e4m3 with per-row scales (``packing.fp8_reference_state`` is the model
-        then computed)."""
+        then computed).  ``watermark`` (a ``watermark.Watermark``; None: none): everything ``__call__`` and ``stream`` return
+        carries the key's mark, added on the GPU last of the float stages (watermark.py)."""
         import torch  # noqa: F401
+
+        from .watermark import Watermark
+
+        if watermark is not None and not isinstance(watermark, Watermark):
+            raise ValueError("watermark must be a smoltts_amd.watermark.Watermark or None")
+        self.watermark = watermark
 
         from .checkpoint import load_checkpoint, load_mimi_state
         from .config import NumericsMode, TokenConfig
@@ -159,7 +166,7 @@ class SmolTTS:
         return pcm
 
     def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None,
-                 speed: Optional[float] = None, segment=False, loudness: Optional[float] = None):
+                 speed: Optional[float] = None, segment=False, loudness: Optional[float] = None, watermark: Optional[bool] = None):
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
         (per-request temperature / min_p / seed, as in ``generate_codes``).  ``speed`` (0.25 to 4.0; None / 1.0: unchanged):
         the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
@@ -168,10 +175,13 @@ class SmolTTS:
         one segment without break tags takes the plain path.  ``last_segments`` then lists each segment's text, seed and codes.
         ``loudness`` (a target in LUFS, -40 to -5; None: the level is left alone): the utterance's BS.1770-4 integrated loudness
         is measured on the GPU and one gain brings it to the target, capped where its peak would pass -1 dBFS (``loudness.py``),
-        behind the seam join and in front of the stretch; ``last_loudness_gain_db`` is the gain applied."""
+        behind the seam join and in front of the stretch; ``last_loudness_gain_db`` is the gain applied.
+        ``watermark`` (None: marked when the instance has a ``watermark``; True without one: ``ValueError``): the utterance gets
+        the instance's mark whole on the GPU, last: behind the seam join, the loudness gain and the stretch (``watermark.py``)."""
         from .request import parse_request
 
-        req = parse_request(input, speed=speed, segment=segment, loudness=loudness)  # a bad request is refused before any work
+        req = parse_request(input, speed=speed, segment=segment, loudness=loudness, watermark=watermark)  # a bad request is refused before any work
+        marked = self._marks(req.watermark)
         voice = voice if voice is not None else "heart"
         if req.plan is not None:
             pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling)
@@ -185,11 +195,21 @@ class SmolTTS:
 
             pcm, g = loudness_normalize(pcm, req.loudness, self.lm.device, with_gain=True)
             self.last_loudness_gain_db = gain_db(g)
-        if req.speed_q is None:
-            return pcm
-        from .stages import stretch_pcm
+        if req.speed_q is not None:
+            from .stages import stretch_pcm
 
-        return stretch_pcm(pcm, req.speed_q, self.lm.device)
+            pcm = stretch_pcm(pcm, req.speed_q, self.lm.device)
+        if marked:
+            from .stages import watermark_embed
+
+            pcm = watermark_embed(pcm, marked, self.lm.device)
+        return pcm
+
+    def _marks(self, asked: Optional[bool]):
+        """The ``watermark.Watermark`` of a request that asked ``asked`` (None: the instance's policy), or None: unmarked."""
+        if asked and self.watermark is None:
+            raise ValueError("watermark asked for, and the model has no watermark key")
+        return self.watermark if asked is None or asked else None
 
     # -- voice-clone prompts (``create_speaker``, __init__.py:97-118)
     def encode_audio(self, audio) -> "np.ndarray":
@@ -225,7 +245,8 @@ class SmolTTS:
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
                reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None,
                speed: Optional[float] = None, container: Optional[str] = None, segment=False,
-               loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None) -> Iterator["np.ndarray"]:
+               loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
+               watermark: Optional[bool] = None) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -248,6 +269,8 @@ class SmolTTS:
         ``loudness`` (as in ``__call__``): the stream is levelled causally on the GPU behind the seam and in front of the
         stretch, by a gain that moves towards the target at 5 dB/s at most, from ``loudness_start_gain_db`` (default 0); every
         frame's samples still leave with the frame (``loudness.StreamState``).
+        ``watermark`` (as in ``__call__``): the stream is marked on the GPU last of the float stages, behind the stretch and in
+        front of the conversion and the framing; a segmented stream keeps one mark grid across its seams.
         ``input`` may be an iterator or generator of strings (or UTF-8 ``bytes``, cut anywhere) in place of a string: text that is
         still being written.  It implies ``segment=True`` (or the options given), is cut by ``longform.IncrementalSplitter``
         and spoken segment after segment while the text is pulled: before segment k starts, just enough text is pulled to have
@@ -262,13 +285,14 @@ class SmolTTS:
         if not isinstance(input, (str, bytes)):
             yield from self._stream_incremental(iter(input), voice if voice is not None else "0", generation_settings, overlap,
                                                 reference_upsample, output_format, sampling, speed, container, segment, loudness,
-                                                loudness_start_gain_db)
+                                                loudness_start_gain_db, watermark)
             return
         req = parse_request(input, stream=True, output_format=output_format, speed=speed, container=container, segment=segment,
-                            loudness=loudness, loudness_start_gain_db=loudness_start_gain_db)
+                            loudness=loudness, loudness_start_gain_db=loudness_start_gain_db, watermark=watermark)
+        marked = self._marks(req.watermark)
         voice = voice if voice is not None else "0"
         if req.plan is not None:
-            yield from self._stream_segmented(req, voice, generation_settings, overlap, reference_upsample, sampling)
+            yield from self._stream_segmented(req, voice, generation_settings, overlap, reference_upsample, sampling, marked=marked)
             return
         prompt = np.asarray(self._get_prompt(input, voice))
         if prompt.ndim == 3:
@@ -280,7 +304,7 @@ class SmolTTS:
         try:
             yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=req.output_format,
                                   speed_q=req.speed_q, container=req.container, loudness=req.loudness,
-                                  start_gain_db=req.start_gain_db)
+                                  start_gain_db=req.start_gain_db, watermark=marked)
         finally:
             msess.close()
             sess.close()
@@ -342,13 +366,14 @@ class SmolTTS:
         return seam_join(pcms, plan.pauses, self.lm.device, lead=plan.lead, trail=plan.trail, joiner=self._seam)
 
     def _stream_incremental(self, texts, voice, generation_settings, overlap, reference_upsample, output_format, sampling, speed,
-                            container, segment, loudness, loudness_start_gain_db):
+                            container, segment, loudness, loudness_start_gain_db, watermark=None):
         """``stream`` of a text that ``texts`` yields in pieces: the segmented stream of a plan that grows as the text is pulled."""
         from .longform import FLUSH, GrowingPlan, IncrementalSplitter, segment_options
         from .request import parse_request
 
         req = parse_request("", stream=True, output_format=output_format, speed=speed, container=container, loudness=loudness,
-                            loudness_start_gain_db=loudness_start_gain_db)
+                            loudness_start_gain_db=loudness_start_gain_db, watermark=watermark)
+        marked = self._marks(req.watermark)
         opts = segment_options(segment or True)
         plan, splitter = GrowingPlan(opts), IncrementalSplitter(opts)
 
@@ -366,10 +391,11 @@ class SmolTTS:
 
         if not pull(0):
             raise ValueError("the text has nothing to speak")
-        yield from self._stream_segmented(req, voice, generation_settings, overlap, reference_upsample, sampling, plan, pull)
+        yield from self._stream_segmented(req, voice, generation_settings, overlap, reference_upsample, sampling, plan, pull, marked)
 
-    def _stream_segmented(self, req, voice, generation_settings, overlap, reference_upsample, sampling, plan=None, pull=None):
-        """``plan`` / ``pull``: a ``longform.GrowingPlan`` in place of the request's, and what completes its segment k."""
+    def _stream_segmented(self, req, voice, generation_settings, overlap, reference_upsample, sampling, plan=None, pull=None, marked=None):
+        """``plan`` / ``pull``: a ``longform.GrowingPlan`` in place of the request's, and what completes its segment k;
+        ``marked``: the stream's ``watermark.Watermark`` or None."""
         import numpy as np
         import torch
 
@@ -379,10 +405,11 @@ class SmolTTS:
 
         plan = plan if plan is not None else req.plan
         dev = self.lm.device
-        conv = StreamConverter(dev, 1, 1920, seam=True)
+        conv = StreamConverter(dev, 1, 1920, seam=True, watermark=marked)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
-            conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container], [req.loudness], [req.start_gain_db])
+            conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container], [req.loudness], [req.start_gain_db],
+                             [marked is not None])
             segments = self._segments(plan, voice, None, generation_settings, sampling)
             for k in range(1 << 30):
                 if pull(k) if pull is not None else k < len(plan.segs):

@@ -232,6 +232,14 @@ SIGNATURES = {
     "smoltts_loudness_measure": (INT, "p p i p q p p"),
     "smoltts_loudness_scale": (INT, "p q d p p"),
     "smoltts_loudness_slot_state": (INT, "p i p p p"),
+    "smoltts_watermark_bytes": (SIZE, "i"),
+    "smoltts_watermark_table_doubles": (I32, ""),
+    "smoltts_watermark_create": (INT, "p z i p i p*"),
+    "smoltts_watermark_destroy": (None, "p"),
+    "smoltts_watermark_reset_slots": (INT, "p p p i p"),
+    "smoltts_watermark_chunk": (INT, "p p q i i p p q p p"),
+    "smoltts_watermark_embed": (INT, "p p i d p p"),
+    "smoltts_watermark_slot_state": (INT, "p i p p p"),
     "smoltts_k_gemm": (INT, "GemmArgs* p"),
     "smoltts_gemm3_attn_fusable": (INT, "i i i"),
     "smoltts_k_gemm3": (INT, "Gemm3Args* p"),

@@ -21,13 +21,15 @@ class SpeechOptions:
     plan: Optional[SegmentPlan]      # None: the plain path (no segment options, or a text that is one plain segment)
     loudness: Optional[float] = None  # target in LUFS (loudness.py), None: the level is left as it is
     start_gain_db: float = 0.0        # a stream's first gain knot
+    watermark: Optional[bool] = None  # mark the audio with the front end's key (watermark.py); None: the front end's policy
 
 
 def parse_request(text: str = "", stream: bool = False, output_format: Optional[str] = None, speed: Optional[float] = None,
                   container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
-                  loudness_start_gain_db: Optional[float] = None) -> SpeechOptions:
+                  loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None) -> SpeechOptions:
     """A request's options checked and normalised; ``ValueError`` for anything a front end refuses.  ``output_format`` and
-    ``container`` apply to streaming requests only, as does ``loudness_start_gain_db``, which needs a ``loudness``."""
+    ``container`` apply to streaming requests only, as does ``loudness_start_gain_db``, which needs a ``loudness``.  ``watermark``: true, false, or None for the
+    front end's own policy (the key and the strength are the front end's: one key per stage)."""
     speed_q = parse_speed(speed)
     if output_format is not None:
         if not stream:
@@ -43,5 +45,7 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
     target = check_target(loudness)
     if loudness_start_gain_db is not None and (target is None or not stream):
         raise ValueError("loudness_start_gain_db applies to streaming requests with a loudness")
+    if watermark is not None and not isinstance(watermark, bool):
+        raise ValueError("watermark must be true, false or null")
     return SpeechOptions(output_format, None if speed_q is None else float(speed), speed_q, container, opts, plan, target,
-                         check_start_gain(loudness_start_gain_db))
+                         check_start_gain(loudness_start_gain_db), watermark)

@@ -12,13 +12,14 @@ import torch
 from .abi import FLAC_F32, FLAC_OFF, FLAC_S16, SEAM_OFF
 from .device import upload
 from .formats import ENC_OFF, check_container, parse_stream_format
-from .stages import FlacEncoder, LoudnessNormalizer, Resampler, SeamJoiner, TimeStretcher
+from .stages import FlacEncoder, LoudnessNormalizer, Resampler, SeamJoiner, TimeStretcher, Watermarker
 from .tsm import out_bound
 
 
 STAGES = ("seam", "stretch", "resample", "flac")  # the stages every build has had, in launch order
 LAUNCH_ORDER = ("seam", "loudness", "stretch", "resample", "flac")  # the stages of a pass, in launch order
-FLOAT_STAGES = ("seam", "loudness", "stretch")  # fp32 in, fp32 out: the stages behind read their rows
+PASS_ORDER = ("seam", "loudness", "stretch", "watermark", "resample", "flac")  # LAUNCH_ORDER with the watermark: what a pass runs by
+FLOAT_STAGES = ("seam", "loudness", "stretch", "watermark")  # fp32 in, fp32 out: the stages behind read their rows
 
 
 @dataclass(frozen=True)
@@ -35,18 +36,19 @@ class SlotRoute:
     head_owed: bool = False
     loudness: Optional[float] = None  # target in LUFS (None: the slot never enters the loudness stage)
     start_gain_db: float = 0.0        # its stream's first knot
+    watermark_gain: float = 0.0       # 10^(strength_db / 20) (0: the slot never enters the watermark stage)
 
     @cached_property
     def stages(self) -> Tuple[str, ...]:
         """The stages the slot goes through, in launch order."""
-        on = (self.segmented, self.loudness is not None, self.speed_q != 65536, self.enc != ENC_OFF, self.flac)
-        return tuple(s for s, o in zip(LAUNCH_ORDER, on) if o)
+        on = (self.segmented, self.loudness is not None, self.speed_q != 65536, self.watermark_gain > 0.0, self.enc != ENC_OFF, self.flac)
+        return tuple(s for s, o in zip(PASS_ORDER, on) if o)
 
 
 class PassPlan(NamedTuple):
     stages: List[str]                 # the stages to launch, in order
     rows: Dict[str, List[int]]        # the live slots each of them serves
-    through: Dict[str, List[int]]     # float stage (seam, loudness, stretch) -> the live slots it does not serve that a later stage does
+    through: Dict[str, List[int]]     # float stage (seam, loudness, stretch, watermark) -> the live slots it does not serve that a later stage does
     source: Dict[int, Optional[str]]  # live slot -> the last stage it goes through (None: its codec rows are its output)
     host: List[str]                   # the stages whose outputs are copied to the host: the sources of the live slots
     routes: Dict[int, SlotRoute]      # live slot -> its route when planned
@@ -54,7 +56,7 @@ class PassPlan(NamedTuple):
 
 def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
     """The plan of one converter pass over the live slots' routes (``{slot: SlotRoute}``, in slot order); no device involved."""
-    rows = {s: [] for s in LAUNCH_ORDER}
+    rows = {s: [] for s in PASS_ORDER}
     through = {s: [] for s in FLOAT_STAGES}
     source = {}
     for b, r in routes.items():
@@ -63,23 +65,26 @@ def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
         for s in path:
             rows[s].append(b)
         for s in through:
-            if path and s not in path and LAUNCH_ORDER.index(path[-1]) > LAUNCH_ORDER.index(s):
+            if path and s not in path and PASS_ORDER.index(path[-1]) > PASS_ORDER.index(s):
                 through[s].append(b)
-    stages = [s for s in LAUNCH_ORDER if rows[s]]
+    stages = [s for s in PASS_ORDER if rows[s]]
     return PassPlan(stages, {s: rows[s] for s in stages}, {s: through[s] for s in through if rows[s]}, source,
                     [s for s in stages if s in source.values()], routes)
 
 
 class StreamConverter:
-    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``STAGES``): a
+    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``PASS_ORDER``): a
     segmented slot (``start_segments``) is joined by the seam stage (``SeamJoiner``), a slot with a speed is time-stretched
-    (``TimeStretcher``), a slot with an output format is converted (``Resampler``), and a slot with a FLAC container is framed
+    (``TimeStretcher``), a marked slot gets the watermark of the converter's key last of the float stages (``Watermarker``:
+    behind the stretch, so that a speed does not rescale the chips), a slot with an output format is converted (``Resampler``), and a slot with a FLAC container is framed
     (``FlacEncoder``, from the resampler's int16, or from the float32 at 24 kHz); each stage reads the output of the one in
     front, and the state of the stages behind the seam carries from segment to segment.  Each stage is created the first time
     a slot needs it (``seam``: the seam stage at once).  ``n_in``: codec samples per slot and call."""
 
-    def __init__(self, device: torch.device, max_batch: int, n_in: int, seam: bool = False):
+    def __init__(self, device: torch.device, max_batch: int, n_in: int, seam: bool = False, watermark=None):
         self.device, self.B, self.n_in = device, max_batch, n_in
+        self.watermark = watermark  # a watermark.Watermark: the one key of this converter's marked slots (None: no slot may ask)
+        self.wm: Optional[Watermarker] = None
         self.rs: Optional[Resampler] = None
         self.ts: Optional[TimeStretcher] = None
         self.fl: Optional[FlacEncoder] = None
@@ -90,25 +95,32 @@ class StreamConverter:
 
     def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]],
                     containers: Optional[Sequence[Optional[str]]] = None, loudness: Optional[Sequence[Optional[float]]] = None,
-                    start_gain_db: Optional[Sequence[Optional[float]]] = None) -> None:
+                    start_gain_db: Optional[Sequence[Optional[float]]] = None, watermark: Optional[Sequence[bool]] = None) -> None:
         """Start new streams in ``slots`` on the current stream: ``formats[i]`` an ``output_format`` (None / ``pcm_24000``:
         float32), ``speed_q[i]`` a Q16 speed (None / 65536: none), ``containers[i]`` None or ``"flac"`` (FLAC frames of the
-        slot's 16-bit samples at its rate), ``loudness[i]`` a target in LUFS (None: none) reached from ``start_gain_db[i]``.
-        A slot with none of them is switched off."""
+        slot's 16-bit samples at its rate), ``loudness[i]`` a target in LUFS (None: none) reached from ``start_gain_db[i]``,
+        ``watermark[i]`` true for a slot that gets the converter's watermark.  A slot with none of them is switched off."""
         if not slots:
             return
         formats = [f or "pcm_24000" for f in formats]
         routes = []
         none = [None] * len(slots)
-        for b, f, q, c, lt, sg in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none):
+        if watermark is not None and any(watermark) and self.watermark is None:
+            raise ValueError("a slot asks for a watermark, and the converter has no key")
+        for b, f, q, c, lt, sg, wm in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none,
+                                          watermark or none):
             rate, enc = parse_stream_format(f)
             flac = check_container(c, f) is not None
             routes.append(SlotRoute(rate, enc, q or 65536, flac, segmented=False, gen=self.routes[b].gen + 1, head_owed=flac,
-                                    loudness=lt, start_gain_db=sg or 0.0))
+                                    loudness=lt, start_gain_db=sg or 0.0, watermark_gain=self.watermark.gain if wm else 0.0))
         if self.ln is None and any(r.loudness is not None for r in routes):
             self.ln = LoudnessNormalizer(self.device, self.B)
         if self.ln is not None:
             self.ln.reset_slots(slots, [r.loudness for r in routes], [r.start_gain_db for r in routes])
+        if self.wm is None and any(r.watermark_gain > 0.0 for r in routes):
+            self.wm = Watermarker(self.device, self.B, self.watermark)
+        if self.wm is not None:
+            self.wm.reset_slots(slots, [r.watermark_gain for r in routes])
         if self.rs is None and any(r.enc != ENC_OFF for r in routes):
             self.rs = Resampler(self.device, self.B, out_bound(self.n_in))
         if self.ts is None and any(r.speed_q != 65536 for r in routes):
@@ -190,6 +202,10 @@ class StreamConverter:
             out, counts = outs["stretch"] = self.ts.new_outputs(batch, n_in)
             self.ts.chunk(pcm, n_in, out, counts, valid=valid, last=last)
             valid, pcm, n_in = self._through(plan, "stretch", out, counts, pcm, n_in, valid), out, out.shape[1]
+        if "watermark" in plan.stages:
+            out, counts = outs["watermark"] = self.wm.new_outputs(batch, n_in)
+            self.wm.chunk(pcm, n_in, out, counts, valid=valid)
+            valid, pcm, n_in = self._through(plan, "watermark", out, counts, pcm, n_in, valid), out, out.shape[1]
         if "resample" in plan.stages:
             out, counts = outs["resample"] = self.rs.new_outputs(batch, n_in)
             self.rs.chunk(pcm, n_in, out, counts, valid=valid)
@@ -200,10 +216,10 @@ class StreamConverter:
         return StreamPass(self, {s: outs[s] for s in plan.host}, plan)
 
     def close(self):
-        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln):
+        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln, self.wm):
             if stage is not None:
                 stage.close()
-        self.rs = self.ts = self.fl = self.sj = self.ln = None
+        self.rs = self.ts = self.fl = self.sj = self.ln = self.wm = None
 
 
 class StreamPass:

@@ -38,6 +38,11 @@ class TTSCore:
         self.voices: Dict[str, dict] = {}  # cloned voices registered through this server: id -> {"name", "prompt_positions"}
         self._voice_lock = threading.Lock()
         self.segments = 0  # segments of the segmented requests that completed (long_text="segment")
+        from .settings import watermark_setting
+
+        block = watermark_setting(self._setting("watermark", None))
+        self.watermark = block.to_watermark() if block is not None else None  # the key a recording is tested against
+        self.watermark_apply = block.apply if block is not None else None
         self._segments_lock = threading.Lock()
 
     def _setting(self, name: str, default):
@@ -49,7 +54,16 @@ class TTSCore:
     def long_text(self) -> str:
         return self._setting("long_text", "refuse")
 
-    def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False) -> Tuple[dict, int]:
+    def _marks(self, voice) -> Optional[bool]:
+        """Whether a request that speaks ``voice`` is marked; None without a ``watermark`` setting (nothing is passed on)."""
+        if self.watermark is None:
+            return None
+        if self.watermark_apply == "all":
+            return True
+        with self._voice_lock:
+            return str(voice) in self.voices
+
+    def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False, voice=None) -> Tuple[dict, int]:
         """(kwargs, segments): ``{"speed": speed}`` for a speed other than 1, ``{"segment": options}`` in ``long_text="segment"``
         mode and ``{"loudness": target}`` for a ``LoudnessFields`` body (or the server's ``loudness`` setting) that names one,
         nothing otherwise, so that the model sees the calls it saw before; a bad speed or loudness, a text over
@@ -72,6 +86,8 @@ class TTSCore:
                 kw["loudness_start_gain_db"] = start
         if seg is not None:
             kw["segment"] = seg
+        if self._marks(voice) is not None:
+            kw["watermark"] = self._marks(voice)
         return kw, len(p.plan.segs) if p.plan is not None else 0
 
     def _count_segments(self, n: int) -> None:
@@ -163,10 +179,13 @@ class TTSCore:
     def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000", sampling=None,
                        speed: Optional[float] = None, loudness=None, info: Optional[dict] = None):
         """-> (bytes, media type, the seed the request sampled with or None).  ``speed``: passed on only when it is not 1.
-        ``loudness``: the body's ``LoudnessFields``; ``info["loudness_gain_db"]`` is then the gain the utterance was given."""
+        ``loudness``: the body's ``LoudnessFields``; ``info["loudness_gain_db"]`` is then the gain the utterance was given, and
+        ``info["watermark"]`` true when the audio is marked."""
         used = None
         try:
-            sp, n_seg = self._request_kw(input_text, speed, loudness)
+            sp, n_seg = self._request_kw(input_text, speed, loudness, voice=voice)
+            if info is not None:
+                info["watermark"] = bool(sp.get("watermark"))
             if self.scheduler is not None:
                 req = self.scheduler.submit(input_text, str(voice), stream=False, **({"sampling": sampling} if sampling is not None else {}), **sp)
                 used = getattr(req, "sampling", None)
@@ -185,8 +204,8 @@ class TTSCore:
         return (*self.format_audio_chunk(pcm, response_format), seed_used(used))
 
     def stream_audio(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
-                     speed: Optional[float] = None, container: Optional[str] = None, loudness=None):
-        """-> (chunks as bytes, the seed the request samples with or None).  Chunks: float32 at 24 kHz for ``pcm_24000``;
+                     speed: Optional[float] = None, container: Optional[str] = None, loudness=None, info: Optional[dict] = None):
+        """-> (chunks as bytes, the seed the request samples with or None); ``info["watermark"]``: the stream is marked.  Chunks: float32 at 24 kHz for ``pcm_24000``;
         otherwise the int16 / mu-law samples the model or scheduler converted on the GPU (the format is passed on only when it is
         not ``pcm_24000``).  The request is submitted here, before the first chunk is asked for.  ``speed``: passed on only when
         it is not 1; the chunks are then the stretched stream (float32 for ``pcm_24000``).  ``container`` ``"flac"``: the
@@ -194,7 +213,9 @@ class TTSCore:
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
         if container is not None:
             kw["container"] = container
-        sp, n_seg = self._request_kw(input_text, speed, loudness, stream=True)
+        sp, n_seg = self._request_kw(input_text, speed, loudness, stream=True, voice=voice)
+        if info is not None:
+            info["watermark"] = bool(sp.get("watermark"))
         if self.scheduler is not None:
             req = self.scheduler.submit(input_text, str(voice), stream=True, **kw, **({"sampling": sampling} if sampling is not None else {}), **sp)
             chunks, used = self.scheduler.iter_chunks(req), getattr(req, "sampling", None)
@@ -204,7 +225,7 @@ class TTSCore:
         return self._stream_bytes(chunks, kw, n_seg), seed_used(used)
 
     def open_input_stream(self, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
-                          speed: Optional[float] = None, container: Optional[str] = None, loudness=None):
+                          speed: Optional[float] = None, container: Optional[str] = None, loudness=None, info: Optional[dict] = None):
         """A stream whose text arrives in pieces -> (an ``InputStream``, the seed it samples with or None).  Behind a scheduler
         or pool it is ``submit_incremental``; a bare model streams from an iterator (``SmolTTS.stream(text_iter)``), which pulls
         the text as it speaks.  The segment options are the settings' ``segment_max_bytes`` / ``seam_pause_ms`` whatever
@@ -223,6 +244,10 @@ class TTSCore:
             if start is not None:
                 sp["loudness_start_gain_db"] = start
         sp["segment"] = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
+        if self._marks(voice) is not None:
+            sp["watermark"] = self._marks(voice)
+        if info is not None:
+            info["watermark"] = bool(sp.get("watermark"))
         if self.scheduler is not None:
             req = self.scheduler.submit_incremental(str(voice), **kw, **({"sampling": sampling} if sampling is not None else {}), **sp,
                                                     idle_timeout_s=float(self._setting("idle_timeout_s", 10.0)),
@@ -294,6 +319,10 @@ def _seed_headers(seed: Optional[int]) -> dict:
 def _gain_headers(info: dict) -> dict:
     g = info.get("loudness_gain_db")
     return {} if g is None else {"X-Loudness-Gain-Db": f"{g:.2f}"}
+
+
+def _mark_headers(info: dict) -> dict:
+    return {"X-Watermark": "1"} if info.get("watermark") else {}
 
 
 class SamplingFields(BaseModel):
@@ -400,9 +429,10 @@ def openai_speech(item: SpeechRequest, http_request: Request):
     core = http_request.app.state.tts_core
     if item.response_format != "wav":
         container = "flac" if item.response_format == "flac" else None
+        info: dict = {}
         try:
             chunks, seed = core.stream_audio(item.input, item.voice, "pcm_24000", sampling=item.request_sampling(), speed=item.speed,
-                                             container=container, loudness=item)
+                                             container=container, loudness=item, info=info)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         if container is None:
@@ -410,12 +440,12 @@ def openai_speech(item: SpeechRequest, http_request: Request):
         media_type = "audio/flac" if container else "audio/x-pcm"
         return StreamingResponse(_answer_first(chunks), media_type=media_type, headers={
             "Content-Disposition": f'attachment; filename="speech.{item.response_format}"', "X-Sample-Rate": "24000",
-            **_seed_headers(seed)})
+            **_seed_headers(seed), **_mark_headers(info)})
     info: dict = {}
     audio, media_type, seed = core.generate_audio(item.input, item.voice, item.response_format + "_24000", sampling=item.request_sampling(),
                                                   speed=item.speed, loudness=item, info=info)
     return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed),
-                                                           **_gain_headers(info)})
+                                                           **_gain_headers(info), **_mark_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}")
@@ -428,7 +458,7 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
                                                     loudness=item, info=info)
     return Response(content=content, media_type=media_type, headers={
         "Content-Disposition": f'attachment; filename="elevenlabs_speech.{fmt.split("_")[0]}"',
-        "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed), **_gain_headers(info)})
+        "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed), **_gain_headers(info), **_mark_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}/stream")
@@ -437,13 +467,14 @@ def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
     """pcm_24000: raw float32 (the reference's stream); pcm_<rate>: int16 little-endian; ulaw_8000: G.711 mu-law bytes."""
     core = http_request.app.state.tts_core
     kind, rate = output_format.split("_")
+    info: dict = {}
     try:
         chunks, seed = core.stream_audio(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling(),
-                                         speed=item.speed, loudness=item)
+                                         speed=item.speed, loudness=item, info=info)
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return StreamingResponse(chunks, media_type="audio/wav", headers={
-        "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed)})
+        "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed), **_mark_headers(info)})
 
 
 class StreamInputOptions(SamplingFields, LoudnessFields):
@@ -513,8 +544,10 @@ async def stream_input_tts(voice_id: str, http_request: Request, output_format: 
         raise HTTPException(status_code=422, detail=_finite(json.loads(e.json(include_url=False, include_context=False))))
     except ValueError as e:
         raise HTTPException(status_code=422, detail=f"line 1: {e}")
+    info: dict = {}
     try:
-        stream, seed = core.open_input_stream(voice_id, output_format, sampling=item.request_sampling(), speed=item.speed, loudness=item)
+        stream, seed = core.open_input_stream(voice_id, output_format, sampling=item.request_sampling(), speed=item.speed, loudness=item,
+                                              info=info)
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     loop = asyncio.get_running_loop()
@@ -574,7 +607,7 @@ async def stream_input_tts(voice_id: str, http_request: Request, output_format: 
                 reader.exception()  # (a bad line behind the first chunk has ended the stream: there is nobody left to tell)
 
     return _DuplexResponse(body(), media_type="audio/wav", headers={
-        "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed)})
+        "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed), **_mark_headers(info)})
 
 
 class VoiceSample(BaseModel):
@@ -630,6 +663,32 @@ def delete_voice(voice_id: str, http_request: Request):
     except KeyError:
         raise HTTPException(status_code=404, detail=f"no voice {voice_id!r}")
     return {"status": "ok"}
+
+
+class DetectRequest(BaseModel):
+    audio: str  # base64 RIFF WAV, as a voice sample's (server/voices.py)
+
+
+@eleven_router.post("/watermark/detect")
+def detect_watermark(item: DetectRequest, http_request: Request):
+    """Whether a recording carries this server's watermark (extension; watermark.detect against the configured key, which is
+    never returned): ``{"detected": bool, "score": float}``.  404 without a ``watermark`` setting, 422 for audio that cannot
+    be read."""
+    import base64
+    import binascii
+
+    from ..watermark import detect
+    from .voices import parse_wav
+
+    core = http_request.app.state.tts_core
+    if core.watermark is None:
+        raise HTTPException(status_code=404, detail="no watermark is configured")
+    try:
+        pcm, rate = parse_wav(base64.b64decode(item.audio, validate=True))
+    except (binascii.Error, ValueError, TypeError) as e:
+        raise HTTPException(status_code=422, detail=f"audio: {e}")
+    d = detect(pcm, core.watermark.key, rate)
+    return {"detected": d.detected, "score": round(d.score, 3)}
 
 
 @eleven_router.get("/stats")
@@ -707,8 +766,10 @@ def main():
 
     if args.gpus > 1:
         # this process stays off the GPUs: it parses HTTP and relays audio; every worker owns one GPU and one scheduler
+        st = ServerSettings(**settings)
         sched = GpuPool(functools.partial(scheduler_from_settings, settings), devices=list(range(args.gpus)),
-                        generation_settings=ServerSettings(**settings).generation.to_settings())
+                        generation_settings=st.generation.to_settings(),
+                        watermark=st.watermark.to_watermark() if st.watermark is not None else None)
         model = None
     else:
         sched = scheduler_from_settings(settings)

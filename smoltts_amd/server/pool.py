@@ -32,6 +32,7 @@ class _PoolRequest:
     closed: bool = False
     sampling: object = None  # config.RequestSampling as sent to the worker (seed resolved here), or None
     loudness_gain_db: Optional[float] = None  # a blocking request with a loudness: the gain applied (known at its end)
+    watermark: bool = False  # the audio carries the workers' watermark
 
 
 @dataclass
@@ -170,14 +171,21 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
 
 class GpuPool:
     def __init__(self, factory: Callable[[], object], devices: Sequence[int], start_method: str = "spawn", ready_timeout: float = 600.0,
-                 respawn: bool = True, generation_settings=None):
+                 respawn: bool = True, generation_settings=None, watermark=None):
         """``factory``: picklable, called once in every worker to build its scheduler.  ``devices``: GPU indices, one
         worker each (an index may repeat: two replicas on one GPU).  ``start_method``: "spawn" or "forkserver" — never
         "fork": a forked copy of a process that has used the GPU is not usable.  ``respawn``: a worker that dies is replaced
         (same GPU); its requests in flight are failed, later ones are served again by all workers.
         ``generation_settings``: what the workers' schedulers are configured with; then every request's sampling is resolved
         here (``RequestSampling.resolve``) and sent along, so that a request samples the same on any worker.  Without it only a
-        request that names a ``sampling`` carries one (its seed drawn here when missing)."""
+        request that names a ``sampling`` carries one (its seed drawn here when missing).
+        ``watermark`` (a ``watermark.Watermark``; None: none): the key the factory gives every worker's scheduler; the pool
+        itself marks nothing, it decides here whether a request is marked (``BatchScheduler.submit``'s rule) and says so."""
+        from ..watermark import Watermark
+
+        if watermark is not None and not isinstance(watermark, Watermark):
+            raise ValueError("watermark must be a smoltts_amd.watermark.Watermark or None")
+        self.watermark = watermark
         if start_method not in ("spawn", "forkserver"):
             raise ValueError("start_method must be 'spawn' or 'forkserver'")
         if not devices:
@@ -232,41 +240,51 @@ class GpuPool:
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
                container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
-               loudness_start_gain_db: Optional[float] = None) -> _PoolRequest:
+               loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None) -> _PoolRequest:
         """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
         from ..request import parse_request
 
-        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db)  # refused here, before a worker sees it
+        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark)  # refused here, before a worker sees it
+        marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
         req = self._new_request(sampling)
+        req.watermark = marked
         w = req.worker
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
         extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
                                    ("container", p.container), ("segment", p.segment), ("loudness", p.loudness),
-                                   ("loudness_start_gain_db", loudness_start_gain_db)) if v is not None}
+                                   ("loudness_start_gain_db", loudness_start_gain_db), ("watermark", p.watermark)) if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
     def submit_incremental(self, voice: str = "heart", max_new_tokens: Optional[int] = None, output_format: Optional[str] = None,
                            sampling=None, speed: Optional[float] = None, container: Optional[str] = None, segment=True,
                            loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
-                           idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None) -> _PoolIncrementalRequest:
+                           idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
+                           watermark: Optional[bool] = None) -> _PoolIncrementalRequest:
         """As ``BatchScheduler.submit_incremental``: the request lives in one slot of one worker, and ``feed`` / ``flush`` /
         ``close`` / ``cancel`` of the handle go to that worker over its queue, in the order they were called.  Text the worker
         refuses (a bad break tag) ends the stream with that ``ValueError`` instead of raising from ``feed``."""
         from ..longform import segment_options
         from ..request import parse_request
 
-        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db)
+        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark)
         opts = segment_options(True if segment is None or segment is False else segment)
+        marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
         req = self._new_request(sampling, _PoolIncrementalRequest, pool=self)
+        req.watermark = marked
         extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
                                    ("container", p.container), ("segment", opts), ("loudness", p.loudness),
                                    ("loudness_start_gain_db", loudness_start_gain_db), ("idle_timeout_s", idle_timeout_s),
-                                   ("flush_after_s", flush_after_s)) if v is not None}
+                                   ("flush_after_s", flush_after_s), ("watermark", p.watermark)) if v is not None}
         self._req_qs[req.worker].put(("submit_incremental", req.rid, voice, max_new_tokens, extra))
         return req
+
+    def _marks(self, asked: Optional[bool]) -> bool:
+        if asked and self.watermark is None:
+            raise ValueError("watermark asked for, and the pool has no watermark key")
+        return self.watermark is not None if asked is None else bool(asked)
 
     def _inc(self, req: _PoolIncrementalRequest, what: str, text=None) -> None:
         if req.closed or req.cancelled:
@@ -531,11 +549,12 @@ def scheduler_from_settings(settings):
 
     st = settings if isinstance(settings, ServerSettings) else ServerSettings(**settings)
     model = SmolTTS(checkpoint_dir=str(st.get_checkpoint_dir()), mimi_checkpoint=st.mimi_checkpoint, weight_format=st.weight_format)
-    return BatchScheduler(model, max_batch=st.max_batch, generation_settings=st.generation.to_settings(), codec_products=st.codec_products)
+    return BatchScheduler(model, max_batch=st.max_batch, generation_settings=st.generation.to_settings(), codec_products=st.codec_products,
+                          watermark=st.watermark.to_watermark() if st.watermark is not None else None)
 
 
 def synthetic_scheduler(model: str = "tiny", seed: int = 21, mimi_seed: int = 5, max_batch: int = 4, frames_per_tick: int = 2,
-                        max_new_tokens: int = 64, mimi_encoder: bool = False):
+                        max_new_tokens: int = 64, mimi_encoder: bool = False, watermark=None):
     """Seeded random weights at the named shapes (tests, rehearsals without a checkpoint); greedy.  ``mimi_encoder``: the codec
     also carries (seeded) encoder weights, so that voices can be cloned."""
     from .. import SmolTTS
@@ -550,4 +569,4 @@ def synthetic_scheduler(model: str = "tiny", seed: int = 21, mimi_seed: int = 5,
         mst = {**mst, **synthetic_mimi_encoder_state(seed=mimi_seed)}
     tts = SmolTTS(state=synthetic_lm_state(cfg, seed=seed), config=cfg, mimi_state=mst)
     return BatchScheduler(tts, max_batch=max_batch, frames_per_tick=frames_per_tick,
-                          generation_settings=GenerationSettings.greedy(max_new_tokens=max_new_tokens))
+                          generation_settings=GenerationSettings.greedy(max_new_tokens=max_new_tokens), watermark=watermark)

@@ -62,6 +62,7 @@ class _Request:
     start_gain_db: float = 0.0        # streaming: the loudness stage's first knot
     loudness_gain_db: Optional[float] = None  # blocking: the gain that was applied (set before the audio goes out)
     inc: Optional["_Incremental"] = None  # a stream whose text is fed in pieces (submit_incremental)
+    watermark: bool = False   # the audio gets the scheduler's watermark: a stream in its codec pass, a blocking utterance whole, last
 
 
 @dataclass
@@ -183,7 +184,9 @@ class BatchScheduler:
 
     def __init__(self, tts, max_batch: int = 32, frames_per_tick: int = 4, generation_settings=None, max_prompt_rows: int = 4096,
                  prefill_chunk: Optional[int] = 128, side_prefill: bool = True, side_prefill_min_active: Optional[int] = None,
-                 codec_products: int = 6):
+                 codec_products: int = 6, watermark=None):
+        """``watermark`` (a ``watermark.Watermark``; None: no request can be marked): the one key of this scheduler's marked
+        requests; a request that does not say (``submit(watermark=None)``) is marked when there is one."""
         import torch
 
         from ..config import GenerationSettings
@@ -191,6 +194,11 @@ class BatchScheduler:
         from ..route import StreamConverter
         from ..generate import _apply_sampling
 
+        from ..watermark import Watermark
+
+        if watermark is not None and not isinstance(watermark, Watermark):
+            raise ValueError("watermark must be a smoltts_amd.watermark.Watermark or None")
+        self.watermark = watermark
         self.tts = tts
         self.B = max_batch
         self.codec_products = codec_products  # SMOLTTS_MIMI_OPT_PRODUCTS of the codec sessions (6: fp32-grade)
@@ -232,7 +240,7 @@ class BatchScheduler:
         self._codec_wait = 0                    # ticks since the last pass while work was waiting
         self._stream_codec = None               # codec session whose slot b carries the stream of LM slot b (streaming requests)
         # behind it, slot b stretches and converts LM slot b's stream when it has a speed / a format
-        self._stream_conv = StreamConverter(self.session.engine.device, max_batch, max(frames_per_tick, 1) * 1920)
+        self._stream_conv = StreamConverter(self.session.engine.device, max_batch, max(frames_per_tick, 1) * 1920, watermark=watermark)
         self._block_ts = None                   # stretcher of the blocking requests' whole utterances
         self._stretches: List[_StretchJob] = []  # blocking utterances with a speed, complete, being stretched (_poll_stretches)
         self._stretch_flight = None             # the stretch call in flight: (event, host output, host counts, keep-alive, [jobs])
@@ -263,7 +271,7 @@ class BatchScheduler:
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
                container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
-               loudness_start_gain_db: Optional[float] = None) -> _Request:
+               loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None) -> _Request:
         """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
         in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
@@ -281,11 +289,14 @@ class BatchScheduler:
         ``loudness`` (a target in LUFS, -40 to -5, ``ValueError`` otherwise; None: the level is left alone): BS.1770-4 loudness
         normalisation on the GPU (loudness.py).  A stream is levelled causally in its codec pass, behind the seam and in front of
         the stretch, from ``loudness_start_gain_db`` (streaming only; default 0); a blocking utterance is measured whole and
-        given one gain (``request.loudness_gain_db``), behind the seam join and in front of the stretch."""
+        given one gain (``request.loudness_gain_db``), behind the seam join and in front of the stretch.
+        ``watermark`` (None: marked when the scheduler has a key; True without a key: ``ValueError``): the audio carries the
+        scheduler's watermark (watermark.py), added on the GPU last of the float stages: a stream in its codec pass behind the
+        stretch, a blocking utterance whole behind everything else.  ``request.watermark`` says whether it was."""
         from ..config import RequestSampling
         from ..request import parse_request
 
-        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db)
+        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         if self._dead is not None:  # the worker is gone (engine failure or close): nobody would ever answer
             raise RuntimeError(f"scheduler is not running: {self._dead}")
@@ -294,17 +305,24 @@ class BatchScheduler:
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
                        output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=p.speed_q,
                        container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None,
-                       loudness=p.loudness, start_gain_db=p.start_gain_db)
+                       loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark))
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
             self._end(req, RuntimeError(f"scheduler is not running: {self._dead}"))
         return req
 
+    def _marks(self, asked: Optional[bool]) -> bool:
+        """Whether a request that asked ``asked`` is marked: the scheduler's policy when it did not say."""
+        if asked and self.watermark is None:
+            raise ValueError("watermark asked for, and the scheduler has no watermark key")
+        return self.watermark is not None if asked is None else bool(asked)
+
     def submit_incremental(self, voice: str = "heart", max_new_tokens: Optional[int] = None, output_format: Optional[str] = None,
                            sampling=None, speed: Optional[float] = None, container: Optional[str] = None, segment=True,
                            loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
-                           idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None) -> IncrementalRequest:
+                           idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
+                           watermark: Optional[bool] = None) -> IncrementalRequest:
         """A stream whose text is not known yet: ``request.feed(text)`` as it arrives, ``request.close()`` at its end, the
         chunks by iterating the request (or ``iter_chunks``).  The options are those of ``submit(stream=True, segment=...)``
         (``segment``: True, a dict or a ``SegmentOptions``; it cannot be off).
@@ -333,7 +351,7 @@ class BatchScheduler:
         from ..longform import GrowingPlan, IncrementalSplitter, segment_options
         from ..request import parse_request
 
-        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db)
+        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark)
         opts = segment_options(True if segment is None or segment is False else segment)
         if not float(idle_timeout_s) > 0.0 or (flush_after_s is not None and not float(flush_after_s) > 0.0):
             raise ValueError("idle_timeout_s and flush_after_s must be positive")
@@ -343,7 +361,7 @@ class BatchScheduler:
         req = IncrementalRequest("", voice, True, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
                                  output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice),
                                  speed_q=p.speed_q, container=p.container, seg=_Segmented(GrowingPlan(opts), resolved),
-                                 loudness=p.loudness, start_gain_db=p.start_gain_db, sched=self,
+                                 loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark), sched=self,
                                  inc=_Incremental(IncrementalSplitter(opts), float(idle_timeout_s),
                                                   None if flush_after_s is None else float(flush_after_s),
                                                   last_input=time.monotonic()))
@@ -867,7 +885,8 @@ class BatchScheduler:
                 fresh = [r for r in new if r.seg is None or r.seg.k == 0]
                 self._stream_conv.reset_slots([r.slot for r in fresh], [r.output_format for r in fresh],
                                               [r.speed_q for r in fresh], [r.container for r in fresh],
-                                              [r.loudness for r in fresh], [r.start_gain_db for r in fresh])
+                                              [r.loudness for r in fresh], [r.start_gain_db for r in fresh],
+                                              [r.watermark for r in fresh] if self.watermark is not None else None)
                 segd = [r for r in new if r.seg is not None]
                 if segd:
                     pauses, flags, leads = zip(*(r.seg.plan.seam_args(r.seg.k) for r in segd))
@@ -1103,8 +1122,9 @@ class BatchScheduler:
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
                         self._counts["frames_delivered"] += n // 1920
-                elif not r.stream and (r.speed_q or r.loudness is not None):
-                    # a blocking utterance with a speed or a loudness target: levelled and stretched whole once its last pass is in
+                elif not r.stream and (r.speed_q or r.loudness is not None or r.watermark):
+                    # a blocking utterance with a speed, a loudness target or the mark: levelled, stretched and marked whole once
+                    # its last pass is in
                     if n and not r.cancelled:
                         r.stretch_in.append(host[b, :n].copy())
                         self._counts["frames_delivered"] += n // 1920
@@ -1113,7 +1133,7 @@ class BatchScheduler:
                         if r.speed_q:
                             self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
                             continue
-                        r.out.put(r.stretch_in.pop())
+                        r.out.put(self._mark(r, r.stretch_in.pop()))
                 elif n and not r.cancelled:
                     r.out.put(host[b, :n].copy())
                     self._counts["frames_delivered"] += n // 1920
@@ -1147,8 +1167,18 @@ class BatchScheduler:
             r.stretch_in = [pcm]
             self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
             return
-        r.out.put(pcm)
+        r.out.put(self._mark(r, pcm))
         self._end(r)
+
+    def _mark(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
+        """A complete blocking utterance, levelled and stretched: a marked request's gets the watermark whole on the GPU
+        (stages.watermark_embed: one launch, waited for here as the seam join is)."""
+        if not r.watermark:
+            return pcm
+        from ..stages import watermark_embed
+
+        with self._torch.cuda.stream(self._stretch_stream):
+            return watermark_embed(pcm, self.watermark, self.session.engine.device)
 
     def _level(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
         """A complete blocking utterance (joined, not yet stretched): with a loudness target it is measured and scaled whole on
@@ -1191,7 +1221,7 @@ class BatchScheduler:
             for job in [j for j in ran if j.state == "ending"]:
                 r = job.req
                 if not r.cancelled:
-                    r.out.put(np.concatenate(job.outs) if job.outs else np.zeros(0, np.float32))
+                    r.out.put(self._mark(r, np.concatenate(job.outs) if job.outs else np.zeros(0, np.float32)))
                 self._end(r)
                 self._stretches.remove(job)
             self._stretch_flight = None

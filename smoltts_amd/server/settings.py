@@ -3,7 +3,7 @@
 (lm/config.py:5-12).  Extensions of this build: ``mimi_checkpoint`` (the reference downloads kyutai/mimi; there is no
 network here), ``max_batch`` (slots per GPU), ``weight_format`` ("bf16" | "fp8"), ``max_voices`` (cloned voices held at once),
 ``long_text`` / ``segment_max_bytes`` / ``seam_pause_ms`` / ``max_input_chars`` (long texts as chained segments),
-``idle_timeout_s`` / ``flush_after_s`` (text fed in pieces).  ``model_id`` is accepted by the schema
+``idle_timeout_s`` / ``flush_after_s`` (text fed in pieces), ``watermark`` (a keyed mark on the audio).  ``model_id`` is accepted by the schema
 but cannot be resolved without network access; ``get_checkpoint_dir`` says so."""
 from __future__ import annotations
 
@@ -42,6 +42,27 @@ class GenerationBlock(BaseModel):
                                    repetition_penalty=self.repetition_penalty, repetition_window=self.repetition_window)
 
 
+class WatermarkBlock(BaseModel):
+    """The server's watermark (watermark.py): ``key`` is 16 hex digits and is never logged or returned,
+    ``strength_db`` the mark's level under the speech, ``apply`` which requests are marked: ``"all"``, or ``"cloned"``: only those
+    that speak a voice registered through ``POST /v1/voices/add``."""
+    key: str = Field(pattern=r"^[0-9a-fA-F]{16}$", repr=False)
+    strength_db: float = Field(default=-26.0, ge=-40.0, le=-20.0, allow_inf_nan=False)
+    apply: Literal["all", "cloned"] = "all"
+
+    def to_watermark(self):
+        from ..watermark import Watermark
+
+        return Watermark(int(self.key, 16), self.strength_db)
+
+
+def watermark_setting(value) -> Optional[WatermarkBlock]:
+    """The ``watermark`` setting as a block: None, a ``WatermarkBlock`` or the dict it is made from (``ValueError`` for a bad one)."""
+    if value is None or isinstance(value, WatermarkBlock):
+        return value
+    return WatermarkBlock(**value)
+
+
 class ServerSettings(BaseModel):
     model_id: Optional[str] = None
     checkpoint_dir: Optional[str] = None
@@ -66,6 +87,10 @@ class ServerSettings(BaseModel):
     # (extension) the loudness target in LUFS of requests whose body names none (loudness.py); null: the level is
     # left as the model gives it
     loudness: Optional[float] = Field(default=None, ge=-40.0, le=-5.0)
+
+    # (extension) a keyed watermark added to the audio on the GPU; null: none.  {"key": "<16 hex digits>", "strength_db": -26.0,
+    # "apply": "all" | "cloned"}; marked responses carry X-Watermark: 1, and POST /v1/watermark/detect tests a recording
+    watermark: Optional[WatermarkBlock] = None
 
     # (extension) requests whose text is fed in pieces (POST .../stream-input): a slot that has waited this long for
     # text is closed as if its text had ended; with flush_after_s, text that has stopped arriving short of a sentence end for that

@@ -1,4 +1,4 @@
-"""The stages behind the codec, one class per C stage (resampler, time stretch, seam, loudness, FLAC), and their
+"""The stages behind the codec, one class per C stage (resampler, time stretch, seam, loudness, watermark, FLAC), and their
 whole-utterance helpers."""
 from __future__ import annotations
 
@@ -355,6 +355,71 @@ def loudness_normalize(pcm: np.ndarray, target: float, device: torch.device, wit
 
     _, _, g, y = _loudness_whole(pcm, device, check_target(target))
     return (y, g) if with_gain else y
+
+
+# ------------------------------------------------------------------------------- watermark
+class Watermarker(_Stage):
+    """Per-slot watermarking of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Watermark"; the numpy model is
+    ``watermark.StreamState``): one launch per call for every slot.  One key per stage: its chip table is uploaded here.  A slot
+    emits exactly the samples it reads.  Slots start off; ``reset_slots`` starts a new stream in a slot (gain 0: off)."""
+
+    C_NAME = "watermark"
+
+    def __init__(self, device: torch.device, max_batch: int, wm):
+        self.wm = wm
+        super().__init__(device, max_batch)
+
+    def _create_args(self) -> tuple:
+        self._tables = self.wm.packed()  # (read by the create call only)
+        assert self._tables.size == self.lib.smoltts_watermark_table_doubles()
+        return self._tables.ctypes.data, int(self._tables.size)
+
+    def reset_slots(self, slots: Sequence[int], gains: Sequence[float]) -> None:
+        """Start new streams in ``slots`` at their ``gains`` (10^(strength_db / 20); 0: the slot is off)."""
+        n = len(slots)
+        if not n:
+            return
+        self._call("reset_slots", self._ints(slots), (C.c_double * n)(*[float(g) for g in gains]), n)
+
+    def out_samples(self, n_in: int) -> int:
+        """A slot emits what it reads (one sample of room for an empty call)."""
+        return max(int(n_in), 1)
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
+        """Mark ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream.
+        ``valid``: device int32 [batch], the real samples of each row.  ``counts[b]``: the samples slot b wrote to ``out[b]``
+        (its valid ones; 0 for a slot that is off, whose row is left alone)."""
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.float32, n_in, counts, 1, valid)
+        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1], dptr(counts))
+
+    def embed(self, row: torch.Tensor, n: int, gain: float, out: torch.Tensor) -> None:
+        """``out[:n]``: the whole utterance ``row[:n]`` (device fp32, contiguous) marked from position 0, on the current stream."""
+        self._call("embed", dptr(row), int(n), float(gain), dptr(out))
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s state (synchronises the current stream), in the layout of ``watermark.StreamState.state``, with ``on``."""
+        ints, v = (C.c_int64 * 2)(), np.zeros(5, np.float64)
+        self._call("slot_state", int(slot), ints, v.ctypes.data)
+        return {"pos": int(ints[0]), "on": int(ints[1]), "values": v}
+
+
+def watermark_embed(pcm: np.ndarray, wm, device: torch.device) -> np.ndarray:
+    """A whole utterance (float32 at 24 kHz) marked with ``wm`` (a ``watermark.Watermark``) on ``device`` in one launch from
+    position 0: ``watermark.embed`` (``SmolTTS.__call__``).  Waits for the result."""
+    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    if x.size == 0:
+        return x
+    with torch.cuda.device(device):
+        st = Watermarker(device, 1, wm)
+        try:
+            def launch(row, n, out, counts):
+                st.embed(row, n, wm.gain, out)
+                counts.fill_(n)
+
+            return _whole_row(st, x, launch)
+        finally:
+            st.close()
 
 
 # ------------------------------------------------------------------------------- FLAC framing
