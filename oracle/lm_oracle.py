@@ -3,7 +3,8 @@
 This file is the *checker*, never the product: only ``tests/``, ``__graft_entry__.smoke()``
 and ``bench.py``'s ``cpu_baseline`` leg may import it.  ``smoltts_amd`` must never import it.
 
-It is a plain PyTorch-eager fp32 restatement (KV-cached, batched) of the reference algorithm:
+It is a plain PyTorch-eager fp32 restatement (KV-cached, batched) of the reference algorithm
+(``LMOracle(..., dtype=torch.float64)``: the same arithmetic with every weight, table, cache and intermediate in float64):
 
 * arithmetic  : ``modeling/model/rq_transformer.py``  (RMSNorm :601-613, RoPE table :616-624 and
                 rotation :627-640, Attention :535-570, FeedForward :573-582, DepthwiseLinear
@@ -104,8 +105,8 @@ class OracleLMConfig:
 
 # ----------------------------------------------------------------------------- primitives
 def rms_norm(x: Tensor, weight: Tensor, eps: float) -> Tensor:
-    """modeling :607-613: x.float() * rsqrt(mean(x^2) + eps), cast back, then * weight."""
-    xf = x.float()
+    """modeling :607-613: x.float() * rsqrt(mean(x^2) + eps), cast back, then * weight.  A float64 input stays float64."""
+    xf = x if x.dtype == torch.float64 else x.float()
     out = (xf * torch.rsqrt(torch.mean(xf * xf, dim=-1, keepdim=True) + eps)).type_as(x)
     return out * weight
 
@@ -126,7 +127,7 @@ def apply_rope(x: Tensor, cs: Tensor) -> Tensor:
     """modeling :627-640, interleaved pairs (2j, 2j+1).
 
     x: (..., H, hd); cs: broadcastable to (..., 1, hd/2, 2)."""
-    xs = x.float().reshape(*x.shape[:-1], -1, 2)
+    xs = (x if x.dtype == torch.float64 else x.float()).reshape(*x.shape[:-1], -1, 2)
     out = torch.stack(
         [
             xs[..., 0] * cs[..., 0] - xs[..., 1] * cs[..., 1],
@@ -146,8 +147,8 @@ def _argmax_with_margin(logits: Tensor) -> Tuple[Tensor, Tensor]:
 
 # ----------------------------------------------------------------------------- model
 class _Block:
-    def __init__(self, st: Dict[str, Tensor], prefix: str, n_head: int, n_kv: int, hd: int, eps: float):
-        g = lambda k: st[prefix + k].float()
+    def __init__(self, st: Dict[str, Tensor], prefix: str, n_head: int, n_kv: int, hd: int, eps: float, dtype=torch.float32):
+        g = lambda k: st[prefix + k].float().to(dtype)  # the stored values, upcast exactly
         if prefix + "attention.wqkv.weight" in st:
             self.wqkv = g("attention.wqkv.weight")
         else:  # legacy split keys, modeling :528-533
@@ -159,24 +160,36 @@ class _Block:
         self.attn_norm = g("attention_norm.weight")
         self.ffn_norm = g("ffn_norm.weight")
         self.n_head, self.n_kv, self.hd, self.eps = n_head, n_kv, hd, eps
+        self.dtype = dtype
+        self.raw_kv = None  # (k, v) of the last ``qkv`` call before the bf16 rounding (the same tensors without ``kv_bf16``)
         self.kv_bf16 = False  # engine option kv_dtype="bf16": K (after RoPE) and V are rounded to bf16 once, as they enter the cache
+
+    def mm(self, x: Tensor, w: Tensor) -> Tensor:
+        """Every weight GEMM of the block: activations x (..., k) times the stored weight w (n, k).  (One place, so that a test
+        can degrade the activation operand of all of them: tests/lm_strict_helpers.TwoPieceBlock.)"""
+        return x @ w.T
 
     def qkv(self, x: Tensor, cs: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
         """x (..., d) -> q (..., H, hd), k, v (..., KV, hd) with RoPE applied (modeling :542-552)."""
-        qkv = rms_norm(x, self.attn_norm, self.eps) @ self.wqkv.T
+        qkv = self.mm(rms_norm(x, self.attn_norm, self.eps), self.wqkv)
         dq, dkv = self.n_head * self.hd, self.n_kv * self.hd
         q, k, v = qkv.split([dq, dkv, dkv], dim=-1)
         q = q.reshape(*q.shape[:-1], self.n_head, self.hd)
         k = k.reshape(*k.shape[:-1], self.n_kv, self.hd)
         v = v.reshape(*v.shape[:-1], self.n_kv, self.hd)
         q, k = apply_rope(q, cs), apply_rope(k, cs)
+        self.raw_kv = (k, v)
         if self.kv_bf16:  # round to nearest even, what the engine's cache write does; every use of K / V sees the rounded values
-            k, v = k.bfloat16().float(), v.bfloat16().float()
+            k, v = k.bfloat16().to(self.dtype), v.bfloat16().to(self.dtype)
         return q, k, v
 
     def mlp(self, h: Tensor) -> Tensor:
         hn = rms_norm(h, self.ffn_norm, self.eps)
-        return h + (torch.nn.functional.silu(hn @ self.w1.T) * (hn @ self.w3.T)) @ self.w2.T
+        return h + self.mm(torch.nn.functional.silu(self.mm(hn, self.w1)) * self.mm(hn, self.w3), self.w2)
+
+    def out(self, a: Tensor) -> Tensor:
+        """Attention output projection wo (modeling :570)."""
+        return self.mm(a, self.wo)
 
 
 def _gqa_attend(q: Tensor, K: Tensor, V: Tensor, mask: Optional[Tensor]) -> Tensor:
@@ -207,7 +220,7 @@ class OracleFrameLog:
 
 
 class LMOracle:
-    """Batched, KV-cached greedy DualAR decode in fp32 torch eager on CPU."""
+    """Batched, KV-cached greedy DualAR decode in fp32 (or float64) torch eager on CPU."""
 
     def __init__(
         self,
@@ -216,13 +229,18 @@ class LMOracle:
         embed_mask: str = "torch",
         rope_bf16: bool = True,
         kv_bf16: bool = False,
+        dtype: torch.dtype = torch.float32,
     ):
-        """``kv_bf16``: mirror of the engine's bf16 KV-cache option (slow transformer only; the depth transformer's 8-entry
+        """``dtype``: torch.float32 (default, the reference's arithmetic) or torch.float64: weights, tables, caches and every
+        intermediate in that type.  The stored weights and the RoPE table (bf16-rounded with ``rope_bf16``) are inputs: float64
+        upcasts the very values the fp32 oracle uses, it does not recompute them.
+
+        ``kv_bf16``: mirror of the engine's bf16 KV-cache option (slow transformer only; the depth transformer's 8-entry
         per-frame cache stays fp32 there too).  The reference itself keeps K/V in the activation dtype (lm/cache.py:6-22)."""
-        assert embed_mask in ("torch", "mlx")
-        self.cfg, self.embed_mask = cfg, embed_mask
+        assert embed_mask in ("torch", "mlx") and dtype in (torch.float32, torch.float64)
+        self.cfg, self.embed_mask, self.dtype = cfg, embed_mask, dtype
         st = {k.replace("_orig_mod.", ""): v for k, v in state.items()}
-        f = lambda k: st[k].float()
+        f = lambda k: st[k].float().to(dtype)
         self.E_text = f("embeddings.weight")
         self.E_cb = f("codebook_embeddings.weight")
         self.E_fast = f("fast_embeddings.weight")
@@ -230,11 +248,11 @@ class LMOracle:
         self.fast_norm_w = f("fast_norm.weight")
         self.out_w = self.E_text if cfg.tie_word_embeddings else f("output.weight")
         self.layers = [
-            _Block(st, f"layers.{i}.", cfg.n_head, cfg.n_local_heads, cfg.head_dim, cfg.norm_eps)
+            _Block(st, f"layers.{i}.", cfg.n_head, cfg.n_local_heads, cfg.head_dim, cfg.norm_eps, dtype)
             for i in range(cfg.n_layer)
         ]
         self.fast_layers = [
-            _Block(st, f"fast_layers.{i}.", cfg.fast_n_head, cfg.fast_n_local_heads, cfg.fast_head_dim, cfg.norm_eps)
+            _Block(st, f"fast_layers.{i}.", cfg.fast_n_head, cfg.fast_n_local_heads, cfg.fast_head_dim, cfg.norm_eps, dtype)
             for i in range(cfg.n_fast_layer)
         ]
         for L in self.layers:
@@ -252,8 +270,8 @@ class LMOracle:
                 self.fast_out = fo.reshape(nfast, cs, fd)
         else:
             self.fast_out = fo.reshape(1, cs, fd).expand(nfast, cs, fd)
-        self.rope = rope_table(cfg.max_seq_len, cfg.head_dim, cfg.rope_base, rope_bf16)
-        self.fast_rope = rope_table(nfast, cfg.fast_head_dim, cfg.rope_base, rope_bf16)
+        self.rope = rope_table(cfg.max_seq_len, cfg.head_dim, cfg.rope_base, rope_bf16).to(dtype)
+        self.fast_rope = rope_table(nfast, cfg.fast_head_dim, cfg.rope_base, rope_bf16).to(dtype)
 
     # ---- embed, modeling :205-221 / lm/rq_transformer.py:150-170
     def embed(self, cols: Tensor) -> Tensor:
@@ -274,8 +292,8 @@ class LMOracle:
     def _alloc(self, B: int, cap: int):
         cfg = self.cfg
         shp = (B, cap, cfg.n_local_heads, cfg.head_dim)
-        self.K = [torch.zeros(shp) for _ in range(cfg.n_layer)]
-        self.V = [torch.zeros(shp) for _ in range(cfg.n_layer)]
+        self.K = [torch.zeros(shp, dtype=self.dtype) for _ in range(cfg.n_layer)]
+        self.V = [torch.zeros(shp, dtype=self.dtype) for _ in range(cfg.n_layer)]
         self.pos = torch.zeros(B, dtype=torch.int64)  # tokens cached so far, per utterance
 
     def prefill_one(self, b: int, grid: Tensor) -> Tensor:
@@ -288,7 +306,7 @@ class LMOracle:
             q, k, v = L.qkv(x, cs)
             self.K[li][b, :T], self.V[li][b, :T] = k[0], v[0]
             a = _gqa_attend(q, k, v, mask)
-            x = L.mlp(x + a @ L.wo.T)
+            x = L.mlp(x + L.out(a))
         self.pos[b] = T
         return x[0, -1]
 
@@ -304,7 +322,7 @@ class LMOracle:
             q, k, v = L.qkv(x, cs)
             self.K[li][bi, self.pos], self.V[li][bi, self.pos] = k[:, 0], v[:, 0]
             a = _gqa_attend(q, self.K[li][:, :Lmax], self.V[li][:, :Lmax], mask)
-            x = L.mlp(x + a @ L.wo.T)
+            x = L.mlp(x + L.out(a))
         self.pos += 1
         return x[:, 0]
 
@@ -318,10 +336,10 @@ class LMOracle:
         cfg = self.cfg
         B, n = hidden.shape[0], cfg.max_fast_seqlen
         x = hidden if self.proj_w is None else hidden @ self.proj_w.T + self.proj_b
-        Kc = [torch.zeros(B, n, cfg.fast_n_local_heads, cfg.fast_head_dim) for _ in self.fast_layers]
+        Kc = [torch.zeros(B, n, cfg.fast_n_local_heads, cfg.fast_head_dim, dtype=self.dtype) for _ in self.fast_layers]
         Vc = [torch.zeros_like(k) for k in Kc]
         codes = torch.zeros(B, n, dtype=torch.int64)
-        margin = torch.full((B,), float("inf"))
+        margin = torch.full((B,), float("inf"), dtype=self.dtype)
         for i in range(n):
             h = x[:, None]
             cs = self.fast_rope[i][None, None, None]
@@ -329,7 +347,7 @@ class LMOracle:
                 q, k, v = L.qkv(h, cs)
                 Kc[li][:, i], Vc[li][:, i] = k[:, 0], v[:, 0]
                 a = _gqa_attend(q, Kc[li][:, : i + 1], Vc[li][:, : i + 1], None)
-                h = L.mlp(h + a @ L.wo.T)
+                h = L.mlp(h + L.out(a))
             logits = rms_norm(h[:, 0], self.fast_norm_w, cfg.norm_eps) @ self.fast_out[i].T
             ids, m = _argmax_with_margin(logits)
             codes[:, i] = ids
@@ -382,16 +400,26 @@ class LMOracle:
         """grid (9, S) -> token_logits (S, V), codebook_logits (S, n_fast, 2048).
 
         Position s's fast pass sees hidden[s] followed by the fast embeddings of codes at s+1
-        (modeling :417-422); the last position sees zeros-padded codes."""
+        (modeling :417-422); the last position sees zeros-padded codes.
+
+        Also leaves the slow transformer's K (after RoPE) and V of every position, as the cache holds them, in ``self.K`` / ``self.V``
+        (per layer ``[1, S, n_kv, hd]``) and stacked in ``self.tf_K`` / ``self.tf_V`` ``[n_layer, S, n_kv, hd]``; with ``kv_bf16``
+        those are the rounded values and ``self.tf_K_raw`` / ``self.tf_V_raw`` the un-rounded ones (otherwise the same values)."""
         cfg = self.cfg
         self._alloc(1, grid.shape[1])
         S = grid.shape[1]
+        raw_k, raw_v = [], []
         x = self.embed(grid.T.contiguous().long())[None]
         cs = self.rope[:S][None, :, None]
         mask = torch.tril(torch.ones(S, S, dtype=torch.bool))[None, None]
-        for L in self.layers:
+        for li, L in enumerate(self.layers):
             q, k, v = L.qkv(x, cs)
-            x = L.mlp(x + _gqa_attend(q, k, v, mask) @ L.wo.T)
+            self.K[li][0], self.V[li][0] = k[0], v[0]
+            raw_k.append(L.raw_kv[0][0]); raw_v.append(L.raw_kv[1][0])
+            x = L.mlp(x + L.out(_gqa_attend(q, k, v, mask)))
+        self.pos[0] = S
+        self.tf_K, self.tf_V = torch.stack([k[0] for k in self.K]), torch.stack([v[0] for v in self.V])
+        self.tf_K_raw, self.tf_V_raw = torch.stack(raw_k), torch.stack(raw_v)
         tok = self.slow_head(x[0])
         n = cfg.max_fast_seqlen
         nxt = torch.zeros(S, grid.shape[0] - 2, dtype=torch.int64)
@@ -407,7 +435,7 @@ class LMOracle:
         fmask = torch.tril(torch.ones(n, n, dtype=torch.bool))[None, None]
         for L in self.fast_layers:
             q, k, v = L.qkv(h, csf)
-            h = L.mlp(h + _gqa_attend(q, k, v, fmask) @ L.wo.T)
+            h = L.mlp(h + L.out(_gqa_attend(q, k, v, fmask)))
         hn = rms_norm(h, self.fast_norm_w, cfg.norm_eps)
         cb = torch.einsum("snd,nkd->snk", hn, self.fast_out)
         # the zero-padded last column is dropped before the fast layers and scattered back as

@@ -238,3 +238,107 @@ def test_mimi_oracle_window_250_is_reached_by_140_frames():
     tail = rms(w250[-15 * 1920:] - w0[-15 * 1920:])
     print(f"window 250 vs 0, 140 frames: rms difference over the last 15 frames {tail:.3e}, over the first 125 {rms(w250[:125 * 1920] - w0[:125 * 1920]):.3e}")
     assert tail > 1e-3 and np.array_equal(w250[: 125 * 1920], w0[: 125 * 1920])
+
+
+def test_lm_float64_oracle_generates_the_golden_ids(golden_dir):
+    """``LMOracle(dtype=torch.float64)``, free-running on the tiny golden prompts: the same ids as the fp32 oracle and the golden
+    grids (whose gaps, >= 2e-5, are far above fp32 noise), with every cache and logit in float64.  That the fp32 default is
+    bit-identical to before the switch existed is what ``test_lm_oracle_reproduces_goldens`` pins."""
+    from oracle.lm_oracle import LMOracle, OracleLMConfig
+
+    g = np.load(golden_dir / "lm_tiny.npz")
+    cfg, state, o32, _ = _lm(str(g["config_name"]), int(g["seed"]))
+    o64 = LMOracle(OracleLMConfig.from_dict(cfg.__dict__), state, dtype=torch.float64)
+    n, frames = len(g["texts"]), int(g["frames"])
+    prompts = [torch.from_numpy(g[f"prompt_{b}"]) for b in range(n)]
+    l32, l64 = o32.generate(prompts, max_frames=frames, stop_on_eos=False), o64.generate(prompts, max_frames=frames, stop_on_eos=False)
+    for b in range(n):
+        assert l64[b].grid == l32[b].grid and np.array_equal(l64[b].as_tensor().numpy(), g[f"grid_{b}"])
+        assert l64[b].min_margin == pytest.approx(l32[b].min_margin, rel=0.05, abs=2e-6)
+    assert all(t.dtype == torch.float64 for t in o64.K + o64.V) and all(t.dtype == torch.float32 for t in o32.K + o32.V)
+    tok, cb = o64.teacher_forced(torch.cat([prompts[0].long(), l64[0].as_tensor()], dim=1))
+    assert tok.dtype == cb.dtype == o64.tf_K.dtype == o64.tf_V.dtype == torch.float64
+    assert o64.rope.dtype == torch.float64 and torch.equal(o64.rope.float(), o32.rope)  # the table is an input: the fp32 oracle's values, upcast
+    assert torch.equal(o64.E_text.float(), o32.E_text)
+
+
+@pytest.mark.parametrize("case", ["CASE2", "CASE4"])
+def test_lm_strict_bound_rejects_two_piece_activations(case):
+    """The yardstick of tests/test_lm_strict_gpu.py has teeth.  A third CPU computation differs from the fp32 oracle only in that
+    every weight GEMM's activation operand is cut to two bf16 pieces (2^-16-grade, the kind of error a dropped term of the bf16
+    split gives); at the shapes of that suite's cases 2 and 4 it must VIOLATE  RMS(x - float64) <= 4 R_ref  at every layer: for K
+    and for V, for every slot, for its prompt rows and its decode rows apart -- every unit the GPU test judges.
+    Measured rms / R_ref of the control (bound 4), smallest .. largest over those units: case 2 (tiny) layer 0 5.9 .. 9.1, layer 1
+    7.1 .. 10.4; case 4 (70m) layer 0 7.6 .. 8.1, layers 1 - 9 6.7 .. 10.2.  (Its max err / E_ref is 2.0 .. 12.7: one element's
+    luck, which is why the control is judged by RMS.)  No layer lets it through, so the per-segment RMS is not too loose."""
+    import lm_strict_helpers as H
+
+    name, Ts, n = getattr(H, case)
+    cfg, _, o32, o64, o2 = H.make_oracles(name, 3, block_cls=H._two_piece_block())
+    gen = torch.Generator().manual_seed(7)
+    lo_hi = {}
+    for b, T in enumerate(Ts):
+        grid = H.random_grid(cfg, T + n, gen)
+        r = H.teacher_refs(o32, o64, grid)
+        (k2, v2, _, _), _, _ = H.teacher_kv(o2, grid)
+        # the fp32 oracle itself passes its own yardstick trivially (ratio 1); the control must fail it everywhere
+        for which, got, r32, r64 in (("K", k2, r.K32, r.K64), ("V", v2, r.V32, r.V64)):
+            fails, worst = H.strict_kv_report(got, r32, r64, T, b, which)
+            units = {(f.layer, f.segment) for f in fails if f.rms_ratio > H.FACTOR}
+            assert units == {(l, s) for l in range(cfg.n_layer) for s in ("prompt", "decode")}, \
+                f"{name} slot {b} {which}: the two-piece control passes the RMS bound at (layer, segment) " \
+                f"{sorted({(l, s) for l in range(cfg.n_layer) for s in ('prompt', 'decode')} - units)}"
+            for f in fails:
+                a = lo_hi.setdefault(f.layer, [f.rms_ratio, f.rms_ratio])
+                a[0], a[1] = min(a[0], f.rms_ratio), max(a[1], f.rms_ratio)
+            assert not H.strict_kv_report(r32, r32, r64, T, b, which)[0]
+    print(f"{name}: two-piece control, rms / R_ref per layer (min .. max over slots, K / V, segments): " +
+          ", ".join(f"{l}: {a[0]:.1f} .. {a[1]:.1f}" for l, a in sorted(lo_hi.items())))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_lm_oracle_kv_bf16_exposes_rounded_and_unrounded(dtype):
+    """``teacher_forced`` of a ``kv_bf16`` oracle: ``tf_K`` / ``tf_V`` (what the cache holds) are the bf16 rounding of ``tf_K_raw`` /
+    ``tf_V_raw``, [n_layer, S, n_kv, 64] in the oracle's dtype; without ``kv_bf16`` the two are the same values."""
+    import lm_strict_helpers as H
+    from oracle.lm_oracle import LMOracle, OracleLMConfig
+
+    cfg, state, _, _ = _lm("tiny", 3)
+    grid = torch.from_numpy(H.random_grid(cfg, 21, torch.Generator().manual_seed(1))).long()
+    ocfg = OracleLMConfig.from_dict(cfg.__dict__)
+    orc = LMOracle(ocfg, state, kv_bf16=True, dtype=dtype)
+    orc.teacher_forced(grid)
+    for cached, raw in ((orc.tf_K, orc.tf_K_raw), (orc.tf_V, orc.tf_V_raw)):
+        assert cached.dtype == raw.dtype == dtype and tuple(cached.shape) == tuple(raw.shape) == (cfg.n_layer, 21, cfg.n_local_heads, 64)
+        assert torch.equal(cached, raw.bfloat16().to(dtype)) and not torch.equal(cached, raw)
+    assert torch.equal(orc.K[1][0], orc.tf_K[1]) and torch.equal(orc.V[0][0], orc.tf_V[0])
+    plain = LMOracle(ocfg, state, dtype=dtype)
+    plain.teacher_forced(grid)
+    assert torch.equal(plain.tf_K, plain.tf_K_raw) and torch.equal(plain.tf_V, plain.tf_V_raw)
+    assert torch.equal(plain.tf_K_raw[0], orc.tf_K_raw[0])  # layer 0 depends on no cached value
+
+
+def test_lm_strict_helper_names_the_wrong_element():
+    """``strict_kv_report`` on synthetic arrays: 1e-5 added to one element of one layer's K is reported as exactly that layer, slot,
+    position, kv head and dimension, on the prompt side and on the decode side; the clean copy passes."""
+    import lm_strict_helpers as H
+
+    rng = np.random.default_rng(0)
+    n_layer, T, n, kv = 3, 19, 5, 2
+    ref64 = rng.standard_normal((n_layer, T + n, kv, 64))
+    ref32 = ref64 + rng.standard_normal(ref64.shape) * 3e-7   # the fp32 oracle's own noise
+    clean = (ref64 + rng.standard_normal(ref64.shape) * 3e-7).astype(np.float32)
+    assert not H.strict_kv_report(clean, ref32, ref64, T, 4, "K")[0]
+    for pos, seg in ((7, "prompt"), (T + 2, "decode")):
+        bad = clean.copy()
+        bad[1, pos, 1, 33] += 1e-5
+        fails, worst = H.strict_kv_report(bad, ref32, ref64, T, 4, "K")
+        assert len(fails) == 1
+        f = fails[0]
+        assert (f.which, f.layer, f.slot, f.segment, f.pos, f.head, f.dim) == ("K", 1, 4, seg, pos, 1, 33)
+        assert f.max_ratio > H.FACTOR and worst[seg][0] == f.max_ratio
+        assert f"K layer 1 slot 4 {seg} rows" in f.msg and f"position {pos} " in f.msg and "kv head 1, dim 33" in f.msg
+    # the half-ulp of the bf16 cache test (8 significant bits: ulp(1.0) = 2^-7), at and between powers of two
+    assert H.half_ulp_bf16(np.array([1.0, 1.5, 2.0, -0.75, 0.0])).tolist() == [2.0 ** -8, 2.0 ** -8, 2.0 ** -7, 2.0 ** -9, 0.0]
+    x = np.array([0.3, -1.7, 100.0])
+    assert (np.abs(torch.tensor(x).bfloat16().double().numpy() - x) <= H.half_ulp_bf16(x)).all()
