@@ -327,6 +327,11 @@ int smoltts_session_outputs(SmolttsSession* s, int32_t** codes_dev, int32_t** n_
 /* Diagnostics: the slow transformer's KV cache of the session -- k / v [n_layer][max_batch][n_kv_head][max_seq][64] in the session's
  * kv format (fp32 or bf16), `layer_bytes` apart per layer.  Read-only use (tests compare cache rows between launch structures). */
 int smoltts_session_kv_cache(SmolttsSession* s, void** k_dev, void** v_dev, uint64_t* layer_bytes);
+/* (ABI 6, additive) Diagnostics: the depth transformer's KV cache of the session -- k / v
+ * [n_fast_layer][max_batch][fast_n_kv_head][n_fast][64], fp32 always (whatever the session's kv format), `layer_bytes` apart per
+ * layer; k is the value after RoPE.  Entry i of a slot holds depth step i of the slot's latest frame until the next frame
+ * overwrites it.  Read-only use (tests hold the rows to a float64 oracle, per layer and step). */
+int smoltts_session_fast_kv_cache(SmolttsSession* s, float** k_dev, float** v_dev, uint64_t* layer_bytes);
 /* int32 [max_batch]: where each slot's smallest gap occurred, frame * 64 + step (step 0 = slow id, i = depth code i-1). */
 int smoltts_session_margin_at(SmolttsSession* s, int32_t** margin_at_dev);
 

@@ -404,7 +404,10 @@ class LMOracle:
 
         Also leaves the slow transformer's K (after RoPE) and V of every position, as the cache holds them, in ``self.K`` / ``self.V``
         (per layer ``[1, S, n_kv, hd]``) and stacked in ``self.tf_K`` / ``self.tf_V`` ``[n_layer, S, n_kv, hd]``; with ``kv_bf16``
-        those are the rounded values and ``self.tf_K_raw`` / ``self.tf_V_raw`` the un-rounded ones (otherwise the same values)."""
+        those are the rounded values and ``self.tf_K_raw`` / ``self.tf_V_raw`` the un-rounded ones (otherwise the same values).
+        The depth transformer's K (after RoPE) and V of every position's ``n_fast`` steps are left in ``self.tf_fK`` / ``self.tf_fV``
+        ``[n_fast_layer, S, n_fast, fast_n_kv, hd]``: position s holds what the depth cache holds after the frame picked at s, given
+        that frame's codes in column s + 1 (the last position's rows belong to the zero-padded column)."""
         cfg = self.cfg
         self._alloc(1, grid.shape[1])
         S = grid.shape[1]
@@ -433,9 +436,12 @@ class LMOracle:
         h = torch.cat([hid[:, None], fe], dim=1)  # S, n, d
         csf = self.fast_rope[:n][None, :, None]
         fmask = torch.tril(torch.ones(n, n, dtype=torch.bool))[None, None]
+        fk, fv = [], []
         for L in self.fast_layers:
             q, k, v = L.qkv(h, csf)
+            fk.append(k); fv.append(v)
             h = L.mlp(h + L.out(_gqa_attend(q, k, v, fmask)))
+        self.tf_fK, self.tf_fV = torch.stack(fk), torch.stack(fv)
         hn = rms_norm(h, self.fast_norm_w, cfg.norm_eps)
         cb = torch.einsum("snd,nkd->snk", hn, self.fast_out)
         # the zero-padded last column is dropped before the fast layers and scattered back as

@@ -175,6 +175,7 @@ SIGNATURES = {
     "smoltts_session_set_slot_filters": (INT, "p p i p p p p p"),
     "smoltts_session_outputs": (INT, "p p* p* p* p*"),
     "smoltts_session_kv_cache": (INT, "p p* p* Q*"),
+    "smoltts_session_fast_kv_cache": (INT, "p p* p* Q*"),
     "smoltts_session_margin_at": (INT, "p p*"),
     "smoltts_prefix_kv_bytes": (SIZE, "p i i"),
     "smoltts_session_save_prefix": (INT, "p i i p PrefixHeader* p"),

@@ -1484,6 +1484,14 @@ int smoltts_session_kv_cache(SmolttsSession* s, void** k_dev, void** v_dev, uint
   return SMOLTTS_OK;
 }
 
+int smoltts_session_fast_kv_cache(SmolttsSession* s, float** k_dev, float** v_dev, uint64_t* layer_bytes) {
+  ST_REQUIRE(s && k_dev && v_dev && layer_bytes, SMOLTTS_E_INVALID, "session_fast_kv_cache: null argument");
+  const SmolttsLMConfig& c = s->e->cfg;
+  *k_dev = s->fkc; *v_dev = s->fvc;
+  *layer_bytes = (uint64_t)s->B * c.fast_n_kv_head * c.n_fast * 64 * sizeof(float);
+  return SMOLTTS_OK;
+}
+
 int smoltts_session_margin_at(SmolttsSession* s, int32_t** margin_at_dev) {
   ST_REQUIRE(s && margin_at_dev, SMOLTTS_E_INVALID, "session_margin_at: null argument");
   *margin_at_dev = s->margin_at;

@@ -384,6 +384,22 @@ class LMSession(ClosesOnDel):
             out.append(self.slab[o: o + n_layer * lb.value].view(dt).view(n_layer, self.B, kvh, self.max_seq, 64))
         return out
 
+    def fast_kv_cache(self):
+        """(K, V) views of the depth transformer's cache: [n_fast_layer, max_batch, fast_n_kv_head, n_fast, 64] fp32, K after RoPE;
+        entry i of a slot is depth step i of its latest frame (diagnostics)."""
+        k, v, lb = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        check(self.lib.smoltts_session_fast_kv_cache(self.handle, C.byref(k), C.byref(v), C.byref(lb)), "smoltts_session_fast_kv_cache")
+        cfg = self.engine.cfg
+        n_layer, kvh, n_fast = cfg.n_fast_layer, cfg.fast_n_local_heads, self.H - 1
+        if lb.value != self.B * kvh * n_fast * 64 * 4:
+            raise SmolttsError(f"smoltts_session_fast_kv_cache: {lb.value} bytes per layer, expected {self.B * kvh * n_fast * 64 * 4}")
+        base = self.slab.data_ptr()
+        out = []
+        for p in (k, v):
+            o = p.value - base
+            out.append(self.slab[o: o + n_layer * lb.value].view(torch.float32).view(n_layer, self.B, kvh, n_fast, 64))
+        return out
+
     def use_fp8_prefill(self, on: bool) -> None:
         """fp8-weight engines: prompt prefills of >= 256 rows on the fp8 x fp8 MFMA (BASELINE configs[4]'s fp8 MFMA prefill).  Faster
         first chunk; the prompt's KV rows carry the activations' fp8 rounding, so ids may leave the reference greedy decode."""

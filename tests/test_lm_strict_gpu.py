@@ -34,12 +34,27 @@ then the gap check's worst |margin - g64| / E_row (bound 8):
   bf16 cache, layer 0: worst (|engine - x64| - 1/2 ulp_bf16) / E_ref = 0.03 (bound 4)
 i.e. the engine's chain is as close to float64 as the fp32 CPU oracle is.  The cases at 348 rows and above, whose prompt rows run the
 matrix-core prefill attention, sit a little higher (up to 1.8) and still well inside the factor; nothing needed it to rise.
+
+fp8 weights (``weight_format="fp8"``, BASELINE config 5) and the 150m shape.  The fp8 engine computes the model whose Linears are the
+dequantised e4m3 values; its cases run both oracles on ``packing.fp8_reference_state`` and are judged in the same way, so the W8
+instantiations of the gemm3 kernels are held to float64 at 17..128, 129..255 and >= 256 rows and at decode M > 16 (``use_fp8_prefill``
+stays off: that path is documented as approximate).  The 150m cases (12 / 4 heads, dim 768, 10 layers; T = 3, 40, 90, 4 frames) are
+the benchmark's model.  That the bound rejects 2^-16-grade arithmetic on the fp8 model and at 150m:
+tests/test_oracle_cpu.py::test_lm_strict_bound_rejects_two_piece_activations_on_the_fp8_model.  Measured, as above:
+  fp8 case 2 (tiny, 117 ragged rows)          0.52, 0.50 | 0.66, 0.54    gaps 0.27
+  fp8 case 3 (tiny, 20 slots)                 0.77, 0.53 | 0.70, 0.60
+  fp8 case 4 (70m, 193 rows)                  0.68, 0.58 | 0.75, 0.62    gaps 0.34
+  fp8 case 5 (70m, 348 rows)                  1.47, 1.18 | 0.90, 0.80
+  150m bf16 (133 rows)                        0.85, 0.61 | 0.77, 0.61    gaps 0.51
+  150m fp8 (133 rows)                         0.73, 0.60 | 0.78, 0.59    gaps 0.26
+The same fp8 rows judged against the UNQUANTISED model's oracles exceed the bound at every slot, for K and V (worst 1.3e5 x E_ref,
+1.2e5 x R_ref at tiny; 1.3e5, 1.1e5 at 150m): the quantisation is in effect, and the bound is 10^5 times tighter than the quantisation's effect.
 """
 import numpy as np
 import pytest
 import torch
 
-from lm_strict_helpers import (CASE2, CASE4, FACTOR, gap_report, half_ulp_bf16, make_oracles, random_grid, rms, slot_rows,
+from lm_strict_helpers import (CASE2, CASE4, CASE150, FACTOR, gap_report, half_ulp_bf16, make_oracles, random_grid, rms, slot_rows,
                                strict_kv_report, teacher_refs)
 
 pytestmark = pytest.mark.gpu
@@ -50,14 +65,17 @@ SEED = 3
 class _Model:
     """One config's engine and its two oracles, with the teacher-forced passes kept by grid (a reference is computed once)."""
 
-    def __init__(self, cfgname):
+    def __init__(self, cfgname, fp8=False):
+        """``fp8``: the engine holds e4m3 weights and the oracles run on ``packing.fp8_reference_state``, the model it computes."""
         from smoltts_amd.config import NumericsMode, TokenConfig
         from smoltts_amd.engine import LMEngine
         from smoltts_amd.tokenizer import load_tokenizer
 
         self.name = cfgname
-        self.cfg, state, self.o32, self.o64 = make_oracles(cfgname, SEED)
-        self.eng = LMEngine(self.cfg, state, TokenConfig.from_tokenizer(load_tokenizer(), self.cfg), NumericsMode.torch_reference())
+        self.cfg, state, self.o32, self.o64 = make_oracles(cfgname, SEED, fp8=fp8)
+        self.eng = LMEngine(self.cfg, state, TokenConfig.from_tokenizer(load_tokenizer(), self.cfg), NumericsMode.torch_reference(),
+                            weight_format="fp8" if fp8 else "bf16")
+        assert self.eng.weight_format == ("fp8" if fp8 else "bf16")
         self.state = state
         self._refs = {}
 
@@ -78,6 +96,34 @@ def tiny():
 @pytest.fixture(scope="module")
 def m70():
     m = _Model("smoltts_byte_70m")
+    yield m
+    m.eng.close()
+
+
+@pytest.fixture(scope="module")
+def tiny_fp8():
+    m = _Model("tiny", fp8=True)
+    yield m
+    m.eng.close()
+
+
+@pytest.fixture(scope="module")
+def m70_fp8():
+    m = _Model("smoltts_byte_70m", fp8=True)
+    yield m
+    m.eng.close()
+
+
+@pytest.fixture(scope="module")
+def m150():
+    m = _Model("smoltts_byte_150m")
+    yield m
+    m.eng.close()
+
+
+@pytest.fixture(scope="module")
+def m150_fp8():
+    m = _Model("smoltts_byte_150m", fp8=True)
     yield m
     m.eng.close()
 
@@ -108,8 +154,8 @@ def _run(m, Ts, n, max_seq, chunk=None, split=None, kv_dtype="fp32", seed=11):
     return prompts, frames, K, V, margin.copy(), margin_at
 
 
-def _judge_kv(label, m, Ts, n, prompts, frames, K, V):
-    """Every slot's T_b + n rows of every layer under the bound; prints and returns the worst ratios {segment: (max, rms)}."""
+def _kv_failures(m, Ts, n, prompts, frames, K, V):
+    """Every slot's T_b + n rows of every layer against ``m``'s oracles -> (failures, worst ratios {segment: [max, rms]})."""
     fails, worst = [], {"prompt": [0.0, 0.0], "decode": [0.0, 0.0]}
     for b, T in enumerate(Ts):
         grid = np.concatenate([prompts[b], frames[b, :n].T], axis=1)  # (9, T + n): the columns whose rows the engine has written
@@ -119,6 +165,12 @@ def _judge_kv(label, m, Ts, n, prompts, frames, K, V):
             fails += f
             for seg, (we, wr) in w.items():
                 worst[seg] = [max(worst[seg][0], we), max(worst[seg][1], wr)]
+    return fails, worst
+
+
+def _judge_kv(label, m, Ts, n, prompts, frames, K, V):
+    """Every slot's T_b + n rows of every layer under the bound; prints and returns the worst ratios {segment: (max, rms)}."""
+    fails, worst = _kv_failures(m, Ts, n, prompts, frames, K, V)
     print(f"{label}: worst max err / E_ref, rms / R_ref (bound {FACTOR:g}): prompt rows {worst['prompt'][0]:.2f}, {worst['prompt'][1]:.2f} | "
           f"decode rows {worst['decode'][0]:.2f}, {worst['decode'][1]:.2f}")
     fails.sort(key=lambda f: -max(f.max_ratio, f.rms_ratio))
@@ -137,6 +189,16 @@ def _judge_gaps(label, m, Ts, n, prompts, frames, margin, margin_at):
         worst = max(worst, ratio)
     print(f"{label}: top-2 gaps: worst |margin - g64| / E_row = {worst:.2f} (bound {2 * FACTOR:g})")
     assert not msgs, f"{label}: " + "\n".join(msgs[:6])
+
+
+def _judge_quantisation_in_effect(label, other, Ts, n, prompts, frames, K, V):
+    """The fp8 engine's rows against the oracles of the UNQUANTISED model (``other``): every slot must fail the bound, for K and for V
+    -- the fp8 cases above pass because the engine computes the dequantised model, not because the bound is wide."""
+    fails, worst = _kv_failures(other, Ts, n, prompts, frames, K, V)
+    print(f"{label}: against the bf16 model's oracles: worst max err / E_ref {max(worst['prompt'][0], worst['decode'][0]):.3g}, rms / R_ref "
+          f"{max(worst['prompt'][1], worst['decode'][1]):.3g} (must exceed {FACTOR:g})")
+    assert {(f.which, f.slot) for f in fails} == {(w, b) for w in "KV" for b in range(len(Ts))}, \
+        f"{label}: rows of an fp8 engine pass the bound against the bf16 model's float64 oracle: the quantisation is not in effect"
 
 
 def test_case1_one_short_prompt(tiny):
@@ -227,3 +289,52 @@ def test_bf16_cache_layer0_rounds_the_fp32_value(tiny):
                                 f"{x64[lo + p, h, i]:.9g}: {over[p, h, i]:.2f} x E_ref ({e_ref:.3e}) beyond half a bf16 ulp")
     print(f"bf16 cache, layer 0: worst (|engine - x64| - 1/2 ulp) / E_ref = {worst:.2f} (bound {FACTOR:g})")
     assert not msgs, "\n".join(msgs[:6])
+
+
+def test_fp8_case2_ragged_117_rows(tiny_fp8, tiny):
+    """Case 2's shape with e4m3 weights, oracles on ``fp8_reference_state``: the W8 instantiations of the 17..128-row kernels.  The
+    same rows against the bf16 model's oracles (the ``tiny`` fixture's) must fail."""
+    name, Ts, n = CASE2
+    out = _run(tiny_fp8, Ts, n, max_seq=128)
+    _judge_kv("fp8 case 2 (tiny, 117 rows)", tiny_fp8, Ts, n, *out[:4])
+    _judge_gaps("fp8 case 2 (tiny, 117 rows)", tiny_fp8, Ts, n, out[0], out[1], out[4], out[5])
+    _judge_quantisation_in_effect("fp8 case 2 (tiny, 117 rows)", tiny, Ts, n, *out[:4])
+
+
+def test_fp8_case3_twenty_slots(tiny_fp8):
+    """Case 3's shape with e4m3 weights: decode M > 16."""
+    Ts, n = tuple(3 + b % 5 for b in range(20)), 6
+    out = _run(tiny_fp8, Ts, n, max_seq=64)
+    _judge_kv("fp8 case 3 (tiny, 20 slots)", tiny_fp8, Ts, n, *out[:4])
+
+
+def test_fp8_case4_193_rows(m70_fp8):
+    """Case 4's shape with e4m3 weights: the 129..255-row kernel."""
+    name, Ts, n = CASE4
+    out = _run(m70_fp8, Ts, n, max_seq=192)
+    _judge_kv("fp8 case 4 (70m, 193 rows)", m70_fp8, Ts, n, *out[:4])
+    _judge_gaps("fp8 case 4 (70m, 193 rows)", m70_fp8, Ts, n, out[0], out[1], out[4], out[5])
+
+
+def test_fp8_case5_348_rows(m70_fp8):
+    """Case 5's shape with e4m3 weights: the >= 256-row kernels on the exact path (``use_fp8_prefill`` stays off)."""
+    Ts, n = (1, 2, 3, 5, 67, 130, 140), 4
+    out = _run(m70_fp8, Ts, n, max_seq=192)
+    _judge_kv("fp8 case 5 (70m, 348 rows)", m70_fp8, Ts, n, *out[:4])
+
+
+def test_150m_bf16(m150):
+    """The benchmark's shape (12 / 4 heads, dim 768, 10 layers) in bf16, T = 3, 40, 90 (133 rows), 4 frames."""
+    name, Ts, n = CASE150
+    out = _run(m150, Ts, n, max_seq=128)
+    _judge_kv("150m bf16 (133 rows)", m150, Ts, n, *out[:4])
+    _judge_gaps("150m bf16 (133 rows)", m150, Ts, n, out[0], out[1], out[4], out[5])
+
+
+def test_150m_fp8(m150_fp8, m150):
+    """BASELINE config 5's model: 150m with e4m3 weights, the same shape; against the bf16 model's oracles the rows must fail."""
+    name, Ts, n = CASE150
+    out = _run(m150_fp8, Ts, n, max_seq=128)
+    _judge_kv("150m fp8 (133 rows)", m150_fp8, Ts, n, *out[:4])
+    _judge_gaps("150m fp8 (133 rows)", m150_fp8, Ts, n, out[0], out[1], out[4], out[5])
+    _judge_quantisation_in_effect("150m fp8 (133 rows)", m150, Ts, n, *out[:4])
