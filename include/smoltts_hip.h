@@ -492,6 +492,31 @@ void smoltts_mimi_encoder_destroy(SmolttsMimiEncoder* e);
 /* Frames produced for n_samples of 24 kHz audio: ceil(ceil(n/960)/2). */
 int32_t smoltts_mimi_encode_frames(int32_t n_samples);
 size_t smoltts_mimi_encode_workspace_bytes(const SmolttsMimiEncoder* e, int32_t n_samples);
+/* Read-only map of the workspace smoltts_mimi_encode carves for n_samples (tests, diagnostics): row counts, and byte offsets
+ * from the workspace base of the fp32 channel-last buffers the chain leaves behind.  Stage i = 0..3 (ratios 4, 5, 6, 8) has
+ * C = 64 << i channels and T[i] rows; T[4] = the 25 Hz transformer positions, F = 12.5 Hz frames.  Launches nothing. */
+typedef struct SmolttsMimiEncLayout {
+  int32_t T[5];            /* rows entering stage i (T[0] = samples); T[4] = transformer positions */
+  int32_t extra[4];        /* stride-alignment rows of stage i's strided conv */
+  int32_t left[4];         /* zero rows in front of the data in yelu[i] (ratio, plus extra unless extra_right) */
+  int32_t F;               /* frames = ceil(T[4] / 2) */
+  int32_t ds_extra;        /* stride-alignment rows of the downsample conv */
+  int32_t ds_left;         /* edge rows in front of the data in ds */
+  uint64_t xraw[4];        /* [T[i]][C]: stage input x_i, raw (conv0 / the previous strided conv) */
+  uint64_t xelu[4];        /* [2 + T[i]][C]: ELU(x_i) behind 2 zero rows */
+  uint64_t helu[4];        /* [T[i]][C/2]: ELU(conv k3(ELU x_i)) */
+  uint64_t yelu[4];        /* [ratio + extra[i] + T[i]][C]: ELU(x_i + conv k1(h_i)) behind left[i] zero rows */
+  uint64_t zelu;           /* [2 + T[4]][1024]: ELU of the last strided conv behind 2 zero rows */
+  uint64_t kc;             /* [n_layers][8][T[4]][64]: K after RoPE, head dims in the kernel's interleaved-pair order */
+  uint64_t vc;             /* [n_layers][8][T[4]][64]: V */
+  uint64_t layer_stride;   /* bytes between two layers' K (or V) caches */
+  uint64_t ds;             /* [2 + ds_extra + T[4]][512]: transformer output behind ds_left edge rows */
+  uint64_t emb;            /* [F][512]: latents (unused when the call passed emb_dev) */
+  uint64_t res;            /* [F][256]: the acoustic group's residual after the last codebook */
+  uint64_t dots;           /* [F][2048]: residual . codebook rows of the last codebook */
+  uint64_t total;          /* == smoltts_mimi_encode_workspace_bytes */
+} SmolttsMimiEncLayout;
+int smoltts_mimi_encode_layout(const SmolttsMimiEncoder* e, int32_t n_samples, SmolttsMimiEncLayout* out);
 /* pcm_dev float [n_samples] -> codes_dev int32 [num_codebooks][frames] (row q = codebook q).
  * Optional outputs (NULL to skip): emb_dev float [frames][512] pre-quantisation latents; gap_dev float
  * [num_codebooks][frames] squared-distance gap between the chosen and the second-nearest entry. */

@@ -107,8 +107,13 @@ class MimiDecodeOracle:
         x1, x2 = x[..., : hd // 2], x[..., hd // 2 :]
         return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
 
-    def transformer(self, x: Tensor) -> Tensor:
-        """x (B, T, 512) -> (B, T, 512); causal (optionally windowed) self-attention."""
+    def _mm(self, x: Tensor, w: Tensor) -> Tensor:
+        """Every Linear of the transformer: activation x times weight w^T (a control oracle overrides it to degrade x)."""
+        return x @ w.T
+
+    def transformer(self, x: Tensor, kv: Optional[list] = None) -> Tensor:
+        """x (B, T, 512) -> (B, T, 512); causal (optionally windowed) self-attention.  ``kv``: a list that receives, per layer,
+        (K after RoPE, V), each (B, 8, T, 64) with the head dims in the checkpoint's half-split order."""
         B, T, D = x.shape
         H, hd = 8, 64
         pos = torch.arange(T)
@@ -120,16 +125,18 @@ class MimiDecodeOracle:
             p = f"decoder_transformer.layers.{li}."
             g = lambda k: self.st[p + k]
             h = F.layer_norm(x, (D,), g("input_layernorm.weight"), g("input_layernorm.bias"), 1e-5)
-            q = (h @ g("self_attn.q_proj.weight").T).view(B, T, H, hd).transpose(1, 2)
-            k = (h @ g("self_attn.k_proj.weight").T).view(B, T, H, hd).transpose(1, 2)
-            v = (h @ g("self_attn.v_proj.weight").T).view(B, T, H, hd).transpose(1, 2)
+            q = self._mm(h, g("self_attn.q_proj.weight")).view(B, T, H, hd).transpose(1, 2)
+            k = self._mm(h, g("self_attn.k_proj.weight")).view(B, T, H, hd).transpose(1, 2)
+            v = self._mm(h, g("self_attn.v_proj.weight")).view(B, T, H, hd).transpose(1, 2)
             q, k = self._rope_half(q, pos), self._rope_half(k, pos)
+            if kv is not None:
+                kv.append((k, v))
             s = (q @ k.transpose(-1, -2)) * (hd ** -0.5)
             s = s.masked_fill(~keep, float("-inf"))
             a = (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(B, T, D)
-            x = x + g("self_attn_layer_scale.scale") * (a @ g("self_attn.o_proj.weight").T)
+            x = x + g("self_attn_layer_scale.scale") * self._mm(a, g("self_attn.o_proj.weight"))
             h = F.layer_norm(x, (D,), g("post_attention_layernorm.weight"), g("post_attention_layernorm.bias"), 1e-5)
-            m = F.gelu(h @ g("mlp.fc1.weight").T) @ g("mlp.fc2.weight").T
+            m = self._mm(F.gelu(self._mm(h, g("mlp.fc1.weight"))), g("mlp.fc2.weight"))
             x = x + g("mlp_layer_scale.scale") * m
         return x
 
@@ -234,18 +241,56 @@ class MimiEncodeOracle:
     Pinned by tests/golden/mimi_enc_hf.npz (``transformers.MimiModel.encode`` on seeded weights).
     """
 
-    def __init__(self, state: Dict[str, Tensor], num_codebooks: int = 8, window: int = 0, extra_right: bool = False):
-        self.st = {k: v.float() for k, v in state.items()}
+    def __init__(self, state: Dict[str, Tensor], num_codebooks: int = 8, window: int = 0, extra_right: bool = False,
+                 dtype: torch.dtype = torch.float32, act=None):
+        """``dtype`` = torch.float64: the fp32 oracle's weights and codebook rows (divided in fp32, as the engine packs them),
+        upcast; the RoPE angles and every intermediate are float64.  ``act``: a function applied to the activation operand of
+        every conv and Linear (the CPU controls of the strict tests degrade it); None computes what the oracle always did."""
+        self.dt = dtype
+        self.act = act
+        st32 = {k: v.float() for k, v in state.items()}
+        self.st = {k: v.to(dtype) for k, v in st32.items()}
         self.nq = num_codebooks
         self.extra_right = extra_right
+        self._cb = {}
+        for grp, n in (("semantic", 1), ("acoustic", num_codebooks - 1)):
+            for i in range(n):
+                p = f"quantizer.{grp}_residual_vector_quantizer.layers.{i}.codebook."
+                self._cb[p] = (st32[p + "embed_sum"] / torch.clamp(st32[p + "cluster_usage"], min=1e-5)[:, None]).to(dtype)
         # the encoder transformer is the decoder's block with other weights: reuse that restatement
-        self._tr = MimiDecodeOracle({k.replace("encoder_transformer.", "decoder_transformer."): v for k, v in self.st.items()
-                                     if k.startswith("encoder_transformer.")}, num_codebooks, window)
+        self._tr = MimiDecodeOracle({k.replace("encoder_transformer.", "decoder_transformer."): v for k, v in st32.items()
+                                     if k.startswith("encoder_transformer.")}, num_codebooks, window, dtype)
+        if act is not None:
+            self._tr._mm = lambda x, w: act(x) @ w.T
+
+    def _a(self, x: Tensor) -> Tensor:
+        return x if self.act is None else self.act(x)
+
+    # -- the single ops, each on a given input (the local checks of the strict tests apply them to the engine's own buffers)
+    def conv(self, x: Tensor, key: str, stride: int = 1) -> Tensor:
+        """One padded conv of the SEANet encoder: x (B, Cin, T) -> (B, Cout, ceil(T / stride)); ``key`` as in ``encoder.layers.<key>``."""
+        g = lambda k: self.st["encoder.layers." + k]
+        return _pad_conv1d(self._a(x.to(self.dt)), g(key + ".conv.weight"), g(key + ".conv.bias"), stride, extra_right=self.extra_right)
+
+    def input_proj(self, emb: Tensor, grp: str) -> Tensor:
+        """The 1x1 ``input_proj`` of the ``semantic`` / ``acoustic`` group: emb (B, 512, F) -> residual rows (B * F, 256)."""
+        w = self.st[f"quantizer.{grp}_residual_vector_quantizer.input_proj.weight"]
+        return F.conv1d(self._a(emb.to(self.dt)), w).transpose(1, 2).reshape(emb.shape[0] * emb.shape[2], -1)
+
+    def codebook(self, q: int) -> Tensor:
+        """Rows (2048, 256) of codebook q (0 = semantic, 1.. = acoustic)."""
+        grp, i = ("semantic", 0) if q == 0 else ("acoustic", q - 1)
+        return self._cb[f"quantizer.{grp}_residual_vector_quantizer.layers.{i}.codebook."]
+
+    def distance_row(self, r: Tensor, q: int) -> Tensor:
+        """Squared distances |r|^2 + |e_j|^2 - 2 r.e_j (rvq.py:16-22 before its sqrt) of residual rows r (N, 256) to codebook q."""
+        cb = self.codebook(q)
+        r = r.to(self.dt)
+        return (r * r).sum(-1, keepdim=True) + (cb * cb).sum(-1)[None, :] - 2.0 * (self._a(r) @ cb.T)
 
     def seanet(self, x: Tensor) -> Tensor:
         """x (B, 1, L) -> (B, 512, ceil(L/960))."""
-        g = lambda k: self.st["encoder.layers." + k]
-        pc = lambda x, key, stride=1: _pad_conv1d(x, g(key + ".conv.weight"), g(key + ".conv.bias"), stride, extra_right=self.extra_right)
+        pc = self.conv
         x = pc(x, "0")
         li = 1
         for r in reversed(RATIOS):
@@ -257,17 +302,62 @@ class MimiEncodeOracle:
         return pc(F.elu(x), "14")
 
     def downsample(self, x: Tensor) -> Tensor:
-        return _pad_conv1d(x, self.st["downsample.conv.weight"], None, 2, mode="edge", extra_right=self.extra_right)
+        return _pad_conv1d(self._a(x.to(self.dt)), self.st["downsample.conv.weight"], None, 2, mode="edge", extra_right=self.extra_right)
 
     def embeddings(self, pcm: Tensor) -> Tensor:
         """Pre-quantisation latents (B, 512, F)."""
-        e = self.seanet(pcm.float())
+        e = self.seanet(pcm.to(self.dt))
         e = self._tr.transformer(e.transpose(1, 2)).transpose(1, 2)
         return self.downsample(e)
 
+    @torch.no_grad()
+    def stages(self, pcm: Tensor) -> Dict[str, Tensor]:
+        """``embeddings`` with every intermediate the engine materialises, channel-last (B, rows, C): "x0" (conv0 output); per SEANet
+        stage i = 0..3 "h{i}" = ELU(conv k3(ELU x_i)), "y{i}" = ELU(x_i + conv k1(h_i)) and "x{i+1}", the strided conv's raw
+        output; "seanet" (the final conv k3 = the transformer's input); per layer l "K{l}" (after RoPE) and "V{l}", (B, 8, T, 64)
+        in the checkpoint's half-split head-dim order; "tr" (the transformer's output); "emb" (B, F, 512) == ``embeddings``."""
+        out: Dict[str, Tensor] = {}
+        cl = lambda t: t.transpose(1, 2)
+        x = self.conv(pcm.to(self.dt), "0")
+        out["x0"] = cl(x)
+        li = 1
+        for i, r in enumerate(reversed(RATIOS)):
+            h = F.elu(self.conv(F.elu(x), f"{li}.block.1"))
+            y = F.elu(x + self.conv(h, f"{li}.block.3"))
+            x = self.conv(y, str(li + 2), r)
+            out[f"h{i}"], out[f"y{i}"], out[f"x{i + 1}"] = cl(h), cl(y), cl(x)
+            li += 3
+        e = self.conv(F.elu(x), "14")
+        out["seanet"] = cl(e)
+        kv: list = []
+        t = self._tr.transformer(cl(e), kv)
+        for l, (k, v) in enumerate(kv):
+            out[f"K{l}"], out[f"V{l}"] = k, v
+        out["tr"] = t
+        out["emb"] = cl(self.downsample(cl(t)))
+        return out
+
     def _codebook(self, prefix: str) -> Tensor:
-        es, cu = self.st[prefix + "embed_sum"], self.st[prefix + "cluster_usage"]
-        return es / torch.clamp(cu, min=1e-5)[:, None]
+        return self._cb[prefix]
+
+    @torch.no_grad()
+    def rvq_walk(self, emb: Tensor, codes: Tensor) -> Dict[str, Tensor]:
+        """Teacher-forced RVQ encode of emb (B, 512, F) along given codes (B, nq, F): for every (codebook, frame) the squared-distance
+        row "d2" (B, nq, F, 2048), its "argmin" and top-2 "gap" (B, nq, F), the residual "before" the pick and "after" the update
+        (B, nq, F, 256).  The update follows the GIVEN codes, so a codebook behind a differing pick is still judged."""
+        B, _, Fr = emb.shape
+        keys = ("d2", "argmin", "gap", "before", "after")
+        out = {k: [] for k in keys}
+        for grp, q0, n in (("semantic", 0, 1), ("acoustic", 1, self.nq - 1)):
+            r = self.input_proj(emb, grp)
+            for q in range(q0, q0 + n):
+                d2 = self.distance_row(r, q)
+                top2 = torch.topk(d2, 2, dim=-1, largest=False).values
+                out["before"].append(r.view(B, Fr, -1))
+                r = r - self.codebook(q)[codes[:, q].reshape(-1).long()]
+                out["d2"].append(d2.view(B, Fr, -1)); out["argmin"].append(d2.argmin(-1).view(B, Fr))
+                out["gap"].append((top2[:, 1] - top2[:, 0]).view(B, Fr)); out["after"].append(r.view(B, Fr, -1))
+        return {k: torch.stack(v, dim=1) for k, v in out.items()}
 
     def rvq_encode(self, emb: Tensor, return_margin: bool = False):
         """emb (B, 512, F) -> codes (B, nq, F) [, smallest best-vs-second distance gap seen]."""
@@ -275,7 +365,7 @@ class MimiEncodeOracle:
         out, min_gap = [], float("inf")
         for grp, n in (("semantic", 1), ("acoustic", self.nq - 1)):
             p = f"quantizer.{grp}_residual_vector_quantizer."
-            r = F.conv1d(emb, self.st[p + "input_proj.weight"]).transpose(1, 2).reshape(B * Fr, -1)  # rows (b, f)
+            r = F.conv1d(emb.to(self.dt), self.st[p + "input_proj.weight"]).transpose(1, 2).reshape(B * Fr, -1)  # rows (b, f)
             for i in range(n):
                 cb = self._codebook(p + f"layers.{i}.codebook.")
                 d2 = (r * r).sum(-1, keepdim=True) + (cb * cb).sum(-1)[None, :] - 2.0 * (r @ cb.T)

@@ -103,6 +103,13 @@ class MimiEncWeights(C.Structure):
                 ("in_proj", C.c_uint64 * 2), ("codebooks_t", C.c_uint64), ("codebooks", C.c_uint64), ("codebook_sq", C.c_uint64)]
 
 
+class MimiEncLayout(C.Structure):
+    _fields_ = [("T", C.c_int32 * 5), ("extra", C.c_int32 * 4), ("left", C.c_int32 * 4), ("F", C.c_int32), ("ds_extra", C.c_int32),
+                ("ds_left", C.c_int32), ("xraw", C.c_uint64 * 4), ("xelu", C.c_uint64 * 4), ("helu", C.c_uint64 * 4),
+                ("yelu", C.c_uint64 * 4), ("zelu", C.c_uint64), ("kc", C.c_uint64), ("vc", C.c_uint64), ("layer_stride", C.c_uint64),
+                ("ds", C.c_uint64), ("emb", C.c_uint64), ("res", C.c_uint64), ("dots", C.c_uint64), ("total", C.c_uint64)]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [
         ("w_dev", C.c_void_p), ("w_is_fp32", C.c_int32), ("x_dev", C.c_void_p), ("ldx", C.c_int64), ("x_bstride", C.c_int64),
@@ -141,7 +148,7 @@ class Gemm3Args(C.Structure):
 
 
 STRUCTS = (BlockWeights, LMConfig, LMWeights, SlotSampling, SlotFilters, PrefixHeader, MimiLayerWeights, MimiConv, MimiConfig,
-           MimiWeights, MimiEncConfig, MimiEncWeights, GemmArgs, PickArgs, Gemm3Args)
+           MimiWeights, MimiEncConfig, MimiEncWeights, MimiEncLayout, GemmArgs, PickArgs, Gemm3Args)
 
 # ------------------------------------------------------------------------------- signatures
 # name -> (restype, argument kinds).  Kinds: p = opaque handle, device pointer, host array or stream (c_void_p); i = int32_t;
@@ -195,6 +202,7 @@ SIGNATURES = {
     "smoltts_mimi_encoder_destroy": (None, "p"),
     "smoltts_mimi_encode_frames": (I32, "i"),
     "smoltts_mimi_encode_workspace_bytes": (SIZE, "p i"),
+    "smoltts_mimi_encode_layout": (INT, "p i MimiEncLayout*"),
     "smoltts_mimi_encode": (INT, "p p i p p p p z p"),
     "smoltts_resample_design": (INT, "i p i i* i* i*"),
     "smoltts_resampler_bytes": (SIZE, "i"),

@@ -33,6 +33,7 @@ struct Plan {
   float *xraw[NSTAGE], *xelu[NSTAGE], *helu[NSTAGE], *yelu[NSTAGE], *zelu;
   float *tx, *tn, *tq, *ta, *th, *kc, *vc, *ds, *emb, *res, *dots;
   int *row_pos, *row_slot;
+  size_t kv_layer;  // floats between two layers' K (or V) caches
   size_t total;
 };
 
@@ -53,8 +54,9 @@ void make_plan(Plan& p, int n_samples, int n_layers, bool extra_right, char* bas
   const size_t T4 = p.T[NSTAGE];
   p.zelu = take((2 + T4) * 1024);
   p.tx = take(T4 * D); p.tn = take(T4 * D); p.tq = take(T4 * D); p.ta = take(T4 * D); p.th = take(T4 * FF);
-  p.kc = take((size_t)n_layers * HEADS * T4 * 64);
-  p.vc = take((size_t)n_layers * HEADS * T4 * 64);
+  p.kv_layer = (size_t)HEADS * T4 * 64;
+  p.kc = take((size_t)n_layers * p.kv_layer);
+  p.vc = take((size_t)n_layers * p.kv_layer);
   p.F = ceil_div((int)T4, 2);
   p.ds_extra = p.F * 2 - (int)T4;
   p.ds_left = 2 + (extra_right ? 0 : p.ds_extra);
@@ -207,6 +209,28 @@ size_t smoltts_mimi_encode_workspace_bytes(const SmolttsMimiEncoder* e, int32_t 
   return p.total;
 }
 
+// The map of the workspace smoltts_mimi_encode carves for n_samples: the same make_plan over a stand-in base address, read as
+// byte offsets.  Host arithmetic only.
+int smoltts_mimi_encode_layout(const SmolttsMimiEncoder* e, int32_t n_samples, SmolttsMimiEncLayout* out) {
+  ST_REQUIRE(e && out, SMOLTTS_E_INVALID, "mimi_encode_layout: null argument");
+  ST_REQUIRE(n_samples > 0, SMOLTTS_E_INVALID, "mimi_encode_layout: empty signal");
+  char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);  // never dereferenced
+  Plan p;
+  make_plan(p, n_samples, e->cfg.n_layers, e->cfg.extra_right != 0, base);
+  auto off = [&](const float* q) { return (uint64_t)(reinterpret_cast<uintptr_t>(q) - reinterpret_cast<uintptr_t>(base)); };
+  memset(out, 0, sizeof(*out));
+  for (int i = 0; i <= NSTAGE; ++i) out->T[i] = p.T[i];
+  for (int i = 0; i < NSTAGE; ++i) {
+    out->extra[i] = p.extra[i]; out->left[i] = p.left[i];
+    out->xraw[i] = off(p.xraw[i]); out->xelu[i] = off(p.xelu[i]); out->helu[i] = off(p.helu[i]); out->yelu[i] = off(p.yelu[i]);
+  }
+  out->F = p.F; out->ds_extra = p.ds_extra; out->ds_left = p.ds_left;
+  out->zelu = off(p.zelu); out->kc = off(p.kc); out->vc = off(p.vc); out->layer_stride = (uint64_t)p.kv_layer * sizeof(float);
+  out->ds = off(p.ds); out->emb = off(p.emb); out->res = off(p.res); out->dots = off(p.dots);
+  out->total = (uint64_t)p.total;
+  return SMOLTTS_OK;
+}
+
 int smoltts_mimi_encode(SmolttsMimiEncoder* e, const float* pcm_dev, int32_t n_samples, int32_t* codes_dev, float* emb_dev,
                         float* gap_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
   ST_REQUIRE(e && pcm_dev && codes_dev && workspace_dev, SMOLTTS_E_INVALID, "mimi_encode: null argument");
@@ -269,7 +293,7 @@ int smoltts_mimi_encode(SmolttsMimiEncoder* e, const float* pcm_dev, int32_t n_s
   // 2. encoder transformer; its last layer writes behind the downsample conv's padding rows
   ST_TRY(launch_mimi_rows(T4, T4, 0, p.row_pos, p.row_slot, st));
   {
-    MimiTransformerBufs tb{p.tx, p.tn, p.tq, p.ta, p.th, p.kc, p.vc, (size_t)HEADS * T4 * 64, p.row_pos, p.row_slot};
+    MimiTransformerBufs tb{p.tx, p.tn, p.tq, p.ta, p.th, p.kc, p.vc, p.kv_layer, p.row_pos, p.row_slot};
     ST_TRY(run_mimi_transformer(A, e->w.layers, c.n_layers, (const float*)(A + e->w.rope), T4, c.window, tb, T4, T4,
                                 p.ds + (size_t)p.ds_left * D, 0, st));
   }

@@ -7,7 +7,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import packing
-from .abi import (MIMI_OPT_PRODUCTS, MIMI_OPT_STATELESS_UPSAMPLE, MimiConfig, MimiEncConfig, MimiEncWeights, MimiWeights, SmolttsError, check,
+from .abi import (MIMI_OPT_PRODUCTS, MIMI_OPT_STATELESS_UPSAMPLE, MimiConfig, MimiEncConfig, MimiEncLayout, MimiEncWeights, MimiWeights, SmolttsError, check,
                   load_library)
 from .device import ClosesOnDel, _alloc_slab, _require_gpu, current_stream_ptr, dptr
 
@@ -77,6 +77,7 @@ class MimiEncoder(ClosesOnDel):
               "smoltts_mimi_encoder_create")
         self.handle = h
         self._ws = None
+        self._last_n, self._last_emb = 0, None
 
     def frames(self, n_samples: int) -> int:
         return int(self.lib.smoltts_mimi_encode_frames(n_samples))
@@ -98,7 +99,48 @@ class MimiEncoder(ClosesOnDel):
         check(self.lib.smoltts_mimi_encode(self.handle, dptr(x), n, dptr(codes), dptr(emb) if return_aux else None,
                                            dptr(gap) if return_aux else None, dptr(self._ws), self._ws.numel(), current_stream_ptr()),
               "smoltts_mimi_encode")
+        self._last_n, self._last_emb = n, emb
         return (codes, emb, gap) if return_aux else codes
+
+    def layout(self, n_samples: int) -> MimiEncLayout:
+        """The map of the workspace an ``encode`` of ``n_samples`` carves (``smoltts_mimi_encode_layout``: rows and byte offsets)."""
+        lay = MimiEncLayout()
+        check(self.lib.smoltts_mimi_encode_layout(self.handle, int(n_samples), C.byref(lay)), "smoltts_mimi_encode_layout")
+        return lay
+
+    def stage_views(self, n_samples: int) -> Dict[str, torch.Tensor]:
+        """Named fp32 views into the workspace of the LAST ``encode`` call, which must have been one of ``n_samples`` (tests,
+        diagnostics): every buffer of ``SmolttsMimiEncLayout`` whole, halo and padding rows included, as [rows, channels] --
+        ``xraw{i}``, ``xelu{i}``, ``helu{i}``, ``yelu{i}`` (i = 0..3), ``zelu``, ``ds``, ``emb``, ``res``, ``dots`` -- and ``kc``,
+        ``vc`` as [n_layers, 8, positions, 64].  ``kc`` keeps the kernel's head-dim order (``packing._perm_heads``: the RoPE pair
+        (j, j + 32) of the checkpoint sits at (2j, 2j + 1)).  ``emb`` is the tensor ``return_aux`` handed out when the call had it
+        (the workspace's own copy stays zero then).  The views alias the workspace: the next ``encode`` overwrites them."""
+        lay = self.layout(n_samples)
+        if self._ws is None or self._last_n != n_samples or self._ws.numel() < lay.total:
+            raise SmolttsError(f"stage_views: the last encode on this encoder was of {self._last_n} samples, not {n_samples}")
+        ws = self._ws.view(torch.uint8)
+
+        def view(off: int, rows: int, cols: int) -> torch.Tensor:
+            return ws[off: off + 4 * rows * cols].view(torch.float32).view(rows, cols)
+
+        out: Dict[str, torch.Tensor] = {}
+        for i, r in enumerate((4, 5, 6, 8)):
+            c, t = 64 << i, lay.T[i]
+            out[f"xraw{i}"] = view(lay.xraw[i], t, c)
+            out[f"xelu{i}"] = view(lay.xelu[i], 2 + t, c)
+            out[f"helu{i}"] = view(lay.helu[i], t, c // 2)
+            out[f"yelu{i}"] = view(lay.yelu[i], r + lay.extra[i] + t, c)
+        t4, nl = lay.T[4], self.c_cfg.n_layers
+        out["zelu"] = view(lay.zelu, 2 + t4, 1024)
+        for name, off in (("kc", lay.kc), ("vc", lay.vc)):
+            if lay.layer_stride != 4 * 8 * t4 * 64:
+                raise SmolttsError(f"stage_views: layer stride {lay.layer_stride} bytes, expected {4 * 8 * t4 * 64}")
+            out[name] = view(off, nl * 8 * t4, 64).view(nl, 8, t4, 64)
+        out["ds"] = view(lay.ds, 2 + lay.ds_extra + t4, 512)
+        out["emb"] = self._last_emb if self._last_emb is not None else view(lay.emb, lay.F, 512)
+        out["res"] = view(lay.res, lay.F, 256)
+        out["dots"] = view(lay.dots, lay.F, 2048)
+        return out
 
     def close(self):
         if getattr(self, "handle", None):
