@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SMOLTTS_ABI_VERSION 6
+#define SMOLTTS_ABI_VERSION 7
 
 enum {
   SMOLTTS_OK = 0,
@@ -681,6 +681,54 @@ int smoltts_seam_chunk(SmolttsSeam* s, const float* pcm_dev, int64_t pcm_stride,
 
 /* Tests and tools: slot's state (n_in, judged, ec, head, open, lead, pause, flags) into state_host[8]; synchronises the stream. */
 int smoltts_seam_slot_state(SmolttsSeam* s, int32_t slot, int64_t* state_host, void* stream);
+
+/* ------------------------------------------------------------------------------ Trim
+ * Leading and trailing silence cut and pauses capped per request on the codec's 24 kHz fp32 PCM, first of the stages behind the
+ * codec and in front of the seam (smoltts_amd/csrc/trim.hip; the numpy model, matched bit for bit, is
+ * smoltts_amd/trim.py).  Blocks are the seam's: 240 samples counted from the segment's first sample, the last one of a segment
+ * may be partial.  A block is silent when max|x| < thr, compared in float32; a NaN is not silence.  A run is a maximal sequence
+ * of consecutive silent blocks, r its length in blocks.  Per segment: its flags (SMOLTTS_SEAM_FIRST / _FINAL; a plain stream
+ * is FIRST|FINAL), trim, and P, the pause cap in blocks (0: none, else 10..200).  Constants: HEAD_KEEP = 2, TAIL_KEEP = 10,
+ * HOLD = 200 blocks.  What is kept of a run, the first matching case applies:
+ *   1. trim, FIRST, and the run starts at block 0: its last min(r, HEAD_KEEP) blocks (this also covers an all-silent segment);
+ *   2. trim, FINAL, and the run reaches the segment's end: its first min(r, K) blocks, K = TAIL_KEEP when P == 0, else
+ *      min(TAIL_KEEP, ceil(P/2)); exception: when P == 0 and r - K > HOLD, its first r - HOLD blocks, so the tail never loses
+ *      more than 2 s;
+ *   3. P > 0 and r > P: its first ceil(P/2) and its last floor(P/2) blocks;
+ *   4. otherwise all of it.
+ * Non-silent blocks are always kept; the output is the kept blocks in order.  Every cut lies in samples below thr, so there are
+ * no fades, as in the seam.  The output does not depend on how a segment is cut into calls; a non-silent block leaves in the call
+ * that completes it, together with whatever was held in front of it; a slot holds at most HOLD blocks and a partial block. */
+typedef struct SmolttsTrim SmolttsTrim;
+
+/* Device slab of a trim stage for max_batch slots (256-byte aligned, caller-owned): two copies of each slot's state (counters and
+ * 48240 held samples).  Every slot starts off; create clears the slab synchronously. */
+size_t smoltts_trim_bytes(int32_t max_batch);
+int smoltts_trim_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, SmolttsTrim** out);
+void smoltts_trim_destroy(SmolttsTrim* t);
+/* Output samples per row that a call of n_in input samples needs (the held blocks released in front of them); 0 when n_in is
+ * negative or above 61440, the most one call takes. */
+size_t smoltts_trim_out_samples(int32_t n_in);
+
+/* Open a segment in each listed slot (host arrays): its flags (SMOLTTS_SEAM_FIRST / _FINAL; SMOLTTS_SEAM_OFF switches the slot
+ * off), whether cases 1 and 2 apply (trim_host, nonzero: yes), its pause cap P in blocks (0, or 10..200) and its threshold
+ * (0 < thr <= 1).  The other slots continue.  Stream-ordered. */
+int smoltts_trim_reset_slots(SmolttsTrim* t, const int32_t* slots_host, const int32_t* flags_host, const int32_t* trim_host,
+                             const int32_t* pause_host, const float* thr_host, int32_t n_slots, void* stream);
+
+/* One launch for slots [0, batch): slot b consumes valid_in_dev[b] (clamped to [0, n_in]; NULL = n_in) samples of pcm_dev float
+ * [batch][pcm_stride]; seg_end_dev[b] or last_dev[b] nonzero ends the slot's segment with them (either may be NULL; a run that
+ * `last` cuts short in a segment that is not FINAL is released by cases 3 and 4).  Slot b writes the samples that became final
+ * in this call to out_dev float [batch][out_stride] (out_stride >= smoltts_trim_out_samples(n_in)) and their number to
+ * counts_dev[b]; slots without an open segment write 0.  Calls on one trim stage must be ordered on one stream (the slot states
+ * alternate between their copies). */
+int smoltts_trim_chunk(SmolttsTrim* t, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
+                       const int32_t* valid_in_dev, const int32_t* seg_end_dev, const int32_t* last_dev, float* out_dev,
+                       int64_t out_stride, int32_t* counts_dev, void* stream);
+
+/* Tests and tools: slot's state (n_in, judged, emitted, held, dropped_head, dropped_pause, dropped_tail: samples; open) into
+ * state_host[8]; synchronises the stream. */
+int smoltts_trim_slot_state(SmolttsTrim* t, int32_t slot, int64_t* state_host, void* stream);
 
 /* ------------------------------------------------------------------------------ Loudness
  * Per-slot loudness normalisation of the codec's 24 kHz fp32 PCM by the ITU-R BS.1770-4 meter (smoltts_amd/csrc/loudness.hip,

@@ -67,6 +67,8 @@ class SmolTTS:
         self.verbose = verbose  # print the reference's per-call timing lines (lm/generate.py:187-214)
         self.last_sampling = None  # resolved RequestSampling list of the last call that was given sampling= (seeds included)
         self._seam = None  # stages.SeamJoiner of the blocking segmented calls (made on first use)
+        self._trim = None  # stages.SilenceTrimmer of the blocking calls that trim silence (made on first use)
+        self.last_trimmed_s = 0.0  # seconds of silence the last blocking call trimmed (trim_silence / max_pause_s)
         self.last_segments: list = []  # per segment of the last segmented call: text, prompt, codes, seed
         self.last_loudness_gain_db = None  # gain of the last call that was given loudness=
         self.last_stats: dict = {}  # timing of the last generate_codes / __call__ (BatchGenerator.stats + codec_ms)
@@ -166,7 +168,9 @@ class SmolTTS:
         return pcm
 
     def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None,
-                 speed: Optional[float] = None, segment=False, loudness: Optional[float] = None, watermark: Optional[bool] = None):
+                 speed: Optional[float] = None, segment=False, loudness: Optional[float] = None, watermark: Optional[bool] = None,
+                 trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
+                 silence_threshold_db: Optional[float] = None):
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
         (per-request temperature / min_p / seed, as in ``generate_codes``).  ``speed`` (0.25 to 4.0; None / 1.0: unchanged):
         the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
@@ -177,18 +181,23 @@ class SmolTTS:
         is measured on the GPU and one gain brings it to the target, capped where its peak would pass -1 dBFS (``loudness.py``),
         behind the seam join and in front of the stretch; ``last_loudness_gain_db`` is the gain applied.
         ``watermark`` (None: marked when the instance has a ``watermark``; True without one: ``ValueError``): the utterance gets
-        the instance's mark whole on the GPU, last: behind the seam join, the loudness gain and the stretch (``watermark.py``)."""
+        the instance's mark whole on the GPU, last: behind the seam join, the loudness gain and the stretch (``watermark.py``).
+        ``trim_silence`` (cut the leading and trailing silence), ``max_pause_s`` (0.1 to 2.0: cap the pauses) and
+        ``silence_threshold_db`` (-72 to -6 dBFS; default 2^-8): the codec's PCM is trimmed on the GPU first of all
+        (``trim.py``), each segment of a segmented text before the seam join; ``last_trimmed_s`` is what was cut."""
         from .request import parse_request
 
-        req = parse_request(input, speed=speed, segment=segment, loudness=loudness, watermark=watermark)  # a bad request is refused before any work
+        req = parse_request(input, speed=speed, segment=segment, loudness=loudness, watermark=watermark, trim_silence=trim_silence,
+                            max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db)  # a bad request is refused before any work
         marked = self._marks(req.watermark)
         voice = voice if voice is not None else "heart"
+        self.last_trimmed_s = 0.0
         if req.plan is not None:
-            pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling)
+            pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling, req)
         else:
             codes = self.generate_codes([input], [voice], generation_settings, speakers=None if speaker is None else [speaker],
                                         sampling=sampling)[0]
-            pcm = self.decode_codes(codes)
+            pcm = self._trimmed(self.decode_codes(codes), req)
         if req.loudness is not None:
             from .stages import loudness_normalize
             from .loudness import gain_db
@@ -204,6 +213,19 @@ class SmolTTS:
 
             pcm = watermark_embed(pcm, marked, self.lm.device)
         return pcm
+
+    def _trimmed(self, pcm, req, flags: int = 3):
+        """``pcm``, one segment with ``flags`` (default: a plain utterance, first and final), through the trim stage when
+        ``req`` asks for it; ``last_trimmed_s`` grows by what was cut."""
+        if not req.trims:
+            return pcm
+        from .stages import SilenceTrimmer, trim_pcm
+
+        if self._trim is None:
+            self._trim = SilenceTrimmer(self.lm.device, 1)
+        out = trim_pcm(pcm, flags, self.lm.device, req.trim_silence, req.pause_blocks, req.silence_thr, trimmer=self._trim)
+        self.last_trimmed_s += (pcm.size - out.size) / self.sampling_rate
+        return out
 
     def _marks(self, asked: Optional[bool]):
         """The ``watermark.Watermark`` of a request that asked ``asked`` (None: the instance's policy), or None: unmarked."""
@@ -246,7 +268,8 @@ class SmolTTS:
                reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None,
                speed: Optional[float] = None, container: Optional[str] = None, segment=False,
                loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
-               watermark: Optional[bool] = None) -> Iterator["np.ndarray"]:
+               watermark: Optional[bool] = None, trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
+               silence_threshold_db: Optional[float] = None) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -271,6 +294,9 @@ class SmolTTS:
         frame's samples still leave with the frame (``loudness.StreamState``).
         ``watermark`` (as in ``__call__``): the stream is marked on the GPU last of the float stages, behind the stretch and in
         front of the conversion and the framing; a segmented stream keeps one mark grid across its seams.
+        ``trim_silence`` / ``max_pause_s`` / ``silence_threshold_db`` (as in ``__call__``): the stream is trimmed on the GPU
+        first of its stages, segment by segment in front of the seam; a non-silent block leaves with the frame that completes
+        it, silence is held back until it is known whether it is kept (``trim.TrimState``).
         ``input`` may be an iterator or generator of strings (or UTF-8 ``bytes``, cut anywhere) in place of a string: text that is
         still being written.  It implies ``segment=True`` (or the options given), is cut by ``longform.IncrementalSplitter``
         and spoken segment after segment while the text is pulled: before segment k starts, just enough text is pulled to have
@@ -285,10 +311,11 @@ class SmolTTS:
         if not isinstance(input, (str, bytes)):
             yield from self._stream_incremental(iter(input), voice if voice is not None else "0", generation_settings, overlap,
                                                 reference_upsample, output_format, sampling, speed, container, segment, loudness,
-                                                loudness_start_gain_db, watermark)
+                                                loudness_start_gain_db, watermark, trim_silence, max_pause_s, silence_threshold_db)
             return
         req = parse_request(input, stream=True, output_format=output_format, speed=speed, container=container, segment=segment,
-                            loudness=loudness, loudness_start_gain_db=loudness_start_gain_db, watermark=watermark)
+                            loudness=loudness, loudness_start_gain_db=loudness_start_gain_db, watermark=watermark,
+                            trim_silence=trim_silence, max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db)
         marked = self._marks(req.watermark)
         voice = voice if voice is not None else "0"
         if req.plan is not None:
@@ -304,7 +331,7 @@ class SmolTTS:
         try:
             yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=req.output_format,
                                   speed_q=req.speed_q, container=req.container, loudness=req.loudness,
-                                  start_gain_db=req.start_gain_db, watermark=marked)
+                                  start_gain_db=req.start_gain_db, watermark=marked, trim=req.trim_route)
         finally:
             msess.close()
             sess.close()
@@ -354,25 +381,28 @@ class SmolTTS:
             yield (k, info[-1], settings, [samp]) if resolved is not None else (k, info[-1], samp, None)
         self.last_sampling = resolved  # (generate_prompt_codes sets it per segment)
 
-    def _call_segmented(self, plan, voice, speaker, generation_settings, sampling):
+    def _call_segmented(self, plan, voice, speaker, generation_settings, sampling, req):
+        from .seam import segment_flags
         from .stages import SeamJoiner, seam_join
 
         pcms = []
-        for _, seg, st_k, samp_k in self._segments(plan, voice, speaker, generation_settings, sampling):
+        for k, seg, st_k, samp_k in self._segments(plan, voice, speaker, generation_settings, sampling):
             seg["codes"] = self.generate_prompt_codes([seg["prompt"]], st_k, samp_k)[0]
-            pcms.append(self.decode_codes(seg["codes"]))
+            pcms.append(self._trimmed(self.decode_codes(seg["codes"]), req, segment_flags(k, len(plan.segs))))
         if self._seam is None:
             self._seam = SeamJoiner(self.lm.device, 1)
         return seam_join(pcms, plan.pauses, self.lm.device, lead=plan.lead, trail=plan.trail, joiner=self._seam)
 
     def _stream_incremental(self, texts, voice, generation_settings, overlap, reference_upsample, output_format, sampling, speed,
-                            container, segment, loudness, loudness_start_gain_db, watermark=None):
+                            container, segment, loudness, loudness_start_gain_db, watermark=None, trim_silence=None, max_pause_s=None,
+                            silence_threshold_db=None):
         """``stream`` of a text that ``texts`` yields in pieces: the segmented stream of a plan that grows as the text is pulled."""
         from .longform import FLUSH, GrowingPlan, IncrementalSplitter, segment_options
         from .request import parse_request
 
         req = parse_request("", stream=True, output_format=output_format, speed=speed, container=container, loudness=loudness,
-                            loudness_start_gain_db=loudness_start_gain_db, watermark=watermark)
+                            loudness_start_gain_db=loudness_start_gain_db, watermark=watermark, trim_silence=trim_silence,
+                            max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db)
         marked = self._marks(req.watermark)
         opts = segment_options(segment or True)
         plan, splitter = GrowingPlan(opts), IncrementalSplitter(opts)
@@ -409,7 +439,7 @@ class SmolTTS:
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
             conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container], [req.loudness], [req.start_gain_db],
-                             [marked is not None])
+                             [marked is not None], trim=None if req.trim_route is None else [req.trim_route])
             segments = self._segments(plan, voice, None, generation_settings, sampling)
             for k in range(1 << 30):
                 if pull(k) if pull is not None else k < len(plan.segs):

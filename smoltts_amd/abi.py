@@ -21,7 +21,7 @@ class SmolttsError(RuntimeError):
 
 
 # ------------------------------------------------------------------------------- constants (the header's names minus SMOLTTS_)
-ABI_VERSION = 6
+ABI_VERSION = 7
 OK, E_INVALID, E_HIP, E_STATE, E_CAPACITY = 0, -1, -2, -3, -4
 MAX_LAYERS, MAX_FAST_LAYERS, MIMI_MAX_LAYERS = 64, 16, 16
 KV_F32, KV_BF16 = 0, 1
@@ -232,6 +232,13 @@ SIGNATURES = {
     "smoltts_seam_reset_slots": (INT, "p p p p p i p"),
     "smoltts_seam_chunk": (INT, "p p q i i p p p i p q p p"),
     "smoltts_seam_slot_state": (INT, "p i p p"),
+    "smoltts_trim_bytes": (SIZE, "i"),
+    "smoltts_trim_create": (INT, "p z i p*"),
+    "smoltts_trim_destroy": (None, "p"),
+    "smoltts_trim_out_samples": (SIZE, "i"),
+    "smoltts_trim_reset_slots": (INT, "p p p p p p i p"),
+    "smoltts_trim_chunk": (INT, "p p q i i p p p p q p p"),
+    "smoltts_trim_slot_state": (INT, "p i p p"),
     "smoltts_loudness_bytes": (SIZE, "i"),
     "smoltts_loudness_table_doubles": (I32, ""),
     "smoltts_loudness_create": (INT, "p z i p i p*"),

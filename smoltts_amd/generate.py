@@ -228,7 +228,8 @@ def generate_blocking(model: LMEngine, prompt: np.ndarray, generation_settings: 
 def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bool = True, max_frames: Optional[int] = None,
                overlap: bool = True, output_format: Optional[str] = None, speed_q: Optional[int] = None,
                container: Optional[str] = None, conv: Optional[StreamConverter] = None, final: bool = True,
-               loudness: Optional[float] = None, start_gain_db: Optional[float] = None, watermark=None) -> Iterator[np.ndarray]:
+               loudness: Optional[float] = None, start_gain_db: Optional[float] = None, watermark=None,
+               trim: Optional[tuple] = None) -> Iterator[np.ndarray]:
     """One utterance in slot 0 of ``session`` -> one 1920-sample float32 chunk per generated frame, as the reference's
     ``SmolTTS.stream`` yields them (mlx_inference/src/smoltts_mlx/__init__.py:83-95: every frame of ``SingleBatchGenerator`` through
     ``codec.decode_step``), the terminating ``<|im_end|>`` frame included.
@@ -262,6 +263,10 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     ``watermark`` (a ``watermark.Watermark``; None: no launch): every frame's PCM gets the key's mark on the codec stream
     (``stages.Watermarker``), last of the float stages: behind the stretch, in front of the conversion and the framing.
 
+    ``trim`` ((trim the ends, the pause cap in blocks, the threshold or None), ``trim.py``; None: no launch): every frame's PCM
+    goes through the trim stage (``stages.SilenceTrimmer``) first of all; the stream is one segment, whose end is derived on the
+    device as for a speed.  A frame that completes no block that is kept yields nothing.
+
     ``conv``: the utterance is one segment of a long text (``longform``): the caller's ``StreamConverter(seam=True)``, with the
     stream's stages started in slot 0 and this segment opened (``start_segments``), converts it and is not closed here; the
     format, speed and container arguments are then ignored.  The end of the utterance, derived on the device, is the seam's end
@@ -285,7 +290,8 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     with torch.cuda.stream(codec_stream):
         msession.reset()
         if own:
-            conv.reset_slots([0], [output_format], [speed_q], [container], [loudness], [start_gain_db], [watermark is not None])
+            conv.reset_slots([0], [output_format], [speed_q], [container], [loudness], [start_gain_db], [watermark is not None],
+                             trim=None if trim is None else [trim])
     converted = conv.converts(0)
     ends_on_device, segmented = conv.ends([0])  # a stage must see the end of the stream / of the segment
     with torch.cuda.stream(lm_stream):

@@ -3,11 +3,12 @@ core): the checks and their ``ValueError`` messages live here once, and the fron
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Tuple
 
 from .formats import ENC_OFF, check_container, parse_stream_format
 from .longform import SegmentOptions, SegmentPlan, segment_options
 from .loudness import check_start_gain, check_target
+from .trim import pause_blocks, threshold
 from .tsm import parse_speed
 
 
@@ -22,14 +23,33 @@ class SpeechOptions:
     loudness: Optional[float] = None  # target in LUFS (loudness.py), None: the level is left as it is
     start_gain_db: float = 0.0        # a stream's first gain knot
     watermark: Optional[bool] = None  # mark the audio with the front end's key (watermark.py); None: the front end's policy
+    trim_silence: bool = False        # cut the leading and trailing silence (trim.py)
+    max_pause_s: Optional[float] = None           # cap the pauses at this length, None: pauses are left alone
+    silence_threshold_db: Optional[float] = None  # what counts as silence, in dBFS; None: the seam's 2^-8
+    pause_blocks: int = 0             # max_pause_s in blocks (0: no cap)
+    silence_thr: float = float(threshold(None))   # silence_threshold_db as a float32 amplitude
+
+    @property
+    def trims(self) -> bool:
+        """Whether the request goes through the trim stage at all."""
+        return self.trim_silence or self.pause_blocks > 0
+
+    @property
+    def trim_route(self) -> Optional[Tuple[bool, int, float]]:
+        """What ``StreamConverter.reset_slots`` takes for the request's slot (None: the slot does not trim)."""
+        return (self.trim_silence, self.pause_blocks, self.silence_thr) if self.trims else None
 
 
 def parse_request(text: str = "", stream: bool = False, output_format: Optional[str] = None, speed: Optional[float] = None,
                   container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
-                  loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None) -> SpeechOptions:
+                  loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
+                  trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
+                  silence_threshold_db: Optional[float] = None) -> SpeechOptions:
     """A request's options checked and normalised; ``ValueError`` for anything a front end refuses.  ``output_format`` and
     ``container`` apply to streaming requests only, as does ``loudness_start_gain_db``, which needs a ``loudness``.  ``watermark``: true, false, or None for the
-    front end's own policy (the key and the strength are the front end's: one key per stage)."""
+    front end's own policy (the key and the strength are the front end's: one key per stage).  ``trim_silence`` (true, false or
+    None: false), ``max_pause_s`` (0.1 to 2.0 seconds, None: no cap) and ``silence_threshold_db`` (-72 to -6 dBFS, which needs
+    one of the other two) are the trim stage's (trim.py)."""
     speed_q = parse_speed(speed)
     if output_format is not None:
         if not stream:
@@ -47,5 +67,16 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
         raise ValueError("loudness_start_gain_db applies to streaming requests with a loudness")
     if watermark is not None and not isinstance(watermark, bool):
         raise ValueError("watermark must be true, false or null")
+    if trim_silence is not None and not isinstance(trim_silence, bool):
+        raise ValueError("trim_silence must be true or false")
+    for name, v in (("max_pause_s", max_pause_s), ("silence_threshold_db", silence_threshold_db)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float))):
+            raise ValueError(f"{name} must be a number")
+    blocks = pause_blocks(max_pause_s)
+    if silence_threshold_db is not None and not (trim_silence or blocks):
+        raise ValueError("silence_threshold_db applies with trim_silence or max_pause_s")
     return SpeechOptions(output_format, None if speed_q is None else float(speed), speed_q, container, opts, plan, target,
-                         check_start_gain(loudness_start_gain_db), watermark)
+                         check_start_gain(loudness_start_gain_db), watermark, bool(trim_silence),
+                         None if max_pause_s is None else float(max_pause_s),
+                         None if silence_threshold_db is None else float(silence_threshold_db), blocks,
+                         float(threshold(silence_threshold_db)))

@@ -9,10 +9,11 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .abi import FLAC_F32, FLAC_OFF, FLAC_S16, SEAM_OFF
+from .abi import FLAC_F32, FLAC_OFF, FLAC_S16, SEAM_FINAL, SEAM_FIRST, SEAM_OFF
 from .device import upload
 from .formats import ENC_OFF, check_container, parse_stream_format
-from .stages import FlacEncoder, LoudnessNormalizer, Resampler, SeamJoiner, TimeStretcher, Watermarker
+from .seam import THRESH
+from .stages import FlacEncoder, LoudnessNormalizer, Resampler, SeamJoiner, SilenceTrimmer, TimeStretcher, Watermarker
 from .tsm import out_bound
 
 
@@ -20,6 +21,8 @@ STAGES = ("seam", "stretch", "resample", "flac")  # the stages every build has h
 LAUNCH_ORDER = ("seam", "loudness", "stretch", "resample", "flac")  # the stages of a pass, in launch order
 PASS_ORDER = ("seam", "loudness", "stretch", "watermark", "resample", "flac")  # LAUNCH_ORDER with the watermark: what a pass runs by
 FLOAT_STAGES = ("seam", "loudness", "stretch", "watermark")  # fp32 in, fp32 out: the stages behind read their rows
+TRIM_ORDER = ("trim",) + PASS_ORDER  # PASS_ORDER behind the silence trim: what a pass is planned by
+TRIM_FLOAT_STAGES = ("trim",) + FLOAT_STAGES
 
 
 @dataclass(frozen=True)
@@ -37,18 +40,26 @@ class SlotRoute:
     loudness: Optional[float] = None  # target in LUFS (None: the slot never enters the loudness stage)
     start_gain_db: float = 0.0        # its stream's first knot
     watermark_gain: float = 0.0       # 10^(strength_db / 20) (0: the slot never enters the watermark stage)
+    trim: bool = False                # its leading and trailing silence is trimmed
+    pause_blocks: int = 0             # its pauses are capped at this many blocks (0: not); neither: the slot never enters the trim stage
+    thr: float = float(THRESH)        # the silence threshold of its trim stage
 
     @cached_property
     def stages(self) -> Tuple[str, ...]:
         """The stages the slot goes through, in launch order."""
-        on = (self.segmented, self.loudness is not None, self.speed_q != 65536, self.watermark_gain > 0.0, self.enc != ENC_OFF, self.flac)
-        return tuple(s for s, o in zip(PASS_ORDER, on) if o)
+        on = (self.trims, self.segmented, self.loudness is not None, self.speed_q != 65536, self.watermark_gain > 0.0,
+              self.enc != ENC_OFF, self.flac)
+        return tuple(s for s, o in zip(TRIM_ORDER, on) if o)
+
+    @property
+    def trims(self) -> bool:
+        return self.trim or self.pause_blocks > 0
 
 
 class PassPlan(NamedTuple):
     stages: List[str]                 # the stages to launch, in order
     rows: Dict[str, List[int]]        # the live slots each of them serves
-    through: Dict[str, List[int]]     # float stage (seam, loudness, stretch, watermark) -> the live slots it does not serve that a later stage does
+    through: Dict[str, List[int]]     # float stage (trim, seam, loudness, stretch, watermark) -> the live slots it does not serve that a later stage does
     source: Dict[int, Optional[str]]  # live slot -> the last stage it goes through (None: its codec rows are its output)
     host: List[str]                   # the stages whose outputs are copied to the host: the sources of the live slots
     routes: Dict[int, SlotRoute]      # live slot -> its route when planned
@@ -56,8 +67,8 @@ class PassPlan(NamedTuple):
 
 def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
     """The plan of one converter pass over the live slots' routes (``{slot: SlotRoute}``, in slot order); no device involved."""
-    rows = {s: [] for s in PASS_ORDER}
-    through = {s: [] for s in FLOAT_STAGES}
+    rows = {s: [] for s in TRIM_ORDER}
+    through = {s: [] for s in TRIM_FLOAT_STAGES}
     source = {}
     for b, r in routes.items():
         path = r.stages
@@ -65,16 +76,16 @@ def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
         for s in path:
             rows[s].append(b)
         for s in through:
-            if path and s not in path and PASS_ORDER.index(path[-1]) > PASS_ORDER.index(s):
+            if path and s not in path and TRIM_ORDER.index(path[-1]) > TRIM_ORDER.index(s):
                 through[s].append(b)
-    stages = [s for s in PASS_ORDER if rows[s]]
+    stages = [s for s in TRIM_ORDER if rows[s]]
     return PassPlan(stages, {s: rows[s] for s in stages}, {s: through[s] for s in through if rows[s]}, source,
                     [s for s in stages if s in source.values()], routes)
 
 
 class StreamConverter:
-    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``PASS_ORDER``): a
-    segmented slot (``start_segments``) is joined by the seam stage (``SeamJoiner``), a slot with a speed is time-stretched
+    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``TRIM_ORDER``): a
+    slot that trims silence goes through the trim stage first (``SilenceTrimmer``), segment by segment, a segmented slot (``start_segments``) is joined by the seam stage (``SeamJoiner``), a slot with a speed is time-stretched
     (``TimeStretcher``), a marked slot gets the watermark of the converter's key last of the float stages (``Watermarker``:
     behind the stretch, so that a speed does not rescale the chips), a slot with an output format is converted (``Resampler``), and a slot with a FLAC container is framed
     (``FlacEncoder``, from the resampler's int16, or from the float32 at 24 kHz); each stage reads the output of the one in
@@ -90,16 +101,19 @@ class StreamConverter:
         self.fl: Optional[FlacEncoder] = None
         self.sj: Optional[SeamJoiner] = SeamJoiner(device, max_batch) if seam else None
         self.ln: Optional[LoudnessNormalizer] = None
+        self.tr: Optional[SilenceTrimmer] = None
         self.routes = [SlotRoute()] * max_batch
         self._plan: Optional[PassPlan] = None  # the last pass's plan
 
     def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]],
                     containers: Optional[Sequence[Optional[str]]] = None, loudness: Optional[Sequence[Optional[float]]] = None,
-                    start_gain_db: Optional[Sequence[Optional[float]]] = None, watermark: Optional[Sequence[bool]] = None) -> None:
+                    start_gain_db: Optional[Sequence[Optional[float]]] = None, watermark: Optional[Sequence[bool]] = None,
+                    trim: Optional[Sequence[Optional[tuple]]] = None) -> None:
         """Start new streams in ``slots`` on the current stream: ``formats[i]`` an ``output_format`` (None / ``pcm_24000``:
         float32), ``speed_q[i]`` a Q16 speed (None / 65536: none), ``containers[i]`` None or ``"flac"`` (FLAC frames of the
         slot's 16-bit samples at its rate), ``loudness[i]`` a target in LUFS (None: none) reached from ``start_gain_db[i]``,
-        ``watermark[i]`` true for a slot that gets the converter's watermark.  A slot with none of them is switched off."""
+        ``watermark[i]`` true for a slot that gets the converter's watermark, ``trim[i]`` None or (trim the ends, the pause cap
+        in blocks, the threshold or None) of a slot that trims silence.  A slot with none of them is switched off."""
         if not slots:
             return
         formats = [f or "pcm_24000" for f in formats]
@@ -107,12 +121,19 @@ class StreamConverter:
         none = [None] * len(slots)
         if watermark is not None and any(watermark) and self.watermark is None:
             raise ValueError("a slot asks for a watermark, and the converter has no key")
-        for b, f, q, c, lt, sg, wm in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none,
-                                          watermark or none):
+        for b, f, q, c, lt, sg, wm, tr in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none,
+                                              watermark or none, trim or none):
             rate, enc = parse_stream_format(f)
             flac = check_container(c, f) is not None
             routes.append(SlotRoute(rate, enc, q or 65536, flac, segmented=False, gen=self.routes[b].gen + 1, head_owed=flac,
-                                    loudness=lt, start_gain_db=sg or 0.0, watermark_gain=self.watermark.gain if wm else 0.0))
+                                    loudness=lt, start_gain_db=sg or 0.0, watermark_gain=self.watermark.gain if wm else 0.0,
+                                    **({} if tr is None else {"trim": bool(tr[0]), "pause_blocks": int(tr[1]),
+                                                              "thr": float(THRESH if tr[2] is None else tr[2])})))
+        if self.tr is None and any(r.trims for r in routes):
+            self.tr = SilenceTrimmer(self.device, self.B)
+        if self.tr is not None:  # (a plain stream is one segment, the first and the last)
+            self.tr.start_segments(slots, [SEAM_FIRST | SEAM_FINAL if r.trims else SEAM_OFF for r in routes], [r.trim for r in routes],
+                                   [r.pause_blocks for r in routes], [r.thr for r in routes])
         if self.ln is None and any(r.loudness is not None for r in routes):
             self.ln = LoudnessNormalizer(self.device, self.B)
         if self.ln is not None:
@@ -142,7 +163,12 @@ class StreamConverter:
     def start_segments(self, slots: Sequence[int], pauses: Sequence[int], flags: Sequence[int],
                        leads: Optional[Sequence[int]] = None) -> None:
         """Open the next segment of the segmented streams in ``slots`` (``SeamJoiner.start_segments``), after ``reset_slots``
-        started the streams; the other stages' state is kept."""
+        started the streams; the other stages' state is kept.  The trim stage opens the segment of its slots with the same flags."""
+        own = [(b, int(f) & (SEAM_FIRST | SEAM_FINAL)) for b, f in zip(slots, flags) if self.routes[b].trims and not int(f) & SEAM_OFF]
+        if own:
+            rs = [self.routes[b] for b, _ in own]
+            self.tr.start_segments([b for b, _ in own], [f for _, f in own], [r.trim for r in rs], [r.pause_blocks for r in rs],
+                                   [r.thr for r in rs])
         if self.sj is None:
             self.sj = SeamJoiner(self.device, self.B)
         self.sj.start_segments(slots, pauses, flags, leads)
@@ -161,10 +187,10 @@ class StreamConverter:
         return p
 
     def ends(self, slots: Sequence[int]):
-        """The end markers a pass over ``slots`` needs: (``last``: some slot has a speed, FLAC or segments; ``seg_end``: some
-        slot has segments)."""
+        """The end markers a pass over ``slots`` needs: (``last``: some slot has a speed, FLAC, segments or a trim; ``seg_end``:
+        some slot has segments or a trim)."""
         stages = self.plan(slots).stages
-        return any(s in stages for s in ("seam", "stretch", "flac")), "seam" in stages
+        return any(s in stages for s in ("trim", "seam", "stretch", "flac")), "seam" in stages or "trim" in stages
 
     def _through(self, plan: PassPlan, stage: str, out: torch.Tensor, counts: torch.Tensor, pcm: torch.Tensor, n_in: int,
                  valid: torch.Tensor) -> torch.Tensor:
@@ -190,6 +216,10 @@ class StreamConverter:
         if not plan.stages:
             return None
         batch, outs = pcm.shape[0], {}
+        if "trim" in plan.stages:
+            out, counts = outs["trim"] = self.tr.new_outputs(batch, n_in)
+            self.tr.chunk(pcm, n_in, out, counts, valid=valid, seg_end=seg_end, last=last)
+            valid, pcm, n_in = self._through(plan, "trim", out, counts, pcm, n_in, valid), out, out.shape[1]
         if "seam" in plan.stages:  # (each float stage's rows, counts and width are what the stages behind it read)
             out, counts = outs["seam"] = self.sj.new_outputs(batch, n_in)
             self.sj.chunk(pcm, n_in, out, counts, valid=valid, seg_end=seg_end, last=last)
@@ -216,10 +246,10 @@ class StreamConverter:
         return StreamPass(self, {s: outs[s] for s in plan.host}, plan)
 
     def close(self):
-        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln, self.wm):
+        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln, self.wm, self.tr):
             if stage is not None:
                 stage.close()
-        self.rs = self.ts = self.fl = self.sj = self.ln = self.wm = None
+        self.rs = self.ts = self.fl = self.sj = self.ln = self.wm = self.tr = None
 
 
 class StreamPass:
@@ -243,7 +273,7 @@ class StreamPass:
 
     def chunk(self, b: int, last: bool) -> np.ndarray:
         """Slot ``b``'s chunk from its source stage: its FLAC frames as uint8 (behind the stream header on the stream's first
-        chunk), its converted samples (with the resampler's tail when ``last``), or the stretched / joined float32."""
+        chunk), its converted samples (with the resampler's tail when ``last``), or the stretched / joined / trimmed float32."""
         route, source = self.plan.routes[b], self.plan.source[b]
         out, counts = (t.numpy() for t in self.host[source])
         if source == "flac":

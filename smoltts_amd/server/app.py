@@ -63,6 +63,21 @@ class TTSCore:
         with self._voice_lock:
             return str(voice) in self.voices
 
+    def _trim_kw(self, body) -> dict:
+        """The trim options of a request: the body's ``trim_silence`` / ``max_pause_s`` where it names them (null: off), else the
+        server's settings, and the body's ``silence_threshold_db``; only those that are on, so that the model sees the calls it
+        saw before when none is."""
+        on, pause = bool(self._setting("trim_silence", False)), self._setting("max_pause_s", None)
+        thr = None
+        if body is not None and hasattr(body, "trim_fields"):
+            on, pause, thr = body.trim_fields(on, pause)
+        kw = {"trim_silence": True} if on else {}
+        if pause is not None:
+            kw["max_pause_s"] = pause
+        if thr is not None:
+            kw["silence_threshold_db"] = thr
+        return kw
+
     def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False, voice=None) -> Tuple[dict, int]:
         """(kwargs, segments): ``{"speed": speed}`` for a speed other than 1, ``{"segment": options}`` in ``long_text="segment"``
         mode and ``{"loudness": target}`` for a ``LoudnessFields`` body (or the server's ``loudness`` setting) that names one,
@@ -78,8 +93,10 @@ class TTSCore:
                 raise ValueError(f"input has {len(text)} characters; max_input_chars is {limit}")
             seg = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
         target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
-        p = parse_request(text, stream=stream, speed=speed, segment=seg, loudness=target, loudness_start_gain_db=start)
+        trim = self._trim_kw(loudness)
+        p = parse_request(text, stream=stream, speed=speed, segment=seg, loudness=target, loudness_start_gain_db=start, **trim)
         kw = {} if p.speed is None else {"speed": p.speed}
+        kw.update(trim)
         if p.loudness is not None:
             kw["loudness"] = p.loudness
             if start is not None:
@@ -191,11 +208,15 @@ class TTSCore:
                 used = getattr(req, "sampling", None)
                 pcm = np.concatenate(list(self.scheduler.iter_chunks(req)) or [np.zeros(0, np.float32)])
                 gain = getattr(req, "loudness_gain_db", None)
+                cut = getattr(req, "trimmed_s", 0.0)
             else:
                 used = self._model_sampling(sampling)
                 kw = {"sampling": used} if used is not None else {}
                 pcm = np.asarray(self.model(input_text, str(voice), **kw, **sp)).flatten()
                 gain = getattr(self.model, "last_loudness_gain_db", None)
+                cut = getattr(self.model, "last_trimmed_s", 0.0)
+            if info is not None and ("trim_silence" in sp or "max_pause_s" in sp):
+                info["trimmed_ms"] = 1e3 * float(cut or 0.0)
             if info is not None and "loudness" in sp:
                 info["loudness_gain_db"] = gain
         except ValueError as e:  # a request the engine refuses (e.g. a text too long for max_seq_len): the client's fault, not a 500
@@ -237,8 +258,10 @@ class TTSCore:
         if container is not None:
             kw["container"] = container
         target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
-        p = parse_request("", stream=True, speed=speed, loudness=target, loudness_start_gain_db=start, **kw)
+        trim = self._trim_kw(loudness)
+        p = parse_request("", stream=True, speed=speed, loudness=target, loudness_start_gain_db=start, **kw, **trim)
         sp = {} if p.speed is None else {"speed": p.speed}
+        sp.update(trim)
         if p.loudness is not None:
             sp["loudness"] = p.loudness
             if start is not None:
@@ -321,6 +344,11 @@ def _gain_headers(info: dict) -> dict:
     return {} if g is None else {"X-Loudness-Gain-Db": f"{g:.2f}"}
 
 
+def _trim_headers(info: dict) -> dict:
+    t = info.get("trimmed_ms")
+    return {} if t is None else {"X-Silence-Trimmed-Ms": f"{t:.0f}"}
+
+
 def _mark_headers(info: dict) -> dict:
     return {"X-Watermark": "1"} if info.get("watermark") else {}
 
@@ -360,6 +388,18 @@ class LoudnessFields(BaseModel):
     ``X-Loudness-Gain-Db``.  ``loudness_start_gain_db`` (streams only, within +-20): the gain a stream starts from."""
     loudness: Optional[float] = Field(default=None, allow_inf_nan=False)
     loudness_start_gain_db: Optional[float] = Field(default=None, allow_inf_nan=False)
+    # Silence trimming (extension; trim.py, on the GPU first of the stages): ``trim_silence`` cuts the leading and trailing
+    # silence, ``max_pause_s`` (0.1 to 2.0, 400 otherwise) caps the pauses; omitted: the server's ``trim_silence`` / ``max_pause_s``
+    # settings; null: off.  ``silence_threshold_db`` (-72 to -6 dBFS, default 2^-8) needs one of the two.  A blocking response
+    # carries ``X-Silence-Trimmed-Ms``.
+    trim_silence: Optional[bool] = Field(default=None)
+    max_pause_s: Optional[float] = Field(default=None, allow_inf_nan=False)
+    silence_threshold_db: Optional[float] = Field(default=None, allow_inf_nan=False)
+
+    def trim_fields(self, default_trim: bool, default_pause):
+        """(trim the ends, the pause cap or None, the threshold or None): the body's fields where it names them, else the defaults."""
+        return (bool(self.trim_silence) if "trim_silence" in self.model_fields_set else default_trim,
+                self.max_pause_s if "max_pause_s" in self.model_fields_set else default_pause, self.silence_threshold_db)
 
     def resolve(self, default):
         """(target or None, start gain or None): the body's field where it names one (null: off), else the server's default."""
@@ -445,7 +485,7 @@ def openai_speech(item: SpeechRequest, http_request: Request):
     audio, media_type, seed = core.generate_audio(item.input, item.voice, item.response_format + "_24000", sampling=item.request_sampling(),
                                                   speed=item.speed, loudness=item, info=info)
     return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed),
-                                                           **_gain_headers(info), **_mark_headers(info)})
+                                                           **_gain_headers(info), **_mark_headers(info), **_trim_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}")
@@ -458,7 +498,8 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
                                                     loudness=item, info=info)
     return Response(content=content, media_type=media_type, headers={
         "Content-Disposition": f'attachment; filename="elevenlabs_speech.{fmt.split("_")[0]}"',
-        "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed), **_gain_headers(info), **_mark_headers(info)})
+        "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed), **_gain_headers(info), **_mark_headers(info),
+        **_trim_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}/stream")

@@ -32,6 +32,7 @@ class _PoolRequest:
     closed: bool = False
     sampling: object = None  # config.RequestSampling as sent to the worker (seed resolved here), or None
     loudness_gain_db: Optional[float] = None  # a blocking request with a loudness: the gain applied (known at its end)
+    trimmed_s: float = 0.0  # a blocking request that trims silence: the seconds cut (known at its end)
     watermark: bool = False  # the audio carries the workers' watermark
 
 
@@ -97,7 +98,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
         try:
             for chunk in sched.iter_chunks(req):
                 res_q.put((rid, "chunk", np.ascontiguousarray(chunk)))  # float32, or int16 / uint8 for a streamed output_format
-            res_q.put((rid, "end", getattr(req, "loudness_gain_db", None)))
+            res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0))))
         except Exception as e:
             res_q.put((rid, "error", (type(e).__name__, str(e))))
         finally:
@@ -240,11 +241,14 @@ class GpuPool:
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
                container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
-               loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None) -> _PoolRequest:
+               loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
+               trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
+               silence_threshold_db: Optional[float] = None) -> _PoolRequest:
         """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
         from ..request import parse_request
 
-        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark)  # refused here, before a worker sees it
+        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
+                          trim_silence, max_pause_s, silence_threshold_db)  # refused here, before a worker sees it
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
         req = self._new_request(sampling)
@@ -253,7 +257,9 @@ class GpuPool:
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
         extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
                                    ("container", p.container), ("segment", p.segment), ("loudness", p.loudness),
-                                   ("loudness_start_gain_db", loudness_start_gain_db), ("watermark", p.watermark)) if v is not None}
+                                   ("loudness_start_gain_db", loudness_start_gain_db), ("watermark", p.watermark),
+                                   ("trim_silence", p.trim_silence or None), ("max_pause_s", p.max_pause_s),
+                                   ("silence_threshold_db", p.silence_threshold_db)) if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
@@ -261,14 +267,16 @@ class GpuPool:
                            sampling=None, speed: Optional[float] = None, container: Optional[str] = None, segment=True,
                            loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
                            idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
-                           watermark: Optional[bool] = None) -> _PoolIncrementalRequest:
+                           watermark: Optional[bool] = None, trim_silence: Optional[bool] = None,
+                           max_pause_s: Optional[float] = None, silence_threshold_db: Optional[float] = None) -> _PoolIncrementalRequest:
         """As ``BatchScheduler.submit_incremental``: the request lives in one slot of one worker, and ``feed`` / ``flush`` /
         ``close`` / ``cancel`` of the handle go to that worker over its queue, in the order they were called.  Text the worker
         refuses (a bad break tag) ends the stream with that ``ValueError`` instead of raising from ``feed``."""
         from ..longform import segment_options
         from ..request import parse_request
 
-        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark)
+        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark,
+                          trim_silence, max_pause_s, silence_threshold_db)
         opts = segment_options(True if segment is None or segment is False else segment)
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
@@ -277,7 +285,9 @@ class GpuPool:
         extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
                                    ("container", p.container), ("segment", opts), ("loudness", p.loudness),
                                    ("loudness_start_gain_db", loudness_start_gain_db), ("idle_timeout_s", idle_timeout_s),
-                                   ("flush_after_s", flush_after_s), ("watermark", p.watermark)) if v is not None}
+                                   ("flush_after_s", flush_after_s), ("watermark", p.watermark),
+                                   ("trim_silence", p.trim_silence or None), ("max_pause_s", p.max_pause_s),
+                                   ("silence_threshold_db", p.silence_threshold_db)) if v is not None}
         self._req_qs[req.worker].put(("submit_incremental", req.rid, voice, max_new_tokens, extra))
         return req
 
@@ -481,7 +491,7 @@ class GpuPool:
                 if not req.cancelled:
                     req.out.put(payload)
             elif kind == "end":
-                req.loudness_gain_db = payload
+                req.loudness_gain_db, req.trimmed_s = payload
                 self._finish(req, None)
             elif kind == "result":  # a registry message's answer
                 self._finish(req, ("result", payload))

@@ -63,6 +63,8 @@ class _Request:
     loudness_gain_db: Optional[float] = None  # blocking: the gain that was applied (set before the audio goes out)
     inc: Optional["_Incremental"] = None  # a stream whose text is fed in pieces (submit_incremental)
     watermark: bool = False   # the audio gets the scheduler's watermark: a stream in its codec pass, a blocking utterance whole, last
+    trim: Optional[tuple] = None  # (trim the ends, the pause cap in blocks, the threshold) of a request that trims silence (trim.py)
+    trimmed_s: float = 0.0    # blocking: the seconds of silence that were cut (set before the audio goes out)
 
 
 @dataclass
@@ -255,6 +257,7 @@ class BatchScheduler:
         self._incs: List[_Request] = []         # the incremental requests alive (worker side)
         self._inc_new: "queue.Queue[_Request]" = queue.Queue()  # ... and those the worker has not seen yet
         self._block_seam = None                 # seam stage of the blocking segmented requests (stages.SeamJoiner, 1 slot)
+        self._block_trim = None                 # trim stage of the blocking requests that trim silence (stages.SilenceTrimmer, 1 slot)
         self._dead: Optional[Exception] = None  # why the worker stopped
         self._draining = False
         self._held: Optional[_Request] = None   # next in line, waiting for room in a prefill call
@@ -271,7 +274,9 @@ class BatchScheduler:
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
                output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
                container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
-               loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None) -> _Request:
+               loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
+               trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
+               silence_threshold_db: Optional[float] = None) -> _Request:
         """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
         in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
@@ -292,11 +297,17 @@ class BatchScheduler:
         given one gain (``request.loudness_gain_db``), behind the seam join and in front of the stretch.
         ``watermark`` (None: marked when the scheduler has a key; True without a key: ``ValueError``): the audio carries the
         scheduler's watermark (watermark.py), added on the GPU last of the float stages: a stream in its codec pass behind the
-        stretch, a blocking utterance whole behind everything else.  ``request.watermark`` says whether it was."""
+        stretch, a blocking utterance whole behind everything else.  ``request.watermark`` says whether it was.
+        ``trim_silence`` (cut the leading and trailing silence), ``max_pause_s`` (0.1 to 2.0: cap the pauses),
+        ``silence_threshold_db`` (-72 to -6 dBFS; default 2^-8; it needs one of the other two): silence trimming on the GPU
+        (trim.py), first of the stages: a stream in its codec pass, segment by segment in front of the seam; a blocking
+        utterance whole, each segment before the seam join (``request.trimmed_s`` is what was cut)."""
         from ..config import RequestSampling
         from ..request import parse_request
 
-        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark)
+        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
+                          trim_silence, max_pause_s, silence_threshold_db)
+        self._check_trim(p)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         if self._dead is not None:  # the worker is gone (engine failure or close): nobody would ever answer
             raise RuntimeError(f"scheduler is not running: {self._dead}")
@@ -305,12 +316,18 @@ class BatchScheduler:
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
                        output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=p.speed_q,
                        container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None,
-                       loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark))
+                       loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark), trim=p.trim_route)
         self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
             self._end(req, RuntimeError(f"scheduler is not running: {self._dead}"))
         return req
+
+    def _check_trim(self, p) -> None:
+        from ..trim import MAX_CALL
+
+        if p.trims and self.tick * 1920 > MAX_CALL:
+            raise ValueError(f"silence trimming takes at most {MAX_CALL // 1920} frames a tick")
 
     def _marks(self, asked: Optional[bool]) -> bool:
         """Whether a request that asked ``asked`` is marked: the scheduler's policy when it did not say."""
@@ -322,7 +339,8 @@ class BatchScheduler:
                            sampling=None, speed: Optional[float] = None, container: Optional[str] = None, segment=True,
                            loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
                            idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
-                           watermark: Optional[bool] = None) -> IncrementalRequest:
+                           watermark: Optional[bool] = None, trim_silence: Optional[bool] = None,
+                           max_pause_s: Optional[float] = None, silence_threshold_db: Optional[float] = None) -> IncrementalRequest:
         """A stream whose text is not known yet: ``request.feed(text)`` as it arrives, ``request.close()`` at its end, the
         chunks by iterating the request (or ``iter_chunks``).  The options are those of ``submit(stream=True, segment=...)``
         (``segment``: True, a dict or a ``SegmentOptions``; it cannot be off).
@@ -351,7 +369,9 @@ class BatchScheduler:
         from ..longform import GrowingPlan, IncrementalSplitter, segment_options
         from ..request import parse_request
 
-        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark)
+        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark,
+                          trim_silence, max_pause_s, silence_threshold_db)
+        self._check_trim(p)
         opts = segment_options(True if segment is None or segment is False else segment)
         if not float(idle_timeout_s) > 0.0 or (flush_after_s is not None and not float(flush_after_s) > 0.0):
             raise ValueError("idle_timeout_s and flush_after_s must be positive")
@@ -361,7 +381,8 @@ class BatchScheduler:
         req = IncrementalRequest("", voice, True, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
                                  output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice),
                                  speed_q=p.speed_q, container=p.container, seg=_Segmented(GrowingPlan(opts), resolved),
-                                 loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark), sched=self,
+                                 loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark),
+                                 trim=p.trim_route, sched=self,
                                  inc=_Incremental(IncrementalSplitter(opts), float(idle_timeout_s),
                                                   None if flush_after_s is None else float(flush_after_s),
                                                   last_input=time.monotonic()))
@@ -473,7 +494,7 @@ class BatchScheduler:
         self._stop.set()
         self._wake.set()
         self._thread.join(timeout=30)
-        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch", "_block_seam"):
+        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch", "_block_seam", "_block_trim"):
             if getattr(self, name) is not None:
                 getattr(self, name).close()
                 setattr(self, name, None)
@@ -886,7 +907,8 @@ class BatchScheduler:
                 self._stream_conv.reset_slots([r.slot for r in fresh], [r.output_format for r in fresh],
                                               [r.speed_q for r in fresh], [r.container for r in fresh],
                                               [r.loudness for r in fresh], [r.start_gain_db for r in fresh],
-                                              [r.watermark for r in fresh] if self.watermark is not None else None)
+                                              [r.watermark for r in fresh] if self.watermark is not None else None,
+                                              [r.trim for r in fresh] if any(r.trim for r in fresh) else None)
                 segd = [r for r in new if r.seg is not None]
                 if segd:
                     pauses, flags, leads = zip(*(r.seg.plan.seam_args(r.seg.k) for r in segd))
@@ -1122,14 +1144,14 @@ class BatchScheduler:
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
                         self._counts["frames_delivered"] += n // 1920
-                elif not r.stream and (r.speed_q or r.loudness is not None or r.watermark):
-                    # a blocking utterance with a speed, a loudness target or the mark: levelled, stretched and marked whole once
+                elif not r.stream and (r.speed_q or r.loudness is not None or r.watermark or r.trim):
+                    # a blocking utterance with a trim, a speed, a loudness target or the mark: trimmed, levelled, stretched and marked whole once
                     # its last pass is in
                     if n and not r.cancelled:
                         r.stretch_in.append(host[b, :n].copy())
                         self._counts["frames_delivered"] += n // 1920
                     if fin and r.stretch_in and not r.cancelled:
-                        r.stretch_in = [self._level(r, np.concatenate(r.stretch_in))]
+                        r.stretch_in = [self._level(r, self._trimmed(r, np.concatenate(r.stretch_in)))]
                         if r.speed_q:
                             self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
                             continue
@@ -1144,6 +1166,7 @@ class BatchScheduler:
     def _part_done(self, part: _Request) -> None:
         """A segment's PCM of a blocking segmented request is complete; once all are, they are joined on the GPU (stages.seam_join)
         and go out, stretched first when the request has a speed."""
+        from ..seam import segment_flags
         from ..stages import SeamJoiner, seam_join
 
         r = part.part_of[0]
@@ -1156,6 +1179,7 @@ class BatchScheduler:
             return
         torch = self._torch
         pcms = [np.concatenate(p) if p else np.zeros(0, np.float32) for p in sg.pcm]
+        pcms = [self._trimmed(r, x, segment_flags(k, len(pcms))) for k, x in enumerate(pcms)]
         dev = self.session.engine.device
         with torch.cuda.stream(self._stretch_stream):
             if self._block_seam is None:
@@ -1169,6 +1193,21 @@ class BatchScheduler:
             return
         r.out.put(self._mark(r, pcm))
         self._end(r)
+
+    def _trimmed(self, r: _Request, pcm: np.ndarray, flags: int = 3) -> np.ndarray:
+        """A complete blocking utterance, or one segment of it with ``flags`` (default: first and final): a request that trims
+        silence has it trimmed whole on the GPU (stages.trim_pcm, waited for here as the seam join is)."""
+        if r.trim is None:
+            return pcm
+        from ..stages import SilenceTrimmer, trim_pcm
+
+        dev = self.session.engine.device
+        with self._torch.cuda.stream(self._stretch_stream):
+            if self._block_trim is None:
+                self._block_trim = SilenceTrimmer(dev, 1)
+            out = trim_pcm(pcm, flags, dev, *r.trim, trimmer=self._block_trim)
+        r.trimmed_s += (pcm.size - out.size) / 24000.0
+        return out
 
     def _mark(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
         """A complete blocking utterance, levelled and stretched: a marked request's gets the watermark whole on the GPU

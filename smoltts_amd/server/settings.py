@@ -87,6 +87,10 @@ class ServerSettings(BaseModel):
     # (extension) the loudness target in LUFS of requests whose body names none (loudness.py); null: the level is
     # left as the model gives it
     loudness: Optional[float] = Field(default=None, ge=-40.0, le=-5.0)
+    # (extension) silence trimming of requests whose body does not say (trim.py): cut the leading and trailing
+    # silence; cap the pauses at max_pause_s seconds (null: pauses are left alone)
+    trim_silence: bool = False
+    max_pause_s: Optional[float] = Field(default=None, ge=0.1, le=2.0)
 
     # (extension) a keyed watermark added to the audio on the GPU; null: none.  {"key": "<16 hex digits>", "strength_db": -26.0,
     # "apply": "all" | "cloned"}; marked responses carry X-Watermark: 1, and POST /v1/watermark/detect tests a recording

@@ -1,5 +1,5 @@
-"""The stages behind the codec, one class per C stage (resampler, time stretch, seam, loudness, watermark, FLAC), and their
-whole-utterance helpers."""
+"""The stages behind the codec, one class per C stage (resampler, time stretch, trim, seam, loudness, watermark, FLAC), and
+their whole-utterance helpers."""
 from __future__ import annotations
 
 import ctypes as C
@@ -184,6 +184,70 @@ def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device) -> np.ndarr
             return _whole_row(ts, pcm, lambda x, n, out, cnt: ts.chunk(x, n, out, cnt, last=torch.ones(1, dtype=torch.int32, device=device)))
         finally:
             ts.close()
+
+
+# ------------------------------------------------------------------------------- silence: trimmed ends, capped pauses
+class SilenceTrimmer(_Stage):
+    """Per-slot silence trimming of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Trim"; the numpy model is
+    ``trim.TrimState``): one launch per call for every slot.  Slots start off; ``start_segments`` opens a segment in a slot with
+    its flags (``SEAM_FIRST`` / ``SEAM_FINAL``; ``SEAM_OFF`` switches the slot off), whether its ends are trimmed, its pause cap
+    in blocks and its threshold."""
+
+    C_NAME = "trim"
+
+    def start_segments(self, slots: Sequence[int], flags: Sequence[int], trims: Sequence[bool], pauses: Sequence[int],
+                       thrs: Sequence[float]) -> None:
+        n = len(slots)
+        if not n:
+            return
+        self._call("reset_slots", self._ints(slots), self._ints(flags), self._ints([bool(t) for t in trims]), self._ints(pauses),
+                   (C.c_float * n)(*[float(t) for t in thrs]), n)
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
+              seg_end: Optional[torch.Tensor] = None, last: Optional[torch.Tensor] = None) -> None:
+        """Trim ``n_in`` samples (at most ``trim.MAX_CALL``) of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous
+        rows) on the current stream.  ``valid``: device int32 [batch], the real samples of each row; ``seg_end`` / ``last``:
+        device int32 [batch], nonzero where the row's segment ends with this call.  ``counts[b]``: the samples slot b wrote to
+        ``out[b]``."""
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, seg_end, last)
+        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(seg_end), dptr(last), dptr(out), out.shape[1],
+                   dptr(counts))
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s state (synchronises the current stream): ``trim.TrimState.COUNTERS`` in samples, and open."""
+        from .trim import TrimState
+
+        v = (C.c_int64 * 8)()
+        self._call("slot_state", int(slot), v)
+        return dict(zip(TrimState.COUNTERS + ("open",), list(v)))
+
+
+def trim_pcm(pcm: np.ndarray, flags: int, device: torch.device, trim: bool = True, pause_blocks: int = 0, thr: Optional[float] = None,
+             trimmer: Optional[SilenceTrimmer] = None) -> np.ndarray:
+    """A whole segment (float32 at 24 kHz) trimmed on ``device`` by the trim rule: what ``trim.trim`` computes
+    (``SmolTTS.__call__``).  The row goes through slot 0 in calls of at most ``trim.MAX_CALL`` samples, the last one ending the
+    segment; one wait for all of them.  ``trimmer``: a caller's ``SilenceTrimmer`` (default: one made for the call)."""
+    from .trim import MAX_CALL, THRESH
+
+    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    with torch.cuda.device(device):
+        st = trimmer if trimmer is not None else SilenceTrimmer(device, 1)
+        try:
+            st.start_segments([0], [flags], [trim], [pause_blocks], [THRESH if thr is None else thr])
+            row = torch.from_numpy(x).to(device)[None] if x.size else torch.zeros(1, 1, dtype=torch.float32, device=device)
+            end = torch.ones(1, dtype=torch.int32, device=device)
+            outs = []
+            for i in range(0, max(x.size, 1), MAX_CALL):
+                n = min(MAX_CALL, x.size - i)
+                out, counts = st.new_outputs(1, n)
+                st.chunk(row[:, i:i + max(n, 1)], n, out, counts, seg_end=end if i + n >= x.size else None)
+                outs.append((out, counts))
+            counts = torch.cat([c for _, c in outs]).cpu().numpy()
+            return np.concatenate([o[0, :int(c)].cpu().numpy() for (o, _), c in zip(outs, counts)])
+        finally:
+            if trimmer is None:
+                st.close()
 
 
 # ------------------------------------------------------------------------------- long texts: the seam between segments

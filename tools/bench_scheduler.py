@@ -9,7 +9,9 @@ all on GPU 0 here: what the relay between processes costs.
 SPEED_HALF=s: every other request, streamed or blocking, asks for speaking speed s (time-stretched on the GPU); its frames are
 counted as the LM frames behind its samples (samples x s / 1920).
 STREAM_FLAC=1: every streamed request asks for FLAC framing (container="flac", framed on the GPU); its frames are counted from
-the request's LM frames."""
+the request's LM frames.
+TRIM_ALL=db: every streamed request trims silence (trim_silence, max_pause_s=0.5, silence_threshold_db=db; "default": 2^-8), on the
+GPU in its codec pass; its frames are counted from the request's LM frames."""
 import functools
 import os
 import sys
@@ -63,6 +65,7 @@ def main():
     first_chunk_ms = []
     half_speed = float(os.environ.get("SPEED_HALF", 0)) or None
     use_flac = os.environ.get("STREAM_FLAC", "0") == "1"
+    trim_all = os.environ.get("TRIM_ALL")
 
 
     def worker(i):
@@ -73,12 +76,14 @@ def main():
             kw = {"speed": sp} if sp else {}
             if use_flac:
                 kw["container"] = "flac"
+            if trim_all:
+                kw.update(trim_silence=True, max_pause_s=0.5, **({} if trim_all == "default" else {"silence_threshold_db": float(trim_all)}))
             req = sched.submit(texts[i], "heart", stream=True, max_new_tokens=int(budgets[i]), **kw)
             for j, chunk in enumerate(sched.iter_chunks(req)):
                 if j == 0:
                     first_chunk_ms.append((time.perf_counter() - t1) * 1e3)
                 n += chunk.shape[0]
-            if use_flac:
+            if use_flac or trim_all:
                 samples[i] = int(req.emitted) * 1920
             else:
                 samples[i] = int(round(n * sp)) if sp else n
