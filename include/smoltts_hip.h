@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SMOLTTS_ABI_VERSION 7
+#define SMOLTTS_ABI_VERSION 8
 
 enum {
   SMOLTTS_OK = 0,
@@ -1011,10 +1011,12 @@ int smoltts_k_attention_split(const float* q_dev, const void* k_cache_dev, const
  *   V3: positions in blocks of 32, dims in four tiles of 16: block (pb, dim tile t, piece) = 1 KiB at
  *       ((pb * 4 + t) * 3 + piece) * 1024; lane l = 16 q + r holds, for j = 0..7, V[32 pb + (j < 4 ? 4q + j : 16 + 4q + j - 4)][16 t + r]
  *       (the key order in which a lane of the score MFMA holds its eight probabilities of a 32-key block).
- * Same keys as smoltts_k_attention: [max(0, pos + 1 - window), pos] of the row's slot. */
+ * Same keys as smoltts_k_attention: [max(0, pos + 1 - window), pos] of the row's slot.
+ * b3_products (ABI 8): as SmolttsGemmArgs.b3_products -- 3 = three products per operand pair (2^-16-grade: what a codec session with
+ * SMOLTTS_MIMI_OPT_PRODUCTS runs), anything else = six. */
 int smoltts_k_attention_rows3(const float* q_dev, const void* k_cache3_dev, const void* v_cache3_dev, const int32_t* row_pos_dev,
                               const int32_t* row_slot_dev, int32_t n_rows, int32_t rows_per_slot, int32_t n_heads, int32_t cache_len,
-                              int32_t window, float* out_dev, void* stream);
+                              int32_t window, float* out_dev, int32_t b3_products, void* stream);
 
 /* x[r] = E_text[cols[r][0]] + keep * sum_k E_cb[cols[r][1+k] + k*codebook_size] */
 int smoltts_k_embed(const int32_t* cols_dev, int32_t n_rows, int32_t n_code_rows,

@@ -21,7 +21,7 @@ class SmolttsError(RuntimeError):
 
 
 # ------------------------------------------------------------------------------- constants (the header's names minus SMOLTTS_)
-ABI_VERSION = 7
+ABI_VERSION = 8
 OK, E_INVALID, E_HIP, E_STATE, E_CAPACITY = 0, -1, -2, -3, -4
 MAX_LAYERS, MAX_FAST_LAYERS, MIMI_MAX_LAYERS = 64, 16, 16
 KV_F32, KV_BF16 = 0, 1
@@ -263,7 +263,7 @@ SIGNATURES = {
     "smoltts_k_attention": (INT, "p p p p p i i i i i p p p"),
     "smoltts_k_attention_kv": (INT, "p p p p p i i i i i p p i p"),
     "smoltts_k_attention_split": (INT, "p p p p p i i i i i p p i p p p"),
-    "smoltts_k_attention_rows3": (INT, "p p p p p i i i i i p p"),
+    "smoltts_k_attention_rows3": (INT, "p p p p p i i i i i p i p"),
     "smoltts_k_embed": (INT, "p i i p p i i i i i i p p"),
     "smoltts_k_argmax": (INT, "p i i q p i p p"),
     "smoltts_k_sample": (INT, "p i i q f f Q i i p p"),

@@ -43,9 +43,9 @@ int smoltts_k_attention_kv(const float* q_dev, const void* k_cache_dev, const vo
 
 int smoltts_k_attention_rows3(const float* q_dev, const void* k_cache3_dev, const void* v_cache3_dev, const int32_t* row_pos_dev,
                               const int32_t* row_slot_dev, int32_t n_rows, int32_t rows_per_slot, int32_t n_heads, int32_t cache_len,
-                              int32_t window, float* out_dev, void* stream) {
+                              int32_t window, float* out_dev, int32_t b3_products, void* stream) {
   return launch_attention_rows3(q_dev, k_cache3_dev, v_cache3_dev, row_pos_dev, row_slot_dev, n_rows, rows_per_slot, n_heads, cache_len,
-                                window, out_dev, (hipStream_t)stream);
+                                window, out_dev, (hipStream_t)stream, b3_products);
 }
 
 int smoltts_k_attention_split(const float* q_dev, const void* k_cache_dev, const void* v_cache_dev, const int32_t* row_pos_dev,

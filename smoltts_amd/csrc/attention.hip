@@ -1039,17 +1039,11 @@ int launch_attention(const float* q, const void* kc, const void* vc, const int32
     ST_CHECK_HIP(hipGetLastError());
     return SMOLTTS_OK;
   }
+  // (fp32 caches only from here: a bf16 cache left with attn_split_kernel above; lds is at most 16.6 KB at G = 4)
   const dim3 grid(n_rows, n_kv_heads);
 #define ST_ATTN(GG)                                                                          \
   case GG:                                                                                    \
-    if (lds > 64 * 1024) {                                                                    \
-      ST_CHECK_HIP(hipFuncSetAttribute((const void*)attn_kernel<GG, false>,                   \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      ST_CHECK_HIP(hipFuncSetAttribute((const void*)attn_kernel<GG, true>,                    \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    }                                                                                         \
-    if (kb) hipLaunchKernelGGL((attn_kernel<GG, true>), grid, dim3(nwaves * 64), lds, stream, d); \
-    else hipLaunchKernelGGL((attn_kernel<GG, false>), grid, dim3(nwaves * 64), lds, stream, d);    \
+    hipLaunchKernelGGL((attn_kernel<GG, false>), grid, dim3(nwaves * 64), lds, stream, d);    \
     break;
   switch (G) {
     ST_ATTN(1)

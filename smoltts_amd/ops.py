@@ -129,11 +129,12 @@ def kv3_encode(values: torch.Tensor, is_v: bool) -> torch.Tensor:
 
 
 def attention_rows3(q: torch.Tensor, k_cache3: torch.Tensor, v_cache3: torch.Tensor, row_pos: torch.Tensor, row_slot: torch.Tensor,
-                    rows_per_slot: int, n_heads: int, cache_len: int, window: int = 0) -> torch.Tensor:
-    """Attention of ``rows_per_slot`` (a multiple of 32) consecutive positions per slot over bf16x3 piece caches (attn_rows3_kernel)."""
+                    rows_per_slot: int, n_heads: int, cache_len: int, window: int = 0, b3_products: int = 6) -> torch.Tensor:
+    """Attention of ``rows_per_slot`` (a multiple of 32) consecutive positions per slot over bf16x3 piece caches (attn_rows3_kernel).
+    ``b3_products`` = 3: three products per operand pair (the 2^-16-grade form of a codec session with ``products=3``)."""
     out = torch.empty_like(q)
     _k("smoltts_k_attention_rows3", dptr(q), dptr(k_cache3), dptr(v_cache3), dptr(row_pos), dptr(row_slot), q.shape[0], rows_per_slot,
-       n_heads, cache_len, window, dptr(out))
+       n_heads, cache_len, window, dptr(out), b3_products)
     return out
 
 

@@ -50,8 +50,8 @@ def test_rows3_attention_matches_float64_softmax_and_the_fp32_kernel(mods, slots
     row_slot = torch.arange(slots).repeat_interleave(rps).int()
     row_pos = torch.cat([torch.arange(rps) + s for s in starts]).int()
     k3, v3 = ops.kv3_encode(k, False).cuda(), ops.kv3_encode(v, True).cuda()
-    # positions a row may not see hold large finite junk in the piece caches: they must get zero weight
-    got = ops.attention_rows3(q.cuda(), k3, v3, row_pos.cuda(), row_slot.cuda(), rps, heads, cache_len, window).cpu()
+    # (positions a row may not see hold ordinary values here; tests/test_attn_strict_gpu.py plants dominant keys and large V behind the masks)
+    got =ops.attention_rows3(q.cuda(), k3, v3, row_pos.cuda(), row_slot.cuda(), rps, heads, cache_len, window).cpu()
     ref = softmax_ref(q, k, v, row_pos, row_slot, heads, window)
     old = ops.attention(q.cuda(), k.cuda(), v.cuda(), row_pos.cuda(), row_slot.cuda(), heads, window).cpu()
     err = ((got.double() - ref).norm() / ref.norm()).item()
