@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SMOLTTS_ABI_VERSION 8
+#define SMOLTTS_ABI_VERSION 9
 
 enum {
   SMOLTTS_OK = 0,
@@ -316,6 +316,31 @@ typedef struct SmolttsSlotFilters {
  * is one more bit of the graph form: while every entry is off, the frames launch exactly the kernels they launch without this table. */
 int smoltts_session_set_slot_filters(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* top_p_host,
                                      const int32_t* top_k_host, const float* penalty_host, const int32_t* window_host, void* stream);
+
+/* (ABI 9, additive) Per-slot length control of the slow pick: a minimum number of frames and a bias on the end-of-speech logit,
+ * beside the slot's other two entries.  Unlike the filters it acts on greedy and sampled rows alike.  On the fp32 slow logits x of
+ * the row (step 0 only; the depth codes are never touched), in front of everything else the pick does:
+ *   1. x[im_end] = x[im_end] + eos_bias            -- one rounded fp32 add;
+ *   2. if frames[slot] < min_frames: x[im_end] = -inf.
+ * The repetition penalty, top_k, top_p, min_p, the Gumbel key and the greedy top-2 (the margin bookkeeping) all see the patched
+ * row.  frames[slot] is the slot's frame counter, read on the device when the row is picked (a multi-frame graph crosses the
+ * boundary inside one replay): with min_frames = m the earliest frame whose slow id can be im_end is frame index m, so at least
+ * m audio frames precede it.  An all-zero entry is off, and a slot whose entry is off picks exactly what it picks without the
+ * table.  Host model: smoltts_amd/sampling.py (length_patch). */
+typedef struct SmolttsSlotLength {
+  int32_t min_frames;   /* <= 0: off.  While frames[slot] < min_frames the im_end column cannot be picked */
+  float   eos_bias;     /* 0: off.  Added to the im_end logit: one rounded fp32 add */
+  int32_t reserved[2];  /* 0 */
+} SmolttsSlotLength;
+#define SMOLTTS_LENGTH_MAX_FRAMES 1073741824 /* 2^30: what this entry accepts; the public interface (config.RequestSampling) stops at 1024 */
+
+/* Set the length entries of slots_host[0 .. n): min_frames in [0, SMOLTTS_LENGTH_MAX_FRAMES] (0: off), eos_bias any finite number
+ * (0: off).  Uploaded like the other two tables (pinned ring, no host wait, ordered on `stream`); the first call of any of the three
+ * puts the session in slot mode.  "Some slot's length entry is on" is bit 3 of the graph form.  In a form that has it the slow token
+ * is picked from the row of logits (as in a form whose slow token is sampled), not from the head GEMM's tile candidates, which hold
+ * unpatched values.  While every entry is off, the frames launch exactly the kernels they launch without this table. */
+int smoltts_session_set_slot_length(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* min_frames_host,
+                                    const float* eos_bias_host, void* stream);
 
 /* Device pointers to the session's results (valid for the session's lifetime):
  *   codes      int32 [max_batch][max_frames][1 + n_fast]   emitted columns (slow id, codes)
@@ -1042,6 +1067,14 @@ int smoltts_k_sample_rows(const float* logits_dev, int32_t n_rows, int32_t n_col
 int smoltts_k_sample_rows_filtered(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const SmolttsSlotSampling* table_dev,
                                    const SmolttsSlotFilters* filters_dev, const int32_t* frames_dev, const int32_t* history_dev,
                                    const int32_t* history_len_dev, int32_t step, int32_t* ids_dev, void* stream);
+
+/* (ABI 9, additive) smoltts_k_sample_rows / smoltts_k_sample_rows_filtered with row r's length entry length_dev[r] acting on
+ * column im_end at step 0, the row's frame counter being frames_dev[r] (NULL: r).  filters_dev may be NULL (then the two history
+ * arguments are ignored): the pick without filters. */
+int smoltts_k_sample_rows_length(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const SmolttsSlotSampling* table_dev,
+                                 const SmolttsSlotFilters* filters_dev, const int32_t* frames_dev, const int32_t* history_dev,
+                                 const int32_t* history_len_dev, const SmolttsSlotLength* length_dev, int32_t im_end, int32_t step,
+                                 int32_t* ids_dev, void* stream);
 
 int smoltts_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, int32_t n_rows,
                         int32_t dim, float eps, float* out_dev, void* stream);

@@ -69,9 +69,17 @@ class SmolTTS:
         self._seam = None  # stages.SeamJoiner of the blocking segmented calls (made on first use)
         self._trim = None  # stages.SilenceTrimmer of the blocking calls that trim silence (made on first use)
         self.last_trimmed_s = 0.0  # seconds of silence the last blocking call trimmed (trim_silence / max_pause_s)
-        self.last_segments: list = []  # per segment of the last segmented call: text, prompt, codes, seed
+        self.last_segments: list = []  # per segment of the last segmented call: text, prompt, codes, seed, frames
         self.last_loudness_gain_db = None  # gain of the last call that was given loudness=
         self.last_stats: dict = {}  # timing of the last generate_codes / __call__ (BatchGenerator.stats + codec_ms)
+        # why the last call's utterance ended: "stop" (its last slow id is <|im_end|>) or "length" (the frame cap or a full
+        # context); a segmented call is "length" if any segment was.  last_finish_reasons: one per input of generate_codes
+        self.last_finish_reason: Optional[str] = None
+        self.last_finish_reasons: List[str] = []
+        # bounds on an utterance's (a segment's) length from its text's UTF-8 byte count (config.length_bounds);
+        # None: off.  12.5 frames are one second of audio: the ratios are the operator's to measure
+        self.min_frames_per_byte: Optional[float] = None
+        self.max_frames_per_byte: Optional[float] = None
 
     # -- prompt (``_get_prompt``, __init__.py:120-151)
     def _get_prompt(self, input: str, voice: str, sysprompt=None):
@@ -136,6 +144,10 @@ class SmolTTS:
                 if tok is not None and tok.audio_codes is not None:
                     cols[b].append(tok.audio_codes[0, :, 0])
         self.last_stats = gen.stats()
+        from .config import merge_finish_reasons
+
+        self.last_finish_reasons = gen.finish_reasons()
+        self.last_finish_reason = merge_finish_reasons(self.last_finish_reasons)
         gen.close()
         if self.verbose and self.last_stats:
             st = self.last_stats
@@ -192,9 +204,16 @@ class SmolTTS:
         marked = self._marks(req.watermark)
         voice = voice if voice is not None else "heart"
         self.last_trimmed_s = 0.0
+        self.last_finish_reason = None  # (known once the call is through)
         if req.plan is not None:
             pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling, req)
         else:
+            if self._bounds_on:
+                from .generate import resolve_sampling
+
+                st = self._settings(generation_settings)
+                generation_settings, one = self._bounded(input, st, resolve_sampling(sampling, st, 1))
+                sampling = None if one is None else one[0]
             codes = self.generate_codes([input], [voice], generation_settings, speakers=None if speaker is None else [speaker],
                                         sampling=sampling)[0]
             pcm = self._trimmed(self.decode_codes(codes), req)
@@ -226,6 +245,38 @@ class SmolTTS:
         out = trim_pcm(pcm, flags, self.lm.device, req.trim_silence, req.pause_blocks, req.silence_thr, trimmer=self._trim)
         self.last_trimmed_s += (pcm.size - out.size) / self.sampling_rate
         return out
+
+    @property
+    def _bounds_on(self) -> bool:
+        return self.min_frames_per_byte is not None or self.max_frames_per_byte is not None
+
+    def _bounded(self, text: str, settings, resolved, plan=None, k: int = 0):
+        """``settings`` and the resolved sampling list (or None) of the utterance that speaks ``text`` (segment ``k`` of ``plan``
+        where one is given), under the instance's ``min_frames_per_byte`` / ``max_frames_per_byte``: the cap becomes the settings'
+        ``max_new_tokens``, the minimum the entry's ``min_frames``.  A call without an entry (session-wide mode) gets the minimum
+        in its settings and, the length control existing in slot mode only, the entry resolved from them."""
+        if not self._bounds_on:
+            return settings, resolved
+        import dataclasses
+
+        from .config import RequestSampling, length_bounds
+        from .generate import resolve_sampling
+
+        carrier = resolved[0] if resolved is not None else RequestSampling(min_frames=settings.min_frames)
+        ratios = (self.min_frames_per_byte, self.max_frames_per_byte)
+        bounded, cap = (plan.length_bounds(k, carrier, self._max_new(settings), *ratios) if plan is not None
+                        else length_bounds(text, carrier, self._max_new(settings), *ratios))
+        if resolved is None:
+            settings = dataclasses.replace(settings, max_new_tokens=cap, min_frames=bounded.min_frames or 0)
+            return settings, resolve_sampling(None, settings, 1)
+        return dataclasses.replace(settings, max_new_tokens=cap), [bounded]
+
+    def _stream_reason(self, sess) -> str:
+        """``finish_reason`` of the utterance a stream's one-slot session has just spoken."""
+        from .config import finish_reason
+
+        codes, n_frames, _, _ = sess.fetch()
+        return finish_reason(codes[0, :int(n_frames[0]), 0], self.token_config.im_end_id)
 
     def _marks(self, asked: Optional[bool]):
         """The ``watermark.Watermark`` of a request that asked ``asked`` (None: the instance's policy), or None: unmarked."""
@@ -308,6 +359,7 @@ class SmolTTS:
         from .generate import resolve_sampling, stream_pcm
         from .request import parse_request
 
+        self.last_finish_reason = None  # (known once the stream has been consumed to its end)
         if not isinstance(input, (str, bytes)):
             yield from self._stream_incremental(iter(input), voice if voice is not None else "0", generation_settings, overlap,
                                                 reference_upsample, output_format, sampling, speed, container, segment, loudness,
@@ -325,13 +377,15 @@ class SmolTTS:
         if prompt.ndim == 3:
             prompt = prompt[0]
         settings = self._settings(generation_settings)
-        self.last_sampling = resolve_sampling(sampling, settings, 1)
+        settings, self.last_sampling = self._bounded(input if isinstance(input, str) else input.decode("utf-8", "replace"), settings,
+                                                     resolve_sampling(sampling, settings, 1))
         sess = self._stream_session(prompt, settings, self.last_sampling)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
             yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=req.output_format,
                                   speed_q=req.speed_q, container=req.container, loudness=req.loudness,
                                   start_gain_db=req.start_gain_db, watermark=marked, trim=req.trim_route)
+            self.last_finish_reason = self._stream_reason(sess)
         finally:
             msess.close()
             sess.close()
@@ -375,19 +429,27 @@ class SmolTTS:
         for k, seg in enumerate(plan.segs):
             prev = (info[-1]["text"], info[-1]["codes"]) if info else None
             samp = plan.sampling(k, base)
-            info.append({"text": seg.text, "prompt": plan.prompt(k, self.prompt_encoder, prefix, prev, self._max_new(settings),
+            # (every segment is an utterance of its own: its bounds come from its own text, its length entry is set anew)
+            st_k, samp_k = (self._bounded(seg.text, settings, [samp], plan, k) if resolved is not None
+                            else self._bounded(seg.text, samp, None, plan, k))
+            info.append({"text": seg.text, "prompt": plan.prompt(k, self.prompt_encoder, prefix, prev, self._max_new(st_k),
                                                                  self.config.max_seq_len),
-                         "codes": None, "seed": samp.seed})
-            yield (k, info[-1], settings, [samp]) if resolved is not None else (k, info[-1], samp, None)
+                         "codes": None, "seed": samp.seed, "frames": None})
+            yield k, info[-1], st_k, samp_k
         self.last_sampling = resolved  # (generate_prompt_codes sets it per segment)
 
     def _call_segmented(self, plan, voice, speaker, generation_settings, sampling, req):
         from .seam import segment_flags
         from .stages import SeamJoiner, seam_join
 
-        pcms = []
+        from .config import merge_finish_reasons
+
+        pcms, reasons = [], []
         for k, seg, st_k, samp_k in self._segments(plan, voice, speaker, generation_settings, sampling):
             seg["codes"] = self.generate_prompt_codes([seg["prompt"]], st_k, samp_k)[0]
+            seg["frames"] = int(self.last_stats.get("frames", 0))  # every frame the segment emitted, its <|im_end|> frame included
+            reasons.append(self.last_finish_reason)
+            self.last_finish_reason = merge_finish_reasons(reasons)
             pcms.append(self._trimmed(self.decode_codes(seg["codes"]), req, segment_flags(k, len(plan.segs))))
         if self._seam is None:
             self._seam = SeamJoiner(self.lm.device, 1)
@@ -433,8 +495,11 @@ class SmolTTS:
         from .route import StreamConverter
         from .generate import semantic_columns, stream_pcm
 
+        from .config import merge_finish_reasons
+
         plan = plan if plan is not None else req.plan
         dev = self.lm.device
+        reasons: list = []
         conv = StreamConverter(dev, 1, 1920, seam=True, watermark=marked)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
@@ -454,6 +519,9 @@ class SmolTTS:
                     conv.start_segments([0], [pause], [flags], [lead])
                     yield from stream_pcm(sess, msess, seg["prompt"], stop_on_eos=True, overlap=overlap, conv=conv, final=final)
                     codes_all, n_frames, _, _ = sess.fetch()
+                    seg["frames"] = int(n_frames[0])
+                    reasons.append(self._stream_reason(sess))
+                    self.last_finish_reason = merge_finish_reasons(reasons)
                     seg["codes"] = semantic_columns(codes_all[0, :int(n_frames[0])], self.token_config,
                                                     self.config.num_codebooks).T.astype(np.uint32)
                 finally:

@@ -21,7 +21,7 @@ class SmolttsError(RuntimeError):
 
 
 # ------------------------------------------------------------------------------- constants (the header's names minus SMOLTTS_)
-ABI_VERSION = 8
+ABI_VERSION = 9
 OK, E_INVALID, E_HIP, E_STATE, E_CAPACITY = 0, -1, -2, -3, -4
 MAX_LAYERS, MAX_FAST_LAYERS, MIMI_MAX_LAYERS = 64, 16, 16
 KV_F32, KV_BF16 = 0, 1
@@ -34,6 +34,7 @@ RESAMPLE_OFF, RESAMPLE_S16, RESAMPLE_ULAW = 0, 1, 2
 SEAM_FIRST, SEAM_FINAL, SEAM_OFF = 1, 2, 4
 FLAC_OFF, FLAC_F32, FLAC_S16 = 0, 1, 2
 FILTER_MAX_WINDOW, FILTER_MAX_PENALTY = 64, 1000.0
+LENGTH_MAX_FRAMES = 1 << 30
 PREFIX_MAGIC, PREFIX_MAX_INSTALL = 0x58464250, 16
 
 KV_FORMATS = {"fp32": KV_F32, "bf16": KV_BF16}
@@ -67,6 +68,10 @@ class SlotSampling(C.Structure):
 class SlotFilters(C.Structure):
     _fields_ = [("top_p", C.c_float), ("top_k", C.c_int32), ("penalty", C.c_float), ("inv_penalty", C.c_float),
                 ("window", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class SlotLength(C.Structure):
+    _fields_ = [("min_frames", C.c_int32), ("eos_bias", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
 class PrefixHeader(C.Structure):
@@ -147,7 +152,7 @@ class Gemm3Args(C.Structure):
     ]
 
 
-STRUCTS = (BlockWeights, LMConfig, LMWeights, SlotSampling, SlotFilters, PrefixHeader, MimiLayerWeights, MimiConv, MimiConfig,
+STRUCTS = (BlockWeights, LMConfig, LMWeights, SlotSampling, SlotFilters, SlotLength, PrefixHeader, MimiLayerWeights, MimiConv, MimiConfig,
            MimiWeights, MimiEncConfig, MimiEncWeights, MimiEncLayout, GemmArgs, PickArgs, Gemm3Args)
 
 # ------------------------------------------------------------------------------- signatures
@@ -180,6 +185,7 @@ SIGNATURES = {
     "smoltts_session_set_sampling": (INT, "p f f f Q"),
     "smoltts_session_set_slot_sampling": (INT, "p p i p p p p p"),
     "smoltts_session_set_slot_filters": (INT, "p p i p p p p p"),
+    "smoltts_session_set_slot_length": (INT, "p p i p p p"),
     "smoltts_session_outputs": (INT, "p p* p* p* p*"),
     "smoltts_session_kv_cache": (INT, "p p* p* Q*"),
     "smoltts_session_fast_kv_cache": (INT, "p p* p* Q*"),
@@ -269,6 +275,7 @@ SIGNATURES = {
     "smoltts_k_sample": (INT, "p i i q f f Q i i p p"),
     "smoltts_k_sample_rows": (INT, "p i i q p p i p p"),
     "smoltts_k_sample_rows_filtered": (INT, "p i i q p p p p p i p p"),
+    "smoltts_k_sample_rows_length": (INT, "p i i q p p p p p p i i p p"),
     "smoltts_k_layernorm": (INT, "p p p i i f p p"),
     "smoltts_k_seanet_resblock": (INT, "i i i p q p p p p p q i p"),
     "smoltts_k_seanet_last": (INT, "i i p q p p p p p p p f p q p i p"),

@@ -182,12 +182,15 @@ class GenerationSettings:
     top_k: int = 0
     repetition_penalty: float = 1.0
     repetition_window: int = 16
+    # extension: the defaults of the per-request length control (``RequestSampling``; both off)
+    min_frames: int = 0
+    eos_bias: float = 0.0
 
     def __post_init__(self):
         if self.min_p_mode not in ("reference", "intended"):
             raise ValueError(f"min_p_mode must be 'reference' or 'intended', got {self.min_p_mode!r}")
         RequestSampling(top_p=self.top_p, top_k=self.top_k, repetition_penalty=self.repetition_penalty,
-                        repetition_window=self.repetition_window)  # the same ranges
+                        repetition_window=self.repetition_window, min_frames=self.min_frames, eos_bias=self.eos_bias)  # the same ranges
 
     @property
     def effective_min_p(self) -> float:
@@ -204,6 +207,62 @@ class GenerationSettings:
         return self.default_temp == 0.0 and fast_greedy
 
 
+FRAMES_PER_SECOND = 12.5  # Mimi frames (slow tokens) per second of audio
+MAX_MIN_FRAMES = 1024     # of the public interface; the device entry takes up to 2**30
+MAX_EOS_BIAS = 100.0
+
+
+def min_frames_from(min_frames=None, min_duration_s=None) -> Optional[int]:
+    """The ``min_frames`` of a request that may spell it as ``min_duration_s`` (seconds of audio, ``ceil(s * 12.5)`` frames)
+    instead; giving both is an error.  Range errors are ``RequestSampling``'s."""
+    import math
+
+    if min_duration_s is None:
+        return min_frames
+    if min_frames is not None:
+        raise ValueError("give min_frames or min_duration_s, not both")
+    if isinstance(min_duration_s, bool) or not isinstance(min_duration_s, (int, float)) or not math.isfinite(min_duration_s) or min_duration_s < 0:
+        raise ValueError(f"min_duration_s must be finite and >= 0, got {min_duration_s!r}")
+    if min_duration_s * FRAMES_PER_SECOND > MAX_MIN_FRAMES:
+        raise ValueError(f"min_duration_s must be at most {MAX_MIN_FRAMES / FRAMES_PER_SECOND:g} s, got {min_duration_s!r}")
+    return int(math.ceil(min_duration_s * FRAMES_PER_SECOND))
+
+
+def length_bounds(text: str, sampling: "RequestSampling", max_new_tokens: int, min_frames_per_byte: Optional[float] = None,
+                  max_frames_per_byte: Optional[float] = None):
+    """(sampling, max_new_tokens) of one utterance or segment under the operator's bounds from the text length: with n the UTF-8
+    byte count of ``text``, ``max_new_tokens = max(1, min(request's, ceil(n * max_frames_per_byte)))`` and ``min_frames =
+    min(max(request's, floor(n * min_frames_per_byte)), max_new_tokens - 1)``.  A ratio of ``None`` leaves its side alone; with
+    both ``None`` the two arguments come back unchanged."""
+    import dataclasses
+    import math
+
+    if min_frames_per_byte is None and max_frames_per_byte is None:
+        return sampling, max_new_tokens
+    n = len(text.encode("utf-8"))
+    cap = int(max_new_tokens)
+    if max_frames_per_byte is not None:
+        cap = max(1, min(cap, int(math.ceil(n * float(max_frames_per_byte)))))
+    if min_frames_per_byte is not None:
+        own = int(sampling.min_frames or 0)
+        want = min(max(own, int(math.floor(n * float(min_frames_per_byte)))), max(cap - 1, 0), MAX_MIN_FRAMES)
+        if want != own:
+            sampling = dataclasses.replace(sampling, min_frames=want)
+    return sampling, cap
+
+
+def finish_reason(slow_ids, im_end_id: int) -> str:
+    """Why an utterance ended: ``"stop"`` if its last emitted slow id is ``<|im_end|>``, else ``"length"`` (the frame cap, the
+    request's ``max_new_tokens`` or a full context)."""
+    n = len(slow_ids)
+    return "stop" if n > 0 and int(slow_ids[n - 1]) == int(im_end_id) else "length"
+
+
+def merge_finish_reasons(reasons) -> str:
+    """Of a segmented request: ``"length"`` if any segment was."""
+    return "length" if any(r == "length" for r in reasons) else "stop"
+
+
 @dataclass
 class RequestSampling:
     """Sampling of one request (per-request settings of the server and the façade).  ``None`` fields take the server's or
@@ -214,7 +273,11 @@ class RequestSampling:
     Filters of the sampled picks, ``None`` <- the settings' field of the same name: ``top_p`` (0 < p <= 1; 1 =
     off), ``top_k`` (>= 0; 0 = off), ``repetition_penalty`` (1 .. 10; 1 = off) over the ids the same step produced in the
     request's last ``repetition_window`` (1 .. 64) frames.  They act only where the request samples: a greedy slow token or
-    greedy depth codes ignore them."""
+    greedy depth codes ignore them.
+
+    Length control, ``None`` <- the settings' field of the same name: ``min_frames`` (0 .. 1024; 0 = off) keeps
+    ``<|im_end|>`` from being picked before that many frames have been emitted; ``eos_bias`` (-100 .. 100; 0 = off) is added to
+    the ``<|im_end|>`` logit.  Both act on greedy and sampled slow tokens alike; the depth codes are never touched."""
 
     temperature: Optional[float] = None
     fast_temperature: Optional[float] = None
@@ -224,6 +287,8 @@ class RequestSampling:
     top_k: Optional[int] = None
     repetition_penalty: Optional[float] = None
     repetition_window: Optional[int] = None
+    min_frames: Optional[int] = None
+    eos_bias: Optional[float] = None
 
     def __post_init__(self):
         import math
@@ -245,6 +310,17 @@ class RequestSampling:
         w = self.repetition_window
         if w is not None and not (isinstance(w, int) and not isinstance(w, bool) and 1 <= w <= 64):
             raise ValueError(f"repetition_window must be an integer in [1, 64], got {w!r}")
+        m = self.min_frames
+        if m is not None and not (isinstance(m, int) and not isinstance(m, bool) and 0 <= m <= MAX_MIN_FRAMES):
+            raise ValueError(f"min_frames must be an integer in [0, {MAX_MIN_FRAMES}], got {m!r}")
+        b = self.eos_bias
+        if b is not None and not (isinstance(b, (int, float)) and not isinstance(b, bool) and math.isfinite(b) and abs(b) <= MAX_EOS_BIAS):
+            raise ValueError(f"eos_bias must be finite and in [-{MAX_EOS_BIAS:g}, {MAX_EOS_BIAS:g}], got {b!r}")
+
+    @property
+    def length_on(self) -> bool:
+        """Whether the length control of an entry is on: a minimum number of frames or a bias on ``<|im_end|>``."""
+        return bool(self.min_frames) or bool(self.eos_bias)
 
     @property
     def filters_on(self) -> bool:
@@ -266,7 +342,8 @@ class RequestSampling:
         cut = GenerationSettings(min_p=self.min_p if self.min_p is not None else settings.min_p, min_p_mode=settings.min_p_mode).effective_min_p
         pick = lambda name: getattr(self, name) if getattr(self, name) is not None else getattr(settings, name)
         out = RequestSampling(max(t, 0.0), max(ft, 0.0), cut, self.seed, float(pick("top_p")), int(pick("top_k")),
-                              float(pick("repetition_penalty")), int(pick("repetition_window")))
+                              float(pick("repetition_penalty")), int(pick("repetition_window")), int(pick("min_frames")),
+                              float(pick("eos_bias")))
         if out.seed is None and draw_seed and out.is_sampled:
             out.seed = int.from_bytes(os.urandom(8), "little")
         return out

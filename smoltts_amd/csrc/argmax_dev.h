@@ -131,7 +131,12 @@ __device__ __forceinline__ float penalised(float x, float r, float inv_r) { retu
 // `r`: the row's index into margin / margin_mask / the sampling arrays.  Greedy rows update margin[r] / margin_at[r].
 // FILTERS: the instantiation that reads sa.filters (slot mode's sampled forms; `F` is its LDS).  A row whose entry is off, and
 // every greedy row, takes one uniform branch and then the instructions of the plain instantiation.
-template <bool FILTERS = false>
+// LENGTH: the instantiation that reads sa.length (slot mode's forms with a length entry on; SmolttsSlotLength, host model
+// smoltts_amd/sampling.py length_patch).  At step 0 the row's im_end column gets the entry's bias (one rounded fp32 add) and, while
+// the row's frame counter is below min_frames, -inf -- as the value is read, in front of the penalty, so greedy and sampled picks,
+// every filter and the top-2 gap see the patched row.  The row always has other finite columns: its maximum stays finite, a -inf
+// column gives z = -inf, mass 0 and key -inf and is never picked.  A row whose entry is off takes one uniform branch.
+template <bool FILTERS = false, bool LENGTH = false>
 __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_vec, int r, float* margin, const int* margin_mask,
                                           const SampleArgs& sa, ArgmaxScratch& S, FilterScratch* F = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -147,6 +152,20 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     key_slot = 0;
   }
   const bool vec = (n_cols & 3) == 0 && ld_vec && n_cols <= 8 * 1024;
+  // the row's length entry (uniform): lcol = the patched column, or -1 (off, or not the slow pick)
+  int lcol = -1;
+  float lbias = 0.f;
+  bool lblock = false;
+  if constexpr (LENGTH) {
+    if (sa.length && sa.step == 0 && (unsigned)sa.im_end < (unsigned)n_cols) {
+      const SmolttsSlotLength le = sa.length[r];
+      lblock = (sa.frames ? sa.frames[r] : sa.frame_base + r) < le.min_frames;
+      lbias = le.eos_bias;
+      if (lblock || lbias != 0.f) lcol = sa.im_end;
+    }
+  }
+  // scalar paths: the value of column J as the pick sees it
+#define ST_LFIX(X, J) ((LENGTH && (J) == lcol) ? (lblock ? -INFINITY : (X) + lbias) : (X))
   // the row's filters (uniform).  History id h sits in lane h of every wave: the loops over it read it with v_readlane.
   int top_k = 0, hn = 0, hid = -1;
   float top_p = 0.f, pen = 1.f, inv_pen = 1.f;
@@ -194,6 +213,7 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     const int j_ = tid + 256 * ((G) * 64 + c_);                         \
     if (j_ >= n_cols) break;                                            \
     float x_ = row[j_];                                                 \
+    x_ = ST_LFIX(x_, j_);                                               \
     if (((PM) >> c_) & 1) x_ = penalised(x_, pen, inv_pen);             \
     BODY(x_, j_)                                                        \
   }
@@ -202,6 +222,7 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     ST_SGROUP(pm0, 0, BODY) ST_SGROUP(pm1, 1, BODY) ST_SGROUP(pm2, 2, BODY) ST_SGROUP(pm3, 3, BODY) \
     for (int j_ = tid + 65536; j_ < n_cols; j_ += 256) {                                     \
       float x_ = row[j_];                                                                    \
+      x_ = ST_LFIX(x_, j_);                                                                  \
       bool hit_ = false;                                                                     \
       for (int h_ = 0; h_ < hn; ++h_) hit_ |= __builtin_amdgcn_readlane(hid, h_) == j_;      \
       if (hit_) x_ = penalised(x_, pen, inv_pen);                                            \
@@ -227,6 +248,18 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
       const int j = tid * 4 + i * 1024;
       v[i] = j < n_cols ? *reinterpret_cast<const float4*>(row + j) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
     }
+    if constexpr (LENGTH) {
+      if (lcol >= 0 && ((lcol >> 2) & 255) == tid) {  // the length entry, patched into the one row register that holds im_end
+        const uint32_t lmask = 1u << (((lcol >> 10) << 2) | (lcol & 3));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          if ((lmask >> (i * 4)) & 1) v[i].x = lblock ? -INFINITY : v[i].x + lbias;
+          if ((lmask >> (i * 4 + 1)) & 1) v[i].y = lblock ? -INFINITY : v[i].y + lbias;
+          if ((lmask >> (i * 4 + 2)) & 1) v[i].z = lblock ? -INFINITY : v[i].z + lbias;
+          if ((lmask >> (i * 4 + 3)) & 1) v[i].w = lblock ? -INFINITY : v[i].w + lbias;
+        }
+      }
+    }
     if constexpr (FILTERS) {
       if (vmask) {  // the penalty, patched into the row registers before the first pass
 #pragma unroll
@@ -246,7 +279,7 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
   } else if (FILTERS && fon) {
     ST_SCOLS(ST_TAKE)
   } else {
-    for (int j = tid; j < n_cols; j += 256) ST_TAKE(row[j], j)
+    for (int j = tid; j < n_cols; j += 256) ST_TAKE(ST_LFIX(row[j], j), j)
   }
 #undef ST_TAKE
 #pragma unroll
@@ -349,7 +382,7 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     } else if (FILTERS && fon) {
       ST_SCOLS(ST_KEY_S)
     } else {
-      for (int j = tid; j < n_cols; j += 256) ST_KEY(row[j], j)
+      for (int j = tid; j < n_cols; j += 256) ST_KEY(ST_LFIX(row[j], j), j)
     }
 #undef ST_KEY_S
 #undef ST_KEY
@@ -366,6 +399,7 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
   }
 #undef ST_SCOLS
 #undef ST_SGROUP
+#undef ST_LFIX
   if (a.i1 < 0 || a.i1 >= n_cols) a.i1 = 0;  // all-NaN row: stay inside the tables
   if (tid == 0) {
     if (temp <= 0.f && margin && (margin_mask == nullptr || margin_mask[r])) {

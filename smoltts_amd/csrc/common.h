@@ -212,6 +212,11 @@ struct SampleArgs {
   int32_t hist_frame_stride;
   int32_t hist_frames;
   const int32_t* hist_len;
+  // per-row length entries of the slow pick (slot mode), or null: the im_end column `im_end` of row r gets the entry's bias and,
+  // while frames[r] < min_frames, -inf, in front of everything else (argmax_dev.h).  Read only at step 0 and only by the LENGTH
+  // instantiations of the picking kernels, which a launcher selects when this pointer is set.
+  const SmolttsSlotLength* length;
+  int32_t im_end;
 };
 
 // Launchers implemented across the .hip files (all asynchronous on `stream`).

@@ -34,6 +34,7 @@ struct SmolttsEngine {
 };
 
 constexpr int STAGE_RING = 8;
+constexpr int GRAPH_FORMS = 16;  // the values of SmolttsSession.form (pick_form)
 
 struct SmolttsSession {
   SmolttsEngine* e;
@@ -73,14 +74,14 @@ struct SmolttsSession {
   hipEvent_t stage_ev[8];      // recorded behind the async copies out of each area
   bool stage_ev_live[8];
   int stage_next;
-  // captured graphs, one set per form (GRAPH_FORMS: which picks sample, and whether some slot filters; index 0 outside slot mode),
-  // each created when first needed
-  hipGraphExec_t graph_exec[8];   // one decode frame (slow step + tail)
-  bool graph_ready[8];
-  hipGraphExec_t tail_exec[8];    // the tail alone (slow head + depth steps + commit) as run after a prefill
-  bool tail_ready[8];
-  hipGraphExec_t multi_exec[8];   // `multi_frames` consecutive decode frames in one graph (fewer graph launches per tick / chunk)
-  bool multi_ready[8];
+  // captured graphs, one set per form (pick_form: which picks sample, whether some slot filters, whether some slot's length entry
+  // is on; index 0 outside slot mode), each created when first needed
+  hipGraphExec_t graph_exec[GRAPH_FORMS];   // one decode frame (slow step + tail)
+  bool graph_ready[GRAPH_FORMS];
+  hipGraphExec_t tail_exec[GRAPH_FORMS];    // the tail alone (slow head + depth steps + commit) as run after a prefill
+  bool tail_ready[GRAPH_FORMS];
+  hipGraphExec_t multi_exec[GRAPH_FORMS];   // `multi_frames` consecutive decode frames in one graph (fewer graph launches per tick / chunk)
+  bool multi_ready[GRAPH_FORMS];
   int form;                       // the form the next launches are built / replayed in (pick_form)
   // slot mode (smoltts_session_set_slot_sampling): per-slot sampling entries
   bool slot_mode;
@@ -96,6 +97,10 @@ struct SmolttsSession {
   SmolttsSlotFilters* filt_tab;       // [B] read by the sampled picks of slot mode; all zero = off
   SmolttsSlotFilters* filt_tab_area;  // [B] table, [B] upload entries, [B] upload slots
   bool* h_filt_on;                    // host mirror: which slots' entries are on (chooses the graph form)
+  // ... and per-slot length entries (smoltts_session_set_slot_length): the third part of each ring area
+  SmolttsSlotLength* len_tab;         // [B] read by the slow picks of slot mode (greedy and sampled); all zero = off
+  SmolttsSlotLength* len_tab_area;    // [B] table, [B] upload entries, [B] upload slots
+  bool* h_len_on;                     // host mirror: which slots' entries are on (bit 3 of the graph form)
   int flight_limit;            // SMOLTTS_MAX_FRAMES_IN_FLIGHT as read at creation (0 = unbounded)
   int multi_frames;            // frames per multi-frame graph (1 = single-frame graphs only): SMOLTTS_FRAMES_PER_GRAPH, else
                                // smoltts_session_set_frames_per_graph, else min(n_frames, 4) of the largest decode call so far
@@ -177,6 +182,7 @@ size_t carve(SmolttsSession* s, char* base) {
   // tail of the slab, in use once the session enters slot mode
   s->slot_tab_area = cv.take<SmolttsSlotSampling>(2 * B + (B * sizeof(int) + sizeof(SmolttsSlotSampling) - 1) / sizeof(SmolttsSlotSampling));
   s->filt_tab_area = cv.take<SmolttsSlotFilters>(2 * B + (B * sizeof(int) + sizeof(SmolttsSlotFilters) - 1) / sizeof(SmolttsSlotFilters));
+  s->len_tab_area = cv.take<SmolttsSlotLength>(2 * B + (B * sizeof(int) + sizeof(SmolttsSlotLength) - 1) / sizeof(SmolttsSlotLength));
   return cv.off;
 }
 
@@ -193,13 +199,9 @@ __global__ void init_state_kernel(int B, int n_fast, int* iota, int* fastpos, in
   for (int i = 0; i <= n_fast; ++i) { cur_col[b * (1 + n_fast) + i] = 0; new_col[b * (1 + n_fast) + i] = 0; }
 }
 
-// Slot mode: table[slots[i]] = entries[i] for the n entries of one upload (distinct slots)
-__global__ void slot_sampling_scatter_kernel(int n, const SmolttsSlotSampling* entries, const int* slots, SmolttsSlotSampling* table) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) table[slots[i]] = entries[i];
-}
-
-__global__ void slot_filters_scatter_kernel(int n, const SmolttsSlotFilters* entries, const int* slots, SmolttsSlotFilters* table) {
+// Slot mode: table[slots[i]] = entries[i] for the n entries of one upload (distinct slots), for each of the three per-slot tables
+template <typename Entry>
+__global__ void slot_scatter_kernel(int n, const Entry* entries, const int* slots, Entry* table) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) table[slots[i]] = entries[i];
 }
@@ -282,8 +284,9 @@ struct CommitArgs {
                      // interrupted launch, a caller's odd count) can invert a later launch's "who arrived last" decision
 };
 
-// FILTERS: the instantiation whose picks read SampleArgs.filters (slot mode's sampled forms)
-template <bool FILTERS>
+// FILTERS: the instantiation whose picks read SampleArgs.filters (slot mode's sampled forms); LENGTH: the one whose slow pick
+// reads SampleArgs.length (slot mode's forms with a length entry on).  The stop rule below sees the id the patched row gave.
+template <bool FILTERS, bool LENGTH>
 __global__ __launch_bounds__(256) void commit_embed_kernel(CommitArgs a, EmbedTables t, float* xt, EmitDev emit) {
   __shared__ int s_col[64];
   __shared__ float sh4[4];
@@ -320,10 +323,10 @@ __global__ __launch_bounds__(256) void commit_embed_kernel(CommitArgs a, EmbedTa
   }
   if constexpr (FILTERS) {
     __shared__ FilterScratch s_filt[2];
-    if (a.slow_logits && !c_slow) id_slow = argmax_row<true>(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0], &s_filt[0]);
+    if (a.slow_logits && !c_slow) id_slow = argmax_row<true, LENGTH>(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0], &s_filt[0]);
     if (a.last_logits && !c_last) id_last = argmax_row<true>(a.last_logits + (long)b * a.last_cols, a.last_cols, (a.last_cols & 3) == 0, b, a.margin, a.mask, a.last_sa, s_pick[1], &s_filt[1]);
   } else {
-    if (a.slow_logits && !c_slow) id_slow = argmax_row(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0]);
+    if (a.slow_logits && !c_slow) id_slow = argmax_row<false, LENGTH>(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0]);
     if (a.last_logits && !c_last) id_last = argmax_row(a.last_logits + (long)b * a.last_cols, a.last_cols, (a.last_cols & 3) == 0, b, a.margin, a.mask, a.last_sa, s_pick[1]);
   }
   int f = 0;
@@ -479,13 +482,18 @@ EmbedTables embed_tables(const SmolttsEngine* e) {
 // being built (pick_form).  A part that no row samples is built exactly as the session-wide greedy one.
 bool slow_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & 1) != 0 : s->temp > 0.f; }
 bool fast_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & 2) != 0 : s->fast_temp > 0.f; }
+// Whether some slot's length entry is on (slot mode only): the slow pick then reads the row of logits with every row's own entries,
+// as in a form whose slow token is sampled -- the head GEMM's tile candidates hold unpatched values
+bool length_on(const SmolttsSession* s) { return s->slot_mode && (s->form & 8) != 0; }
 
 // The pick arguments of step 0 (slow token) / step >= 1 (depth codes).  Slot mode, sampling form: every row reads its own entry
 // (a greedy row then takes the argmax inside argmax_row); greedy form: plain greedy arguments.
 SampleArgs pick_args(const SmolttsSession* s, int step) {
   if (s->slot_mode) {
     const bool sampled = step == 0 ? slow_sampled(s) : fast_sampled(s);
-    SampleArgs sa{0.f, 0.f, 0, step, 0, s->frames, nullptr, s->margin_at, sampled ? s->slot_tab : nullptr};
+    const bool length = step == 0 && length_on(s);
+    SampleArgs sa{0.f, 0.f, 0, step, 0, s->frames, nullptr, s->margin_at, sampled || length ? s->slot_tab : nullptr};
+    if (length) { sa.length = s->len_tab; sa.im_end = s->e->cfg.im_end_id; }
     if (sampled && (s->form & 4)) {  // the filters of the sampled rows; the penalty's history: this step's column of the slot's emitted frames
       sa.filters = s->filt_tab;
       sa.hist = s->codes + step; sa.hist_slot_stride = (int64_t)s->max_frames * (1 + s->e->cfg.n_fast);
@@ -498,7 +506,7 @@ SampleArgs pick_args(const SmolttsSession* s, int step) {
 }
 
 // The commit kernel's greedy picks read the head GEMMs' tile candidates where run_tail has had them written (same conditions there)
-bool commit_cand_slow(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && !slow_sampled(s) && s->B < 256; }
+bool commit_cand_slow(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && !slow_sampled(s) && !length_on(s) && s->B < 256; }
 bool commit_cand_last(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && !fast_sampled(s) && s->B < 256; }
 
 // commit (optional) + next-frame mask + embedding of every slot's current column (see commit_embed_kernel); `picks`: the
@@ -523,10 +531,14 @@ int launch_commit_embed(SmolttsSession* s, int do_commit, int advance_pos, hipSt
     if (commit_cand_last(s)) { a.last_cand = s->cand; a.last_tiles = (c.codebook_size + 15) / 16; }
   }
   const EmitDev em{s->x3n, gamma_at(e, e->w.layers[0].attn_norm), nullptr, nullptr, s->ssq};
-  if (picks && (a.slow_sa.filters || a.last_sa.filters))
-    hipLaunchKernelGGL(commit_embed_kernel<true>, dim3(s->B), dim3(256), 0, st, a, embed_tables(e), s->xt, em);
-  else
-    hipLaunchKernelGGL(commit_embed_kernel<false>, dim3(s->B), dim3(256), 0, st, a, embed_tables(e), s->xt, em);
+  const bool filters = picks && (a.slow_sa.filters || a.last_sa.filters), length = picks && a.slow_sa.length;
+#define ST_COMMIT(F, L) hipLaunchKernelGGL((commit_embed_kernel<F, L>), dim3(s->B), dim3(256), 0, st, a, embed_tables(e), s->xt, em)
+  if (length) {
+    if (filters) ST_COMMIT(true, true); else ST_COMMIT(false, true);
+  } else {
+    if (filters) ST_COMMIT(true, false); else ST_COMMIT(false, false);
+  }
+#undef ST_COMMIT
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }
@@ -677,12 +689,12 @@ int stage_upload(SmolttsSession* s, const int32_t* slots_host, const int32_t* la
 }
 
 void drop_multi_graphs(SmolttsSession* s) {
-  for (int f = 0; f < 8; ++f)
+  for (int f = 0; f < GRAPH_FORMS; ++f)
     if (s->multi_ready[f]) { (void)hipGraphExecDestroy(s->multi_exec[f]); s->multi_ready[f] = false; }
 }
 
 void drop_graphs(SmolttsSession* s) {
-  for (int f = 0; f < 8; ++f) {
+  for (int f = 0; f < GRAPH_FORMS; ++f) {
     if (s->graph_ready[f]) { (void)hipGraphExecDestroy(s->graph_exec[f]); s->graph_ready[f] = false; }
     if (s->tail_ready[f]) { (void)hipGraphExecDestroy(s->tail_exec[f]); s->tail_ready[f] = false; }
   }
@@ -725,15 +737,19 @@ int arm_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos
 }
 
 // The form of the frame launches: bit 0 = some slot samples its slow token, bit 1 = some slot samples its depth codes, bit 2 = some
-// slot's filter entry is on (the sampled picks are then the FILTERS instantiations; without it they are the parent's kernels).  Outside
-// slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
+// slot's filter entry is on (the sampled picks are then the FILTERS instantiations; without it they are the parent's kernels), bit 3 =
+// some slot's length entry is on (the slow pick is then the LENGTH instantiation over the row of logits; it acts on greedy rows too, so
+// it outlives the rule that clears the filter bit).  Outside slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
 // point that launches or captures picks, after the last change of the table.
 void pick_form(SmolttsSession* s) {
-  int f = 0;
+  int f = 0, len = 0;
   if (s->slot_mode)
-    for (int b = 0; b < s->B; ++b) f |= (s->h_slot[b].temp > 0.f ? 1 : 0) | (s->h_slot[b].fast_temp > 0.f ? 2 : 0) | (s->h_filt_on[b] ? 4 : 0);
+    for (int b = 0; b < s->B; ++b) {
+      f |= (s->h_slot[b].temp > 0.f ? 1 : 0) | (s->h_slot[b].fast_temp > 0.f ? 2 : 0) | (s->h_filt_on[b] ? 4 : 0);
+      len |= s->h_len_on[b] ? 8 : 0;
+    }
   if ((f & 3) == 0) f = 0;  // nothing samples: the filters have nothing to act on
-  s->form = f;
+  s->form = f | len;
 }
 
 // Record `body` (a fixed launch sequence on the given stream) into an executable graph.
@@ -1099,6 +1115,7 @@ void smoltts_session_destroy(SmolttsSession* s) {
   if (s->h_slot_stage) (void)hipHostFree(s->h_slot_stage);
   delete[] s->h_slot;
   delete[] s->h_filt_on;
+  delete[] s->h_len_on;
   delete s;
 }
 
@@ -1277,7 +1294,9 @@ int smoltts_session_set_sampling(SmolttsSession* s, float temp, float fast_temp,
 namespace {
 size_t slot_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotSampling) + sizeof(int)); }
 size_t filt_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotFilters) + sizeof(int)); }
-size_t ring_area_bytes(const SmolttsSession* s) { return slot_area_bytes(s) + filt_area_bytes(s); }
+size_t len_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotLength) + sizeof(int)); }
+// (the length part is padded to 8 bytes: every area of the ring starts with sampling entries, which hold a uint64_t)
+size_t ring_area_bytes(const SmolttsSession* s) { return slot_area_bytes(s) + filt_area_bytes(s) + ((len_area_bytes(s) + 7) & ~(size_t)7); }
 
 // Enter slot mode (first per-slot call of either kind): host mirror, pinned ring, events; every slot greedy with seed 0 and
 // its filters off
@@ -1290,6 +1309,9 @@ int enter_slot_mode(SmolttsSession* s, hipStream_t st) {
   delete[] s->h_filt_on;
   s->h_filt_on = new (std::nothrow) bool[B]();
   ST_REQUIRE(s->h_filt_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
+  delete[] s->h_len_on;
+  s->h_len_on = new (std::nothrow) bool[B]();
+  ST_REQUIRE(s->h_len_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
   if (hipHostMalloc((void**)&s->h_slot_stage, ring_area_bytes(s) * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
     s->h_slot_stage = nullptr;
     delete[] s->h_slot;
@@ -1313,8 +1335,10 @@ int enter_slot_mode(SmolttsSession* s, hipStream_t st) {
   }
   s->slot_tab = s->slot_tab_area;
   s->filt_tab = s->filt_tab_area;
+  s->len_tab = s->len_tab_area;
   ST_CHECK_HIP(hipMemsetAsync(s->slot_tab, 0, B * sizeof(SmolttsSlotSampling), st));
   ST_CHECK_HIP(hipMemsetAsync(s->filt_tab, 0, B * sizeof(SmolttsSlotFilters), st));
+  ST_CHECK_HIP(hipMemsetAsync(s->len_tab, 0, B * sizeof(SmolttsSlotLength), st));
   s->slot_mode = true;
   drop_graphs(s);  // (the session-wide set: slot mode builds its own)
   return SMOLTTS_OK;
@@ -1356,7 +1380,7 @@ int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_ho
   ST_CHECK_HIP(hipMemcpyAsync(up, h, area, hipMemcpyHostToDevice, st));
   ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
   s->slot_ev_live[k] = true;
-  hipLaunchKernelGGL(slot_sampling_scatter_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->slot_tab);
+  hipLaunchKernelGGL(slot_scatter_kernel<SmolttsSlotSampling>, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->slot_tab);
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }
@@ -1402,7 +1426,48 @@ int smoltts_session_set_slot_filters(SmolttsSession* s, const int32_t* slots_hos
   ST_CHECK_HIP(hipMemcpyAsync(up, h, filt_area_bytes(s), hipMemcpyHostToDevice, st));
   ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
   s->slot_ev_live[k] = true;
-  hipLaunchKernelGGL(slot_filters_scatter_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->filt_tab);
+  hipLaunchKernelGGL(slot_scatter_kernel<SmolttsSlotFilters>, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->filt_tab);
+  ST_CHECK_HIP(hipGetLastError());
+  return SMOLTTS_OK;
+}
+
+// The length entries of slot mode, uploaded like the other two tables (the length part of the next ring area, one copy + one scatter
+// launch on `stream`).  Whether any entry is on is bit 3 of the graph form (pick_form): no graph is dropped here.
+int smoltts_session_set_slot_length(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* min_frames_host,
+                                    const float* eos_bias_host, void* stream) {
+  ST_REQUIRE(s && (n == 0 || (slots_host && min_frames_host && eos_bias_host)), SMOLTTS_E_INVALID, "session_set_slot_length: null argument");
+  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_length: %d entries, session holds %d slots", n, s->B);
+  for (int i = 0; i < n; ++i) {
+    ST_TRY(check_slot("session_set_slot_length", slots_host[i], s->B));
+    for (int j = 0; j < i; ++j)
+      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_length: slot %d listed twice", slots_host[i]);
+    const float b = eos_bias_host[i];
+    ST_REQUIRE(min_frames_host[i] >= 0 && min_frames_host[i] <= SMOLTTS_LENGTH_MAX_FRAMES && b - b == 0.f, SMOLTTS_E_INVALID,
+               "session_set_slot_length: slot %d: 0 <= min_frames <= %d, eos_bias finite", slots_host[i], SMOLTTS_LENGTH_MAX_FRAMES);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t B = s->B;
+  ST_TRY(enter_slot_mode(s, st));
+  if (n == 0) return SMOLTTS_OK;
+  const int k = s->slot_next;
+  s->slot_next = (k + 1) % STAGE_RING;
+  if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
+  SmolttsSlotLength* h = reinterpret_cast<SmolttsSlotLength*>(s->h_slot_stage + (size_t)k * ring_area_bytes(s) + slot_area_bytes(s) + filt_area_bytes(s));
+  int* hi = reinterpret_cast<int*>(h + B);
+  for (int i = 0; i < n; ++i) {
+    SmolttsSlotLength en;
+    memset(&en, 0, sizeof(en));
+    en.min_frames = min_frames_host[i];
+    en.eos_bias = eos_bias_host[i];
+    h[i] = en;
+    hi[i] = slots_host[i];
+    s->h_len_on[slots_host[i]] = en.min_frames > 0 || en.eos_bias != 0.f;
+  }
+  SmolttsSlotLength* up = s->len_tab_area + B;  // device upload area: the same layout as the ring area's length part
+  ST_CHECK_HIP(hipMemcpyAsync(up, h, len_area_bytes(s), hipMemcpyHostToDevice, st));
+  ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
+  s->slot_ev_live[k] = true;
+  hipLaunchKernelGGL(slot_scatter_kernel<SmolttsSlotLength>, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->len_tab);
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }

@@ -36,8 +36,8 @@ int launch_embed(const int32_t* cols, int n_rows, int n_code_rows, const void* t
 // Row pick (argmax_dev.h) + optionally the next depth step's input: the embedding row of the picked code
 // (lm/generate.py:134-140: fast_embeddings(code + i*codebook_size)) as fp32 residual row (+ X3 operand / sums of squares when a
 // GEMM consumes it), and / or the precomputed layer-0 q | k | v of that row (QkvGather: no wqkv launch in the next step).
-// FILTERS: the instantiation whose pick reads SampleArgs.filters (launched only when that pointer is set)
-template <bool FILTERS>
+// FILTERS: the instantiation whose pick reads SampleArgs.filters (launched only when that pointer is set); LENGTH: SampleArgs.length
+template <bool FILTERS, bool LENGTH>
 __global__ __launch_bounds__(256) void argmax_kernel(const float* logits, int n_cols, long ld, int* ids, int ids_stride,
                                                      float* margin, const int* margin_mask, const uint16_t* emb,
                                                      int emb_row_offset, int dim, float* xnext, EmitDev emit, SampleArgs sa, QkvGather qg) {
@@ -47,9 +47,9 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* logits, int n_
   int id;
   if constexpr (FILTERS) {
     __shared__ FilterScratch F;
-    id = argmax_row<true>(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S, &F);
+    id = argmax_row<true, LENGTH>(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S, &F);
   } else {
-    id = argmax_row(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S);
+    id = argmax_row<false, LENGTH>(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S);
   }
   if (tid == 0) ids[(long)r * ids_stride] = id;
   if (emb == nullptr) return;
@@ -96,12 +96,16 @@ int launch_argmax(const float* logits, int n_rows, int n_cols, int64_t ld, int32
   ST_REQUIRE(emb == nullptr || (xnext && dim % 4 == 0), SMOLTTS_E_INVALID, "argmax: bad gather arguments");
   ST_REQUIRE(qg.table == nullptr || (qg.rope && qg.q_out && qg.kc && qg.vc && qg.pos >= 0 && qg.pos < qg.cache_len), SMOLTTS_E_INVALID,
              "argmax: bad q|k|v gather arguments");
-  if (sa.filters)
-    hipLaunchKernelGGL(argmax_kernel<true>, dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, ids, ids_stride, margin,
-                       margin_mask, (const uint16_t*)emb, emb_row_offset, dim, xnext, e, sa, qg);
-  else
-    hipLaunchKernelGGL(argmax_kernel<false>, dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, ids, ids_stride, margin,
-                       margin_mask, (const uint16_t*)emb, emb_row_offset, dim, xnext, e, sa, qg);
+  ST_REQUIRE(sa.length == nullptr || sa.table, SMOLTTS_E_INVALID, "argmax: length entries need the per-row table");
+#define ST_ARGMAX(F, L)                                                                                                                 \
+  hipLaunchKernelGGL((argmax_kernel<F, L>), dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, ids, ids_stride, margin, \
+                     margin_mask, (const uint16_t*)emb, emb_row_offset, dim, xnext, e, sa, qg)
+  if (sa.length) {
+    if (sa.filters) ST_ARGMAX(true, true); else ST_ARGMAX(false, true);
+  } else {
+    if (sa.filters) ST_ARGMAX(true, false); else ST_ARGMAX(false, false);
+  }
+#undef ST_ARGMAX
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }

@@ -57,12 +57,20 @@ def _apply_slot_sampling(session: LMSession, slots: Sequence[int], sampling: Seq
                                  [sampling[i].top_k if o else 0 for i, o in zip(todo, on)],
                                  [sampling[i].repetition_penalty if o else 0.0 for i, o in zip(todo, on)],
                                  [sampling[i].repetition_window if o else 0 for i, o in zip(todo, on)])
+    # ... and their length entries, by the same rule (a recycled slot must not inherit its predecessor's)
+    todo = [i for i, (b, r) in enumerate(zip(slots, sampling)) if r.length_on or b in session.length_slots]
+    if todo:
+        session.set_slot_length([slots[i] for i in todo], [sampling[i].min_frames or 0 for i in todo],
+                                [sampling[i].eos_bias or 0.0 for i in todo])
 
 
 def resolve_sampling(sampling, settings: GenerationSettings, n: int) -> Optional[List[RequestSampling]]:
-    """``sampling=`` of the façade -> one resolved ``RequestSampling`` per utterance (None stays None: session-wide mode)."""
+    """``sampling=`` of the façade -> one resolved ``RequestSampling`` per utterance (None stays None: session-wide mode, unless
+    the settings turn the length control on, which exists in slot mode only: every utterance then takes the settings whole)."""
     if sampling is None:
-        return None
+        if not (settings.min_frames or settings.eos_bias):
+            return None
+        sampling = RequestSampling(seed=settings.seed)
     items = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * n
     if len(items) != n:
         raise ValueError(f"sampling: {len(items)} entries for {n} inputs")
@@ -117,6 +125,7 @@ class BatchGenerator:
         self._emitted = np.zeros(self.B, dtype=np.int64)
         self._per_sync = max(1, frames_per_sync)
         self._pending: List[List[Optional[VQToken]]] = []
+        self.last_slow: List[Optional[int]] = [None] * self.B  # each utterance's last emitted slow id so far
         # wall-clock figures of the reference (prefill ms, frames/s, x realtime: lm/generate.py:187-214), from events on the
         # launch stream so that measuring does not add a synchronisation
         self._ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]  # before prefill, after it, after the last decode
@@ -152,6 +161,14 @@ class BatchGenerator:
                 self._pending.append(row)
         self._emitted = np.maximum(self._emitted, n_frames)
         self._all_done = bool(done.all())
+        self.last_slow = [int(codes[b, n_frames[b] - 1, 0]) if n_frames[b] > 0 else None for b in range(self.B)]
+
+    def finish_reasons(self) -> List[str]:
+        """Per utterance, why it ended (``config.finish_reason`` of its last emitted slow id), once the generator is through."""
+        from .config import finish_reason
+
+        im_end = self.engine.token_config.im_end_id
+        return [finish_reason([] if s is None else [s], im_end) for s in self.last_slow]
 
     def __next__(self) -> List[Optional[VQToken]]:
         if not self._pending:

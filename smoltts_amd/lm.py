@@ -112,6 +112,7 @@ class LMSession(ClosesOnDel):
         self.engine, self.lib = engine, engine.lib
         self.B = max_batch
         self.filtered_slots = set()  # slots whose filter entry on the device is on (set_slot_filters)
+        self.length_slots = set()  # slots whose length entry on the device is on (set_slot_length)
         self.max_seq = max_seq or engine.cfg.max_seq_len
         self.max_rows = max(max_rows, max_batch)
         self.max_frames = max_frames
@@ -350,6 +351,20 @@ class LMSession(ClosesOnDel):
             (C.c_int32 * max(n, 1))(*[int(w) for w in window]), current_stream_ptr()), "smoltts_session_set_slot_filters")
         for b, p, k, r, w in zip(slots, top_p, top_k, penalty, window):
             (self.filtered_slots.add if (0 < p < 1 or k > 0 or (r > 1 and w > 0)) else self.filtered_slots.discard)(int(b))
+
+    def set_slot_length(self, slots: Sequence[int], min_frames: Sequence[int], eos_bias: Sequence[float]) -> None:
+        """Per-slot length control of the slow pick (``smoltts_session_set_slot_length``): while slot ``slots[i]`` has emitted fewer
+        than ``min_frames[i]`` frames its ``<|im_end|>`` column cannot be picked (0: off), and ``eos_bias[i]`` is added to that
+        logit (0: off) -- for greedy and sampled slow tokens alike (``sampling.length_patch``).  Queued on the current stream like
+        ``set_slot_sampling``; a new tenant without the option needs an off entry, or it inherits its predecessor's."""
+        n = len(slots)
+        if not (len(min_frames) == len(eos_bias) == n):
+            raise ValueError("slot length: one value per slot in every list")
+        check(self.lib.smoltts_session_set_slot_length(
+            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_int32 * max(n, 1))(*[int(m) for m in min_frames]),
+            (C.c_float * max(n, 1))(*[float(x) for x in eos_bias]), current_stream_ptr()), "smoltts_session_set_slot_length")
+        for b, m, x in zip(slots, min_frames, eos_bias):
+            (self.length_slots.add if (m > 0 or x != 0) else self.length_slots.discard)(int(b))
 
     def measure_duplicate(self, code: int = -1, n_filter: int = 0) -> None:
         """Measurement aid (this session only): issue every launch of one kernel class twice; -1 switches it off."""

@@ -270,6 +270,14 @@ class SegmentPlan:
         """Segment k's copy of ``base`` (a resolved ``RequestSampling``, or ``GenerationSettings``) with ``segment_seed``."""
         return replace(base, seed=segment_seed(base.seed, k))
 
+    def length_bounds(self, k: int, sampling, max_new_tokens: int, min_frames_per_byte: Optional[float] = None,
+                      max_frames_per_byte: Optional[float] = None):
+        """(sampling, max_new_tokens) of segment k under the bounds from its own text's length (``config.length_bounds``): every
+        segment is an utterance whose frame counter starts at 0."""
+        from .config import length_bounds
+
+        return length_bounds(self.segs[k].text, sampling, max_new_tokens, min_frames_per_byte, max_frames_per_byte)
+
 
 # ---------------------------------------------------------------------------------- text that arrives in pieces
 def _tag_may_follow(s: str) -> bool:
@@ -578,3 +586,4 @@ class GrowingPlan:
 
     prompt = SegmentPlan.prompt
     sampling = staticmethod(SegmentPlan.sampling)
+    length_bounds = SegmentPlan.length_bounds

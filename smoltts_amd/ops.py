@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import abi as E
-from .abi import Gemm3Args, PickArgs, SlotFilters, SlotSampling
+from .abi import Gemm3Args, PickArgs, SlotFilters, SlotLength, SlotSampling
 from .device import current_stream_ptr, dptr
 from .packing import tile_t16x32, tile_w3
 
@@ -228,6 +228,45 @@ def sample_rows_filtered(logits: torch.Tensor, table: torch.Tensor, filters: tor
     ids = torch.empty(R, dtype=torch.int32, device=logits.device)
     _k("smoltts_k_sample_rows_filtered", dptr(logits), R, logits.shape[1], logits.stride(0), dptr(table), dptr(filters), dptr(frames),
        dptr(history), dptr(history_len), int(step), dptr(ids))
+    return ids
+
+
+def slot_length_table(min_frames, eos_bias, device="cuda") -> torch.Tensor:
+    """Rows of ``SmolttsSlotLength`` (min_frames, eos_bias, 0, 0: 16 bytes each) as a uint8 device tensor."""
+    import numpy as np
+
+    a = np.zeros(len(min_frames), np.dtype(SlotLength))
+    a["min_frames"] = np.asarray(min_frames, np.int32)
+    a["eos_bias"] = np.asarray(eos_bias, np.float32)
+    return torch.from_numpy(a.view(np.uint8).copy()).to(device)
+
+
+def sample_rows_length(logits: torch.Tensor, table: torch.Tensor, length: torch.Tensor, im_end: int, frames: Optional[torch.Tensor] = None,
+                       step: int = 0, filters: Optional[torch.Tensor] = None, history: Optional[torch.Tensor] = None,
+                       history_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``smoltts_k_sample_rows_length``: ``sample_rows`` (``filters`` None) or ``sample_rows_filtered`` with row r's length entry
+    ``length`` row r (``slot_length_table``) acting on column ``im_end`` at step 0, the row's frame counter being ``frames[r]``
+    (None: r) -- the pick of ``sampling.length_patch`` of the row."""
+    R = logits.shape[0]
+    if table.dtype != torch.uint8 or table.numel() < C.sizeof(SlotSampling) * R:
+        raise ValueError("table: 24 bytes per row (slot_sampling_table)")
+    if length.dtype != torch.uint8 or length.numel() < C.sizeof(SlotLength) * R:
+        raise ValueError("length: 16 bytes per row (slot_length_table)")
+    if not 0 <= int(im_end) < logits.shape[1]:
+        raise ValueError("im_end: a column of the row")
+    if frames is not None and (frames.dtype != torch.int32 or frames.numel() < R):
+        raise ValueError("frames: int32, one per row")
+    if filters is not None:
+        if filters.dtype != torch.uint8 or filters.numel() < C.sizeof(SlotFilters) * R:
+            raise ValueError("filters: 32 bytes per row (slot_filter_table)")
+        if history is None or history.dtype != torch.int32 or tuple(history.shape) != (R, 64) or not history.is_contiguous():
+            raise ValueError("history: contiguous int32 [rows, 64]")
+        if history_len is None or history_len.dtype != torch.int32 or history_len.numel() < R:
+            raise ValueError("history_len: int32, one per row")
+    ids = torch.empty(R, dtype=torch.int32, device=logits.device)
+    _k("smoltts_k_sample_rows_length", dptr(logits), R, logits.shape[1], logits.stride(0), dptr(table), dptr(filters), dptr(frames),
+       dptr(history if filters is not None else None), dptr(history_len if filters is not None else None), dptr(length), int(im_end),
+       int(step), dptr(ids))
     return ids
 
 

@@ -12,6 +12,9 @@ model may name the other one; ``gumbel_keys`` gives the keys to check that margi
 device's order: repetition penalty over the history ids, ``top_k``, ``top_p``, then ``min_p`` and the unchanged Gumbel key.  The
 device sums fp32 ``expf`` masses (rounded down to multiples of 2^-40, exactly); a row whose nucleus edge lies within
 ``TOP_P_EDGE_MARGIN`` (relative) of ``top_p`` may keep or drop its edge column there: ``top_p_edge`` names that column.
+
+``length_patch`` models the per-request length control of the slow pick (``SmolttsSlotLength``): the row a pick
+sees, in front of everything above.  It is exact: one rounded fp32 add, or a store of -inf.
 """
 from __future__ import annotations
 
@@ -157,3 +160,15 @@ def top_p_edge(logits, temp: float, top_k: int = 0, top_p: float = 1.0, penalty:
     dist = np.where(keep, np.abs(above / total - tp) / tp, np.inf)
     j = int(np.argmin(dist))
     return j, float(dist[j])
+
+
+def length_patch(logits, im_end: int, frame: int, min_frames: int = 0, eos_bias: float = 0.0) -> np.ndarray:
+    """The fp32 slow-logit row as the pick of frame ``frame`` sees it under a length entry: ``x[im_end] + fp32(eos_bias)`` (one
+    rounded fp32 add), then -inf while ``frame < min_frames``.  An off entry (``min_frames <= 0``, ``eos_bias == 0``) returns
+    the row unchanged.  The greedy pick is ``argmax`` of this row; a sampled pick runs its filters and keys on it."""
+    x = np.array(logits, dtype=np.float32, copy=True)
+    if eos_bias != 0:
+        x[im_end] = np.float32(x[im_end]) + np.float32(eos_bias)
+    if frame < min_frames:
+        x[im_end] = -np.inf
+    return x

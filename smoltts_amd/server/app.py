@@ -21,7 +21,7 @@ import numpy as np
 from fastapi import APIRouter, FastAPI, HTTPException, Query, Request, Response
 from fastapi.exceptions import RequestValidationError
 from fastapi.responses import JSONResponse, StreamingResponse
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, model_validator
 
 from ..formats import lin2ulaw
 from .wav import pcm_to_wav_bytes
@@ -44,6 +44,11 @@ class TTSCore:
         self.watermark = block.to_watermark() if block is not None else None  # the key a recording is tested against
         self.watermark_apply = block.apply if block is not None else None
         self._segments_lock = threading.Lock()
+        # the model-only path: the settings' bounds from the text length are the façade's (a scheduler is built with its own)
+        if scheduler is None and hasattr(model, "min_frames_per_byte") and hasattr(model, "max_frames_per_byte"):
+            for name in ("min_frames_per_byte", "max_frames_per_byte"):
+                if self._setting(name, None) is not None:
+                    setattr(model, name, float(self._setting(name, None)))
 
     def _setting(self, name: str, default):
         st = self.settings
@@ -196,6 +201,7 @@ class TTSCore:
     def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000", sampling=None,
                        speed: Optional[float] = None, loudness=None, info: Optional[dict] = None):
         """-> (bytes, media type, the seed the request sampled with or None).  ``speed``: passed on only when it is not 1.
+        ``info["finish_reason"]``: ``"stop"`` or ``"length"`` (``config.finish_reason``).
         ``loudness``: the body's ``LoudnessFields``; ``info["loudness_gain_db"]`` is then the gain the utterance was given, and
         ``info["watermark"]`` true when the audio is marked."""
         used = None
@@ -209,12 +215,16 @@ class TTSCore:
                 pcm = np.concatenate(list(self.scheduler.iter_chunks(req)) or [np.zeros(0, np.float32)])
                 gain = getattr(req, "loudness_gain_db", None)
                 cut = getattr(req, "trimmed_s", 0.0)
+                reason = getattr(req, "finish_reason", None)
             else:
                 used = self._model_sampling(sampling)
                 kw = {"sampling": used} if used is not None else {}
                 pcm = np.asarray(self.model(input_text, str(voice), **kw, **sp)).flatten()
                 gain = getattr(self.model, "last_loudness_gain_db", None)
                 cut = getattr(self.model, "last_trimmed_s", 0.0)
+                reason = getattr(self.model, "last_finish_reason", None)
+            if info is not None and reason is not None:
+                info["finish_reason"] = reason
             if info is not None and ("trim_silence" in sp or "max_pause_s" in sp):
                 info["trimmed_ms"] = 1e3 * float(cut or 0.0)
             if info is not None and "loudness" in sp:
@@ -353,6 +363,12 @@ def _mark_headers(info: dict) -> dict:
     return {"X-Watermark": "1"} if info.get("watermark") else {}
 
 
+def _finish_headers(info: dict) -> dict:
+    """``X-Finish-Reason: stop | length`` of a blocking response: whether the utterance ended with ``<|im_end|>`` or at its cap."""
+    r = info.get("finish_reason")
+    return {} if r is None else {"X-Finish-Reason": str(r)}
+
+
 class SamplingFields(BaseModel):
     """Per-request sampling (extension; the ElevenLabs body's ``seed``): omitted fields take the server's generation settings.
     A sampled response carries ``X-Seed``: the seed it used, drawn by the server when the body names none."""
@@ -365,16 +381,29 @@ class SamplingFields(BaseModel):
     top_k: Optional[int] = Field(default=None, ge=0, lt=2**31)
     repetition_penalty: Optional[float] = Field(default=None, ge=1, le=10)
     repetition_window: Optional[int] = Field(default=None, ge=1, le=64)
+    # length control, on greedy and sampled requests alike: ``<|im_end|>`` cannot be picked before ``min_frames``
+    # frames (12.5 a second; ``min_duration_s`` spells it in seconds of audio, ceil(s * 12.5): one of the two), ``eos_bias`` is
+    # added to its logit.  A blocking response carries ``X-Finish-Reason``
+    min_frames: Optional[int] = Field(default=None, ge=0, le=1024)
+    min_duration_s: Optional[float] = Field(default=None, ge=0, le=1024 / 12.5, allow_inf_nan=False)
+    eos_bias: Optional[float] = Field(default=None, ge=-100, le=100, allow_inf_nan=False)
+
+    @model_validator(mode="after")
+    def _one_minimum(self):
+        if self.min_frames is not None and self.min_duration_s is not None:
+            raise ValueError("give min_frames or min_duration_s, not both")
+        return self
 
     def request_sampling(self):
+        from ..config import RequestSampling, min_frames_from
+
+        min_frames = min_frames_from(self.min_frames, self.min_duration_s)
         fields = (self.seed, self.temperature, self.fast_temperature, self.min_p, self.top_p, self.top_k, self.repetition_penalty,
-                  self.repetition_window)
+                  self.repetition_window, min_frames, self.eos_bias)
         if all(v is None for v in fields):
             return None
-        from ..config import RequestSampling
-
         return RequestSampling(self.temperature, self.fast_temperature, self.min_p, self.seed, self.top_p, self.top_k,
-                               self.repetition_penalty, self.repetition_window)
+                               self.repetition_penalty, self.repetition_window, min_frames, self.eos_bias)
 
 
 # speaking speed (OpenAI's ``speed``, ElevenLabs' ``voice_settings.speed``): pitch-preserving time stretch on the GPU (tsm.py);
@@ -485,7 +514,8 @@ def openai_speech(item: SpeechRequest, http_request: Request):
     audio, media_type, seed = core.generate_audio(item.input, item.voice, item.response_format + "_24000", sampling=item.request_sampling(),
                                                   speed=item.speed, loudness=item, info=info)
     return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed),
-                                                           **_gain_headers(info), **_mark_headers(info), **_trim_headers(info)})
+                                                           **_gain_headers(info), **_mark_headers(info), **_trim_headers(info),
+                                                           **_finish_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}")
@@ -499,7 +529,7 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
     return Response(content=content, media_type=media_type, headers={
         "Content-Disposition": f'attachment; filename="elevenlabs_speech.{fmt.split("_")[0]}"',
         "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed), **_gain_headers(info), **_mark_headers(info),
-        **_trim_headers(info)})
+        **_trim_headers(info), **_finish_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}/stream")

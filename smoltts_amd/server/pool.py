@@ -34,6 +34,7 @@ class _PoolRequest:
     loudness_gain_db: Optional[float] = None  # a blocking request with a loudness: the gain applied (known at its end)
     trimmed_s: float = 0.0  # a blocking request that trims silence: the seconds cut (known at its end)
     watermark: bool = False  # the audio carries the workers' watermark
+    finish_reason: Optional[str] = None  # "stop" / "length" (config.finish_reason), known at the request's end
 
 
 @dataclass
@@ -98,7 +99,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
         try:
             for chunk in sched.iter_chunks(req):
                 res_q.put((rid, "chunk", np.ascontiguousarray(chunk)))  # float32, or int16 / uint8 for a streamed output_format
-            res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0))))
+            res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0), getattr(req, "finish_reason", None))))
         except Exception as e:
             res_q.put((rid, "error", (type(e).__name__, str(e))))
         finally:
@@ -491,7 +492,7 @@ class GpuPool:
                 if not req.cancelled:
                     req.out.put(payload)
             elif kind == "end":
-                req.loudness_gain_db, req.trimmed_s = payload
+                req.loudness_gain_db, req.trimmed_s, req.finish_reason = payload
                 self._finish(req, None)
             elif kind == "result":  # a registry message's answer
                 self._finish(req, ("result", payload))
@@ -560,7 +561,8 @@ def scheduler_from_settings(settings):
     st = settings if isinstance(settings, ServerSettings) else ServerSettings(**settings)
     model = SmolTTS(checkpoint_dir=str(st.get_checkpoint_dir()), mimi_checkpoint=st.mimi_checkpoint, weight_format=st.weight_format)
     return BatchScheduler(model, max_batch=st.max_batch, generation_settings=st.generation.to_settings(), codec_products=st.codec_products,
-                          watermark=st.watermark.to_watermark() if st.watermark is not None else None)
+                          watermark=st.watermark.to_watermark() if st.watermark is not None else None,
+                          min_frames_per_byte=st.min_frames_per_byte, max_frames_per_byte=st.max_frames_per_byte)
 
 
 def synthetic_scheduler(model: str = "tiny", seed: int = 21, mimi_seed: int = 5, max_batch: int = 4, frames_per_tick: int = 2,

@@ -65,6 +65,14 @@ class _Request:
     watermark: bool = False   # the audio gets the scheduler's watermark: a stream in its codec pass, a blocking utterance whole, last
     trim: Optional[tuple] = None  # (trim the ends, the pause cap in blocks, the threshold) of a request that trims silence (trim.py)
     trimmed_s: float = 0.0    # blocking: the seconds of silence that were cut (set before the audio goes out)
+    finish_reason: Optional[str] = None  # "stop" / "length" (config.finish_reason), valid once the request has ended; a segmented
+                                         # request is "length" if any segment was
+    reasons: list = field(default_factory=list)  # ... of the utterances (segments) that have ended so far
+    frame_counts: list = field(default_factory=list)  # ... and the frames each of them was given (its <|im_end|> frame included)
+    request_cap: Optional[int] = None    # the request's own max_new_tokens; ``max_new_tokens`` is the cap of the utterance (segment)
+                                         # in the slot, which the scheduler's max_frames_per_byte may lower
+    slot_sampling: object = None         # the entry of the utterance (segment) in the slot: ``sampling`` (the segment's) with the
+                                         # scheduler's min_frames_per_byte applied
 
 
 @dataclass
@@ -186,9 +194,12 @@ class BatchScheduler:
 
     def __init__(self, tts, max_batch: int = 32, frames_per_tick: int = 4, generation_settings=None, max_prompt_rows: int = 4096,
                  prefill_chunk: Optional[int] = 128, side_prefill: bool = True, side_prefill_min_active: Optional[int] = None,
-                 codec_products: int = 6, watermark=None):
+                 codec_products: int = 6, watermark=None, min_frames_per_byte: Optional[float] = None,
+                 max_frames_per_byte: Optional[float] = None):
         """``watermark`` (a ``watermark.Watermark``; None: no request can be marked): the one key of this scheduler's marked
-        requests; a request that does not say (``submit(watermark=None)``) is marked when there is one."""
+        requests; a request that does not say (``submit(watermark=None)``) is marked when there is one.
+        ``min_frames_per_byte`` / ``max_frames_per_byte`` (None: off): bounds on every utterance's length from its text's UTF-8
+        byte count, per segment on the long-text path (``config.length_bounds``)."""
         import torch
 
         from ..config import GenerationSettings
@@ -201,6 +212,7 @@ class BatchScheduler:
         if watermark is not None and not isinstance(watermark, Watermark):
             raise ValueError("watermark must be a smoltts_amd.watermark.Watermark or None")
         self.watermark = watermark
+        self.min_frames_per_byte, self.max_frames_per_byte = min_frames_per_byte, max_frames_per_byte
         self.tts = tts
         self.B = max_batch
         self.codec_products = codec_products  # SMOLTTS_MIMI_OPT_PRODUCTS of the codec sessions (6: fp32-grade)
@@ -602,6 +614,14 @@ class BatchScheduler:
             if req.prompt is None:
                 try:
                     v, sg, enc = req.voice_entry, req.seg, self.tts.prompt_encoder
+                    # the utterance's (segment's) length entry and cap: the request's own, within the bounds from its text
+                    from ..config import length_bounds
+
+                    if req.request_cap is None:
+                        req.request_cap = req.max_new_tokens
+                    ratios = (self.min_frames_per_byte, self.max_frames_per_byte)
+                    req.slot_sampling, req.max_new_tokens = (sg.plan.length_bounds(sg.k, sg.sampling, req.request_cap, *ratios) if sg is not None
+                                                             else length_bounds(req.text, req.sampling, req.request_cap, *ratios))
                     if sg is not None:  # segment k's chained prompt
                         from ..longform import voice_prefix
 
@@ -639,7 +659,7 @@ class BatchScheduler:
                 req.slot = self._free.pop(0)
             new.append(req)
         entries = {b: self._default_sampling for b in freed}
-        entries.update({r.slot: (r.seg.sampling if r.seg is not None else r.sampling) for r in new})
+        entries.update({r.slot: r.slot_sampling for r in new})
         self._write_sampling(entries)  # on the frame stream, ahead of the park / prefill of the new tenants
         if not new:
             return
@@ -944,6 +964,7 @@ class BatchScheduler:
         self._gpu_wait_s += time.perf_counter() - t
 
     def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery]) -> None:
+        from ..config import finish_reason, merge_finish_reasons
         from ..generate import semantic_columns
 
         stream_items = []  # the streams' share of this tick's codec pass: (request, pcm row, samples, last?) handed out by _deliver
@@ -974,6 +995,10 @@ class BatchScheduler:
             n = min(int(n_frames[slot]), r.max_new_tokens + 1)
             finished = bool(stream_ends(n_frames[slot], done[slot], r.max_new_tokens + 1))
             seg_more = r.seg is not None and not r.seg.final  # a segment follows this one
+            if finished:  # why: from the last slow id the request was given
+                r.reasons.append(finish_reason(codes[slot, :n, 0], tc.im_end_id))
+                r.frame_counts.append(n)
+                r.finish_reason = merge_finish_reasons(r.reasons)
             if r.stream:
                 # streaming requests decode every frame (__init__.py:88-92); this tick's PCM of the slot starts at its frame
                 # r.emitted (== f0 of the tick: one codec frame per LM frame)

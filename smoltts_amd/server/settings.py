@@ -35,11 +35,15 @@ class GenerationBlock(BaseModel):
     top_k: int = Field(default=0, ge=0, lt=2**31)
     repetition_penalty: float = Field(default=1.0, ge=1, le=10)
     repetition_window: int = Field(default=16, ge=1, le=64)
+    # extension: the length control of requests whose body does not name it (config.RequestSampling); both off
+    min_frames: int = Field(default=0, ge=0, le=1024)
+    eos_bias: float = Field(default=0.0, ge=-100, le=100, allow_inf_nan=False)
 
     def to_settings(self) -> _GenerationSettings:
         return _GenerationSettings(default_temp=self.default_temp, default_fast_temp=self.default_fast_temp, min_p=self.min_p,
                                    max_new_tokens=self.max_new_tokens, min_p_mode=self.min_p_mode, top_p=self.top_p, top_k=self.top_k,
-                                   repetition_penalty=self.repetition_penalty, repetition_window=self.repetition_window)
+                                   repetition_penalty=self.repetition_penalty, repetition_window=self.repetition_window,
+                                   min_frames=self.min_frames, eos_bias=self.eos_bias)
 
 
 class WatermarkBlock(BaseModel):
@@ -101,6 +105,13 @@ class ServerSettings(BaseModel):
     # long is spoken as it is
     idle_timeout_s: float = Field(default=10.0, gt=0, allow_inf_nan=False)
     flush_after_s: Optional[float] = Field(default=None, gt=0, allow_inf_nan=False)
+
+    # (extension) bounds on every utterance's length from its text's UTF-8 byte count n, per segment on the long-text path
+    # (config.length_bounds): min_frames = max(request's, floor(n * min_frames_per_byte)), at most the cap - 1;
+    # max_new_tokens = min(request's, ceil(n * max_frames_per_byte)), at least 1.  12.5 frames are one second of audio; the
+    # ratios depend on the checkpoint's speaking rate and are the operator's to measure: null (off) by default
+    min_frames_per_byte: Optional[float] = Field(default=None, ge=0, allow_inf_nan=False)
+    max_frames_per_byte: Optional[float] = Field(default=None, ge=0, allow_inf_nan=False)
 
     model_config = {"protected_namespaces": ()}
 
