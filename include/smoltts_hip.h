@@ -342,6 +342,25 @@ typedef struct SmolttsSlotLength {
 int smoltts_session_set_slot_length(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* min_frames_host,
                                     const float* eos_bias_host, void* stream);
 
+/* (ABI 9, additive) Score the slow token of slots_host[0 .. n): on_host[i] != 0 switches slot slots_host[i]'s score on.  Host flags
+ * only: nothing is uploaded and the call takes no stream (the first per-slot call of any kind puts the session in slot mode; when
+ * this is that call it waits for the device once).  The score of a frame is the log-probability, at temperature 1, of the slow id
+ * the slot emitted, under the fp32 row x' its pick saw -- after the length entry and the repetition penalty, before temperature,
+ * top_k, top_p and min_p:
+ *   z_j = fp32(x'_j - max x');  q_j = floor(expf(z_j) * 2^40);  S = sum_j q_j (exact);  lp = z_picked - (log S - 40 ln 2), as fp32.
+ * "Some slot scores" is bit 4 of the graph form.  In a form that has it the slow token is picked from the row of logits (as in a
+ * form whose slow token is sampled) and every row is scored; no id changes.  While no slot scores, the frames launch exactly the
+ * kernels they launch without this call.  Depth codes are not scored.  Host model: smoltts_amd/sampling.py (pick_logprob). */
+int smoltts_session_set_slot_score(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* on_host);
+
+/* (ABI 9, additive) The scores: float [max_batch][*stride], entry [slot][f] written with frame f of a slot while the form has bit
+ * 4 (any slot of such a form, asked or not); other entries keep what they held.  stride = max_frames; may be NULL. */
+int smoltts_session_logprobs(SmolttsSession* s, float** logprob_dev, int32_t* stride);
+
+/* (ABI 9, additive) Diagnostic: the slow head's fp32 logits of the latest frame, [max_batch][*ld] (ld = vocab_size; may be NULL),
+ * as the slow pick read them -- in front of the length entry and the penalty.  Overwritten by every frame. */
+int smoltts_session_slow_logits(SmolttsSession* s, float** logits_dev, int32_t* ld);
+
 /* Device pointers to the session's results (valid for the session's lifetime):
  *   codes      int32 [max_batch][max_frames][1 + n_fast]   emitted columns (slow id, codes)
  *   n_frames   int32 [max_batch]                            frames emitted so far per slot
@@ -1075,6 +1094,14 @@ int smoltts_k_sample_rows_length(const float* logits_dev, int32_t n_rows, int32_
                                  const SmolttsSlotFilters* filters_dev, const int32_t* frames_dev, const int32_t* history_dev,
                                  const int32_t* history_len_dev, const SmolttsSlotLength* length_dev, int32_t im_end, int32_t step,
                                  int32_t* ids_dev, void* stream);
+
+/* (ABI 9, additive) smoltts_k_sample_rows_length that also writes logprob_out_dev[r]: the log-probability, at temperature 1, of the
+ * id row r emitted under the row as its pick saw it (smoltts_session_set_slot_score has the definition).  length_dev may be NULL too
+ * (im_end is then ignored).  The ids are those of smoltts_k_sample_rows_length on the same arguments. */
+int smoltts_k_sample_rows_scored(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const SmolttsSlotSampling* table_dev,
+                                 const SmolttsSlotFilters* filters_dev, const int32_t* frames_dev, const int32_t* history_dev,
+                                 const int32_t* history_len_dev, const SmolttsSlotLength* length_dev, int32_t im_end, int32_t step,
+                                 int32_t* ids_dev, float* logprob_out_dev, void* stream);
 
 int smoltts_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, int32_t n_rows,
                         int32_t dim, float eps, float* out_dev, void* stream);

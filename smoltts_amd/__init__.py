@@ -76,6 +76,13 @@ class SmolTTS:
         # context); a segmented call is "length" if any segment was.  last_finish_reasons: one per input of generate_codes
         self.last_finish_reason: Optional[str] = None
         self.last_finish_reasons: List[str] = []
+        # scores of the last call whose sampling= asked for them (RequestSampling.logprobs / best_of): the float32
+        # log-probabilities of the (chosen) utterance's slow ids, their float64 mean, and per take of a best_of call its seed,
+        # mean_logprob, min_logprob, frames, finish_reason, chosen and codes.  last_logprobs_all: one array per input of generate_codes
+        self.last_logprobs = None
+        self.last_mean_logprob: Optional[float] = None
+        self.last_takes: Optional[list] = None
+        self.last_logprobs_all: Optional[list] = None
         # bounds on an utterance's (a segment's) length from its text's UTF-8 byte count (config.length_bounds);
         # None: off.  12.5 frames are one second of audio: the ratios are the operator's to measure
         self.min_frames_per_byte: Optional[float] = None
@@ -148,6 +155,9 @@ class SmolTTS:
 
         self.last_finish_reasons = gen.finish_reasons()
         self.last_finish_reason = merge_finish_reasons(self.last_finish_reasons)
+        # per input, the float32 scores of its frames (None where the input did not ask: RequestSampling.logprobs / best_of)
+        scores = gen.logprobs() if resolved is not None and any(r.scored for r in resolved) else None
+        self.last_logprobs_all = None if scores is None else [lp if r.scored else None for lp, r in zip(scores, resolved)]
         gen.close()
         if self.verbose and self.last_stats:
             st = self.last_stats
@@ -205,17 +215,27 @@ class SmolTTS:
         voice = voice if voice is not None else "heart"
         self.last_trimmed_s = 0.0
         self.last_finish_reason = None  # (known once the call is through)
+        self.last_takes = self.last_logprobs = self.last_mean_logprob = None
+        self._check_best_of(sampling, generation_settings, segmented=req.plan is not None)
         if req.plan is not None:
             pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling, req)
         else:
-            if self._bounds_on:
+            if self._bounds_on or sampling is not None:
                 from .generate import resolve_sampling
 
                 st = self._settings(generation_settings)
                 generation_settings, one = self._bounded(input, st, resolve_sampling(sampling, st, 1))
                 sampling = None if one is None else one[0]
-            codes = self.generate_codes([input], [voice], generation_settings, speakers=None if speaker is None else [speaker],
-                                        sampling=sampling)[0]
+            if sampling is not None and sampling.takes > 1:
+                codes = self._best_of(input, voice, speaker, generation_settings, sampling)
+            else:
+                codes = self.generate_codes([input], [voice], generation_settings, speakers=None if speaker is None else [speaker],
+                                            sampling=sampling)[0]
+                if self.last_logprobs_all is not None and self.last_logprobs_all[0] is not None:
+                    from .config import mean_logprob
+
+                    self.last_logprobs = self.last_logprobs_all[0]
+                    self.last_mean_logprob = mean_logprob(self.last_logprobs)
             pcm = self._trimmed(self.decode_codes(codes), req)
         if req.loudness is not None:
             from .stages import loudness_normalize
@@ -232,6 +252,40 @@ class SmolTTS:
 
             pcm = watermark_embed(pcm, marked, self.lm.device)
         return pcm
+
+    def _check_best_of(self, sampling, generation_settings, stream: bool = False, segmented: bool = False) -> None:
+        """``config.check_best_of`` of a call's ``sampling=`` (one entry, or a list of one), before any work."""
+        from .config import MAX_BEST_OF, RequestSampling, check_best_of
+
+        items = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling]
+        if not any(isinstance(r, RequestSampling) and r.takes > 1 for r in items):
+            return
+        st = self._settings(generation_settings)
+        for r in items:
+            if r is not None:
+                check_best_of(r.resolve(st, draw_seed=False), MAX_BEST_OF, stream=stream, segmented=segmented)
+
+    def _best_of(self, text: str, voice: str, speaker, generation_settings, sampling):
+        """The takes of a resolved ``best_of`` entry as one batch -> the winner's audio codes (``config.rank_takes``); only they
+        go through the codec.  Sets ``last_takes``, ``last_logprobs``, ``last_mean_logprob``, and ``last_sampling`` to the
+        winner's entry: a plain request with its seed gives the same audio."""
+        from .config import mean_logprob, rank_takes, take_sampling
+
+        n = sampling.takes
+        entries = [take_sampling(sampling, k) for k in range(n)]
+        codes = self.generate_codes([text] * n, [voice] * n, generation_settings, speakers=None if speaker is None else [speaker] * n,
+                                    sampling=entries)
+        scores, reasons = self.last_logprobs_all, self.last_finish_reasons
+        means = [mean_logprob(lp) for lp in scores]
+        order = rank_takes(list(zip(reasons, means)))
+        win = order[0]
+        self.last_takes = [{"seed": entries[k].seed, "mean_logprob": means[k], "min_logprob": float(scores[k].min()) if len(scores[k]) else float("-inf"),
+                            "frames": int(len(scores[k])), "finish_reason": reasons[k], "chosen": k == win, "codes": codes[k]} for k in range(n)]
+        self.last_logprobs, self.last_mean_logprob = scores[win], means[win]
+        self.last_sampling = [self.last_sampling[win]]
+        self.last_finish_reason = reasons[win]
+        self.last_finish_reasons = [reasons[win]]
+        return codes[win]
 
     def _trimmed(self, pcm, req, flags: int = 3):
         """``pcm``, one segment with ``flags`` (default: a plain utterance, first and final), through the trim stage when
@@ -360,6 +414,8 @@ class SmolTTS:
         from .request import parse_request
 
         self.last_finish_reason = None  # (known once the stream has been consumed to its end)
+        self.last_takes = self.last_logprobs = self.last_mean_logprob = None
+        self._check_best_of(sampling, generation_settings, stream=True)
         if not isinstance(input, (str, bytes)):
             yield from self._stream_incremental(iter(input), voice if voice is not None else "0", generation_settings, overlap,
                                                 reference_upsample, output_format, sampling, speed, container, segment, loudness,
@@ -386,6 +442,12 @@ class SmolTTS:
                                   speed_q=req.speed_q, container=req.container, loudness=req.loudness,
                                   start_gain_db=req.start_gain_db, watermark=marked, trim=req.trim_route)
             self.last_finish_reason = self._stream_reason(sess)
+            if self.last_sampling is not None and self.last_sampling[0].scored:
+                from .config import mean_logprob
+
+                _, n_frames, _, _ = sess.fetch()
+                self.last_logprobs = sess.fetch_logprobs()[0, :int(n_frames[0])].copy()
+                self.last_mean_logprob = mean_logprob(self.last_logprobs)
         finally:
             msess.close()
             sess.close()

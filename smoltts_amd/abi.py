@@ -186,6 +186,9 @@ SIGNATURES = {
     "smoltts_session_set_slot_sampling": (INT, "p p i p p p p p"),
     "smoltts_session_set_slot_filters": (INT, "p p i p p p p p"),
     "smoltts_session_set_slot_length": (INT, "p p i p p p"),
+    "smoltts_session_set_slot_score": (INT, "p p i p"),
+    "smoltts_session_logprobs": (INT, "p p* i*"),
+    "smoltts_session_slow_logits": (INT, "p p* i*"),
     "smoltts_session_outputs": (INT, "p p* p* p* p*"),
     "smoltts_session_kv_cache": (INT, "p p* p* Q*"),
     "smoltts_session_fast_kv_cache": (INT, "p p* p* Q*"),
@@ -276,6 +279,7 @@ SIGNATURES = {
     "smoltts_k_sample_rows": (INT, "p i i q p p i p p"),
     "smoltts_k_sample_rows_filtered": (INT, "p i i q p p p p p i p p"),
     "smoltts_k_sample_rows_length": (INT, "p i i q p p p p p p i i p p"),
+    "smoltts_k_sample_rows_scored": (INT, "p i i q p p p p p p i i p p p"),
     "smoltts_k_layernorm": (INT, "p p p i i f p p"),
     "smoltts_k_seanet_resblock": (INT, "i i i p q p p p p p q i p"),
     "smoltts_k_seanet_last": (INT, "i i p q p p p p p p p f p q p i p"),

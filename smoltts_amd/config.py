@@ -210,6 +210,7 @@ class GenerationSettings:
 FRAMES_PER_SECOND = 12.5  # Mimi frames (slow tokens) per second of audio
 MAX_MIN_FRAMES = 1024     # of the public interface; the device entry takes up to 2**30
 MAX_EOS_BIAS = 100.0
+MAX_BEST_OF = 8           # takes of one request (``RequestSampling.best_of``)
 
 
 def min_frames_from(min_frames=None, min_duration_s=None) -> Optional[int]:
@@ -263,6 +264,47 @@ def merge_finish_reasons(reasons) -> str:
     return "length" if any(r == "length" for r in reasons) else "stop"
 
 
+def take_seed(seed: int, k: int) -> int:
+    """The seed of take ``k`` of a ``best_of`` request: ``(seed + k) mod 2**64``.  Take 0 is the request without ``best_of``."""
+    return (int(seed) + int(k)) % 2**64
+
+
+def take_sampling(sampling: "RequestSampling", k: int) -> "RequestSampling":
+    """The resolved entry of take ``k``: a plain scored request with that take's seed."""
+    import dataclasses
+
+    return dataclasses.replace(sampling, seed=take_seed(sampling.seed, k), logprobs=True, best_of=None)
+
+
+def mean_logprob(logprobs) -> float:
+    """Mean score of an utterance in float64 over its frames as the host clipped them (its ``<|im_end|>`` frame included);
+    ``-inf`` for no frames."""
+    n = len(logprobs)
+    return float(sum(float(x) for x in logprobs) / n) if n else float("-inf")
+
+
+def rank_takes(takes) -> list:
+    """The order of a ``best_of`` request's takes, best first; ``takes[k]`` is ``(finish_reason, mean_logprob)`` of take k.
+    Takes that ended with ``"stop"`` come before takes that ended with ``"length"``, then the higher mean wins, then the lower k."""
+    return sorted(range(len(takes)), key=lambda k: (0 if takes[k][0] == "stop" else 1, -float(takes[k][1]), k))
+
+
+def check_best_of(sampling: "RequestSampling", slots: int, stream: bool = False, segmented: bool = False) -> None:
+    """The one check of ``best_of`` shared by every front end; ``sampling`` is resolved, ``slots`` the front end's slot count.
+    A request with one take passes."""
+    n = sampling.takes
+    if n <= 1:
+        return
+    if stream:
+        raise ValueError("best_of > 1 needs a blocking request: a stream's audio is out before the takes can be ranked")
+    if segmented:
+        raise ValueError("best_of > 1 is not available for segmented or incremental requests")
+    if (sampling.temperature or 0.0) <= 0:
+        raise ValueError("best_of > 1 needs a sampled slow token (temperature > 0): greedy takes are all the same")
+    if n > int(slots):
+        raise ValueError(f"best_of={n} exceeds the {int(slots)} slots of this engine")
+
+
 @dataclass
 class RequestSampling:
     """Sampling of one request (per-request settings of the server and the façade).  ``None`` fields take the server's or
@@ -277,7 +319,13 @@ class RequestSampling:
 
     Length control, ``None`` <- the settings' field of the same name: ``min_frames`` (0 .. 1024; 0 = off) keeps
     ``<|im_end|>`` from being picked before that many frames have been emitted; ``eos_bias`` (-100 .. 100; 0 = off) is added to
-    the ``<|im_end|>`` logit.  Both act on greedy and sampled slow tokens alike; the depth codes are never touched."""
+    the ``<|im_end|>`` logit.  Both act on greedy and sampled slow tokens alike; the depth codes are never touched.
+
+    Scores: ``logprobs`` asks for the log-probability, at temperature 1, of every slow id the request emits,
+    under the row its pick saw (after the length control and the repetition penalty, before temperature and the other filters).
+    ``best_of`` (1 .. 8; None or 1 = one take) draws that many takes, take k with seed ``(seed + k) mod 2**64``, and keeps the
+    one ``rank_takes`` puts first; more than one take implies ``logprobs``.  Blocking, unsegmented, sampled requests only
+    (``check_best_of``)."""
 
     temperature: Optional[float] = None
     fast_temperature: Optional[float] = None
@@ -289,9 +337,17 @@ class RequestSampling:
     repetition_window: Optional[int] = None
     min_frames: Optional[int] = None
     eos_bias: Optional[float] = None
+    logprobs: bool = False
+    best_of: Optional[int] = None
 
     def __post_init__(self):
         import math
+
+        if not isinstance(self.logprobs, bool):
+            raise ValueError(f"logprobs must be true or false, got {self.logprobs!r}")
+        n = self.best_of
+        if n is not None and not (isinstance(n, int) and not isinstance(n, bool) and 1 <= n <= MAX_BEST_OF):
+            raise ValueError(f"best_of must be an integer in [1, {MAX_BEST_OF}], got {n!r}")
 
         for name in ("temperature", "fast_temperature"):
             v = getattr(self, name)
@@ -316,6 +372,16 @@ class RequestSampling:
         b = self.eos_bias
         if b is not None and not (isinstance(b, (int, float)) and not isinstance(b, bool) and math.isfinite(b) and abs(b) <= MAX_EOS_BIAS):
             raise ValueError(f"eos_bias must be finite and in [-{MAX_EOS_BIAS:g}, {MAX_EOS_BIAS:g}], got {b!r}")
+
+    @property
+    def takes(self) -> int:
+        """How many takes the request draws (1 without ``best_of``)."""
+        return int(self.best_of or 1)
+
+    @property
+    def scored(self) -> bool:
+        """Whether the request's slow tokens are scored: it asked for ``logprobs``, or it has more than one take to rank."""
+        return bool(self.logprobs) or self.takes > 1
 
     @property
     def length_on(self) -> bool:
@@ -343,7 +409,7 @@ class RequestSampling:
         pick = lambda name: getattr(self, name) if getattr(self, name) is not None else getattr(settings, name)
         out = RequestSampling(max(t, 0.0), max(ft, 0.0), cut, self.seed, float(pick("top_p")), int(pick("top_k")),
                               float(pick("repetition_penalty")), int(pick("repetition_window")), int(pick("min_frames")),
-                              float(pick("eos_bias")))
+                              float(pick("eos_bias")), bool(self.logprobs), self.best_of)
         if out.seed is None and draw_seed and out.is_sampled:
             out.seed = int.from_bytes(os.urandom(8), "little")
         return out

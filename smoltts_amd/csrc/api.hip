@@ -117,6 +117,26 @@ int smoltts_k_sample_rows_length(const float* logits_dev, int32_t n_rows, int32_
                        (hipStream_t)stream);
 }
 
+int smoltts_k_sample_rows_scored(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const SmolttsSlotSampling* table_dev,
+                                 const SmolttsSlotFilters* filters_dev, const int32_t* frames_dev, const int32_t* history_dev,
+                                 const int32_t* history_len_dev, const SmolttsSlotLength* length_dev, int32_t im_end, int32_t step,
+                                 int32_t* ids_dev, float* logprob_out_dev, void* stream) {
+  ST_REQUIRE(table_dev && logprob_out_dev, SMOLTTS_E_INVALID, "k_sample_rows_scored: null table or output");
+  ST_REQUIRE(filters_dev == nullptr || (history_dev && history_len_dev), SMOLTTS_E_INVALID, "k_sample_rows_scored: filters without a history");
+  ST_REQUIRE(length_dev == nullptr || (im_end >= 0 && im_end < n_cols), SMOLTTS_E_INVALID,
+             "k_sample_rows_scored: im_end %d outside the row (%d columns)", im_end, n_cols);
+  SampleArgs sa{0.f, 0.f, 0, step, 0, frames_dev, nullptr, nullptr, table_dev};
+  if (filters_dev) {
+    sa.filters = filters_dev;
+    sa.hist = history_dev; sa.hist_slot_stride = SMOLTTS_FILTER_MAX_WINDOW; sa.hist_frame_stride = 1; sa.hist_frames = SMOLTTS_FILTER_MAX_WINDOW;
+    sa.hist_len = history_len_dev;
+  }
+  if (length_dev) { sa.length = length_dev; sa.im_end = im_end; }
+  sa.logprob = logprob_out_dev;  // (stride 0: row r's value at [r])
+  return launch_argmax(logits_dev, n_rows, n_cols, ld, ids_dev, 1, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, &sa,
+                       (hipStream_t)stream);
+}
+
 int smoltts_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, int32_t n_rows, int32_t dim, float eps,
                         float* out_dev, void* stream) {
   return launch_layernorm(x_dev, w_dev, b_dev, n_rows, dim, eps, out_dev, (hipStream_t)stream);

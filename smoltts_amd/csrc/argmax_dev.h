@@ -127,6 +127,12 @@ __device__ __forceinline__ uint32_t nz_bits(float z) { return __float_as_uint(z)
 __device__ __forceinline__ float mass_q(float z) { return floorf(expf(z) * 0x1p40f); }
 __device__ __forceinline__ float penalised(float x, float r, float inv_r) { return x > 0.f ? x * inv_r : x * r; }
 
+// LDS of the SCORE pass of one call: the waves' partial mass sums and the picked column's z (sampled rows)
+struct ScoreScratch {
+  double m[4];
+  float z;
+};
+
 // One workgroup of exactly 256 threads picks the id of logits row `row` (n_cols entries); every thread returns it.
 // `r`: the row's index into margin / margin_mask / the sampling arrays.  Greedy rows update margin[r] / margin_at[r].
 // FILTERS: the instantiation that reads sa.filters (slot mode's sampled forms; `F` is its LDS).  A row whose entry is off, and
@@ -136,9 +142,16 @@ __device__ __forceinline__ float penalised(float x, float r, float inv_r) { retu
 // the row's frame counter is below min_frames, -inf -- as the value is read, in front of the penalty, so greedy and sampled picks,
 // every filter and the top-2 gap see the patched row.  The row always has other finite columns: its maximum stays finite, a -inf
 // column gives z = -inf, mass 0 and key -inf and is never picked.  A row whose entry is off takes one uniform branch.
-template <bool FILTERS = false, bool LENGTH = false>
+// SCORE: the instantiation that also gives the log-probability, at temperature 1, of the id it returns under the row as the pick
+// sees it (after the length entry and the penalty, before temperature, top_k, top_p and min_p; host model smoltts_amd/sampling.py
+// pick_logprob): z_j = fp32(x'_j - max x'), q_j = mass_q(z_j), S = sum q_j (exact in fp64 in any order), lp = z_picked -
+// (log S - 40 ln 2).  One more pass over the row behind the top-2 merge and one workgroup sum on `C`; a sampled row carries its z
+// beside the winning key.  Thread 0 computes the value and gets it in *lp_out.  The pass reads and writes nothing the pick uses:
+// the id is the one the other instantiations return.
+template <bool FILTERS = false, bool LENGTH = false, bool SCORE = false>
 __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_vec, int r, float* margin, const int* margin_mask,
-                                          const SampleArgs& sa, ArgmaxScratch& S, FilterScratch* F = nullptr) {
+                                          const SampleArgs& sa, ArgmaxScratch& S, FilterScratch* F = nullptr, ScoreScratch* C = nullptr,
+                                          float* lp_out = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the row's sampling parameters (uniform in the workgroup: scalar loads, no divergence)
   float temp = sa.temp, min_p = sa.min_p;
@@ -291,6 +304,25 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
   if (lane == 0) S.sh[wave] = t;
   __syncthreads();
   Top2 a = top2_merge(top2_merge(S.sh[0], S.sh[1]), top2_merge(S.sh[2], S.sh[3]));
+  double score_s = 0.0;  // SCORE: the row's total mass at temperature 1, in units of 2^-40
+  float score_z = 0.f;   // ... and the picked column's z (a greedy pick is the maximum: 0)
+  if constexpr (SCORE) {  // before top_k takes its columns out of the row registers
+    double m = 0.0;
+#define ST_SUM(V, J) m += (double)mass_q((V) - a.v1);
+    if (vec) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { ST_SUM(v[i].x, 0) ST_SUM(v[i].y, 0) ST_SUM(v[i].z, 0) ST_SUM(v[i].w, 0) }  // (an absent column is -inf: mass 0)
+    } else if (FILTERS && fon) {
+      ST_SCOLS(ST_SUM)
+    } else {
+      for (int j = tid; j < n_cols; j += 256) ST_SUM(ST_LFIX(row[j], j), j)
+    }
+#undef ST_SUM
+    m = wave_sum_f64(m, lane);
+    if (lane == 0) C->m[wave] = m;
+    __syncthreads();
+    score_s = (C->m[0] + C->m[1]) + (C->m[2] + C->m[3]);
+  }
   if (temp > 0.f) {  // uniform: second pass over the row with perturbed keys
     const int frame = sa.frames ? sa.frames[r] : sa.frame_base + r;
     if (!sa.table && sa.salt) seed += 0x9E3779B97F4A7C15ULL * (uint64_t)sa.salt[r];
@@ -363,13 +395,17 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
       }
     }
     Top2 k{-INFINITY, 0x7fffffff, -INFINITY};
+    float kz = 0.f;  // SCORE: x' - max of this thread's best column
 #define ST_KEY(V, J)                                                  \
   {                                                                   \
     const float z = ((V) - a.v1) * inv_t; /* <= 0 */                  \
     if (z >= cut && (!FILTERS || nz_bits(z) <= wu)) {                 \
       const float u = uniform01(seed, key_slot, frame, sa.step, (J)); \
       const float key = z - logf(-logf(u));                           \
-      if (key > k.v1) { k.v1 = key; k.i1 = (J); }                     \
+      if (key > k.v1) {                                               \
+        k.v1 = key; k.i1 = (J);                                       \
+        if constexpr (SCORE) kz = (V) - a.v1;                         \
+      }                                                               \
     }                                                                 \
   }
 #define ST_KEY_S(V, J) if (ord_key(V) >= tk) ST_KEY(V, J)
@@ -386,6 +422,7 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     }
 #undef ST_KEY_S
 #undef ST_KEY
+    const int ki = k.i1;  // this thread's own best column (columns belong to one thread each)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       Top2 b;
@@ -396,6 +433,11 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
     __syncthreads();
     const Top2 w = top2_merge(top2_merge(S.sh2[0], S.sh2[1]), top2_merge(S.sh2[2], S.sh2[3]));
     a.i1 = w.i1;
+    if constexpr (SCORE) {  // the winner's owner hands its z over
+      if (ki == w.i1) C->z = kz;
+      __syncthreads();
+      score_z = C->z;
+    }
   }
 #undef ST_SCOLS
 #undef ST_SGROUP
@@ -410,6 +452,8 @@ __device__ __forceinline__ int argmax_row(const float* row, int n_cols, bool ld_
       }
     }
   }
+  if constexpr (SCORE)
+    if (tid == 0) *lp_out = (float)((double)score_z - (log(score_s) - 40.0 * 0.6931471805599453094));
   return a.i1;  // the same value in every thread (merged from LDS)
 }
 

@@ -217,6 +217,12 @@ struct SampleArgs {
   // instantiations of the picking kernels, which a launcher selects when this pointer is set.
   const SmolttsSlotLength* length;
   int32_t im_end;
+  // log-probability of the picked id (argmax_dev.h SCORE), or null.  Selects the SCORE instantiations of the picking kernels; read
+  // only at step 0.  argmax_kernel stores row r's value at logprob[r] (logprob_stride == 0), or at logprob[r * logprob_stride +
+  // frames[r]] where the row's mask is set and frames[r] < logprob_stride (a session's [slot][frame] array; the commit kernel
+  // stores there itself, beside the codes).
+  float* logprob;
+  int32_t logprob_stride;
 };
 
 // Launchers implemented across the .hip files (all asynchronous on `stream`).

@@ -34,7 +34,7 @@ struct SmolttsEngine {
 };
 
 constexpr int STAGE_RING = 8;
-constexpr int GRAPH_FORMS = 16;  // the values of SmolttsSession.form (pick_form)
+constexpr int GRAPH_FORMS = 32;  // the values of SmolttsSession.form (pick_form)
 
 struct SmolttsSession {
   SmolttsEngine* e;
@@ -101,6 +101,10 @@ struct SmolttsSession {
   SmolttsSlotLength* len_tab;         // [B] read by the slow picks of slot mode (greedy and sampled); all zero = off
   SmolttsSlotLength* len_tab_area;    // [B] table, [B] upload entries, [B] upload slots
   bool* h_len_on;                     // host mirror: which slots' entries are on (bit 3 of the graph form)
+  // ... and per-slot score flags (smoltts_session_set_slot_score): host only.  In a form with bit 4 every row's slow pick is scored
+  // and the host reads the slots it asked about.
+  bool* h_score_on;
+  float* logprob;                     // [B][max_frames]: the log-probability of each emitted slow id, written by the scored forms
   int flight_limit;            // SMOLTTS_MAX_FRAMES_IN_FLIGHT as read at creation (0 = unbounded)
   int multi_frames;            // frames per multi-frame graph (1 = single-frame graphs only): SMOLTTS_FRAMES_PER_GRAPH, else
                                // smoltts_session_set_frames_per_graph, else min(n_frames, 4) of the largest decode call so far
@@ -178,6 +182,7 @@ size_t carve(SmolttsSession* s, char* base) {
   s->attn_ticket = cv.take<int>(ATT_SPLIT_MAX_PAIRS);
   s->margin_at = cv.take<int>(B);
   s->codes = cv.take<int>(B * (size_t)s->max_frames * H);
+  s->logprob = cv.take<float>(B * (size_t)s->max_frames);
   // slot mode only (smoltts_session_set_slot_sampling): the table, then the upload area (B entries, B slot numbers) -- the
   // tail of the slab, in use once the session enters slot mode
   s->slot_tab_area = cv.take<SmolttsSlotSampling>(2 * B + (B * sizeof(int) + sizeof(SmolttsSlotSampling) - 1) / sizeof(SmolttsSlotSampling));
@@ -280,13 +285,16 @@ struct CommitArgs {
   // each, side by side, 2.4 KB instead of 9.5 + 8 KB per slot to look at; null = from the logits (argmax_row: sampling)
   const float* slow_cand; int slow_tiles;
   const float* last_cand; int last_tiles;
+  float* logprob;    // SCORE: [B][max_frames], the slow id's log-probability beside its codes row
   int* attn_ticket;  // the key-split attention's arrival tickets: back to zero at the end of every frame, so that no history (an
                      // interrupted launch, a caller's odd count) can invert a later launch's "who arrived last" decision
 };
 
 // FILTERS: the instantiation whose picks read SampleArgs.filters (slot mode's sampled forms); LENGTH: the one whose slow pick
 // reads SampleArgs.length (slot mode's forms with a length entry on).  The stop rule below sees the id the patched row gave.
-template <bool FILTERS, bool LENGTH>
+// SCORE: the one whose slow pick also gives the id's log-probability (slot mode's forms in which some slot scores), stored at
+// logprob[b][f] with the codes of frame f.
+template <bool FILTERS, bool LENGTH, bool SCORE>
 __global__ __launch_bounds__(256) void commit_embed_kernel(CommitArgs a, EmbedTables t, float* xt, EmitDev emit) {
   __shared__ int s_col[64];
   __shared__ float sh4[4];
@@ -321,12 +329,18 @@ __global__ __launch_bounds__(256) void commit_embed_kernel(CommitArgs a, EmbedTa
     if (c_slow) id_slow = s_id[0];
     if (c_last) id_last = s_id[1];
   }
+  float lp_slow = 0.f;
+  ScoreScratch* sc = nullptr;
+  if constexpr (SCORE) {
+    __shared__ ScoreScratch s_score;
+    sc = &s_score;
+  }
   if constexpr (FILTERS) {
     __shared__ FilterScratch s_filt[2];
-    if (a.slow_logits && !c_slow) id_slow = argmax_row<true, LENGTH>(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0], &s_filt[0]);
+    if (a.slow_logits && !c_slow) id_slow = argmax_row<true, LENGTH, SCORE>(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0], &s_filt[0], sc, &lp_slow);
     if (a.last_logits && !c_last) id_last = argmax_row<true>(a.last_logits + (long)b * a.last_cols, a.last_cols, (a.last_cols & 3) == 0, b, a.margin, a.mask, a.last_sa, s_pick[1], &s_filt[1]);
   } else {
-    if (a.slow_logits && !c_slow) id_slow = argmax_row<false, LENGTH>(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0]);
+    if (a.slow_logits && !c_slow) id_slow = argmax_row<false, LENGTH, SCORE>(a.slow_logits + (long)b * a.slow_cols, a.slow_cols, (a.slow_cols & 3) == 0, b, a.margin, a.mask, a.slow_sa, s_pick[0], nullptr, sc, &lp_slow);
     if (a.last_logits && !c_last) id_last = argmax_row(a.last_logits + (long)b * a.last_cols, a.last_cols, (a.last_cols & 3) == 0, b, a.margin, a.mask, a.last_sa, s_pick[1]);
   }
   int f = 0;
@@ -344,6 +358,9 @@ __global__ __launch_bounds__(256) void commit_embed_kernel(CommitArgs a, EmbedTa
     if (publish) {
       a.cur_col[b * H + tid] = v;
       a.codes[((long)b * a.max_frames + f) * H + tid] = v;
+      if constexpr (SCORE) {
+        if (tid == 0 && a.logprob && a.slow_logits && !c_slow) a.logprob[(long)b * a.max_frames + f] = lp_slow;
+      }
     }
   }
   slow_now = a.slow_logits ? id_slow : a.new_col[b * H];  // (tid 0 reads what it may just have written itself)
@@ -485,6 +502,9 @@ bool fast_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & 2)
 // Whether some slot's length entry is on (slot mode only): the slow pick then reads the row of logits with every row's own entries,
 // as in a form whose slow token is sampled -- the head GEMM's tile candidates hold unpatched values
 bool length_on(const SmolttsSession* s) { return s->slot_mode && (s->form & 8) != 0; }
+// Whether some slot scores its slow token (slot mode only): the slow pick then reads the row of logits, by the same rule -- the score
+// sums over the whole row, which the tile candidates do not hold
+bool score_on(const SmolttsSession* s) { return s->slot_mode && (s->form & 16) != 0; }
 
 // The pick arguments of step 0 (slow token) / step >= 1 (depth codes).  Slot mode, sampling form: every row reads its own entry
 // (a greedy row then takes the argmax inside argmax_row); greedy form: plain greedy arguments.
@@ -492,8 +512,10 @@ SampleArgs pick_args(const SmolttsSession* s, int step) {
   if (s->slot_mode) {
     const bool sampled = step == 0 ? slow_sampled(s) : fast_sampled(s);
     const bool length = step == 0 && length_on(s);
-    SampleArgs sa{0.f, 0.f, 0, step, 0, s->frames, nullptr, s->margin_at, sampled || length ? s->slot_tab : nullptr};
+    const bool score = step == 0 && score_on(s);
+    SampleArgs sa{0.f, 0.f, 0, step, 0, s->frames, nullptr, s->margin_at, sampled || length || score ? s->slot_tab : nullptr};
     if (length) { sa.length = s->len_tab; sa.im_end = s->e->cfg.im_end_id; }
+    if (score) { sa.logprob = s->logprob; sa.logprob_stride = s->max_frames; }
     if (sampled && (s->form & 4)) {  // the filters of the sampled rows; the penalty's history: this step's column of the slot's emitted frames
       sa.filters = s->filt_tab;
       sa.hist = s->codes + step; sa.hist_slot_stride = (int64_t)s->max_frames * (1 + s->e->cfg.n_fast);
@@ -506,7 +528,7 @@ SampleArgs pick_args(const SmolttsSession* s, int step) {
 }
 
 // The commit kernel's greedy picks read the head GEMMs' tile candidates where run_tail has had them written (same conditions there)
-bool commit_cand_slow(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && !slow_sampled(s) && !length_on(s) && s->B < 256; }
+bool commit_cand_slow(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && !slow_sampled(s) && !length_on(s) && !score_on(s) && s->B < 256; }
 bool commit_cand_last(const SmolttsSession* s) { return s->commit_picks && s->fuse_pick && !fast_sampled(s) && s->B < 256; }
 
 // commit (optional) + next-frame mask + embedding of every slot's current column (see commit_embed_kernel); `picks`: the
@@ -523,6 +545,7 @@ int launch_commit_embed(SmolttsSession* s, int do_commit, int advance_pos, hipSt
   a.margin = s->margin;
   a.attn_ticket = s->attn_ticket;
   if (picks) {
+    a.logprob = s->logprob;
     a.slow_logits = s->logits_slow; a.slow_cols = c.vocab_size;
     a.slow_sa = pick_args(s, 0);
     a.last_logits = s->logits; a.last_cols = c.codebook_size;
@@ -532,12 +555,16 @@ int launch_commit_embed(SmolttsSession* s, int do_commit, int advance_pos, hipSt
   }
   const EmitDev em{s->x3n, gamma_at(e, e->w.layers[0].attn_norm), nullptr, nullptr, s->ssq};
   const bool filters = picks && (a.slow_sa.filters || a.last_sa.filters), length = picks && a.slow_sa.length;
-#define ST_COMMIT(F, L) hipLaunchKernelGGL((commit_embed_kernel<F, L>), dim3(s->B), dim3(256), 0, st, a, embed_tables(e), s->xt, em)
+  const bool score = picks && a.slow_sa.logprob;
+#define ST_COMMIT(F, L, S) hipLaunchKernelGGL((commit_embed_kernel<F, L, S>), dim3(s->B), dim3(256), 0, st, a, embed_tables(e), s->xt, em)
+#define ST_COMMIT_S(F, L) \
+  { if (score) ST_COMMIT(F, L, true); else ST_COMMIT(F, L, false); }
   if (length) {
-    if (filters) ST_COMMIT(true, true); else ST_COMMIT(false, true);
+    if (filters) ST_COMMIT_S(true, true) else ST_COMMIT_S(false, true)
   } else {
-    if (filters) ST_COMMIT(true, false); else ST_COMMIT(false, false);
+    if (filters) ST_COMMIT_S(true, false) else ST_COMMIT_S(false, false)
   }
+#undef ST_COMMIT_S
 #undef ST_COMMIT
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
@@ -739,14 +766,15 @@ int arm_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos
 // The form of the frame launches: bit 0 = some slot samples its slow token, bit 1 = some slot samples its depth codes, bit 2 = some
 // slot's filter entry is on (the sampled picks are then the FILTERS instantiations; without it they are the parent's kernels), bit 3 =
 // some slot's length entry is on (the slow pick is then the LENGTH instantiation over the row of logits; it acts on greedy rows too, so
-// it outlives the rule that clears the filter bit).  Outside slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
+// it outlives the rule that clears the filter bit), bit 4 = some slot scores its slow token (the slow pick is then the SCORE
+// instantiation over the row of logits; greedy rows are scored too, so it is not cleared either).  Outside slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
 // point that launches or captures picks, after the last change of the table.
 void pick_form(SmolttsSession* s) {
   int f = 0, len = 0;
   if (s->slot_mode)
     for (int b = 0; b < s->B; ++b) {
       f |= (s->h_slot[b].temp > 0.f ? 1 : 0) | (s->h_slot[b].fast_temp > 0.f ? 2 : 0) | (s->h_filt_on[b] ? 4 : 0);
-      len |= s->h_len_on[b] ? 8 : 0;
+      len |= (s->h_len_on[b] ? 8 : 0) | (s->h_score_on[b] ? 16 : 0);
     }
   if ((f & 3) == 0) f = 0;  // nothing samples: the filters have nothing to act on
   s->form = f | len;
@@ -1116,6 +1144,7 @@ void smoltts_session_destroy(SmolttsSession* s) {
   delete[] s->h_slot;
   delete[] s->h_filt_on;
   delete[] s->h_len_on;
+  delete[] s->h_score_on;
   delete s;
 }
 
@@ -1312,6 +1341,9 @@ int enter_slot_mode(SmolttsSession* s, hipStream_t st) {
   delete[] s->h_len_on;
   s->h_len_on = new (std::nothrow) bool[B]();
   ST_REQUIRE(s->h_len_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
+  delete[] s->h_score_on;
+  s->h_score_on = new (std::nothrow) bool[B]();
+  ST_REQUIRE(s->h_score_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
   if (hipHostMalloc((void**)&s->h_slot_stage, ring_area_bytes(s) * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
     s->h_slot_stage = nullptr;
     delete[] s->h_slot;
@@ -1538,6 +1570,35 @@ int smoltts_session_outputs(SmolttsSession* s, int32_t** codes_dev, int32_t** n_
   if (n_frames_dev) *n_frames_dev = s->frames;
   if (done_dev) *done_dev = s->done;
   if (margin_dev) *margin_dev = s->margin;
+  return SMOLTTS_OK;
+}
+
+// Which slots score their slow token: host flags only (nothing is uploaded: a form with bit 4 scores every row, and the host reads
+// the slots it asked about).  The first per-slot call of any kind enters slot mode; here its tables are zeroed on the null stream
+// and waited for, since this call has no stream to order them on.
+int smoltts_session_set_slot_score(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* on_host) {
+  ST_REQUIRE(s && (n == 0 || (slots_host && on_host)), SMOLTTS_E_INVALID, "session_set_slot_score: null argument");
+  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_score: %d entries, session holds %d slots", n, s->B);
+  for (int i = 0; i < n; ++i) ST_TRY(check_slot("session_set_slot_score", slots_host[i], s->B));
+  if (!s->slot_mode) {
+    ST_TRY(enter_slot_mode(s, nullptr));
+    ST_CHECK_HIP(hipStreamSynchronize(nullptr));
+  }
+  for (int i = 0; i < n; ++i) s->h_score_on[slots_host[i]] = on_host[i] != 0;
+  return SMOLTTS_OK;
+}
+
+int smoltts_session_logprobs(SmolttsSession* s, float** logprob_dev, int32_t* stride) {
+  ST_REQUIRE(s && logprob_dev, SMOLTTS_E_INVALID, "session_logprobs: null argument");
+  *logprob_dev = s->logprob;
+  if (stride) *stride = s->max_frames;
+  return SMOLTTS_OK;
+}
+
+int smoltts_session_slow_logits(SmolttsSession* s, float** logits_dev, int32_t* ld) {
+  ST_REQUIRE(s && logits_dev, SMOLTTS_E_INVALID, "session_slow_logits: null argument");
+  *logits_dev = s->logits_slow;
+  if (ld) *ld = s->e->cfg.vocab_size;
   return SMOLTTS_OK;
 }
 

@@ -36,8 +36,9 @@ int launch_embed(const int32_t* cols, int n_rows, int n_code_rows, const void* t
 // Row pick (argmax_dev.h) + optionally the next depth step's input: the embedding row of the picked code
 // (lm/generate.py:134-140: fast_embeddings(code + i*codebook_size)) as fp32 residual row (+ X3 operand / sums of squares when a
 // GEMM consumes it), and / or the precomputed layer-0 q | k | v of that row (QkvGather: no wqkv launch in the next step).
-// FILTERS: the instantiation whose pick reads SampleArgs.filters (launched only when that pointer is set); LENGTH: SampleArgs.length
-template <bool FILTERS, bool LENGTH>
+// FILTERS: the instantiation whose pick reads SampleArgs.filters (launched only when that pointer is set); LENGTH: SampleArgs.length;
+// SCORE: SampleArgs.logprob, which receives the log-probability of the picked id (layout: common.h)
+template <bool FILTERS, bool LENGTH, bool SCORE>
 __global__ __launch_bounds__(256) void argmax_kernel(const float* logits, int n_cols, long ld, int* ids, int ids_stride,
                                                      float* margin, const int* margin_mask, const uint16_t* emb,
                                                      int emb_row_offset, int dim, float* xnext, EmitDev emit, SampleArgs sa, QkvGather qg) {
@@ -45,13 +46,29 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* logits, int n_
   __shared__ float sh4[4];
   const int r = blockIdx.x, tid = threadIdx.x;
   int id;
+  float lp = 0.f;
+  ScoreScratch* C = nullptr;
+  if constexpr (SCORE) {
+    __shared__ ScoreScratch s_score;
+    C = &s_score;
+  }
   if constexpr (FILTERS) {
     __shared__ FilterScratch F;
-    id = argmax_row<true, LENGTH>(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S, &F);
+    id = argmax_row<true, LENGTH, SCORE>(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S, &F, C, &lp);
   } else {
-    id = argmax_row<false, LENGTH>(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S);
+    id = argmax_row<false, LENGTH, SCORE>(logits + (long)r * ld, n_cols, (ld & 3) == 0, r, margin, margin_mask, sa, S, nullptr, C, &lp);
   }
   if (tid == 0) ids[(long)r * ids_stride] = id;
+  if constexpr (SCORE) {
+    if (tid == 0) {
+      if (sa.logprob_stride == 0) {
+        sa.logprob[r] = lp;
+      } else if (margin_mask == nullptr || margin_mask[r]) {  // a session's [slot][frame] array: what the commit will publish
+        const int f = sa.frames ? sa.frames[r] : sa.frame_base + r;
+        if (f >= 0 && f < sa.logprob_stride) sa.logprob[(long)r * sa.logprob_stride + f] = lp;
+      }
+    }
+  }
   if (emb == nullptr) return;
   const long erow = (long)id + emb_row_offset;
   // everything that depends on the id is requested in one go: the embedding row and (where the engine has the table) the row's
@@ -97,14 +114,18 @@ int launch_argmax(const float* logits, int n_rows, int n_cols, int64_t ld, int32
   ST_REQUIRE(qg.table == nullptr || (qg.rope && qg.q_out && qg.kc && qg.vc && qg.pos >= 0 && qg.pos < qg.cache_len), SMOLTTS_E_INVALID,
              "argmax: bad q|k|v gather arguments");
   ST_REQUIRE(sa.length == nullptr || sa.table, SMOLTTS_E_INVALID, "argmax: length entries need the per-row table");
-#define ST_ARGMAX(F, L)                                                                                                                 \
-  hipLaunchKernelGGL((argmax_kernel<F, L>), dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, ids, ids_stride, margin, \
+  ST_REQUIRE(sa.logprob == nullptr || (sa.table && sa.logprob_stride >= 0), SMOLTTS_E_INVALID, "argmax: a score needs the per-row table");
+#define ST_ARGMAX(F, L, S)                                                                                                                 \
+  hipLaunchKernelGGL((argmax_kernel<F, L, S>), dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, ids, ids_stride, margin, \
                      margin_mask, (const uint16_t*)emb, emb_row_offset, dim, xnext, e, sa, qg)
+#define ST_ARGMAX_S(F, L) \
+  { if (sa.logprob) ST_ARGMAX(F, L, true); else ST_ARGMAX(F, L, false); }
   if (sa.length) {
-    if (sa.filters) ST_ARGMAX(true, true); else ST_ARGMAX(false, true);
+    if (sa.filters) ST_ARGMAX_S(true, true) else ST_ARGMAX_S(false, true)
   } else {
-    if (sa.filters) ST_ARGMAX(true, false); else ST_ARGMAX(false, false);
+    if (sa.filters) ST_ARGMAX_S(true, false) else ST_ARGMAX_S(false, false)
   }
+#undef ST_ARGMAX_S
 #undef ST_ARGMAX
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;

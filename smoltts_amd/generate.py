@@ -62,6 +62,11 @@ def _apply_slot_sampling(session: LMSession, slots: Sequence[int], sampling: Seq
     if todo:
         session.set_slot_length([slots[i] for i in todo], [sampling[i].min_frames or 0 for i in todo],
                                 [sampling[i].eos_bias or 0.0 for i in todo])
+    # ... and their score flags (host flags: the session keeps scoring while any slot's is on)
+    was = getattr(session, "scored_slots", ())
+    todo = [i for i, (b, r) in enumerate(zip(slots, sampling)) if r.scored or b in was]
+    if todo:
+        session.set_slot_score([slots[i] for i in todo], [sampling[i].scored for i in todo])
 
 
 def resolve_sampling(sampling, settings: GenerationSettings, n: int) -> Optional[List[RequestSampling]]:
@@ -169,6 +174,12 @@ class BatchGenerator:
 
         im_end = self.engine.token_config.im_end_id
         return [finish_reason([] if s is None else [s], im_end) for s in self.last_slow]
+
+    def logprobs(self) -> List[np.ndarray]:
+        """Per utterance, the float32 scores of the frames it has emitted so far, its ``<|im_end|>`` frame included (meaningful
+        where the utterance's entry asked for them: ``RequestSampling.scored``).  Call before ``close``."""
+        lp = self.session.fetch_logprobs()
+        return [lp[b, :int(self._emitted[b])].copy() for b in range(self.B)]
 
     def __next__(self) -> List[Optional[VQToken]]:
         if not self._pending:

@@ -113,6 +113,7 @@ class LMSession(ClosesOnDel):
         self.B = max_batch
         self.filtered_slots = set()  # slots whose filter entry on the device is on (set_slot_filters)
         self.length_slots = set()  # slots whose length entry on the device is on (set_slot_length)
+        self.scored_slots = set()  # slots whose slow token is scored (set_slot_score)
         self.max_seq = max_seq or engine.cfg.max_seq_len
         self.max_rows = max(max_rows, max_batch)
         self.max_frames = max_frames
@@ -140,6 +141,13 @@ class LMSession(ClosesOnDel):
         mp = C.c_void_p()
         check(self.lib.smoltts_session_margin_at(h, C.byref(mp)), "smoltts_session_margin_at")
         self.margin_at = view(mp, self.B * 4, torch.int32, (self.B,))  # frame * 64 + step of each slot's smallest gap
+        lp, stride = C.c_void_p(), C.c_int32()
+        check(self.lib.smoltts_session_logprobs(h, C.byref(lp), C.byref(stride)), "smoltts_session_logprobs")
+        # [slot][frame]: log-probability of each emitted slow id, written while some slot scores (set_slot_score)
+        self.logprobs = view(lp, self.B * stride.value * 4, torch.float32, (self.B, stride.value))
+        sl, ld = C.c_void_p(), C.c_int32()
+        check(self.lib.smoltts_session_slow_logits(h, C.byref(sl), C.byref(ld)), "smoltts_session_slow_logits")
+        self.slow_logits = view(sl, self.B * ld.value * 4, torch.float32, (self.B, ld.value))  # the latest frame's (diagnostic)
         self._keep = None
         self._keep_prefixes = None
         if os.environ.get("SMOLTTS_COMMIT_PICKS") == "0":  # A/B switches of tools/ (the ids are the same either way)
@@ -365,6 +373,24 @@ class LMSession(ClosesOnDel):
             (C.c_float * max(n, 1))(*[float(x) for x in eos_bias]), current_stream_ptr()), "smoltts_session_set_slot_length")
         for b, m, x in zip(slots, min_frames, eos_bias):
             (self.length_slots.add if (m > 0 or x != 0) else self.length_slots.discard)(int(b))
+
+    def set_slot_score(self, slots: Sequence[int], on: Sequence[bool]) -> None:
+        """Score the slow token of slot ``slots[i]`` where ``on[i]`` (``smoltts_session_set_slot_score``): ``logprobs[slot][f]`` then
+        receives, with frame f, the log-probability at temperature 1 of the id the slot emitted (``sampling.pick_logprob``).  Host
+        flags only; a new tenant without the option needs an off flag, or the session keeps scoring for nobody."""
+        n = len(slots)
+        if len(on) != n:
+            raise ValueError("slot score: one flag per slot")
+        check(self.lib.smoltts_session_set_slot_score(
+            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_int32 * max(n, 1))(*[1 if x else 0 for x in on])),
+            "smoltts_session_set_slot_score")
+        for b, x in zip(slots, on):
+            (self.scored_slots.add if x else self.scored_slots.discard)(int(b))
+
+    def fetch_logprobs(self) -> np.ndarray:
+        """Host copy of ``logprobs`` ([max_batch, max_frames] float32); an entry means something for a frame its slot emitted
+        while some slot scored.  Waits for the current stream."""
+        return self.logprobs.cpu().numpy()
 
     def measure_duplicate(self, code: int = -1, n_filter: int = 0) -> None:
         """Measurement aid (this session only): issue every launch of one kernel class twice; -1 switches it off."""

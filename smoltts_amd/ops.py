@@ -270,6 +270,37 @@ def sample_rows_length(logits: torch.Tensor, table: torch.Tensor, length: torch.
     return ids
 
 
+def sample_rows_scored(logits: torch.Tensor, table: torch.Tensor, length: Optional[torch.Tensor] = None, im_end: int = 0,
+                       frames: Optional[torch.Tensor] = None, step: int = 0, filters: Optional[torch.Tensor] = None,
+                       history: Optional[torch.Tensor] = None, history_len: Optional[torch.Tensor] = None):
+    """``smoltts_k_sample_rows_scored``: the ids of ``sample_rows_length`` on the same arguments (``length`` None: of
+    ``sample_rows`` / ``sample_rows_filtered``) and, per row, the fp32 log-probability at temperature 1 of that id under the row
+    its pick saw (``sampling.pick_logprob``) -> ``(ids, logprobs)``."""
+    R = logits.shape[0]
+    if table.dtype != torch.uint8 or table.numel() < C.sizeof(SlotSampling) * R:
+        raise ValueError("table: 24 bytes per row (slot_sampling_table)")
+    if length is not None:
+        if length.dtype != torch.uint8 or length.numel() < C.sizeof(SlotLength) * R:
+            raise ValueError("length: 16 bytes per row (slot_length_table)")
+        if not 0 <= int(im_end) < logits.shape[1]:
+            raise ValueError("im_end: a column of the row")
+    if frames is not None and (frames.dtype != torch.int32 or frames.numel() < R):
+        raise ValueError("frames: int32, one per row")
+    if filters is not None:
+        if filters.dtype != torch.uint8 or filters.numel() < C.sizeof(SlotFilters) * R:
+            raise ValueError("filters: 32 bytes per row (slot_filter_table)")
+        if history is None or history.dtype != torch.int32 or tuple(history.shape) != (R, 64) or not history.is_contiguous():
+            raise ValueError("history: contiguous int32 [rows, 64]")
+        if history_len is None or history_len.dtype != torch.int32 or history_len.numel() < R:
+            raise ValueError("history_len: int32, one per row")
+    ids = torch.empty(R, dtype=torch.int32, device=logits.device)
+    lp = torch.empty(R, dtype=torch.float32, device=logits.device)
+    _k("smoltts_k_sample_rows_scored", dptr(logits), R, logits.shape[1], logits.stride(0), dptr(table), dptr(filters), dptr(frames),
+       dptr(history if filters is not None else None), dptr(history_len if filters is not None else None), dptr(length), int(im_end),
+       int(step), dptr(ids), dptr(lp))
+    return ids, lp
+
+
 def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     out = torch.empty_like(x)
     _k("smoltts_k_layernorm", dptr(x), dptr(w), dptr(b), x.shape[0], x.shape[1], eps, dptr(out))

@@ -15,6 +15,10 @@ device sums fp32 ``expf`` masses (rounded down to multiples of 2^-40, exactly); 
 
 ``length_patch`` models the per-request length control of the slow pick (``SmolttsSlotLength``): the row a pick
 sees, in front of everything above.  It is exact: one rounded fp32 add, or a store of -inf.
+
+``pick_logprob`` models the score of the slow pick (``smoltts_session_set_slot_score``): the log-probability, at
+temperature 1, of the emitted id under the row the pick saw.  The device's ``expf`` is the only inexact step:
+``LOGPROB_MARGIN`` bounds what it can move.
 """
 from __future__ import annotations
 
@@ -79,6 +83,9 @@ MAX_REPETITION_PENALTY = 10.0  # of the public interface (RequestSampling); the 
 # fp32 expf (about 2 ulp: 1.2e-7 relative per column) and the 2^-40 quantum of the device's mass sums stay below 1e-6 of the
 # total; x 10
 TOP_P_EDGE_MARGIN = 1e-5
+# the same two sources bound the relative error of the score's mass sum S below 1e-6, which is the absolute error of log S (a CPU
+# simulation with expf biased by +-3 ulp over rows of 5 .. 65,836 columns gave 3e-7); x 10.  Absolute, per pick.
+LOGPROB_MARGIN = 1e-5
 
 
 def penalised_row(logits, penalty: float, history) -> np.ndarray:
@@ -172,3 +179,17 @@ def length_patch(logits, im_end: int, frame: int, min_frames: int = 0, eos_bias:
     if frame < min_frames:
         x[im_end] = -np.inf
     return x
+
+
+def pick_logprob(row, picked: int) -> float:
+    """The score of one slow pick: ``row`` is the fp32 row as the pick sees it (after ``length_patch`` and ``penalised_row``, before
+    temperature, ``top_k``, ``top_p`` and ``min_p``), ``picked`` the id the request emitted.  With ``z = fp32(x - max x)`` (one
+    rounded subtract, as on the device), ``q = floor(expf(z) * 2^40)`` and ``S = sum q`` (exact in float64 in any order):
+    ``float64(z[picked]) - (log S - 40 ln 2)``, rounded to fp32 as the device stores it.  A column beyond |z| of about 28 has
+    mass 0 but a finite score; a -inf column (a length block) contributes nothing."""
+    x = np.asarray(row, dtype=np.float32)
+    z = _z32(x, 1.0)
+    with np.errstate(under="ignore"):
+        q = np.floor(np.exp(z, dtype=np.float32).astype(np.float64) * 2.0**40)
+    total = float(q.sum())
+    return float(np.float32(float(z[int(picked)]) - (np.log(total) - 40.0 * np.log(2.0))))

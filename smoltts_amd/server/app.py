@@ -198,6 +198,18 @@ class TTSCore:
         base = self.model._settings(None) if hasattr(self.model, "_settings") else GenerationSettings()
         return sampling.resolve(base)
 
+    def _check_best_of(self, sampling, stream: bool = False) -> None:
+        """The routes' share of the ``best_of`` refusals (``ValueError`` -> 400): the settings' ``max_best_of`` (default 4), and a
+        streaming route.  The engine's own check (``config.check_best_of``) refuses the rest."""
+        n = getattr(sampling, "takes", 1) if sampling is not None else 1
+        if n <= 1:
+            return
+        if stream:
+            raise ValueError("best_of > 1 needs a blocking request: a stream's audio is out before the takes can be ranked")
+        cap = int(self._setting("max_best_of", 4))
+        if n > cap:
+            raise ValueError(f"best_of={n} exceeds this server's max_best_of={cap}")
+
     def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000", sampling=None,
                        speed: Optional[float] = None, loudness=None, info: Optional[dict] = None):
         """-> (bytes, media type, the seed the request sampled with or None).  ``speed``: passed on only when it is not 1.
@@ -206,6 +218,7 @@ class TTSCore:
         ``info["watermark"]`` true when the audio is marked."""
         used = None
         try:
+            self._check_best_of(sampling)
             sp, n_seg = self._request_kw(input_text, speed, loudness, voice=voice)
             if info is not None:
                 info["watermark"] = bool(sp.get("watermark"))
@@ -216,6 +229,8 @@ class TTSCore:
                 gain = getattr(req, "loudness_gain_db", None)
                 cut = getattr(req, "trimmed_s", 0.0)
                 reason = getattr(req, "finish_reason", None)
+                mean, n_takes = getattr(req, "mean_logprob", None), getattr(req, "best_of", 1)
+                used = getattr(req, "sampling", None)  # (a best_of request's entry is the chosen take's by now)
             else:
                 used = self._model_sampling(sampling)
                 kw = {"sampling": used} if used is not None else {}
@@ -223,6 +238,12 @@ class TTSCore:
                 gain = getattr(self.model, "last_loudness_gain_db", None)
                 cut = getattr(self.model, "last_trimmed_s", 0.0)
                 reason = getattr(self.model, "last_finish_reason", None)
+                mean, takes = getattr(self.model, "last_mean_logprob", None), getattr(self.model, "last_takes", None)
+                n_takes = len(takes) if takes else 1
+                if takes:
+                    used = self.model.last_sampling[0]  # the chosen take's entry
+            if info is not None and mean is not None:
+                info["mean_logprob"], info["best_of"] = mean, n_takes
             if info is not None and reason is not None:
                 info["finish_reason"] = reason
             if info is not None and ("trim_silence" in sp or "max_pause_s" in sp):
@@ -241,6 +262,7 @@ class TTSCore:
         not ``pcm_24000``).  The request is submitted here, before the first chunk is asked for.  ``speed``: passed on only when
         it is not 1; the chunks are then the stretched stream (float32 for ``pcm_24000``).  ``container`` ``"flac"``: the
         chunks are the stream's FLAC bytes (framed on the GPU), the stream header in front of the first."""
+        self._check_best_of(sampling, stream=True)
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
         if container is not None:
             kw["container"] = container
@@ -264,6 +286,7 @@ class TTSCore:
         the settings' too.  ``ValueError``: options the engine refuses."""
         from ..request import parse_request
 
+        self._check_best_of(sampling, stream=True)
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
         if container is not None:
             kw["container"] = container
@@ -363,6 +386,12 @@ def _mark_headers(info: dict) -> dict:
     return {"X-Watermark": "1"} if info.get("watermark") else {}
 
 
+def _score_headers(info: dict) -> dict:
+    """``X-Mean-Logprob`` (the chosen take's mean slow-token log-probability) and ``X-Best-Of`` of a blocking response that was scored."""
+    m = info.get("mean_logprob")
+    return {} if m is None else {"X-Mean-Logprob": f"{m:.4f}", "X-Best-Of": str(int(info.get("best_of") or 1))}
+
+
 def _finish_headers(info: dict) -> dict:
     """``X-Finish-Reason: stop | length`` of a blocking response: whether the utterance ended with ``<|im_end|>`` or at its cap."""
     r = info.get("finish_reason")
@@ -387,6 +416,11 @@ class SamplingFields(BaseModel):
     min_frames: Optional[int] = Field(default=None, ge=0, le=1024)
     min_duration_s: Optional[float] = Field(default=None, ge=0, le=1024 / 12.5, allow_inf_nan=False)
     eos_bias: Optional[float] = Field(default=None, ge=-100, le=100, allow_inf_nan=False)
+    # scores: ``logprobs`` scores the request's slow tokens; ``best_of`` (blocking routes, sampled requests, at most
+    # the settings' ``max_best_of``) draws that many takes with seeds seed, seed + 1, ... and answers the best one.  A blocking
+    # response then carries ``X-Mean-Logprob`` and ``X-Best-Of``, and its ``X-Seed`` is the chosen take's
+    logprobs: Optional[bool] = None
+    best_of: Optional[int] = Field(default=None, ge=1, le=8)
 
     @model_validator(mode="after")
     def _one_minimum(self):
@@ -399,11 +433,11 @@ class SamplingFields(BaseModel):
 
         min_frames = min_frames_from(self.min_frames, self.min_duration_s)
         fields = (self.seed, self.temperature, self.fast_temperature, self.min_p, self.top_p, self.top_k, self.repetition_penalty,
-                  self.repetition_window, min_frames, self.eos_bias)
+                  self.repetition_window, min_frames, self.eos_bias, self.logprobs or None, self.best_of)
         if all(v is None for v in fields):
             return None
         return RequestSampling(self.temperature, self.fast_temperature, self.min_p, self.seed, self.top_p, self.top_k,
-                               self.repetition_penalty, self.repetition_window, min_frames, self.eos_bias)
+                               self.repetition_penalty, self.repetition_window, min_frames, self.eos_bias, bool(self.logprobs), self.best_of)
 
 
 # speaking speed (OpenAI's ``speed``, ElevenLabs' ``voice_settings.speed``): pitch-preserving time stretch on the GPU (tsm.py);
@@ -515,7 +549,7 @@ def openai_speech(item: SpeechRequest, http_request: Request):
                                                   speed=item.speed, loudness=item, info=info)
     return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed),
                                                            **_gain_headers(info), **_mark_headers(info), **_trim_headers(info),
-                                                           **_finish_headers(info)})
+                                                           **_finish_headers(info), **_score_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}")
@@ -529,7 +563,7 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
     return Response(content=content, media_type=media_type, headers={
         "Content-Disposition": f'attachment; filename="elevenlabs_speech.{fmt.split("_")[0]}"',
         "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed), **_gain_headers(info), **_mark_headers(info),
-        **_trim_headers(info), **_finish_headers(info)})
+        **_trim_headers(info), **_finish_headers(info), **_score_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}/stream")

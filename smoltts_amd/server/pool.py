@@ -35,6 +35,12 @@ class _PoolRequest:
     trimmed_s: float = 0.0  # a blocking request that trims silence: the seconds cut (known at its end)
     watermark: bool = False  # the audio carries the workers' watermark
     finish_reason: Optional[str] = None  # "stop" / "length" (config.finish_reason), known at the request's end
+    # scores of a request that asked for them (RequestSampling.logprobs / best_of), known at its end; all takes of a best_of
+    # request run on the one worker the request went to, and ``sampling`` then carries the winner's seed
+    logprobs: object = None
+    mean_logprob: Optional[float] = None
+    takes: object = None
+    best_of: int = 1
 
 
 @dataclass
@@ -99,7 +105,11 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
         try:
             for chunk in sched.iter_chunks(req):
                 res_q.put((rid, "chunk", np.ascontiguousarray(chunk)))  # float32, or int16 / uint8 for a streamed output_format
-            res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0), getattr(req, "finish_reason", None))))
+            scores = None
+            if getattr(req, "logprobs", None) is not None:
+                scores = {"logprobs": np.asarray(req.logprobs), "mean_logprob": req.mean_logprob, "takes": req.takes, "best_of": req.best_of,
+                          "seed": req.sampling.seed}
+            res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0), getattr(req, "finish_reason", None), scores)))
         except Exception as e:
             res_q.put((rid, "error", (type(e).__name__, str(e))))
         finally:
@@ -252,6 +262,10 @@ class GpuPool:
                           trim_silence, max_pause_s, silence_threshold_db)  # refused here, before a worker sees it
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
+        if sampling is not None and sampling.takes > 1 and (stream or p.plan is not None):
+            from ..config import MAX_BEST_OF, check_best_of
+
+            check_best_of(sampling, MAX_BEST_OF, stream=stream, segmented=p.plan is not None)  # (the worker checks the rest)
         req = self._new_request(sampling)
         req.watermark = marked
         w = req.worker
@@ -492,7 +506,13 @@ class GpuPool:
                 if not req.cancelled:
                     req.out.put(payload)
             elif kind == "end":
-                req.loudness_gain_db, req.trimmed_s, req.finish_reason = payload
+                req.loudness_gain_db, req.trimmed_s, req.finish_reason, scores = payload
+                if scores is not None:
+                    import dataclasses
+
+                    req.logprobs, req.mean_logprob, req.takes, req.best_of = (scores[k] for k in ("logprobs", "mean_logprob", "takes", "best_of"))
+                    if req.sampling is not None and req.best_of > 1:  # the winner's entry: its seed replays the chosen audio
+                        req.sampling = dataclasses.replace(req.sampling, seed=scores["seed"], best_of=None, logprobs=True)
                 self._finish(req, None)
             elif kind == "result":  # a registry message's answer
                 self._finish(req, ("result", payload))

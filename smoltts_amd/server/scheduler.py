@@ -73,6 +73,16 @@ class _Request:
                                          # in the slot, which the scheduler's max_frames_per_byte may lower
     slot_sampling: object = None         # the entry of the utterance (segment) in the slot: ``sampling`` (the segment's) with the
                                          # scheduler's min_frames_per_byte applied
+    # scores.  A best_of request is a parent that never holds a slot: its takes are ordinary blocking requests
+    # (``take_of`` = (parent, k)) that report to it when they end instead of going to the codec; the winner's codes then become
+    # the parent's own codec job, and ``sampling`` the winner's entry (its seed replays the chosen audio as a plain request)
+    lp: list = field(default_factory=list)  # a scored blocking request: its frames' scores, tick by tick
+    logprobs: object = None              # float32 scores of the (chosen) utterance's frames, valid once the request has ended
+    mean_logprob: Optional[float] = None  # ... and their float64 mean
+    takes: object = None                 # parent: per take its seed, mean_logprob, min_logprob, frames, finish_reason, chosen
+    take_reqs: list = field(default_factory=list)  # parent: the takes' requests
+    take_of: object = None
+    best_of: int = 1
 
 
 @dataclass
@@ -158,6 +168,7 @@ class _Snapshot:
     done: object
     event: object
     tick_no: int
+    logprobs: object = None  # the score array, cloned only while some live slot scores
 
 
 @dataclass
@@ -314,13 +325,14 @@ class BatchScheduler:
         ``silence_threshold_db`` (-72 to -6 dBFS; default 2^-8; it needs one of the other two): silence trimming on the GPU
         (trim.py), first of the stages: a stream in its codec pass, segment by segment in front of the seam; a blocking
         utterance whole, each segment before the seam join (``request.trimmed_s`` is what was cut)."""
-        from ..config import RequestSampling
+        from ..config import RequestSampling, check_best_of, take_sampling
         from ..request import parse_request
 
         p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
                           trim_silence, max_pause_s, silence_threshold_db)
         self._check_trim(p)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
+        check_best_of(resolved, self.B, stream=stream, segmented=p.plan is not None)
         if self._dead is not None:  # the worker is gone (engine failure or close): nobody would ever answer
             raise RuntimeError(f"scheduler is not running: {self._dead}")
         if self._draining:
@@ -329,9 +341,20 @@ class BatchScheduler:
                        output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=p.speed_q,
                        container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None,
                        loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark), trim=p.trim_route)
-        self._pending.put(req)
+        if resolved.takes > 1:
+            # the parent carries the audio options and the response; its takes are plain blocking requests, admitted as slots
+            # come free
+            req.best_of = resolved.takes
+            req.take_reqs = [_Request(text, voice, False, req.max_new_tokens, sampling=take_sampling(resolved, k), voice_entry=req.voice_entry,
+                                      take_of=(req, k)) for k in range(resolved.takes)]
+            for t in req.take_reqs:
+                self._pending.put(t)
+        else:
+            self._pending.put(req)
         self._wake.set()
         if self._dead is not None:  # lost the race with a failing worker: answer it ourselves
+            for t in req.take_reqs:
+                self._end(t, RuntimeError(f"scheduler is not running: {self._dead}"))
             self._end(req, RuntimeError(f"scheduler is not running: {self._dead}"))
         return req
 
@@ -388,6 +411,9 @@ class BatchScheduler:
         if not float(idle_timeout_s) > 0.0 or (flush_after_s is not None and not float(flush_after_s) > 0.0):
             raise ValueError("idle_timeout_s and flush_after_s must be positive")
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
+        from ..config import check_best_of
+
+        check_best_of(resolved, self.B, stream=True, segmented=True)
         if self._dead is not None or self._draining:
             raise RuntimeError(f"scheduler is not running: {self._dead or 'shutting down'}")
         req = IncrementalRequest("", voice, True, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
@@ -451,6 +477,10 @@ class BatchScheduler:
         req.cancelled = True
         for part in list(req.seg.parts) if req.seg is not None else []:
             part.cancelled = True
+        for t in req.take_reqs:  # a best_of request: its takes give their slots back at the worker's next look
+            t.cancelled = True
+        if req.take_reqs:
+            self._wake.set()
         if req.inc is not None:
             self._wake.set()  # (a parked one is in no tick's books: the worker frees its slot when it looks at the text side)
 
@@ -878,7 +908,9 @@ class BatchScheduler:
         torch = self._torch
         s = self.session
         s.decode(self.tick)
-        snap = _Snapshot(s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no)
+        scoring = any(r.slot_sampling is not None and r.slot_sampling.scored for r in list(self._active.values()) + self._retiring)
+        snap = _Snapshot(s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no,
+                         s.logprobs.clone() if scoring else None)
         snap.event.record(torch.cuda.current_stream())
         self._snaps.append(snap)
         self._tick_no += 1
@@ -897,8 +929,9 @@ class BatchScheduler:
                 codes = snap.codes.to("cpu", non_blocking=True)
                 n_frames = snap.n_frames.to("cpu", non_blocking=True)
                 done = snap.done.to("cpu", non_blocking=True)
+                scores = snap.logprobs.to("cpu", non_blocking=True) if snap.logprobs is not None else None
             self._sync_copies()
-            self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), snap.tick_no, stream_pass)
+            self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), snap.tick_no, stream_pass, None if scores is None else scores.numpy())
 
     def _launch_stream_codec(self, snap: _Snapshot) -> Optional[_Delivery]:
         """The codec pass of the streaming requests for tick ``snap.tick_no``, on the codec stream, from the tick's snapshot of
@@ -963,7 +996,7 @@ class BatchScheduler:
         self._copy_stream.synchronize()
         self._gpu_wait_s += time.perf_counter() - t
 
-    def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery]) -> None:
+    def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery], scores=None) -> None:
         from ..config import finish_reason, merge_finish_reasons
         from ..generate import semantic_columns
 
@@ -1021,6 +1054,10 @@ class BatchScheduler:
                 continue
             # blocking requests keep only frames whose slow id is a semantic token (generate_blocking, lm/generate.py:196-207)
             cols = semantic_columns(codes[slot, r.emitted:n], tc, nq)
+            if r.seg is None and r.slot_sampling is not None and r.slot_sampling.scored and n > r.emitted:
+                if scores is None:
+                    raise RuntimeError("scheduler lost the scores of a request")
+                r.lp.append(scores[slot, r.emitted:n].copy())
             r.emitted = n
             if cols.shape[0]:
                 r.pending.append(cols)
@@ -1039,7 +1076,15 @@ class BatchScheduler:
                 continue
             if finished:
                 release(r)
-                self._finished.append(r)
+                if r.lp:
+                    from ..config import mean_logprob
+
+                    r.logprobs = np.concatenate(r.lp)
+                    r.mean_logprob = mean_logprob(r.logprobs)
+                if r.take_of is not None:
+                    self._end(r)  # (reports to its parent: only the winner's codes see the codec)
+                else:
+                    self._finished.append(r)
         if stream_items:
             d = stream_pass or _Delivery(None, None, [])
             d.items, d.urgent = stream_items, urgent
@@ -1399,10 +1444,47 @@ class BatchScheduler:
             if r.cancelled or e is not None:
                 self._end(r.part_of[0], e)
             return
+        if r.take_of is not None:  # a take of a best_of request: the parent answers
+            if not r.closed:
+                r.closed = True
+                self._take_ended(r, e)
+            return
         if not r.closed:
             r.closed = True
             self._counts["failed" if e is not None else ("cancelled" if r.cancelled else "completed")] += 1
             r.out.put(e)
+
+    def _take_ended(self, take: _Request, e: Optional[Exception]) -> None:
+        """A take of a best_of request has ended (its frames are through, it failed, or it was cancelled).  A failure fails the
+        parent and cancels the other takes; when the last take has ended, the winner (``config.rank_takes``) becomes the parent's
+        codec job, and only it is decoded."""
+        from ..config import rank_takes
+
+        parent = take.take_of[0]
+        if parent.closed:
+            return
+        if e is not None:
+            for t in parent.take_reqs:
+                t.cancelled = True
+            self._end(parent, e)
+            return
+        if not all(t.closed for t in parent.take_reqs):
+            return
+        if parent.cancelled or any(t.cancelled for t in parent.take_reqs):
+            parent.cancelled = True
+            self._end(parent)
+            return
+        ts = parent.take_reqs
+        order = rank_takes([(t.finish_reason, t.mean_logprob) for t in ts])
+        win = ts[order[0]]
+        parent.takes = [{"seed": t.sampling.seed, "mean_logprob": t.mean_logprob, "min_logprob": float(t.logprobs.min()), "frames": int(len(t.logprobs)),
+                         "finish_reason": t.finish_reason, "chosen": t is win} for t in ts]
+        parent.sampling, parent.logprobs, parent.mean_logprob = win.sampling, win.logprobs, win.mean_logprob
+        parent.finish_reason, parent.reasons, parent.frame_counts = win.finish_reason, list(win.reasons), list(win.frame_counts)
+        parent.pending, parent.emitted = win.pending, win.emitted
+        for t in ts:
+            t.pending = []
+        self._finished.append(parent)
 
     def stats(self) -> dict:
         """Counters since start (served by ``GET /v1/stats``): requests by outcome, audio frames handed to clients, ticks,

@@ -113,6 +113,10 @@ class ServerSettings(BaseModel):
     min_frames_per_byte: Optional[float] = Field(default=None, ge=0, allow_inf_nan=False)
     max_frames_per_byte: Optional[float] = Field(default=None, ge=0, allow_inf_nan=False)
 
+    # (extension) the most takes a request's ``best_of`` may ask for; a body above it is answered 400.  Every take
+    # holds a slot for its whole length
+    max_best_of: int = Field(default=4, ge=1, le=8)
+
     model_config = {"protected_namespaces": ()}
 
     @model_validator(mode="after")
