@@ -357,6 +357,45 @@ int smoltts_session_set_slot_score(SmolttsSession* s, const int32_t* slots_host,
  * 4 (any slot of such a form, asked or not); other entries keep what they held.  stride = max_frames; may be NULL. */
 int smoltts_session_logprobs(SmolttsSession* s, float** logprob_dev, int32_t* stride);
 
+/* (ABI 9, additive) Where chosen heads of the slow attention look while a frame is produced.  For a decode row of slot s at position
+ * pos that produces frame f, and a chosen (layer, query head) pair: p = the softmax over keys 0 .. pos of that head, the distribution
+ * the slow attention weighs V with; over the slot's text window [t0, t1) clipped to the visible keys
+ *   m = sum_{j in window} p_j  (the mass on the text),   s1 = sum_{j in window} p_j (j - t0)  (the first moment)
+ * are written to out[s][f][pair] = (m, s1); the host forms the centroid s1 / m.  Host model and the fit to times: smoltts_amd/align.py.
+ *
+ * smoltts_session_set_align_heads chooses the pairs: n <= SMOLTTS_MAX_ALIGN_HEADS (layer, head) pairs sorted by layer (ties in any
+ * order), each inside the model; n = 0 turns the feature off (out_dev may then be NULL).  out_dev is caller-owned, 16-byte aligned,
+ * out_bytes >= smoltts_session_align_bytes(s, n): the call places the session's [max_batch] window table (and the upload area of
+ * smoltts_session_set_slot_align) in front of the float rows [max_batch][max_frames][n][2] and zeroes the table on the null stream
+ * (waited for: the call takes no stream).  The session slab is untouched.  The call first waits for the whole device
+ * (hipDeviceSynchronize), with n = 0 as well: frames in flight on any stream may be replaying a graph of a form with bit 5 or writing
+ * the buffer being replaced; then the captured graphs of those forms are dropped.  Not for the serving loop's hot path.
+ * smoltts_session_align_bytes: the size of that buffer for n pairs (0 for n outside 1 .. SMOLTTS_MAX_ALIGN_HEADS): a size helper,
+ * as smoltts_session_slab_bytes is for the slab. */
+#define SMOLTTS_MAX_ALIGN_HEADS 16
+size_t smoltts_session_align_bytes(SmolttsSession* s, int32_t n);
+int smoltts_session_set_align_heads(SmolttsSession* s, const int32_t* layers_host, const int32_t* heads_host, int32_t n, void* out_dev,
+                                    size_t out_bytes);
+
+/* (ABI 9, additive) Set the windows of slots_host[0 .. n): 0 <= t0, t1 <= max_seq; t1 <= t0 switches the slot's measurement off.
+ * Uploaded like the slot length entries (pinned ring, no host wait, ordered on `stream`; the first per-slot call of any kind puts
+ * the session in slot mode), and behind the upload the rows out[slot][*][*] of the listed slots are filled with (m, s1) = (-1, 0),
+ * "not measured": a frame whose slow step ran as a prefill row (frame 0 after smoltts_lm_prefill) keeps that value.  "Some slot's
+ * window is on" is bit 5 of the graph form: in a form that has it every decode frame queues one launch behind the block of each
+ * layer that has chosen heads, in the frame's one serial chain.  A row writes nothing while its slot is masked, its window is off,
+ * frames[slot] >= max_frames or its position lies outside the cache.  No id changes; while every window is off, the frames launch
+ * exactly the kernels they launch without this call. */
+int smoltts_session_set_slot_align(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* t0_host,
+                                   const int32_t* t1_host, void* stream);
+
+/* (ABI 9, additive) Diagnostic, for tests: reads host state only and changes nothing.  The graph form the next frame launches
+ * would take (>= 0: bit 0 / 1 = some slot samples its slow token / its
+ * depth codes, bit 2 = filters, bit 3 = length entries, bit 4 = scores, bit 5 = alignment windows), or a negative status. */
+int smoltts_session_graph_form(SmolttsSession* s);
+
+/* (ABI 9, additive) The rows: float [max_batch][max_frames][*n_pairs][2] inside the caller's buffer (NULL, 0 while off). */
+int smoltts_session_alignment(SmolttsSession* s, float** out_dev, int32_t* n_pairs);
+
 /* (ABI 9, additive) Diagnostic: the slow head's fp32 logits of the latest frame, [max_batch][*ld] (ld = vocab_size; may be NULL),
  * as the slow pick read them -- in front of the length entry and the penalty.  Overwritten by every frame. */
 int smoltts_session_slow_logits(SmolttsSession* s, float** logits_dev, int32_t* ld);
@@ -1035,6 +1074,16 @@ int smoltts_k_attention_kv(const float* q_dev, const void* k_cache_dev, const vo
                            const int32_t* row_pos_dev, const int32_t* row_slot_dev, int32_t n_rows,
                            int32_t n_q_heads, int32_t n_kv_heads, int32_t cache_len, int32_t window,
                            float* out_dev, void* out_x3_dev, int32_t kv_format, void* stream);
+/* (ABI 9, additive) Text mass and first moment of chosen query heads over the keys the attention above sees with window 0
+ * (smoltts_session_set_align_heads has the definition), as one launch: q_dev [n_rows][n_q_heads*64]; k_cache_dev
+ * [slots][n_kv_heads][cache_len][64] in kv_format; row r is slot row_slot_dev[r] at position row_pos_dev[r] and produces frame
+ * row_frame_dev[r]; windows_dev int32 [slots][2] = (t0, t1); heads_host: n_heads <= SMOLTTS_MAX_ALIGN_HEADS query heads;
+ * out_dev float [slots][max_frames][n_heads][2].  A row writes nothing when row_mask_dev[r] == 0, its slot's t1 <= t0, its frame
+ * index is outside [0, max_frames) or its position outside the cache. */
+int smoltts_k_attention_align(const float* q_dev, const void* k_cache_dev, int32_t kv_format, const int32_t* row_pos_dev,
+                              const int32_t* row_slot_dev, const int32_t* row_frame_dev, const int32_t* row_mask_dev,
+                              const int32_t* windows_dev, const int32_t* heads_host, int32_t n_heads, int32_t n_rows, int32_t n_q_heads,
+                              int32_t n_kv_heads, int32_t cache_len, int32_t max_frames, float* out_dev, void* stream);
 /* The same with the keys of every (row, kv head) pair dealt over two workgroups and merged inside the launch (decode frames
  * at B <= 32: rows x kv heads <= 128, caches longer than 128 entries; other shapes run the one-workgroup kernels).
  * split_part_dev: 128 * 2 * (4 * 64 + 8) floats of scratch; split_ticket_dev: 128 int32 zeroed ONCE (tickets count up across

@@ -19,15 +19,23 @@ class NoEncoderError(ValueError):
 class SmolTTS:
     def __init__(self, model_id: Optional[str] = None, checkpoint_dir: Optional[str] = None,
                  mimi_checkpoint: Optional[str] = None, numerics=None, state=None, config=None, mimi_state=None,
-                 codec_window: int = 0, weight_format: str = "bf16", verbose: bool = False, watermark=None):
+                 codec_window: int = 0, weight_format: str = "bf16", verbose: bool = False, watermark=None,
+                 alignment_heads=None):
         """``checkpoint_dir``: config.json + tokenizer.json + model.safetensors | model.pth (reference
         layouts).  ``mimi_checkpoint``: the Hugging Face kyutai/mimi ``model.safetensors`` (or its
         directory).  ``state``/``config``/``mimi_state`` allow in-memory (e.g. synthetic) weights.
         ``model_id`` (Hugging Face download in the reference) needs network access and is refused.
         ``weight_format="fp8"`` stores the Linears as e4m3 with per-row scales (``packing.fp8_reference_state`` is the model
         then computed).  ``watermark`` (a ``watermark.Watermark``; None: none): everything ``__call__`` and ``stream`` return
-        carries the key's mark, added on the GPU last of the float stages (watermark.py)."""
+        carries the key's mark, added on the GPU last of the float stages (watermark.py).
+        ``alignment_heads`` (``[(layer, head), ...]``, at most 16; None: none): the heads of the slow attention that
+        ``__call__(..., timestamps=True)`` reads character times from (align.py).  Which heads of a checkpoint track
+        the text is the operator's to find: ``python -m smoltts_amd.align rank``."""
         import torch  # noqa: F401
+
+        from .align import check_heads
+
+        self.last_alignment = None  # align.Alignment of the last call that asked for timestamps
 
         from .watermark import Watermark
 
@@ -53,6 +61,7 @@ class SmolTTS:
                 raise ValueError("pass mimi_checkpoint (kyutai/mimi model.safetensors) or mimi_state")
             mimi_state = load_mimi_state(mimi_checkpoint)
         self.config = config
+        self.alignment_heads = check_heads(alignment_heads, config)
         self.tokenizer = tokenizer
         self.token_config = TokenConfig.from_tokenizer(tokenizer, config)
         self.lm = LMEngine(config, state, self.token_config, numerics or NumericsMode.torch_reference(), weight_format=weight_format)
@@ -124,18 +133,20 @@ class SmolTTS:
         return generation_settings or GenerationSettings()
 
     def generate_codes(self, inputs: List[str], voices: Optional[List[str]] = None, generation_settings=None, speakers=None,
-                       sampling=None):
+                       sampling=None, timestamps: bool = False):
         """Batched synthesis to audio-code grids: one (n_codebooks, F_b) uint32 array per input.
         ``sampling``: a ``config.RequestSampling`` for every input, or a list of one per input; missing fields come from the
         generation settings, and a sampled entry without a seed draws one (see ``last_sampling``).  The inputs then sample
         independently, each with the request key of its seed: the same seed gives the same codes whatever the
-        other inputs are, as long as the batch selects the same kernel variants.  None: every input samples with the settings."""
+        other inputs are, as long as the batch selects the same kernel variants.  None: every input samples with the settings.
+        ``timestamps`` (needs ``sampling`` and the instance's ``alignment_heads``): the frames also measure where those heads look
+        over each input's own text; ``_align_rows`` then holds per input (rows [frames, heads, 2], text window, token row)."""
         voices = voices or ["heart"] * len(inputs)
         speakers = speakers or [None] * len(inputs)
         prompts = [self._get_prompt(t, v, sp) for t, v, sp in zip(inputs, voices, speakers)]
-        return self.generate_prompt_codes(prompts, generation_settings, sampling)
+        return self.generate_prompt_codes(prompts, generation_settings, sampling, timestamps=timestamps)
 
-    def generate_prompt_codes(self, prompts, generation_settings=None, sampling=None):
+    def generate_prompt_codes(self, prompts, generation_settings=None, sampling=None, timestamps: bool = False):
         """``generate_codes`` of ready prompt grids ((1 + depth, T) each: ``build_prompt``, ``longform.chain_prompt``)."""
         import numpy as np
 
@@ -144,7 +155,15 @@ class SmolTTS:
         settings = self._settings(generation_settings)
         resolved = resolve_sampling(sampling, settings, len(prompts))
         self.last_sampling = resolved  # what the call sampled with, seeds included (None: the settings, session-wide)
-        gen = BatchGenerator(self.lm, prompts, settings, frames_per_sync=16, sampling=resolved)
+        windows = None
+        if timestamps:
+            from .align import window_of
+
+            if not self.alignment_heads or resolved is None:
+                raise ValueError("timestamps need alignment_heads and per-input sampling entries")
+            windows = [window_of(np.asarray(p)[0], self.tokenizer) for p in prompts]
+        gen = BatchGenerator(self.lm, prompts, settings, frames_per_sync=16, sampling=resolved,
+                             align=None if windows is None else (self.alignment_heads, windows))
         cols: List[list] = [[] for _ in prompts]
         for row in gen:
             for b, tok in enumerate(row):
@@ -158,6 +177,7 @@ class SmolTTS:
         # per input, the float32 scores of its frames (None where the input did not ask: RequestSampling.logprobs / best_of)
         scores = gen.logprobs() if resolved is not None and any(r.scored for r in resolved) else None
         self.last_logprobs_all = None if scores is None else [lp if r.scored else None for lp, r in zip(scores, resolved)]
+        self._align_rows = None if windows is None else [(r, w, np.asarray(p)[0].copy()) for r, w, p in zip(gen.alignment(), windows, prompts)]
         gen.close()
         if self.verbose and self.last_stats:
             st = self.last_stats
@@ -192,7 +212,7 @@ class SmolTTS:
     def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None,
                  speed: Optional[float] = None, segment=False, loudness: Optional[float] = None, watermark: Optional[bool] = None,
                  trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-                 silence_threshold_db: Optional[float] = None):
+                 silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None):
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
         (per-request temperature / min_p / seed, as in ``generate_codes``).  ``speed`` (0.25 to 4.0; None / 1.0: unchanged):
         the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
@@ -206,11 +226,24 @@ class SmolTTS:
         the instance's mark whole on the GPU, last: behind the seam join, the loudness gain and the stretch (``watermark.py``).
         ``trim_silence`` (cut the leading and trailing silence), ``max_pause_s`` (0.1 to 2.0: cap the pauses) and
         ``silence_threshold_db`` (-72 to -6 dBFS; default 2^-8): the codec's PCM is trimmed on the GPU first of all
-        (``trim.py``), each segment of a segmented text before the seam join; ``last_trimmed_s`` is what was cut."""
+        (``trim.py``), each segment of a segmented text before the seam join; ``last_trimmed_s`` is what was cut.
+        ``timestamps`` (needs the instance's ``alignment_heads``; not with ``segment``, the trim options or ``best_of``):
+        ``last_alignment`` becomes the ``align.Alignment`` of the audio returned -- per character of ``input`` its start and end in
+        seconds, read from where the chosen heads of the slow attention look while each frame is produced.  The option changes no
+        id: with ``sampling=`` (its seed) or greedy settings the audio is the one the call returns without it.  A call without
+        ``sampling=`` whose settings sample runs in the per-request mode here (the measurement exists only there) and draws a
+        request seed, so its audio is another draw than the session-wide one; ``last_sampling`` carries the seed that replays it."""
         from .request import parse_request
 
         req = parse_request(input, speed=speed, segment=segment, loudness=loudness, watermark=watermark, trim_silence=trim_silence,
-                            max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db)  # a bad request is refused before any work
+                            max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db,
+                            timestamps=timestamps)  # a bad request is refused before any work
+        self.last_alignment = None
+        if req.timestamps:
+            if not self.alignment_heads:
+                raise ValueError("timestamps need alignment_heads: rank a checkpoint's heads with `python -m smoltts_amd.align rank`")
+            if sampling is not None and getattr(sampling, "takes", 1) > 1:
+                raise ValueError("timestamps cannot be combined with best_of")
         marked = self._marks(req.watermark)
         voice = voice if voice is not None else "heart"
         self.last_trimmed_s = 0.0
@@ -220,8 +253,12 @@ class SmolTTS:
         if req.plan is not None:
             pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling, req)
         else:
-            if self._bounds_on or sampling is not None:
+            if self._bounds_on or sampling is not None or req.timestamps:  # (the measurement exists in slot mode only)
+                from .config import RequestSampling
                 from .generate import resolve_sampling
+
+                if sampling is None and req.timestamps:
+                    sampling = RequestSampling()
 
                 st = self._settings(generation_settings)
                 generation_settings, one = self._bounded(input, st, resolve_sampling(sampling, st, 1))
@@ -230,7 +267,7 @@ class SmolTTS:
                 codes = self._best_of(input, voice, speaker, generation_settings, sampling)
             else:
                 codes = self.generate_codes([input], [voice], generation_settings, speakers=None if speaker is None else [speaker],
-                                            sampling=sampling)[0]
+                                            sampling=sampling, timestamps=req.timestamps)[0]
                 if self.last_logprobs_all is not None and self.last_logprobs_all[0] is not None:
                     from .config import mean_logprob
 
@@ -251,6 +288,13 @@ class SmolTTS:
             from .stages import watermark_embed
 
             pcm = watermark_embed(pcm, marked, self.lm.device)
+        if req.timestamps:
+            from .align import align
+
+            rows, (t0, t1), row0 = self._align_rows[0]
+            F = int(codes.shape[1])  # audio frames: the <|im_end|> frame carries none
+            self.last_alignment = align(input, row0[t0:t1], rows[:F, :, 0], rows[:F, :, 1], self.tokenizer, speed=req.speed,
+                                        duration_s=pcm.size / self.sampling_rate)
         return pcm
 
     def _check_best_of(self, sampling, generation_settings, stream: bool = False, segmented: bool = False) -> None:

@@ -24,6 +24,7 @@ class SmolttsError(RuntimeError):
 ABI_VERSION = 9
 OK, E_INVALID, E_HIP, E_STATE, E_CAPACITY = 0, -1, -2, -3, -4
 MAX_LAYERS, MAX_FAST_LAYERS, MIMI_MAX_LAYERS = 64, 16, 16
+MAX_ALIGN_HEADS = 16
 KV_F32, KV_BF16 = 0, 1
 W_BF16, W_FP8 = 0, 1
 OPT_QKV_TABLE, OPT_COMMIT_PICKS, OPT_SPLIT_ATTN, OPT_STREAM_W, OPT_FUSE_DEPTH_ATTN, OPT_FUSE_PICK, OPT_FP8_PREFILL = 1, 2, 3, 4, 5, 6, 7
@@ -188,6 +189,11 @@ SIGNATURES = {
     "smoltts_session_set_slot_length": (INT, "p p i p p p"),
     "smoltts_session_set_slot_score": (INT, "p p i p"),
     "smoltts_session_logprobs": (INT, "p p* i*"),
+    "smoltts_session_align_bytes": (SIZE, "p i"),
+    "smoltts_session_set_align_heads": (INT, "p p p i p z"),
+    "smoltts_session_set_slot_align": (INT, "p p i p p p"),
+    "smoltts_session_alignment": (INT, "p p* i*"),
+    "smoltts_session_graph_form": (INT, "p"),
     "smoltts_session_slow_logits": (INT, "p p* i*"),
     "smoltts_session_outputs": (INT, "p p* p* p* p*"),
     "smoltts_session_kv_cache": (INT, "p p* p* Q*"),
@@ -271,6 +277,7 @@ SIGNATURES = {
     "smoltts_k_x3_pack": (INT, "p q i i p p p p p p"),
     "smoltts_k_attention": (INT, "p p p p p i i i i i p p p"),
     "smoltts_k_attention_kv": (INT, "p p p p p i i i i i p p i p"),
+    "smoltts_k_attention_align": (INT, "p p i p p p p p p i i i i i i p p"),
     "smoltts_k_attention_split": (INT, "p p p p p i i i i i p p i p p p"),
     "smoltts_k_attention_rows3": (INT, "p p p p p i i i i i p i p"),
     "smoltts_k_embed": (INT, "p i i p p i i i i i i p p"),

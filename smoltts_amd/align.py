@@ -1,0 +1,303 @@
+"""Character timestamps from the slow transformer's attention: the host side.
+
+The session measures, per audio frame f and chosen (layer, head) pair, the mass m its attention puts on the request's own text and
+the first moment s1 of that mass over the text's positions (``LMSession.set_align_heads`` / ``set_slot_align``).  The tokenizer is a
+byte-level BPE without merges, so a position is a byte (or an added token spelled out in the text), and s1 / m is "which byte the
+head looks at" in units of tokens.  Here that curve is made monotone (weighted isotonic regression), cut into token intervals and
+mapped to characters and seconds.  numpy only; nothing here touches the GPU except ``measure_heads`` and the command line, which run
+the ranking tool on a checkpoint:
+
+    python -m smoltts_amd.align rank --checkpoint DIR --texts FILE
+
+Which heads of a checkpoint track the text is a property of that checkpoint; nobody has checked this on real speech (README).
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from dataclasses import dataclass, field
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+FRAME_SAMPLES, SAMPLE_RATE = 1920, 24_000
+FRAME_S = FRAME_SAMPLES / SAMPLE_RATE
+# Frames whose chosen heads put less than this much mass (summed over the heads) on the text carry no weight in the fit: the
+# centroid s1 / m of such a frame is a ratio of two small numbers -- the head is looking at the speaker turns, the audio history
+# or its attention sink -- and its fp32 noise, about 1e-7 on m, is no longer small against m.  0.05 keeps every frame in which one
+# head spends a twentieth of its attention on the text; DESIGN.md 21.
+MIN_MASS = 0.05
+
+
+def check_heads(heads, config=None) -> List[Tuple[int, int]]:
+    """``alignment_heads`` of a front end -> sorted ``[(layer, head), ...]`` (None: none); ``ValueError`` for pairs that are no pairs
+    of ints, for more than 16, for duplicates and, given the model's ``config``, for pairs outside it."""
+    if heads is None:
+        return []
+    out = []
+    for p in heads:
+        if not isinstance(p, (list, tuple)) or len(p) != 2 or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in p):
+            raise ValueError(f"alignment_heads: {p!r} is not a [layer, head] pair")
+        out.append((int(p[0]), int(p[1])))
+    if len(out) > 16 or len(set(out)) != len(out):
+        raise ValueError("alignment_heads: at most 16 distinct [layer, head] pairs")
+    for l, h in out:
+        if l < 0 or h < 0 or (config is not None and (l >= config.n_layer or h >= config.n_head)):
+            raise ValueError(f"alignment_heads: [{l}, {h}] lies outside the model")
+    return sorted(out)
+
+
+# ------------------------------------------------------------------------------------------------ the prompt's text window
+def window_of(row0: Sequence[int], tokenizer) -> Tuple[int, int]:
+    """[t0, t1) of the request's own user text inside its prompt grid's token row: behind the last ``<|im_start|>user\\n``, up to
+    that turn's closing ``<|im_end|>``.  With a cloned voice's speaker turns in front (user turns of their own) it is the last."""
+    ids = [int(x) for x in row0]
+    head = [tokenizer.token_to_id("<|im_start|>"), tokenizer.token_to_id("user"), tokenizer.token_to_id("\n")]
+    end = tokenizer.token_to_id("<|im_end|>")
+    if None in head or end is None:
+        raise ValueError("the tokenizer has no ChatML tokens")
+    starts = [i for i in range(len(ids) - 2) if ids[i:i + 3] == head]
+    if not starts:
+        raise ValueError("the prompt has no user turn")
+    t0 = starts[-1] + 3
+    ends = [i for i in range(t0, len(ids)) if ids[i] == end]
+    if not ends:
+        raise ValueError("the prompt's last user turn is not closed")
+    return t0, ends[-1]
+
+
+def token_spans(text: str, ids: Sequence[int], tokenizer=None) -> List[Tuple[int, int]]:
+    """Per character of ``text`` the tokens [a, b) of ``ids`` (the text's own tokens, in order) that spell it.  A byte token
+    belongs to the character whose UTF-8 encoding contains it (one token per byte; a vocabulary whose base is the latin-1 code
+    points has one token per such character); an added token spelled out in the text covers all of its characters (``tokenizer``
+    names it); a character the tokenizer dropped has an empty span where it would stand."""
+    ids = [int(x) for x in ids]
+    spans: List[Tuple[int, int]] = []
+    k, i, n = 0, 0, len(text)
+    while i < n:
+        ch = text[i]
+        if k < len(ids) and ids[k] >= 256 and tokenizer is not None:
+            tok = tokenizer.id_to_token(ids[k])
+            if tok and text.startswith(tok, i):
+                spans += [(k, k + 1)] * len(tok)
+                i, k = i + len(tok), k + 1
+                continue
+        b = list(ch.encode("utf-8"))
+        if ids[k:k + len(b)] == b:
+            spans.append((k, k + len(b)))
+            k += len(b)
+        elif ord(ch) < 256 and k < len(ids) and ids[k] == ord(ch):
+            spans.append((k, k + 1))
+            k += 1
+        else:
+            spans.append((k, k))  # dropped by the tokenizer
+        i += 1
+    if k != len(ids):
+        raise ValueError(f"the ids do not spell the text: {len(ids) - k} of {len(ids)} tokens left over")
+    return spans
+
+
+# ------------------------------------------------------------------------------------------------ the fit
+def isotonic(y: Sequence[float], w: Sequence[float]) -> np.ndarray:
+    """Weighted isotonic regression (non-decreasing) by pool-adjacent-violators: the x that minimises sum w (x - y)^2 under
+    x_0 <= x_1 <= ..; every weight > 0."""
+    y, w = np.asarray(y, np.float64), np.asarray(w, np.float64)
+    if y.size and not (w > 0).all():
+        raise ValueError("isotonic: weights must be positive")
+    vals: List[float] = []
+    wts: List[float] = []
+    cnt: List[int] = []
+    for yi, wi in zip(y, w):
+        vals.append(float(yi)); wts.append(float(wi)); cnt.append(1)
+        while len(vals) > 1 and vals[-2] > vals[-1]:  # pool the two last blocks
+            ww = wts[-2] + wts[-1]
+            vals[-2] = (vals[-2] * wts[-2] + vals[-1] * wts[-1]) / ww
+            wts[-2] = ww
+            cnt[-2] += cnt[-1]
+            vals.pop(); wts.pop(); cnt.pop()
+    return np.repeat(np.asarray(vals, np.float64), cnt) if vals else np.zeros(0)
+
+
+@dataclass
+class Fit:
+    starts: np.ndarray     # [n_tokens] start of each token, in frames
+    ends: np.ndarray       # [n_tokens]
+    mass: np.ndarray       # [frames] summed mass of the chosen heads (-1: not measured)
+    centroid: np.ndarray   # [frames] s1 / m of the sums (nan where the frame carries no weight)
+    curve: np.ndarray      # [frames] the fitted monotone curve at the frame centres (interpolated over the weightless frames)
+
+
+def fit(m: np.ndarray, s1: np.ndarray, n_tokens: int) -> Fit:
+    """``m``, ``s1`` [frames] or [frames, heads] -> token intervals in frames.  The chosen heads are summed per frame; a frame with
+    m < 0 in any head (not measured) or a summed mass below ``MIN_MASS`` has weight 0, the others their mass.  The centroids are
+    fitted by weighted isotonic regression; token i starts where the fitted curve, linear between frame centres f + 0.5, passes
+    i - 0.5, and ends where token i + 1 starts; the first start is 0, the last end is the number of frames."""
+    m, s1 = np.asarray(m, np.float64), np.asarray(s1, np.float64)
+    if m.ndim == 1:
+        m, s1 = m[:, None], s1[:, None]
+    F = m.shape[0]
+    measured = (m >= 0).all(axis=1) if m.shape[1] else np.zeros(F, bool)
+    mass = np.where(measured, m.sum(axis=1), -1.0)
+    ok = measured & (mass >= MIN_MASS)
+    cen = np.full(F, np.nan)
+    cen[ok] = s1.sum(axis=1)[ok] / mass[ok]
+    x = np.nonzero(ok)[0] + 0.5
+    yhat = isotonic(cen[ok], mass[ok])
+    starts = np.zeros(max(n_tokens, 0))
+    if x.size == 0:  # nothing measured: the tokens share the utterance evenly
+        starts = np.arange(n_tokens) * (F / max(n_tokens, 1))
+        curve = np.full(F, np.nan)
+    else:
+        curve = np.interp(np.arange(F) + 0.5, x, yhat)
+        for i in range(1, n_tokens):
+            level = i - 0.5
+            k = int(np.searchsorted(yhat, level, side="left"))  # the first weighted frame at or above the level
+            if k == 0:
+                starts[i] = 0.0
+            elif k == x.size:
+                starts[i] = float(F)
+            else:
+                starts[i] = x[k - 1] + (level - yhat[k - 1]) / (yhat[k] - yhat[k - 1]) * (x[k] - x[k - 1])
+    starts = np.minimum(np.maximum.accumulate(starts), F) if n_tokens else starts
+    ends = np.append(starts[1:], float(F)) if n_tokens else starts
+    return Fit(starts, ends, mass, cen, curve)
+
+
+@dataclass
+class Alignment:
+    """ElevenLabs' alignment object, plus the per-frame mass and centroid the times were fitted to."""
+    characters: List[str]
+    start_s: List[float]
+    end_s: List[float]
+    mass: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    centroid: np.ndarray = field(default_factory=lambda: np.zeros(0))
+
+    def to_json(self) -> dict:
+        return {"characters": list(self.characters), "character_start_times_seconds": [float(t) for t in self.start_s],
+                "character_end_times_seconds": [float(t) for t in self.end_s]}
+
+
+def align(text: str, ids: Sequence[int], m: np.ndarray, s1: np.ndarray, tokenizer=None, speed: Optional[float] = None,
+          duration_s: Optional[float] = None) -> Alignment:
+    """``text`` and its tokens ``ids`` (the prompt's window), the rows ``m`` / ``s1`` [audio frames(, heads)] -> ``Alignment``.
+    One frame is 1920 samples at 24 kHz.  ``speed`` other than 1: the times are divided by it -- nominal: the stretch (WSOLA) is
+    piecewise and moves a sample by up to a search window around that.  ``duration_s``: what was delivered; the last end is set to
+    it and no time lies behind it."""
+    spans = token_spans(text, ids, tokenizer)
+    ft = fit(m, s1, len(ids))
+    scale = FRAME_S / (float(speed) if speed else 1.0)
+    total = ft.mass.shape[0] * scale if duration_s is None else float(duration_s)
+    ts, te = np.minimum(ft.starts * scale, total), np.minimum(ft.ends * scale, total)
+    if te.size:
+        te[-1] = total
+    start_s, end_s = [], []
+    for a, b in spans:
+        if b > a:
+            start_s.append(float(ts[a])); end_s.append(float(te[b - 1]))
+        else:  # a dropped character: an empty interval where it would stand
+            t = float(ts[a]) if a < ts.size else total
+            start_s.append(t); end_s.append(t)
+    return Alignment(list(text), start_s, end_s, ft.mass, ft.centroid)
+
+
+# ------------------------------------------------------------------------------------------------ which heads track the text
+@dataclass
+class HeadScore:
+    layer: int
+    head: int
+    mean_mass: float    # mean text mass over the measured frames
+    monotone: float     # mass-weighted share of the frame-to-frame centroid steps that are >= 0
+    coverage: float     # share of the text the fitted curve runs over
+
+    @property
+    def score(self) -> float:
+        return self.mean_mass * self.monotone * self.coverage
+
+
+def rank_heads(runs: Sequence[dict]) -> List[HeadScore]:
+    """``runs``: per utterance ``{"pairs": [(layer, head), ..], "m": [frames, pairs], "s1": [frames, pairs], "n_tokens": n}`` ->
+    one ``HeadScore`` per (layer, head), averaged over the utterances that measured it, best first."""
+    acc: dict = {}
+    for run in runs:
+        m, s1, n = np.asarray(run["m"], np.float64), np.asarray(run["s1"], np.float64), int(run["n_tokens"])
+        for i, pair in enumerate(run["pairs"]):
+            mi, si = m[:, i], s1[:, i]
+            ok = mi >= 0
+            if not ok.any():
+                continue
+            mean_mass = float(mi[ok].mean())
+            ft = fit(mi, si, n)
+            good = ~np.isnan(ft.centroid)
+            c, wgt = ft.centroid[good], mi[good]
+            if c.size >= 2:
+                step_w = np.minimum(wgt[1:], wgt[:-1])
+                mono = float(step_w[np.diff(c) >= 0].sum() / step_w.sum())
+                cov = float(np.clip((np.nanmax(ft.curve) - np.nanmin(ft.curve)) / max(n - 1, 1), 0.0, 1.0))
+            else:
+                mono, cov = 0.0, 0.0
+            acc.setdefault((int(pair[0]), int(pair[1])), []).append((mean_mass, mono, cov))
+    out = [HeadScore(l, h, *(float(np.mean([v[k] for v in vals])) for k in range(3))) for (l, h), vals in acc.items()]
+    return sorted(out, key=lambda s: (-s.score, s.layer, s.head))
+
+
+def measure_heads(engine, prompts, windows, pairs, settings=None, max_frames: int = 256):
+    """The rows of ``pairs`` (at most ``abi.MAX_ALIGN_HEADS``) for each prompt grid with its text window, greedy unless
+    ``settings`` says otherwise: a list of ``{"pairs", "m", "s1", "n_tokens"}`` as ``rank_heads`` takes them.  Runs on the GPU."""
+    from .config import GenerationSettings, RequestSampling
+    from .generate import BatchGenerator, resolve_sampling
+
+    import dataclasses
+
+    st = dataclasses.replace(settings or GenerationSettings.greedy(), max_new_tokens=max_frames)
+    gen = BatchGenerator(engine, prompts, st, frames_per_sync=16, sampling=resolve_sampling(RequestSampling(), st, len(prompts)),
+                         align=(pairs, windows))
+    for _ in gen:
+        pass
+    rows = gen.alignment()
+    gen.close()
+    return [{"pairs": sorted((int(l), int(h)) for l, h in pairs), "m": r[:, :, 0], "s1": r[:, :, 1], "n_tokens": w[1] - w[0]}
+            for r, w in zip(rows, windows)]
+
+
+def _rank_main(args) -> int:
+    from .abi import MAX_ALIGN_HEADS
+    from .checkpoint import load_checkpoint
+    from .config import NumericsMode, TokenConfig
+    from .lm import LMEngine
+    from .prompt import PromptEncoder
+
+    texts = [t.strip() for t in open(args.texts, encoding="utf-8").read().splitlines() if t.strip()]
+    if not texts:
+        print("no texts", file=sys.stderr)
+        return 2
+    config, tokenizer, state = load_checkpoint(args.checkpoint)
+    tc = TokenConfig.from_tokenizer(tokenizer, config)
+    engine = LMEngine(config, state, tc, NumericsMode.torch_reference())
+    enc = PromptEncoder.from_config(tokenizer, config, tc)
+    prompts = [enc.build_prompt(t, args.voice) for t in texts]
+    windows = [window_of(p[0], tokenizer) for p in prompts]
+    every = [(l, h) for l in range(config.n_layer) for h in range(config.n_head)]
+    runs = []
+    for i in range(0, len(every), MAX_ALIGN_HEADS):  # the heads 16 at a time: the same greedy utterances every time
+        runs += measure_heads(engine, prompts, windows, every[i:i + MAX_ALIGN_HEADS], max_frames=args.max_frames)
+    print(f"{'layer':>5} {'head':>4} {'mass':>7} {'monotone':>8} {'coverage':>8} {'score':>7}")
+    for s in rank_heads(runs)[:args.top]:
+        print(f"{s.layer:5d} {s.head:4d} {s.mean_mass:7.4f} {s.monotone:8.4f} {s.coverage:8.4f} {s.score:7.4f}")
+    engine.close()
+    return 0
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m smoltts_amd.align", description=__doc__.split("\n\n")[0])
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    r = sub.add_parser("rank", help="rank every (layer, head) of a checkpoint by how well it tracks the text; pick alignment_heads from the top")
+    r.add_argument("--checkpoint", required=True)
+    r.add_argument("--texts", required=True, help="a file with one text per line")
+    r.add_argument("--voice", default="heart")
+    r.add_argument("--max-frames", type=int, default=256)
+    r.add_argument("--top", type=int, default=32)
+    return _rank_main(ap.parse_args(argv))
+
+
+if __name__ == "__main__":
+    sys.exit(main())

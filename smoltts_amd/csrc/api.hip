@@ -41,6 +41,15 @@ int smoltts_k_attention_kv(const float* q_dev, const void* k_cache_dev, const vo
                           window, out_dev, out_x3_dev, (hipStream_t)stream, kv_format);
 }
 
+int smoltts_k_attention_align(const float* q_dev, const void* k_cache_dev, int32_t kv_format, const int32_t* row_pos_dev,
+                              const int32_t* row_slot_dev, const int32_t* row_frame_dev, const int32_t* row_mask_dev,
+                              const int32_t* windows_dev, const int32_t* heads_host, int32_t n_heads, int32_t n_rows, int32_t n_q_heads,
+                              int32_t n_kv_heads, int32_t cache_len, int32_t max_frames, float* out_dev, void* stream) {
+  return launch_attention_align(q_dev, k_cache_dev, kv_format, row_pos_dev, row_slot_dev, row_frame_dev, row_mask_dev, windows_dev,
+                                heads_host, n_heads, 0, n_heads, n_rows, n_q_heads, n_kv_heads, cache_len, max_frames, out_dev,
+                                (hipStream_t)stream);
+}
+
 int smoltts_k_attention_rows3(const float* q_dev, const void* k_cache3_dev, const void* v_cache3_dev, const int32_t* row_pos_dev,
                               const int32_t* row_slot_dev, int32_t n_rows, int32_t rows_per_slot, int32_t n_heads, int32_t cache_len,
                               int32_t window, float* out_dev, int32_t b3_products, void* stream) {

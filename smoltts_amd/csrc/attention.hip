@@ -1059,6 +1059,164 @@ int launch_attention(const float* q, const void* kc, const void* vc, const int32
   return SMOLTTS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Where a chosen query head of the slow attention looks, reduced to two numbers.  For row r (slot s, position pos,
+// frame index f) and query head hq: p = softmax over keys 0 .. pos of (q / 8) . K, the distribution attn_kernel weighs V with, and over
+// the slot's text window [t0, t1) clipped to the visible keys
+//   out[s][f][pair] = (m, s1),  m = sum_{j in window} p_j,  s1 = sum_{j in window} p_j (j - t0).
+// One workgroup of 4 waves per (row, pair); 16 lanes per key with a float4 each, so the 16 lane groups take keys g, g + 16, ..
+// Pass 1 leaves every score in LDS and finds the maximum; pass 2 lets thread t sum e_j = exp(s_j - max) over keys t, t + 256, ..
+// into (denominator, mass, moment), then the wave's xor tree, then the four waves in order: an order that depends on pos and the
+// window alone, so the same (q, K, pos, window) gives the same bits in any slot of any batch.  A cache whose scores do not fit in
+// LDS is read twice instead: pass 2 recomputes each score in its lane group (the same operations, the same bits) and lane i % 16 of
+// the group takes its i-th key, which gives the same 256 partial sums.  The centroid s1 / m is the host's to form.
+struct AlignDev {
+  const float* q;
+  const void* kc;
+  const int* row_pos;
+  const int* row_slot;
+  const int* row_frame;   // [rows] index of the frame the row produces
+  const int* row_mask;    // [rows] 0: the row writes nothing
+  const int* windows;     // [slots][2] (t0, t1); t1 <= t0: the slot writes nothing
+  float* out;
+  int n_q_heads, n_kv_heads, cache_len, max_frames, n_pairs, pair0, staged;
+  int heads[SMOLTTS_MAX_ALIGN_HEADS];  // query heads of this launch's pairs (blockIdx.y)
+};
+constexpr int ALIGN_RED = 16;          // floats of LDS in front of the scores: 4 maxima, 4 x 3 sums
+constexpr int ALIGN_UN = 4;            // keys per lane group in flight
+constexpr int ALIGN_LDS_KEYS = (64 * 1024) / (int)sizeof(float) - ALIGN_RED;  // longer caches take the two-pass form
+
+template <bool KB>
+__global__ __launch_bounds__(256) void attn_align_kernel(AlignDev p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* red = smem;
+  float* sc = smem + ALIGN_RED;  // [cache_len] when staged (16-byte aligned: ALIGN_RED floats = 64 bytes)
+  const int row = blockIdx.x, pi = blockIdx.y;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int kk = lane >> 4, dl = lane & 15;
+  // every exit below is uniform over the workgroup and stands in front of the first barrier
+  if (p.row_mask[row] == 0) return;
+  const int pos = p.row_pos[row], slot = p.row_slot[row], f = p.row_frame[row];
+  if (pos < 0 || pos >= p.cache_len || f < 0 || f >= p.max_frames) return;  // (in front of every address formed from pos or f)
+  const int t0 = p.windows[2 * slot], t1 = p.windows[2 * slot + 1];
+  if (t1 <= t0) return;
+  const int L = pos + 1;
+  const int w_lo = t0 > 0 ? t0 : 0, w_hi = t1 < L ? t1 : L;  // the window's visible keys [w_lo, w_hi); empty when it begins beyond pos
+  const int hq = p.heads[pi], h = hq / (p.n_q_heads / p.n_kv_heads);
+  const long ebase = (((long)slot * p.n_kv_heads + h) * p.cache_len) * 64 + dl * 4;
+  const float4 t = *reinterpret_cast<const float4*>(p.q + (long)row * p.n_q_heads * 64 + hq * 64 + dl * 4);
+  const float4 qv = make_float4(t.x * 0.125f, t.y * 0.125f, t.z * 0.125f, t.w * 0.125f);
+  const bool staged = p.staged != 0;
+
+  auto score = [&](const float4& kv) {
+    float s = qv.x * kv.x;
+    s = fmaf(qv.y, kv.y, s);
+    s = fmaf(qv.z, kv.z, s);
+    s = fmaf(qv.w, kv.w, s);
+    return row16_sum(s);
+  };
+
+  // ---- pass 1: scores and their maximum (a maximum does not depend on the order it is taken in)
+  float mx = -INFINITY;
+  for (int j0 = wave * 4; j0 < L; j0 += 16 * ALIGN_UN) {  // (wave-uniform trip count)
+    float4 kv[ALIGN_UN];
+#pragma unroll
+    for (int u = 0; u < ALIGN_UN; ++u) {
+      const int j = j0 + u * 16 + kk;
+      kv[u] = j < L ? load_kv4<KB>(p.kc, ebase + (long)j * 64) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < ALIGN_UN; ++u) {
+      const int j = j0 + u * 16 + kk;
+      const float s = score(kv[u]);
+      if (j < L) {
+        mx = fmaxf(mx, s);
+        if (staged && dl == 0) sc[j] = s;
+      }
+    }
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  const float gm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+
+  // ---- pass 2: the three sums
+  float den = 0.f, mass = 0.f, mom = 0.f;
+  if (staged) {
+    for (int j = tid; j < L; j += 256) {
+      const float e = __expf(sc[j] - gm);
+      den += e;
+      if (j >= w_lo && j < w_hi) {
+        mass += e;
+        mom = fmaf(e, (float)(j - t0), mom);
+      }
+    }
+  } else {
+    for (int j0 = wave * 4; j0 < L; j0 += 16 * ALIGN_UN) {
+      float4 kv[ALIGN_UN];
+#pragma unroll
+      for (int u = 0; u < ALIGN_UN; ++u) {
+        const int j = j0 + u * 16 + kk;
+        kv[u] = j < L ? load_kv4<KB>(p.kc, ebase + (long)j * 64) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int u = 0; u < ALIGN_UN; ++u) {
+        const int j = j0 + u * 16 + kk;
+        const float s = score(kv[u]);
+        if (j < L && dl == ((j >> 4) & 15)) {  // key i of the group in lane i % 16: 256 partial sums, as in the staged form
+          const float e = __expf(s - gm);
+          den += e;
+          if (j >= w_lo && j < w_hi) {
+            mass += e;
+            mom = fmaf(e, (float)(j - t0), mom);
+          }
+        }
+      }
+    }
+  }
+  den = wave_sum(den); mass = wave_sum(mass); mom = wave_sum(mom);
+  if (lane == 0) { red[4 + wave * 3] = den; red[4 + wave * 3 + 1] = mass; red[4 + wave * 3 + 2] = mom; }
+  __syncthreads();
+  if (tid == 0) {
+    const float d = ((red[4] + red[7]) + red[10]) + red[13];
+    const float m = ((red[5] + red[8]) + red[11]) + red[14];
+    const float s1 = ((red[6] + red[9]) + red[12]) + red[15];
+    const float inv = 1.0f / d;  // (d >= 1: the key that holds the maximum contributes exp(0))
+    float* o = p.out + (((long)slot * p.max_frames + f) * p.n_pairs + p.pair0 + pi) * 2;
+    *reinterpret_cast<float2*>(o) = make_float2(__fmul_rn(m, inv), __fmul_rn(s1, inv));
+  }
+}
+
+int launch_attention_align(const float* q, const void* kc, int kv_format, const int32_t* row_pos, const int32_t* row_slot,
+                           const int32_t* row_frame, const int32_t* row_mask, const int32_t* windows, const int32_t* heads_host,
+                           int n_heads, int pair0, int n_pairs, int n_rows, int n_q_heads, int n_kv_heads, int cache_len, int max_frames,
+                           float* out, hipStream_t stream) {
+  ST_REQUIRE(kv_format == SMOLTTS_KV_F32 || kv_format == SMOLTTS_KV_BF16, SMOLTTS_E_INVALID, "attention_align: kv_format %d", kv_format);
+  ST_REQUIRE(q && kc && row_pos && row_slot && row_frame && row_mask && windows && heads_host && out, SMOLTTS_E_INVALID,
+             "attention_align: null pointer");
+  ST_REQUIRE(n_rows > 0 && n_kv_heads > 0 && n_q_heads % n_kv_heads == 0 && cache_len > 0 && max_frames > 0, SMOLTTS_E_INVALID,
+             "attention_align: bad shape rows=%d q_heads=%d kv_heads=%d cache_len=%d max_frames=%d", n_rows, n_q_heads, n_kv_heads,
+             cache_len, max_frames);
+  ST_REQUIRE(n_heads > 0 && n_heads <= SMOLTTS_MAX_ALIGN_HEADS && pair0 >= 0 && pair0 + n_heads <= n_pairs, SMOLTTS_E_INVALID,
+             "attention_align: %d heads at pair %d of %d (at most %d per launch)", n_heads, pair0, n_pairs, SMOLTTS_MAX_ALIGN_HEADS);
+  AlignDev d;
+  memset(&d, 0, sizeof(d));
+  d.q = q; d.kc = kc; d.row_pos = row_pos; d.row_slot = row_slot; d.row_frame = row_frame; d.row_mask = row_mask; d.windows = windows;
+  d.out = out; d.n_q_heads = n_q_heads; d.n_kv_heads = n_kv_heads; d.cache_len = cache_len; d.max_frames = max_frames;
+  d.n_pairs = n_pairs; d.pair0 = pair0; d.staged = cache_len <= ALIGN_LDS_KEYS;
+  for (int i = 0; i < n_heads; ++i) {
+    ST_REQUIRE(heads_host[i] >= 0 && heads_host[i] < n_q_heads, SMOLTTS_E_INVALID, "attention_align: head %d outside the %d query heads",
+               heads_host[i], n_q_heads);
+    d.heads[i] = heads_host[i];
+  }
+  const size_t lds = (size_t)(ALIGN_RED + (d.staged ? cache_len : 0)) * sizeof(float);
+  const dim3 grid(n_rows, n_heads);
+  if (kv_format == SMOLTTS_KV_BF16) hipLaunchKernelGGL((attn_align_kernel<true>), grid, dim3(256), lds, stream, d);
+  else hipLaunchKernelGGL((attn_align_kernel<false>), grid, dim3(256), lds, stream, d);
+  ST_CHECK_HIP(hipGetLastError());
+  return SMOLTTS_OK;
+}
+
 int launch_attention_rows3(const float* q, const void* kc3, const void* vc3, const int32_t* row_pos, const int32_t* row_slot, int n_rows,
                            int rows_per_slot, int n_heads, int cache_len, int window, float* out, hipStream_t stream, int b3_products) {
   ST_REQUIRE(q && kc3 && vc3 && row_pos && row_slot && out, SMOLTTS_E_INVALID, "attention_rows3: null pointer");

@@ -242,6 +242,12 @@ int launch_attention_rows3(const float* q, const void* kc3, const void* vc3, con
 // scratch of the key-split attention: records for this many (row, kv head) pairs x 2 parts x (4 heads x 64 + 8) floats, one ticket per pair
 constexpr int ATT_SPLIT_MAX_PAIRS = 128;
 constexpr size_t ATT_SPLIT_PART_FLOATS = (size_t)ATT_SPLIT_MAX_PAIRS * 2 * (4 * 64 + 8);
+// Text mass and first moment of chosen query heads' softmax over each row's visible keys (attention.hip, attn_align_kernel):
+// out [slots][max_frames][n_pairs][2]; this launch writes pairs pair0 .. pair0 + n_heads of rows whose mask is set
+int launch_attention_align(const float* q, const void* kc, int kv_format, const int32_t* row_pos, const int32_t* row_slot,
+                           const int32_t* row_frame, const int32_t* row_mask, const int32_t* windows, const int32_t* heads_host,
+                           int n_heads, int pair0, int n_pairs, int n_rows, int n_q_heads, int n_kv_heads, int cache_len, int max_frames,
+                           float* out, hipStream_t stream);
 int launch_embed(const int32_t* cols, int n_rows, int n_code_rows, const void* text_emb,
                  const void* cb_emb, int dim, int codebook_size, int cb_first_offset, int mask_mode,
                  int sem_start, int sem_end, int text_rows, int cb_rows, float* x, const EmitArgs* emit,

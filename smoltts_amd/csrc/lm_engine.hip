@@ -34,7 +34,8 @@ struct SmolttsEngine {
 };
 
 constexpr int STAGE_RING = 8;
-constexpr int GRAPH_FORMS = 32;  // the values of SmolttsSession.form (pick_form)
+constexpr int GRAPH_FORMS = 64;  // the values of SmolttsSession.form (pick_form)
+constexpr int FORM_ALIGN = 32;   // bit 5: some slot's alignment window is on
 
 struct SmolttsSession {
   SmolttsEngine* e;
@@ -105,6 +106,14 @@ struct SmolttsSession {
   // and the host reads the slots it asked about.
   bool* h_score_on;
   float* logprob;                     // [B][max_frames]: the log-probability of each emitted slow id, written by the scored forms
+  // ... and per-slot alignment windows (smoltts_session_set_slot_align) for the chosen (layer, head) pairs
+  // (smoltts_session_set_align_heads).  Table, upload area and rows live in the caller's buffer, not in the slab.
+  int n_align;                        // chosen pairs, sorted by layer; 0 = off
+  int align_layer[SMOLTTS_MAX_ALIGN_HEADS], align_head[SMOLTTS_MAX_ALIGN_HEADS];
+  int* align_win;                     // [B][2] (t0, t1) read by attn_align_kernel; t1 <= t0 = off
+  int* align_up;                      // upload area: [B][2] entries, [B] slots
+  float* align_out;                   // [B][max_frames][n_align][2] (m, s1); m = -1: not measured
+  bool* h_align_on;                   // host mirror: which slots' windows are on (bit 5 of the graph form)
   int flight_limit;            // SMOLTTS_MAX_FRAMES_IN_FLIGHT as read at creation (0 = unbounded)
   int multi_frames;            // frames per multi-frame graph (1 = single-frame graphs only): SMOLTTS_FRAMES_PER_GRAPH, else
                                // smoltts_session_set_frames_per_graph, else min(n_frames, 4) of the largest decode call so far
@@ -677,6 +686,19 @@ int run_slow_layers(SmolttsSession* s, float* x, float* q, int M, const int* row
                      (const float*)(e->arena + e->w.rope), s->kc + l * l_stride, s->vc + l * l_stride, s->max_seq, s->x3n, next, st,
                      /*first_pos=*/false, s->kv_format, -1, false, /*w_stream=*/((s->stream_w & SMOLTTS_STREAM_W_SLOW) && M <= 128)
                          ? ((s->stream_w & SMOLTTS_STREAM_W_SLOW_ONLY_W13) ? SMOLTTS_STREAM_W_DEPTH_W13 : ((s->stream_w & SMOLTTS_STREAM_W_SLOW_NOT_W13) ? (SMOLTTS_STREAM_W_DEPTH_W2 | SMOLTTS_STREAM_W_DEPTH_QKVO) : 1)) : 0));
+    if (publish_hidden && (s->form & FORM_ALIGN)) {
+      // decode frames of a form with bit 5: where this layer's chosen heads look, from q (untouched until the next layer's wqkv
+      // launch) and the layer's K rows 0 .. pos -- one more link of the frame's serial chain; row r is slot r (row_slot = iota)
+      int p0 = 0, np = 0;
+      for (int i = 0; i < s->n_align; ++i) {
+        if (s->align_layer[i] < l) p0 = i + 1;
+        if (s->align_layer[i] == l) ++np;
+      }
+      if (np > 0)
+        ST_TRY(launch_attention_align(q, s->kc + l * l_stride, s->kv_format, row_pos, row_slot, s->frames, s->mask, s->align_win,
+                                      s->align_head + p0, np, p0, s->n_align, M, c.n_head, c.n_kv_head, s->max_seq, s->max_frames,
+                                      s->align_out, st));
+    }
   }
   return SMOLTTS_OK;
 }
@@ -767,18 +789,20 @@ int arm_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos
 // slot's filter entry is on (the sampled picks are then the FILTERS instantiations; without it they are the parent's kernels), bit 3 =
 // some slot's length entry is on (the slow pick is then the LENGTH instantiation over the row of logits; it acts on greedy rows too, so
 // it outlives the rule that clears the filter bit), bit 4 = some slot scores its slow token (the slow pick is then the SCORE
-// instantiation over the row of logits; greedy rows are scored too, so it is not cleared either).  Outside slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
+// instantiation over the row of logits; greedy rows are scored too, so it is not cleared either), bit 5 = some slot's alignment
+// window is on (every decode frame then queues attn_align_kernel behind the blocks of the chosen layers; no pick changes).  Outside slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
 // point that launches or captures picks, after the last change of the table.
-void pick_form(SmolttsSession* s) {
+int form_of(const SmolttsSession* s) {
   int f = 0, len = 0;
   if (s->slot_mode)
     for (int b = 0; b < s->B; ++b) {
       f |= (s->h_slot[b].temp > 0.f ? 1 : 0) | (s->h_slot[b].fast_temp > 0.f ? 2 : 0) | (s->h_filt_on[b] ? 4 : 0);
-      len |= (s->h_len_on[b] ? 8 : 0) | (s->h_score_on[b] ? 16 : 0);
+      len |= (s->h_len_on[b] ? 8 : 0) | (s->h_score_on[b] ? 16 : 0) | (s->n_align > 0 && s->h_align_on[b] ? FORM_ALIGN : 0);
     }
   if ((f & 3) == 0) f = 0;  // nothing samples: the filters have nothing to act on
-  s->form = f | len;
+  return f | len;
 }
+void pick_form(SmolttsSession* s) { s->form = form_of(s); }
 
 // Record `body` (a fixed launch sequence on the given stream) into an executable graph.
 template <typename F>
@@ -1145,6 +1169,7 @@ void smoltts_session_destroy(SmolttsSession* s) {
   delete[] s->h_filt_on;
   delete[] s->h_len_on;
   delete[] s->h_score_on;
+  delete[] s->h_align_on;
   delete s;
 }
 
@@ -1325,7 +1350,15 @@ size_t slot_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(
 size_t filt_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotFilters) + sizeof(int)); }
 size_t len_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotLength) + sizeof(int)); }
 // (the length part is padded to 8 bytes: every area of the ring starts with sampling entries, which hold a uint64_t)
-size_t ring_area_bytes(const SmolttsSession* s) { return slot_area_bytes(s) + filt_area_bytes(s) + ((len_area_bytes(s) + 7) & ~(size_t)7); }
+size_t len_part_bytes(const SmolttsSession* s) { return (len_area_bytes(s) + 7) & ~(size_t)7; }
+// (the fourth part: alignment windows, B (t0, t1) pairs + B slot numbers)
+size_t align_area_bytes(const SmolttsSession* s) { return (size_t)s->B * 3 * sizeof(int); }
+size_t ring_area_bytes(const SmolttsSession* s) {
+  return slot_area_bytes(s) + filt_area_bytes(s) + len_part_bytes(s) + ((align_area_bytes(s) + 7) & ~(size_t)7);
+}
+// the caller's alignment buffer: [B][2] window table | upload area | rows, each part 16-byte aligned
+size_t align_table_bytes(const SmolttsSession* s) { return ((size_t)s->B * 2 * sizeof(int) + 15) & ~(size_t)15; }
+size_t align_header_bytes(const SmolttsSession* s) { return align_table_bytes(s) + ((align_area_bytes(s) + 15) & ~(size_t)15); }
 
 // Enter slot mode (first per-slot call of either kind): host mirror, pinned ring, events; every slot greedy with seed 0 and
 // its filters off
@@ -1344,6 +1377,9 @@ int enter_slot_mode(SmolttsSession* s, hipStream_t st) {
   delete[] s->h_score_on;
   s->h_score_on = new (std::nothrow) bool[B]();
   ST_REQUIRE(s->h_score_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
+  delete[] s->h_align_on;
+  s->h_align_on = new (std::nothrow) bool[B]();
+  ST_REQUIRE(s->h_align_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
   if (hipHostMalloc((void**)&s->h_slot_stage, ring_area_bytes(s) * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
     s->h_slot_stage = nullptr;
     delete[] s->h_slot;
@@ -1501,6 +1537,114 @@ int smoltts_session_set_slot_length(SmolttsSession* s, const int32_t* slots_host
   s->slot_ev_live[k] = true;
   hipLaunchKernelGGL(slot_scatter_kernel<SmolttsSlotLength>, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->len_tab);
   ST_CHECK_HIP(hipGetLastError());
+  return SMOLTTS_OK;
+}
+
+size_t smoltts_session_align_bytes(SmolttsSession* s, int32_t n) {
+  if (!s || n <= 0 || n > SMOLTTS_MAX_ALIGN_HEADS) return 0;
+  return align_header_bytes(s) + (size_t)s->B * s->max_frames * n * 2 * sizeof(float);
+}
+
+// The chosen (layer, head) pairs and the caller's buffer for the window table and the rows.  The launches of a form with bit 5 are
+// built from both, so the captured graphs of those forms are dropped; every window starts off.
+int smoltts_session_set_align_heads(SmolttsSession* s, const int32_t* layers_host, const int32_t* heads_host, int32_t n, void* out_dev,
+                                    size_t out_bytes) {
+  ST_REQUIRE(s, SMOLTTS_E_INVALID, "session_set_align_heads: null session");
+  ST_REQUIRE(n >= 0 && n <= SMOLTTS_MAX_ALIGN_HEADS, SMOLTTS_E_CAPACITY, "session_set_align_heads: %d pairs (at most %d)", n,
+             SMOLTTS_MAX_ALIGN_HEADS);
+  ST_REQUIRE(n == 0 || (layers_host && heads_host && out_dev), SMOLTTS_E_INVALID, "session_set_align_heads: null argument");
+  const SmolttsLMConfig& c = s->e->cfg;
+  for (int i = 0; i < n; ++i) {
+    ST_REQUIRE(layers_host[i] >= 0 && layers_host[i] < c.n_layer && heads_host[i] >= 0 && heads_host[i] < c.n_head, SMOLTTS_E_INVALID,
+               "session_set_align_heads: pair %d = (layer %d, head %d) outside the model (%d layers, %d heads)", i, layers_host[i],
+               heads_host[i], c.n_layer, c.n_head);
+    ST_REQUIRE(i == 0 || layers_host[i - 1] <= layers_host[i], SMOLTTS_E_INVALID, "session_set_align_heads: pairs must be sorted by layer");
+  }
+  if (n > 0) {
+    ST_REQUIRE(((uintptr_t)out_dev & 15) == 0, SMOLTTS_E_INVALID, "session_set_align_heads: the buffer must be 16-byte aligned");
+    const size_t need = smoltts_session_align_bytes(s, n);
+    ST_REQUIRE(out_bytes >= need, SMOLTTS_E_CAPACITY, "session_set_align_heads: buffer has %zu bytes, %zu needed", out_bytes, need);
+  }
+  // frames in flight, on any stream, may be replaying a graph of these forms or writing the buffer this call replaces
+  ST_CHECK_HIP(hipDeviceSynchronize());
+  for (int f = 0; f < GRAPH_FORMS; ++f) {
+    if (!(f & FORM_ALIGN)) continue;
+    if (s->graph_ready[f]) { (void)hipGraphExecDestroy(s->graph_exec[f]); s->graph_ready[f] = false; }
+    if (s->tail_ready[f]) { (void)hipGraphExecDestroy(s->tail_exec[f]); s->tail_ready[f] = false; }
+    if (s->multi_ready[f]) { (void)hipGraphExecDestroy(s->multi_exec[f]); s->multi_ready[f] = false; }
+  }
+  s->n_align = 0; s->align_win = nullptr; s->align_up = nullptr; s->align_out = nullptr;
+  if (s->h_align_on) memset(s->h_align_on, 0, s->B * sizeof(bool));
+  if (n == 0) return SMOLTTS_OK;
+  ST_CHECK_HIP(hipMemsetAsync(out_dev, 0, align_table_bytes(s), nullptr));
+  ST_CHECK_HIP(hipStreamSynchronize(nullptr));
+  for (int i = 0; i < n; ++i) { s->align_layer[i] = layers_host[i]; s->align_head[i] = heads_host[i]; }
+  s->align_win = reinterpret_cast<int*>(out_dev);
+  s->align_up = reinterpret_cast<int*>((char*)out_dev + align_table_bytes(s));
+  s->align_out = reinterpret_cast<float*>((char*)out_dev + align_header_bytes(s));
+  s->n_align = n;
+  return SMOLTTS_OK;
+}
+
+namespace {
+// out[slots[i]][*][*] = (-1, 0) for the n listed slots: "not measured"
+__global__ __launch_bounds__(256) void align_fill_kernel(const int* slots, long per_slot, float* out) {
+  float2* o = reinterpret_cast<float2*>(out) + (long)slots[blockIdx.y] * per_slot;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per_slot; i += (long)gridDim.x * 256) o[i] = make_float2(-1.f, 0.f);
+}
+}  // namespace
+
+// The alignment windows of slot mode, uploaded like the other tables (the fourth part of the next ring area, one copy + one scatter
+// launch on `stream`), and behind them the fill of the listed slots' rows.  Whether any window is on is bit 5 of the graph form.
+int smoltts_session_set_slot_align(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* t0_host,
+                                   const int32_t* t1_host, void* stream) {
+  ST_REQUIRE(s && (n == 0 || (slots_host && t0_host && t1_host)), SMOLTTS_E_INVALID, "session_set_slot_align: null argument");
+  ST_REQUIRE(s->n_align > 0, SMOLTTS_E_STATE, "session_set_slot_align: call smoltts_session_set_align_heads first");
+  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_align: %d entries, session holds %d slots", n, s->B);
+  for (int i = 0; i < n; ++i) {
+    ST_TRY(check_slot("session_set_slot_align", slots_host[i], s->B));
+    for (int j = 0; j < i; ++j)
+      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_align: slot %d listed twice", slots_host[i]);
+    ST_REQUIRE(t0_host[i] >= 0 && t0_host[i] <= s->max_seq && t1_host[i] >= 0 && t1_host[i] <= s->max_seq, SMOLTTS_E_INVALID,
+               "session_set_slot_align: slot %d: window [%d, %d) outside 0 .. %d", slots_host[i], t0_host[i], t1_host[i], s->max_seq);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t B = s->B;
+  ST_TRY(enter_slot_mode(s, st));
+  if (n == 0) return SMOLTTS_OK;
+  const int k = s->slot_next;
+  s->slot_next = (k + 1) % STAGE_RING;
+  if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
+  int* h = reinterpret_cast<int*>(s->h_slot_stage + (size_t)k * ring_area_bytes(s) + slot_area_bytes(s) + filt_area_bytes(s) + len_part_bytes(s));
+  for (int i = 0; i < n; ++i) {
+    h[2 * i] = t0_host[i]; h[2 * i + 1] = t1_host[i];
+    h[2 * B + i] = slots_host[i];
+    s->h_align_on[slots_host[i]] = t1_host[i] > t0_host[i];
+  }
+  ST_CHECK_HIP(hipMemcpyAsync(s->align_up, h, align_area_bytes(s), hipMemcpyHostToDevice, st));
+  ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
+  s->slot_ev_live[k] = true;
+  hipLaunchKernelGGL(slot_scatter_kernel<int2>, dim3((n + 63) / 64), dim3(64), 0, st, n, reinterpret_cast<const int2*>(s->align_up),
+                     s->align_up + 2 * B, reinterpret_cast<int2*>(s->align_win));
+  ST_CHECK_HIP(hipGetLastError());
+  const long per_slot = (long)s->max_frames * s->n_align;
+  const unsigned gx = (unsigned)((per_slot + 255) / 256 < 64 ? (per_slot + 255) / 256 : 64);
+  hipLaunchKernelGGL(align_fill_kernel, dim3(gx, n), dim3(256), 0, st, s->align_up + 2 * B, per_slot, s->align_out);
+  ST_CHECK_HIP(hipGetLastError());
+  return SMOLTTS_OK;
+}
+
+// Diagnostic: the form the next frame launches would be built / replayed in (what pick_form would choose now), or a negative
+// status.  Reads the host mirrors only; the session is not changed.
+int smoltts_session_graph_form(SmolttsSession* s) {
+  ST_REQUIRE(s, SMOLTTS_E_INVALID, "session_graph_form: null session");
+  return form_of(s);
+}
+
+int smoltts_session_alignment(SmolttsSession* s, float** out_dev, int32_t* n_pairs) {
+  ST_REQUIRE(s && out_dev, SMOLTTS_E_INVALID, "session_alignment: null argument");
+  *out_dev = s->n_align > 0 ? s->align_out : nullptr;
+  if (n_pairs) *n_pairs = s->n_align;
   return SMOLTTS_OK;
 }
 

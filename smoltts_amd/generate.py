@@ -108,9 +108,11 @@ class BatchGenerator:
 
     def __init__(self, engine: LMEngine, prompts: Sequence[np.ndarray], generation_settings: GenerationSettings,
                  audio_only: bool = True, frames_per_sync: int = 1, session: Optional[LMSession] = None,
-                 sampling: Optional[Sequence[RequestSampling]] = None):
+                 sampling: Optional[Sequence[RequestSampling]] = None, align: Optional[tuple] = None):
         """``sampling``: one resolved ``RequestSampling`` per prompt (``resolve_sampling``): the session runs in slot mode with
-        them; None: every utterance samples with ``generation_settings`` (session-wide)."""
+        them; None: every utterance samples with ``generation_settings`` (session-wide).
+        ``align``: ``(pairs, windows)`` -- the (layer, head) pairs and per prompt its text window ``(t0, t1)`` or None: the frames
+        measure where those heads look (``alignment()``; align.py).  Slot mode only: it needs ``sampling``."""
         self.engine = engine
         self.settings = generation_settings
         self.audio_only = audio_only
@@ -125,6 +127,16 @@ class BatchGenerator:
             if len(sampling) != self.B:
                 raise ValueError(f"sampling: {len(sampling)} entries for {self.B} prompts")
             _apply_slot_sampling(self.session, range(self.B), sampling)
+        if align is not None:
+            if sampling is None:
+                raise ValueError("align needs per-utterance sampling entries (slot mode)")
+            pairs, windows = align
+            if len(windows) != self.B:
+                raise ValueError(f"align: {len(windows)} windows for {self.B} prompts")
+            if self.session.align_pairs != sorted((int(l), int(h)) for l, h in pairs):
+                self.session.set_align_heads(pairs)
+            wins = [w if w is not None else (0, 0) for w in windows]
+            self.session.set_slot_align(list(range(self.B)), [w[0] for w in wins], [w[1] for w in wins])
         self._prompts = list(prompts)
         self._started = False
         self._emitted = np.zeros(self.B, dtype=np.int64)
@@ -180,6 +192,13 @@ class BatchGenerator:
         where the utterance's entry asked for them: ``RequestSampling.scored``).  Call before ``close``."""
         lp = self.session.fetch_logprobs()
         return [lp[b, :int(self._emitted[b])].copy() for b in range(self.B)]
+
+    def alignment(self) -> List[np.ndarray]:
+        """Per utterance, the rows [frames emitted so far, pairs, 2] = (m, s1) of its frames (m = -1: not measured; frame 0 comes
+        out of the prefill and is never measured here).  Needs ``align``.  Call before ``close``."""
+        torch.cuda.current_stream().synchronize()
+        rows = self.session.alignment.cpu().numpy()
+        return [rows[b, :int(self._emitted[b])].copy() for b in range(self.B)]
 
     def __next__(self) -> List[Optional[VQToken]]:
         if not self._pending:

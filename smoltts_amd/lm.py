@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import packing
-from .abi import (KV_FORMATS, OPT_COMMIT_PICKS, OPT_FP8_PREFILL, OPT_FUSE_DEPTH_ATTN, OPT_FUSE_PICK, OPT_QKV_TABLE, OPT_SPLIT_ATTN,
+from .abi import (KV_FORMATS, MAX_ALIGN_HEADS, OPT_COMMIT_PICKS, OPT_FP8_PREFILL, OPT_FUSE_DEPTH_ATTN, OPT_FUSE_PICK, OPT_QKV_TABLE, OPT_SPLIT_ATTN,
                   OPT_STREAM_W, BlockWeights, LMConfig, LMWeights, PrefixHeader, SmolttsError, check, load_library)
 from .config import NumericsMode, RQTransformerModelArgs, TokenConfig
 from .device import ClosesOnDel, _alloc_slab, _require_gpu, current_stream_ptr, dptr, upload, upload_stream
@@ -114,6 +114,8 @@ class LMSession(ClosesOnDel):
         self.filtered_slots = set()  # slots whose filter entry on the device is on (set_slot_filters)
         self.length_slots = set()  # slots whose length entry on the device is on (set_slot_length)
         self.scored_slots = set()  # slots whose slow token is scored (set_slot_score)
+        self.align_slots = set()  # slots whose alignment window is on (set_slot_align)
+        self.align_pairs, self.alignment, self._align_buf = [], None, None  # set_align_heads
         self.max_seq = max_seq or engine.cfg.max_seq_len
         self.max_rows = max(max_rows, max_batch)
         self.max_frames = max_frames
@@ -391,6 +393,56 @@ class LMSession(ClosesOnDel):
         """Host copy of ``logprobs`` ([max_batch, max_frames] float32); an entry means something for a frame its slot emitted
         while some slot scored.  Waits for the current stream."""
         return self.logprobs.cpu().numpy()
+
+    # ---- where chosen heads of the slow attention look (include/smoltts_hip.h at smoltts_session_set_align_heads)
+    def set_align_heads(self, pairs: Sequence) -> None:
+        """Choose the (layer, head) pairs whose text mass and first moment the decode frames measure (at most ``MAX_ALIGN_HEADS``;
+        sorted by layer here; empty: off).  The rows live in a buffer of their own, not in the session slab.  Waits for the device."""
+        pairs = sorted((int(l), int(h)) for l, h in pairs)
+        n = len(pairs)
+        if n > MAX_ALIGN_HEADS:
+            raise ValueError(f"at most {MAX_ALIGN_HEADS} alignment heads, got {n}")
+        torch.cuda.current_stream().synchronize()  # (frames in flight may still write the buffer this call replaces)
+        need = self.lib.smoltts_session_align_bytes(self.handle, n) if n else 0
+        buf = _alloc_slab(need, self.engine.device, settle=True) if n else None  # (the C call zeroes its table on the null stream)
+        check(self.lib.smoltts_session_set_align_heads(
+            self.handle, (C.c_int32 * max(n, 1))(*[p[0] for p in pairs]), (C.c_int32 * max(n, 1))(*[p[1] for p in pairs]), n,
+            dptr(buf), need), "smoltts_session_set_align_heads")
+        self.align_pairs, self._align_buf = pairs, buf
+        self.align_slots = set()
+        self.alignment = None
+        if n:
+            p, k = C.c_void_p(), C.c_int32()
+            check(self.lib.smoltts_session_alignment(self.handle, C.byref(p), C.byref(k)), "smoltts_session_alignment")
+            o = p.value - buf.data_ptr()
+            # [slot][frame][pair] = (m, s1); m = -1: not measured
+            self.alignment = buf[o: o + self.B * self.max_frames * n * 8].view(torch.float32).view(self.B, self.max_frames, n, 2)
+
+    def set_slot_align(self, slots: Sequence[int], t0: Sequence[int], t1: Sequence[int]) -> None:
+        """The text window ``[t0[i], t1[i])`` (prompt positions) of slot ``slots[i]``; ``t1 <= t0`` switches its measurement off.
+        The slot's rows are reset to "not measured".  Queued on the current stream like ``set_slot_sampling``; a new tenant
+        without the option needs an off entry, or it inherits its predecessor's window."""
+        n = len(slots)
+        if not (len(t0) == len(t1) == n):
+            raise ValueError("slot align: one window per slot")
+        check(self.lib.smoltts_session_set_slot_align(
+            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_int32 * max(n, 1))(*[int(x) for x in t0]),
+            (C.c_int32 * max(n, 1))(*[int(x) for x in t1]), current_stream_ptr()), "smoltts_session_set_slot_align")
+        for b, a, z in zip(slots, t0, t1):
+            (self.align_slots.add if z > a else self.align_slots.discard)(int(b))
+
+    def graph_form(self) -> int:
+        """The graph form of the next frame launches (``smoltts_session_graph_form``; bit 5: some slot's alignment window is on)."""
+        f = self.lib.smoltts_session_graph_form(self.handle)
+        if f < 0:
+            check(f, "smoltts_session_graph_form")
+        return int(f)
+
+    def fetch_alignment(self, slot: int, n_frames: int) -> np.ndarray:
+        """Host copy of ``alignment[slot, :n_frames]`` ([n_frames, pairs, 2] float32).  Waits for the current stream."""
+        if self.alignment is None:
+            raise SmolttsError("no alignment heads are set (set_align_heads)")
+        return self.alignment[int(slot), :int(n_frames)].cpu().numpy()
 
     def measure_duplicate(self, code: int = -1, n_filter: int = 0) -> None:
         """Measurement aid (this session only): issue every launch of one kernel class twice; -1 switches it off."""

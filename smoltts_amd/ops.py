@@ -90,6 +90,24 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, row
     return out
 
 
+def attention_align(q: torch.Tensor, k_cache: torch.Tensor, row_pos: torch.Tensor, row_slot: torch.Tensor, row_frame: torch.Tensor,
+                    row_mask: torch.Tensor, windows: torch.Tensor, heads, n_q_heads: int, out: torch.Tensor) -> torch.Tensor:
+    """Text mass and first moment of the query heads ``heads`` (``smoltts_k_attention_align``): q [rows, Hq*64]; k_cache
+    [slots, KV, cache_len, 64] fp32 or bf16; row_pos / row_slot / row_frame / row_mask int32 [rows]; windows int32 [slots, 2];
+    ``out`` float32 [slots, max_frames, len(heads), 2] is written in place (rows that write nothing keep what it held)."""
+    heads = [int(h) for h in heads]
+    slots, n_kv, cache_len = k_cache.shape[0], k_cache.shape[1], k_cache.shape[2]
+    assert k_cache.dtype in (torch.float32, torch.bfloat16) and k_cache.is_contiguous() and q.is_contiguous()
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] == slots and tuple(out.shape[2:]) == (len(heads), 2)
+    assert windows.dtype == torch.int32 and tuple(windows.shape) == (slots, 2) and windows.is_contiguous()
+    for t in (row_pos, row_slot, row_frame, row_mask):
+        assert t.dtype == torch.int32 and t.numel() == q.shape[0]
+    _k("smoltts_k_attention_align", dptr(q), dptr(k_cache), 1 if k_cache.dtype == torch.bfloat16 else 0, dptr(row_pos), dptr(row_slot),
+       dptr(row_frame), dptr(row_mask), dptr(windows), (C.c_int32 * max(len(heads), 1))(*heads), len(heads), q.shape[0], n_q_heads, n_kv,
+       cache_len, out.shape[1], dptr(out))
+    return out
+
+
 def kv3_cache(slots: int, n_heads: int, cache_len: int, device="cuda") -> torch.Tensor:
     """A zero-filled bf16x3 piece cache (include/smoltts_hip.h SMOLTTS_KV3_BYTES): uint8 [slots, heads, ceil32(cache_len) * 384]."""
     return torch.zeros(slots, n_heads, (cache_len + 31) // 32 * 32 * 384, dtype=torch.uint8, device=device)

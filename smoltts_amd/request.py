@@ -28,6 +28,7 @@ class SpeechOptions:
     silence_threshold_db: Optional[float] = None  # what counts as silence, in dBFS; None: the seam's 2^-8
     pause_blocks: int = 0             # max_pause_s in blocks (0: no cap)
     silence_thr: float = float(threshold(None))   # silence_threshold_db as a float32 amplitude
+    timestamps: bool = False          # character timestamps from the slow attention (align.py); blocking requests only
 
     @property
     def trims(self) -> bool:
@@ -44,12 +45,16 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
                   container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
                   loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
                   trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-                  silence_threshold_db: Optional[float] = None) -> SpeechOptions:
+                  silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
+                  pieces: bool = False) -> SpeechOptions:
     """A request's options checked and normalised; ``ValueError`` for anything a front end refuses.  ``output_format`` and
     ``container`` apply to streaming requests only, as does ``loudness_start_gain_db``, which needs a ``loudness``.  ``watermark``: true, false, or None for the
     front end's own policy (the key and the strength are the front end's: one key per stage).  ``trim_silence`` (true, false or
     None: false), ``max_pause_s`` (0.1 to 2.0 seconds, None: no cap) and ``silence_threshold_db`` (-72 to -6 dBFS, which needs
-    one of the other two) are the trim stage's (trim.py)."""
+    one of the other two) are the trim stage's (trim.py).  ``timestamps`` (true, false or None: false): character timestamps
+    (align.py), for blocking requests of one utterance whose frames keep their place in the output: refused with ``segment``,
+    with ``trim_silence`` / ``max_pause_s`` (the seam and the trim stage cut samples where the audio says so), with a stream, and
+    with text fed in pieces (``pieces``: the front end's text is an iterator)."""
     speed_q = parse_speed(speed)
     if output_format is not None:
         if not stream:
@@ -75,8 +80,19 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
     blocks = pause_blocks(max_pause_s)
     if silence_threshold_db is not None and not (trim_silence or blocks):
         raise ValueError("silence_threshold_db applies with trim_silence or max_pause_s")
+    if timestamps is not None and not isinstance(timestamps, bool):
+        raise ValueError("timestamps must be true or false")
+    if timestamps:
+        if pieces:
+            raise ValueError("timestamps cannot be combined with text fed in pieces: the seam cuts samples where the audio says so")
+        if opts is not None:
+            raise ValueError("timestamps cannot be combined with segment: the seam cuts samples where the audio says so")
+        if trim_silence or blocks:
+            raise ValueError("timestamps cannot be combined with trim_silence or max_pause_s: the trim stage cuts samples where the audio says so")
+        if stream:
+            raise ValueError("timestamps apply to blocking requests (a stream needs a causal fit)")
     return SpeechOptions(output_format, None if speed_q is None else float(speed), speed_q, container, opts, plan, target,
                          check_start_gain(loudness_start_gain_db), watermark, bool(trim_silence),
                          None if max_pause_s is None else float(max_pause_s),
                          None if silence_threshold_db is None else float(silence_threshold_db), blocks,
-                         float(threshold(silence_threshold_db)))
+                         float(threshold(silence_threshold_db)), bool(timestamps))

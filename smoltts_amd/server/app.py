@@ -83,7 +83,8 @@ class TTSCore:
             kw["silence_threshold_db"] = thr
         return kw
 
-    def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False, voice=None) -> Tuple[dict, int]:
+    def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False, voice=None,
+                    timestamps: bool = False) -> Tuple[dict, int]:
         """(kwargs, segments): ``{"speed": speed}`` for a speed other than 1, ``{"segment": options}`` in ``long_text="segment"``
         mode and ``{"loudness": target}`` for a ``LoudnessFields`` body (or the server's ``loudness`` setting) that names one,
         nothing otherwise, so that the model sees the calls it saw before; a bad speed or loudness, a text over
@@ -96,11 +97,15 @@ class TTSCore:
             limit = int(self._setting("max_input_chars", 5000))
             if len(text) > limit:
                 raise ValueError(f"input has {len(text)} characters; max_input_chars is {limit}")
+        if self.long_text == "segment" and not timestamps:  # (a request with timestamps is one utterance: chained segments have none)
             seg = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
         target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
         trim = self._trim_kw(loudness)
-        p = parse_request(text, stream=stream, speed=speed, segment=seg, loudness=target, loudness_start_gain_db=start, **trim)
+        p = parse_request(text, stream=stream, speed=speed, segment=seg, loudness=target, loudness_start_gain_db=start,
+                          timestamps=timestamps or None, **trim)
         kw = {} if p.speed is None else {"speed": p.speed}
+        if p.timestamps:
+            kw["timestamps"] = True
         kw.update(trim)
         if p.loudness is not None:
             kw["loudness"] = p.loudness
@@ -210,18 +215,35 @@ class TTSCore:
         if n > cap:
             raise ValueError(f"best_of={n} exceeds this server's max_best_of={cap}")
 
+    @property
+    def alignment_heads(self):
+        """The (layer, head) pairs character timestamps are read from: the ``alignment_heads`` setting, else what the scheduler
+        (pool) or the model was built with; empty: the with-timestamps route answers 501."""
+        from ..align import check_heads
+
+        for src in (self._setting("alignment_heads", None), getattr(self.scheduler, "alignment_heads", None),
+                    getattr(self.model, "alignment_heads", None)):
+            if src:
+                return check_heads(src)
+        return []
+
     def generate_audio(self, input_text: str, voice: Union[str, int], response_format: str = "wav_24000", sampling=None,
-                       speed: Optional[float] = None, loudness=None, info: Optional[dict] = None):
+                       speed: Optional[float] = None, loudness=None, info: Optional[dict] = None, timestamps: bool = False):
         """-> (bytes, media type, the seed the request sampled with or None).  ``speed``: passed on only when it is not 1.
+        ``timestamps``: the request also measures its character times (align.py): ``info["alignment"]`` is the ``align.Alignment``;
+        it is spoken as one utterance whatever ``long_text`` says, and refused (``ValueError`` -> 400) with the trim options and
+        ``best_of``.
         ``info["finish_reason"]``: ``"stop"`` or ``"length"`` (``config.finish_reason``).
         ``loudness``: the body's ``LoudnessFields``; ``info["loudness_gain_db"]`` is then the gain the utterance was given, and
         ``info["watermark"]`` true when the audio is marked."""
         used = None
         try:
             self._check_best_of(sampling)
-            sp, n_seg = self._request_kw(input_text, speed, loudness, voice=voice)
+            sp, n_seg = self._request_kw(input_text, speed, loudness, voice=voice, timestamps=timestamps)
             if info is not None:
                 info["watermark"] = bool(sp.get("watermark"))
+            if timestamps and sampling is not None and getattr(sampling, "takes", 1) > 1:
+                raise ValueError("timestamps cannot be combined with best_of")
             if self.scheduler is not None:
                 req = self.scheduler.submit(input_text, str(voice), stream=False, **({"sampling": sampling} if sampling is not None else {}), **sp)
                 used = getattr(req, "sampling", None)
@@ -231,6 +253,7 @@ class TTSCore:
                 reason = getattr(req, "finish_reason", None)
                 mean, n_takes = getattr(req, "mean_logprob", None), getattr(req, "best_of", 1)
                 used = getattr(req, "sampling", None)  # (a best_of request's entry is the chosen take's by now)
+                alignment = getattr(req, "alignment", None)
             else:
                 used = self._model_sampling(sampling)
                 kw = {"sampling": used} if used is not None else {}
@@ -242,6 +265,12 @@ class TTSCore:
                 n_takes = len(takes) if takes else 1
                 if takes:
                     used = self.model.last_sampling[0]  # the chosen take's entry
+                alignment = getattr(self.model, "last_alignment", None)
+            if timestamps:
+                if alignment is None:
+                    raise RuntimeError("the engine returned no alignment for a request with timestamps")
+                if info is not None:
+                    info["alignment"] = alignment
             if info is not None and mean is not None:
                 info["mean_logprob"], info["best_of"] = mean, n_takes
             if info is not None and reason is not None:
@@ -566,6 +595,29 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
         **_trim_headers(info), **_finish_headers(info), **_score_headers(info)})
 
 
+@eleven_router.post("/text-to-speech/{voice_id}/with-timestamps")
+def text_to_speech_with_timestamps(voice_id: str, item: CreateSpeechRequest, http_request: Request,
+                                   output_format: Optional[str] = Query(None, description="pcm_<rate> | wav_<rate>")):
+    """ElevenLabs' JSON: ``audio_base64`` (the blocking route's audio, in its formats), ``alignment`` and ``normalized_alignment``
+    (the text is spoken as written, so the two are the same) with ``characters``, ``character_start_times_seconds`` and
+    ``character_end_times_seconds``, read from the slow attention (align.py).  501 unless the server has ``alignment_heads``; 400
+    with the trim options, ``best_of`` or a text the engine refuses."""
+    import base64
+
+    core = http_request.app.state.tts_core
+    if not core.alignment_heads:
+        raise HTTPException(status_code=501, detail="this server has no alignment_heads: rank the checkpoint's heads with "
+                                                    "`python -m smoltts_amd.align rank --checkpoint DIR --texts FILE` and set them")
+    fmt = output_format or "wav_24000"
+    info: dict = {}
+    content, _media, seed = core.generate_audio(item.text, voice_id, fmt, sampling=item.request_sampling(), speed=item.speed,
+                                                loudness=item, info=info, timestamps=True)
+    al = info["alignment"].to_json()
+    return JSONResponse({"audio_base64": base64.b64encode(content).decode("ascii"), "alignment": al, "normalized_alignment": al},
+                        headers={"X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed),
+                                 **_gain_headers(info), **_mark_headers(info), **_finish_headers(info)})
+
+
 @eleven_router.post("/text-to-speech/{voice_id}/stream")
 def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
                      output_format: StreamFormat = "pcm_24000"):
@@ -874,7 +926,8 @@ def main():
         st = ServerSettings(**settings)
         sched = GpuPool(functools.partial(scheduler_from_settings, settings), devices=list(range(args.gpus)),
                         generation_settings=st.generation.to_settings(),
-                        watermark=st.watermark.to_watermark() if st.watermark is not None else None)
+                        watermark=st.watermark.to_watermark() if st.watermark is not None else None,
+                        alignment_heads=st.alignment_heads)
         model = None
     else:
         sched = scheduler_from_settings(settings)

@@ -41,6 +41,7 @@ class _PoolRequest:
     mean_logprob: Optional[float] = None
     takes: object = None
     best_of: int = 1
+    alignment: object = None  # align.Alignment of a request that asked for timestamps, known at its end
 
 
 @dataclass
@@ -109,7 +110,8 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
             if getattr(req, "logprobs", None) is not None:
                 scores = {"logprobs": np.asarray(req.logprobs), "mean_logprob": req.mean_logprob, "takes": req.takes, "best_of": req.best_of,
                           "seed": req.sampling.seed}
-            res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0), getattr(req, "finish_reason", None), scores)))
+            res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0), getattr(req, "finish_reason", None), scores,
+                                    getattr(req, "alignment", None))))
         except Exception as e:
             res_q.put((rid, "error", (type(e).__name__, str(e))))
         finally:
@@ -183,7 +185,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
 
 class GpuPool:
     def __init__(self, factory: Callable[[], object], devices: Sequence[int], start_method: str = "spawn", ready_timeout: float = 600.0,
-                 respawn: bool = True, generation_settings=None, watermark=None):
+                 respawn: bool = True, generation_settings=None, watermark=None, alignment_heads=None):
         """``factory``: picklable, called once in every worker to build its scheduler.  ``devices``: GPU indices, one
         worker each (an index may repeat: two replicas on one GPU).  ``start_method``: "spawn" or "forkserver" — never
         "fork": a forked copy of a process that has used the GPU is not usable.  ``respawn``: a worker that dies is replaced
@@ -198,6 +200,10 @@ class GpuPool:
         if watermark is not None and not isinstance(watermark, Watermark):
             raise ValueError("watermark must be a smoltts_amd.watermark.Watermark or None")
         self.watermark = watermark
+        from ..align import check_heads
+
+        # what the workers' schedulers were built with (the factory's business): lets the front end refuse ``timestamps`` itself
+        self.alignment_heads = check_heads(alignment_heads)
         if start_method not in ("spawn", "forkserver"):
             raise ValueError("start_method must be 'spawn' or 'forkserver'")
         if not devices:
@@ -254,14 +260,19 @@ class GpuPool:
                container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
                loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
                trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-               silence_threshold_db: Optional[float] = None) -> _PoolRequest:
+               silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None) -> _PoolRequest:
         """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
         from ..request import parse_request
 
         p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db)  # refused here, before a worker sees it
+                          trim_silence, max_pause_s, silence_threshold_db, timestamps=timestamps)  # refused here, before a worker sees it
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
+        if p.timestamps:
+            if not self.alignment_heads:
+                raise ValueError("timestamps need alignment_heads: rank a checkpoint's heads with `python -m smoltts_amd.align rank`")
+            if sampling is not None and sampling.takes > 1:
+                raise ValueError("timestamps cannot be combined with best_of")
         if sampling is not None and sampling.takes > 1 and (stream or p.plan is not None):
             from ..config import MAX_BEST_OF, check_best_of
 
@@ -274,7 +285,7 @@ class GpuPool:
                                    ("container", p.container), ("segment", p.segment), ("loudness", p.loudness),
                                    ("loudness_start_gain_db", loudness_start_gain_db), ("watermark", p.watermark),
                                    ("trim_silence", p.trim_silence or None), ("max_pause_s", p.max_pause_s),
-                                   ("silence_threshold_db", p.silence_threshold_db)) if v is not None}
+                                   ("silence_threshold_db", p.silence_threshold_db), ("timestamps", p.timestamps or None)) if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
@@ -506,7 +517,7 @@ class GpuPool:
                 if not req.cancelled:
                     req.out.put(payload)
             elif kind == "end":
-                req.loudness_gain_db, req.trimmed_s, req.finish_reason, scores = payload
+                req.loudness_gain_db, req.trimmed_s, req.finish_reason, scores, req.alignment = payload
                 if scores is not None:
                     import dataclasses
 
@@ -582,11 +593,12 @@ def scheduler_from_settings(settings):
     model = SmolTTS(checkpoint_dir=str(st.get_checkpoint_dir()), mimi_checkpoint=st.mimi_checkpoint, weight_format=st.weight_format)
     return BatchScheduler(model, max_batch=st.max_batch, generation_settings=st.generation.to_settings(), codec_products=st.codec_products,
                           watermark=st.watermark.to_watermark() if st.watermark is not None else None,
-                          min_frames_per_byte=st.min_frames_per_byte, max_frames_per_byte=st.max_frames_per_byte)
+                          min_frames_per_byte=st.min_frames_per_byte, max_frames_per_byte=st.max_frames_per_byte,
+                          alignment_heads=st.alignment_heads)
 
 
 def synthetic_scheduler(model: str = "tiny", seed: int = 21, mimi_seed: int = 5, max_batch: int = 4, frames_per_tick: int = 2,
-                        max_new_tokens: int = 64, mimi_encoder: bool = False, watermark=None):
+                        max_new_tokens: int = 64, mimi_encoder: bool = False, watermark=None, alignment_heads=None):
     """Seeded random weights at the named shapes (tests, rehearsals without a checkpoint); greedy.  ``mimi_encoder``: the codec
     also carries (seeded) encoder weights, so that voices can be cloned."""
     from .. import SmolTTS
@@ -601,4 +613,5 @@ def synthetic_scheduler(model: str = "tiny", seed: int = 21, mimi_seed: int = 5,
         mst = {**mst, **synthetic_mimi_encoder_state(seed=mimi_seed)}
     tts = SmolTTS(state=synthetic_lm_state(cfg, seed=seed), config=cfg, mimi_state=mst)
     return BatchScheduler(tts, max_batch=max_batch, frames_per_tick=frames_per_tick,
-                          generation_settings=GenerationSettings.greedy(max_new_tokens=max_new_tokens), watermark=watermark)
+                          generation_settings=GenerationSettings.greedy(max_new_tokens=max_new_tokens), watermark=watermark,
+                          alignment_heads=alignment_heads)

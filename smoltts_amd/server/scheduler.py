@@ -83,6 +83,16 @@ class _Request:
     take_reqs: list = field(default_factory=list)  # parent: the takes' requests
     take_of: object = None
     best_of: int = 1
+    # character timestamps: a blocking request of one utterance whose frames measure where the scheduler's
+    # alignment heads look over its own text
+    timestamps: bool = False
+    align_window: object = None          # (t0, t1): the text's positions in the slot, known at admission
+    align_ids: object = None             # ... and the text's token ids
+    al: list = field(default_factory=list)  # its frames' rows [frames, heads, 2], tick by tick
+    speed: Optional[float] = None        # the speed asked for (the times are divided by it)
+    out_samples: int = 0                 # samples handed out so far: the delivered duration
+    audio_frames: int = 0                # frames whose slow id was semantic: the ones the codec decodes
+    alignment: object = None             # align.Alignment, set before the request's end marker
 
 
 @dataclass
@@ -169,6 +179,7 @@ class _Snapshot:
     event: object
     tick_no: int
     logprobs: object = None  # the score array, cloned only while some live slot scores
+    alignment: object = None  # the alignment rows, cloned only while some live slot measures
 
 
 @dataclass
@@ -206,8 +217,10 @@ class BatchScheduler:
     def __init__(self, tts, max_batch: int = 32, frames_per_tick: int = 4, generation_settings=None, max_prompt_rows: int = 4096,
                  prefill_chunk: Optional[int] = 128, side_prefill: bool = True, side_prefill_min_active: Optional[int] = None,
                  codec_products: int = 6, watermark=None, min_frames_per_byte: Optional[float] = None,
-                 max_frames_per_byte: Optional[float] = None):
-        """``watermark`` (a ``watermark.Watermark``; None: no request can be marked): the one key of this scheduler's marked
+                 max_frames_per_byte: Optional[float] = None, alignment_heads=None):
+        """``alignment_heads`` (``[(layer, head), ...]``, at most 16; None: no request can ask for timestamps): the heads of the slow
+        attention that ``submit(timestamps=True)`` reads character times from (align.py).
+        ``watermark`` (a ``watermark.Watermark``; None: no request can be marked): the one key of this scheduler's marked
         requests; a request that does not say (``submit(watermark=None)``) is marked when there is one.
         ``min_frames_per_byte`` / ``max_frames_per_byte`` (None: off): bounds on every utterance's length from its text's UTF-8
         byte count, per segment on the long-text path (``config.length_bounds``)."""
@@ -247,6 +260,12 @@ class BatchScheduler:
         self._default_sampling = RequestSampling().resolve(self.settings, draw_seed=False)
         self._slot_sampling: Dict[int, object] = {}  # the entry each slot has on the device
         self._write_sampling({b: self._default_sampling for b in range(max_batch)})
+        from ..align import check_heads
+
+        self.alignment_heads = check_heads(alignment_heads, tts.config)
+        self._slot_align: Dict[int, tuple] = {}  # the window each slot has on the device (absent: off)
+        if self.alignment_heads:
+            self.session.set_align_heads(self.alignment_heads)
         torch.cuda.current_stream().synchronize()  # (the worker's frame stream is another one)
         self.session.set_frames_per_graph(min(max(frames_per_tick, 1), 8))  # a tick is one graph launch where it fits
         self._torch = torch
@@ -299,8 +318,11 @@ class BatchScheduler:
                container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
                loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
                trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-               silence_threshold_db: Optional[float] = None) -> _Request:
-        """``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
+               silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None) -> _Request:
+        """``timestamps`` (blocking requests of one utterance; needs the scheduler's ``alignment_heads``; ``ValueError`` with
+        ``segment``, the trim options, a stream or ``best_of``): ``request.alignment`` is an ``align.Alignment`` -- per character of
+        the text its start and end in seconds of the audio delivered -- once the request has ended.  The audio is not changed.
+        ``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
         in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
         a seed gets one here.  The resolved value is ``request.sampling``; its seed replays the request.
@@ -329,10 +351,15 @@ class BatchScheduler:
         from ..request import parse_request
 
         p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db)
+                          trim_silence, max_pause_s, silence_threshold_db, timestamps=timestamps)
         self._check_trim(p)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         check_best_of(resolved, self.B, stream=stream, segmented=p.plan is not None)
+        if p.timestamps:
+            if not self.alignment_heads:
+                raise ValueError("timestamps need alignment_heads: rank a checkpoint's heads with `python -m smoltts_amd.align rank`")
+            if resolved.takes > 1:
+                raise ValueError("timestamps cannot be combined with best_of")
         if self._dead is not None:  # the worker is gone (engine failure or close): nobody would ever answer
             raise RuntimeError(f"scheduler is not running: {self._dead}")
         if self._draining:
@@ -340,7 +367,8 @@ class BatchScheduler:
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
                        output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=p.speed_q,
                        container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None,
-                       loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark), trim=p.trim_route)
+                       loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark), trim=p.trim_route,
+                       timestamps=p.timestamps, speed=p.speed)
         if resolved.takes > 1:
             # the parent carries the audio options and the response; its takes are plain blocking requests, admitted as slots
             # come free
@@ -659,6 +687,11 @@ class BatchScheduler:
                         prompt = sg.plan.prompt(sg.k, enc, prefix, sg.prev, req.max_new_tokens, self.session.max_seq)
                     else:
                         prompt = enc.build_prompt(req.text, req.voice, v.grid) if v is not None else self.tts._get_prompt(req.text, req.voice)
+                    if req.timestamps:  # the text's positions in the slot: of the whole prompt, a voice's speaker turns included
+                        from ..align import window_of
+
+                        req.align_window = window_of(prompt[0], self.tts.tokenizer)
+                        req.align_ids = np.asarray(prompt[0, req.align_window[0]:req.align_window[1]]).copy()
                     if v is not None:  # a registered voice: its speaker turns' KV rows are installed, its own turns prefilled at P
                         P = int(v.grid.shape[1])
                         req.prompt, req.pos0, req.prefix = prompt[:, P:], P, v.prefix
@@ -691,6 +724,12 @@ class BatchScheduler:
         entries = {b: self._default_sampling for b in freed}
         entries.update({r.slot: r.slot_sampling for r in new})
         self._write_sampling(entries)  # on the frame stream, ahead of the park / prefill of the new tenants
+        if self.alignment_heads:
+            # ... and the slots' text windows: a new tenant's own (its rows start as "not measured"), off for a tenant without
+            # the option and for a slot handed back, so that nobody inherits a predecessor's window
+            wins = {b: None for b in self._free if b in self._slot_align}
+            wins.update({r.slot: r.align_window for r in new})
+            self._write_align(wins)
         if not new:
             return
         if side:
@@ -821,6 +860,20 @@ class BatchScheduler:
         for b in todo:
             self._slot_sampling[b] = entries[b]
 
+    def _write_align(self, wins: Dict[int, object]) -> None:
+        """Slot b measures over ``wins[b]`` = (t0, t1) from the next frame on the current stream on; None: its window is off (only
+        windows that were on are switched off; a window that is switched on is always written: it resets the slot's rows)."""
+        todo = sorted(b for b, w in wins.items() if w is not None or b in self._slot_align)
+        if not todo:
+            return
+        w = [wins[b] if wins[b] is not None else (0, 0) for b in todo]
+        self.session.set_slot_align(todo, [x[0] for x in w], [x[1] for x in w])
+        for b in todo:
+            if wins[b] is None:
+                self._slot_align.pop(b, None)
+            else:
+                self._slot_align[b] = tuple(wins[b])
+
     def _prefill(self, new: List[_Request]) -> None:
         """In-line admission: the registered voices' prefixes are installed in one launch, then every prompt (a registered
         voice's: its own turns only) is prefilled from its pos0.  Frame 0 of the new slots comes out of the next tick's first
@@ -909,8 +962,9 @@ class BatchScheduler:
         s = self.session
         s.decode(self.tick)
         scoring = any(r.slot_sampling is not None and r.slot_sampling.scored for r in list(self._active.values()) + self._retiring)
+        measuring = any(r.timestamps for r in list(self._active.values()) + self._retiring)
         snap = _Snapshot(s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no,
-                         s.logprobs.clone() if scoring else None)
+                         s.logprobs.clone() if scoring else None, s.alignment.clone() if measuring else None)
         snap.event.record(torch.cuda.current_stream())
         self._snaps.append(snap)
         self._tick_no += 1
@@ -930,8 +984,10 @@ class BatchScheduler:
                 n_frames = snap.n_frames.to("cpu", non_blocking=True)
                 done = snap.done.to("cpu", non_blocking=True)
                 scores = snap.logprobs.to("cpu", non_blocking=True) if snap.logprobs is not None else None
+                rows = snap.alignment.to("cpu", non_blocking=True) if snap.alignment is not None else None
             self._sync_copies()
-            self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), snap.tick_no, stream_pass, None if scores is None else scores.numpy())
+            self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), snap.tick_no, stream_pass, None if scores is None else scores.numpy(),
+                        None if rows is None else rows.numpy())
 
     def _launch_stream_codec(self, snap: _Snapshot) -> Optional[_Delivery]:
         """The codec pass of the streaming requests for tick ``snap.tick_no``, on the codec stream, from the tick's snapshot of
@@ -996,7 +1052,7 @@ class BatchScheduler:
         self._copy_stream.synchronize()
         self._gpu_wait_s += time.perf_counter() - t
 
-    def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery], scores=None) -> None:
+    def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery], scores=None, align_rows=None) -> None:
         from ..config import finish_reason, merge_finish_reasons
         from ..generate import semantic_columns
 
@@ -1058,7 +1114,12 @@ class BatchScheduler:
                 if scores is None:
                     raise RuntimeError("scheduler lost the scores of a request")
                 r.lp.append(scores[slot, r.emitted:n].copy())
+            if r.timestamps and n > r.emitted:
+                if align_rows is None:
+                    raise RuntimeError("scheduler lost the alignment rows of a request")
+                r.al.append(align_rows[slot, r.emitted:n].copy())
             r.emitted = n
+            r.audio_frames += int(cols.shape[0])
             if cols.shape[0]:
                 r.pending.append(cols)
             if finished and r.seg is not None:  # a segment of a blocking segmented request: its own codec job
@@ -1225,9 +1286,9 @@ class BatchScheduler:
                         if r.speed_q:
                             self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
                             continue
-                        r.out.put(self._mark(r, r.stretch_in.pop()))
+                        self._put(r, self._mark(r, r.stretch_in.pop()))
                 elif n and not r.cancelled:
-                    r.out.put(host[b, :n].copy())
+                    self._put(r, host[b, :n].copy())
                     self._counts["frames_delivered"] += n // 1920
                 if fin:
                     self._end(r)
@@ -1330,7 +1391,7 @@ class BatchScheduler:
             for job in [j for j in ran if j.state == "ending"]:
                 r = job.req
                 if not r.cancelled:
-                    r.out.put(self._mark(r, np.concatenate(job.outs) if job.outs else np.zeros(0, np.float32)))
+                    self._put(r, self._mark(r, np.concatenate(job.outs) if job.outs else np.zeros(0, np.float32)))
                 self._end(r)
                 self._stretches.remove(job)
             self._stretch_flight = None
@@ -1438,6 +1499,21 @@ class BatchScheduler:
         except Exception as e:  # engine failure: fail every waiter loudly
             self._fail_all(e)
 
+    def _put(self, r: _Request, pcm: np.ndarray) -> None:
+        """A piece of a blocking utterance's final audio goes out."""
+        r.out_samples += int(pcm.size)
+        r.out.put(pcm)
+
+    def _aligned(self, r: _Request) -> None:
+        """``r.alignment`` of a request with timestamps that has ended well: its frames' rows fitted to its text (align.py); the
+        audio frames are the ones whose slow id is semantic, the delivered duration is what went out."""
+        from ..align import align
+
+        rows = np.concatenate(r.al) if r.al else np.zeros((0, len(self.alignment_heads), 2), np.float32)
+        F = min(rows.shape[0], r.audio_frames)
+        r.alignment = align(r.text, r.align_ids, rows[:F, :, 0], rows[:F, :, 1], self.tts.tokenizer, speed=r.speed,
+                            duration_s=r.out_samples / 24000.0)
+
     def _end(self, r: _Request, e: Optional[Exception] = None) -> None:
         """Queue the end marker of a request (exactly once)."""
         if r.part_of is not None:  # a segment's codec job: the segmented request ends, not its part
@@ -1452,6 +1528,11 @@ class BatchScheduler:
         if not r.closed:
             r.closed = True
             self._counts["failed" if e is not None else ("cancelled" if r.cancelled else "completed")] += 1
+            if r.timestamps and e is None and not r.cancelled and r.align_ids is not None:
+                try:
+                    self._aligned(r)
+                except Exception as err:  # (the request fails; the worker goes on)
+                    e = err
             r.out.put(e)
 
     def _take_ended(self, take: _Request, e: Optional[Exception]) -> None:

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import json
 from pathlib import Path
-from typing import Literal, Optional
+from typing import List, Literal, Optional, Tuple
 
 from pydantic import BaseModel, Field, model_validator
 
@@ -116,6 +116,11 @@ class ServerSettings(BaseModel):
     # (extension) the most takes a request's ``best_of`` may ask for; a body above it is answered 400.  Every take
     # holds a slot for its whole length
     max_best_of: int = Field(default=4, ge=1, le=8)
+
+    # (extension) the (layer, head) pairs of the slow attention that character timestamps are read from: at most 16
+    # [layer, head] pairs; null (default): POST /v1/text-to-speech/{voice_id}/with-timestamps answers 501.  Which heads of a
+    # checkpoint track the text is the operator's to find: python -m smoltts_amd.align rank --checkpoint DIR --texts FILE
+    alignment_heads: Optional[List[Tuple[int, int]]] = Field(default=None, max_length=16)
 
     model_config = {"protected_namespaces": ()}
 
