@@ -927,16 +927,17 @@ typedef struct SmolttsGemmArgs {
   int64_t ldr, r_bstride;
   float* out_dev;             /* row m at out + (m / rows_per_batch) * o_bstride + (m % rpb) * ldo */
   int64_t ldo, o_bstride;
-  int32_t elu_out;            /* STORE / RESID: store ELU(result) (the consumer then needs no ELU prologue) */
-  float* raw_out_dev;         /* STORE: optional second copy of the un-activated result, row stride ldo */
+  int32_t elu_out;            /* STORE / RESID: store ELU(result) (the consumer then needs no ELU prologue); N < 4 included */
+  float* raw_out_dev;         /* STORE: optional second copy of the un-activated result, row stride ldo; N < 4 included */
   int64_t raw_bstride;
   /* EPI_QKV_ROPE */
-  const float* rope_dev;      /* [pos][32][2] */
+  const float* rope_dev;      /* [pos][32][2]; q rows are rotated by the entry at row_pos even where that lies outside
+                                 [0, cache_len) (such rows write no K / V): the table must reach every row_pos given */
   const int32_t* row_pos_dev; /* [M] */
   const int32_t* row_slot_dev;/* [M] */
   float* k_cache_dev;         /* [slots][n_kv][cache_len][64] */
   float* v_cache_dev;
-  int32_t n_q_heads, n_kv_heads, cache_len;
+  int32_t n_q_heads, n_kv_heads, cache_len; /* both head counts >= 1: N = (n_q_heads + 2 n_kv_heads) * 64 >= 192 */
   const void* w3_dev;         /* optional, fp32 weights only: the same matrix as "W3" tiles; many-row calls (M >= 256, N >= 64,
                                  no prologue or the ELU one) then run on the bf16 matrix cores with split operands (fp32-grade results) */
   float* splitk_ws_dev;       /* optional, with w3_dev: workspace for split-K partial sums (long K over few tiles) ... */

@@ -66,8 +66,8 @@ __global__ __launch_bounds__(MT >= 4 ? 512 : 1024) void gemm_kernel(GemmDev p) {
   float ln_mu[MT], ln_rs[MT];
   if (PRO == SMOLTTS_PRO_LAYERNORM) {
     float* stat = smem + nwaves * MT * (256 + 16);  // [MT * 16][2]
-    // (the dispatcher sends only calls of at most 16 rows and K <= 512 here: a wave has at most 4 rows, whose values it keeps in
-    // registers between the two passes -- all its loads are in flight together)
+    // (the dispatcher sends only calls of at most 16 rows and K <= 512 here, with at least 4 waves: a wave has at most 4 rows, whose
+    // values it keeps in registers between the two passes -- all its loads are in flight together)
     constexpr int RPW = 4;
     float4 xv4[RPW][2];
     bool on[RPW];
@@ -252,8 +252,12 @@ __global__ __launch_bounds__(MT >= 4 ? 512 : 1024) void gemm_kernel(GemmDev p) {
         *reinterpret_cast<float4*>(p.raw_out + row_off(m, p.rows_per_batch, p.ldo, p.raw_bstride) + n0) = make_float4(v[0], v[1], v[2], v[3]);
       if (p.elu_out) { v[0] = elu1(v[0]); v[1] = elu1(v[1]); v[2] = elu1(v[2]); v[3] = elu1(v[3]); }
       *reinterpret_cast<float4*>(p.out + orow + n0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {  // N < 4 (the final 1-channel conv): scalar tail
-      for (int i = 0; i < 4 && n0 + i < p.N; ++i) p.out[orow + n0 + i] = v[i];
+    } else {  // N < 4 (the final 1-channel conv): scalar tail, raw_out / elu_out as in the float4 arm
+      const long wrow = row_off(m, p.rows_per_batch, p.ldo, p.raw_bstride);
+      for (int i = 0; i < 4 && n0 + i < p.N; ++i) {
+        if (p.raw_out) p.raw_out[wrow + n0 + i] = v[i];
+        p.out[orow + n0 + i] = p.elu_out ? elu1(v[i]) : v[i];
+      }
     }
   } else if (EPI == SMOLTTS_EPI_RESID) {
     const float4 rr = *reinterpret_cast<const float4*>(p.resid + rrow + n0);
@@ -423,8 +427,9 @@ static int launch_rows(const GemmDev& d, hipStream_t stream) {
   const int WM = 4 / WN;
   const dim3 grid((per + WN - 1) / WN, (d.M + 64 * WM - 1) / (64 * WM));
   ST_REQUIRE(grid.y <= 65535, SMOLTTS_E_INVALID, "gemm: M=%d too large for one launch", d.M);
+  // (QKV_ROPE has N >= 192 = 12 column tiles, launch_gemm_impl requires a q and a kv head: always two tiles per wave)
   if (NTW == 2) hipLaunchKernelGGL((gemm_rows_kernel<2, EPI>), grid, dim3(256), 0, stream, d, WN);
-  else hipLaunchKernelGGL((gemm_rows_kernel<1, EPI>), grid, dim3(256), 0, stream, d, WN);
+  else if constexpr (EPI != SMOLTTS_EPI_QKV_ROPE) hipLaunchKernelGGL((gemm_rows_kernel<1, EPI>), grid, dim3(256), 0, stream, d, WN);
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }
@@ -526,7 +531,7 @@ static int launch_gemm_impl(const SmolttsGemmArgs& a, hipStream_t stream) {
   if (E == SMOLTTS_EPI_SCALE_RESID) ST_REQUIRE(a.scale_dev, SMOLTTS_E_INVALID, "gemm: scale missing");
   if (E == SMOLTTS_EPI_QKV_ROPE)
     ST_REQUIRE(a.rope_dev && a.row_pos_dev && a.row_slot_dev && a.k_cache_dev && a.v_cache_dev && a.out_dev &&
-                   a.N == (a.n_q_heads + 2 * a.n_kv_heads) * 64 && a.cache_len > 0,
+                   a.n_q_heads > 0 && a.n_kv_heads > 0 && a.N == (a.n_q_heads + 2 * a.n_kv_heads) * 64 && a.cache_len > 0,
                SMOLTTS_E_INVALID, "gemm: QKV_ROPE epilogue arguments inconsistent");
   else
     ST_REQUIRE(a.out_dev, SMOLTTS_E_INVALID, "gemm: null output");
@@ -589,8 +594,15 @@ static int launch_gemm_impl(const SmolttsGemmArgs& a, hipStream_t stream) {
   ST_CASE(true, SMOLTTS_PRO_NONE, SMOLTTS_EPI_RESID)
   ST_CASE(true, SMOLTTS_PRO_ELU, SMOLTTS_EPI_STORE)
   ST_CASE(true, SMOLTTS_PRO_ELU, SMOLTTS_EPI_RESID)
-  ST_CASE(true, SMOLTTS_PRO_LAYERNORM, SMOLTTS_EPI_QKV_ROPE)
-  ST_CASE(true, SMOLTTS_PRO_LAYERNORM, SMOLTTS_EPI_GELU)
+  // (the in-kernel LayerNorm prologue is reached with at most 16 rows, see the re-route above: one row tile.  Its statistics pass
+  // gives a wave at most 4 of the 16 rows: at least 4 waves, also where K < 320 would ask for fewer -- with 1..3 waves the rows
+  // from 4 * nwaves on were normalised with whatever the LDS held)
+#define ST_CASE_LN(EE) \
+  if (a.w_is_fp32 && P == SMOLTTS_PRO_LAYERNORM && E == EE) \
+    return launch_one<true, 1, 3, SMOLTTS_PRO_LAYERNORM, EE>(d, nwaves < 4 ? 4 : nwaves, stream);
+  ST_CASE_LN(SMOLTTS_EPI_QKV_ROPE)
+  ST_CASE_LN(SMOLTTS_EPI_GELU)
+#undef ST_CASE_LN
 #undef ST_CASE
   set_error("gemm: unsupported combination w_is_fp32=%d prologue=%d epilogue=%d", a.w_is_fp32, P, E);
   return SMOLTTS_E_INVALID;

@@ -193,12 +193,19 @@ static int launch_b3_epi_np(const GemmDev& d, hipStream_t stream) {
   if (force == 44 || (force == 0 && blocks(128, 128) >= 512 && d.N >= 128)) {
     const dim3 grid = grid1d(128, 128);
     hipLaunchKernelGGL((gemm_b3_kernel<4, 4, EPI, NP>), grid, dim3(256), 0, stream, g);
-  } else if (force == 42 || (force == 0 && blocks(128, 64) >= 512 && d.N < 128)) {
-    const dim3 grid = grid1d(128, 64);
-    hipLaunchKernelGGL((gemm_b3_kernel<4, 2, EPI, NP>), grid, dim3(256), 0, stream, g);
   } else {
-    const dim3 grid = grid1d(64, 64);
-    hipLaunchKernelGGL((gemm_b3_kernel<2, 2, EPI, NP>), grid, dim3(256), 0, stream, g);
+    bool narrow = false;
+    if constexpr (EPI != SMOLTTS_EPI_QKV_ROPE) {  // 128 x 64 tiles serve N < 128; QKV_ROPE has N >= 192: no such instantiation
+      narrow = force == 42 || (force == 0 && blocks(128, 64) >= 512 && d.N < 128);
+      if (narrow) {
+        const dim3 grid = grid1d(128, 64);
+        hipLaunchKernelGGL((gemm_b3_kernel<4, 2, EPI, NP>), grid, dim3(256), 0, stream, g);
+      }
+    }
+    if (!narrow) {
+      const dim3 grid = grid1d(64, 64);
+      hipLaunchKernelGGL((gemm_b3_kernel<2, 2, EPI, NP>), grid, dim3(256), 0, stream, g);
+    }
   }
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;

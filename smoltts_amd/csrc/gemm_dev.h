@@ -99,8 +99,12 @@ __device__ __forceinline__ void rows_epilogue(const GemmDev& p, int m, long orow
     for (int i = 0; i < 4; ++i)
       if (n0 + i < p.N) v[i] += p.bias[n0 + i];
   }
-  if (n0 + 4 > p.N) {  // N < 4: scalar tail (the 1-channel output conv)
-    for (int i = 0; i < 4 && n0 + i < p.N; ++i) p.out[orow + n0 + i] = p.elu_out ? elu_rows(v[i]) : v[i];
+  if (n0 + 4 > p.N) {  // N < 4: scalar tail (the 1-channel output conv; EPI_STORE only, so raw_out / elu_out apply)
+    const long wrow = p.raw_out ? row_off(m, p.rows_per_batch, p.ldo, p.raw_bstride) : 0;
+    for (int i = 0; i < 4 && n0 + i < p.N; ++i) {
+      if (p.raw_out) p.raw_out[wrow + n0 + i] = v[i];
+      p.out[orow + n0 + i] = p.elu_out ? elu_rows(v[i]) : v[i];
+    }
     return;
   }
   if (EPI == SMOLTTS_EPI_GELU) {
