@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 
 #include "argmax_dev.h"
@@ -35,7 +36,22 @@ struct SmolttsEngine {
 
 constexpr int STAGE_RING = 8;
 constexpr int GRAPH_FORMS = 64;  // the values of SmolttsSession.form (pick_form)
-constexpr int FORM_ALIGN = 32;   // bit 5: some slot's alignment window is on
+// the bits of a form (form_of), and of h_form[b]: what slot b asks for -- its slow token / its depth codes sampled, its filter entry
+// on, its length entry on, its slow token scored, its alignment window on
+constexpr int FORM_SLOW = 1, FORM_FAST = 2, FORM_FILTER = 4, FORM_LENGTH = 8, FORM_SCORE = 16, FORM_ALIGN = 32;
+// the captured graphs of a form: one decode frame (slow step + tail); the tail alone (slow head + depth steps + commit) as run after
+// a prefill; `multi_frames` consecutive decode frames in one graph (fewer graph launches per tick / chunk)
+enum GraphKind { GRAPH_FRAME, GRAPH_TAIL, GRAPH_MULTI, GRAPH_KINDS };
+
+// STAGE_RING pinned host areas of `area` bytes each, used in turn as the source of async copies; ev[k] is recorded behind the copies
+// out of area k, and the host waits for it before it writes that area again (ring_create / _destroy / _take / _sent)
+struct PinnedRing {
+  char* base;
+  size_t area;
+  hipEvent_t ev[STAGE_RING];
+  bool live[STAGE_RING];
+  int next;
+};
 
 struct SmolttsSession {
   SmolttsEngine* e;
@@ -70,41 +86,24 @@ struct SmolttsSession {
   int* attn_ticket;          // ... and arrival tickets [ATT_SPLIT_MAX_PAIRS]: zeroed at creation and again by every commit kernel (end of frame)
   int* margin_at;            // [B] frame * 64 + step of the slot's smallest top-2 gap
   int* codes;                // [B][max_frames][1+n_fast]
-  // host staging (pinned)
-  int* h_stage;                // STAGE_RING pinned areas of 2*B ints, used in turn
-  hipEvent_t stage_ev[8];      // recorded behind the async copies out of each area
-  bool stage_ev_live[8];
-  int stage_next;
-  // captured graphs, one set per form (pick_form: which picks sample, whether some slot filters, whether some slot's length entry
-  // is on; index 0 outside slot mode), each created when first needed
-  hipGraphExec_t graph_exec[GRAPH_FORMS];   // one decode frame (slow step + tail)
-  bool graph_ready[GRAPH_FORMS];
-  hipGraphExec_t tail_exec[GRAPH_FORMS];    // the tail alone (slow head + depth steps + commit) as run after a prefill
-  bool tail_ready[GRAPH_FORMS];
-  hipGraphExec_t multi_exec[GRAPH_FORMS];   // `multi_frames` consecutive decode frames in one graph (fewer graph launches per tick / chunk)
-  bool multi_ready[GRAPH_FORMS];
+  PinnedRing stage_ring;       // host staging of the prefill calls' lists (stage_upload): areas of 2*B ints
+  // captured graphs, one set per form (pick_form; index 0 outside slot mode), each created when first needed; null = not built
+  hipGraphExec_t graphs[GRAPH_KINDS][GRAPH_FORMS];
   int form;                       // the form the next launches are built / replayed in (pick_form)
   // slot mode (smoltts_session_set_slot_sampling): per-slot sampling entries
   bool slot_mode;
   SmolttsSlotSampling* slot_tab;      // [B] read by the picks; null until slot mode
   SmolttsSlotSampling* slot_tab_area; // where it is carved (the slab's tail): [B] table, [B] upload entries, [B] upload slots
-  SmolttsSlotSampling* h_slot;        // host mirror of the table: chooses the graph form
-  char* h_slot_stage;                 // STAGE_RING pinned areas (B entries + B slots of each table), used in turn
-  hipEvent_t slot_ev[STAGE_RING];
-  bool slot_ev_live[STAGE_RING];
-  int slot_next;
-  // ... and per-slot filter entries (smoltts_session_set_slot_filters): uploaded through the same ring (each area holds a
-  // filter part behind its sampling part)
+  uint8_t* h_form;                    // [B] host mirror of every per-slot table, as FORM_* bits: chooses the graph form
+  PinnedRing slot_ring;               // host staging of the table uploads (upload_slot_entries): areas of B entries + B slots of the largest entry
+  // ... and per-slot filter entries (smoltts_session_set_slot_filters)
   SmolttsSlotFilters* filt_tab;       // [B] read by the sampled picks of slot mode; all zero = off
   SmolttsSlotFilters* filt_tab_area;  // [B] table, [B] upload entries, [B] upload slots
-  bool* h_filt_on;                    // host mirror: which slots' entries are on (chooses the graph form)
-  // ... and per-slot length entries (smoltts_session_set_slot_length): the third part of each ring area
+  // ... and per-slot length entries (smoltts_session_set_slot_length)
   SmolttsSlotLength* len_tab;         // [B] read by the slow picks of slot mode (greedy and sampled); all zero = off
   SmolttsSlotLength* len_tab_area;    // [B] table, [B] upload entries, [B] upload slots
-  bool* h_len_on;                     // host mirror: which slots' entries are on (bit 3 of the graph form)
-  // ... and per-slot score flags (smoltts_session_set_slot_score): host only.  In a form with bit 4 every row's slow pick is scored
-  // and the host reads the slots it asked about.
-  bool* h_score_on;
+  // ... and per-slot score flags (smoltts_session_set_slot_score): host only (FORM_SCORE of h_form).  In a form with that bit every
+  // row's slow pick is scored and the host reads the slots it asked about.
   float* logprob;                     // [B][max_frames]: the log-probability of each emitted slow id, written by the scored forms
   // ... and per-slot alignment windows (smoltts_session_set_slot_align) for the chosen (layer, head) pairs
   // (smoltts_session_set_align_heads).  Table, upload area and rows live in the caller's buffer, not in the slab.
@@ -113,7 +112,6 @@ struct SmolttsSession {
   int* align_win;                     // [B][2] (t0, t1) read by attn_align_kernel; t1 <= t0 = off
   int* align_up;                      // upload area: [B][2] entries, [B] slots
   float* align_out;                   // [B][max_frames][n_align][2] (m, s1); m = -1: not measured
-  bool* h_align_on;                   // host mirror: which slots' windows are on (bit 5 of the graph form)
   int flight_limit;            // SMOLTTS_MAX_FRAMES_IN_FLIGHT as read at creation (0 = unbounded)
   int multi_frames;            // frames per multi-frame graph (1 = single-frame graphs only): SMOLTTS_FRAMES_PER_GRAPH, else
                                // smoltts_session_set_frames_per_graph, else min(n_frames, 4) of the largest decode call so far
@@ -506,14 +504,14 @@ EmbedTables embed_tables(const SmolttsEngine* e) {
 
 // Whether some row samples its slow token / depth codes: the session-wide temperatures, or in slot mode the form of the launches
 // being built (pick_form).  A part that no row samples is built exactly as the session-wide greedy one.
-bool slow_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & 1) != 0 : s->temp > 0.f; }
-bool fast_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & 2) != 0 : s->fast_temp > 0.f; }
+bool slow_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & FORM_SLOW) != 0 : s->temp > 0.f; }
+bool fast_sampled(const SmolttsSession* s) { return s->slot_mode ? (s->form & FORM_FAST) != 0 : s->fast_temp > 0.f; }
 // Whether some slot's length entry is on (slot mode only): the slow pick then reads the row of logits with every row's own entries,
 // as in a form whose slow token is sampled -- the head GEMM's tile candidates hold unpatched values
-bool length_on(const SmolttsSession* s) { return s->slot_mode && (s->form & 8) != 0; }
+bool length_on(const SmolttsSession* s) { return s->slot_mode && (s->form & FORM_LENGTH) != 0; }
 // Whether some slot scores its slow token (slot mode only): the slow pick then reads the row of logits, by the same rule -- the score
 // sums over the whole row, which the tile candidates do not hold
-bool score_on(const SmolttsSession* s) { return s->slot_mode && (s->form & 16) != 0; }
+bool score_on(const SmolttsSession* s) { return s->slot_mode && (s->form & FORM_SCORE) != 0; }
 
 // The pick arguments of step 0 (slow token) / step >= 1 (depth codes).  Slot mode, sampling form: every row reads its own entry
 // (a greedy row then takes the argmax inside argmax_row); greedy form: plain greedy arguments.
@@ -525,7 +523,7 @@ SampleArgs pick_args(const SmolttsSession* s, int step) {
     SampleArgs sa{0.f, 0.f, 0, step, 0, s->frames, nullptr, s->margin_at, sampled || length || score ? s->slot_tab : nullptr};
     if (length) { sa.length = s->len_tab; sa.im_end = s->e->cfg.im_end_id; }
     if (score) { sa.logprob = s->logprob; sa.logprob_stride = s->max_frames; }
-    if (sampled && (s->form & 4)) {  // the filters of the sampled rows; the penalty's history: this step's column of the slot's emitted frames
+    if (sampled && (s->form & FORM_FILTER)) {  // the filters of the sampled rows; the penalty's history: this step's column of the slot's emitted frames
       sa.filters = s->filt_tab;
       sa.hist = s->codes + step; sa.hist_slot_stride = (int64_t)s->max_frames * (1 + s->e->cfg.n_fast);
       sa.hist_frame_stride = 1 + s->e->cfg.n_fast; sa.hist_frames = s->max_frames;
@@ -720,34 +718,80 @@ int run_decode_frame(SmolttsSession* s, hipStream_t st) {
   return run_tail(s, /*advance_pos=*/1, st);
 }
 
+// ---- PinnedRing.  ring_destroy tolerates a zeroed ring and leaves one; ring_create is all or nothing (the error under the caller's name)
+void ring_destroy(PinnedRing* r) {
+  for (int k = 0; k < STAGE_RING; ++k)
+    if (r->ev[k]) (void)hipEventDestroy(r->ev[k]);
+  if (r->base) (void)hipHostFree(r->base);
+  memset(r, 0, sizeof(*r));
+}
+
+int ring_create(const char* what, PinnedRing* r, size_t area) {
+  memset(r, 0, sizeof(*r));
+  r->area = area;
+  const char* failed = hipHostMalloc((void**)&r->base, area * STAGE_RING, hipHostMallocDefault) != hipSuccess ? "hipHostMalloc" : nullptr;
+  if (failed) r->base = nullptr;
+  for (int k = 0; k < STAGE_RING && !failed; ++k)
+    if (hipEventCreateWithFlags(&r->ev[k], hipEventDisableTiming) != hipSuccess) {
+      r->ev[k] = nullptr;
+      failed = "hipEventCreate";
+    }
+  if (!failed) return SMOLTTS_OK;
+  ring_destroy(r);
+  set_error("%s: %s failed", what, failed);
+  return SMOLTTS_E_HIP;
+}
+
+// The next area, once the copies that last read it are through: the host's only wait, and only when STAGE_RING uploads are queued
+int ring_take(PinnedRing* r, char** area, int* k) {
+  *k = r->next;
+  r->next = (*k + 1) % STAGE_RING;
+  if (r->live[*k]) ST_CHECK_HIP(hipEventSynchronize(r->ev[*k]));
+  *area = r->base + (size_t)*k * r->area;
+  return SMOLTTS_OK;
+}
+
+// Behind the async copies out of area k
+int ring_sent(PinnedRing* r, int k, hipStream_t st) {
+  ST_CHECK_HIP(hipEventRecord(r->ev[k], st));
+  r->live[k] = true;
+  return SMOLTTS_OK;
+}
+
+// What enter_slot_mode makes; after it the session is outside slot mode and owns nothing of it (a later call may enter again)
+void leave_slot_mode(SmolttsSession* s) {
+  ring_destroy(&s->slot_ring);
+  delete[] s->h_form;
+  s->h_form = nullptr;
+  s->slot_tab = nullptr; s->filt_tab = nullptr; s->len_tab = nullptr;
+  s->slot_mode = false;
+}
+
 // Slot / last-row lists of a prefill call -> device, through the session's pinned staging buffer.  Only the previous
 // upload is waited for (an event), never the stream: a serving loop calls this while earlier frames are still running.
 int stage_upload(SmolttsSession* s, const int32_t* slots_host, const int32_t* last_row_host, int n_slots, hipStream_t st) {
   // a ring of pinned areas: the host only waits when STAGE_RING uploads are still queued behind other work on `st`
   // (a serving loop uploads while a tick of frame graphs is pending; waiting for the previous upload would stall it)
-  const int k = s->stage_next;
-  s->stage_next = (k + 1) % STAGE_RING;
-  if (s->stage_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->stage_ev[k]));
-  int* h = s->h_stage + (size_t)k * 2 * s->B;
+  char* area;
+  int k;
+  ST_TRY(ring_take(&s->stage_ring, &area, &k));
+  int* h = reinterpret_cast<int*>(area);
   for (int i = 0; i < n_slots; ++i) { h[i] = slots_host[i]; h[s->B + i] = last_row_host[i]; }
   ST_CHECK_HIP(hipMemcpyAsync(s->stage_slots, h, sizeof(int) * n_slots, hipMemcpyHostToDevice, st));
   ST_CHECK_HIP(hipMemcpyAsync(s->stage_last, h + s->B, sizeof(int) * n_slots, hipMemcpyHostToDevice, st));
-  ST_CHECK_HIP(hipEventRecord(s->stage_ev[k], st));
-  s->stage_ev_live[k] = true;
-  return SMOLTTS_OK;
+  return ring_sent(&s->stage_ring, k, st);
 }
 
-void drop_multi_graphs(SmolttsSession* s) {
-  for (int f = 0; f < GRAPH_FORMS; ++f)
-    if (s->multi_ready[f]) { (void)hipGraphExecDestroy(s->multi_exec[f]); s->multi_ready[f] = false; }
-}
-
-void drop_graphs(SmolttsSession* s) {
-  for (int f = 0; f < GRAPH_FORMS; ++f) {
-    if (s->graph_ready[f]) { (void)hipGraphExecDestroy(s->graph_exec[f]); s->graph_ready[f] = false; }
-    if (s->tail_ready[f]) { (void)hipGraphExecDestroy(s->tail_exec[f]); s->tail_ready[f] = false; }
-  }
-  drop_multi_graphs(s);
+// Forget captured graphs: the kinds of the mask (bit GraphKind), in every form or (form_bit != 0) in the forms with that bit
+void drop_graphs(SmolttsSession* s, unsigned kinds = ~0u, int form_bit = 0) {
+  for (int k = 0; k < GRAPH_KINDS; ++k)
+    for (int f = 0; f < GRAPH_FORMS; ++f) {
+      hipGraphExec_t& g = s->graphs[k][f];
+      if (g && (kinds >> k & 1) && (form_bit == 0 || (f & form_bit))) {
+        (void)hipGraphExecDestroy(g);
+        g = nullptr;
+      }
+    }
 }
 
 void set_stop_on_eos(SmolttsSession* s, int stop_on_eos) {
@@ -793,16 +837,16 @@ int arm_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos
 // window is on (every decode frame then queues attn_align_kernel behind the blocks of the chosen layers; no pick changes).  Outside slot mode always 0 (the session-wide temperatures are baked into the one set; changing them drops it).  Called by every entry
 // point that launches or captures picks, after the last change of the table.
 int form_of(const SmolttsSession* s) {
-  int f = 0, len = 0;
+  int f = 0;
   if (s->slot_mode)
-    for (int b = 0; b < s->B; ++b) {
-      f |= (s->h_slot[b].temp > 0.f ? 1 : 0) | (s->h_slot[b].fast_temp > 0.f ? 2 : 0) | (s->h_filt_on[b] ? 4 : 0);
-      len |= (s->h_len_on[b] ? 8 : 0) | (s->h_score_on[b] ? 16 : 0) | (s->n_align > 0 && s->h_align_on[b] ? FORM_ALIGN : 0);
-    }
-  if ((f & 3) == 0) f = 0;  // nothing samples: the filters have nothing to act on
-  return f | len;
+    for (int b = 0; b < s->B; ++b) f |= s->h_form[b];
+  if ((f & (FORM_SLOW | FORM_FAST)) == 0) f &= ~FORM_FILTER;  // nothing samples: the filters have nothing to act on
+  if (s->n_align <= 0) f &= ~FORM_ALIGN;                      // no head is chosen: the windows have nothing to measure
+  return f;
 }
 void pick_form(SmolttsSession* s) { s->form = form_of(s); }
+// h_form[slot]: the bits of `mask` become `bits`
+void set_form_bits(SmolttsSession* s, int slot, int mask, int bits) { s->h_form[slot] = (uint8_t)((s->h_form[slot] & ~mask) | bits); }
 
 // Record `body` (a fixed launch sequence on the given stream) into an executable graph.
 template <typename F>
@@ -834,6 +878,16 @@ bool graphs_enabled() {
   return !(no_graph && no_graph[0] == '1');
 }
 
+// s->graphs[kind][s->form], captured from `body` when first needed (a failed capture leaves the entry empty)
+template <typename F>
+int ensure_graph(SmolttsSession* s, GraphKind kind, hipStream_t st, F body) {
+  if (s->graphs[kind][s->form]) return SMOLTTS_OK;
+  hipGraphExec_t made = nullptr;
+  ST_TRY(capture_graph(st, &made, body));
+  s->graphs[kind][s->form] = made;
+  return SMOLTTS_OK;
+}
+
 int run_decode_frame(SmolttsSession* s, hipStream_t st);
 
 // The graph of `multi_frames` consecutive frames (every graph launch costs the GPU a gap between the last node of one graph and
@@ -841,13 +895,82 @@ int run_decode_frame(SmolttsSession* s, hipStream_t st);
 int ensure_multi_graph(SmolttsSession* s, int n_frames, hipStream_t st) {
   if (s->flight_limit > 0 && s->multi_frames > s->flight_limit) s->multi_frames = s->flight_limit;
   const int mf = s->multi_frames;
-  if (mf > 1 && n_frames >= mf && !s->multi_ready[s->form]) {
-    ST_TRY(capture_graph(st, &s->multi_exec[s->form], [&](hipStream_t cap) {
+  if (mf > 1 && n_frames >= mf)
+    ST_TRY(ensure_graph(s, GRAPH_MULTI, st, [&](hipStream_t cap) {
       for (int i = 0; i < mf; ++i) ST_TRY(run_decode_frame(s, cap));
       return (int)SMOLTTS_OK;
     }));
-    s->multi_ready[s->form] = true;
+  return SMOLTTS_OK;
+}
+
+// ---- slot mode
+// One upload of a per-slot table, on the host and on the device alike: B entries, then B slot numbers
+template <typename Entry>
+constexpr size_t upload_bytes(size_t B) { return B * (sizeof(Entry) + sizeof(int)); }
+constexpr size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
+// the caller's alignment buffer: [B][2] window table | upload area | rows, each part 16-byte aligned
+size_t align_table_bytes(const SmolttsSession* s) { return round16((size_t)s->B * 2 * sizeof(int)); }
+size_t align_header_bytes(const SmolttsSession* s) { return align_table_bytes(s) + round16(upload_bytes<int2>(s->B)); }
+
+// Enter slot mode (first per-slot call of either kind): host mirror, pinned ring, events; every slot greedy with seed 0 and
+// its filters off
+int enter_slot_mode(SmolttsSession* s, hipStream_t st) {
+  if (s->slot_mode) return SMOLTTS_OK;
+  const size_t B = s->B;
+  const int rc = [&]() -> int {
+    s->h_form = new (std::nothrow) uint8_t[B]();
+    ST_REQUIRE(s->h_form, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
+    // an area holds one upload of any table: every call writes at the start of the area it takes
+    const size_t area = std::max({upload_bytes<SmolttsSlotSampling>(B), upload_bytes<SmolttsSlotFilters>(B),
+                                  upload_bytes<SmolttsSlotLength>(B), upload_bytes<int2>(B)});
+    ST_TRY(ring_create("session_set_slot_sampling", &s->slot_ring, round16(area)));
+    s->slot_tab = s->slot_tab_area;
+    s->filt_tab = s->filt_tab_area;
+    s->len_tab = s->len_tab_area;
+    ST_CHECK_HIP(hipMemsetAsync(s->slot_tab, 0, B * sizeof(SmolttsSlotSampling), st));
+    ST_CHECK_HIP(hipMemsetAsync(s->filt_tab, 0, B * sizeof(SmolttsSlotFilters), st));
+    ST_CHECK_HIP(hipMemsetAsync(s->len_tab, 0, B * sizeof(SmolttsSlotLength), st));
+    return SMOLTTS_OK;
+  }();
+  if (rc != SMOLTTS_OK) {
+    leave_slot_mode(s);  // (slot mode is not entered, and nothing of it is left behind)
+    return rc;
   }
+  s->slot_mode = true;
+  drop_graphs(s);  // (the session-wide set: slot mode builds its own)
+  return SMOLTTS_OK;
+}
+
+// One upload of `n` entries of a per-slot table: table_dev[slots_host[i]] = entry i.  check(i) validates the caller's values of entry
+// i (it may refuse with a status); fill(i, entry) writes the entry and updates the host mirror.  Every check passes before anything
+// changes: a refused call leaves the session as it was.  The host copies the entries and their slot numbers into the next area of the
+// pinned ring and queues one copy (into up_dev: [B] entries, [B] slots) + one scatter launch on `st`; it waits only for the upload that
+// last used that area (an event), never for the stream.
+template <typename Entry, typename Check, typename Fill>
+int upload_slot_entries(SmolttsSession* s, const char* what, const int32_t* slots_host, int n, Entry* up_dev, Entry* table_dev,
+                        hipStream_t st, Check check, Fill fill) {
+  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "%s: %d entries, session holds %d slots", what, n, s->B);
+  for (int i = 0; i < n; ++i) {
+    ST_TRY(check_slot(what, slots_host[i], s->B));
+    for (int j = 0; j < i; ++j) ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "%s: slot %d listed twice", what, slots_host[i]);
+    ST_TRY(check(i));
+  }
+  ST_TRY(enter_slot_mode(s, st));
+  if (n == 0) return SMOLTTS_OK;
+  const size_t B = s->B;
+  char* area;
+  int k;
+  ST_TRY(ring_take(&s->slot_ring, &area, &k));
+  Entry* h = reinterpret_cast<Entry*>(area);
+  int* hi = reinterpret_cast<int*>(h + B);
+  for (int i = 0; i < n; ++i) {
+    fill(i, h[i]);
+    hi[i] = slots_host[i];
+  }
+  ST_CHECK_HIP(hipMemcpyAsync(up_dev, h, upload_bytes<Entry>(B), hipMemcpyHostToDevice, st));
+  ST_TRY(ring_sent(&s->slot_ring, k, st));
+  hipLaunchKernelGGL(slot_scatter_kernel<Entry>, dim3((n + 63) / 64), dim3(64), 0, st, n, up_dev, reinterpret_cast<const int*>(up_dev + B), table_dev);
+  ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }
 
@@ -1111,19 +1234,10 @@ int smoltts_session_create_kv(SmolttsEngine* e, void* slab_dev, size_t slab_byte
   s->fuse_pick = true;
   s->kv_format = kv_format;
   carve(s, (char*)slab_dev);
-  if (hipHostMalloc((void**)&s->h_stage, sizeof(int) * 2 * max_batch * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
-    delete s;
-    set_error("session_create: hipHostMalloc failed");
-    return SMOLTTS_E_HIP;
-  }
-  for (int k = 0; k < STAGE_RING; ++k) {
-    if (hipEventCreateWithFlags(&s->stage_ev[k], hipEventDisableTiming) != hipSuccess) {
-      for (int j = 0; j < k; ++j) (void)hipEventDestroy(s->stage_ev[j]);
-      (void)hipHostFree(s->h_stage);
-      delete s;
-      set_error("session_create: hipEventCreate failed");
-      return SMOLTTS_E_HIP;
-    }
+  // from here a failure sets its message and hands the half-built session to smoltts_session_destroy
+  if (const int rc = ring_create("session_create", &s->stage_ring, sizeof(int) * 2 * max_batch); rc != SMOLTTS_OK) {
+    smoltts_session_destroy(s);
+    return rc;
   }
   {  // frames the host may run ahead of the GPU: SMOLTTS_MAX_FRAMES_IN_FLIGHT (default 64; 0 = unbounded).  A profiler that
      // rewrites every dispatch into several packets (rocprofv3 --pmc) needs a small bound and one frame per graph: its
@@ -1144,32 +1258,22 @@ int smoltts_session_create_kv(SmolttsEngine* e, void* slab_dev, size_t slab_byte
   hipError_t err = hipGetLastError();
   if (err == hipSuccess) err = hipStreamSynchronize(0);
   if (err != hipSuccess) {
-    for (int k = 0; k < STAGE_RING; ++k) (void)hipEventDestroy(s->stage_ev[k]);
-    (void)hipHostFree(s->h_stage);
-    delete s;
     set_error("session_create: init kernel failed: %s", hipGetErrorString(err));
+    smoltts_session_destroy(s);
     return SMOLTTS_E_HIP;
   }
   *out = s;
   return SMOLTTS_OK;
 }
 
+// (copes with a half-built, zero-initialised session: smoltts_session_create_kv's failures end here)
 void smoltts_session_destroy(SmolttsSession* s) {
   if (!s) return;
   drop_graphs(s);
-  for (int k = 0; k < STAGE_RING; ++k)
-    if (s->stage_ev[k]) (void)hipEventDestroy(s->stage_ev[k]);
-  if (s->h_stage) (void)hipHostFree(s->h_stage);
+  ring_destroy(&s->stage_ring);
   for (int k = 0; k < 2; ++k)
     if (s->flight_ev[k]) (void)hipEventDestroy(s->flight_ev[k]);
-  for (int k = 0; k < STAGE_RING; ++k)
-    if (s->slot_ev[k]) (void)hipEventDestroy(s->slot_ev[k]);
-  if (s->h_slot_stage) (void)hipHostFree(s->h_slot_stage);
-  delete[] s->h_slot;
-  delete[] s->h_filt_on;
-  delete[] s->h_len_on;
-  delete[] s->h_score_on;
-  delete[] s->h_align_on;
+  leave_slot_mode(s);
   delete s;
 }
 
@@ -1199,11 +1303,8 @@ int smoltts_lm_prefill(SmolttsSession* s, const int32_t* grid_dev, const int32_t
   // frame 0: the tail is the same ~180 launches after every prefill -> replayed from a graph (host launch time is what
   // a single short prompt waits for)
   if (graphs_enabled()) {
-    if (!s->tail_ready[s->form]) {
-      ST_TRY(capture_graph(st, &s->tail_exec[s->form], [&](hipStream_t cap) { return run_tail(s, /*advance_pos=*/0, cap); }));
-      s->tail_ready[s->form] = true;
-    }
-    ST_CHECK_HIP(hipGraphLaunch(s->tail_exec[s->form], st));
+    ST_TRY(ensure_graph(s, GRAPH_TAIL, st, [&](hipStream_t cap) { return run_tail(s, /*advance_pos=*/0, cap); }));
+    ST_CHECK_HIP(hipGraphLaunch(s->graphs[GRAPH_TAIL][s->form], st));
   } else {
     ST_TRY(run_tail(s, /*advance_pos=*/0, st));
   }
@@ -1288,10 +1389,7 @@ int smoltts_lm_decode(SmolttsSession* s, int32_t n_frames, void* stream) {
     for (int f = 0; f < n_frames; ++f) ST_TRY(run_decode_frame(s, st));
     return SMOLTTS_OK;
   }
-  if (!s->graph_ready[s->form]) {
-    ST_TRY(capture_graph(st, &s->graph_exec[s->form], [&](hipStream_t cap) { return run_decode_frame(s, cap); }));
-    s->graph_ready[s->form] = true;
-  }
+  ST_TRY(ensure_graph(s, GRAPH_FRAME, st, [&](hipStream_t cap) { return run_decode_frame(s, cap); }));
   // Bounded run-ahead: a frame is ~230 AQL packets, and nothing stops a caller from queueing hundreds of frames.  The
   // hardware queue holds 16K packets; the runtime copes with a full ring, but a profiler that rewrites every dispatch into
   // several packets (rocprofv3 --pmc: counter start / stop + serialisation barriers around each kernel) overflows its
@@ -1307,11 +1405,12 @@ int smoltts_lm_decode(SmolttsSession* s, int32_t n_frames, void* stream) {
     const int want = n_frames < 4 ? n_frames : 4;
     if (want > s->multi_frames) {
       s->multi_frames = want;
-      drop_multi_graphs(s);
+      drop_graphs(s, 1u << GRAPH_MULTI);
     }
   }
   ST_TRY(ensure_multi_graph(s, n_frames, st));
-  const int mf = s->multi_ready[s->form] ? s->multi_frames : 1;
+  const hipGraphExec_t frame = s->graphs[GRAPH_FRAME][s->form], multi = s->graphs[GRAPH_MULTI][s->form];
+  const int mf = multi ? s->multi_frames : 1;
   for (int f = 0; f < n_frames;) {
     if (s->flight_group > 0 && s->flight_count >= s->flight_group) {
       const int k = s->flight_cur;
@@ -1322,11 +1421,11 @@ int smoltts_lm_decode(SmolttsSession* s, int32_t n_frames, void* stream) {
       s->flight_count = 0;
     }
     if (mf > 1 && n_frames - f >= mf) {
-      ST_CHECK_HIP(hipGraphLaunch(s->multi_exec[s->form], st));
+      ST_CHECK_HIP(hipGraphLaunch(multi, st));
       s->flight_count += mf;
       f += mf;
     } else {
-      ST_CHECK_HIP(hipGraphLaunch(s->graph_exec[s->form], st));
+      ST_CHECK_HIP(hipGraphLaunch(frame, st));
       s->flight_count++;
       f++;
     }
@@ -1345,199 +1444,69 @@ int smoltts_session_set_sampling(SmolttsSession* s, float temp, float fast_temp,
   return SMOLTTS_OK;
 }
 
-namespace {
-size_t slot_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotSampling) + sizeof(int)); }
-size_t filt_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotFilters) + sizeof(int)); }
-size_t len_area_bytes(const SmolttsSession* s) { return (size_t)s->B * (sizeof(SmolttsSlotLength) + sizeof(int)); }
-// (the length part is padded to 8 bytes: every area of the ring starts with sampling entries, which hold a uint64_t)
-size_t len_part_bytes(const SmolttsSession* s) { return (len_area_bytes(s) + 7) & ~(size_t)7; }
-// (the fourth part: alignment windows, B (t0, t1) pairs + B slot numbers)
-size_t align_area_bytes(const SmolttsSession* s) { return (size_t)s->B * 3 * sizeof(int); }
-size_t ring_area_bytes(const SmolttsSession* s) {
-  return slot_area_bytes(s) + filt_area_bytes(s) + len_part_bytes(s) + ((align_area_bytes(s) + 7) & ~(size_t)7);
-}
-// the caller's alignment buffer: [B][2] window table | upload area | rows, each part 16-byte aligned
-size_t align_table_bytes(const SmolttsSession* s) { return ((size_t)s->B * 2 * sizeof(int) + 15) & ~(size_t)15; }
-size_t align_header_bytes(const SmolttsSession* s) { return align_table_bytes(s) + ((align_area_bytes(s) + 15) & ~(size_t)15); }
-
-// Enter slot mode (first per-slot call of either kind): host mirror, pinned ring, events; every slot greedy with seed 0 and
-// its filters off
-int enter_slot_mode(SmolttsSession* s, hipStream_t st) {
-  if (s->slot_mode) return SMOLTTS_OK;
-  const size_t B = s->B;
-  s->h_slot = new (std::nothrow) SmolttsSlotSampling[B];
-  ST_REQUIRE(s->h_slot, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
-  memset(s->h_slot, 0, B * sizeof(SmolttsSlotSampling));
-  delete[] s->h_filt_on;
-  s->h_filt_on = new (std::nothrow) bool[B]();
-  ST_REQUIRE(s->h_filt_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
-  delete[] s->h_len_on;
-  s->h_len_on = new (std::nothrow) bool[B]();
-  ST_REQUIRE(s->h_len_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
-  delete[] s->h_score_on;
-  s->h_score_on = new (std::nothrow) bool[B]();
-  ST_REQUIRE(s->h_score_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
-  delete[] s->h_align_on;
-  s->h_align_on = new (std::nothrow) bool[B]();
-  ST_REQUIRE(s->h_align_on, SMOLTTS_E_INVALID, "session_set_slot_sampling: out of host memory");
-  if (hipHostMalloc((void**)&s->h_slot_stage, ring_area_bytes(s) * STAGE_RING, hipHostMallocDefault) != hipSuccess) {
-    s->h_slot_stage = nullptr;
-    delete[] s->h_slot;
-    s->h_slot = nullptr;
-    set_error("session_set_slot_sampling: hipHostMalloc failed");
-    return SMOLTTS_E_HIP;
-  }
-  for (int k = 0; k < STAGE_RING; ++k) {
-    if (hipEventCreateWithFlags(&s->slot_ev[k], hipEventDisableTiming) != hipSuccess) {
-      for (int j = 0; j <= k; ++j) {
-        if (j < k) (void)hipEventDestroy(s->slot_ev[j]);
-        s->slot_ev[j] = nullptr;
-      }
-      (void)hipHostFree(s->h_slot_stage);
-      s->h_slot_stage = nullptr;
-      delete[] s->h_slot;
-      s->h_slot = nullptr;
-      set_error("session_set_slot_sampling: hipEventCreate failed");
-      return SMOLTTS_E_HIP;  // (slot mode is not entered)
-    }
-  }
-  s->slot_tab = s->slot_tab_area;
-  s->filt_tab = s->filt_tab_area;
-  s->len_tab = s->len_tab_area;
-  ST_CHECK_HIP(hipMemsetAsync(s->slot_tab, 0, B * sizeof(SmolttsSlotSampling), st));
-  ST_CHECK_HIP(hipMemsetAsync(s->filt_tab, 0, B * sizeof(SmolttsSlotFilters), st));
-  ST_CHECK_HIP(hipMemsetAsync(s->len_tab, 0, B * sizeof(SmolttsSlotLength), st));
-  s->slot_mode = true;
-  drop_graphs(s);  // (the session-wide set: slot mode builds its own)
-  return SMOLTTS_OK;
-}
-}  // namespace
-
-// Slot mode: per-slot entries (include/smoltts_hip.h).  The host copies the entries into the next area of a pinned ring and queues
-// one copy + one scatter launch on `stream`; it waits only for the upload that last used that area (an event), never for the stream.
+// Slot mode: per-slot entries (include/smoltts_hip.h), uploaded on `stream` by upload_slot_entries.
 int smoltts_session_set_slot_sampling(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* temp_host,
                                       const float* fast_temp_host, const float* min_p_host, const uint64_t* seed_host, void* stream) {
   ST_REQUIRE(s && (n == 0 || (slots_host && temp_host && fast_temp_host && min_p_host && seed_host)), SMOLTTS_E_INVALID,
              "session_set_slot_sampling: null argument");
-  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_sampling: %d entries, session holds %d slots", n, s->B);
-  for (int i = 0; i < n; ++i) {
-    ST_TRY(check_slot("session_set_slot_sampling", slots_host[i], s->B));
-    for (int j = 0; j < i; ++j)
-      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d listed twice", slots_host[i]);
-    ST_REQUIRE(temp_host[i] == temp_host[i] && fast_temp_host[i] == fast_temp_host[i] && min_p_host[i] >= 0.f && min_p_host[i] < 1.f,
-               SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d: temperatures must be numbers, 0 <= min_p < 1", slots_host[i]);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t B = s->B;
-  ST_TRY(enter_slot_mode(s, st));
-  if (n == 0) return SMOLTTS_OK;
-  const int k = s->slot_next;
-  s->slot_next = (k + 1) % STAGE_RING;
-  if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
-  const size_t area = slot_area_bytes(s);
-  SmolttsSlotSampling* h = reinterpret_cast<SmolttsSlotSampling*>(s->h_slot_stage + (size_t)k * ring_area_bytes(s));
-  int* hi = reinterpret_cast<int*>(h + B);
-  for (int i = 0; i < n; ++i) {
-    SmolttsSlotSampling en;
-    en.temp = temp_host[i]; en.fast_temp = fast_temp_host[i]; en.min_p = min_p_host[i]; en.reserved = 0; en.seed = seed_host[i];
-    h[i] = en;
-    hi[i] = slots_host[i];
-    s->h_slot[slots_host[i]] = en;
-  }
-  SmolttsSlotSampling* up = s->slot_tab_area + B;  // device upload area: the same layout as a ring area
-  ST_CHECK_HIP(hipMemcpyAsync(up, h, area, hipMemcpyHostToDevice, st));
-  ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
-  s->slot_ev_live[k] = true;
-  hipLaunchKernelGGL(slot_scatter_kernel<SmolttsSlotSampling>, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->slot_tab);
-  ST_CHECK_HIP(hipGetLastError());
-  return SMOLTTS_OK;
+  return upload_slot_entries(
+      s, "session_set_slot_sampling", slots_host, n, s->slot_tab_area + s->B, s->slot_tab_area, (hipStream_t)stream,
+      [&](int i) -> int {
+        ST_REQUIRE(temp_host[i] == temp_host[i] && fast_temp_host[i] == fast_temp_host[i] && min_p_host[i] >= 0.f && min_p_host[i] < 1.f,
+                   SMOLTTS_E_INVALID, "session_set_slot_sampling: slot %d: temperatures must be numbers, 0 <= min_p < 1", slots_host[i]);
+        return SMOLTTS_OK;
+      },
+      [&](int i, SmolttsSlotSampling& en) {
+        en.temp = temp_host[i]; en.fast_temp = fast_temp_host[i]; en.min_p = min_p_host[i]; en.reserved = 0; en.seed = seed_host[i];
+        set_form_bits(s, slots_host[i], FORM_SLOW | FORM_FAST, (en.temp > 0.f ? FORM_SLOW : 0) | (en.fast_temp > 0.f ? FORM_FAST : 0));
+      });
 }
 
-// The filter entries of slot mode, uploaded like the sampling entries (the filter part of the next ring area, one copy + one
-// scatter launch on `stream`).  Whether any entry is on is a bit of the graph form (pick_form): no graph is dropped here.
+// The filter entries of slot mode, uploaded like the sampling entries.  Whether any entry is on is a bit of the graph form
+// (pick_form): no graph is dropped here.
 int smoltts_session_set_slot_filters(SmolttsSession* s, const int32_t* slots_host, int32_t n, const float* top_p_host,
                                      const int32_t* top_k_host, const float* penalty_host, const int32_t* window_host, void* stream) {
   ST_REQUIRE(s && (n == 0 || (slots_host && top_p_host && top_k_host && penalty_host && window_host)), SMOLTTS_E_INVALID,
              "session_set_slot_filters: null argument");
-  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_filters: %d entries, session holds %d slots", n, s->B);
-  for (int i = 0; i < n; ++i) {
-    ST_TRY(check_slot("session_set_slot_filters", slots_host[i], s->B));
-    for (int j = 0; j < i; ++j)
-      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_filters: slot %d listed twice", slots_host[i]);
-    const float r = penalty_host[i];
-    ST_REQUIRE(top_p_host[i] >= 0.f && top_p_host[i] <= 1.f && top_k_host[i] >= 0 && (r == 0.f || (r >= 1.f && r <= SMOLTTS_FILTER_MAX_PENALTY)) &&
-                   window_host[i] >= 0 && window_host[i] <= SMOLTTS_FILTER_MAX_WINDOW,
-               SMOLTTS_E_INVALID, "session_set_slot_filters: slot %d: 0 <= top_p <= 1, top_k >= 0, penalty 0 or in [1, %g], 0 <= window <= %d",
-               slots_host[i], (double)SMOLTTS_FILTER_MAX_PENALTY, SMOLTTS_FILTER_MAX_WINDOW);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t B = s->B;
-  ST_TRY(enter_slot_mode(s, st));
-  if (n == 0) return SMOLTTS_OK;
-  const int k = s->slot_next;
-  s->slot_next = (k + 1) % STAGE_RING;
-  if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
-  SmolttsSlotFilters* h = reinterpret_cast<SmolttsSlotFilters*>(s->h_slot_stage + (size_t)k * ring_area_bytes(s) + slot_area_bytes(s));
-  int* hi = reinterpret_cast<int*>(h + B);
-  for (int i = 0; i < n; ++i) {
-    SmolttsSlotFilters en;
-    memset(&en, 0, sizeof(en));
-    const float r = penalty_host[i];
-    en.top_p = top_p_host[i] < 1.f ? top_p_host[i] : 0.f;
-    en.top_k = top_k_host[i];
-    if (r > 1.f && window_host[i] > 0) { en.penalty = r; en.inv_penalty = 1.0f / r; en.window = window_host[i]; }
-    h[i] = en;
-    hi[i] = slots_host[i];
-    s->h_filt_on[slots_host[i]] = en.top_p > 0.f || en.top_k > 0 || en.window > 0;
-  }
-  SmolttsSlotFilters* up = s->filt_tab_area + B;  // device upload area: the same layout as the ring area's filter part
-  ST_CHECK_HIP(hipMemcpyAsync(up, h, filt_area_bytes(s), hipMemcpyHostToDevice, st));
-  ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
-  s->slot_ev_live[k] = true;
-  hipLaunchKernelGGL(slot_scatter_kernel<SmolttsSlotFilters>, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->filt_tab);
-  ST_CHECK_HIP(hipGetLastError());
-  return SMOLTTS_OK;
+  return upload_slot_entries(
+      s, "session_set_slot_filters", slots_host, n, s->filt_tab_area + s->B, s->filt_tab_area, (hipStream_t)stream,
+      [&](int i) -> int {
+        const float r = penalty_host[i];
+        ST_REQUIRE(top_p_host[i] >= 0.f && top_p_host[i] <= 1.f && top_k_host[i] >= 0 && (r == 0.f || (r >= 1.f && r <= SMOLTTS_FILTER_MAX_PENALTY)) &&
+                       window_host[i] >= 0 && window_host[i] <= SMOLTTS_FILTER_MAX_WINDOW,
+                   SMOLTTS_E_INVALID, "session_set_slot_filters: slot %d: 0 <= top_p <= 1, top_k >= 0, penalty 0 or in [1, %g], 0 <= window <= %d",
+                   slots_host[i], (double)SMOLTTS_FILTER_MAX_PENALTY, SMOLTTS_FILTER_MAX_WINDOW);
+        return SMOLTTS_OK;
+      },
+      [&](int i, SmolttsSlotFilters& en) {
+        memset(&en, 0, sizeof(en));
+        const float r = penalty_host[i];
+        en.top_p = top_p_host[i] < 1.f ? top_p_host[i] : 0.f;
+        en.top_k = top_k_host[i];
+        if (r > 1.f && window_host[i] > 0) { en.penalty = r; en.inv_penalty = 1.0f / r; en.window = window_host[i]; }
+        set_form_bits(s, slots_host[i], FORM_FILTER, en.top_p > 0.f || en.top_k > 0 || en.window > 0 ? FORM_FILTER : 0);
+      });
 }
 
-// The length entries of slot mode, uploaded like the other two tables (the length part of the next ring area, one copy + one scatter
-// launch on `stream`).  Whether any entry is on is bit 3 of the graph form (pick_form): no graph is dropped here.
+// The length entries of slot mode, uploaded like the other two tables.  Whether any entry is on is bit 3 of the graph form
+// (pick_form): no graph is dropped here.
 int smoltts_session_set_slot_length(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* min_frames_host,
                                     const float* eos_bias_host, void* stream) {
   ST_REQUIRE(s && (n == 0 || (slots_host && min_frames_host && eos_bias_host)), SMOLTTS_E_INVALID, "session_set_slot_length: null argument");
-  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_length: %d entries, session holds %d slots", n, s->B);
-  for (int i = 0; i < n; ++i) {
-    ST_TRY(check_slot("session_set_slot_length", slots_host[i], s->B));
-    for (int j = 0; j < i; ++j)
-      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_length: slot %d listed twice", slots_host[i]);
-    const float b = eos_bias_host[i];
-    ST_REQUIRE(min_frames_host[i] >= 0 && min_frames_host[i] <= SMOLTTS_LENGTH_MAX_FRAMES && b - b == 0.f, SMOLTTS_E_INVALID,
-               "session_set_slot_length: slot %d: 0 <= min_frames <= %d, eos_bias finite", slots_host[i], SMOLTTS_LENGTH_MAX_FRAMES);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t B = s->B;
-  ST_TRY(enter_slot_mode(s, st));
-  if (n == 0) return SMOLTTS_OK;
-  const int k = s->slot_next;
-  s->slot_next = (k + 1) % STAGE_RING;
-  if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
-  SmolttsSlotLength* h = reinterpret_cast<SmolttsSlotLength*>(s->h_slot_stage + (size_t)k * ring_area_bytes(s) + slot_area_bytes(s) + filt_area_bytes(s));
-  int* hi = reinterpret_cast<int*>(h + B);
-  for (int i = 0; i < n; ++i) {
-    SmolttsSlotLength en;
-    memset(&en, 0, sizeof(en));
-    en.min_frames = min_frames_host[i];
-    en.eos_bias = eos_bias_host[i];
-    h[i] = en;
-    hi[i] = slots_host[i];
-    s->h_len_on[slots_host[i]] = en.min_frames > 0 || en.eos_bias != 0.f;
-  }
-  SmolttsSlotLength* up = s->len_tab_area + B;  // device upload area: the same layout as the ring area's length part
-  ST_CHECK_HIP(hipMemcpyAsync(up, h, len_area_bytes(s), hipMemcpyHostToDevice, st));
-  ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
-  s->slot_ev_live[k] = true;
-  hipLaunchKernelGGL(slot_scatter_kernel<SmolttsSlotLength>, dim3((n + 63) / 64), dim3(64), 0, st, n, up, reinterpret_cast<const int*>(up + B), s->len_tab);
-  ST_CHECK_HIP(hipGetLastError());
-  return SMOLTTS_OK;
+  return upload_slot_entries(
+      s, "session_set_slot_length", slots_host, n, s->len_tab_area + s->B, s->len_tab_area, (hipStream_t)stream,
+      [&](int i) -> int {
+        const float b = eos_bias_host[i];
+        ST_REQUIRE(min_frames_host[i] >= 0 && min_frames_host[i] <= SMOLTTS_LENGTH_MAX_FRAMES && b - b == 0.f, SMOLTTS_E_INVALID,
+                   "session_set_slot_length: slot %d: 0 <= min_frames <= %d, eos_bias finite", slots_host[i], SMOLTTS_LENGTH_MAX_FRAMES);
+        return SMOLTTS_OK;
+      },
+      [&](int i, SmolttsSlotLength& en) {
+        memset(&en, 0, sizeof(en));
+        en.min_frames = min_frames_host[i];
+        en.eos_bias = eos_bias_host[i];
+        set_form_bits(s, slots_host[i], FORM_LENGTH, en.min_frames > 0 || en.eos_bias != 0.f ? FORM_LENGTH : 0);
+      });
 }
 
 size_t smoltts_session_align_bytes(SmolttsSession* s, int32_t n) {
@@ -1567,14 +1536,9 @@ int smoltts_session_set_align_heads(SmolttsSession* s, const int32_t* layers_hos
   }
   // frames in flight, on any stream, may be replaying a graph of these forms or writing the buffer this call replaces
   ST_CHECK_HIP(hipDeviceSynchronize());
-  for (int f = 0; f < GRAPH_FORMS; ++f) {
-    if (!(f & FORM_ALIGN)) continue;
-    if (s->graph_ready[f]) { (void)hipGraphExecDestroy(s->graph_exec[f]); s->graph_ready[f] = false; }
-    if (s->tail_ready[f]) { (void)hipGraphExecDestroy(s->tail_exec[f]); s->tail_ready[f] = false; }
-    if (s->multi_ready[f]) { (void)hipGraphExecDestroy(s->multi_exec[f]); s->multi_ready[f] = false; }
-  }
+  drop_graphs(s, ~0u, FORM_ALIGN);
   s->n_align = 0; s->align_win = nullptr; s->align_up = nullptr; s->align_out = nullptr;
-  if (s->h_align_on) memset(s->h_align_on, 0, s->B * sizeof(bool));
+  for (int b = 0; s->h_form && b < s->B; ++b) set_form_bits(s, b, FORM_ALIGN, 0);
   if (n == 0) return SMOLTTS_OK;
   ST_CHECK_HIP(hipMemsetAsync(out_dev, 0, align_table_bytes(s), nullptr));
   ST_CHECK_HIP(hipStreamSynchronize(nullptr));
@@ -1594,42 +1558,28 @@ __global__ __launch_bounds__(256) void align_fill_kernel(const int* slots, long 
 }
 }  // namespace
 
-// The alignment windows of slot mode, uploaded like the other tables (the fourth part of the next ring area, one copy + one scatter
-// launch on `stream`), and behind them the fill of the listed slots' rows.  Whether any window is on is bit 5 of the graph form.
+// The alignment windows of slot mode, uploaded like the other tables, and behind them the fill of the listed slots' rows.  Whether
+// any window is on is bit 5 of the graph form.
 int smoltts_session_set_slot_align(SmolttsSession* s, const int32_t* slots_host, int32_t n, const int32_t* t0_host,
                                    const int32_t* t1_host, void* stream) {
   ST_REQUIRE(s && (n == 0 || (slots_host && t0_host && t1_host)), SMOLTTS_E_INVALID, "session_set_slot_align: null argument");
   ST_REQUIRE(s->n_align > 0, SMOLTTS_E_STATE, "session_set_slot_align: call smoltts_session_set_align_heads first");
-  ST_REQUIRE(n >= 0 && n <= s->B, SMOLTTS_E_CAPACITY, "session_set_slot_align: %d entries, session holds %d slots", n, s->B);
-  for (int i = 0; i < n; ++i) {
-    ST_TRY(check_slot("session_set_slot_align", slots_host[i], s->B));
-    for (int j = 0; j < i; ++j)
-      ST_REQUIRE(slots_host[j] != slots_host[i], SMOLTTS_E_INVALID, "session_set_slot_align: slot %d listed twice", slots_host[i]);
-    ST_REQUIRE(t0_host[i] >= 0 && t0_host[i] <= s->max_seq && t1_host[i] >= 0 && t1_host[i] <= s->max_seq, SMOLTTS_E_INVALID,
-               "session_set_slot_align: slot %d: window [%d, %d) outside 0 .. %d", slots_host[i], t0_host[i], t1_host[i], s->max_seq);
-  }
   hipStream_t st = (hipStream_t)stream;
-  const size_t B = s->B;
-  ST_TRY(enter_slot_mode(s, st));
+  ST_TRY(upload_slot_entries(
+      s, "session_set_slot_align", slots_host, n, reinterpret_cast<int2*>(s->align_up), reinterpret_cast<int2*>(s->align_win), st,
+      [&](int i) -> int {
+        ST_REQUIRE(t0_host[i] >= 0 && t0_host[i] <= s->max_seq && t1_host[i] >= 0 && t1_host[i] <= s->max_seq, SMOLTTS_E_INVALID,
+                   "session_set_slot_align: slot %d: window [%d, %d) outside 0 .. %d", slots_host[i], t0_host[i], t1_host[i], s->max_seq);
+        return SMOLTTS_OK;
+      },
+      [&](int i, int2& en) {
+        en = make_int2(t0_host[i], t1_host[i]);
+        set_form_bits(s, slots_host[i], FORM_ALIGN, en.y > en.x ? FORM_ALIGN : 0);
+      }));
   if (n == 0) return SMOLTTS_OK;
-  const int k = s->slot_next;
-  s->slot_next = (k + 1) % STAGE_RING;
-  if (s->slot_ev_live[k]) ST_CHECK_HIP(hipEventSynchronize(s->slot_ev[k]));
-  int* h = reinterpret_cast<int*>(s->h_slot_stage + (size_t)k * ring_area_bytes(s) + slot_area_bytes(s) + filt_area_bytes(s) + len_part_bytes(s));
-  for (int i = 0; i < n; ++i) {
-    h[2 * i] = t0_host[i]; h[2 * i + 1] = t1_host[i];
-    h[2 * B + i] = slots_host[i];
-    s->h_align_on[slots_host[i]] = t1_host[i] > t0_host[i];
-  }
-  ST_CHECK_HIP(hipMemcpyAsync(s->align_up, h, align_area_bytes(s), hipMemcpyHostToDevice, st));
-  ST_CHECK_HIP(hipEventRecord(s->slot_ev[k], st));
-  s->slot_ev_live[k] = true;
-  hipLaunchKernelGGL(slot_scatter_kernel<int2>, dim3((n + 63) / 64), dim3(64), 0, st, n, reinterpret_cast<const int2*>(s->align_up),
-                     s->align_up + 2 * B, reinterpret_cast<int2*>(s->align_win));
-  ST_CHECK_HIP(hipGetLastError());
   const long per_slot = (long)s->max_frames * s->n_align;
   const unsigned gx = (unsigned)((per_slot + 255) / 256 < 64 ? (per_slot + 255) / 256 : 64);
-  hipLaunchKernelGGL(align_fill_kernel, dim3(gx, n), dim3(256), 0, st, s->align_up + 2 * B, per_slot, s->align_out);
+  hipLaunchKernelGGL(align_fill_kernel, dim3(gx, n), dim3(256), 0, st, s->align_up + 2 * s->B, per_slot, s->align_out);
   ST_CHECK_HIP(hipGetLastError());
   return SMOLTTS_OK;
 }
@@ -1692,16 +1642,13 @@ int smoltts_session_set_frames_per_graph(SmolttsSession* s, int32_t n, void* str
   ST_REQUIRE(s, SMOLTTS_E_INVALID, "session_set_frames_per_graph: null session");
   ST_REQUIRE(n >= 0 && n <= 16, SMOLTTS_E_INVALID, "session_set_frames_per_graph: %d frames per graph (0..16)", n);
   if (s->multi_env) n = s->multi_frames;  // SMOLTTS_FRAMES_PER_GRAPH wins (a profiler run pins one frame per graph)
-  if (n != s->multi_frames) drop_multi_graphs(s);
+  if (n != s->multi_frames) drop_graphs(s, 1u << GRAPH_MULTI);
   s->multi_frames = n;
   s->multi_fixed = n > 0;
   if (n > 0 && s->prefilled && graphs_enabled()) {
     hipStream_t st = (hipStream_t)stream;
     pick_form(s);
-    if (!s->graph_ready[s->form]) {
-      ST_TRY(capture_graph(st, &s->graph_exec[s->form], [&](hipStream_t cap) { return run_decode_frame(s, cap); }));
-      s->graph_ready[s->form] = true;
-    }
+    ST_TRY(ensure_graph(s, GRAPH_FRAME, st, [&](hipStream_t cap) { return run_decode_frame(s, cap); }));
     ST_TRY(ensure_multi_graph(s, n, st));
   }
   return SMOLTTS_OK;
@@ -1728,7 +1675,7 @@ int smoltts_session_set_slot_score(SmolttsSession* s, const int32_t* slots_host,
     ST_TRY(enter_slot_mode(s, nullptr));
     ST_CHECK_HIP(hipStreamSynchronize(nullptr));
   }
-  for (int i = 0; i < n; ++i) s->h_score_on[slots_host[i]] = on_host[i] != 0;
+  for (int i = 0; i < n; ++i) set_form_bits(s, slots_host[i], FORM_SCORE, on_host[i] != 0 ? FORM_SCORE : 0);
   return SMOLTTS_OK;
 }
 

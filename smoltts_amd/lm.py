@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -333,32 +333,34 @@ class LMSession(ClosesOnDel):
         check(self.lib.smoltts_session_set_sampling(self.handle, float(temp), float(fast_temp), float(min_p), int(seed) & (2**64 - 1)),
               "smoltts_session_set_sampling")
 
+    def _set_slot_table(self, fn: str, slots: Sequence[int], columns: Sequence[Tuple[type, Callable, Sequence]], mismatch: str,
+                        stream: bool = True) -> None:
+        """One per-slot table call of the C library: the slot list, its length, one array per ``(ctype, convert, values)`` column and
+        (``stream``) the current stream.  ``mismatch``: the ``ValueError`` of lists that are not one value per slot."""
+        n = len(slots)
+        if any(len(values) != n for _, _, values in columns):
+            raise ValueError(mismatch)
+        arrays = [(ctype * max(n, 1))(*[convert(x) for x in values]) for ctype, convert, values in [(C.c_int32, int, slots), *columns]]
+        check(getattr(self.lib, fn)(self.handle, arrays[0], n, *arrays[1:], *([current_stream_ptr()] if stream else [])), fn)
+
     def set_slot_sampling(self, slots: Sequence[int], temp: Sequence[float], fast_temp: Sequence[float], min_p: Sequence[float],
                           seed: Sequence[int]) -> None:
         """Per-slot sampling (slot mode, include/smoltts_hip.h): slot ``slots[i]`` samples its slow token at ``temp[i]`` and its
         depth codes at ``fast_temp[i]`` (<= 0: greedy) with the effective cut ``min_p[i]`` and the request key of ``seed[i]``.  The
         first call puts the session in slot mode for good (unlisted slots: greedy).  Queued on the current stream: the picks
         behind it on that stream use the new entries; the host does not wait for the stream."""
-        n = len(slots)
-        if not (len(temp) == len(fast_temp) == len(min_p) == len(seed) == n):
-            raise ValueError("slot sampling: one value per slot in every list")
-        check(self.lib.smoltts_session_set_slot_sampling(
-            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_float * max(n, 1))(*[float(t) for t in temp]),
-            (C.c_float * max(n, 1))(*[float(t) for t in fast_temp]), (C.c_float * max(n, 1))(*[float(p) for p in min_p]),
-            (C.c_uint64 * max(n, 1))(*[int(x) & (2**64 - 1) for x in seed]), current_stream_ptr()), "smoltts_session_set_slot_sampling")
+        self._set_slot_table("smoltts_session_set_slot_sampling", slots,
+                             [(C.c_float, float, temp), (C.c_float, float, fast_temp), (C.c_float, float, min_p),
+                              (C.c_uint64, lambda x: int(x) & (2**64 - 1), seed)], "slot sampling: one value per slot in every list")
 
     def set_slot_filters(self, slots: Sequence[int], top_p: Sequence[float], top_k: Sequence[int], penalty: Sequence[float],
                          window: Sequence[int]) -> None:
         """Per-slot filters of the sampled picks (``smoltts_session_set_slot_filters``): slot ``slots[i]`` keeps its ``top_k[i]``
         largest logits (0: off), then the ``top_p[i]`` nucleus (0 or 1: off), after the repetition penalty ``penalty[i]`` (0 or
         1: off) over the ids of its last ``window[i]`` frames.  Queued on the current stream like ``set_slot_sampling``."""
-        n = len(slots)
-        if not (len(top_p) == len(top_k) == len(penalty) == len(window) == n):
-            raise ValueError("slot filters: one value per slot in every list")
-        check(self.lib.smoltts_session_set_slot_filters(
-            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_float * max(n, 1))(*[float(p) for p in top_p]),
-            (C.c_int32 * max(n, 1))(*[int(k) for k in top_k]), (C.c_float * max(n, 1))(*[float(r) for r in penalty]),
-            (C.c_int32 * max(n, 1))(*[int(w) for w in window]), current_stream_ptr()), "smoltts_session_set_slot_filters")
+        self._set_slot_table("smoltts_session_set_slot_filters", slots,
+                             [(C.c_float, float, top_p), (C.c_int32, int, top_k), (C.c_float, float, penalty), (C.c_int32, int, window)],
+                             "slot filters: one value per slot in every list")
         for b, p, k, r, w in zip(slots, top_p, top_k, penalty, window):
             (self.filtered_slots.add if (0 < p < 1 or k > 0 or (r > 1 and w > 0)) else self.filtered_slots.discard)(int(b))
 
@@ -367,12 +369,8 @@ class LMSession(ClosesOnDel):
         than ``min_frames[i]`` frames its ``<|im_end|>`` column cannot be picked (0: off), and ``eos_bias[i]`` is added to that
         logit (0: off) -- for greedy and sampled slow tokens alike (``sampling.length_patch``).  Queued on the current stream like
         ``set_slot_sampling``; a new tenant without the option needs an off entry, or it inherits its predecessor's."""
-        n = len(slots)
-        if not (len(min_frames) == len(eos_bias) == n):
-            raise ValueError("slot length: one value per slot in every list")
-        check(self.lib.smoltts_session_set_slot_length(
-            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_int32 * max(n, 1))(*[int(m) for m in min_frames]),
-            (C.c_float * max(n, 1))(*[float(x) for x in eos_bias]), current_stream_ptr()), "smoltts_session_set_slot_length")
+        self._set_slot_table("smoltts_session_set_slot_length", slots, [(C.c_int32, int, min_frames), (C.c_float, float, eos_bias)],
+                             "slot length: one value per slot in every list")
         for b, m, x in zip(slots, min_frames, eos_bias):
             (self.length_slots.add if (m > 0 or x != 0) else self.length_slots.discard)(int(b))
 
@@ -380,12 +378,8 @@ class LMSession(ClosesOnDel):
         """Score the slow token of slot ``slots[i]`` where ``on[i]`` (``smoltts_session_set_slot_score``): ``logprobs[slot][f]`` then
         receives, with frame f, the log-probability at temperature 1 of the id the slot emitted (``sampling.pick_logprob``).  Host
         flags only; a new tenant without the option needs an off flag, or the session keeps scoring for nobody."""
-        n = len(slots)
-        if len(on) != n:
-            raise ValueError("slot score: one flag per slot")
-        check(self.lib.smoltts_session_set_slot_score(
-            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_int32 * max(n, 1))(*[1 if x else 0 for x in on])),
-            "smoltts_session_set_slot_score")
+        self._set_slot_table("smoltts_session_set_slot_score", slots, [(C.c_int32, lambda x: 1 if x else 0, on)],
+                             "slot score: one flag per slot", stream=False)
         for b, x in zip(slots, on):
             (self.scored_slots.add if x else self.scored_slots.discard)(int(b))
 
@@ -422,12 +416,8 @@ class LMSession(ClosesOnDel):
         """The text window ``[t0[i], t1[i])`` (prompt positions) of slot ``slots[i]``; ``t1 <= t0`` switches its measurement off.
         The slot's rows are reset to "not measured".  Queued on the current stream like ``set_slot_sampling``; a new tenant
         without the option needs an off entry, or it inherits its predecessor's window."""
-        n = len(slots)
-        if not (len(t0) == len(t1) == n):
-            raise ValueError("slot align: one window per slot")
-        check(self.lib.smoltts_session_set_slot_align(
-            self.handle, (C.c_int32 * max(n, 1))(*[int(b) for b in slots]), n, (C.c_int32 * max(n, 1))(*[int(x) for x in t0]),
-            (C.c_int32 * max(n, 1))(*[int(x) for x in t1]), current_stream_ptr()), "smoltts_session_set_slot_align")
+        self._set_slot_table("smoltts_session_set_slot_align", slots, [(C.c_int32, int, t0), (C.c_int32, int, t1)],
+                             "slot align: one window per slot")
         for b, a, z in zip(slots, t0, t1):
             (self.align_slots.add if z > a else self.align_slots.discard)(int(b))
 
