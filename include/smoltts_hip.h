@@ -891,6 +891,53 @@ int smoltts_watermark_embed(SmolttsWatermark* s, const float* pcm_dev, int32_t n
  * sub-blocks, the open and the previous block's gain, the slot's gain.  Synchronises the stream. */
 int smoltts_watermark_slot_state(SmolttsWatermark* s, int32_t slot, int64_t* ints_host, double* values_host, void* stream);
 
+/* ------------------------------------------------------------------------------ Limiter
+ * A look-ahead peak limiter on the codec's 24 kHz fp32 PCM, the last float stage (smoltts_amd/csrc/limiter.hip, DESIGN.md section
+ * 22; the numpy model, reproduced bit for bit, is smoltts_amd/limiter.py).  The peak of a sample is the largest magnitude of
+ * itself and of three 12-tap interpolated values between it and the next one; the required gain is ceiling / peak where the
+ * peak passes the ceiling, else 1; a sample's gain is the smaller of its own required gain and the mean of 121 minima of the
+ * required gain, each over 1200 samples of hold and 120 of look-ahead.  A slot holds back 126 samples; a stream's end flushes
+ * them.  Where nothing near passes the ceiling the gain is exactly 1 and the samples leave unchanged.  The output does not
+ * depend on how a stream is cut into calls. */
+typedef struct SmolttsLimiter SmolttsLimiter;
+
+/* Device slab of a limiter stage for max_batch slots (256-byte aligned, caller-owned): two copies of each slot's state (126
+ * samples, 1440 required gains, the position, the ceiling, the smallest gain so far) and the stage's table.  tables_host:
+ * smoltts_limiter_table_doubles() doubles (limiter.packed: the three phases' 12 taps); the device designs nothing.  Every slot
+ * starts off; create clears the slab and uploads the table synchronously. */
+size_t smoltts_limiter_bytes(int32_t max_batch);
+int32_t smoltts_limiter_table_doubles(void);
+int smoltts_limiter_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, const double* tables_host, int32_t n_tables,
+                           SmolttsLimiter** out);
+void smoltts_limiter_destroy(SmolttsLimiter* l);
+/* Output samples per row that a call of n_in input samples needs (n_in + 126: the held samples a stream's end releases); 0 when
+ * n_in is negative or above 61440, the most one call takes. */
+size_t smoltts_limiter_out_samples(int32_t n_in);
+
+/* Start a new stream in each listed slot (host arrays) under its ceiling 10^(peak_limit_db / 20) (0 switches the slot off; at
+ * most 1).  The other slots continue.  Stream-ordered. */
+int smoltts_limiter_reset_slots(SmolttsLimiter* l, const int32_t* slots_host, const double* ceiling_host, int32_t n_slots,
+                                void* stream);
+
+/* One launch for slots [0, batch): slot b consumes valid_in_dev[b] (clamped to [0, n_in]; NULL = n_in) samples of pcm_dev float
+ * [batch][pcm_stride]; last_dev[b] nonzero (last_dev may be NULL) ends the slot's stream with them.  Slot b writes the samples
+ * that became final in this call to out_dev float [batch][out_stride] (out_stride >= smoltts_limiter_out_samples(n_in)) and
+ * their number to counts_dev[b]: so far max(0, consumed - 126) in total, and all of them once the stream has ended.  Slots that
+ * are off write 0 and leave their rows alone, as do slots whose stream has ended.  Calls on one stage must be ordered on one
+ * stream. */
+int smoltts_limiter_chunk(SmolttsLimiter* l, const float* pcm_dev, int64_t pcm_stride, int32_t batch, int32_t n_in,
+                          const int32_t* valid_in_dev, const int32_t* last_dev, float* out_dev, int64_t out_stride,
+                          int32_t* counts_dev, void* stream);
+
+/* A whole utterance of n samples limited under `ceiling` (0 < ceiling <= 1) in one launch (no slot involved): n samples to
+ * out_dev, the samples a stream gives, and result_dev[0] = the smallest gain applied (1 when nothing was limited). */
+int smoltts_limiter_apply(SmolttsLimiter* l, const float* pcm_dev, int32_t n, double ceiling, float* out_dev, double* result_dev,
+                          void* stream);
+
+/* Tests and tools: slot's state; ints_host[3] = pos, on, ended; values_host[1568] = the ceiling, the smallest gain so far, the
+ * 1440 required gains of samples pos - 1446 .. pos - 7, the 126 samples pos - 126 .. pos - 1.  Synchronises the stream. */
+int smoltts_limiter_slot_state(SmolttsLimiter* l, int32_t slot, int64_t* ints_host, double* values_host, void* stream);
+
 /* --------------------------------------------------------------- operator-level test entry points */
 enum {  /* prologue applied to the activation operand */
   SMOLTTS_PRO_NONE = 0,

@@ -80,6 +80,7 @@ class SmolTTS:
         self.last_trimmed_s = 0.0  # seconds of silence the last blocking call trimmed (trim_silence / max_pause_s)
         self.last_segments: list = []  # per segment of the last segmented call: text, prompt, codes, seed, frames
         self.last_loudness_gain_db = None  # gain of the last call that was given loudness=
+        self.last_peak_reduction_db = None  # -20 log10(min g) of the last call that was given peak_limit_db= (0.0: never limited)
         self.last_stats: dict = {}  # timing of the last generate_codes / __call__ (BatchGenerator.stats + codec_ms)
         # why the last call's utterance ended: "stop" (its last slow id is <|im_end|>) or "length" (the frame cap or a full
         # context); a segmented call is "length" if any segment was.  last_finish_reasons: one per input of generate_codes
@@ -212,7 +213,8 @@ class SmolTTS:
     def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None,
                  speed: Optional[float] = None, segment=False, loudness: Optional[float] = None, watermark: Optional[bool] = None,
                  trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-                 silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None):
+                 silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
+                 peak_limit_db: Optional[float] = None):
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
         (per-request temperature / min_p / seed, as in ``generate_codes``).  ``speed`` (0.25 to 4.0; None / 1.0: unchanged):
         the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
@@ -232,13 +234,18 @@ class SmolTTS:
         seconds, read from where the chosen heads of the slow attention look while each frame is produced.  The option changes no
         id: with ``sampling=`` (its seed) or greedy settings the audio is the one the call returns without it.  A call without
         ``sampling=`` whose settings sample runs in the per-request mode here (the measurement exists only there) and draws a
-        request seed, so its audio is another draw than the session-wide one; ``last_sampling`` carries the seed that replays it."""
+        request seed, so its audio is another draw than the session-wide one; ``last_sampling`` carries the seed that replays it.
+        ``peak_limit_db`` (a ceiling in dBFS, -12 to 0; None: none): the utterance goes through the look-ahead peak limiter whole
+        on the GPU, last of all: behind the seam join, the loudness gain, the stretch and the watermark (``limiter.py``);
+        ``last_peak_reduction_db`` is ``-20 log10`` of the smallest gain applied, 0.0 when nothing was limited.  With a
+        ``loudness`` as well, the loudness gain is not capped by the peak: the limiter takes the peaks down instead."""
         from .request import parse_request
 
         req = parse_request(input, speed=speed, segment=segment, loudness=loudness, watermark=watermark, trim_silence=trim_silence,
                             max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db,
-                            timestamps=timestamps)  # a bad request is refused before any work
+                            timestamps=timestamps, peak_limit_db=peak_limit_db)  # a bad request is refused before any work
         self.last_alignment = None
+        self.last_peak_reduction_db = None
         if req.timestamps:
             if not self.alignment_heads:
                 raise ValueError("timestamps need alignment_heads: rank a checkpoint's heads with `python -m smoltts_amd.align rank`")
@@ -278,7 +285,7 @@ class SmolTTS:
             from .stages import loudness_normalize
             from .loudness import gain_db
 
-            pcm, g = loudness_normalize(pcm, req.loudness, self.lm.device, with_gain=True)
+            pcm, g = loudness_normalize(pcm, req.loudness, self.lm.device, with_gain=True, cap=req.peak_limit_db is None)
             self.last_loudness_gain_db = gain_db(g)
         if req.speed_q is not None:
             from .stages import stretch_pcm
@@ -288,6 +295,10 @@ class SmolTTS:
             from .stages import watermark_embed
 
             pcm = watermark_embed(pcm, marked, self.lm.device)
+        if req.peak_limit_db is not None:
+            from .stages import peak_limit
+
+            pcm, self.last_peak_reduction_db = peak_limit(pcm, req.peak_limit_db, self.lm.device)
         if req.timestamps:
             from .align import align
 
@@ -418,7 +429,7 @@ class SmolTTS:
                speed: Optional[float] = None, container: Optional[str] = None, segment=False,
                loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
                watermark: Optional[bool] = None, trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-               silence_threshold_db: Optional[float] = None) -> Iterator["np.ndarray"]:
+               silence_threshold_db: Optional[float] = None, peak_limit_db: Optional[float] = None) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -446,6 +457,10 @@ class SmolTTS:
         ``trim_silence`` / ``max_pause_s`` / ``silence_threshold_db`` (as in ``__call__``): the stream is trimmed on the GPU
         first of its stages, segment by segment in front of the seam; a non-silent block leaves with the frame that completes
         it, silence is held back until it is known whether it is kept (``trim.TrimState``).
+        ``peak_limit_db`` (as in ``__call__``): the stream is peak-limited on the GPU last of the float stages, behind the
+        watermark and in front of the conversion and the framing; the limiter holds back 126 samples (5.25 ms), which leave
+        with the stream's last chunk, and its state runs on across the seams of a segmented stream (``limiter.StreamState``).
+        A stream reports no reduction, and its loudness rule is the causal one, unchanged.
         ``input`` may be an iterator or generator of strings (or UTF-8 ``bytes``, cut anywhere) in place of a string: text that is
         still being written.  It implies ``segment=True`` (or the options given), is cut by ``longform.IncrementalSplitter``
         and spoken segment after segment while the text is pulled: before segment k starts, just enough text is pulled to have
@@ -463,11 +478,13 @@ class SmolTTS:
         if not isinstance(input, (str, bytes)):
             yield from self._stream_incremental(iter(input), voice if voice is not None else "0", generation_settings, overlap,
                                                 reference_upsample, output_format, sampling, speed, container, segment, loudness,
-                                                loudness_start_gain_db, watermark, trim_silence, max_pause_s, silence_threshold_db)
+                                                loudness_start_gain_db, watermark, trim_silence, max_pause_s, silence_threshold_db,
+                                                peak_limit_db)
             return
         req = parse_request(input, stream=True, output_format=output_format, speed=speed, container=container, segment=segment,
                             loudness=loudness, loudness_start_gain_db=loudness_start_gain_db, watermark=watermark,
-                            trim_silence=trim_silence, max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db)
+                            trim_silence=trim_silence, max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db,
+                            peak_limit_db=peak_limit_db)
         marked = self._marks(req.watermark)
         voice = voice if voice is not None else "0"
         if req.plan is not None:
@@ -484,7 +501,7 @@ class SmolTTS:
         try:
             yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=req.output_format,
                                   speed_q=req.speed_q, container=req.container, loudness=req.loudness,
-                                  start_gain_db=req.start_gain_db, watermark=marked, trim=req.trim_route)
+                                  start_gain_db=req.start_gain_db, watermark=marked, trim=req.trim_route, ceiling=req.ceiling)
             self.last_finish_reason = self._stream_reason(sess)
             if self.last_sampling is not None and self.last_sampling[0].scored:
                 from .config import mean_logprob
@@ -563,14 +580,14 @@ class SmolTTS:
 
     def _stream_incremental(self, texts, voice, generation_settings, overlap, reference_upsample, output_format, sampling, speed,
                             container, segment, loudness, loudness_start_gain_db, watermark=None, trim_silence=None, max_pause_s=None,
-                            silence_threshold_db=None):
+                            silence_threshold_db=None, peak_limit_db=None):
         """``stream`` of a text that ``texts`` yields in pieces: the segmented stream of a plan that grows as the text is pulled."""
         from .longform import FLUSH, GrowingPlan, IncrementalSplitter, segment_options
         from .request import parse_request
 
         req = parse_request("", stream=True, output_format=output_format, speed=speed, container=container, loudness=loudness,
                             loudness_start_gain_db=loudness_start_gain_db, watermark=watermark, trim_silence=trim_silence,
-                            max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db)
+                            max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db, peak_limit_db=peak_limit_db)
         marked = self._marks(req.watermark)
         opts = segment_options(segment or True)
         plan, splitter = GrowingPlan(opts), IncrementalSplitter(opts)
@@ -610,7 +627,8 @@ class SmolTTS:
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
             conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container], [req.loudness], [req.start_gain_db],
-                             [marked is not None], trim=None if req.trim_route is None else [req.trim_route])
+                             [marked is not None], trim=None if req.trim_route is None else [req.trim_route],
+                             limit=[req.ceiling] if req.ceiling else None)
             segments = self._segments(plan, voice, None, generation_settings, sampling)
             for k in range(1 << 30):
                 if pull(k) if pull is not None else k < len(plan.segs):

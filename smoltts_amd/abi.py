@@ -271,6 +271,15 @@ SIGNATURES = {
     "smoltts_watermark_chunk": (INT, "p p q i i p p q p p"),
     "smoltts_watermark_embed": (INT, "p p i d p p"),
     "smoltts_watermark_slot_state": (INT, "p i p p p"),
+    "smoltts_limiter_bytes": (SIZE, "i"),
+    "smoltts_limiter_table_doubles": (I32, ""),
+    "smoltts_limiter_create": (INT, "p z i p i p*"),
+    "smoltts_limiter_destroy": (None, "p"),
+    "smoltts_limiter_out_samples": (SIZE, "i"),
+    "smoltts_limiter_reset_slots": (INT, "p p p i p"),
+    "smoltts_limiter_chunk": (INT, "p p q i i p p p q p p"),
+    "smoltts_limiter_apply": (INT, "p p i d p p p"),
+    "smoltts_limiter_slot_state": (INT, "p i p p p"),
     "smoltts_k_gemm": (INT, "GemmArgs* p"),
     "smoltts_gemm3_attn_fusable": (INT, "i i i"),
     "smoltts_k_gemm3": (INT, "Gemm3Args* p"),

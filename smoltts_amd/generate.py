@@ -276,7 +276,7 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
                overlap: bool = True, output_format: Optional[str] = None, speed_q: Optional[int] = None,
                container: Optional[str] = None, conv: Optional[StreamConverter] = None, final: bool = True,
                loudness: Optional[float] = None, start_gain_db: Optional[float] = None, watermark=None,
-               trim: Optional[tuple] = None) -> Iterator[np.ndarray]:
+               trim: Optional[tuple] = None, ceiling: Optional[float] = None) -> Iterator[np.ndarray]:
     """One utterance in slot 0 of ``session`` -> one 1920-sample float32 chunk per generated frame, as the reference's
     ``SmolTTS.stream`` yields them (mlx_inference/src/smoltts_mlx/__init__.py:83-95: every frame of ``SingleBatchGenerator`` through
     ``codec.decode_step``), the terminating ``<|im_end|>`` frame included.
@@ -314,6 +314,11 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     goes through the trim stage (``stages.SilenceTrimmer``) first of all; the stream is one segment, whose end is derived on the
     device as for a speed.  A frame that completes no block that is kept yields nothing.
 
+    ``ceiling`` (the peak limiter's ceiling as an amplitude, ``SpeechOptions.ceiling``; None or 0: no launch): every frame's PCM
+    goes through the limiter (``stages.PeakLimiter``), the last float stage: behind the watermark, in front of the conversion
+    and the framing.  The slot holds back 126 samples, which leave with the end of the stream, derived on the device as for a
+    speed.
+
     ``conv``: the utterance is one segment of a long text (``longform``): the caller's ``StreamConverter(seam=True)``, with the
     stream's stages started in slot 0 and this segment opened (``start_segments``), converts it and is not closed here; the
     format, speed and container arguments are then ignored.  The end of the utterance, derived on the device, is the seam's end
@@ -338,7 +343,7 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
         msession.reset()
         if own:
             conv.reset_slots([0], [output_format], [speed_q], [container], [loudness], [start_gain_db], [watermark is not None],
-                             trim=None if trim is None else [trim])
+                             trim=None if trim is None else [trim], limit=[ceiling] if ceiling else None)
     converted = conv.converts(0)
     ends_on_device, segmented = conv.ends([0])  # a stage must see the end of the stream / of the segment
     with torch.cuda.stream(lm_stream):

@@ -278,24 +278,25 @@ def measure(x: np.ndarray) -> Tuple[float, float]:
     return lufs_of_power(p), peak
 
 
-def static_gain(target: float, power: float, peak: float) -> float:
-    """The blocking rule's gain from a measured power and peak (1 when nothing was measured)."""
+def static_gain(target: float, power: float, peak: float, cap: bool = True) -> float:
+    """The blocking rule's gain from a measured power and peak (1 when nothing was measured).  ``cap`` false: the gain that
+    reaches the target whatever the peak, for an utterance that a peak limiter (limiter.py) finishes."""
     if not power > 0:
         return 1.0
     g = float(10.0 ** ((float(target) - lufs_of_power(power)) / 20.0))
-    return min(g, tables().ceiling / peak) if peak > 0 else g
+    return min(g, tables().ceiling / peak) if cap and peak > 0 else g
 
 
 def apply_gain(x: np.ndarray, g: float) -> np.ndarray:
     return (np.asarray(x, np.float32).astype(np.float64) * np.float64(g)).astype(np.float32)
 
 
-def normalize(x: np.ndarray, target: float) -> Tuple[np.ndarray, float]:
+def normalize(x: np.ndarray, target: float, cap: bool = True) -> Tuple[np.ndarray, float]:
     """The blocking rule: (the utterance at ``target`` LUFS or at peak c, the gain applied).  Silence and utterances shorter
-    than a block come back unchanged (gain 1)."""
+    than a block come back unchanged (gain 1).  ``cap`` false: at ``target`` whatever the peak (``static_gain``)."""
     x = np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1))
     p, peak = measure_power(x)
-    g = static_gain(target, p, peak)
+    g = static_gain(target, p, peak, cap)
     return (x.copy() if g == 1.0 else apply_gain(x, g)), g
 
 

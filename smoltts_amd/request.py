@@ -7,6 +7,7 @@ from typing import Optional, Tuple
 
 from .formats import ENC_OFF, check_container, parse_stream_format
 from .longform import SegmentOptions, SegmentPlan, segment_options
+from .limiter import ceiling_of_db, check_peak_limit
 from .loudness import check_start_gain, check_target
 from .trim import pause_blocks, threshold
 from .tsm import parse_speed
@@ -29,6 +30,12 @@ class SpeechOptions:
     pause_blocks: int = 0             # max_pause_s in blocks (0: no cap)
     silence_thr: float = float(threshold(None))   # silence_threshold_db as a float32 amplitude
     timestamps: bool = False          # character timestamps from the slow attention (align.py); blocking requests only
+    peak_limit_db: Optional[float] = None  # the ceiling of the peak limiter in dBFS (limiter.py), None: no limiter
+
+    @property
+    def ceiling(self) -> float:
+        """The limiter's ceiling as an amplitude, 10^(peak_limit_db / 20); 0.0 without one (``SlotRoute.ceiling``)."""
+        return 0.0 if self.peak_limit_db is None else ceiling_of_db(self.peak_limit_db)
 
     @property
     def trims(self) -> bool:
@@ -46,7 +53,7 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
                   loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
                   trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
                   silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
-                  pieces: bool = False) -> SpeechOptions:
+                  pieces: bool = False, peak_limit_db: Optional[float] = None) -> SpeechOptions:
     """A request's options checked and normalised; ``ValueError`` for anything a front end refuses.  ``output_format`` and
     ``container`` apply to streaming requests only, as does ``loudness_start_gain_db``, which needs a ``loudness``.  ``watermark``: true, false, or None for the
     front end's own policy (the key and the strength are the front end's: one key per stage).  ``trim_silence`` (true, false or
@@ -54,8 +61,11 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
     one of the other two) are the trim stage's (trim.py).  ``timestamps`` (true, false or None: false): character timestamps
     (align.py), for blocking requests of one utterance whose frames keep their place in the output: refused with ``segment``,
     with ``trim_silence`` / ``max_pause_s`` (the seam and the trim stage cut samples where the audio says so), with a stream, and
-    with text fed in pieces (``pieces``: the front end's text is an iterator)."""
+    with text fed in pieces (``pieces``: the front end's text is an iterator).  ``peak_limit_db`` (-12 to 0 dBFS, None: none):
+    the ceiling of the peak limiter (limiter.py), the last float stage; it goes with every other option, because the stage
+    copies samples one to one and only delays them."""
     speed_q = parse_speed(speed)
+    peak_limit_db = check_peak_limit(peak_limit_db)
     if output_format is not None:
         if not stream:
             raise ValueError("output_format applies to streaming requests")
@@ -95,4 +105,4 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
                          check_start_gain(loudness_start_gain_db), watermark, bool(trim_silence),
                          None if max_pause_s is None else float(max_pause_s),
                          None if silence_threshold_db is None else float(silence_threshold_db), blocks,
-                         float(threshold(silence_threshold_db)), bool(timestamps))
+                         float(threshold(silence_threshold_db)), bool(timestamps), peak_limit_db)

@@ -13,7 +13,7 @@ from .abi import FLAC_F32, FLAC_OFF, FLAC_S16, SEAM_FINAL, SEAM_FIRST, SEAM_OFF
 from .device import upload
 from .formats import ENC_OFF, check_container, parse_stream_format
 from .seam import THRESH
-from .stages import FlacEncoder, LoudnessNormalizer, Resampler, SeamJoiner, SilenceTrimmer, TimeStretcher, Watermarker
+from .stages import FlacEncoder, LoudnessNormalizer, PeakLimiter, Resampler, SeamJoiner, SilenceTrimmer, TimeStretcher, Watermarker
 from .tsm import out_bound
 
 
@@ -23,6 +23,9 @@ PASS_ORDER = ("seam", "loudness", "stretch", "watermark", "resample", "flac")  #
 FLOAT_STAGES = ("seam", "loudness", "stretch", "watermark")  # fp32 in, fp32 out: the stages behind read their rows
 TRIM_ORDER = ("trim",) + PASS_ORDER  # PASS_ORDER behind the silence trim: what a pass is planned by
 TRIM_FLOAT_STAGES = ("trim",) + FLOAT_STAGES
+# TRIM_ORDER with the peak limiter, the last float stage: behind the watermark, in front of the conversion and the framing
+LIMIT_ORDER = ("trim",) + FLOAT_STAGES + ("limit", "resample", "flac")
+LIMIT_FLOAT_STAGES = TRIM_FLOAT_STAGES + ("limit",)
 
 
 @dataclass(frozen=True)
@@ -40,6 +43,7 @@ class SlotRoute:
     loudness: Optional[float] = None  # target in LUFS (None: the slot never enters the loudness stage)
     start_gain_db: float = 0.0        # its stream's first knot
     watermark_gain: float = 0.0       # 10^(strength_db / 20) (0: the slot never enters the watermark stage)
+    ceiling: float = 0.0              # 10^(peak_limit_db / 20) (0: the slot never enters the limiter stage)
     trim: bool = False                # its leading and trailing silence is trimmed
     pause_blocks: int = 0             # its pauses are capped at this many blocks (0: not); neither: the slot never enters the trim stage
     thr: float = float(THRESH)        # the silence threshold of its trim stage
@@ -48,8 +52,8 @@ class SlotRoute:
     def stages(self) -> Tuple[str, ...]:
         """The stages the slot goes through, in launch order."""
         on = (self.trims, self.segmented, self.loudness is not None, self.speed_q != 65536, self.watermark_gain > 0.0,
-              self.enc != ENC_OFF, self.flac)
-        return tuple(s for s, o in zip(TRIM_ORDER, on) if o)
+              self.ceiling > 0.0, self.enc != ENC_OFF, self.flac)
+        return tuple(s for s, o in zip(LIMIT_ORDER, on) if o)
 
     @property
     def trims(self) -> bool:
@@ -59,7 +63,7 @@ class SlotRoute:
 class PassPlan(NamedTuple):
     stages: List[str]                 # the stages to launch, in order
     rows: Dict[str, List[int]]        # the live slots each of them serves
-    through: Dict[str, List[int]]     # float stage (trim, seam, loudness, stretch, watermark) -> the live slots it does not serve that a later stage does
+    through: Dict[str, List[int]]     # float stage (trim, seam, loudness, stretch, watermark, limit) -> the live slots it does not serve that a later stage does
     source: Dict[int, Optional[str]]  # live slot -> the last stage it goes through (None: its codec rows are its output)
     host: List[str]                   # the stages whose outputs are copied to the host: the sources of the live slots
     routes: Dict[int, SlotRoute]      # live slot -> its route when planned
@@ -67,8 +71,8 @@ class PassPlan(NamedTuple):
 
 def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
     """The plan of one converter pass over the live slots' routes (``{slot: SlotRoute}``, in slot order); no device involved."""
-    rows = {s: [] for s in TRIM_ORDER}
-    through = {s: [] for s in TRIM_FLOAT_STAGES}
+    rows = {s: [] for s in LIMIT_ORDER}
+    through = {s: [] for s in LIMIT_FLOAT_STAGES}
     source = {}
     for b, r in routes.items():
         path = r.stages
@@ -76,18 +80,19 @@ def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
         for s in path:
             rows[s].append(b)
         for s in through:
-            if path and s not in path and TRIM_ORDER.index(path[-1]) > TRIM_ORDER.index(s):
+            if path and s not in path and LIMIT_ORDER.index(path[-1]) > LIMIT_ORDER.index(s):
                 through[s].append(b)
-    stages = [s for s in TRIM_ORDER if rows[s]]
+    stages = [s for s in LIMIT_ORDER if rows[s]]
     return PassPlan(stages, {s: rows[s] for s in stages}, {s: through[s] for s in through if rows[s]}, source,
                     [s for s in stages if s in source.values()], routes)
 
 
 class StreamConverter:
-    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``TRIM_ORDER``): a
+    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``LIMIT_ORDER``): a
     slot that trims silence goes through the trim stage first (``SilenceTrimmer``), segment by segment, a segmented slot (``start_segments``) is joined by the seam stage (``SeamJoiner``), a slot with a speed is time-stretched
     (``TimeStretcher``), a marked slot gets the watermark of the converter's key last of the float stages (``Watermarker``:
-    behind the stretch, so that a speed does not rescale the chips), a slot with an output format is converted (``Resampler``), and a slot with a FLAC container is framed
+    behind the stretch, so that a speed does not rescale the chips), a slot with a ceiling is peak-limited behind that
+    (``PeakLimiter``: the last float stage, so that nothing behind it can raise a peak again), a slot with an output format is converted (``Resampler``), and a slot with a FLAC container is framed
     (``FlacEncoder``, from the resampler's int16, or from the float32 at 24 kHz); each stage reads the output of the one in
     front, and the state of the stages behind the seam carries from segment to segment.  Each stage is created the first time
     a slot needs it (``seam``: the seam stage at once).  ``n_in``: codec samples per slot and call."""
@@ -102,18 +107,20 @@ class StreamConverter:
         self.sj: Optional[SeamJoiner] = SeamJoiner(device, max_batch) if seam else None
         self.ln: Optional[LoudnessNormalizer] = None
         self.tr: Optional[SilenceTrimmer] = None
+        self.lim: Optional[PeakLimiter] = None
         self.routes = [SlotRoute()] * max_batch
         self._plan: Optional[PassPlan] = None  # the last pass's plan
 
     def reset_slots(self, slots: Sequence[int], formats: Sequence[Optional[str]], speed_q: Sequence[Optional[int]],
                     containers: Optional[Sequence[Optional[str]]] = None, loudness: Optional[Sequence[Optional[float]]] = None,
                     start_gain_db: Optional[Sequence[Optional[float]]] = None, watermark: Optional[Sequence[bool]] = None,
-                    trim: Optional[Sequence[Optional[tuple]]] = None) -> None:
+                    trim: Optional[Sequence[Optional[tuple]]] = None, limit: Optional[Sequence[Optional[float]]] = None) -> None:
         """Start new streams in ``slots`` on the current stream: ``formats[i]`` an ``output_format`` (None / ``pcm_24000``:
         float32), ``speed_q[i]`` a Q16 speed (None / 65536: none), ``containers[i]`` None or ``"flac"`` (FLAC frames of the
         slot's 16-bit samples at its rate), ``loudness[i]`` a target in LUFS (None: none) reached from ``start_gain_db[i]``,
         ``watermark[i]`` true for a slot that gets the converter's watermark, ``trim[i]`` None or (trim the ends, the pause cap
-        in blocks, the threshold or None) of a slot that trims silence.  A slot with none of them is switched off."""
+        in blocks, the threshold or None) of a slot that trims silence, ``limit[i]`` the ceiling of a slot's peak limiter as
+        an amplitude in (0, 1] (``SpeechOptions.ceiling``; None / 0: none).  A slot with none of them is switched off."""
         if not slots:
             return
         formats = [f or "pcm_24000" for f in formats]
@@ -121,12 +128,13 @@ class StreamConverter:
         none = [None] * len(slots)
         if watermark is not None and any(watermark) and self.watermark is None:
             raise ValueError("a slot asks for a watermark, and the converter has no key")
-        for b, f, q, c, lt, sg, wm, tr in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none,
-                                              watermark or none, trim or none):
+        for b, f, q, c, lt, sg, wm, tr, lim in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none,
+                                                   watermark or none, trim or none, limit or none):
             rate, enc = parse_stream_format(f)
             flac = check_container(c, f) is not None
             routes.append(SlotRoute(rate, enc, q or 65536, flac, segmented=False, gen=self.routes[b].gen + 1, head_owed=flac,
                                     loudness=lt, start_gain_db=sg or 0.0, watermark_gain=self.watermark.gain if wm else 0.0,
+                                    ceiling=float(lim or 0.0),
                                     **({} if tr is None else {"trim": bool(tr[0]), "pause_blocks": int(tr[1]),
                                                               "thr": float(THRESH if tr[2] is None else tr[2])})))
         if self.tr is None and any(r.trims for r in routes):
@@ -142,6 +150,10 @@ class StreamConverter:
             self.wm = Watermarker(self.device, self.B, self.watermark)
         if self.wm is not None:
             self.wm.reset_slots(slots, [r.watermark_gain for r in routes])
+        if self.lim is None and any(r.ceiling > 0.0 for r in routes):
+            self.lim = PeakLimiter(self.device, self.B)
+        if self.lim is not None:
+            self.lim.reset_slots(slots, [r.ceiling for r in routes])
         if self.rs is None and any(r.enc != ENC_OFF for r in routes):
             self.rs = Resampler(self.device, self.B, out_bound(self.n_in))
         if self.ts is None and any(r.speed_q != 65536 for r in routes):
@@ -187,10 +199,10 @@ class StreamConverter:
         return p
 
     def ends(self, slots: Sequence[int]):
-        """The end markers a pass over ``slots`` needs: (``last``: some slot has a speed, FLAC, segments or a trim; ``seg_end``:
-        some slot has segments or a trim)."""
+        """The end markers a pass over ``slots`` needs: (``last``: some slot has a speed, FLAC, segments, a trim or a limiter;
+        ``seg_end``: some slot has segments or a trim)."""
         stages = self.plan(slots).stages
-        return any(s in stages for s in ("trim", "seam", "stretch", "flac")), "seam" in stages or "trim" in stages
+        return any(s in stages for s in ("trim", "seam", "stretch", "limit", "flac")), "seam" in stages or "trim" in stages
 
     def _through(self, plan: PassPlan, stage: str, out: torch.Tensor, counts: torch.Tensor, pcm: torch.Tensor, n_in: int,
                  valid: torch.Tensor) -> torch.Tensor:
@@ -236,6 +248,10 @@ class StreamConverter:
             out, counts = outs["watermark"] = self.wm.new_outputs(batch, n_in)
             self.wm.chunk(pcm, n_in, out, counts, valid=valid)
             valid, pcm, n_in = self._through(plan, "watermark", out, counts, pcm, n_in, valid), out, out.shape[1]
+        if "limit" in plan.stages:
+            out, counts = outs["limit"] = self.lim.new_outputs(batch, n_in)
+            self.lim.run(pcm, n_in, out, counts, valid, last)
+            valid, pcm, n_in = self._through(plan, "limit", out, counts, pcm, n_in, valid), out, out.shape[1]
         if "resample" in plan.stages:
             out, counts = outs["resample"] = self.rs.new_outputs(batch, n_in)
             self.rs.chunk(pcm, n_in, out, counts, valid=valid)
@@ -246,10 +262,10 @@ class StreamConverter:
         return StreamPass(self, {s: outs[s] for s in plan.host}, plan)
 
     def close(self):
-        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln, self.wm, self.tr):
+        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln, self.wm, self.tr, self.lim):
             if stage is not None:
                 stage.close()
-        self.rs = self.ts = self.fl = self.sj = self.ln = self.wm = self.tr = None
+        self.rs = self.ts = self.fl = self.sj = self.ln = self.wm = self.tr = self.lim = None
 
 
 class StreamPass:
@@ -273,7 +289,7 @@ class StreamPass:
 
     def chunk(self, b: int, last: bool) -> np.ndarray:
         """Slot ``b``'s chunk from its source stage: its FLAC frames as uint8 (behind the stream header on the stream's first
-        chunk), its converted samples (with the resampler's tail when ``last``), or the stretched / joined / trimmed float32."""
+        chunk), its converted samples (with the resampler's tail when ``last``), or the stretched / joined / trimmed / limited float32."""
         route, source = self.plan.routes[b], self.plan.source[b]
         out, counts = (t.numpy() for t in self.host[source])
         if source == "flac":

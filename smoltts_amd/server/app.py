@@ -83,6 +83,14 @@ class TTSCore:
             kw["silence_threshold_db"] = thr
         return kw
 
+    def _limit_kw(self, body) -> dict:
+        """``{"peak_limit_db": ceiling}`` of a request: the body's field where it names one (null: off), else the server's
+        ``peak_limit_db`` setting; nothing without either, so that the model sees the calls it saw before."""
+        db = self._setting("peak_limit_db", None)
+        if body is not None and hasattr(body, "peak_limit"):
+            db = body.peak_limit(db)
+        return {} if db is None else {"peak_limit_db": db}
+
     def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False, voice=None,
                     timestamps: bool = False) -> Tuple[dict, int]:
         """(kwargs, segments): ``{"speed": speed}`` for a speed other than 1, ``{"segment": options}`` in ``long_text="segment"``
@@ -101,6 +109,7 @@ class TTSCore:
             seg = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
         target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
         trim = self._trim_kw(loudness)
+        trim.update(self._limit_kw(loudness))
         p = parse_request(text, stream=stream, speed=speed, segment=seg, loudness=target, loudness_start_gain_db=start,
                           timestamps=timestamps or None, **trim)
         kw = {} if p.speed is None else {"speed": p.speed}
@@ -234,7 +243,8 @@ class TTSCore:
         it is spoken as one utterance whatever ``long_text`` says, and refused (``ValueError`` -> 400) with the trim options and
         ``best_of``.
         ``info["finish_reason"]``: ``"stop"`` or ``"length"`` (``config.finish_reason``).
-        ``loudness``: the body's ``LoudnessFields``; ``info["loudness_gain_db"]`` is then the gain the utterance was given, and
+        ``loudness``: the body's ``LoudnessFields``; ``info["loudness_gain_db"]`` is then the gain the utterance was given,
+        ``info["peak_reduction_db"]`` what its peak limiter took off where the body or the server names a ``peak_limit_db``, and
         ``info["watermark"]`` true when the audio is marked."""
         used = None
         try:
@@ -254,6 +264,7 @@ class TTSCore:
                 mean, n_takes = getattr(req, "mean_logprob", None), getattr(req, "best_of", 1)
                 used = getattr(req, "sampling", None)  # (a best_of request's entry is the chosen take's by now)
                 alignment = getattr(req, "alignment", None)
+                reduction = getattr(req, "peak_reduction_db", None)
             else:
                 used = self._model_sampling(sampling)
                 kw = {"sampling": used} if used is not None else {}
@@ -266,6 +277,7 @@ class TTSCore:
                 if takes:
                     used = self.model.last_sampling[0]  # the chosen take's entry
                 alignment = getattr(self.model, "last_alignment", None)
+                reduction = getattr(self.model, "last_peak_reduction_db", None)
             if timestamps:
                 if alignment is None:
                     raise RuntimeError("the engine returned no alignment for a request with timestamps")
@@ -279,6 +291,8 @@ class TTSCore:
                 info["trimmed_ms"] = 1e3 * float(cut or 0.0)
             if info is not None and "loudness" in sp:
                 info["loudness_gain_db"] = gain
+            if info is not None and "peak_limit_db" in sp:
+                info["peak_reduction_db"] = float(reduction or 0.0)
         except ValueError as e:  # a request the engine refuses (e.g. a text too long for max_seq_len): the client's fault, not a 500
             raise HTTPException(status_code=400, detail=str(e))
         self._count_segments(n_seg)
@@ -321,6 +335,7 @@ class TTSCore:
             kw["container"] = container
         target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
         trim = self._trim_kw(loudness)
+        trim.update(self._limit_kw(loudness))
         p = parse_request("", stream=True, speed=speed, loudness=target, loudness_start_gain_db=start, **kw, **trim)
         sp = {} if p.speed is None else {"speed": p.speed}
         sp.update(trim)
@@ -406,6 +421,11 @@ def _gain_headers(info: dict) -> dict:
     return {} if g is None else {"X-Loudness-Gain-Db": f"{g:.2f}"}
 
 
+def _peak_headers(info: dict) -> dict:
+    r = info.get("peak_reduction_db")
+    return {} if r is None else {"X-Peak-Reduction-Db": f"{r:.2f}"}
+
+
 def _trim_headers(info: dict) -> dict:
     t = info.get("trimmed_ms")
     return {} if t is None else {"X-Silence-Trimmed-Ms": f"{t:.0f}"}
@@ -487,6 +507,14 @@ class LoudnessFields(BaseModel):
     trim_silence: Optional[bool] = Field(default=None)
     max_pause_s: Optional[float] = Field(default=None, allow_inf_nan=False)
     silence_threshold_db: Optional[float] = Field(default=None, allow_inf_nan=False)
+    # Peak limiting (extension; limiter.py, on the GPU last of the float stages): ``peak_limit_db`` is a ceiling in dBFS (-12 to
+    # 0, 400 otherwise); omitted: the server's ``peak_limit_db`` setting; null: off.  A blocking response carries
+    # ``X-Peak-Reduction-Db`` (0.00 when nothing was limited); with a ``loudness`` its gain is then not capped by the peak.
+    peak_limit_db: Optional[float] = Field(default=None, allow_inf_nan=False)
+
+    def peak_limit(self, default):
+        """The ceiling in dBFS or None: the body's field where it names one (null: off), else the server's default."""
+        return self.peak_limit_db if "peak_limit_db" in self.model_fields_set else default
 
     def trim_fields(self, default_trim: bool, default_pause):
         """(trim the ends, the pause cap or None, the threshold or None): the body's fields where it names them, else the defaults."""
@@ -578,7 +606,7 @@ def openai_speech(item: SpeechRequest, http_request: Request):
                                                   speed=item.speed, loudness=item, info=info)
     return Response(audio, media_type=media_type, headers={"Content-Disposition": 'attachment; filename="speech.wav"', **_seed_headers(seed),
                                                            **_gain_headers(info), **_mark_headers(info), **_trim_headers(info),
-                                                           **_finish_headers(info), **_score_headers(info)})
+                                                           **_peak_headers(info), **_finish_headers(info), **_score_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}")
@@ -592,7 +620,7 @@ def text_to_speech_blocking(voice_id: str, item: CreateSpeechRequest, http_reque
     return Response(content=content, media_type=media_type, headers={
         "Content-Disposition": f'attachment; filename="elevenlabs_speech.{fmt.split("_")[0]}"',
         "X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed), **_gain_headers(info), **_mark_headers(info),
-        **_trim_headers(info), **_finish_headers(info), **_score_headers(info)})
+        **_trim_headers(info), **_peak_headers(info), **_finish_headers(info), **_score_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}/with-timestamps")
@@ -615,7 +643,7 @@ def text_to_speech_with_timestamps(voice_id: str, item: CreateSpeechRequest, htt
     al = info["alignment"].to_json()
     return JSONResponse({"audio_base64": base64.b64encode(content).decode("ascii"), "alignment": al, "normalized_alignment": al},
                         headers={"X-Sample-Rate": fmt.split("_")[1] if "_" in fmt else "24000", **_seed_headers(seed),
-                                 **_gain_headers(info), **_mark_headers(info), **_finish_headers(info)})
+                                 **_gain_headers(info), **_mark_headers(info), **_peak_headers(info), **_finish_headers(info)})
 
 
 @eleven_router.post("/text-to-speech/{voice_id}/stream")

@@ -42,6 +42,7 @@ class _PoolRequest:
     takes: object = None
     best_of: int = 1
     alignment: object = None  # align.Alignment of a request that asked for timestamps, known at its end
+    peak_reduction_db: Optional[float] = None  # a blocking request with a peak_limit_db: -20 log10(min g) (known at its end)
 
 
 @dataclass
@@ -111,7 +112,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
                 scores = {"logprobs": np.asarray(req.logprobs), "mean_logprob": req.mean_logprob, "takes": req.takes, "best_of": req.best_of,
                           "seed": req.sampling.seed}
             res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0), getattr(req, "finish_reason", None), scores,
-                                    getattr(req, "alignment", None))))
+                                    getattr(req, "alignment", None), getattr(req, "peak_reduction_db", None))))
         except Exception as e:
             res_q.put((rid, "error", (type(e).__name__, str(e))))
         finally:
@@ -260,12 +261,14 @@ class GpuPool:
                container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
                loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
                trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-               silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None) -> _PoolRequest:
+               silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
+               peak_limit_db: Optional[float] = None) -> _PoolRequest:
         """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
         from ..request import parse_request
 
         p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db, timestamps=timestamps)  # refused here, before a worker sees it
+                          trim_silence, max_pause_s, silence_threshold_db, timestamps=timestamps,
+                          peak_limit_db=peak_limit_db)  # refused here, before a worker sees it
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
         if p.timestamps:
@@ -285,7 +288,8 @@ class GpuPool:
                                    ("container", p.container), ("segment", p.segment), ("loudness", p.loudness),
                                    ("loudness_start_gain_db", loudness_start_gain_db), ("watermark", p.watermark),
                                    ("trim_silence", p.trim_silence or None), ("max_pause_s", p.max_pause_s),
-                                   ("silence_threshold_db", p.silence_threshold_db), ("timestamps", p.timestamps or None)) if v is not None}
+                                   ("silence_threshold_db", p.silence_threshold_db), ("timestamps", p.timestamps or None),
+                                   ("peak_limit_db", p.peak_limit_db)) if v is not None}
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
@@ -294,7 +298,8 @@ class GpuPool:
                            loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
                            idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
                            watermark: Optional[bool] = None, trim_silence: Optional[bool] = None,
-                           max_pause_s: Optional[float] = None, silence_threshold_db: Optional[float] = None) -> _PoolIncrementalRequest:
+                           max_pause_s: Optional[float] = None, silence_threshold_db: Optional[float] = None,
+                           peak_limit_db: Optional[float] = None) -> _PoolIncrementalRequest:
         """As ``BatchScheduler.submit_incremental``: the request lives in one slot of one worker, and ``feed`` / ``flush`` /
         ``close`` / ``cancel`` of the handle go to that worker over its queue, in the order they were called.  Text the worker
         refuses (a bad break tag) ends the stream with that ``ValueError`` instead of raising from ``feed``."""
@@ -302,7 +307,7 @@ class GpuPool:
         from ..request import parse_request
 
         p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db)
+                          trim_silence, max_pause_s, silence_threshold_db, peak_limit_db=peak_limit_db)
         opts = segment_options(True if segment is None or segment is False else segment)
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
@@ -313,7 +318,7 @@ class GpuPool:
                                    ("loudness_start_gain_db", loudness_start_gain_db), ("idle_timeout_s", idle_timeout_s),
                                    ("flush_after_s", flush_after_s), ("watermark", p.watermark),
                                    ("trim_silence", p.trim_silence or None), ("max_pause_s", p.max_pause_s),
-                                   ("silence_threshold_db", p.silence_threshold_db)) if v is not None}
+                                   ("silence_threshold_db", p.silence_threshold_db), ("peak_limit_db", p.peak_limit_db)) if v is not None}
         self._req_qs[req.worker].put(("submit_incremental", req.rid, voice, max_new_tokens, extra))
         return req
 
@@ -517,7 +522,8 @@ class GpuPool:
                 if not req.cancelled:
                     req.out.put(payload)
             elif kind == "end":
-                req.loudness_gain_db, req.trimmed_s, req.finish_reason, scores, req.alignment = payload
+                req.loudness_gain_db, req.trimmed_s, req.finish_reason, scores, req.alignment = payload[:5]
+                req.peak_reduction_db = payload[5] if len(payload) > 5 else None
                 if scores is not None:
                     import dataclasses
 

@@ -93,6 +93,10 @@ class _Request:
     out_samples: int = 0                 # samples handed out so far: the delivered duration
     audio_frames: int = 0                # frames whose slow id was semantic: the ones the codec decodes
     alignment: object = None             # align.Alignment, set before the request's end marker
+    # peak limiter: a stream is limited in its codec pass, last of the float stages; a blocking utterance whole, last
+    peak_limit_db: Optional[float] = None
+    ceiling: float = 0.0                 # 10^(peak_limit_db / 20); 0: no limiter
+    peak_reduction_db: Optional[float] = None  # blocking: -20 log10 of the smallest gain applied (set before the audio goes out)
 
 
 @dataclass
@@ -318,8 +322,14 @@ class BatchScheduler:
                container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
                loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
                trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-               silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None) -> _Request:
-        """``timestamps`` (blocking requests of one utterance; needs the scheduler's ``alignment_heads``; ``ValueError`` with
+               silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
+               peak_limit_db: Optional[float] = None) -> _Request:
+        """``peak_limit_db`` (a ceiling in dBFS, -12 to 0, ``ValueError`` otherwise; None: none): look-ahead peak limiting on the
+        GPU (limiter.py), last of the float stages.  A stream is limited in its codec pass, behind the watermark and in front of
+        the conversion and the framing: it holds back 126 samples, which leave with its last chunk, and reports nothing.  A
+        blocking utterance is limited whole behind everything else (``request.peak_reduction_db``: ``-20 log10`` of the smallest
+        gain, 0.0 when nothing was limited), and with a ``loudness`` as well its one gain is not capped by the peak.
+        ``timestamps`` (blocking requests of one utterance; needs the scheduler's ``alignment_heads``; ``ValueError`` with
         ``segment``, the trim options, a stream or ``best_of``): ``request.alignment`` is an ``align.Alignment`` -- per character of
         the text its start and end in seconds of the audio delivered -- once the request has ended.  The audio is not changed.
         ``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
@@ -351,7 +361,7 @@ class BatchScheduler:
         from ..request import parse_request
 
         p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db, timestamps=timestamps)
+                          trim_silence, max_pause_s, silence_threshold_db, timestamps=timestamps, peak_limit_db=peak_limit_db)
         self._check_trim(p)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         check_best_of(resolved, self.B, stream=stream, segmented=p.plan is not None)
@@ -368,7 +378,7 @@ class BatchScheduler:
                        output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=p.speed_q,
                        container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None,
                        loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark), trim=p.trim_route,
-                       timestamps=p.timestamps, speed=p.speed)
+                       timestamps=p.timestamps, speed=p.speed, peak_limit_db=p.peak_limit_db, ceiling=p.ceiling)
         if resolved.takes > 1:
             # the parent carries the audio options and the response; its takes are plain blocking requests, admitted as slots
             # come free
@@ -403,7 +413,8 @@ class BatchScheduler:
                            loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
                            idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
                            watermark: Optional[bool] = None, trim_silence: Optional[bool] = None,
-                           max_pause_s: Optional[float] = None, silence_threshold_db: Optional[float] = None) -> IncrementalRequest:
+                           max_pause_s: Optional[float] = None, silence_threshold_db: Optional[float] = None,
+                           peak_limit_db: Optional[float] = None) -> IncrementalRequest:
         """A stream whose text is not known yet: ``request.feed(text)`` as it arrives, ``request.close()`` at its end, the
         chunks by iterating the request (or ``iter_chunks``).  The options are those of ``submit(stream=True, segment=...)``
         (``segment``: True, a dict or a ``SegmentOptions``; it cannot be off).
@@ -433,7 +444,7 @@ class BatchScheduler:
         from ..request import parse_request
 
         p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db)
+                          trim_silence, max_pause_s, silence_threshold_db, peak_limit_db=peak_limit_db)
         self._check_trim(p)
         opts = segment_options(True if segment is None or segment is False else segment)
         if not float(idle_timeout_s) > 0.0 or (flush_after_s is not None and not float(flush_after_s) > 0.0):
@@ -448,7 +459,7 @@ class BatchScheduler:
                                  output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice),
                                  speed_q=p.speed_q, container=p.container, seg=_Segmented(GrowingPlan(opts), resolved),
                                  loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark),
-                                 trim=p.trim_route, sched=self,
+                                 trim=p.trim_route, sched=self, peak_limit_db=p.peak_limit_db, ceiling=p.ceiling,
                                  inc=_Incremental(IncrementalSplitter(opts), float(idle_timeout_s),
                                                   None if flush_after_s is None else float(flush_after_s),
                                                   last_input=time.monotonic()))
@@ -1017,7 +1028,8 @@ class BatchScheduler:
                                               [r.speed_q for r in fresh], [r.container for r in fresh],
                                               [r.loudness for r in fresh], [r.start_gain_db for r in fresh],
                                               [r.watermark for r in fresh] if self.watermark is not None else None,
-                                              [r.trim for r in fresh] if any(r.trim for r in fresh) else None)
+                                              [r.trim for r in fresh] if any(r.trim for r in fresh) else None,
+                                              [r.ceiling for r in fresh] if any(r.ceiling for r in fresh) else None)
                 segd = [r for r in new if r.seg is not None]
                 if segd:
                     pauses, flags, leads = zip(*(r.seg.plan.seam_args(r.seg.k) for r in segd))
@@ -1275,8 +1287,8 @@ class BatchScheduler:
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
                         self._counts["frames_delivered"] += n // 1920
-                elif not r.stream and (r.speed_q or r.loudness is not None or r.watermark or r.trim):
-                    # a blocking utterance with a trim, a speed, a loudness target or the mark: trimmed, levelled, stretched and marked whole once
+                elif not r.stream and (r.speed_q or r.loudness is not None or r.watermark or r.trim or r.ceiling):
+                    # a blocking utterance with a trim, a speed, a loudness target, the mark or a ceiling: trimmed, levelled, stretched, marked and limited whole once
                     # its last pass is in
                     if n and not r.cancelled:
                         r.stretch_in.append(host[b, :n].copy())
@@ -1342,13 +1354,19 @@ class BatchScheduler:
 
     def _mark(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
         """A complete blocking utterance, levelled and stretched: a marked request's gets the watermark whole on the GPU
-        (stages.watermark_embed: one launch, waited for here as the seam join is)."""
-        if not r.watermark:
-            return pcm
-        from ..stages import watermark_embed
+        (stages.watermark_embed: one launch, waited for here as the seam join is), and a request with a ceiling is limited
+        whole behind that, last of all (stages.peak_limit: one launch)."""
+        if r.watermark:
+            from ..stages import watermark_embed
 
-        with self._torch.cuda.stream(self._stretch_stream):
-            return watermark_embed(pcm, self.watermark, self.session.engine.device)
+            with self._torch.cuda.stream(self._stretch_stream):
+                pcm = watermark_embed(pcm, self.watermark, self.session.engine.device)
+        if r.peak_limit_db is not None:
+            from ..stages import peak_limit
+
+            with self._torch.cuda.stream(self._stretch_stream):
+                pcm, r.peak_reduction_db = peak_limit(pcm, r.peak_limit_db, self.session.engine.device)
+        return pcm
 
     def _level(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
         """A complete blocking utterance (joined, not yet stretched): with a loudness target it is measured and scaled whole on
@@ -1359,7 +1377,7 @@ class BatchScheduler:
         from ..loudness import gain_db
 
         with self._torch.cuda.stream(self._stretch_stream):
-            pcm, g = loudness_normalize(pcm, r.loudness, self.session.engine.device, with_gain=True)
+            pcm, g = loudness_normalize(pcm, r.loudness, self.session.engine.device, with_gain=True, cap=r.peak_limit_db is None)
         r.loudness_gain_db = gain_db(g)
         return pcm
 

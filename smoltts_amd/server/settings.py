@@ -95,6 +95,9 @@ class ServerSettings(BaseModel):
     # silence; cap the pauses at max_pause_s seconds (null: pauses are left alone)
     trim_silence: bool = False
     max_pause_s: Optional[float] = Field(default=None, ge=0.1, le=2.0)
+    # (extension) the ceiling in dBFS of the look-ahead peak limiter for requests whose body names none (limiter.py, DESIGN.md
+    # 22); null: no limiter.  A blocking response that was limited carries X-Peak-Reduction-Db
+    peak_limit_db: Optional[float] = Field(default=None, ge=-12.0, le=0.0)
 
     # (extension) a keyed watermark added to the audio on the GPU; null: none.  {"key": "<16 hex digits>", "strength_db": -26.0,
     # "apply": "all" | "cloned"}; marked responses carry X-Watermark: 1, and POST /v1/watermark/detect tests a recording

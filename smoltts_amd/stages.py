@@ -1,4 +1,4 @@
-"""The stages behind the codec, one class per C stage (resampler, time stretch, trim, seam, loudness, watermark, FLAC), and
+"""The stages behind the codec, one class per C stage (resampler, time stretch, trim, seam, loudness, watermark, limiter, FLAC), and
 their whole-utterance helpers."""
 from __future__ import annotations
 
@@ -379,9 +379,9 @@ class LoudnessNormalizer(_Stage):
                 "ptarget": float(v[18]), "filter": v[:17].copy(), "ring": v[19:].copy()}
 
 
-def _loudness_whole(pcm: np.ndarray, device: torch.device, target: Optional[float]):
+def _loudness_whole(pcm: np.ndarray, device: torch.device, target: Optional[float], cap: bool = True):
     """(power, peak, gain, output or None) of a whole utterance on ``device``: measured in one launch, and with a ``target``
-    scaled by the blocking rule's gain in a second one."""
+    scaled by the blocking rule's gain (``cap`` false: not capped by the peak) in a second one."""
     from .loudness import static_gain
 
     x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
@@ -392,7 +392,7 @@ def _loudness_whole(pcm: np.ndarray, device: torch.device, target: Optional[floa
 
             def launch(row, n, out, counts):
                 seen["p"], seen["peak"] = ln.measure(row, n) if n else (0.0, 0.0)
-                seen["g"] = 1.0 if target is None else static_gain(target, seen["p"], seen["peak"])
+                seen["g"] = 1.0 if target is None else static_gain(target, seen["p"], seen["peak"], cap)
                 ln.scale(row, n, seen["g"], out)
                 counts.fill_(n)
 
@@ -411,13 +411,14 @@ def measure_loudness(pcm: np.ndarray, device: torch.device) -> Tuple[float, floa
     return lufs_of_power(p), peak
 
 
-def loudness_normalize(pcm: np.ndarray, target: float, device: torch.device, with_gain: bool = False):
+def loudness_normalize(pcm: np.ndarray, target: float, device: torch.device, with_gain: bool = False, cap: bool = True):
     """A whole utterance (float32 at 24 kHz) brought to ``target`` LUFS on ``device`` by one gain, capped so that its peak
     stays at -1 dBFS: ``loudness.normalize`` (``SmolTTS.__call__``).  An utterance that measures nothing comes back
-    unchanged.  ``with_gain``: -> (samples, the gain applied).  Waits for the result."""
+    unchanged.  ``with_gain``: -> (samples, the gain applied).  ``cap`` false: the gain is not capped by the peak (a request
+    whose peaks a limiter takes down behind it).  Waits for the result."""
     from .loudness import check_target
 
-    _, _, g, y = _loudness_whole(pcm, device, check_target(target))
+    _, _, g, y = _loudness_whole(pcm, device, check_target(target), cap)
     return (y, g) if with_gain else y
 
 
@@ -482,6 +483,107 @@ def watermark_embed(pcm: np.ndarray, wm, device: torch.device) -> np.ndarray:
                 counts.fill_(n)
 
             return _whole_row(st, x, launch)
+        finally:
+            st.close()
+
+
+# ------------------------------------------------------------------------------- peak limiter
+class PeakLimiter(_Stage):
+    """Per-slot look-ahead peak limiting of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Limiter"; the numpy
+    model is ``limiter.StreamState``): one launch per call for every slot, each under its own ceiling.  A slot holds back
+    ``limiter.HOLD_BACK`` samples until its stream ends.  Slots start off; ``reset_slots`` starts a new stream in a slot
+    (ceiling 0: off)."""
+
+    C_NAME = "limiter"
+
+    def _create_args(self) -> tuple:
+        from .limiter import packed
+
+        self._tables = packed()  # (read by the create call only)
+        assert self._tables.size == self.lib.smoltts_limiter_table_doubles()
+        return self._tables.ctypes.data, int(self._tables.size)
+
+    def reset_slots(self, slots: Sequence[int], ceilings: Sequence[float]) -> None:
+        """Start new streams in ``slots`` under their ``ceilings`` (10^(peak_limit_db / 20); 0: the slot is off)."""
+        n = len(slots)
+        if not n:
+            return
+        self._call("reset_slots", self._ints(slots), (C.c_double * n)(*[float(c) for c in ceilings]), n)
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
+              last: Optional[torch.Tensor] = None) -> None:
+        """Limit ``n_in`` samples (at most ``limiter.MAX_CALL``) of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous
+        rows) on the current stream.  ``valid``: device int32 [batch], the real samples of each row; ``last``: device int32
+        [batch], nonzero where the row's stream ends with this call (the slot flushes).  ``counts[b]``: the samples slot b
+        wrote to ``out[b]`` (0 for a slot that is off, whose row is left alone)."""
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, last)
+        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(last), dptr(out), out.shape[1], dptr(counts))
+
+    def out_samples(self, n_in: int) -> int:
+        """Output samples per row of a pass of ``n_in`` input samples (``run``): what the C call says up to the most one call
+        takes, the same rule past it."""
+        from .limiter import HOLD_BACK, MAX_CALL
+
+        return super().out_samples(n_in) if n_in <= MAX_CALL else int(n_in) + HOLD_BACK
+
+    def run(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: torch.Tensor,
+            last: Optional[torch.Tensor] = None) -> None:
+        """``chunk`` for rows of any width (the stages in front can hand over more than one call takes: a trim stage that
+        releases what it held, stretched): the row goes through in pieces of ``limiter.MAX_CALL`` samples, the stream's end with
+        the last one, and each piece's samples are moved behind those of the pieces in front.  No wait."""
+        from .limiter import MAX_CALL
+
+        if n_in <= MAX_CALL:
+            return self.chunk(pcm, n_in, out, counts, valid=valid, last=last)
+        batch = pcm.shape[0]
+        at = torch.arange(out.shape[1], device=self.device)[None]
+        total = torch.zeros(batch, dtype=torch.int64, device=self.device)
+        for i in range(0, n_in, MAX_CALL):
+            w = min(MAX_CALL, n_in - i)
+            part, cnt = self.new_outputs(batch, w)
+            self.chunk(pcm[:, i:i + w], w, part, cnt, valid=(valid - i).clamp(0, w).to(torch.int32),
+                       last=last if i + w >= n_in else None)
+            idx = at - total[:, None]
+            mine = (idx >= 0) & (idx < cnt[:, None])
+            out.copy_(torch.where(mine, part.gather(1, idx.clamp(0, part.shape[1] - 1)), out))
+            total += cnt
+        counts.copy_(total.to(torch.int32))
+
+    def apply(self, row: torch.Tensor, n: int, ceiling: float, out: torch.Tensor, result: torch.Tensor) -> None:
+        """``out[:n]``: the whole utterance ``row[:n]`` (device fp32, contiguous) limited under ``ceiling`` from position 0 to its
+        end, on the current stream; ``result[0]`` (device fp64): the smallest gain applied."""
+        assert result.dtype == torch.float64 and result.numel() >= 1 and out.numel() >= n
+        self._call("apply", dptr(row), int(n), float(ceiling), dptr(out), dptr(result))
+
+    def slot_state(self, slot: int) -> dict:
+        """Slot ``slot``'s state (synchronises the current stream), in the layout of ``limiter.StreamState.state``, with ``on``."""
+        from .limiter import HOLD_BACK, R_HIST
+
+        ints, v = (C.c_int64 * 3)(), np.zeros(2 + R_HIST + HOLD_BACK, np.float64)
+        self._call("slot_state", int(slot), ints, v.ctypes.data)
+        return {"pos": int(ints[0]), "on": int(ints[1]), "ended": int(ints[2]), "c": float(v[0]), "min_g": float(v[1]),
+                "r": v[2:2 + R_HIST].copy(), "x": v[2 + R_HIST:].astype(np.float32)}
+
+
+def peak_limit(pcm: np.ndarray, peak_limit_db: float, device: torch.device) -> Tuple[np.ndarray, float]:
+    """A whole utterance (float32 at 24 kHz) limited under ``peak_limit_db`` dBFS on ``device`` in one launch: ``limiter.limit``
+    (``SmolTTS.__call__``) -> (samples, as many as went in; the reduction in dB, ``-20 log10(min g)``, 0.0 when nothing was
+    limited).  Waits for the result."""
+    from .limiter import ceiling_of_db, check_peak_limit, reduction_db
+
+    c = ceiling_of_db(check_peak_limit(peak_limit_db))
+    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    if x.size == 0:
+        return x, 0.0
+    with torch.cuda.device(device):
+        st = PeakLimiter(device, 1)
+        try:
+            res = torch.empty(1, dtype=torch.float64, device=device)
+            row = torch.from_numpy(x).to(device)
+            out = torch.empty_like(row)
+            st.apply(row, x.size, c, out, res)
+            return out.cpu().numpy(), reduction_db(float(res.cpu()[0]))
         finally:
             st.close()
 
