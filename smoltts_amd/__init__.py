@@ -211,39 +211,35 @@ class SmolTTS:
         return pcm
 
     def __call__(self, input: str, voice: Optional[str] = "heart", speaker=None, generation_settings=None, sampling=None,
-                 speed: Optional[float] = None, segment=False, loudness: Optional[float] = None, watermark: Optional[bool] = None,
-                 trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-                 silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
-                 peak_limit_db: Optional[float] = None):
+                 **options):
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
-        (per-request temperature / min_p / seed, as in ``generate_codes``).  ``speed`` (0.25 to 4.0; None / 1.0: unchanged):
-        the utterance is time-stretched on the GPU, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
-        ``segment`` (True, a dict or a ``longform.SegmentOptions``): a long text is spoken as chained segments (``longform``),
-        one after another, each decoded as its own utterance and joined on the GPU (``seam``) before the stretch; a text that is
-        one segment without break tags takes the plain path.  ``last_segments`` then lists each segment's text, seed and codes.
-        ``loudness`` (a target in LUFS, -40 to -5; None: the level is left alone): the utterance's BS.1770-4 integrated loudness
-        is measured on the GPU and one gain brings it to the target, capped where its peak would pass -1 dBFS (``loudness.py``),
-        behind the seam join and in front of the stretch; ``last_loudness_gain_db`` is the gain applied.
+        (per-request temperature / min_p / seed, as in ``generate_codes``).  ``options``: the blocking request's audio options,
+        handed whole to ``request.parse_request``, which lists them with their ranges and refuses a bad one before any work
+        (``ValueError``; ``TypeError`` for a name it does not know).  Here every stage takes the utterance whole on the GPU:
+        ``trim_silence`` / ``max_pause_s`` / ``silence_threshold_db``: the codec's PCM is trimmed first of all (``trim.py``),
+        each segment of a segmented text before the seam join; ``last_trimmed_s`` is what was cut.
+        ``segment``: the segments are spoken one after another, each decoded as its own utterance and joined (``seam``) before
+        the stretch; a text that is one segment without break tags takes the plain path.  ``last_segments`` then lists each
+        segment's text, seed and codes.
+        ``loudness``: the utterance's integrated loudness is measured and one gain brings it to the target, capped where its
+        peak would pass -1 dBFS (``loudness.py``), behind the seam join and in front of the stretch; ``last_loudness_gain_db``
+        is the gain applied.
+        ``speed``: the time stretch, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
         ``watermark`` (None: marked when the instance has a ``watermark``; True without one: ``ValueError``): the utterance gets
-        the instance's mark whole on the GPU, last: behind the seam join, the loudness gain and the stretch (``watermark.py``).
-        ``trim_silence`` (cut the leading and trailing silence), ``max_pause_s`` (0.1 to 2.0: cap the pauses) and
-        ``silence_threshold_db`` (-72 to -6 dBFS; default 2^-8): the codec's PCM is trimmed on the GPU first of all
-        (``trim.py``), each segment of a segmented text before the seam join; ``last_trimmed_s`` is what was cut.
+        the instance's mark behind the seam join, the loudness gain and the stretch (``watermark.py``).
         ``timestamps`` (needs the instance's ``alignment_heads``; not with ``segment``, the trim options or ``best_of``):
         ``last_alignment`` becomes the ``align.Alignment`` of the audio returned -- per character of ``input`` its start and end in
         seconds, read from where the chosen heads of the slow attention look while each frame is produced.  The option changes no
         id: with ``sampling=`` (its seed) or greedy settings the audio is the one the call returns without it.  A call without
         ``sampling=`` whose settings sample runs in the per-request mode here (the measurement exists only there) and draws a
         request seed, so its audio is another draw than the session-wide one; ``last_sampling`` carries the seed that replays it.
-        ``peak_limit_db`` (a ceiling in dBFS, -12 to 0; None: none): the utterance goes through the look-ahead peak limiter whole
-        on the GPU, last of all: behind the seam join, the loudness gain, the stretch and the watermark (``limiter.py``);
-        ``last_peak_reduction_db`` is ``-20 log10`` of the smallest gain applied, 0.0 when nothing was limited.  With a
-        ``loudness`` as well, the loudness gain is not capped by the peak: the limiter takes the peaks down instead."""
+        ``peak_limit_db``: the look-ahead peak limiter, last of all: behind the seam join, the loudness gain, the stretch and
+        the watermark (``limiter.py``); ``last_peak_reduction_db`` is ``-20 log10`` of the smallest gain applied, 0.0 when
+        nothing was limited.  With a ``loudness`` as well, the loudness gain is not capped by the peak: the limiter takes the
+        peaks down instead."""
         from .request import parse_request
 
-        req = parse_request(input, speed=speed, segment=segment, loudness=loudness, watermark=watermark, trim_silence=trim_silence,
-                            max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db,
-                            timestamps=timestamps, peak_limit_db=peak_limit_db)  # a bad request is refused before any work
+        req = parse_request(input, False, **options)  # a bad request is refused before any work
         self.last_alignment = None
         self.last_peak_reduction_db = None
         if req.timestamps:
@@ -426,10 +422,7 @@ class SmolTTS:
 
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
                reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None,
-               speed: Optional[float] = None, container: Optional[str] = None, segment=False,
-               loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
-               watermark: Optional[bool] = None, trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-               silence_threshold_db: Optional[float] = None, peak_limit_db: Optional[float] = None) -> Iterator["np.ndarray"]:
+               **options) -> Iterator["np.ndarray"]:
         """Yields one 1920-sample float32 chunk per generated frame, including the terminating
         <|im_end|> frame (reference stream, __init__.py:83-95, decodes vq_tensor[:, 1:, :] of every
         frame).  The codec carries its streaming state, so the chunks concatenate to the batch decode.
@@ -438,29 +431,30 @@ class SmolTTS:
         decode; a quirk kept switchable like ``NumericsMode``'s.
         ``overlap``: the codec step of frame f runs beside frame f + 1 on a second stream (``generate.stream_pcm``); the chunks
         are the same numbers either way.
-        ``output_format``: ``pcm_8000`` / ``pcm_16000`` / ``pcm_22050`` / ``pcm_44100`` / ``pcm_48000`` (int16 chunks) or
-        ``ulaw_8000`` (uint8 chunks), converted on the GPU chunk by chunk; over the utterance they concatenate to
-        ``scipy.signal.resample_poly`` of the float32 stream, quantised (formats.py).  ``None`` / ``pcm_24000``: float32.
         ``sampling``: a ``config.RequestSampling`` (as in ``generate_codes``); it is resolved when the generator starts.
-        ``speed`` (0.25 to 4.0; None / 1.0: unchanged): the stream is time-stretched on the GPU in front of the conversion; each
-        chunk holds the samples that became final with its frame (none for some frames: no chunk then).
-        ``container``: ``"flac"`` frames the stream's 16-bit samples (``output_format`` ``pcm_<rate>``, the float32 of
-        ``pcm_24000`` quantised as rint(clip(x, -1, 1) * 32767)) as FLAC on the GPU: uint8 chunks, the stream header in front of
-        the first, which decode to exactly those samples (flac.py).
-        ``segment`` (as in ``__call__``): a long text streams segment after segment in slot 0, each one's codec output through
-        the seam stage in front of the stream's other stages, which run on across the segments: one stream (one FLAC header).
-        ``loudness`` (as in ``__call__``): the stream is levelled causally on the GPU behind the seam and in front of the
-        stretch, by a gain that moves towards the target at 5 dB/s at most, from ``loudness_start_gain_db`` (default 0); every
-        frame's samples still leave with the frame (``loudness.StreamState``).
-        ``watermark`` (as in ``__call__``): the stream is marked on the GPU last of the float stages, behind the stretch and in
-        front of the conversion and the framing; a segmented stream keeps one mark grid across its seams.
-        ``trim_silence`` / ``max_pause_s`` / ``silence_threshold_db`` (as in ``__call__``): the stream is trimmed on the GPU
-        first of its stages, segment by segment in front of the seam; a non-silent block leaves with the frame that completes
-        it, silence is held back until it is known whether it is kept (``trim.TrimState``).
-        ``peak_limit_db`` (as in ``__call__``): the stream is peak-limited on the GPU last of the float stages, behind the
-        watermark and in front of the conversion and the framing; the limiter holds back 126 samples (5.25 ms), which leave
-        with the stream's last chunk, and its state runs on across the seams of a segmented stream (``limiter.StreamState``).
-        A stream reports no reduction, and its loudness rule is the causal one, unchanged.
+        ``output_format`` and ``options``: the streaming request's audio options, handed whole to ``request.parse_request``,
+        which lists them with their ranges.  Here every stage runs on the GPU chunk by chunk, right behind the frame's codec
+        step (``generate.stream_pcm``):
+        ``output_format``: the int16 / uint8 chunks concatenate over the utterance to ``scipy.signal.resample_poly`` of the
+        float32 stream, quantised (formats.py).
+        ``speed``: the stream is time-stretched in front of the conversion; each chunk holds the samples that became final with
+        its frame (none for some frames: no chunk then).
+        ``container``: the FLAC frames decode to exactly the stream's 16-bit samples (those of ``pcm_<rate>``, or the float32 of
+        ``pcm_24000`` quantised as rint(clip(x, -1, 1) * 32767)); the stream header stands in front of the first chunk (flac.py).
+        ``segment``: a long text streams segment after segment in slot 0, each one's codec output through the seam stage in
+        front of the stream's other stages, which run on across the segments: one stream (one FLAC header).
+        ``loudness``: the stream is levelled causally behind the seam and in front of the stretch, by a gain that moves towards
+        the target at 5 dB/s at most, from ``loudness_start_gain_db``; every frame's samples still leave with the frame
+        (``loudness.StreamState``).
+        ``watermark`` (as in ``__call__``): the stream is marked last of the float stages but for the limiter, behind the stretch
+        and in front of the conversion and the framing; a segmented stream keeps one mark grid across its seams.
+        ``trim_silence`` / ``max_pause_s`` / ``silence_threshold_db``: the stream is trimmed first of its stages, segment by
+        segment in front of the seam; a non-silent block leaves with the frame that completes it, silence is held back until
+        it is known whether it is kept (``trim.TrimState``).
+        ``peak_limit_db``: the stream is peak-limited last of the float stages, behind the watermark and in front of the
+        conversion and the framing; the limiter holds back 126 samples (5.25 ms), which leave with the stream's last chunk, and
+        its state runs on across the seams of a segmented stream (``limiter.StreamState``).  A stream reports no reduction, and
+        its loudness rule is the causal one, unchanged.
         ``input`` may be an iterator or generator of strings (or UTF-8 ``bytes``, cut anywhere) in place of a string: text that is
         still being written.  It implies ``segment=True`` (or the options given), is cut by ``longform.IncrementalSplitter``
         and spoken segment after segment while the text is pulled: before segment k starts, just enough text is pulled to have
@@ -477,14 +471,9 @@ class SmolTTS:
         self._check_best_of(sampling, generation_settings, stream=True)
         if not isinstance(input, (str, bytes)):
             yield from self._stream_incremental(iter(input), voice if voice is not None else "0", generation_settings, overlap,
-                                                reference_upsample, output_format, sampling, speed, container, segment, loudness,
-                                                loudness_start_gain_db, watermark, trim_silence, max_pause_s, silence_threshold_db,
-                                                peak_limit_db)
+                                                reference_upsample, output_format, sampling, **options)
             return
-        req = parse_request(input, stream=True, output_format=output_format, speed=speed, container=container, segment=segment,
-                            loudness=loudness, loudness_start_gain_db=loudness_start_gain_db, watermark=watermark,
-                            trim_silence=trim_silence, max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db,
-                            peak_limit_db=peak_limit_db)
+        req = parse_request(input, stream=True, output_format=output_format, **options)
         marked = self._marks(req.watermark)
         voice = voice if voice is not None else "0"
         if req.plan is not None:
@@ -499,9 +488,7 @@ class SmolTTS:
         sess = self._stream_session(prompt, settings, self.last_sampling)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
-            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, output_format=req.output_format,
-                                  speed_q=req.speed_q, container=req.container, loudness=req.loudness,
-                                  start_gain_db=req.start_gain_db, watermark=marked, trim=req.trim_route, ceiling=req.ceiling)
+            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, options=req, watermark=marked)
             self.last_finish_reason = self._stream_reason(sess)
             if self.last_sampling is not None and self.last_sampling[0].scored:
                 from .config import mean_logprob
@@ -578,16 +565,14 @@ class SmolTTS:
             self._seam = SeamJoiner(self.lm.device, 1)
         return seam_join(pcms, plan.pauses, self.lm.device, lead=plan.lead, trail=plan.trail, joiner=self._seam)
 
-    def _stream_incremental(self, texts, voice, generation_settings, overlap, reference_upsample, output_format, sampling, speed,
-                            container, segment, loudness, loudness_start_gain_db, watermark=None, trim_silence=None, max_pause_s=None,
-                            silence_threshold_db=None, peak_limit_db=None):
-        """``stream`` of a text that ``texts`` yields in pieces: the segmented stream of a plan that grows as the text is pulled."""
+    def _stream_incremental(self, texts, voice, generation_settings, overlap, reference_upsample, output_format, sampling,
+                            segment=False, **options):
+        """``stream`` of a text that ``texts`` yields in pieces: the segmented stream of a plan that grows as the text is pulled
+        (``segment``: its options; it cannot be off)."""
         from .longform import FLUSH, GrowingPlan, IncrementalSplitter, segment_options
         from .request import parse_request
 
-        req = parse_request("", stream=True, output_format=output_format, speed=speed, container=container, loudness=loudness,
-                            loudness_start_gain_db=loudness_start_gain_db, watermark=watermark, trim_silence=trim_silence,
-                            max_pause_s=max_pause_s, silence_threshold_db=silence_threshold_db, peak_limit_db=peak_limit_db)
+        req = parse_request("", stream=True, output_format=output_format, **options)
         marked = self._marks(req.watermark)
         opts = segment_options(segment or True)
         plan, splitter = GrowingPlan(opts), IncrementalSplitter(opts)
@@ -626,9 +611,7 @@ class SmolTTS:
         conv = StreamConverter(dev, 1, 1920, seam=True, watermark=marked)
         msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1, stateless_upsample=reference_upsample)
         try:
-            conv.reset_slots([0], [req.output_format], [req.speed_q], [req.container], [req.loudness], [req.start_gain_db],
-                             [marked is not None], trim=None if req.trim_route is None else [req.trim_route],
-                             limit=[req.ceiling] if req.ceiling else None)
+            conv.start([0], [req], [marked is not None])
             segments = self._segments(plan, voice, None, generation_settings, sampling)
             for k in range(1 << 30):
                 if pull(k) if pull is not None else k < len(plan.segs):

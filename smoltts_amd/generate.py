@@ -24,6 +24,7 @@ import torch
 
 from .config import GenerationSettings, RequestSampling
 from .lm import LMEngine, LMSession
+from .request import SpeechOptions, parse_request
 from .route import StreamConverter
 
 
@@ -273,10 +274,8 @@ def generate_blocking(model: LMEngine, prompt: np.ndarray, generation_settings: 
 
 
 def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bool = True, max_frames: Optional[int] = None,
-               overlap: bool = True, output_format: Optional[str] = None, speed_q: Optional[int] = None,
-               container: Optional[str] = None, conv: Optional[StreamConverter] = None, final: bool = True,
-               loudness: Optional[float] = None, start_gain_db: Optional[float] = None, watermark=None,
-               trim: Optional[tuple] = None, ceiling: Optional[float] = None) -> Iterator[np.ndarray]:
+               overlap: bool = True, conv: Optional[StreamConverter] = None, final: bool = True,
+               options: Optional[SpeechOptions] = None, watermark=None) -> Iterator[np.ndarray]:
     """One utterance in slot 0 of ``session`` -> one 1920-sample float32 chunk per generated frame, as the reference's
     ``SmolTTS.stream`` yields them (mlx_inference/src/smoltts_mlx/__init__.py:83-95: every frame of ``SingleBatchGenerator`` through
     ``codec.decode_step``), the terminating ``<|im_end|>`` frame included.
@@ -288,43 +287,27 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     one-stream loop (``overlap=False``), only the order in which the GPU sees the launches changes.  A frame queued behind the
     last one is not a frame: a stopped slot is frozen (smoltts_lm_decode).
 
-    ``output_format`` (``pcm_<rate>`` / ``ulaw_8000``, formats.py): every chunk is converted on the codec stream right behind its
-    decode (``stages.Resampler``) and leaves as int16 / uint8 samples -- the outputs that became final with it; the resampler's
-    tail (<= 20 samples) follows the last chunk.  A frame the slot did not produce is not fed to the resampler (its valid count is
-    taken from the device's frame counter), so the tail is that of the last real frame.  ``None`` / ``pcm_24000``: float32.
-
-    ``speed_q`` (``tsm.speed_q``; None or 65536: no stretch, no launch): every frame's PCM goes through the time stretch
-    (``stages.TimeStretcher``) on the codec stream in front of the resampler, which then consumes the stretcher's output.  The end
-    of the stream is derived on the device from the same snapshot of the frame counter and ``done`` that the host reads, and the
-    stretcher flushes with it.  A chunk holds the samples that became final with its frame; a frame that finalised none yields
-    nothing.
-
-    ``container`` (``"flac"``): the stream's 16-bit samples (the converted ones, or the float32 quantised) are framed as FLAC on
-    the codec stream behind the other stages (``stages.FlacEncoder``): uint8 chunks, the stream header in front of the first;
-    the end of the stream is derived on the device as for a speed.
-
-    ``loudness`` (a target in LUFS, ``loudness.py``; None: no launch): every frame's PCM goes through the loudness stage
-    (``stages.LoudnessNormalizer``) in front of the stretch, from the first knot ``start_gain_db``; a frame's 1920 samples come
-    out with the frame.
+    ``options`` (a ``request.SpeechOptions``; None: a request without any): what the stream goes through behind its codec decode,
+    on the codec stream right behind it (``StreamConverter.start``: the route is ``SlotRoute.of`` the options, and only the
+    stages it names are made and launched).  Silence is trimmed first of all (the stream is one segment; a frame that
+    completes no block that is kept yields nothing), then come the loudness stage, whose 1920 samples leave with their frame,
+    and the stretch (a chunk holds the samples that became final with its frame; a frame that finalised none yields
+    nothing).  The limiter, the last float stage, holds back 126 samples, which leave with the end of the stream.  An
+    ``output_format`` makes every chunk int16 / uint8 samples -- the outputs that became final with it; the resampler's tail
+    (<= 20 samples) follows the last chunk.  A frame the slot did not produce is not fed to the stages (its valid count is taken
+    from the device's frame counter), so the tail is that of the last real frame.  A FLAC ``container`` frames the stream's
+    16-bit samples behind the other stages: uint8 chunks, the stream header in front of the first.  Where a stage must see the
+    end of the stream (``StreamConverter.ends``), it is derived on the device from the same snapshot of the frame counter and
+    ``done`` that the host reads.
 
     ``watermark`` (a ``watermark.Watermark``; None: no launch): every frame's PCM gets the key's mark on the codec stream
-    (``stages.Watermarker``), last of the float stages: behind the stretch, in front of the conversion and the framing.
-
-    ``trim`` ((trim the ends, the pause cap in blocks, the threshold or None), ``trim.py``; None: no launch): every frame's PCM
-    goes through the trim stage (``stages.SilenceTrimmer``) first of all; the stream is one segment, whose end is derived on the
-    device as for a speed.  A frame that completes no block that is kept yields nothing.
-
-    ``ceiling`` (the peak limiter's ceiling as an amplitude, ``SpeechOptions.ceiling``; None or 0: no launch): every frame's PCM
-    goes through the limiter (``stages.PeakLimiter``), the last float stage: behind the watermark, in front of the conversion
-    and the framing.  The slot holds back 126 samples, which leave with the end of the stream, derived on the device as for a
-    speed.
+    (``stages.Watermarker``), last of the float stages but for the limiter: behind the stretch, in front of the conversion and
+    the framing.  Whether a request is marked is its front end's policy, so it is not read from ``options``.
 
     ``conv``: the utterance is one segment of a long text (``longform``): the caller's ``StreamConverter(seam=True)``, with the
-    stream's stages started in slot 0 and this segment opened (``start_segments``), converts it and is not closed here; the
-    format, speed and container arguments are then ignored.  The end of the utterance, derived on the device, is the seam's end
+    stream's stages started in slot 0 and this segment opened (``start_segments``), converts it and is not closed here;
+    ``options`` and ``watermark`` are then ignored.  The end of the utterance, derived on the device, is the seam's end
     of segment, and the end of the stream only where ``final``; the resampler's tail follows the final segment only."""
-    if speed_q is not None and speed_q == 65536:
-        speed_q = None
     s = session
     limit = s.max_frames if max_frames is None else min(max_frames, s.max_frames)
     dev = s.engine.device
@@ -338,12 +321,11 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     state_host = torch.zeros(2, dtype=torch.int32).pin_memory()  # n_frames[0], done[0]
     own = conv is None
     if own:
-        conv = StreamConverter(dev, 1, 1920, watermark=watermark)  # (its stages are made by reset_slots, as the stream needs them)
+        conv = StreamConverter(dev, 1, 1920, watermark=watermark)  # (its stages are made by start, as the stream needs them)
     with torch.cuda.stream(codec_stream):
         msession.reset()
         if own:
-            conv.reset_slots([0], [output_format], [speed_q], [container], [loudness], [start_gain_db], [watermark is not None],
-                             trim=None if trim is None else [trim], limit=[ceiling] if ceiling else None)
+            conv.start([0], [options if options is not None else parse_request()], [watermark is not None])
     converted = conv.converts(0)
     ends_on_device, segmented = conv.ends([0])  # a stage must see the end of the stream / of the segment
     with torch.cuda.stream(lm_stream):

@@ -22,7 +22,7 @@ class SpeechOptions:
     segment: Optional[SegmentOptions]
     plan: Optional[SegmentPlan]      # None: the plain path (no segment options, or a text that is one plain segment)
     loudness: Optional[float] = None  # target in LUFS (loudness.py), None: the level is left as it is
-    start_gain_db: float = 0.0        # a stream's first gain knot
+    start_gain_db: float = 0.0        # a stream's first gain knot, on the knot grid
     watermark: Optional[bool] = None  # mark the audio with the front end's key (watermark.py); None: the front end's policy
     trim_silence: bool = False        # cut the leading and trailing silence (trim.py)
     max_pause_s: Optional[float] = None           # cap the pauses at this length, None: pauses are left alone
@@ -31,6 +31,18 @@ class SpeechOptions:
     silence_thr: float = float(threshold(None))   # silence_threshold_db as a float32 amplitude
     timestamps: bool = False          # character timestamps from the slow attention (align.py); blocking requests only
     peak_limit_db: Optional[float] = None  # the ceiling of the peak limiter in dBFS (limiter.py), None: no limiter
+    loudness_start_gain_db: Optional[float] = None  # start_gain_db as the caller gave it, None: not given
+
+    def given(self) -> dict:
+        """The options that are on, as ``parse_request`` keywords: ``parse_request(text, stream, **p.given()) == p`` (the plans
+        compared by their segments).  This is how the value crosses a process boundary (``GpuPool``) and how the HTTP core
+        hands it to a front end; a request with no option gives ``{}``."""
+        kw = {"output_format": self.output_format, "speed": self.speed, "container": self.container, "segment": self.segment,
+              "loudness": self.loudness, "loudness_start_gain_db": self.loudness_start_gain_db, "watermark": self.watermark,
+              "trim_silence": self.trim_silence or None, "max_pause_s": self.max_pause_s,
+              "silence_threshold_db": self.silence_threshold_db, "timestamps": self.timestamps or None,
+              "peak_limit_db": self.peak_limit_db}
+        return {k: v for k, v in kw.items() if v is not None}
 
     @property
     def ceiling(self) -> float:
@@ -44,7 +56,7 @@ class SpeechOptions:
 
     @property
     def trim_route(self) -> Optional[Tuple[bool, int, float]]:
-        """What ``StreamConverter.reset_slots`` takes for the request's slot (None: the slot does not trim)."""
+        """What ``stages.trim_pcm`` and ``StreamConverter.reset_slots`` take for the request (None: it does not trim)."""
         return (self.trim_silence, self.pause_blocks, self.silence_thr) if self.trims else None
 
 
@@ -54,8 +66,15 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
                   trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
                   silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
                   pieces: bool = False, peak_limit_db: Optional[float] = None) -> SpeechOptions:
-    """A request's options checked and normalised; ``ValueError`` for anything a front end refuses.  ``output_format`` and
-    ``container`` apply to streaming requests only, as does ``loudness_start_gain_db``, which needs a ``loudness``.  ``watermark``: true, false, or None for the
+    """A request's options checked and normalised; ``ValueError`` for anything a front end refuses.  Every front end takes these
+    keywords as its ``**options`` and hands them here whole, so this is the one list of the options and their ranges; a name
+    that is not in it is a ``TypeError``.  ``output_format`` (``pcm_8000 / 16000 / 22050 / 44100 / 48000``: int16 chunks,
+    ``ulaw_8000``: uint8 chunks; None / ``pcm_24000``: the codec's float32) and ``container`` (``"flac"``: FLAC frames of the
+    stream's 16-bit samples, uint8 chunks behind one stream header) apply to streaming requests only, as does
+    ``loudness_start_gain_db`` (within +-20 dB, default 0: the gain a stream starts from), which needs a ``loudness``.
+    ``speed`` (0.25 to 4.0; None / 1.0: unchanged): the pitch-preserving time stretch (tsm.py).  ``segment`` (True, a dict or a
+    ``longform.SegmentOptions``; None / False: off): a long text is spoken as chained segments (longform.py).  ``loudness``
+    (a target in LUFS, -40 to -5; None: the level is left alone): BS.1770-4 normalisation (loudness.py).  ``watermark``: true, false, or None for the
     front end's own policy (the key and the strength are the front end's: one key per stage).  ``trim_silence`` (true, false or
     None: false), ``max_pause_s`` (0.1 to 2.0 seconds, None: no cap) and ``silence_threshold_db`` (-72 to -6 dBFS, which needs
     one of the other two) are the trim stage's (trim.py).  ``timestamps`` (true, false or None: false): character timestamps
@@ -105,4 +124,5 @@ def parse_request(text: str = "", stream: bool = False, output_format: Optional[
                          check_start_gain(loudness_start_gain_db), watermark, bool(trim_silence),
                          None if max_pause_s is None else float(max_pause_s),
                          None if silence_threshold_db is None else float(silence_threshold_db), blocks,
-                         float(threshold(silence_threshold_db)), bool(timestamps), peak_limit_db)
+                         float(threshold(silence_threshold_db)), bool(timestamps), peak_limit_db,
+                         None if loudness_start_gain_db is None else float(loudness_start_gain_db))

@@ -11,7 +11,8 @@ import torch
 
 from .abi import FLAC_F32, FLAC_OFF, FLAC_S16, SEAM_FINAL, SEAM_FIRST, SEAM_OFF
 from .device import upload
-from .formats import ENC_OFF, check_container, parse_stream_format
+from .formats import ENC_OFF, ENC_ULAW, check_container, parse_stream_format
+from .request import SpeechOptions
 from .seam import THRESH
 from .stages import FlacEncoder, LoudnessNormalizer, PeakLimiter, Resampler, SeamJoiner, SilenceTrimmer, TimeStretcher, Watermarker
 from .tsm import out_bound
@@ -58,6 +59,22 @@ class SlotRoute:
     @property
     def trims(self) -> bool:
         return self.trim or self.pause_blocks > 0
+
+    @property
+    def format(self) -> str:
+        """The ``output_format`` of the route's rate and encoding (``pcm_24000``: not converted)."""
+        return "ulaw_8000" if self.enc == ENC_ULAW else f"pcm_{self.rate}"
+
+    @classmethod
+    def of(cls, options: SpeechOptions, watermark_gain: float, gen: int) -> "SlotRoute":
+        """The route of a new stream with a request's ``options``: the one place that maps an option to what a slot goes
+        through.  ``watermark_gain``: the converter's key's gain for a marked stream, else 0; ``gen``: the stream's generation
+        in its slot."""
+        rate, enc = parse_stream_format(options.output_format or "pcm_24000")
+        flac = options.container is not None
+        return cls(rate, enc, options.speed_q or 65536, flac, gen=gen, head_owed=flac, loudness=options.loudness,
+                   start_gain_db=options.start_gain_db, watermark_gain=watermark_gain, ceiling=options.ceiling,
+                   trim=options.trim_silence, pause_blocks=options.pause_blocks, thr=options.silence_thr)
 
 
 class PassPlan(NamedTuple):
@@ -120,23 +137,39 @@ class StreamConverter:
         slot's 16-bit samples at its rate), ``loudness[i]`` a target in LUFS (None: none) reached from ``start_gain_db[i]``,
         ``watermark[i]`` true for a slot that gets the converter's watermark, ``trim[i]`` None or (trim the ends, the pause cap
         in blocks, the threshold or None) of a slot that trims silence, ``limit[i]`` the ceiling of a slot's peak limiter as
-        an amplitude in (0, 1] (``SpeechOptions.ceiling``; None / 0: none).  A slot with none of them is switched off."""
+        an amplitude in (0, 1] (``SpeechOptions.ceiling``; None / 0: none).  A slot with none of them is switched off.
+        The list form of ``start``, for callers that drive the stages without a request."""
         if not slots:
             return
         formats = [f or "pcm_24000" for f in formats]
         routes = []
         none = [None] * len(slots)
-        if watermark is not None and any(watermark) and self.watermark is None:
-            raise ValueError("a slot asks for a watermark, and the converter has no key")
-        for b, f, q, c, lt, sg, wm, tr, lim in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none,
-                                                   watermark or none, trim or none, limit or none):
+        for b, f, q, c, lt, sg, g, tr, lim in zip(slots, formats, speed_q, containers or none, loudness or none, start_gain_db or none,
+                                                  self._gains(watermark, len(slots)), trim or none, limit or none):
             rate, enc = parse_stream_format(f)
             flac = check_container(c, f) is not None
             routes.append(SlotRoute(rate, enc, q or 65536, flac, segmented=False, gen=self.routes[b].gen + 1, head_owed=flac,
-                                    loudness=lt, start_gain_db=sg or 0.0, watermark_gain=self.watermark.gain if wm else 0.0,
-                                    ceiling=float(lim or 0.0),
+                                    loudness=lt, start_gain_db=sg or 0.0, watermark_gain=g, ceiling=float(lim or 0.0),
                                     **({} if tr is None else {"trim": bool(tr[0]), "pause_blocks": int(tr[1]),
                                                               "thr": float(THRESH if tr[2] is None else tr[2])})))
+        self._start(slots, routes)
+
+    def start(self, slots: Sequence[int], options: Sequence[SpeechOptions], marked: Optional[Sequence[bool]] = None) -> None:
+        """Start new streams in ``slots`` on the current stream, each by its request's options (``SlotRoute.of``); ``marked[i]``
+        true for a slot that gets the converter's watermark (the front end's policy applied to the request's wish)."""
+        if not slots:
+            return
+        gains = self._gains(marked, len(slots))
+        self._start(slots, [SlotRoute.of(o, g, self.routes[b].gen + 1) for b, o, g in zip(slots, options, gains)])
+
+    def _gains(self, marked: Optional[Sequence[bool]], n: int) -> List[float]:
+        """The watermark gain of each of ``n`` new streams; a slot may ask only of a converter that has a key."""
+        if marked is not None and any(marked) and self.watermark is None:
+            raise ValueError("a slot asks for a watermark, and the converter has no key")
+        return [self.watermark.gain if m else 0.0 for m in (marked or [False] * n)]
+
+    def _start(self, slots: Sequence[int], routes: Sequence[SlotRoute]) -> None:
+        """The new streams' stages, each created the first time a route needs it, then reset for every slot in ``slots``."""
         if self.tr is None and any(r.trims for r in routes):
             self.tr = SilenceTrimmer(self.device, self.B)
         if self.tr is not None:  # (a plain stream is one segment, the first and the last)
@@ -161,7 +194,7 @@ class StreamConverter:
         if self.fl is None and any(r.flac for r in routes):
             self.fl = FlacEncoder(self.device, self.B)
         if self.rs is not None:
-            self.rs.reset_slots(slots, formats)
+            self.rs.reset_slots(slots, [r.format for r in routes])
         if self.ts is not None:
             self.ts.reset_slots(slots, [r.speed_q for r in routes])
         if self.fl is not None:

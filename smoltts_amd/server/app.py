@@ -68,60 +68,39 @@ class TTSCore:
         with self._voice_lock:
             return str(voice) in self.voices
 
-    def _trim_kw(self, body) -> dict:
-        """The trim options of a request: the body's ``trim_silence`` / ``max_pause_s`` where it names them (null: off), else the
-        server's settings, and the body's ``silence_threshold_db``; only those that are on, so that the model sees the calls it
-        saw before when none is."""
-        on, pause = bool(self._setting("trim_silence", False)), self._setting("max_pause_s", None)
-        thr = None
-        if body is not None and hasattr(body, "trim_fields"):
-            on, pause, thr = body.trim_fields(on, pause)
-        kw = {"trim_silence": True} if on else {}
-        if pause is not None:
-            kw["max_pause_s"] = pause
-        if thr is not None:
-            kw["silence_threshold_db"] = thr
-        return kw
-
-    def _limit_kw(self, body) -> dict:
-        """``{"peak_limit_db": ceiling}`` of a request: the body's field where it names one (null: off), else the server's
-        ``peak_limit_db`` setting; nothing without either, so that the model sees the calls it saw before."""
-        db = self._setting("peak_limit_db", None)
-        if body is not None and hasattr(body, "peak_limit"):
-            db = body.peak_limit(db)
-        return {} if db is None else {"peak_limit_db": db}
-
     def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False, voice=None,
-                    timestamps: bool = False) -> Tuple[dict, int]:
-        """(kwargs, segments): ``{"speed": speed}`` for a speed other than 1, ``{"segment": options}`` in ``long_text="segment"``
-        mode and ``{"loudness": target}`` for a ``LoudnessFields`` body (or the server's ``loudness`` setting) that names one,
-        nothing otherwise, so that the model sees the calls it saw before; a bad speed or loudness, a text over
-        ``max_input_chars`` or with a bad break tag is the client's fault (ValueError).  The segments the request speaks (0: an unsegmented one) are
-        counted once it has completed."""
+                    timestamps: bool = False, pieces: Optional[dict] = None) -> Tuple[dict, int]:
+        """(kwargs, segments): the request's options resolved -- the body's fields where it names them (null: off), else the
+        server's settings -- parsed once, and handed on as the parsed value's own keywords (``SpeechOptions.given``): only the
+        options that are on, so that the model sees the calls it saw before when none is.  ``loudness``: the body's
+        ``LoudnessFields`` (None: the settings alone).  The segment options of ``long_text="segment"`` mode and ``watermark``
+        (``_marks``) are added as the settings give them.  ``pieces`` (the format keywords of a stream fed in pieces, which is
+        always spoken in segments whatever ``long_text`` says): they are parsed and handed on with the rest.  A bad option, a text
+        over ``max_input_chars`` or with a bad break tag is the client's fault (ValueError).  The segments the request speaks
+        (0: an unsegmented one) are counted once it has completed."""
         from ..request import parse_request
 
+        st, body = self._setting, loudness
+        seg_opts = {"max_bytes": int(st("segment_max_bytes", 300)), "pause_s": float(st("seam_pause_ms", 250)) / 1e3}
         seg = None
-        if self.long_text == "segment":
-            limit = int(self._setting("max_input_chars", 5000))
+        if pieces is None and self.long_text == "segment":
+            limit = int(st("max_input_chars", 5000))
             if len(text) > limit:
                 raise ValueError(f"input has {len(text)} characters; max_input_chars is {limit}")
-        if self.long_text == "segment" and not timestamps:  # (a request with timestamps is one utterance: chained segments have none)
-            seg = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
-        target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
-        trim = self._trim_kw(loudness)
-        trim.update(self._limit_kw(loudness))
+            if not timestamps:  # (a request with timestamps is one utterance: chained segments have none)
+                seg = seg_opts
+        target, start = body.resolve(st("loudness", None)) if body is not None else (st("loudness", None), None)
+        on, pause, thr, ceiling = bool(st("trim_silence", False)), st("max_pause_s", None), None, st("peak_limit_db", None)
+        if body is not None and hasattr(body, "trim_fields"):
+            on, pause, thr = body.trim_fields(on, pause)
+        if body is not None and hasattr(body, "peak_limit"):
+            ceiling = body.peak_limit(ceiling)
         p = parse_request(text, stream=stream, speed=speed, segment=seg, loudness=target, loudness_start_gain_db=start,
-                          timestamps=timestamps or None, **trim)
-        kw = {} if p.speed is None else {"speed": p.speed}
-        if p.timestamps:
-            kw["timestamps"] = True
-        kw.update(trim)
-        if p.loudness is not None:
-            kw["loudness"] = p.loudness
-            if start is not None:
-                kw["loudness_start_gain_db"] = start
-        if seg is not None:
-            kw["segment"] = seg
+                          trim_silence=on, max_pause_s=pause, silence_threshold_db=thr, timestamps=timestamps or None,
+                          peak_limit_db=ceiling, **(pieces or {}))
+        kw = p.given()
+        if seg is not None or pieces is not None:
+            kw["segment"] = seg_opts
         if self._marks(voice) is not None:
             kw["watermark"] = self._marks(voice)
         return kw, len(p.plan.segs) if p.plan is not None else 0
@@ -327,29 +306,15 @@ class TTSCore:
         the text as it speaks.  The segment options are the settings' ``segment_max_bytes`` / ``seam_pause_ms`` whatever
         ``long_text`` says (a text fed in pieces is always spoken in segments); ``idle_timeout_s`` and ``flush_after_s`` are
         the settings' too.  ``ValueError``: options the engine refuses."""
-        from ..request import parse_request
-
         self._check_best_of(sampling, stream=True)
         kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
         if container is not None:
             kw["container"] = container
-        target, start = loudness.resolve(self._setting("loudness", None)) if loudness is not None else (self._setting("loudness", None), None)
-        trim = self._trim_kw(loudness)
-        trim.update(self._limit_kw(loudness))
-        p = parse_request("", stream=True, speed=speed, loudness=target, loudness_start_gain_db=start, **kw, **trim)
-        sp = {} if p.speed is None else {"speed": p.speed}
-        sp.update(trim)
-        if p.loudness is not None:
-            sp["loudness"] = p.loudness
-            if start is not None:
-                sp["loudness_start_gain_db"] = start
-        sp["segment"] = {"max_bytes": int(self._setting("segment_max_bytes", 300)), "pause_s": float(self._setting("seam_pause_ms", 250)) / 1e3}
-        if self._marks(voice) is not None:
-            sp["watermark"] = self._marks(voice)
+        sp, _ = self._request_kw("", speed, loudness, stream=True, voice=voice, pieces=kw)
         if info is not None:
             info["watermark"] = bool(sp.get("watermark"))
         if self.scheduler is not None:
-            req = self.scheduler.submit_incremental(str(voice), **kw, **({"sampling": sampling} if sampling is not None else {}), **sp,
+            req = self.scheduler.submit_incremental(str(voice), **({"sampling": sampling} if sampling is not None else {}), **sp,
                                                     idle_timeout_s=float(self._setting("idle_timeout_s", 10.0)),
                                                     flush_after_s=self._setting("flush_after_s", None))
             used = getattr(req, "sampling", None)
@@ -358,7 +323,7 @@ class TTSCore:
 
         used = self._model_sampling(sampling)
         texts: "queue.Queue" = queue.Queue()  # pieces, FLUSH marks, then None
-        chunks = self.model.stream(iter(texts.get, None), str(voice), **kw, **({"sampling": used} if used is not None else {}), **sp)
+        chunks = self.model.stream(iter(texts.get, None), str(voice), **({"sampling": used} if used is not None else {}), **sp)
         end = lambda: texts.put(None)  # (a bare model cannot be interrupted: it speaks what it has pulled, then ends)
         return InputStream(texts.put, lambda: texts.put(FLUSH), end, end, self._stream_bytes(chunks, kw)), seed_used(used)
 

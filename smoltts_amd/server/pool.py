@@ -45,6 +45,10 @@ class _PoolRequest:
     peak_reduction_db: Optional[float] = None  # a blocking request with a peak_limit_db: -20 log10(min g) (known at its end)
 
 
+# what a worker reports at a request's end, by ``_PoolRequest`` attribute, with the value of a request that has none
+END_REPORT = {"loudness_gain_db": None, "trimmed_s": 0.0, "finish_reason": None, "alignment": None, "peak_reduction_db": None}
+
+
 @dataclass
 class _PoolIncrementalRequest(_PoolRequest):
     """``GpuPool.submit_incremental``'s handle: the text calls travel to the worker that owns the request, in order."""
@@ -111,8 +115,8 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
             if getattr(req, "logprobs", None) is not None:
                 scores = {"logprobs": np.asarray(req.logprobs), "mean_logprob": req.mean_logprob, "takes": req.takes, "best_of": req.best_of,
                           "seed": req.sampling.seed}
-            res_q.put((rid, "end", (getattr(req, "loudness_gain_db", None), getattr(req, "trimmed_s", 0.0), getattr(req, "finish_reason", None), scores,
-                                    getattr(req, "alignment", None), getattr(req, "peak_reduction_db", None))))
+            end = {k: getattr(req, k, d) for k, d in END_REPORT.items()}  # (a stand-in scheduler's request may lack some)
+            res_q.put((rid, "end", dict(end, scores=scores)))
         except Exception as e:
             res_q.put((rid, "error", (type(e).__name__, str(e))))
         finally:
@@ -257,18 +261,13 @@ class GpuPool:
 
     # ------------------------------------------------------------------ client side (the BatchScheduler interface)
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
-               container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
-               loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
-               trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-               silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
-               peak_limit_db: Optional[float] = None) -> _PoolRequest:
-        """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker)."""
+               output_format: Optional[str] = None, sampling=None, **options) -> _PoolRequest:
+        """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker).  The options are parsed
+        here, so that a bad request is refused before a worker sees it, and travel to the worker as the parsed value's own
+        keywords (``SpeechOptions.given``)."""
         from ..request import parse_request
 
-        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db, timestamps=timestamps,
-                          peak_limit_db=peak_limit_db)  # refused here, before a worker sees it
+        p = parse_request(text, stream, output_format, **options)
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
         if p.timestamps:
@@ -284,41 +283,30 @@ class GpuPool:
         req.watermark = marked
         w = req.worker
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
-        extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
-                                   ("container", p.container), ("segment", p.segment), ("loudness", p.loudness),
-                                   ("loudness_start_gain_db", loudness_start_gain_db), ("watermark", p.watermark),
-                                   ("trim_silence", p.trim_silence or None), ("max_pause_s", p.max_pause_s),
-                                   ("silence_threshold_db", p.silence_threshold_db), ("timestamps", p.timestamps or None),
-                                   ("peak_limit_db", p.peak_limit_db)) if v is not None}
+        extra = dict(p.given(), **({} if sampling is None else {"sampling": sampling}))
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
     def submit_incremental(self, voice: str = "heart", max_new_tokens: Optional[int] = None, output_format: Optional[str] = None,
-                           sampling=None, speed: Optional[float] = None, container: Optional[str] = None, segment=True,
-                           loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
-                           idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
-                           watermark: Optional[bool] = None, trim_silence: Optional[bool] = None,
-                           max_pause_s: Optional[float] = None, silence_threshold_db: Optional[float] = None,
-                           peak_limit_db: Optional[float] = None) -> _PoolIncrementalRequest:
+                           sampling=None, segment=True, idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
+                           **options) -> _PoolIncrementalRequest:
         """As ``BatchScheduler.submit_incremental``: the request lives in one slot of one worker, and ``feed`` / ``flush`` /
         ``close`` / ``cancel`` of the handle go to that worker over its queue, in the order they were called.  Text the worker
         refuses (a bad break tag) ends the stream with that ``ValueError`` instead of raising from ``feed``."""
         from ..longform import segment_options
         from ..request import parse_request
 
-        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db, peak_limit_db=peak_limit_db)
+        p = parse_request("", True, output_format, **options)
         opts = segment_options(True if segment is None or segment is False else segment)
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
         req = self._new_request(sampling, _PoolIncrementalRequest, pool=self)
         req.watermark = marked
-        extra = {k: v for k, v in (("output_format", p.output_format), ("sampling", sampling), ("speed", p.speed),
-                                   ("container", p.container), ("segment", opts), ("loudness", p.loudness),
-                                   ("loudness_start_gain_db", loudness_start_gain_db), ("idle_timeout_s", idle_timeout_s),
-                                   ("flush_after_s", flush_after_s), ("watermark", p.watermark),
-                                   ("trim_silence", p.trim_silence or None), ("max_pause_s", p.max_pause_s),
-                                   ("silence_threshold_db", p.silence_threshold_db), ("peak_limit_db", p.peak_limit_db)) if v is not None}
+        extra = dict(p.given(), segment=opts, idle_timeout_s=idle_timeout_s)
+        if sampling is not None:
+            extra["sampling"] = sampling
+        if flush_after_s is not None:
+            extra["flush_after_s"] = flush_after_s
         self._req_qs[req.worker].put(("submit_incremental", req.rid, voice, max_new_tokens, extra))
         return req
 
@@ -522,8 +510,9 @@ class GpuPool:
                 if not req.cancelled:
                     req.out.put(payload)
             elif kind == "end":
-                req.loudness_gain_db, req.trimmed_s, req.finish_reason, scores, req.alignment = payload[:5]
-                req.peak_reduction_db = payload[5] if len(payload) > 5 else None
+                scores = payload.pop("scores")
+                for k, v in payload.items():
+                    setattr(req, k, v)
                 if scores is not None:
                     import dataclasses
 

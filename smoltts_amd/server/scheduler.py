@@ -29,6 +29,10 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from ..request import SpeechOptions, parse_request
+
+NO_OPTIONS = parse_request()  # a request without any audio option
+
 
 @dataclass
 class _Request:
@@ -48,22 +52,19 @@ class _Request:
     stream_done: bool = False  # streaming: the last frames have been seen (the end marker goes out with the last codec pass)
     cancelled: bool = False  # set by the client side (cancel / an abandoned chunk iterator), honoured by the worker at its next look
     closed: bool = False  # the end marker (None or an exception) has been queued
-    output_format: Optional[str] = None  # streaming: pcm_<rate> / ulaw_8000 converted on the GPU (None: float32 at 24 kHz)
+    # the request's audio options as parsed at submit (request.py), read where a stage is started or applied: a stream's in its
+    # codec pass (StreamConverter.start), a blocking utterance's whole.  A best_of take, a segment's codec job: the default value
+    opts: SpeechOptions = NO_OPTIONS
     sampling: object = None  # config.RequestSampling, resolved at submit (seed drawn there for a sampled request without one)
     voice_entry: object = None  # _Voice of a registered voice, taken at submit (a later remove_voice does not affect the request)
     pos0: int = 0             # position of the prompt's first column: the voice's prefix length P for a registered voice
     prefix: object = None     # lm.PrefixKV installed into the slot at admission (None: the whole prompt is prefilled)
-    speed_q: Optional[int] = None  # speaking speed in Q16 (tsm.py), time-stretched on the GPU; None: speed 1, no stretch
     stretch_in: list = field(default_factory=list)  # blocking requests with a speed: the utterance's PCM until its last pass
-    container: Optional[str] = None  # streaming: "flac" frames the stream's 16-bit samples on the GPU (uint8 chunks)
     seg: Optional["_Segmented"] = None  # a long text as chained segments (None: one utterance)
     part_of: object = None    # (request, k): this codec job decodes segment k of a blocking segmented request
-    loudness: Optional[float] = None  # target in LUFS (loudness.py): a stream is levelled in its codec pass, a blocking utterance whole
-    start_gain_db: float = 0.0        # streaming: the loudness stage's first knot
     loudness_gain_db: Optional[float] = None  # blocking: the gain that was applied (set before the audio goes out)
     inc: Optional["_Incremental"] = None  # a stream whose text is fed in pieces (submit_incremental)
     watermark: bool = False   # the audio gets the scheduler's watermark: a stream in its codec pass, a blocking utterance whole, last
-    trim: Optional[tuple] = None  # (trim the ends, the pause cap in blocks, the threshold) of a request that trims silence (trim.py)
     trimmed_s: float = 0.0    # blocking: the seconds of silence that were cut (set before the audio goes out)
     finish_reason: Optional[str] = None  # "stop" / "length" (config.finish_reason), valid once the request has ended; a segmented
                                          # request is "length" if any segment was
@@ -85,17 +86,13 @@ class _Request:
     best_of: int = 1
     # character timestamps: a blocking request of one utterance whose frames measure where the scheduler's
     # alignment heads look over its own text
-    timestamps: bool = False
     align_window: object = None          # (t0, t1): the text's positions in the slot, known at admission
     align_ids: object = None             # ... and the text's token ids
     al: list = field(default_factory=list)  # its frames' rows [frames, heads, 2], tick by tick
-    speed: Optional[float] = None        # the speed asked for (the times are divided by it)
     out_samples: int = 0                 # samples handed out so far: the delivered duration
     audio_frames: int = 0                # frames whose slow id was semantic: the ones the codec decodes
     alignment: object = None             # align.Alignment, set before the request's end marker
     # peak limiter: a stream is limited in its codec pass, last of the float stages; a blocking utterance whole, last
-    peak_limit_db: Optional[float] = None
-    ceiling: float = 0.0                 # 10^(peak_limit_db / 20); 0: no limiter
     peak_reduction_db: Optional[float] = None  # blocking: -20 log10 of the smallest gain applied (set before the audio goes out)
 
 
@@ -318,50 +315,39 @@ class BatchScheduler:
 
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None, sampling=None, speed: Optional[float] = None,
-               container: Optional[str] = None, segment=None, loudness: Optional[float] = None,
-               loudness_start_gain_db: Optional[float] = None, watermark: Optional[bool] = None,
-               trim_silence: Optional[bool] = None, max_pause_s: Optional[float] = None,
-               silence_threshold_db: Optional[float] = None, timestamps: Optional[bool] = None,
-               peak_limit_db: Optional[float] = None) -> _Request:
-        """``peak_limit_db`` (a ceiling in dBFS, -12 to 0, ``ValueError`` otherwise; None: none): look-ahead peak limiting on the
-        GPU (limiter.py), last of the float stages.  A stream is limited in its codec pass, behind the watermark and in front of
-        the conversion and the framing: it holds back 126 samples, which leave with its last chunk, and reports nothing.  A
-        blocking utterance is limited whole behind everything else (``request.peak_reduction_db``: ``-20 log10`` of the smallest
-        gain, 0.0 when nothing was limited), and with a ``loudness`` as well its one gain is not capped by the peak.
+               output_format: Optional[str] = None, sampling=None, **options) -> _Request:
+        """``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
+        a seed gets one here.  The resolved value is ``request.sampling``; its seed replays the request.
+        ``output_format`` and ``options``: the request's audio options, handed whole to ``request.parse_request``, which lists
+        them with their ranges and refuses a bad one here, before the request is queued (``ValueError``; ``TypeError`` for a
+        name it does not know).  The parsed value is ``request.opts``.  Every stage runs on the GPU: a stream's in its codec
+        pass (``StreamConverter.start`` when the stream takes its slot), a blocking utterance's over the whole utterance once
+        its last codec pass is in.  What this front end adds to each:
+        ``output_format``: the resampler's tail comes with the stream's last chunk.
+        ``speed``: a stream is stretched in front of the format conversion, a blocking utterance as a whole.
+        ``container``: FLAC framing in the same pass, behind the other stages; the stream header in front of the first chunk.
+        ``segment``: a long text is spoken as chained segments in one slot, kept from the first segment to the last; each
+        segment's end, seen in a snapshot, refills the slot with the next chained prompt.  A stream runs through the seam stage
+        in front of its other stages (one stream); a blocking request decodes each segment as its own codec job and joins them
+        on the GPU.  A text that is one segment without break tags is an ordinary request.
+        ``loudness``: a stream is levelled causally, behind the seam and in front of the stretch, from
+        ``loudness_start_gain_db``; a blocking utterance is measured whole and given one gain (``request.loudness_gain_db``),
+        behind the seam join and in front of the stretch.
+        ``watermark`` (None: marked when the scheduler has a key; True without a key: ``ValueError``): the scheduler's watermark
+        (watermark.py), last of the float stages but for the limiter: a stream's behind the stretch, a blocking utterance's
+        whole.  ``request.watermark`` says whether it was.
+        ``trim_silence`` / ``max_pause_s`` / ``silence_threshold_db``: first of the stages: a stream segment by segment in front
+        of the seam; a blocking utterance whole, each segment before the seam join (``request.trimmed_s`` is what was cut).
+        ``peak_limit_db``: last of the float stages.  A stream is limited behind the watermark and in front of the conversion
+        and the framing: it holds back 126 samples, which leave with its last chunk, and reports nothing.  A blocking utterance
+        is limited whole behind everything else (``request.peak_reduction_db``: ``-20 log10`` of the smallest gain, 0.0 when
+        nothing was limited), and with a ``loudness`` as well its one gain is not capped by the peak.
         ``timestamps`` (blocking requests of one utterance; needs the scheduler's ``alignment_heads``; ``ValueError`` with
         ``segment``, the trim options, a stream or ``best_of``): ``request.alignment`` is an ``align.Alignment`` -- per character of
-        the text its start and end in seconds of the audio delivered -- once the request has ended.  The audio is not changed.
-        ``output_format`` (streaming only): ``pcm_<rate>`` / ``ulaw_8000`` chunks of int16 / uint8 samples, converted on the GPU
-        in the stream's codec pass (formats.py); the resampler's tail comes with the last chunk.  None / ``pcm_24000``: float32.
-        ``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
-        a seed gets one here.  The resolved value is ``request.sampling``; its seed replays the request.
-        ``speed`` (0.25 to 4.0, ``ValueError`` otherwise; None / 1.0: unchanged): pitch-preserving time stretch on the GPU
-        (tsm.py).  A stream is stretched in its codec pass in front of the format conversion, a blocking utterance as a whole.
-        ``container`` (streaming only, ``ValueError`` otherwise): ``"flac"`` frames the stream's 16-bit samples (of its
-        ``pcm_<rate>``, 24 kHz by default) as FLAC in the same pass, behind the other stages: uint8 chunks, the stream header in
-        front of the first.
-        ``segment`` (True, a dict or a ``longform.SegmentOptions``): a long text is spoken as chained segments in one slot, kept
-        from the first segment to the last; each segment's end, seen in a snapshot, refills the slot with the next chained
-        prompt.  A stream runs through the seam stage in front of its other stages (one stream); a blocking request decodes
-        each segment as its own codec job and joins them on the GPU.  A text that is one segment without break tags is an
-        ordinary request.
-        ``loudness`` (a target in LUFS, -40 to -5, ``ValueError`` otherwise; None: the level is left alone): BS.1770-4 loudness
-        normalisation on the GPU (loudness.py).  A stream is levelled causally in its codec pass, behind the seam and in front of
-        the stretch, from ``loudness_start_gain_db`` (streaming only; default 0); a blocking utterance is measured whole and
-        given one gain (``request.loudness_gain_db``), behind the seam join and in front of the stretch.
-        ``watermark`` (None: marked when the scheduler has a key; True without a key: ``ValueError``): the audio carries the
-        scheduler's watermark (watermark.py), added on the GPU last of the float stages: a stream in its codec pass behind the
-        stretch, a blocking utterance whole behind everything else.  ``request.watermark`` says whether it was.
-        ``trim_silence`` (cut the leading and trailing silence), ``max_pause_s`` (0.1 to 2.0: cap the pauses),
-        ``silence_threshold_db`` (-72 to -6 dBFS; default 2^-8; it needs one of the other two): silence trimming on the GPU
-        (trim.py), first of the stages: a stream in its codec pass, segment by segment in front of the seam; a blocking
-        utterance whole, each segment before the seam join (``request.trimmed_s`` is what was cut)."""
+        the text its start and end in seconds of the audio delivered -- once the request has ended.  The audio is not changed."""
         from ..config import RequestSampling, check_best_of, take_sampling
-        from ..request import parse_request
 
-        p = parse_request(text, stream, output_format, speed, container, segment, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db, timestamps=timestamps, peak_limit_db=peak_limit_db)
+        p = parse_request(text, stream, output_format, **options)
         self._check_trim(p)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
         check_best_of(resolved, self.B, stream=stream, segmented=p.plan is not None)
@@ -375,10 +361,8 @@ class BatchScheduler:
         if self._draining:
             raise RuntimeError("scheduler is not running: shutting down")
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
-                       output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice), speed_q=p.speed_q,
-                       container=p.container, seg=_Segmented(p.plan, resolved) if p.plan is not None else None,
-                       loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark), trim=p.trim_route,
-                       timestamps=p.timestamps, speed=p.speed, peak_limit_db=p.peak_limit_db, ceiling=p.ceiling)
+                       opts=p, sampling=resolved, voice_entry=self._voices.get(voice),
+                       seg=_Segmented(p.plan, resolved) if p.plan is not None else None, watermark=self._marks(p.watermark))
         if resolved.takes > 1:
             # the parent carries the audio options and the response; its takes are plain blocking requests, admitted as slots
             # come free
@@ -409,15 +393,11 @@ class BatchScheduler:
         return self.watermark is not None if asked is None else bool(asked)
 
     def submit_incremental(self, voice: str = "heart", max_new_tokens: Optional[int] = None, output_format: Optional[str] = None,
-                           sampling=None, speed: Optional[float] = None, container: Optional[str] = None, segment=True,
-                           loudness: Optional[float] = None, loudness_start_gain_db: Optional[float] = None,
-                           idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
-                           watermark: Optional[bool] = None, trim_silence: Optional[bool] = None,
-                           max_pause_s: Optional[float] = None, silence_threshold_db: Optional[float] = None,
-                           peak_limit_db: Optional[float] = None) -> IncrementalRequest:
+                           sampling=None, segment=True, idle_timeout_s: float = 10.0, flush_after_s: Optional[float] = None,
+                           **options) -> IncrementalRequest:
         """A stream whose text is not known yet: ``request.feed(text)`` as it arrives, ``request.close()`` at its end, the
-        chunks by iterating the request (or ``iter_chunks``).  The options are those of ``submit(stream=True, segment=...)``
-        (``segment``: True, a dict or a ``SegmentOptions``; it cannot be off).
+        chunks by iterating the request (or ``iter_chunks``).  ``output_format`` and ``options`` are those of
+        ``submit(stream=True, segment=...)`` (``segment``: True, a dict or a ``SegmentOptions``; it cannot be off).
 
         The text is cut by ``longform.IncrementalSplitter`` into the segments ``SegmentPlan.create`` gives the whole text, each
         handed over once no later input can change it, and spoken as a segmented stream whose segment list grows: the request
@@ -441,10 +421,8 @@ class BatchScheduler:
         from the whole text's."""
         from ..config import RequestSampling
         from ..longform import GrowingPlan, IncrementalSplitter, segment_options
-        from ..request import parse_request
 
-        p = parse_request("", True, output_format, speed, container, None, loudness, loudness_start_gain_db, watermark,
-                          trim_silence, max_pause_s, silence_threshold_db, peak_limit_db=peak_limit_db)
+        p = parse_request("", True, output_format, **options)
         self._check_trim(p)
         opts = segment_options(True if segment is None or segment is False else segment)
         if not float(idle_timeout_s) > 0.0 or (flush_after_s is not None and not float(flush_after_s) > 0.0):
@@ -456,10 +434,8 @@ class BatchScheduler:
         if self._dead is not None or self._draining:
             raise RuntimeError(f"scheduler is not running: {self._dead or 'shutting down'}")
         req = IncrementalRequest("", voice, True, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
-                                 output_format=p.output_format, sampling=resolved, voice_entry=self._voices.get(voice),
-                                 speed_q=p.speed_q, container=p.container, seg=_Segmented(GrowingPlan(opts), resolved),
-                                 loudness=p.loudness, start_gain_db=p.start_gain_db, watermark=self._marks(p.watermark),
-                                 trim=p.trim_route, sched=self, peak_limit_db=p.peak_limit_db, ceiling=p.ceiling,
+                                 opts=p, sampling=resolved, voice_entry=self._voices.get(voice),
+                                 seg=_Segmented(GrowingPlan(opts), resolved), watermark=self._marks(p.watermark), sched=self,
                                  inc=_Incremental(IncrementalSplitter(opts), float(idle_timeout_s),
                                                   None if flush_after_s is None else float(flush_after_s),
                                                   last_input=time.monotonic()))
@@ -698,7 +674,7 @@ class BatchScheduler:
                         prompt = sg.plan.prompt(sg.k, enc, prefix, sg.prev, req.max_new_tokens, self.session.max_seq)
                     else:
                         prompt = enc.build_prompt(req.text, req.voice, v.grid) if v is not None else self.tts._get_prompt(req.text, req.voice)
-                    if req.timestamps:  # the text's positions in the slot: of the whole prompt, a voice's speaker turns included
+                    if req.opts.timestamps:  # the text's positions in the slot: of the whole prompt, a voice's speaker turns included
                         from ..align import window_of
 
                         req.align_window = window_of(prompt[0], self.tts.tokenizer)
@@ -973,7 +949,7 @@ class BatchScheduler:
         s = self.session
         s.decode(self.tick)
         scoring = any(r.slot_sampling is not None and r.slot_sampling.scored for r in list(self._active.values()) + self._retiring)
-        measuring = any(r.timestamps for r in list(self._active.values()) + self._retiring)
+        measuring = any(r.opts.timestamps for r in list(self._active.values()) + self._retiring)
         snap = _Snapshot(s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no,
                          s.logprobs.clone() if scoring else None, s.alignment.clone() if measuring else None)
         snap.event.record(torch.cuda.current_stream())
@@ -1024,12 +1000,7 @@ class BatchScheduler:
                 self._stream_codec.reset_slots(sorted(set(restart)))
                 # (a segmented stream's later segments restart the codec only: its other stages run on)
                 fresh = [r for r in new if r.seg is None or r.seg.k == 0]
-                self._stream_conv.reset_slots([r.slot for r in fresh], [r.output_format for r in fresh],
-                                              [r.speed_q for r in fresh], [r.container for r in fresh],
-                                              [r.loudness for r in fresh], [r.start_gain_db for r in fresh],
-                                              [r.watermark for r in fresh] if self.watermark is not None else None,
-                                              [r.trim for r in fresh] if any(r.trim for r in fresh) else None,
-                                              [r.ceiling for r in fresh] if any(r.ceiling for r in fresh) else None)
+                self._stream_conv.start([r.slot for r in fresh], [r.opts for r in fresh], [r.watermark for r in fresh])
                 segd = [r for r in new if r.seg is not None]
                 if segd:
                     pauses, flags, leads = zip(*(r.seg.plan.seam_args(r.seg.k) for r in segd))
@@ -1126,7 +1097,7 @@ class BatchScheduler:
                 if scores is None:
                     raise RuntimeError("scheduler lost the scores of a request")
                 r.lp.append(scores[slot, r.emitted:n].copy())
-            if r.timestamps and n > r.emitted:
+            if r.opts.timestamps and n > r.emitted:
                 if align_rows is None:
                     raise RuntimeError("scheduler lost the alignment rows of a request")
                 r.al.append(align_rows[slot, r.emitted:n].copy())
@@ -1287,7 +1258,7 @@ class BatchScheduler:
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
                         self._counts["frames_delivered"] += n // 1920
-                elif not r.stream and (r.speed_q or r.loudness is not None or r.watermark or r.trim or r.ceiling):
+                elif not r.stream and (r.opts.speed_q or r.opts.loudness is not None or r.watermark or r.opts.trims or r.opts.peak_limit_db is not None):
                     # a blocking utterance with a trim, a speed, a loudness target, the mark or a ceiling: trimmed, levelled, stretched, marked and limited whole once
                     # its last pass is in
                     if n and not r.cancelled:
@@ -1295,7 +1266,7 @@ class BatchScheduler:
                         self._counts["frames_delivered"] += n // 1920
                     if fin and r.stretch_in and not r.cancelled:
                         r.stretch_in = [self._level(r, self._trimmed(r, np.concatenate(r.stretch_in)))]
-                        if r.speed_q:
+                        if r.opts.speed_q:
                             self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
                             continue
                         self._put(r, self._mark(r, r.stretch_in.pop()))
@@ -1330,7 +1301,7 @@ class BatchScheduler:
             pcm = seam_join(pcms, sg.plan.pauses, dev, lead=sg.plan.lead, trail=sg.plan.trail, joiner=self._block_seam)
         sg.pcm = []
         pcm = self._level(r, pcm)
-        if r.speed_q:
+        if r.opts.speed_q:
             r.stretch_in = [pcm]
             self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
             return
@@ -1340,7 +1311,7 @@ class BatchScheduler:
     def _trimmed(self, r: _Request, pcm: np.ndarray, flags: int = 3) -> np.ndarray:
         """A complete blocking utterance, or one segment of it with ``flags`` (default: first and final): a request that trims
         silence has it trimmed whole on the GPU (stages.trim_pcm, waited for here as the seam join is)."""
-        if r.trim is None:
+        if not r.opts.trims:
             return pcm
         from ..stages import SilenceTrimmer, trim_pcm
 
@@ -1348,7 +1319,7 @@ class BatchScheduler:
         with self._torch.cuda.stream(self._stretch_stream):
             if self._block_trim is None:
                 self._block_trim = SilenceTrimmer(dev, 1)
-            out = trim_pcm(pcm, flags, dev, *r.trim, trimmer=self._block_trim)
+            out = trim_pcm(pcm, flags, dev, *r.opts.trim_route, trimmer=self._block_trim)
         r.trimmed_s += (pcm.size - out.size) / 24000.0
         return out
 
@@ -1361,23 +1332,23 @@ class BatchScheduler:
 
             with self._torch.cuda.stream(self._stretch_stream):
                 pcm = watermark_embed(pcm, self.watermark, self.session.engine.device)
-        if r.peak_limit_db is not None:
+        if r.opts.peak_limit_db is not None:
             from ..stages import peak_limit
 
             with self._torch.cuda.stream(self._stretch_stream):
-                pcm, r.peak_reduction_db = peak_limit(pcm, r.peak_limit_db, self.session.engine.device)
+                pcm, r.peak_reduction_db = peak_limit(pcm, r.opts.peak_limit_db, self.session.engine.device)
         return pcm
 
     def _level(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
         """A complete blocking utterance (joined, not yet stretched): with a loudness target it is measured and scaled whole on
         the GPU (stages.loudness_normalize: two launches, waited for here as the seam join is)."""
-        if r.loudness is None:
+        if r.opts.loudness is None:
             return pcm
         from ..stages import loudness_normalize
         from ..loudness import gain_db
 
         with self._torch.cuda.stream(self._stretch_stream):
-            pcm, g = loudness_normalize(pcm, r.loudness, self.session.engine.device, with_gain=True, cap=r.peak_limit_db is None)
+            pcm, g = loudness_normalize(pcm, r.opts.loudness, self.session.engine.device, with_gain=True, cap=r.opts.peak_limit_db is None)
         r.loudness_gain_db = gain_db(g)
         return pcm
 
@@ -1432,7 +1403,7 @@ class BatchScheduler:
                     used.add(job.slot)
                     fresh.append(job)
             if fresh:
-                ts.reset_slots([j.slot for j in fresh], [j.req.speed_q for j in fresh])
+                ts.reset_slots([j.slot for j in fresh], [j.req.opts.speed_q for j in fresh])
             running = [j for j in self._stretches if j.state == "running"]
             batch = max(j.slot for j in running) + 1
             n_in = min(P, max(j.pcm.size - j.pos for j in running))
@@ -1529,7 +1500,7 @@ class BatchScheduler:
 
         rows = np.concatenate(r.al) if r.al else np.zeros((0, len(self.alignment_heads), 2), np.float32)
         F = min(rows.shape[0], r.audio_frames)
-        r.alignment = align(r.text, r.align_ids, rows[:F, :, 0], rows[:F, :, 1], self.tts.tokenizer, speed=r.speed,
+        r.alignment = align(r.text, r.align_ids, rows[:F, :, 0], rows[:F, :, 1], self.tts.tokenizer, speed=r.opts.speed,
                             duration_s=r.out_samples / 24000.0)
 
     def _end(self, r: _Request, e: Optional[Exception] = None) -> None:
@@ -1546,7 +1517,7 @@ class BatchScheduler:
         if not r.closed:
             r.closed = True
             self._counts["failed" if e is not None else ("cancelled" if r.cancelled else "completed")] += 1
-            if r.timestamps and e is None and not r.cancelled and r.align_ids is not None:
+            if r.opts.timestamps and e is None and not r.cancelled and r.align_ids is not None:
                 try:
                     self._aligned(r)
                 except Exception as err:  # (the request fails; the worker goes on)

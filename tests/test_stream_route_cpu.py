@@ -95,13 +95,13 @@ def _stand_ins(monkeypatch, log):
     def stage(name, width=0, count=0):
         class Stage:
             def __init__(self, *a):
-                log.append(("create", name))
+                log.append(("create", name, a))
 
             def reset_slots(self, slots, *a):
-                log.append(("reset", name))
+                log.append(("reset", name, list(slots), a))
 
             def start_segments(self, slots, *a):
-                log.append(("reset", name))
+                log.append(("reset", name, list(slots), a))
 
             def new_outputs(self, batch, n):
                 if name == "resample":
@@ -126,6 +126,8 @@ def _stand_ins(monkeypatch, log):
     monkeypatch.setattr(route, "TimeStretcher", stage("stretch", 32, 5))
     monkeypatch.setattr(route, "Resampler", stage("resample"))
     monkeypatch.setattr(route, "FlacEncoder", stage("flac"))
+    for cls in ("SilenceTrimmer", "LoudnessNormalizer", "Watermarker", "PeakLimiter"):
+        monkeypatch.setattr(route, cls, stage(cls))
     monkeypatch.setattr(route, "upload", lambda arrays, device: [torch.from_numpy(np.ascontiguousarray(a)) for a in arrays])
 
 
@@ -173,3 +175,55 @@ def test_run_executes_the_plan_and_the_pass_keeps_its_routes(monkeypatch):
     p = conv.run(pcm, 1920, valid, last=torch.zeros(5, dtype=torch.int32), slots=[4])
     p.host = p.dev
     assert p.chunk(4, False).tobytes() == stream_header(24000) and p.chunk(4, False).size == 0  # the header once per stream
+
+
+# ------------------------------------------------------------------------------- a route from a request's options
+def test_start_from_options_is_reset_slots_from_the_nine_lists(monkeypatch):
+    """Every (speed, format, FLAC) of ``COMBOS`` crossed with trim, loudness, watermark and limiter on and off: ``start`` from
+    the parsed requests leaves the routes ``reset_slots`` leaves from the nine lists (generation and owed header included), and
+    creates and resets the stages in the same order with the same arguments.  (``segmented`` is ``start_segments``' to set.)"""
+    from smoltts_amd import watermark as W
+    from smoltts_amd.request import parse_request
+
+    key = W.Watermark(0x0123456789ABCDEF, -26.0)
+    cases = []
+    for (_, q, fmt, fl), trim, loud, wm, lim in itertools.product(sorted(set((False,) + c[1:] for c in COMBOS)), (0, 1, 2), (0, 1, 2),
+                                                                  (False, True), (False, True)):
+        kw = dict(output_format=fmt, speed=q / 65536, container="flac" if fl else None)
+        kw.update([{}, dict(trim_silence=True), dict(max_pause_s=0.3, silence_threshold_db=-40.0)][trim])
+        kw.update([{}, dict(loudness=-20.0), dict(loudness=-16.0, loudness_start_gain_db=1.5)][loud])
+        if lim:
+            kw["peak_limit_db"] = -6.0
+        cases.append((parse_request("x", stream=True, **kw), wm))
+    assert len(cases) == 10 * 3 * 3 * 2 * 2
+    B = 7  # more than one batch of slots, restarted case after case: every slot's generation grows
+    logs, convs = ([], []), []
+    for log in logs:
+        _stand_ins(monkeypatch, log)
+        convs.append(engine.StreamConverter(torch.device("cpu"), B, 1920, watermark=key))
+    by_options, by_lists = convs
+    for i in range(0, len(cases), B - 2):
+        batch = cases[i:i + B - 2]
+        slots = [(i + 3 * k) % B for k in range(len(batch))]
+        opts, marked = [p for p, _ in batch], [wm for _, wm in batch]
+        _stand_ins(monkeypatch, logs[0])
+        by_options.start(slots, opts, marked)
+        _stand_ins(monkeypatch, logs[1])
+        by_lists.reset_slots(slots, [p.output_format for p in opts], [p.speed_q for p in opts], [p.container for p in opts],
+                             [p.loudness for p in opts], [p.start_gain_db for p in opts], marked,
+                             [p.trim_route for p in opts], [p.ceiling for p in opts])
+        assert by_options.routes == by_lists.routes
+        assert all(r.gen >= 1 and r.head_owed == r.flac for r in (by_options.routes[b] for b in slots))
+    assert logs[0] == logs[1] and len(logs[0]) > len(cases)
+    assert {e[1] for e in logs[0] if e[0] == "create"} == {"SilenceTrimmer", "LoudnessNormalizer", "Watermarker", "PeakLimiter",
+                                                            "resample", "stretch", "flac"}
+    routes = {by_options.routes[b] for b in range(B)}
+    assert max(r.gen for r in routes) > 1 and any(r.watermark_gain == key.gain for r in routes)
+    # a converter without a key refuses a marked slot from either entry point, and starts nothing
+    bare = engine.StreamConverter(torch.device("cpu"), 2, 1920)
+    for start in (lambda: bare.start([0], [cases[0][0]], [True]), lambda: bare.reset_slots([0], [None], [None], watermark=[True])):
+        with pytest.raises(ValueError, match="has no key"):
+            start()
+    assert bare.routes == [engine.SlotRoute()] * 2
+    bare.start([1], [parse_request("x", stream=True)])
+    assert bare.routes[1] == engine.SlotRoute(gen=1) and not bare.converts(1)
