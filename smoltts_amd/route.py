@@ -4,7 +4,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, replace
 from functools import cached_property
-from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -14,19 +14,52 @@ from .device import upload
 from .formats import ENC_OFF, ENC_ULAW, check_container, parse_stream_format
 from .request import SpeechOptions
 from .seam import THRESH
-from .stages import FlacEncoder, LoudnessNormalizer, PeakLimiter, Resampler, SeamJoiner, SilenceTrimmer, TimeStretcher, Watermarker
+from .stages import FlacEncoder, LoudnessNormalizer, PeakLimiter, Resampler, SeamJoiner, SilenceTrimmer, TimeStretcher, Watermarker  # noqa: F401  (STAGE_TABLE names them)
 from .tsm import out_bound
 
 
-STAGES = ("seam", "stretch", "resample", "flac")  # the stages every build has had, in launch order
-LAUNCH_ORDER = ("seam", "loudness", "stretch", "resample", "flac")  # the stages of a pass, in launch order
-PASS_ORDER = ("seam", "loudness", "stretch", "watermark", "resample", "flac")  # LAUNCH_ORDER with the watermark: what a pass runs by
-FLOAT_STAGES = ("seam", "loudness", "stretch", "watermark")  # fp32 in, fp32 out: the stages behind read their rows
-TRIM_ORDER = ("trim",) + PASS_ORDER  # PASS_ORDER behind the silence trim: what a pass is planned by
-TRIM_FLOAT_STAGES = ("trim",) + FLOAT_STAGES
-# TRIM_ORDER with the peak limiter, the last float stage: behind the watermark, in front of the conversion and the framing
-LIMIT_ORDER = ("trim",) + FLOAT_STAGES + ("limit", "resample", "flac")
-LIMIT_FLOAT_STAGES = TRIM_FLOAT_STAGES + ("limit",)
+class StageSpec(NamedTuple):
+    """One stage of a pass, as the route, the plan and the converter know it."""
+    name: str        # its name in a plan
+    attr: str        # the converter attribute that holds its instance
+    cls: str         # its class: looked up in this module when the stage is made
+    fp32: bool       # fp32 in, fp32 out: the stages behind read its rows
+    on: Callable     # (route) -> whether a slot with that route goes through it
+    start: Callable  # (stage, slots, their new routes): start the new streams in it; a slot that does not use it is switched off
+    args: Callable = lambda conv: ()  # (converter) -> what its constructor takes behind (device, max_batch)
+    call: str = "chunk"               # the method a pass calls
+
+
+# The stages of a pass in launch order, the one place that lists them: the watermark behind the stretch (a speed does not rescale
+# the chips), the limiter the last float stage (nothing behind it can raise a peak again), then the conversion and the framing.
+STAGE_TABLE = (
+    StageSpec("trim", "tr", "SilenceTrimmer", True, lambda r: r.trims,  # (a plain stream is one segment, the first and the last)
+              lambda st, slots, rs: st.start_segments(slots, [SEAM_FIRST | SEAM_FINAL if r.trims else SEAM_OFF for r in rs],
+                                                      [r.trim for r in rs], [r.pause_blocks for r in rs], [r.thr for r in rs])),
+    StageSpec("seam", "sj", "SeamJoiner", True, lambda r: r.segmented,  # (no new stream is segmented: ``start_segments`` makes it)
+              lambda st, slots, rs: st.start_segments(slots, [0] * len(slots), [SEAM_OFF] * len(slots))),
+    StageSpec("loudness", "ln", "LoudnessNormalizer", True, lambda r: r.loudness is not None,
+              lambda st, slots, rs: st.reset_slots(slots, [r.loudness for r in rs], [r.start_gain_db for r in rs])),
+    StageSpec("stretch", "ts", "TimeStretcher", True, lambda r: r.speed_q != 65536,
+              lambda st, slots, rs: st.reset_slots(slots, [r.speed_q for r in rs])),
+    StageSpec("watermark", "wm", "Watermarker", True, lambda r: r.watermark_gain > 0.0,
+              lambda st, slots, rs: st.reset_slots(slots, [r.watermark_gain for r in rs]), lambda conv: (conv.watermark,)),
+    StageSpec("limit", "lim", "PeakLimiter", True, lambda r: r.ceiling > 0.0,
+              lambda st, slots, rs: st.reset_slots(slots, [r.ceiling for r in rs]), call="run"),  # (``run``: rows of any width)
+    StageSpec("resample", "rs", "Resampler", False, lambda r: r.enc != ENC_OFF,
+              lambda st, slots, rs: st.reset_slots(slots, [r.format for r in rs]), lambda conv: (out_bound(conv.n_in),)),
+    StageSpec("flac", "fl", "FlacEncoder", False, lambda r: r.flac,
+              lambda st, slots, rs: st.reset_slots(slots, [r.rate for r in rs], [
+                  FLAC_OFF if not r.flac else (FLAC_F32 if r.enc == ENC_OFF else FLAC_S16) for r in rs])),
+)
+END_MARKERS = {s.name: globals()[s.cls].END_MARKERS for s in STAGE_TABLE}  # stage -> the end markers its class declares
+LIMIT_ORDER = tuple(s.name for s in STAGE_TABLE)
+LIMIT_FLOAT_STAGES = tuple(s.name for s in STAGE_TABLE if s.fp32)
+# Historical names, kept for callers: the orders before the limiter, the trim, the watermark and the loudness stage came.
+TRIM_ORDER, TRIM_FLOAT_STAGES = (tuple(s for s in o if s != "limit") for o in (LIMIT_ORDER, LIMIT_FLOAT_STAGES))
+PASS_ORDER, FLOAT_STAGES = (tuple(s for s in o if s != "trim") for o in (TRIM_ORDER, TRIM_FLOAT_STAGES))
+LAUNCH_ORDER = tuple(s for s in PASS_ORDER if s != "watermark")
+STAGES = tuple(s for s in LAUNCH_ORDER if s != "loudness")
 
 
 @dataclass(frozen=True)
@@ -52,9 +85,7 @@ class SlotRoute:
     @cached_property
     def stages(self) -> Tuple[str, ...]:
         """The stages the slot goes through, in launch order."""
-        on = (self.trims, self.segmented, self.loudness is not None, self.speed_q != 65536, self.watermark_gain > 0.0,
-              self.ceiling > 0.0, self.enc != ENC_OFF, self.flac)
-        return tuple(s for s, o in zip(LIMIT_ORDER, on) if o)
+        return tuple(s.name for s in STAGE_TABLE if s.on(self))
 
     @property
     def trims(self) -> bool:
@@ -105,26 +136,20 @@ def plan_pass(routes: Dict[int, SlotRoute]) -> PassPlan:
 
 
 class StreamConverter:
-    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch`` (``SlotRoute``, ``LIMIT_ORDER``): a
-    slot that trims silence goes through the trim stage first (``SilenceTrimmer``), segment by segment, a segmented slot (``start_segments``) is joined by the seam stage (``SeamJoiner``), a slot with a speed is time-stretched
-    (``TimeStretcher``), a marked slot gets the watermark of the converter's key last of the float stages (``Watermarker``:
-    behind the stretch, so that a speed does not rescale the chips), a slot with a ceiling is peak-limited behind that
-    (``PeakLimiter``: the last float stage, so that nothing behind it can raise a peak again), a slot with an output format is converted (``Resampler``), and a slot with a FLAC container is framed
-    (``FlacEncoder``, from the resampler's int16, or from the float32 at 24 kHz); each stage reads the output of the one in
-    front, and the state of the stages behind the seam carries from segment to segment.  Each stage is created the first time
-    a slot needs it (``seam``: the seam stage at once).  ``n_in``: codec samples per slot and call."""
+    """What a stream's PCM goes through behind its codec decode, per slot of ``max_batch``: the stages of ``STAGE_TABLE`` that
+    its route (``SlotRoute``) switches on, in the table's order.  Each stage reads the output of the one in front: the float
+    stages hand on float32 rows, FLAC frames the resampler's int16, or the float32 at 24 kHz.  A slot that trims goes through
+    the trim stage segment by segment, and the state of the stages behind the seam carries from segment to segment.  Each stage
+    is created the first time a slot needs it (``seam``: the seam stage at once) and held in the table's attribute (``tr``,
+    ``sj``, ``ln``, ``ts``, ``wm``, ``lim``, ``rs``, ``fl``; None until then).  ``n_in``: codec samples per slot and call."""
 
     def __init__(self, device: torch.device, max_batch: int, n_in: int, seam: bool = False, watermark=None):
         self.device, self.B, self.n_in = device, max_batch, n_in
         self.watermark = watermark  # a watermark.Watermark: the one key of this converter's marked slots (None: no slot may ask)
-        self.wm: Optional[Watermarker] = None
-        self.rs: Optional[Resampler] = None
-        self.ts: Optional[TimeStretcher] = None
-        self.fl: Optional[FlacEncoder] = None
-        self.sj: Optional[SeamJoiner] = SeamJoiner(device, max_batch) if seam else None
-        self.ln: Optional[LoudnessNormalizer] = None
-        self.tr: Optional[SilenceTrimmer] = None
-        self.lim: Optional[PeakLimiter] = None
+        for s in STAGE_TABLE:
+            setattr(self, s.attr, None)
+        if seam:
+            self.sj = SeamJoiner(device, max_batch)
         self.routes = [SlotRoute()] * max_batch
         self._plan: Optional[PassPlan] = None  # the last pass's plan
 
@@ -170,38 +195,13 @@ class StreamConverter:
 
     def _start(self, slots: Sequence[int], routes: Sequence[SlotRoute]) -> None:
         """The new streams' stages, each created the first time a route needs it, then reset for every slot in ``slots``."""
-        if self.tr is None and any(r.trims for r in routes):
-            self.tr = SilenceTrimmer(self.device, self.B)
-        if self.tr is not None:  # (a plain stream is one segment, the first and the last)
-            self.tr.start_segments(slots, [SEAM_FIRST | SEAM_FINAL if r.trims else SEAM_OFF for r in routes], [r.trim for r in routes],
-                                   [r.pause_blocks for r in routes], [r.thr for r in routes])
-        if self.ln is None and any(r.loudness is not None for r in routes):
-            self.ln = LoudnessNormalizer(self.device, self.B)
-        if self.ln is not None:
-            self.ln.reset_slots(slots, [r.loudness for r in routes], [r.start_gain_db for r in routes])
-        if self.wm is None and any(r.watermark_gain > 0.0 for r in routes):
-            self.wm = Watermarker(self.device, self.B, self.watermark)
-        if self.wm is not None:
-            self.wm.reset_slots(slots, [r.watermark_gain for r in routes])
-        if self.lim is None and any(r.ceiling > 0.0 for r in routes):
-            self.lim = PeakLimiter(self.device, self.B)
-        if self.lim is not None:
-            self.lim.reset_slots(slots, [r.ceiling for r in routes])
-        if self.rs is None and any(r.enc != ENC_OFF for r in routes):
-            self.rs = Resampler(self.device, self.B, out_bound(self.n_in))
-        if self.ts is None and any(r.speed_q != 65536 for r in routes):
-            self.ts = TimeStretcher(self.device, self.B)
-        if self.fl is None and any(r.flac for r in routes):
-            self.fl = FlacEncoder(self.device, self.B)
-        if self.rs is not None:
-            self.rs.reset_slots(slots, [r.format for r in routes])
-        if self.ts is not None:
-            self.ts.reset_slots(slots, [r.speed_q for r in routes])
-        if self.fl is not None:
-            self.fl.reset_slots(slots, [r.rate for r in routes],
-                                [FLAC_OFF if not r.flac else (FLAC_F32 if r.enc == ENC_OFF else FLAC_S16) for r in routes])
-        if self.sj is not None:
-            self.sj.start_segments(slots, [0] * len(slots), [SEAM_OFF] * len(slots))
+        for s in STAGE_TABLE:
+            stage = getattr(self, s.attr)
+            if stage is None and any(s.on(r) for r in routes):
+                stage = globals()[s.cls](self.device, self.B, *s.args(self))
+                setattr(self, s.attr, stage)
+            if stage is not None:
+                s.start(stage, slots, routes)
         for b, r in zip(slots, routes):
             self.routes[b] = r
 
@@ -232,10 +232,9 @@ class StreamConverter:
         return p
 
     def ends(self, slots: Sequence[int]):
-        """The end markers a pass over ``slots`` needs: (``last``: some slot has a speed, FLAC, segments, a trim or a limiter;
-        ``seg_end``: some slot has segments or a trim)."""
-        stages = self.plan(slots).stages
-        return any(s in stages for s in ("trim", "seam", "stretch", "limit", "flac")), "seam" in stages or "trim" in stages
+        """The end markers a pass over ``slots`` needs, (``last``, ``seg_end``): those that a planned stage's class declares."""
+        need = {m for s in self.plan(slots).stages for m in END_MARKERS[s]}
+        return "last" in need, "seg_end" in need
 
     def _through(self, plan: PassPlan, stage: str, out: torch.Tensor, counts: torch.Tensor, pcm: torch.Tensor, n_in: int,
                  valid: torch.Tensor) -> torch.Tensor:
@@ -252,39 +251,21 @@ class StreamConverter:
 
     def run(self, pcm: torch.Tensor, n_in: int, valid: torch.Tensor, last: Optional[torch.Tensor] = None,
             slots: Optional[Sequence[int]] = None, seg_end: Optional[torch.Tensor] = None) -> Optional["StreamPass"]:
-        """Queue the stages for ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in]) on the current stream.
-        ``valid`` (device int32 [batch]): the samples of each row that are real; ``last`` / ``seg_end`` (device int32 [batch],
-        needed as ``ends`` says): nonzero where the row's stream / segment ends with this call.  ``slots``: the live streams
-        (default: every slot); the others consume what ``valid`` gives them and are never read.  None when no live slot
-        converts: no launch."""
+        """Queue the planned stages, in ``STAGE_TABLE``'s order (the float stages, then the resampler and FLAC), for ``n_in``
+        samples of every row of ``pcm`` (device fp32 [batch, >= n_in]) on the current stream.  ``valid`` (device int32 [batch]):
+        the samples of each row that are real; ``last`` / ``seg_end`` (device int32 [batch], needed as ``ends`` says): nonzero
+        where the row's stream / segment ends with this call.  ``slots``: the live streams (default: every slot); the others
+        consume what ``valid`` gives them and are never read.  None when no live slot converts: no launch."""
         plan = self.plan(range(self.B) if slots is None else slots)
         if not plan.stages:
             return None
-        batch, outs = pcm.shape[0], {}
-        if "trim" in plan.stages:
-            out, counts = outs["trim"] = self.tr.new_outputs(batch, n_in)
-            self.tr.chunk(pcm, n_in, out, counts, valid=valid, seg_end=seg_end, last=last)
-            valid, pcm, n_in = self._through(plan, "trim", out, counts, pcm, n_in, valid), out, out.shape[1]
-        if "seam" in plan.stages:  # (each float stage's rows, counts and width are what the stages behind it read)
-            out, counts = outs["seam"] = self.sj.new_outputs(batch, n_in)
-            self.sj.chunk(pcm, n_in, out, counts, valid=valid, seg_end=seg_end, last=last)
-            valid, pcm, n_in = self._through(plan, "seam", out, counts, pcm, n_in, valid), out, out.shape[1]
-        if "loudness" in plan.stages:
-            out, counts = outs["loudness"] = self.ln.new_outputs(batch, n_in)
-            self.ln.chunk(pcm, n_in, out, counts, valid=valid)
-            valid, pcm, n_in = self._through(plan, "loudness", out, counts, pcm, n_in, valid), out, out.shape[1]
-        if "stretch" in plan.stages:
-            out, counts = outs["stretch"] = self.ts.new_outputs(batch, n_in)
-            self.ts.chunk(pcm, n_in, out, counts, valid=valid, last=last)
-            valid, pcm, n_in = self._through(plan, "stretch", out, counts, pcm, n_in, valid), out, out.shape[1]
-        if "watermark" in plan.stages:
-            out, counts = outs["watermark"] = self.wm.new_outputs(batch, n_in)
-            self.wm.chunk(pcm, n_in, out, counts, valid=valid)
-            valid, pcm, n_in = self._through(plan, "watermark", out, counts, pcm, n_in, valid), out, out.shape[1]
-        if "limit" in plan.stages:
-            out, counts = outs["limit"] = self.lim.new_outputs(batch, n_in)
-            self.lim.run(pcm, n_in, out, counts, valid, last)
-            valid, pcm, n_in = self._through(plan, "limit", out, counts, pcm, n_in, valid), out, out.shape[1]
+        batch, outs, ends = pcm.shape[0], {}, {"seg_end": seg_end, "last": last}
+        for s in STAGE_TABLE:  # (each float stage's rows, counts and width are what the stages behind it read)
+            if s.fp32 and s.name in plan.rows:
+                stage = getattr(self, s.attr)
+                out, counts = outs[s.name] = stage.new_outputs(batch, n_in)
+                getattr(stage, s.call)(pcm, n_in, out, counts, valid=valid, **{m: ends[m] for m in END_MARKERS[s.name]})
+                valid, pcm, n_in = self._through(plan, s.name, out, counts, pcm, n_in, valid), out, out.shape[1]
         if "resample" in plan.stages:
             out, counts = outs["resample"] = self.rs.new_outputs(batch, n_in)
             self.rs.chunk(pcm, n_in, out, counts, valid=valid)
@@ -295,10 +276,10 @@ class StreamConverter:
         return StreamPass(self, {s: outs[s] for s in plan.host}, plan)
 
     def close(self):
-        for stage in (self.rs, self.ts, self.fl, self.sj, self.ln, self.wm, self.tr, self.lim):
-            if stage is not None:
-                stage.close()
-        self.rs = self.ts = self.fl = self.sj = self.ln = self.wm = self.tr = self.lim = None
+        for s in STAGE_TABLE:
+            if getattr(self, s.attr) is not None:
+                getattr(self, s.attr).close()
+                setattr(self, s.attr, None)
 
 
 class StreamPass:

@@ -32,6 +32,7 @@ class _Stage(ClosesOnDel):
     ``smoltts_<C_NAME>_create`` lives in, destroyed by ``close`` once the device is idle, and the checks of a ``chunk`` call."""
 
     C_NAME = ""
+    END_MARKERS: Tuple[str, ...] = ()  # the end markers the stage's ``chunk`` takes, of ``seg_end`` and ``last``, in the C call's order
 
     def __init__(self, device: torch.device, max_batch: int):
         self.lib = load_library()
@@ -86,6 +87,44 @@ class _Stage(ClosesOnDel):
             self.handle = None
 
 
+class _FloatStage(_Stage):
+    """A stage that reads fp32 rows and writes fp32 rows, so that the stage behind it can read them: one ``chunk`` for all of
+    them.  A class declares the end markers its C call takes (``END_MARKERS``)."""
+
+    def _width(self, n_in: int) -> int:
+        """The least width of ``out`` in a call of ``n_in`` input samples."""
+        return self.out_samples(n_in)
+
+    def _chunk_args(self) -> tuple:
+        """What the stage's chunk call takes between the end markers and ``out``."""
+        return ()
+
+    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
+              seg_end: Optional[torch.Tensor] = None, last: Optional[torch.Tensor] = None) -> None:
+        """Run ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) through the stage on the
+        current stream.  ``valid``: device int32 [batch], the samples of each row that are real; ``seg_end`` / ``last``: device
+        int32 [batch], nonzero where the row's segment / stream ends with this call (a stage takes the ones it declares, and
+        refuses another).  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
+        given = {"seg_end": seg_end, "last": last}
+        assert all(t is None or m in self.END_MARKERS for m, t in given.items()), f"{type(self).__name__} takes {self.END_MARKERS}"
+        ends = [given[m] for m in self.END_MARKERS]
+        batch = pcm.shape[0]
+        self._check(batch, pcm, n_in, out, torch.float32, self._width(n_in), counts, 1, valid, *ends)
+        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), *map(dptr, ends), *self._chunk_args(), dptr(out),
+                   out.shape[1], dptr(counts))
+
+
+class _SameLengthStage(_FloatStage):
+    """A float stage whose slots emit exactly the samples they read: no end marker."""
+
+    def out_samples(self, n_in: int) -> int:
+        """A slot emits what it reads (one sample of room for an empty call)."""
+        return max(int(n_in), 1)
+
+    def _width(self, n_in: int) -> int:
+        return n_in
+
+
 class Resampler(_Stage):
     """Per-slot conversion of streamed 24 kHz fp32 PCM to ``pcm_<rate>`` int16 / ``ulaw_8000`` bytes on the GPU
     (include/smoltts_hip.h, "Streamed output formats"): one launch per call for every slot, each at its own format.  Slots
@@ -131,24 +170,16 @@ class Resampler(_Stage):
 
 
 # ------------------------------------------------------------------------------- speaking speed
-class TimeStretcher(_Stage):
+class TimeStretcher(_FloatStage):
     """Per-slot pitch-preserving time stretch of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Speaking speed";
     the numpy model is ``tsm.Stretcher``): one launch per call for every slot, each at its own speed.  Slots start off;
-    ``reset_slots`` starts a new stream in a slot at its ``speed_q`` (65536: off)."""
+    ``reset_slots`` starts a new stream in a slot at its ``speed_q`` (65536: off).  A slot flushes with ``last``."""
 
     C_NAME = "tsm"
+    END_MARKERS = ("last",)
 
     def reset_slots(self, slots: Sequence[int], speed_q: Sequence[int]) -> None:
         self._call("reset_slots", self._ints(slots), self._ints(speed_q), len(slots))
-
-    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
-              last: Optional[torch.Tensor] = None) -> None:
-        """Stretch ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream.
-        ``valid``: device int32 [batch], the samples of each row that are real; ``last``: device int32 [batch], nonzero where the
-        row's stream ends with this call (the slot flushes).  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
-        batch = pcm.shape[0]
-        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, last)
-        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(last), dptr(out), out.shape[1], dptr(counts))
 
     def slot_state(self, slot: int) -> dict:
         """Slot ``slot``'s counters (synchronises the current stream): k (next segment), p_prev, n_in, n_out, ended."""
@@ -187,13 +218,14 @@ def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device) -> np.ndarr
 
 
 # ------------------------------------------------------------------------------- silence: trimmed ends, capped pauses
-class SilenceTrimmer(_Stage):
+class SilenceTrimmer(_FloatStage):
     """Per-slot silence trimming of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Trim"; the numpy model is
-    ``trim.TrimState``): one launch per call for every slot.  Slots start off; ``start_segments`` opens a segment in a slot with
-    its flags (``SEAM_FIRST`` / ``SEAM_FINAL``; ``SEAM_OFF`` switches the slot off), whether its ends are trimmed, its pause cap
-    in blocks and its threshold."""
+    ``trim.TrimState``): one launch per call, of at most ``trim.MAX_CALL`` samples, for every slot.  Slots start off;
+    ``start_segments`` opens a segment in a slot with its flags (``SEAM_FIRST`` / ``SEAM_FINAL``; ``SEAM_OFF`` switches the slot
+    off), whether its ends are trimmed, its pause cap in blocks and its threshold; ``seg_end`` / ``last`` end it."""
 
     C_NAME = "trim"
+    END_MARKERS = ("seg_end", "last")
 
     def start_segments(self, slots: Sequence[int], flags: Sequence[int], trims: Sequence[bool], pauses: Sequence[int],
                        thrs: Sequence[float]) -> None:
@@ -202,17 +234,6 @@ class SilenceTrimmer(_Stage):
             return
         self._call("reset_slots", self._ints(slots), self._ints(flags), self._ints([bool(t) for t in trims]), self._ints(pauses),
                    (C.c_float * n)(*[float(t) for t in thrs]), n)
-
-    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
-              seg_end: Optional[torch.Tensor] = None, last: Optional[torch.Tensor] = None) -> None:
-        """Trim ``n_in`` samples (at most ``trim.MAX_CALL``) of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous
-        rows) on the current stream.  ``valid``: device int32 [batch], the real samples of each row; ``seg_end`` / ``last``:
-        device int32 [batch], nonzero where the row's segment ends with this call.  ``counts[b]``: the samples slot b wrote to
-        ``out[b]``."""
-        batch = pcm.shape[0]
-        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, seg_end, last)
-        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(seg_end), dptr(last), dptr(out), out.shape[1],
-                   dptr(counts))
 
     def slot_state(self, slot: int) -> dict:
         """Slot ``slot``'s state (synchronises the current stream): ``trim.TrimState.COUNTERS`` in samples, and open."""
@@ -251,12 +272,13 @@ def trim_pcm(pcm: np.ndarray, flags: int, device: torch.device, trim: bool = Tru
 
 
 # ------------------------------------------------------------------------------- long texts: the seam between segments
-class SeamJoiner(_Stage):
+class SeamJoiner(_FloatStage):
     """Per-slot joining of a long text's segments on the GPU (include/smoltts_hip.h, "Seam"; the numpy model is
     ``seam.SeamState``): one launch per call for every slot.  Slots start off; ``start_segments`` opens a segment in a slot with
     its pause and flags (``SEAM_FIRST`` / ``SEAM_FINAL``; ``SEAM_OFF`` switches the slot off)."""
 
     C_NAME = "seam"
+    END_MARKERS = ("seg_end", "last")
 
     def __init__(self, device: torch.device, max_batch: int):
         super().__init__(device, max_batch)
@@ -278,15 +300,8 @@ class SeamJoiner(_Stage):
         for b, p, f, ld in zip(slots, pauses, flags, leads):
             self.zeros[b] = 0 if int(f) & SEAM_OFF else int(p) + (int(ld) if int(f) & SEAM_FIRST else 0)
 
-    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
-              seg_end: Optional[torch.Tensor] = None, last: Optional[torch.Tensor] = None) -> None:
-        """Join ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream.
-        ``valid``: device int32 [batch], the real samples of each row; ``seg_end`` / ``last``: device int32 [batch], nonzero where
-        the row's segment / stream ends with this call.  ``counts[b]``: the samples slot b wrote to ``out[b]``."""
-        batch = pcm.shape[0]
-        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, seg_end, last)
-        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(seg_end), dptr(last), max(self.zeros), dptr(out),
-                   out.shape[1], dptr(counts))
+    def _chunk_args(self) -> tuple:
+        return (max(self.zeros),)
 
     def slot_state(self, slot: int) -> dict:
         """Slot ``slot``'s state (synchronises the current stream): n_in, judged, ec, head, open, lead, pause, flags."""
@@ -319,10 +334,11 @@ def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: tor
 
 
 # ------------------------------------------------------------------------------- loudness
-class LoudnessNormalizer(_Stage):
+class LoudnessNormalizer(_SameLengthStage):
     """Per-slot loudness normalisation of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Loudness"; the numpy
     model is ``loudness.StreamState``): one launch per call for every slot, each towards its own target.  A slot emits exactly
-    the samples it reads.  Slots start off; ``reset_slots`` starts a new stream in a slot (target None: off)."""
+    the samples it reads: ``counts[b]`` is its valid ones, 0 for a slot that is off.  Slots start off; ``reset_slots`` starts a
+    new stream in a slot (target None: off)."""
 
     C_NAME = "loudness"
 
@@ -345,18 +361,6 @@ class LoudnessNormalizer(_Stage):
         power = (C.c_double * n)(*[0.0 if t is None else target_power(t) for t in targets])
         knots = self._ints([knot_of_db(g or 0.0) for g in (start_gain_db or [0.0] * n)])
         self._call("reset_slots", self._ints(slots), power, knots, n)
-
-    def out_samples(self, n_in: int) -> int:
-        """A slot emits what it reads (one sample of room for an empty call)."""
-        return max(int(n_in), 1)
-
-    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
-        """Normalise ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current
-        stream.  ``valid``: device int32 [batch], the real samples of each row.  ``counts[b]``: the samples slot b wrote to
-        ``out[b]`` (its valid ones; 0 for a slot that is off)."""
-        batch = pcm.shape[0]
-        self._check(batch, pcm, n_in, out, torch.float32, n_in, counts, 1, valid)
-        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1], dptr(counts))
 
     def measure(self, row: torch.Tensor, n: int) -> Tuple[float, float]:
         """(gated mean power, peak) of the whole utterance ``row[:n]`` (device fp32, contiguous); waits for the result."""
@@ -423,10 +427,11 @@ def loudness_normalize(pcm: np.ndarray, target: float, device: torch.device, wit
 
 
 # ------------------------------------------------------------------------------- watermark
-class Watermarker(_Stage):
+class Watermarker(_SameLengthStage):
     """Per-slot watermarking of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Watermark"; the numpy model is
     ``watermark.StreamState``): one launch per call for every slot.  One key per stage: its chip table is uploaded here.  A slot
-    emits exactly the samples it reads.  Slots start off; ``reset_slots`` starts a new stream in a slot (gain 0: off)."""
+    emits exactly the samples it reads: ``counts[b]`` is its valid ones, 0 for a slot that is off, whose row is left alone.
+    Slots start off; ``reset_slots`` starts a new stream in a slot (gain 0: off)."""
 
     C_NAME = "watermark"
 
@@ -445,18 +450,6 @@ class Watermarker(_Stage):
         if not n:
             return
         self._call("reset_slots", self._ints(slots), (C.c_double * n)(*[float(g) for g in gains]), n)
-
-    def out_samples(self, n_in: int) -> int:
-        """A slot emits what it reads (one sample of room for an empty call)."""
-        return max(int(n_in), 1)
-
-    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
-        """Mark ``n_in`` samples of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous rows) on the current stream.
-        ``valid``: device int32 [batch], the real samples of each row.  ``counts[b]``: the samples slot b wrote to ``out[b]``
-        (its valid ones; 0 for a slot that is off, whose row is left alone)."""
-        batch = pcm.shape[0]
-        self._check(batch, pcm, n_in, out, torch.float32, n_in, counts, 1, valid)
-        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(out), out.shape[1], dptr(counts))
 
     def embed(self, row: torch.Tensor, n: int, gain: float, out: torch.Tensor) -> None:
         """``out[:n]``: the whole utterance ``row[:n]`` (device fp32, contiguous) marked from position 0, on the current stream."""
@@ -488,13 +481,15 @@ def watermark_embed(pcm: np.ndarray, wm, device: torch.device) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------- peak limiter
-class PeakLimiter(_Stage):
+class PeakLimiter(_FloatStage):
     """Per-slot look-ahead peak limiting of streamed 24 kHz fp32 PCM on the GPU (include/smoltts_hip.h, "Limiter"; the numpy
-    model is ``limiter.StreamState``): one launch per call for every slot, each under its own ceiling.  A slot holds back
-    ``limiter.HOLD_BACK`` samples until its stream ends.  Slots start off; ``reset_slots`` starts a new stream in a slot
+    model is ``limiter.StreamState``): one launch per call, of at most ``limiter.MAX_CALL`` samples, for every slot, each under
+    its own ceiling.  A slot holds back ``limiter.HOLD_BACK`` samples until its stream ends (``last``: it flushes); the row of a
+    slot that is off is left alone, with a count of 0.  Slots start off; ``reset_slots`` starts a new stream in a slot
     (ceiling 0: off)."""
 
     C_NAME = "limiter"
+    END_MARKERS = ("last",)
 
     def _create_args(self) -> tuple:
         from .limiter import packed
@@ -509,16 +504,6 @@ class PeakLimiter(_Stage):
         if not n:
             return
         self._call("reset_slots", self._ints(slots), (C.c_double * n)(*[float(c) for c in ceilings]), n)
-
-    def chunk(self, pcm: torch.Tensor, n_in: int, out: torch.Tensor, counts: torch.Tensor, valid: Optional[torch.Tensor] = None,
-              last: Optional[torch.Tensor] = None) -> None:
-        """Limit ``n_in`` samples (at most ``limiter.MAX_CALL``) of every row of ``pcm`` (device fp32 [batch, >= n_in], contiguous
-        rows) on the current stream.  ``valid``: device int32 [batch], the real samples of each row; ``last``: device int32
-        [batch], nonzero where the row's stream ends with this call (the slot flushes).  ``counts[b]``: the samples slot b
-        wrote to ``out[b]`` (0 for a slot that is off, whose row is left alone)."""
-        batch = pcm.shape[0]
-        self._check(batch, pcm, n_in, out, torch.float32, self.out_samples(n_in), counts, 1, valid, last)
-        self._call("chunk", dptr(pcm), pcm.stride(0), batch, n_in, dptr(valid), dptr(last), dptr(out), out.shape[1], dptr(counts))
 
     def out_samples(self, n_in: int) -> int:
         """Output samples per row of a pass of ``n_in`` input samples (``run``): what the C call says up to the most one call
@@ -595,6 +580,7 @@ class FlacEncoder(_Stage):
     Slots start off; ``reset_slots`` starts a new stream in a slot.  The stream header (``flac.stream_header``) is the caller's."""
 
     C_NAME = "flac"
+    END_MARKERS = ("last",)
 
     def reset_slots(self, slots: Sequence[int], rates: Sequence[int], sources: Sequence[int]) -> None:
         """Start new streams in ``slots`` at their rate and source (``FLAC_F32`` / ``FLAC_S16``; ``FLAC_OFF``: off)."""

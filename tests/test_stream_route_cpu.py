@@ -1,7 +1,8 @@
 """The routing of the stream stages behind the codec, host side (no GPU, no library): ``engine.plan_pass`` over batches that mix
 plain slots with every allowed combination of segments, speed, format and FLAC, checked against the rules the converter has
 always followed; and ``StreamConverter.run`` executing a plan on stand-in stages (CPU tensors), with the per-slot snapshot a
-pass keeps while its slots are restarted."""
+pass keeps while its slots are restarted; and the stage table (``route.STAGE_TABLE``) as the single source of the routes, the
+end markers and the calls of a pass over all eight stages."""
 import itertools
 
 import numpy as np
@@ -113,6 +114,8 @@ def _stand_ins(monkeypatch, log):
             def chunk(self, *a, **k):
                 log.append(("chunk", name, a, k))
 
+            run = chunk  # (the limiter's entry for rows of any width)
+
             def slot_bytes(self, out, counts, b, tail=False, enc=None):
                 return ("bytes", b, enc)
 
@@ -126,8 +129,8 @@ def _stand_ins(monkeypatch, log):
     monkeypatch.setattr(route, "TimeStretcher", stage("stretch", 32, 5))
     monkeypatch.setattr(route, "Resampler", stage("resample"))
     monkeypatch.setattr(route, "FlacEncoder", stage("flac"))
-    for cls in ("SilenceTrimmer", "LoudnessNormalizer", "Watermarker", "PeakLimiter"):
-        monkeypatch.setattr(route, cls, stage(cls))
+    for cls, width, count in (("SilenceTrimmer", 8, 11), ("LoudnessNormalizer", 0, 13), ("Watermarker", 0, 17), ("PeakLimiter", 126, 19)):
+        monkeypatch.setattr(route, cls, stage(cls, width, count))
     monkeypatch.setattr(route, "upload", lambda arrays, device: [torch.from_numpy(np.ascontiguousarray(a)) for a in arrays])
 
 
@@ -143,8 +146,8 @@ def test_run_executes_the_plan_and_the_pass_keeps_its_routes(monkeypatch):
 
     conv.reset_slots([1, 2, 4], ["pcm_16000", None, "pcm_24000"], [None, 32768, None], [None, None, "flac"])
     conv.start_segments([3], [480], [engine.SEAM_FIRST], [240])
-    assert [e[:2] for e in log] == [("create", "resample"), ("create", "stretch"), ("create", "flac"), ("reset", "resample"),
-                                    ("reset", "stretch"), ("reset", "flac"), ("create", "seam"), ("reset", "seam")]
+    assert [e[:2] for e in log] == [("create", "stretch"), ("reset", "stretch"), ("create", "resample"), ("reset", "resample"),
+                                    ("create", "flac"), ("reset", "flac"), ("create", "seam"), ("reset", "seam")]  # (launch order)
     assert [conv.converts(b) for b in range(5)] == [False, True, True, True, True]
     assert conv.ends([0, 1]) == (False, False) and conv.ends([0, 2]) == (True, False) and conv.ends([4]) == (True, False)
     assert conv.ends([1, 3]) == (True, True)
@@ -227,3 +230,144 @@ def test_start_from_options_is_reset_slots_from_the_nine_lists(monkeypatch):
     assert bare.routes == [engine.SlotRoute()] * 2
     bare.start([1], [parse_request("x", stream=True)])
     assert bare.routes[1] == engine.SlotRoute(gen=1) and not bare.converts(1)
+
+
+# ------------------------------------------------------------------------------- the stage table
+DECLARED = {"trim": {"seg_end", "last"}, "seam": {"seg_end", "last"}, "stretch": {"last"}, "limit": {"last"}, "loudness": set(),
+            "watermark": set()}  # the end markers each float stage's class declares
+
+
+def _every_route():
+    """``COMBOS`` crossed with the trim (off, the ends, a pause cap), loudness, watermark and limiter on and off."""
+    return [_route_of(c, trim=t, pause_blocks=p, loudness=ld, watermark_gain=g, ceiling=ce)
+            for c, (t, p), ld, g, ce in itertools.product(COMBOS, ((False, 0), (True, 0), (False, 3)), (None, -20.0), (0.0, 0.05), (0.0, 0.5))]
+
+
+def _route_of(combo, **kw):
+    seg, q, fmt, fl = combo
+    rate, enc = parse_stream_format(fmt)
+    return route.SlotRoute(rate, enc, q, fl, segmented=seg, **kw)
+
+
+def test_the_table_is_the_single_source():
+    assert tuple(s.name for s in route.STAGE_TABLE) == route.LIMIT_ORDER
+    assert tuple(s.name for s in route.STAGE_TABLE if s.fp32) == route.LIMIT_FLOAT_STAGES
+    assert [s.attr for s in route.STAGE_TABLE] == ["tr", "sj", "ln", "ts", "wm", "lim", "rs", "fl"]
+    assert {s.name: set(getattr(route, s.cls).END_MARKERS) for s in route.STAGE_TABLE if s.fp32} == DECLARED
+    routes = _every_route()
+    assert len(routes) == len(COMBOS) * 3 * 2 * 2 * 2
+    for r in routes:  # the eight conditions as the route stated them before the table
+        path = []
+        if r.trim or r.pause_blocks > 0:
+            path.append("trim")
+        if r.segmented:
+            path.append("seam")
+        if r.loudness is not None:
+            path.append("loudness")
+        if r.speed_q != 65536:
+            path.append("stretch")
+        if r.watermark_gain > 0.0:
+            path.append("watermark")
+        if r.ceiling > 0.0:
+            path.append("limit")
+        if r.enc != ENC_OFF:
+            path.append("resample")
+        if r.flac:
+            path.append("flac")
+        assert r.stages == tuple(path)
+
+
+def test_ends_of_every_one_and_two_slot_plan_follow_the_literal_rule():
+    conv = engine.StreamConverter(torch.device("cpu"), 2, 1920)
+    routes = _every_route()
+    for r0, r1 in itertools.product(routes, routes):
+        conv.routes[:] = [r0, r1]
+        for slots in ([0], [0, 1]) if r1 is routes[0] else ([0, 1],):
+            stages = conv.plan(slots).stages
+            assert conv.ends(slots) == (any(s in stages for s in ("trim", "seam", "stretch", "limit", "flac")),
+                                        "seam" in stages or "trim" in stages)
+
+
+def test_a_pass_with_all_eight_stages_runs_in_table_order_with_each_stage_its_declared_markers(monkeypatch):
+    """Slot 0 takes every stage, slot 1 is plain, slot 2 takes the loudness stage and the resampler: every other float stage
+    passes it through."""
+    from smoltts_amd import watermark as W
+
+    log = []
+    _stand_ins(monkeypatch, log)
+    name_of = {"SilenceTrimmer": "trim", "LoudnessNormalizer": "loudness", "Watermarker": "watermark", "PeakLimiter": "limit"}
+    conv = engine.StreamConverter(torch.device("cpu"), 3, 1920, watermark=W.Watermark(0x0123456789ABCDEF, -26.0))
+    conv.reset_slots([0, 1, 2], ["pcm_16000", None, "ulaw_8000"], [32768, None, None], ["flac", None, None], [-20.0, None, -16.0],
+                     None, [True, False, False], [(True, 0, None), None, None], [0.5, None, None])
+    conv.start_segments([0], [480], [engine.SEAM_FIRST], [240])
+    assert conv.routes[0].stages == route.LIMIT_ORDER and conv.routes[1].stages == () and conv.routes[2].stages == ("loudness", "resample")
+    assert all(getattr(conv, s.attr) is not None for s in route.STAGE_TABLE) and conv.ends([0, 1, 2]) == (True, True)
+
+    log.clear()
+    pcm = torch.arange(3 * 1920, dtype=torch.float32).reshape(3, 1920)
+    valid = torch.tensor([1920, 1900, 1800], dtype=torch.int32)
+    last, seg_end = torch.zeros(3, dtype=torch.int32), torch.zeros(3, dtype=torch.int32)
+    p = conv.run(pcm, 1920, valid, last=last, seg_end=seg_end)
+    assert all(e[0] == "chunk" for e in log) and [name_of.get(e[1], e[1]) for e in log] == list(route.LIMIT_ORDER)
+    assert p.plan.source == {0: "flac", 1: None, 2: "resample"} and list(p.dev) == ["resample", "flac"]
+    src, width, seen = pcm, 1920, valid
+    want_valid = {"trim": [11, 1900, 1800], "seam": [7, 1900, 1800], "loudness": [13, 13, 13], "stretch": [5, 13, 13],
+                  "watermark": [17, 13, 13], "limit": [19, 13, 13]}  # (a stage that passes no slot through hands on its counts)
+    for (_, cls, a, k), grows in zip(log[:6], (8, 16, 0, 32, 0, 126)):
+        s = name_of.get(cls, cls)
+        assert len(a) == 4 and a[0] is src and a[1] == width and a[2].shape == (3, width + grows) and a[3].shape == (3,)
+        assert set(k) == {"valid"} | DECLARED[s] and k["valid"].tolist() == seen.tolist()
+        assert k.get("last", last) is last and k.get("seg_end", seg_end) is seg_end
+        if s != "loudness":
+            assert torch.equal(a[2][2, :width], src[2])  # passed through
+        src, width, seen = a[2], width + grows, torch.tensor(want_valid[s], dtype=torch.int32)
+    assert width == 1920 + 8 + 16 + 32 + 126
+    rs_call, flac_call = log[6:]
+    rs_out, rs_counts = p.dev["resample"]
+    assert rs_call[2][0] is src and rs_call[2][1] == width and rs_call[2][2] is rs_out and rs_call[2][3] is rs_counts and len(rs_call[2]) == 4
+    assert set(rs_call[3]) == {"valid"} and rs_call[3]["valid"].tolist() == [19, 13, 13]
+    fout, fsizes = p.dev["flac"]
+    assert flac_call[2][0] == 3 and flac_call[2][1] is fout and flac_call[2][2] is fsizes and len(flac_call[2]) == 3
+    k = flac_call[3]
+    assert set(k) == {"pcm", "n_in", "valid", "s16", "s16_counts", "last"}
+    assert k["pcm"] is src and k["n_in"] == width and k["valid"].tolist() == [19, 13, 13] and k["last"] is last
+    assert k["s16"] is rs_out and k["s16_counts"] is rs_counts  # (the framed slot converts: FLAC reads the resampler's int16)
+    conv.close()
+    assert all(getattr(conv, s.attr) is None for s in route.STAGE_TABLE)
+
+
+def test_the_shared_chunk_refuses_an_end_marker_its_stage_does_not_declare():
+    from types import SimpleNamespace
+
+    from smoltts_amd import stages
+
+    class Bare(stages._FloatStage):  # no device: the C call is recorded
+        C_NAME = "bare"
+
+        def __init__(self):
+            self.B, self.calls = 2, []
+            self.lib = SimpleNamespace(smoltts_bare_out_samples=lambda n_in: n_in + 4)
+
+        def _call(self, suffix, *args):
+            self.calls.append((suffix, args))
+
+    class Ending(Bare):
+        END_MARKERS = ("last",)
+
+    pcm, out, counts = torch.zeros(2, 16), torch.zeros(2, 20), torch.zeros(2, dtype=torch.int32)
+    flag = torch.ones(2, dtype=torch.int32)
+    st = Bare()
+    assert st.END_MARKERS == ()
+    with pytest.raises(AssertionError, match="Bare"):
+        st.chunk(pcm, 16, out, counts, last=flag)
+    with pytest.raises(AssertionError):
+        st.chunk(pcm, 16, out, counts, seg_end=flag)
+    assert st.calls == []
+    st.chunk(pcm, 16, out, counts, valid=flag, last=None)
+    assert st.calls == [("chunk", (pcm.data_ptr(), 16, 2, 16, flag.data_ptr(), out.data_ptr(), 20, counts.data_ptr()))]
+    st = Ending()
+    st.chunk(pcm, 16, out, counts, last=flag)
+    st.chunk(pcm, 16, out, counts)
+    assert [c[1][5] for c in st.calls] == [flag.data_ptr(), None] and all(len(c[1]) == 9 for c in st.calls)
+    with pytest.raises(AssertionError):
+        st.chunk(pcm, 16, out, counts, seg_end=flag, last=flag)
