@@ -75,8 +75,9 @@ class SmolTTS:
         self.voices: Dict[str, "np.ndarray"] = {}  # registered voice id -> speaker grid (add_voice)
         self.verbose = verbose  # print the reference's per-call timing lines (lm/generate.py:187-214)
         self.last_sampling = None  # resolved RequestSampling list of the last call that was given sampling= (seeds included)
-        self._seam = None  # stages.SeamJoiner of the blocking segmented calls (made on first use)
-        self._trim = None  # stages.SilenceTrimmer of the blocking calls that trim silence (made on first use)
+        from .stages import Finisher
+
+        self._finish = Finisher(self.lm.device)  # the blocking calls' chain behind the codec (its stages are made on first use)
         self.last_trimmed_s = 0.0  # seconds of silence the last blocking call trimmed (trim_silence / max_pause_s)
         self.last_segments: list = []  # per segment of the last segmented call: text, prompt, codes, seed, frames
         self.last_loudness_gain_db = None  # gain of the last call that was given loudness=
@@ -215,28 +216,26 @@ class SmolTTS:
         """Returns flattened float32 PCM (reference __call__, __init__.py:64-81).  ``sampling``: a ``config.RequestSampling``
         (per-request temperature / min_p / seed, as in ``generate_codes``).  ``options``: the blocking request's audio options,
         handed whole to ``request.parse_request``, which lists them with their ranges and refuses a bad one before any work
-        (``ValueError``; ``TypeError`` for a name it does not know).  Here every stage takes the utterance whole on the GPU:
-        ``trim_silence`` / ``max_pause_s`` / ``silence_threshold_db``: the codec's PCM is trimmed first of all (``trim.py``),
-        each segment of a segmented text before the seam join; ``last_trimmed_s`` is what was cut.
-        ``segment``: the segments are spoken one after another, each decoded as its own utterance and joined (``seam``) before
-        the stretch; a text that is one segment without break tags takes the plain path.  ``last_segments`` then lists each
-        segment's text, seed and codes.
+        (``ValueError``; ``TypeError`` for a name it does not know).  Here every stage takes the utterance whole on the GPU,
+        in the order and by the rules of ``stages.Finisher``:
+        ``trim_silence`` / ``max_pause_s`` / ``silence_threshold_db`` (``trim.py``): ``last_trimmed_s`` is what was cut.
+        ``segment``: the segments are spoken one after another, each decoded as its own utterance, and joined (``seam``); a
+        text that is one segment without break tags takes the plain path.  ``last_segments`` then lists each segment's text,
+        seed and codes.
         ``loudness``: the utterance's integrated loudness is measured and one gain brings it to the target, capped where its
-        peak would pass -1 dBFS (``loudness.py``), behind the seam join and in front of the stretch; ``last_loudness_gain_db``
-        is the gain applied.
+        peak would pass -1 dBFS (``loudness.py``); ``last_loudness_gain_db`` is the gain applied.
         ``speed``: the time stretch, pitch kept (``tsm.py``): ``tsm.out_length(1920 F, speed_q)`` samples.
         ``watermark`` (None: marked when the instance has a ``watermark``; True without one: ``ValueError``): the utterance gets
-        the instance's mark behind the seam join, the loudness gain and the stretch (``watermark.py``).
+        the instance's mark (``watermark.py``).
         ``timestamps`` (needs the instance's ``alignment_heads``; not with ``segment``, the trim options or ``best_of``):
         ``last_alignment`` becomes the ``align.Alignment`` of the audio returned -- per character of ``input`` its start and end in
         seconds, read from where the chosen heads of the slow attention look while each frame is produced.  The option changes no
         id: with ``sampling=`` (its seed) or greedy settings the audio is the one the call returns without it.  A call without
         ``sampling=`` whose settings sample runs in the per-request mode here (the measurement exists only there) and draws a
         request seed, so its audio is another draw than the session-wide one; ``last_sampling`` carries the seed that replays it.
-        ``peak_limit_db``: the look-ahead peak limiter, last of all: behind the seam join, the loudness gain, the stretch and
-        the watermark (``limiter.py``); ``last_peak_reduction_db`` is ``-20 log10`` of the smallest gain applied, 0.0 when
-        nothing was limited.  With a ``loudness`` as well, the loudness gain is not capped by the peak: the limiter takes the
-        peaks down instead."""
+        ``peak_limit_db``: the look-ahead peak limiter, last of all (``limiter.py``); ``last_peak_reduction_db`` is
+        ``-20 log10`` of the smallest gain applied, 0.0 when nothing was limited.  With a ``loudness`` as well, the loudness gain
+        is not capped by the peak: the limiter takes the peaks down instead."""
         from .request import parse_request
 
         req = parse_request(input, False, **options)  # a bad request is refused before any work
@@ -254,7 +253,7 @@ class SmolTTS:
         self.last_takes = self.last_logprobs = self.last_mean_logprob = None
         self._check_best_of(sampling, generation_settings, segmented=req.plan is not None)
         if req.plan is not None:
-            pcm = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling, req)
+            pcms = self._call_segmented(req.plan, voice, speaker, generation_settings, sampling)
         else:
             if self._bounds_on or sampling is not None or req.timestamps:  # (the measurement exists in slot mode only)
                 from .config import RequestSampling
@@ -276,25 +275,10 @@ class SmolTTS:
 
                     self.last_logprobs = self.last_logprobs_all[0]
                     self.last_mean_logprob = mean_logprob(self.last_logprobs)
-            pcm = self._trimmed(self.decode_codes(codes), req)
+            pcms = [self.decode_codes(codes)]
+        pcm, self.last_trimmed_s, gain, self.last_peak_reduction_db = self._finish(pcms, req, marked, req.plan)
         if req.loudness is not None:
-            from .stages import loudness_normalize
-            from .loudness import gain_db
-
-            pcm, g = loudness_normalize(pcm, req.loudness, self.lm.device, with_gain=True, cap=req.peak_limit_db is None)
-            self.last_loudness_gain_db = gain_db(g)
-        if req.speed_q is not None:
-            from .stages import stretch_pcm
-
-            pcm = stretch_pcm(pcm, req.speed_q, self.lm.device)
-        if marked:
-            from .stages import watermark_embed
-
-            pcm = watermark_embed(pcm, marked, self.lm.device)
-        if req.peak_limit_db is not None:
-            from .stages import peak_limit
-
-            pcm, self.last_peak_reduction_db = peak_limit(pcm, req.peak_limit_db, self.lm.device)
+            self.last_loudness_gain_db = gain
         if req.timestamps:
             from .align import align
 
@@ -337,19 +321,6 @@ class SmolTTS:
         self.last_finish_reason = reasons[win]
         self.last_finish_reasons = [reasons[win]]
         return codes[win]
-
-    def _trimmed(self, pcm, req, flags: int = 3):
-        """``pcm``, one segment with ``flags`` (default: a plain utterance, first and final), through the trim stage when
-        ``req`` asks for it; ``last_trimmed_s`` grows by what was cut."""
-        if not req.trims:
-            return pcm
-        from .stages import SilenceTrimmer, trim_pcm
-
-        if self._trim is None:
-            self._trim = SilenceTrimmer(self.lm.device, 1)
-        out = trim_pcm(pcm, flags, self.lm.device, req.trim_silence, req.pause_blocks, req.silence_thr, trimmer=self._trim)
-        self.last_trimmed_s += (pcm.size - out.size) / self.sampling_rate
-        return out
 
     @property
     def _bounds_on(self) -> bool:
@@ -548,10 +519,8 @@ class SmolTTS:
             yield k, info[-1], st_k, samp_k
         self.last_sampling = resolved  # (generate_prompt_codes sets it per segment)
 
-    def _call_segmented(self, plan, voice, speaker, generation_settings, sampling, req):
-        from .seam import segment_flags
-        from .stages import SeamJoiner, seam_join
-
+    def _call_segmented(self, plan, voice, speaker, generation_settings, sampling):
+        """The PCM of ``plan``'s segments, each spoken and decoded as its own utterance."""
         from .config import merge_finish_reasons
 
         pcms, reasons = [], []
@@ -560,10 +529,8 @@ class SmolTTS:
             seg["frames"] = int(self.last_stats.get("frames", 0))  # every frame the segment emitted, its <|im_end|> frame included
             reasons.append(self.last_finish_reason)
             self.last_finish_reason = merge_finish_reasons(reasons)
-            pcms.append(self._trimmed(self.decode_codes(seg["codes"]), req, segment_flags(k, len(plan.segs))))
-        if self._seam is None:
-            self._seam = SeamJoiner(self.lm.device, 1)
-        return seam_join(pcms, plan.pauses, self.lm.device, lead=plan.lead, trail=plan.trail, joiner=self._seam)
+            pcms.append(self.decode_codes(seg["codes"]))
+        return pcms
 
     def _stream_incremental(self, texts, voice, generation_settings, overlap, reference_upsample, output_format, sampling,
                             segment=False, **options):

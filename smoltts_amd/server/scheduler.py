@@ -230,6 +230,7 @@ class BatchScheduler:
         from ..config import GenerationSettings
         from ..lm import LMSession
         from ..route import StreamConverter
+        from ..stages import Finisher
         from ..generate import _apply_sampling
 
         from ..watermark import Watermark
@@ -299,8 +300,7 @@ class BatchScheduler:
         self._parked: List[_Request] = []       # ... and incremental ones whose slot waits for text that has not arrived yet
         self._incs: List[_Request] = []         # the incremental requests alive (worker side)
         self._inc_new: "queue.Queue[_Request]" = queue.Queue()  # ... and those the worker has not seen yet
-        self._block_seam = None                 # seam stage of the blocking segmented requests (stages.SeamJoiner, 1 slot)
-        self._block_trim = None                 # trim stage of the blocking requests that trim silence (stages.SilenceTrimmer, 1 slot)
+        self._finisher = Finisher(self.session.engine.device)  # the blocking requests' chain behind the codec (stages made on first use)
         self._dead: Optional[Exception] = None  # why the worker stopped
         self._draining = False
         self._held: Optional[_Request] = None   # next in line, waiting for room in a prefill call
@@ -322,7 +322,7 @@ class BatchScheduler:
         them with their ranges and refuses a bad one here, before the request is queued (``ValueError``; ``TypeError`` for a
         name it does not know).  The parsed value is ``request.opts``.  Every stage runs on the GPU: a stream's in its codec
         pass (``StreamConverter.start`` when the stream takes its slot), a blocking utterance's over the whole utterance once
-        its last codec pass is in.  What this front end adds to each:
+        its last codec pass is in, in the order and by the rules of ``stages.Finisher``.  What this front end adds to each:
         ``output_format``: the resampler's tail comes with the stream's last chunk.
         ``speed``: a stream is stretched in front of the format conversion, a blocking utterance as a whole.
         ``container``: FLAC framing in the same pass, behind the other stages; the stream header in front of the first chunk.
@@ -551,10 +551,11 @@ class BatchScheduler:
         self._stop.set()
         self._wake.set()
         self._thread.join(timeout=30)
-        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch", "_block_seam", "_block_trim"):
+        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch"):
             if getattr(self, name) is not None:
                 getattr(self, name).close()
                 setattr(self, name, None)
+        self._finisher.close()
         self._stream_conv.close()
         self.session.close()
 
@@ -1258,18 +1259,14 @@ class BatchScheduler:
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)
                         self._counts["frames_delivered"] += n // 1920
-                elif not r.stream and (r.opts.speed_q or r.opts.loudness is not None or r.watermark or r.opts.trims or r.opts.peak_limit_db is not None):
-                    # a blocking utterance with a trim, a speed, a loudness target, the mark or a ceiling: trimmed, levelled, stretched, marked and limited whole once
-                    # its last pass is in
+                elif not r.stream and self._finisher.needed(r.opts, self._key(r)):
+                    # a blocking utterance that stages.Finisher has work on: finished whole once its last pass is in
                     if n and not r.cancelled:
                         r.stretch_in.append(host[b, :n].copy())
                         self._counts["frames_delivered"] += n // 1920
                     if fin and r.stretch_in and not r.cancelled:
-                        r.stretch_in = [self._level(r, self._trimmed(r, np.concatenate(r.stretch_in)))]
-                        if r.opts.speed_q:
-                            self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
-                            continue
-                        self._put(r, self._mark(r, r.stretch_in.pop()))
+                        self._finish(r, [np.concatenate(r.stretch_in)])
+                        continue
                 elif n and not r.cancelled:
                     self._put(r, host[b, :n].copy())
                     self._counts["frames_delivered"] += n // 1920
@@ -1278,11 +1275,7 @@ class BatchScheduler:
             wait = False
 
     def _part_done(self, part: _Request) -> None:
-        """A segment's PCM of a blocking segmented request is complete; once all are, they are joined on the GPU (stages.seam_join)
-        and go out, stretched first when the request has a speed."""
-        from ..seam import segment_flags
-        from ..stages import SeamJoiner, seam_join
-
+        """A segment's PCM of a blocking segmented request is complete; once all are, they are joined and finished (``_finish``)."""
         r = part.part_of[0]
         sg = r.seg
         sg.done += 1
@@ -1291,66 +1284,28 @@ class BatchScheduler:
             return
         if sg.done < len(sg.plan.segs):
             return
-        torch = self._torch
         pcms = [np.concatenate(p) if p else np.zeros(0, np.float32) for p in sg.pcm]
-        pcms = [self._trimmed(r, x, segment_flags(k, len(pcms))) for k, x in enumerate(pcms)]
-        dev = self.session.engine.device
-        with torch.cuda.stream(self._stretch_stream):
-            if self._block_seam is None:
-                self._block_seam = SeamJoiner(dev, 1)
-            pcm = seam_join(pcms, sg.plan.pauses, dev, lead=sg.plan.lead, trail=sg.plan.trail, joiner=self._block_seam)
         sg.pcm = []
-        pcm = self._level(r, pcm)
-        if r.opts.speed_q:
-            r.stretch_in = [pcm]
-            self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
-            return
-        r.out.put(self._mark(r, pcm))
+        self._finish(r, pcms, sg.plan)
+
+    def _key(self, r: _Request):
+        """The watermark key of a request's audio, or None: unmarked."""
+        return self.watermark if r.watermark else None
+
+    def _finish(self, r: _Request, segments: List[np.ndarray], plan=None) -> None:
+        """A complete blocking utterance (``plan``: the segments of a segmented one) goes through ``stages.Finisher`` on the
+        stretch stream, waited for here, and out.  One with a speed leaves the chain between ``head`` and ``tail`` for the
+        batched stretch (``_poll_stretches``)."""
+        with self._torch.cuda.stream(self._stretch_stream):
+            pcm, r.trimmed_s, r.loudness_gain_db = self._finisher.head(segments, r.opts, plan)
+            if r.opts.speed_q:
+                r.stretch_in = [pcm]
+                self._start_stretch(r)  # (its end marker follows the stretched audio, in _poll_stretches)
+                return
+            pcm, r.peak_reduction_db = self._finisher.tail(pcm, r.opts, self._key(r))
+        r.stretch_in = []
+        self._put(r, pcm)
         self._end(r)
-
-    def _trimmed(self, r: _Request, pcm: np.ndarray, flags: int = 3) -> np.ndarray:
-        """A complete blocking utterance, or one segment of it with ``flags`` (default: first and final): a request that trims
-        silence has it trimmed whole on the GPU (stages.trim_pcm, waited for here as the seam join is)."""
-        if not r.opts.trims:
-            return pcm
-        from ..stages import SilenceTrimmer, trim_pcm
-
-        dev = self.session.engine.device
-        with self._torch.cuda.stream(self._stretch_stream):
-            if self._block_trim is None:
-                self._block_trim = SilenceTrimmer(dev, 1)
-            out = trim_pcm(pcm, flags, dev, *r.opts.trim_route, trimmer=self._block_trim)
-        r.trimmed_s += (pcm.size - out.size) / 24000.0
-        return out
-
-    def _mark(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
-        """A complete blocking utterance, levelled and stretched: a marked request's gets the watermark whole on the GPU
-        (stages.watermark_embed: one launch, waited for here as the seam join is), and a request with a ceiling is limited
-        whole behind that, last of all (stages.peak_limit: one launch)."""
-        if r.watermark:
-            from ..stages import watermark_embed
-
-            with self._torch.cuda.stream(self._stretch_stream):
-                pcm = watermark_embed(pcm, self.watermark, self.session.engine.device)
-        if r.opts.peak_limit_db is not None:
-            from ..stages import peak_limit
-
-            with self._torch.cuda.stream(self._stretch_stream):
-                pcm, r.peak_reduction_db = peak_limit(pcm, r.opts.peak_limit_db, self.session.engine.device)
-        return pcm
-
-    def _level(self, r: _Request, pcm: np.ndarray) -> np.ndarray:
-        """A complete blocking utterance (joined, not yet stretched): with a loudness target it is measured and scaled whole on
-        the GPU (stages.loudness_normalize: two launches, waited for here as the seam join is)."""
-        if r.opts.loudness is None:
-            return pcm
-        from ..stages import loudness_normalize
-        from ..loudness import gain_db
-
-        with self._torch.cuda.stream(self._stretch_stream):
-            pcm, g = loudness_normalize(pcm, r.opts.loudness, self.session.engine.device, with_gain=True, cap=r.opts.peak_limit_db is None)
-        r.loudness_gain_db = gain_db(g)
-        return pcm
 
     STRETCH_SLOTS, STRETCH_PIECE = 16, 65536  # blocking utterances stretched side by side, input samples per slot and call
 
@@ -1380,7 +1335,10 @@ class BatchScheduler:
             for job in [j for j in ran if j.state == "ending"]:
                 r = job.req
                 if not r.cancelled:
-                    self._put(r, self._mark(r, np.concatenate(job.outs) if job.outs else np.zeros(0, np.float32)))
+                    with torch.cuda.stream(self._stretch_stream):
+                        pcm, r.peak_reduction_db = self._finisher.tail(np.concatenate(job.outs) if job.outs else np.zeros(0, np.float32),
+                                                                       r.opts, self._key(r))
+                    self._put(r, pcm)
                 self._end(r)
                 self._stretches.remove(job)
             self._stretch_flight = None

@@ -1,7 +1,8 @@
 """The stages behind the codec, one class per C stage (resampler, time stretch, trim, seam, loudness, watermark, limiter, FLAC), and
-their whole-utterance helpers."""
+their whole-utterance helpers, with the blocking front ends' chain over those (``Finisher``)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import List, Optional, Sequence, Tuple
 
@@ -188,6 +189,25 @@ class TimeStretcher(_FloatStage):
         return dict(zip(("k", "p_prev", "n_in", "n_out", "ended"), list(v)))
 
 
+def _f32(pcm) -> np.ndarray:
+    """``pcm`` as a contiguous float32 1-D host array."""
+    return np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+
+
+@contextlib.contextmanager
+def _held(cls, device: torch.device, given, *args):
+    """The one-slot ``cls`` stage of a whole-utterance call, with ``device`` current: the caller's (``given``), or one made for
+    the call and closed behind it.  The whole-utterance calls take no slot or reset slot 0, so a held stage carries nothing from
+    one utterance to the next."""
+    with torch.cuda.device(device):
+        stage = given if given is not None else cls(device, 1, *args)
+        try:
+            yield stage
+        finally:
+            if given is None:
+                stage.close()
+
+
 def _whole_row(stage: _Stage, x: np.ndarray, launch):
     """A whole utterance through slot 0 of ``stage``: ``x`` (host, contiguous) goes up as the device row [1, n] (one zero sample
     when empty), and ``launch(row, n, out, counts)`` queues the stage's call into ``stage.new_outputs(1, n)``.  Waits, and
@@ -201,20 +221,16 @@ def _whole_row(stage: _Stage, x: np.ndarray, launch):
     return FlacEncoder.slot_frames(out.cpu().numpy(), counts.cpu().numpy(), 0)
 
 
-def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device) -> np.ndarray:
+def stretch_pcm(pcm: np.ndarray, speed_q: int, device: torch.device, held: Optional[TimeStretcher] = None) -> np.ndarray:
     """A whole utterance (float32 at 24 kHz) stretched on ``device`` (the model's) in one call with ``last`` set: exactly
     ``tsm.out_length(len(pcm), speed_q)`` samples (``SmolTTS.__call__``).  Waits for the result.  ``speed_q == 65536`` returns
-    ``pcm`` untouched."""
-    pcm = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    ``pcm`` untouched.  ``held``: a caller's ``TimeStretcher`` whose slot 0 is used (default: one made for the call)."""
+    pcm = _f32(pcm)
     if speed_q == 65536:
         return pcm
-    with torch.cuda.device(device):
-        ts = TimeStretcher(device, 1)
-        try:
-            ts.reset_slots([0], [speed_q])
-            return _whole_row(ts, pcm, lambda x, n, out, cnt: ts.chunk(x, n, out, cnt, last=torch.ones(1, dtype=torch.int32, device=device)))
-        finally:
-            ts.close()
+    with _held(TimeStretcher, device, held) as ts:
+        ts.reset_slots([0], [speed_q])
+        return _whole_row(ts, pcm, lambda x, n, out, cnt: ts.chunk(x, n, out, cnt, last=torch.ones(1, dtype=torch.int32, device=device)))
 
 
 # ------------------------------------------------------------------------------- silence: trimmed ends, capped pauses
@@ -245,30 +261,26 @@ class SilenceTrimmer(_FloatStage):
 
 
 def trim_pcm(pcm: np.ndarray, flags: int, device: torch.device, trim: bool = True, pause_blocks: int = 0, thr: Optional[float] = None,
-             trimmer: Optional[SilenceTrimmer] = None) -> np.ndarray:
+             held: Optional[SilenceTrimmer] = None) -> np.ndarray:
     """A whole segment (float32 at 24 kHz) trimmed on ``device`` by the trim rule: what ``trim.trim`` computes
     (``SmolTTS.__call__``).  The row goes through slot 0 in calls of at most ``trim.MAX_CALL`` samples, the last one ending the
-    segment; one wait for all of them.  ``trimmer``: a caller's ``SilenceTrimmer`` (default: one made for the call)."""
+    segment; one wait for all of them.  ``held``: a caller's ``SilenceTrimmer`` whose slot 0 is used (default: one made for the
+    call)."""
     from .trim import MAX_CALL, THRESH
 
-    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
-    with torch.cuda.device(device):
-        st = trimmer if trimmer is not None else SilenceTrimmer(device, 1)
-        try:
-            st.start_segments([0], [flags], [trim], [pause_blocks], [THRESH if thr is None else thr])
-            row = torch.from_numpy(x).to(device)[None] if x.size else torch.zeros(1, 1, dtype=torch.float32, device=device)
-            end = torch.ones(1, dtype=torch.int32, device=device)
-            outs = []
-            for i in range(0, max(x.size, 1), MAX_CALL):
-                n = min(MAX_CALL, x.size - i)
-                out, counts = st.new_outputs(1, n)
-                st.chunk(row[:, i:i + max(n, 1)], n, out, counts, seg_end=end if i + n >= x.size else None)
-                outs.append((out, counts))
-            counts = torch.cat([c for _, c in outs]).cpu().numpy()
-            return np.concatenate([o[0, :int(c)].cpu().numpy() for (o, _), c in zip(outs, counts)])
-        finally:
-            if trimmer is None:
-                st.close()
+    x = _f32(pcm)
+    with _held(SilenceTrimmer, device, held) as st:
+        st.start_segments([0], [flags], [trim], [pause_blocks], [THRESH if thr is None else thr])
+        row = torch.from_numpy(x).to(device)[None] if x.size else torch.zeros(1, 1, dtype=torch.float32, device=device)
+        end = torch.ones(1, dtype=torch.int32, device=device)
+        outs = []
+        for i in range(0, max(x.size, 1), MAX_CALL):
+            n = min(MAX_CALL, x.size - i)
+            out, counts = st.new_outputs(1, n)
+            st.chunk(row[:, i:i + max(n, 1)], n, out, counts, seg_end=end if i + n >= x.size else None)
+            outs.append((out, counts))
+        counts = torch.cat([c for _, c in outs]).cpu().numpy()
+        return np.concatenate([o[0, :int(c)].cpu().numpy() for (o, _), c in zip(outs, counts)])
 
 
 # ------------------------------------------------------------------------------- long texts: the seam between segments
@@ -311,25 +323,20 @@ class SeamJoiner(_FloatStage):
 
 
 def seam_join(segments: Sequence[np.ndarray], pauses: Sequence[int], device: torch.device, lead: int = 0, trail: int = 0,
-              joiner: Optional[SeamJoiner] = None) -> np.ndarray:
+              held: Optional[SeamJoiner] = None) -> np.ndarray:
     """Whole segments (float32 at 24 kHz) joined on ``device`` by the seam rule, one call per segment with its end set: what
     ``seam.join`` computes (``SmolTTS.__call__`` with ``segment``).  ``pauses[k]``: the seam after segment k, in samples.
-    ``joiner``: a caller's ``SeamJoiner`` whose slot 0 is used (default: one made for the call).  Waits for the result."""
-    segs = [np.ascontiguousarray(np.asarray(s, dtype=np.float32).reshape(-1)) for s in segments]
+    ``held``: a caller's ``SeamJoiner`` whose slot 0 is used (default: one made for the call).  Waits for the result."""
+    segs = [_f32(s) for s in segments]
     if len(pauses) != max(len(segs) - 1, 0):
         raise ValueError("one pause per seam")
     out = []
-    with torch.cuda.device(device):
-        sj = joiner if joiner is not None else SeamJoiner(device, 1)
-        try:
-            end = torch.ones(1, dtype=torch.int32, device=device)
-            for k, x in enumerate(segs):
-                final = k == len(segs) - 1
-                sj.start_segments([0], [trail if final else pauses[k]], [segment_flags(k, len(segs))], [lead])
-                out.append(_whole_row(sj, x, lambda xd, n, y, cnt: sj.chunk(xd, n, y, cnt, seg_end=end, last=end if final else None)))
-        finally:
-            if joiner is None:
-                sj.close()
+    with _held(SeamJoiner, device, held) as sj:
+        end = torch.ones(1, dtype=torch.int32, device=device)
+        for k, x in enumerate(segs):
+            final = k == len(segs) - 1
+            sj.start_segments([0], [trail if final else pauses[k]], [segment_flags(k, len(segs))], [lead])
+            out.append(_whole_row(sj, x, lambda xd, n, y, cnt: sj.chunk(xd, n, y, cnt, seg_end=end, last=end if final else None)))
     return np.concatenate(out) if out else np.zeros(0, np.float32)
 
 
@@ -383,46 +390,43 @@ class LoudnessNormalizer(_SameLengthStage):
                 "ptarget": float(v[18]), "filter": v[:17].copy(), "ring": v[19:].copy()}
 
 
-def _loudness_whole(pcm: np.ndarray, device: torch.device, target: Optional[float], cap: bool = True):
+def _loudness_whole(pcm: np.ndarray, device: torch.device, target: Optional[float], cap: bool = True, held=None):
     """(power, peak, gain, output or None) of a whole utterance on ``device``: measured in one launch, and with a ``target``
-    scaled by the blocking rule's gain (``cap`` false: not capped by the peak) in a second one."""
+    scaled by the blocking rule's gain (``cap`` false: not capped by the peak) in a second one.  ``held``: a caller's
+    ``LoudnessNormalizer`` (default: one made for the call)."""
     from .loudness import static_gain
 
-    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
-    with torch.cuda.device(device):
-        ln = LoudnessNormalizer(device, 1)
-        try:
-            seen = {}
+    x = _f32(pcm)
+    with _held(LoudnessNormalizer, device, held) as ln:
+        seen = {}
 
-            def launch(row, n, out, counts):
-                seen["p"], seen["peak"] = ln.measure(row, n) if n else (0.0, 0.0)
-                seen["g"] = 1.0 if target is None else static_gain(target, seen["p"], seen["peak"], cap)
-                ln.scale(row, n, seen["g"], out)
-                counts.fill_(n)
+        def launch(row, n, out, counts):
+            seen["p"], seen["peak"] = ln.measure(row, n) if n else (0.0, 0.0)
+            seen["g"] = 1.0 if target is None else static_gain(target, seen["p"], seen["peak"], cap)
+            ln.scale(row, n, seen["g"], out)
+            counts.fill_(n)
 
-            y = _whole_row(ln, x, launch)
-        finally:
-            ln.close()
+        y = _whole_row(ln, x, launch)
     return seen["p"], seen["peak"], seen["g"], (x if seen["g"] == 1.0 else y)
 
 
-def measure_loudness(pcm: np.ndarray, device: torch.device) -> Tuple[float, float]:
+def measure_loudness(pcm: np.ndarray, device: torch.device, held: Optional[LoudnessNormalizer] = None) -> Tuple[float, float]:
     """(integrated loudness in LUFS by BS.1770-4, -inf when no block passes the absolute gate or the utterance is shorter than
     400 ms; peak) of a whole utterance (float32 at 24 kHz), measured on ``device``: ``loudness.measure``.  Waits."""
     from .loudness import lufs_of_power
 
-    p, peak, _, _ = _loudness_whole(pcm, device, None)
+    p, peak, _, _ = _loudness_whole(pcm, device, None, held=held)
     return lufs_of_power(p), peak
 
 
-def loudness_normalize(pcm: np.ndarray, target: float, device: torch.device, with_gain: bool = False, cap: bool = True):
+def loudness_normalize(pcm: np.ndarray, target: float, device: torch.device, with_gain: bool = False, cap: bool = True, held=None):
     """A whole utterance (float32 at 24 kHz) brought to ``target`` LUFS on ``device`` by one gain, capped so that its peak
     stays at -1 dBFS: ``loudness.normalize`` (``SmolTTS.__call__``).  An utterance that measures nothing comes back
     unchanged.  ``with_gain``: -> (samples, the gain applied).  ``cap`` false: the gain is not capped by the peak (a request
     whose peaks a limiter takes down behind it).  Waits for the result."""
     from .loudness import check_target
 
-    _, _, g, y = _loudness_whole(pcm, device, check_target(target), cap)
+    _, _, g, y = _loudness_whole(pcm, device, check_target(target), cap, held)
     return (y, g) if with_gain else y
 
 
@@ -462,22 +466,21 @@ class Watermarker(_SameLengthStage):
         return {"pos": int(ints[0]), "on": int(ints[1]), "values": v}
 
 
-def watermark_embed(pcm: np.ndarray, wm, device: torch.device) -> np.ndarray:
+def watermark_embed(pcm: np.ndarray, wm, device: torch.device, held: Optional[Watermarker] = None) -> np.ndarray:
     """A whole utterance (float32 at 24 kHz) marked with ``wm`` (a ``watermark.Watermark``) on ``device`` in one launch from
-    position 0: ``watermark.embed`` (``SmolTTS.__call__``).  Waits for the result."""
-    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    position 0: ``watermark.embed`` (``SmolTTS.__call__``).  ``held``: a caller's ``Watermarker`` of that key (default: one made
+    for the call).  Waits for the result."""
+    x = _f32(pcm)
     if x.size == 0:
         return x
-    with torch.cuda.device(device):
-        st = Watermarker(device, 1, wm)
-        try:
-            def launch(row, n, out, counts):
-                st.embed(row, n, wm.gain, out)
-                counts.fill_(n)
+    with _held(Watermarker, device, held, wm) as st:
+        assert st.wm is wm, "the held Watermarker carries another key's chip table"
 
-            return _whole_row(st, x, launch)
-        finally:
-            st.close()
+        def launch(row, n, out, counts):
+            st.embed(row, n, wm.gain, out)
+            counts.fill_(n)
+
+        return _whole_row(st, x, launch)
 
 
 # ------------------------------------------------------------------------------- peak limiter
@@ -551,26 +554,96 @@ class PeakLimiter(_FloatStage):
                 "r": v[2:2 + R_HIST].copy(), "x": v[2 + R_HIST:].astype(np.float32)}
 
 
-def peak_limit(pcm: np.ndarray, peak_limit_db: float, device: torch.device) -> Tuple[np.ndarray, float]:
+def peak_limit(pcm: np.ndarray, peak_limit_db: float, device: torch.device, held: Optional[PeakLimiter] = None) -> Tuple[np.ndarray, float]:
     """A whole utterance (float32 at 24 kHz) limited under ``peak_limit_db`` dBFS on ``device`` in one launch: ``limiter.limit``
     (``SmolTTS.__call__``) -> (samples, as many as went in; the reduction in dB, ``-20 log10(min g)``, 0.0 when nothing was
-    limited).  Waits for the result."""
+    limited).  ``held``: a caller's ``PeakLimiter`` (default: one made for the call).  Waits for the result."""
     from .limiter import ceiling_of_db, check_peak_limit, reduction_db
 
     c = ceiling_of_db(check_peak_limit(peak_limit_db))
-    x = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+    x = _f32(pcm)
     if x.size == 0:
         return x, 0.0
-    with torch.cuda.device(device):
-        st = PeakLimiter(device, 1)
-        try:
-            res = torch.empty(1, dtype=torch.float64, device=device)
-            row = torch.from_numpy(x).to(device)
-            out = torch.empty_like(row)
-            st.apply(row, x.size, c, out, res)
-            return out.cpu().numpy(), reduction_db(float(res.cpu()[0]))
-        finally:
-            st.close()
+    with _held(PeakLimiter, device, held) as st:
+        res = torch.empty(1, dtype=torch.float64, device=device)
+        row = torch.from_numpy(x).to(device)
+        out = torch.empty_like(row)
+        st.apply(row, x.size, c, out, res)
+        return out.cpu().numpy(), reduction_db(float(res.cpu()[0]))
+
+
+# ------------------------------------------------------------------------------- a blocking utterance, finished
+class Finisher:
+    """What both blocking front ends do to a complete utterance behind the codec, on ``device``'s current stream, each step
+    waited for as its helper waits.  The order: trim -> seam join -> loudness -> stretch -> watermark -> limiter.
+    Segment k of n is trimmed with ``segment_flags(k, n)`` (a plain utterance is one segment, first and final) and the trimmed
+    seconds are summed over the segments; the loudness gain is capped by the peak exactly when no limiter follows; the
+    watermark stands behind the stretch and the limiter is last of all.  ``head`` is the part in front of the stretch and
+    ``tail`` the part behind it, for a caller that stretches by its own means (the scheduler's batched stretch).
+    At most one one-slot stage per class is held (``held``), made by ``_make`` when an option first needs it."""
+
+    def __init__(self, device: torch.device):
+        self.device = device
+        self.held: dict = {}  # stage class -> its one-slot stage
+
+    def _make(self, cls, *args):
+        with torch.cuda.device(self.device):
+            return cls(self.device, 1, *args)
+
+    def _stage(self, cls, *args):
+        if cls not in self.held:
+            self.held[cls] = self._make(cls, *args)
+        return self.held[cls]
+
+    def close(self) -> None:
+        for stage in self.held.values():
+            stage.close()
+        self.held = {}
+
+    @staticmethod
+    def needed(opts, mark) -> bool:
+        """Whether a request with ``opts`` and the key ``mark`` (None: unmarked) has anything done to it here."""
+        return bool(opts.trims or opts.loudness is not None or opts.speed_q or mark is not None or opts.peak_limit_db is not None)
+
+    def head(self, segments: Sequence[np.ndarray], opts, plan=None):
+        """``segments`` (host float32; one entry: a plain utterance) trimmed, joined by ``plan`` (a ``longform`` segment plan)
+        and levelled -> (samples, seconds trimmed, loudness gain in dB or None)."""
+        from .loudness import gain_db
+
+        whole, gain = segments, None
+        if opts.trims:
+            segments = [trim_pcm(x, segment_flags(k, len(whole)), self.device, *opts.trim_route, held=self._stage(SilenceTrimmer))
+                        for k, x in enumerate(whole)]
+        trimmed_s = float(sum((x.size - y.size) / 24000.0 for x, y in zip(whole, segments)))
+        if plan is not None:
+            pcm = seam_join(segments, plan.pauses, self.device, lead=plan.lead, trail=plan.trail, held=self._stage(SeamJoiner))
+        else:
+            pcm, = segments
+        if opts.loudness is not None:
+            pcm, g = loudness_normalize(pcm, opts.loudness, self.device, with_gain=True, cap=opts.peak_limit_db is None,
+                                        held=self._stage(LoudnessNormalizer))
+            gain = gain_db(g)
+        return pcm, trimmed_s, gain
+
+    def tail(self, pcm: np.ndarray, opts, mark):
+        """``pcm`` marked with the key ``mark`` (a ``watermark.Watermark``; None: unmarked), then limited -> (samples, peak
+        reduction in dB or None).  The held ``Watermarker`` is one key's: another key object has it made anew."""
+        reduction = None
+        if mark is not None:
+            if Watermarker in self.held and self.held[Watermarker].wm is not mark:
+                self.held.pop(Watermarker).close()
+            pcm = watermark_embed(pcm, mark, self.device, held=self._stage(Watermarker, mark))
+        if opts.peak_limit_db is not None:
+            pcm, reduction = peak_limit(pcm, opts.peak_limit_db, self.device, held=self._stage(PeakLimiter))
+        return pcm, reduction
+
+    def __call__(self, segments: Sequence[np.ndarray], opts, mark, plan=None):
+        """The whole chain -> (samples, seconds trimmed, loudness gain in dB or None, peak reduction in dB or None)."""
+        pcm, trimmed_s, gain = self.head(segments, opts, plan)
+        if opts.speed_q:
+            pcm = stretch_pcm(pcm, opts.speed_q, self.device, held=self._stage(TimeStretcher))
+        pcm, reduction = self.tail(pcm, opts, mark)
+        return pcm, trimmed_s, gain, reduction
 
 
 # ------------------------------------------------------------------------------- FLAC framing
@@ -628,16 +701,12 @@ def flac_encode(samples: np.ndarray, sample_rate: int, device: torch.device) -> 
     is_f32 = x.dtype != np.int16
     x = np.ascontiguousarray(x, dtype=np.float32 if is_f32 else np.int16)
     s16 = flac.quantize(x) if is_f32 else x
-    with torch.cuda.device(device):
-        fe = FlacEncoder(device, 1)
-        try:
-            fe.reset_slots([0], [sample_rate], [FLAC_F32 if is_f32 else FLAC_S16])
-            last = torch.ones(1, dtype=torch.int32, device=device)
-            if is_f32:
-                frames = _whole_row(fe, x, lambda row, n, out, sizes: fe.chunk(1, out, sizes, pcm=row, n_in=n, last=last))
-            else:  # (the int16 row read as the resampler's bytes, all of it final)
-                frames = _whole_row(fe, x, lambda row, n, out, sizes: fe.chunk(
-                    1, out, sizes, s16=row.view(torch.uint8), s16_counts=torch.tensor([[n, 0]], dtype=torch.int32, device=device), last=last))
-        finally:
-            fe.close()
+    with _held(FlacEncoder, device, None) as fe:
+        fe.reset_slots([0], [sample_rate], [FLAC_F32 if is_f32 else FLAC_S16])
+        last = torch.ones(1, dtype=torch.int32, device=device)
+        if is_f32:
+            frames = _whole_row(fe, x, lambda row, n, out, sizes: fe.chunk(1, out, sizes, pcm=row, n_in=n, last=last))
+        else:  # (the int16 row read as the resampler's bytes, all of it final)
+            frames = _whole_row(fe, x, lambda row, n, out, sizes: fe.chunk(
+                1, out, sizes, s16=row.view(torch.uint8), s16_counts=torch.tensor([[n, 0]], dtype=torch.int32, device=device), last=last))
     return flac.file_from_frames(frames, s16, sample_rate)

@@ -269,7 +269,7 @@ def test_requests_without_the_options_make_no_trim_stage(tts, monkeypatch):
     real = engine.SilenceTrimmer.__init__
     monkeypatch.setattr(engine.SilenceTrimmer, "__init__", lambda self, *a, **k: (made.append(1), real(self, *a, **k))[1])
     gs = GenerationSettings.greedy(max_new_tokens=8)
-    tts._trim = None
+    tts._finish.held.pop(engine.SilenceTrimmer, None)
     a = tts(SHORT, "heart", generation_settings=gs)
     b = np.concatenate(list(tts.stream(SHORT, "heart", generation_settings=gs, trim_silence=False, max_pause_s=None)))
     tts(TEXT, "heart", generation_settings=gs, segment=OPTS)
@@ -278,10 +278,10 @@ def test_requests_without_the_options_make_no_trim_stage(tts, monkeypatch):
     try:
         np.testing.assert_array_equal(np.concatenate(list(sched.iter_chunks(sched.submit(SHORT, "heart")))), a)
         c = np.concatenate(list(sched.iter_chunks(sched.submit(SHORT, "heart", stream=True))))
-        assert c.size > 0 and b.size > 0 and sched._stream_conv.tr is None and sched._block_trim is None
+        assert c.size > 0 and b.size > 0 and sched._stream_conv.tr is None and sched._finisher.held.get(engine.SilenceTrimmer) is None
     finally:
         sched.close()
-    assert not made and tts._trim is None
+    assert not made and tts._finish.held.get(engine.SilenceTrimmer) is None
     tts(SHORT, "heart", generation_settings=gs, trim_silence=True)
     assert made == [1]
 
