@@ -200,6 +200,24 @@ int smoltts_lm_prefill_side(SmolttsSession* s, const int32_t* grid_dev, const in
 int smoltts_lm_start_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos_dev, const int32_t* slots_host,
                            const int32_t* last_row_host, int32_t n_slots, int32_t stop_on_eos, void* stream);
 
+/* (ABI 9, additive) Forced alignment: MEASURE n_rows further prompt rows of idle slots instead of only storing them (DESIGN.md
+ * section 23).  The rows go through the slow transformer exactly as in a non-final smoltts_lm_prefill_chunk -- the same KV rows by
+ * the same kernels in the same order, on the session's prefill workspace, chunks in position order -- but the call takes no slot
+ * list and parks nothing: the rows' slots are idle and already parked at or behind the last position that will be measured
+ * (smoltts_lm_park_slots).  No frame is emitted, no slot is armed, nothing is captured and no graph is dropped.
+ *   Alignment rows: while heads are chosen (smoltts_session_set_align_heads), one smoltts_k_attention_align launch is queued behind
+ *   the block of each layer that has chosen heads, with the workspace's q rows, the slots' windows (smoltts_session_set_slot_align)
+ *   and row_frame_dev: row r writes out[row_slot[r]][row_frame_dev[r]][pair]; a row with row_frame_dev[r] < 0 (or >= max_frames)
+ *   writes nothing.
+ *   Scores: with logprob_dev != NULL the rows get the final norm and the slow head, max_batch rows at a time through the rows the
+ *   decode frames' slow head writes (smoltts_session_slow_logits: overwritten), and logprob_dev[r] receives the score of column
+ *   target_dev[r] under row r's fp32 logits -- the definition at smoltts_session_set_slot_score, no length entry and no penalty.  A
+ *   row with target_dev[r] outside [0, vocab_size) writes nothing (the caller checks its ids on the host).  target_dev may be NULL
+ *   when logprob_dev is.
+ * grid_dev / row_slot_dev / row_pos_dev as in smoltts_lm_prefill; frame-stream call, like smoltts_lm_prefill_chunk. */
+int smoltts_lm_measure_rows(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_slot_dev, const int32_t* row_pos_dev,
+                            const int32_t* row_frame_dev, const int32_t* target_dev, int32_t n_rows, float* logprob_dev, void* stream);
+
 /* Decode n_frames further frames for every slot of the session: each frame feeds the previous
  * column back (slow step at the slot's next position), then slow head + n_fast depth steps, all
  * greedy and on device; the frame loop is a captured hipGraph replayed n_frames times.  Slots that
@@ -1132,6 +1150,12 @@ int smoltts_k_attention_align(const float* q_dev, const void* k_cache_dev, int32
                               const int32_t* row_slot_dev, const int32_t* row_frame_dev, const int32_t* row_mask_dev,
                               const int32_t* windows_dev, const int32_t* heads_host, int32_t n_heads, int32_t n_rows, int32_t n_q_heads,
                               int32_t n_kv_heads, int32_t cache_len, int32_t max_frames, float* out_dev, void* stream);
+/* (ABI 9, additive) The score of a GIVEN column of each of n_rows rows of fp32 logits (row r at logits_dev + r * ld, n_cols wide,
+ * any width): logprob_dev[r] = the log-probability at temperature 1 of column target_dev[r], by the definition at
+ * smoltts_session_set_slot_score with no length entry and no penalty.  One workgroup per row.  A -inf target column gives -inf; a
+ * row whose target lies outside [0, n_cols) writes nothing.  Host model: smoltts_amd/sampling.py (pick_logprob). */
+int smoltts_k_score_rows(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const int32_t* target_dev,
+                         float* logprob_dev, void* stream);
 /* The same with the keys of every (row, kv head) pair dealt over two workgroups and merged inside the launch (decode frames
  * at B <= 32: rows x kv heads <= 128, caches longer than 128 entries; other shapes run the one-workgroup kernels).
  * split_part_dev: 128 * 2 * (4 * 64 + 8) floats of scratch; split_ticket_dev: 128 int32 zeroed ONCE (tickets count up across

@@ -391,6 +391,49 @@ class SmolTTS:
             turns = [self.prompt_encoder.encode_text_turn("system", system_prompt), *turns]
         return np.concatenate(turns, axis=1).astype(np.int32)
 
+    # -- forced alignment (align.py)
+    def recording_grid(self, audio, text: str, voice: str = "heart", speaker=None, rate: int = 24000, max_seq: Optional[int] = None,
+                       max_frames: int = 1 << 30):
+        """The ``align.RecordingGrid`` of a recording and its transcript, after every refusal of ``align_recording`` (``ValueError``):
+        no ``alignment_heads``, an empty text, audio without a full frame, prompt plus frames beyond ``max_seq`` (default: the
+        model's) or ``max_frames``."""
+        import numpy as np
+
+        from .align import check_recording_fits, no_heads_error, recording_grid
+        from .server.voices import to_codec_rate
+
+        if not self.alignment_heads:
+            raise no_heads_error()
+        if not isinstance(text, str) or not text.strip():
+            raise ValueError("forced alignment needs a text")
+        pcm = to_codec_rate(np.asarray(audio, dtype=np.float64).reshape(-1), int(rate))
+        F = pcm.size // 1920
+        if F < 1:
+            raise ValueError("the audio holds no full frame (1920 samples at 24 kHz)")
+        sysprompt = speaker if speaker is not None else self.voices.get(voice)
+        a0 = int(self.prompt_encoder.build_prompt(text, voice, sysprompt).shape[1])
+        check_recording_fits(a0, F, max_seq or self.config.max_seq_len, max_frames)  # (before the encoder runs)
+        codes = self.encode_audio(pcm[: F * 1920])[:, :F]
+        return recording_grid(self.prompt_encoder, self.tokenizer, self.token_config, text, codes, voice, sysprompt)
+
+    def align_recording(self, audio, text: str, voice: str = "heart", speaker=None, rate: int = 24000):
+        """Forced alignment: mono float PCM ``audio`` at ``rate`` Hz (resampled to 24 kHz as a voice sample is) and its transcript
+        ``text`` -> ``align.RecordingAlignment``: per character and per word its start and end in seconds, and the model's own
+        log-probability of the recording's slow tokens under the text (``loss``: a wrong transcript scores worse).  The recording's
+        Mimi codes go through the slow transformer teacher-forced behind the prompt of ``text`` (``voice`` / ``speaker`` as in
+        ``__call__``) and the instance's ``alignment_heads`` are read on every audio row.  ``ValueError`` without
+        ``alignment_heads``, for an empty text, for audio shorter than one frame and for a recording that does not fit the
+        model's context."""
+        from .align import measure_recording, recording, recording_session
+
+        rg = self.recording_grid(audio, text, voice, speaker, rate)
+        sess = recording_session(self.lm, self.alignment_heads, rg.a0, rg.n_frames)
+        try:
+            rows, lp = measure_recording(sess, 0, rg)
+        finally:
+            sess.close()
+        return recording(text, rg, rows, lp, self.tokenizer)
+
     def stream(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
                reference_upsample: bool = False, output_format: Optional[str] = None, sampling=None,
                **options) -> Iterator["np.ndarray"]:

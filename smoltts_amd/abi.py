@@ -180,6 +180,7 @@ SIGNATURES = {
     "smoltts_lm_park_slots": (INT, "p p p i p"),
     "smoltts_lm_prefill_side": (INT, "p p p p i p"),
     "smoltts_lm_start_slots": (INT, "p p p p p i i p"),
+    "smoltts_lm_measure_rows": (INT, "p p p p p p i p p"),
     "smoltts_lm_decode": (INT, "p i p"),
     "smoltts_session_set_frames_per_graph": (INT, "p i p"),
     "smoltts_session_set_option": (INT, "p i i"),
@@ -287,6 +288,7 @@ SIGNATURES = {
     "smoltts_k_attention": (INT, "p p p p p i i i i i p p p"),
     "smoltts_k_attention_kv": (INT, "p p p p p i i i i i p p i p"),
     "smoltts_k_attention_align": (INT, "p p i p p p p p p i i i i i i p p"),
+    "smoltts_k_score_rows": (INT, "p i i q p p p"),
     "smoltts_k_attention_split": (INT, "p p p p p i i i i i p p i p p p"),
     "smoltts_k_attention_rows3": (INT, "p p p p p i i i i i p i p"),
     "smoltts_k_embed": (INT, "p i i p p i i i i i i p p"),

@@ -8,6 +8,11 @@ mapped to characters and seconds.  numpy only; nothing here touches the GPU exce
 the ranking tool on a checkpoint:
 
     python -m smoltts_amd.align rank --checkpoint DIR --texts FILE
+    python -m smoltts_amd.align rank --checkpoint DIR --recordings FILE --mimi-checkpoint FILE
+
+The second half is forced alignment: a recording and its transcript become the grid the model would have
+produced (``recording_grid``), the session measures that grid's audio rows teacher-forced (``LMSession.measure_rows``), and
+``recording`` turns the rows and scores into character and word times with a loss (``RecordingAlignment``).
 
 Which heads of a checkpoint track the text is a property of that checkpoint; nobody has checked this on real speech (README).
 """
@@ -259,7 +264,197 @@ def measure_heads(engine, prompts, windows, pairs, settings=None, max_frames: in
             for r, w in zip(rows, windows)]
 
 
+# ------------------------------------------------------------------------------------------------ forced alignment
+@dataclass
+class RecordingGrid:
+    """A recording with its transcript as the model would have produced it: the prompt turns, then the recording's audio columns."""
+    grid: np.ndarray          # (1 + depth, a0 + F) int32
+    a0: int                   # the first audio column
+    n_frames: int             # F
+    window: Tuple[int, int]   # [t0, t1) of the transcript's tokens in row 0
+    frame_of_row: np.ndarray  # [a0 + F] the frame a column's row produces: a0 - 1 + f -> f; -1 elsewhere
+    targets: np.ndarray       # [a0 + F] the slow id that row should produce (-1: not scored); the last column's is <|im_end|>
+
+    @property
+    def end_row(self) -> int:
+        return self.grid.shape[1] - 1
+
+
+def recording_grid(encoder, tokenizer, token_config, text: str, codes, voice: str = "heart", sysprompt=None) -> RecordingGrid:
+    """The grid of a recording: system turn (``voice``, or a cloned speaker's turns ``sysprompt``), user turn with ``text``, the
+    assistant header, then the audio columns of ``encoder.encode_vq(codes)`` without its closing turn.  ``codes``: (n_codebooks,
+    F >= 1) Mimi codes.  The row at position a0 - 1 + f produces frame f and is scored against ``codes[0, f] +
+    semantic_start_id``; the last audio column's row is scored against ``<|im_end|>`` and has no frame."""
+    if not isinstance(text, str) or not text.strip():
+        raise ValueError("forced alignment needs a text")
+    codes = np.asarray(codes)
+    if codes.ndim != 2 or codes.shape[1] < 1:
+        raise ValueError("the audio holds no full frame (1920 samples at 24 kHz)")
+    F = int(codes.shape[1])
+    prompt = np.asarray(encoder.build_prompt(text, voice, sysprompt))
+    audio = encoder.encode_vq(codes.astype(np.int64))[:, :F]
+    grid = np.concatenate([prompt, audio], axis=1).astype(np.int32)
+    a0 = int(prompt.shape[1])
+    frame_of_row = np.full(a0 + F, -1, np.int32)
+    frame_of_row[a0 - 1: a0 - 1 + F] = np.arange(F, dtype=np.int32)
+    targets = np.full(a0 + F, -1, np.int32)
+    targets[a0 - 1: a0 - 1 + F] = codes[0].astype(np.int64) + token_config.semantic_start_id
+    targets[a0 + F - 1] = token_config.im_end_id
+    return RecordingGrid(grid, a0, F, window_of(grid[0, :a0], tokenizer), frame_of_row, targets)
+
+
+def recording_limit_frames(a0: int, max_seq: int, max_frames: int) -> int:
+    """The most frames a recording behind a prompt of ``a0`` columns may have in a session of ``max_seq`` / ``max_frames``."""
+    return max(0, min(int(max_frames), int(max_seq) - 1 - int(a0)))
+
+
+def check_recording_fits(a0: int, n_frames: int, max_seq: int, max_frames: int) -> None:
+    limit = recording_limit_frames(a0, max_seq, max_frames)
+    if n_frames > limit:
+        raise ValueError(f"the recording has {n_frames * FRAME_S:.2f} s; behind this prompt the model's context allows "
+                         f"{limit * FRAME_S:.2f} s (max_seq {max_seq}, max_frames {max_frames})")
+
+
+def no_heads_error() -> ValueError:
+    return ValueError("forced alignment needs alignment_heads: rank a checkpoint's heads with `python -m smoltts_amd.align rank`")
+
+
+@dataclass
+class Word:
+    text: str
+    start: float
+    end: float
+    loss: Optional[float]  # mean -logprob of the frames whose centre lies in [start, end); None: no such frame
+
+
+@dataclass
+class RecordingAlignment:
+    """ElevenLabs' forced-alignment answer, plus what it was fitted to."""
+    alignment: Alignment
+    words: List[Word]
+    logprobs: np.ndarray   # [F] float32: the model's log-probability of each frame's slow token under the transcript
+    end_logprob: float     # ... of <|im_end|> behind the last frame (not part of the mean)
+    loss: float            # -mean(logprobs)
+
+    def to_json(self) -> dict:
+        a = self.alignment
+        return {"characters": [{"text": c, "start": float(s), "end": float(e)} for c, s, e in zip(a.characters, a.start_s, a.end_s)],
+                "words": [{"text": w.text, "start": float(w.start), "end": float(w.end), "loss": None if w.loss is None else float(w.loss)}
+                          for w in self.words],
+                "loss": float(self.loss)}
+
+
+def words_of(alignment: Alignment, logprobs: np.ndarray) -> List[Word]:
+    """Maximal runs of non-whitespace characters with the start of their first and the end of their last character."""
+    lp = np.asarray(logprobs, np.float64)
+    centres = (np.arange(lp.shape[0]) + 0.5) * FRAME_S
+    words: List[Word] = []
+    chars, n = alignment.characters, len(alignment.characters)
+    i = 0
+    while i < n:
+        if chars[i].isspace():
+            i += 1
+            continue
+        j = i
+        while j < n and not chars[j].isspace():
+            j += 1
+        start, end = float(alignment.start_s[i]), float(alignment.end_s[j - 1])
+        inside = (centres >= start) & (centres < end)
+        words.append(Word("".join(chars[i:j]), start, end, float(-lp[inside].mean()) if inside.any() else None))
+        i = j
+    return words
+
+
+def recording(text: str, rg: RecordingGrid, rows: np.ndarray, logprobs: np.ndarray, tokenizer=None) -> RecordingAlignment:
+    """``rows`` [F, heads, 2] (``LMSession.fetch_alignment`` of the measured slot) and ``logprobs`` [a0 + F]
+    (``LMSession.measure_rows``) of ``rg`` -> the ``RecordingAlignment``.  Frame f spans [f, f + 1) * 1920 / 24000 s; the last end
+    is the recording's duration."""
+    F, (t0, t1) = rg.n_frames, rg.window
+    rows = np.asarray(rows)[:F]
+    al = align(text, rg.grid[0, t0:t1], rows[:, :, 0], rows[:, :, 1], tokenizer, duration_s=F * FRAME_S)
+    lp = np.asarray(logprobs, np.float32)[rg.a0 - 1: rg.a0 - 1 + F].copy()
+    return RecordingAlignment(al, words_of(al, lp), lp, float(np.asarray(logprobs)[rg.end_row]), float(-lp.astype(np.float64).mean()))
+
+
+def measure_recording(session, slot: int, rg: RecordingGrid, chunk: Optional[int] = None, score: bool = True):
+    """``rg`` measured in the idle ``slot`` of ``session`` (its heads are set): (rows [F, heads, 2], logprobs [a0 + F]).  GPU."""
+    session.set_slot_align([slot], [rg.window[0]], [rg.window[1]])
+    lp = session.measure_rows(rg.grid, slot, rg.frame_of_row, rg.targets if score else np.full_like(rg.targets, -1), chunk)
+    return session.fetch_alignment(slot, rg.n_frames), lp
+
+
+def recording_session(engine, pairs, a0: int, n_frames: int, kv_dtype: str = "fp32"):
+    """A one-slot ``LMSession`` sized for a recording of ``n_frames`` behind ``a0`` prompt columns, measuring ``pairs``."""
+    from .lm import LMSession
+
+    T = a0 + n_frames
+    sess = LMSession(engine, 1, max_seq=T + 1, max_rows=T, max_frames=n_frames, kv_dtype=kv_dtype)
+    sess.set_align_heads(pairs)
+    return sess
+
+
+def measure_heads_recorded(engine, grids, windows, frame_maps, pairs):
+    """``measure_heads`` without sampling: each grid (a recording behind its transcript, ``recording_grid``) goes teacher-forced
+    through ``LMSession.measure_rows`` with its text window and its column -> frame map; -> the list ``rank_heads`` takes."""
+    runs = []
+    for g, w, fm in zip(grids, windows, frame_maps):
+        g, fm = np.asarray(g), np.asarray(fm, np.int32)
+        F = int(fm.max()) + 1
+        sess = recording_session(engine, pairs, g.shape[1] - F, F)
+        try:
+            sess.set_slot_align([0], [w[0]], [w[1]])
+            sess.measure_rows(g, 0, fm, np.full(g.shape[1], -1, np.int32))
+            r = sess.fetch_alignment(0, F)
+        finally:
+            sess.close()
+        runs.append({"pairs": sorted((int(l), int(h)) for l, h in pairs), "m": r[:, :, 0], "s1": r[:, :, 1], "n_tokens": w[1] - w[0]})
+    return runs
+
+
+def _rank_recordings(args) -> int:
+    """``rank --recordings FILE``: every head, 16 pairs at a time, teacher-forced on the file's recordings."""
+    from . import SmolTTS
+    from .abi import MAX_ALIGN_HEADS
+    from .server.voices import parse_wav, to_codec_rate
+
+    lines = [l.rstrip("\n").split("\t", 1) for l in open(args.recordings, encoding="utf-8") if l.strip()]
+    if not lines or any(len(l) != 2 or not l[1].strip() for l in lines):
+        print("--recordings: every line is path.wav<TAB>transcript", file=sys.stderr)
+        return 2
+    if not args.mimi_checkpoint:
+        print("--recordings needs --mimi-checkpoint (the full kyutai/mimi model: its encoder turns the recordings into codes)", file=sys.stderr)
+        return 2
+    tts = SmolTTS(checkpoint_dir=args.checkpoint, mimi_checkpoint=args.mimi_checkpoint)
+    config = tts.config
+    grids = []
+    for path, text in lines:
+        with open(path, "rb") as f:
+            codes = tts.encode_audio(to_codec_rate(*parse_wav(f.read())))
+        rg = recording_grid(tts.prompt_encoder, tts.tokenizer, tts.token_config, text.strip(), codes, args.voice)
+        check_recording_fits(rg.a0, rg.n_frames, config.max_seq_len, 1 << 30)
+        grids.append(rg)
+    every = [(l, h) for l in range(config.n_layer) for h in range(config.n_head)]
+    runs = []
+    for i in range(0, len(every), MAX_ALIGN_HEADS):
+        runs += measure_heads_recorded(tts.lm, [g.grid for g in grids], [g.window for g in grids], [g.frame_of_row for g in grids],
+                                       every[i:i + MAX_ALIGN_HEADS])
+    _print_ranking(runs, args.top)
+    tts.lm.close()
+    return 0
+
+
+def _print_ranking(runs, top: int) -> None:
+    print(f"{'layer':>5} {'head':>4} {'mass':>7} {'monotone':>8} {'coverage':>8} {'score':>7}")
+    for s in rank_heads(runs)[:top]:
+        print(f"{s.layer:5d} {s.head:4d} {s.mean_mass:7.4f} {s.monotone:8.4f} {s.coverage:8.4f} {s.score:7.4f}")
+
+
 def _rank_main(args) -> int:
+    if args.recordings:
+        return _rank_recordings(args)
+    if not args.texts:
+        print("rank needs --texts FILE or --recordings FILE", file=sys.stderr)
+        return 2
     from .abi import MAX_ALIGN_HEADS
     from .checkpoint import load_checkpoint
     from .config import NumericsMode, TokenConfig
@@ -280,9 +475,7 @@ def _rank_main(args) -> int:
     runs = []
     for i in range(0, len(every), MAX_ALIGN_HEADS):  # the heads 16 at a time: the same greedy utterances every time
         runs += measure_heads(engine, prompts, windows, every[i:i + MAX_ALIGN_HEADS], max_frames=args.max_frames)
-    print(f"{'layer':>5} {'head':>4} {'mass':>7} {'monotone':>8} {'coverage':>8} {'score':>7}")
-    for s in rank_heads(runs)[:args.top]:
-        print(f"{s.layer:5d} {s.head:4d} {s.mean_mass:7.4f} {s.monotone:8.4f} {s.coverage:8.4f} {s.score:7.4f}")
+    _print_ranking(runs, args.top)
     engine.close()
     return 0
 
@@ -292,7 +485,10 @@ def main(argv=None) -> int:
     sub = ap.add_subparsers(dest="cmd", required=True)
     r = sub.add_parser("rank", help="rank every (layer, head) of a checkpoint by how well it tracks the text; pick alignment_heads from the top")
     r.add_argument("--checkpoint", required=True)
-    r.add_argument("--texts", required=True, help="a file with one text per line")
+    r.add_argument("--texts", help="a file with one text per line: the heads are ranked on what the model generates for them")
+    r.add_argument("--recordings", help="a file with one `path.wav<TAB>transcript` per line: the heads are ranked teacher-forced "
+                                        "on these recordings (no sampling); needs --mimi-checkpoint")
+    r.add_argument("--mimi-checkpoint", help="the kyutai/mimi model.safetensors (with its encoder), for --recordings")
     r.add_argument("--voice", default="heart")
     r.add_argument("--max-frames", type=int, default=256)
     r.add_argument("--top", type=int, default=32)

@@ -50,6 +50,11 @@ int smoltts_k_attention_align(const float* q_dev, const void* k_cache_dev, int32
                                 (hipStream_t)stream);
 }
 
+int smoltts_k_score_rows(const float* logits_dev, int32_t n_rows, int32_t n_cols, int64_t ld, const int32_t* target_dev,
+                         float* logprob_dev, void* stream) {
+  return launch_score_rows(logits_dev, n_rows, n_cols, ld, target_dev, logprob_dev, (hipStream_t)stream);
+}
+
 int smoltts_k_attention_rows3(const float* q_dev, const void* k_cache3_dev, const void* v_cache3_dev, const int32_t* row_pos_dev,
                               const int32_t* row_slot_dev, int32_t n_rows, int32_t rows_per_slot, int32_t n_heads, int32_t cache_len,
                               int32_t window, float* out_dev, int32_t b3_products, void* stream) {

@@ -259,6 +259,9 @@ int launch_argmax(const float* logits, int n_rows, int n_cols, int64_t ld, int32
                   int ids_stride, float* margin, const int32_t* margin_mask, const void* emb,
                   int emb_row_offset, int dim, float* xnext, const EmitArgs* emit, const SampleArgs* sample,
                   hipStream_t stream, const QkvGather* qkv = nullptr);
+// logprob[r] = the score (SampleArgs.logprob's definition, no length entry, no penalty) of column target[r] of row r; rows whose
+// target lies outside [0, n_cols) write nothing (small_ops.hip, score_rows_kernel)
+int launch_score_rows(const float* logits, int n_rows, int n_cols, int64_t ld, const int32_t* target, float* logprob, hipStream_t stream);
 // rows [row0, row0 + n_rows) of a bf16 embedding table -> X3 operand (x gamma) + sums of squares
 int launch_emb_rows_pack(const void* emb, int64_t row0, int n_rows, int dim, const EmitArgs& emit, hipStream_t stream);
 int launch_layernorm(const float* x, const float* w, const float* b, int n_rows, int dim, float eps,

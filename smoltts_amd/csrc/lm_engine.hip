@@ -670,9 +670,18 @@ int run_tail(SmolttsSession* s, int advance_pos, hipStream_t st) {
   return launch_commit_embed(s, /*do_commit=*/1, advance_pos, st, picks);
 }
 
+// mask[r] = row r of a smoltts_lm_measure_rows call is measured (attn_align_kernel's row mask)
+__global__ void measure_mask_kernel(int n, const int* row_frame, int* mask) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n) mask[r] = row_frame[r] >= 0;
+}
+
 // Slow transformer over M rows of x (already embedded and published for layer 0).
+// `measure_frames` (smoltts_lm_measure_rows; prompt rows only): the chosen heads are measured on these rows too, row r as frame
+// measure_frames[r] of its slot (< 0: not measured).  `emit_head` (the same call, when it scores): the last block publishes the
+// slow head's operand (x * norm, sums of squares) for all M rows, as the last block of a decode frame does for its B rows.
 int run_slow_layers(SmolttsSession* s, float* x, float* q, int M, const int* row_pos, const int* row_slot, bool publish_hidden,
-                    hipStream_t st) {
+                    hipStream_t st, const int* measure_frames = nullptr, bool emit_head = false) {
   const SmolttsEngine* e = s->e;
   const SmolttsLMConfig& c = e->cfg;
   const size_t l_stride = (size_t)s->B * c.n_kv_head * s->max_seq * 64 * (s->kv_format == SMOLTTS_KV_BF16 ? 2 : 4);  // bytes
@@ -680,20 +689,32 @@ int run_slow_layers(SmolttsSession* s, float* x, float* q, int M, const int* row
     EmitArgs next{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (l + 1 < c.n_layer) next = EmitArgs{s->x3n, gamma_at(e, e->w.layers[l + 1].attn_norm), nullptr, nullptr, s->ssq};
     else if (publish_hidden) next = slow_hidden_emit(s);
+    else if (emit_head) next = EmitArgs{s->x3n, gamma_at(e, e->w.norm), nullptr, nullptr, s->ssq};
     ST_TRY(run_block(s, e->w.layers[l], c.dim, c.n_head, c.n_kv_head, c.inter, x, q, M, row_pos, row_slot,
                      (const float*)(e->arena + e->w.rope), s->kc + l * l_stride, s->vc + l * l_stride, s->max_seq, s->x3n, next, st,
                      /*first_pos=*/false, s->kv_format, -1, false, /*w_stream=*/((s->stream_w & SMOLTTS_STREAM_W_SLOW) && M <= 128)
                          ? ((s->stream_w & SMOLTTS_STREAM_W_SLOW_ONLY_W13) ? SMOLTTS_STREAM_W_DEPTH_W13 : ((s->stream_w & SMOLTTS_STREAM_W_SLOW_NOT_W13) ? (SMOLTTS_STREAM_W_DEPTH_W2 | SMOLTTS_STREAM_W_DEPTH_QKVO) : 1)) : 0));
-    if (publish_hidden && (s->form & FORM_ALIGN)) {
+    const bool frame_align = publish_hidden && (s->form & FORM_ALIGN);
+    if (frame_align || (measure_frames && s->n_align > 0)) {
       // decode frames of a form with bit 5: where this layer's chosen heads look, from q (untouched until the next layer's wqkv
-      // launch) and the layer's K rows 0 .. pos -- one more link of the frame's serial chain; row r is slot r (row_slot = iota)
+      // launch) and the layer's K rows 0 .. pos -- one more link of the frame's serial chain; row r is slot r (row_slot = iota).
+      // Measured prompt rows: the same launch with the rows' own frames; its row mask (row_frame >= 0) goes through x3h, which
+      // nothing reads between this block's w2 launch and the next block's w13 launch
       int p0 = 0, np = 0;
       for (int i = 0; i < s->n_align; ++i) {
         if (s->align_layer[i] < l) p0 = i + 1;
         if (s->align_layer[i] == l) ++np;
       }
+      const int* frames = s->frames;
+      const int* row_mask = s->mask;
+      if (np > 0 && !frame_align) {
+        frames = measure_frames;
+        row_mask = reinterpret_cast<const int*>(s->x3h);
+        hipLaunchKernelGGL(measure_mask_kernel, dim3((M + 255) / 256), dim3(256), 0, st, M, measure_frames, reinterpret_cast<int*>(s->x3h));
+        ST_CHECK_HIP(hipGetLastError());
+      }
       if (np > 0)
-        ST_TRY(launch_attention_align(q, s->kc + l * l_stride, s->kv_format, row_pos, row_slot, s->frames, s->mask, s->align_win,
+        ST_TRY(launch_attention_align(q, s->kc + l * l_stride, s->kv_format, row_pos, row_slot, frames, row_mask, s->align_win,
                                       s->align_head + p0, np, p0, s->n_align, M, c.n_head, c.n_kv_head, s->max_seq, s->max_frames,
                                       s->align_out, st));
     }
@@ -814,9 +835,9 @@ int check_slot_lists(const char* what, const SmolttsSession* s, const int32_t* s
 
 // KV rows of n_rows prompt rows, through the prefill workspace of the session given (the side call passes its shadow session)
 int prefill_rows(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_slot_dev, const int32_t* row_pos_dev, int n_rows,
-                 hipStream_t st) {
+                 hipStream_t st, const int32_t* measure_frames_dev = nullptr, bool emit_head = false) {
   ST_TRY(embed_rows(s, grid_dev, n_rows, s->xr, st));
-  return run_slow_layers(s, s->xr, s->qr, n_rows, row_pos_dev, row_slot_dev, /*publish_hidden=*/false, st);
+  return run_slow_layers(s, s->xr, s->qr, n_rows, row_pos_dev, row_slot_dev, /*publish_hidden=*/false, st, measure_frames_dev, emit_head);
 }
 
 // The staged slots (stage_upload) become live at their last prompt column; their first decode frame recomputes that column's row
@@ -1367,6 +1388,49 @@ int smoltts_lm_prefill_side(SmolttsSession* s, const int32_t* grid_dev, const in
   side.dup_code = -1;
   hipStream_t st = (hipStream_t)stream;
   return prefill_rows(&side, grid_dev, row_slot_dev, row_pos_dev, n_rows, st);
+}
+
+// Rows [r0, r0 + n) of an X3 operand of 32 * nchunks columns and of its sums of squares [rows][2 * nchunks] -> rows [0, n) of another
+// operand and array: 16-byte copies, one workgroup per row (x3.h has the layout)
+__global__ __launch_bounds__(256) void x3_rows_gather_kernel(const char* src, const float* ssq_src, int r0, int nchunks, char* dst,
+                                                             float* ssq_dst) {
+  const int md = blockIdx.x, ms = r0 + md;
+  for (int i = threadIdx.x; i < nchunks * 12; i += 256) {
+    const int c = i / 12, piece = (i % 12) >> 2, q = i & 3;
+    const size_t so = ((size_t)(ms >> 4) * nchunks + c) * 3072 + piece * 1024 + (size_t)(q * 16 + (ms & 15)) * 16;
+    const size_t dp = ((size_t)(md >> 4) * nchunks + c) * 3072 + piece * 1024 + (size_t)(q * 16 + (md & 15)) * 16;
+    *reinterpret_cast<uint4*>(dst + dp) = *reinterpret_cast<const uint4*>(src + so);
+  }
+  for (int i = threadIdx.x; i < 2 * nchunks; i += 256) ssq_dst[(size_t)md * 2 * nchunks + i] = ssq_src[(size_t)ms * 2 * nchunks + i];
+}
+
+// Forced alignment: the rows of a non-final prefill chunk, measured.  The last block publishes the head's
+// operand for every row, as a decode frame's does; the slow head then reads max_batch rows at a time -- copied to the front of
+// x3n2, their sums of squares to xt, both of which the closing commit_embed launch rewrites or nothing reads before the next
+// frame rewrites them -- into the rows the decode frames' head writes: no workspace of its own, the GEMM forms of the decode
+// frames, and a row's logits are the bits a decode frame computes for it (tests/test_forced_align_gpu.py).
+int smoltts_lm_measure_rows(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_slot_dev, const int32_t* row_pos_dev,
+                            const int32_t* row_frame_dev, const int32_t* target_dev, int32_t n_rows, float* logprob_dev, void* stream) {
+  ST_REQUIRE(s && grid_dev && row_slot_dev && row_pos_dev && row_frame_dev, SMOLTTS_E_INVALID, "lm_measure_rows: null argument");
+  ST_REQUIRE(logprob_dev == nullptr || target_dev, SMOLTTS_E_INVALID, "lm_measure_rows: scores need targets");
+  ST_REQUIRE(n_rows > 0 && n_rows <= s->max_rows, SMOLTTS_E_CAPACITY, "lm_measure_rows: %d rows, session holds %d", n_rows, s->max_rows);
+  hipStream_t st = (hipStream_t)stream;
+  const SmolttsEngine* e = s->e;
+  const SmolttsLMConfig& c = e->cfg;
+  ST_REQUIRE(c.dim % 32 == 0, SMOLTTS_E_INVALID, "lm_measure_rows: dim %% 32 != 0");
+  ST_TRY(prefill_rows(s, grid_dev, row_slot_dev, row_pos_dev, n_rows, st, row_frame_dev, /*emit_head=*/logprob_dev != nullptr));
+  if (logprob_dev) {
+    for (int r0 = 0; r0 < n_rows; r0 += s->B) {
+      const int n = n_rows - r0 < s->B ? n_rows - r0 : s->B;
+      hipLaunchKernelGGL(x3_rows_gather_kernel, dim3(n), dim3(256), 0, st, s->x3n, s->ssq, r0, c.dim / 32, s->x3n2, s->xt);
+      ST_CHECK_HIP(hipGetLastError());
+      SmolttsGemm3Args a = base3(c.weight_format, e->arena + e->w.head, s->x3n2, n, c.vocab_size, c.dim, SMOLTTS_EPI_STORE);
+      a.ssq_in_dev = s->xt; a.eps = c.norm_eps; a.out_dev = s->logits_slow; a.ldo = c.vocab_size;
+      ST_TRY(launch_gemm3(a, st));
+      ST_TRY(launch_score_rows(s->logits_slow, n, c.vocab_size, c.vocab_size, target_dev + r0, logprob_dev + r0, st));
+    }
+  }
+  return launch_commit_embed(s, /*do_commit=*/0, 0, st);  // the rows went through x3n / ssq: re-publish the decode rows
 }
 
 int smoltts_lm_start_slots(SmolttsSession* s, const int32_t* grid_dev, const int32_t* row_pos_dev, const int32_t* slots_host,

@@ -155,6 +155,63 @@ int launch_emb_rows_pack(const void* emb, int64_t row0, int n_rows, int dim, con
   return SMOLTTS_OK;
 }
 
+// ------------------------------------------------------------------------------------ score rows
+// The score of a GIVEN column: lp[r] = the log-probability, at temperature 1, of column target[r] of row r -- argmax_row's SCORE pass
+// (mass_q, the fp64 partial sums) for an id the caller supplies instead of the one the pick returns; no length entry, no penalty.
+// One workgroup per row: pass 1 takes the row's maximum, pass 2 the masses (the row comes out of L2 the second time).  The fp64
+// sum of the integer-valued masses is exact, so the order it is taken in does not matter.  A row whose target lies outside
+// [0, n_cols) writes nothing (the exit is uniform and stands in front of the first barrier); a -inf target column gives -inf.
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* logits, int n_cols, long ld, const int* target, float* lp) {
+  __shared__ float sh_max[4];
+  __shared__ double sh_m[4];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = target[r];
+  if (t < 0 || t >= n_cols) return;
+  const float* row = logits + (long)r * ld;
+  const bool vec = ((n_cols | ld) & 3) == 0;
+  float mx = -INFINITY;
+  if (vec) {
+    for (int j = tid * 4; j < n_cols; j += 1024) {
+      const float4 v = *reinterpret_cast<const float4*>(row + j);
+      mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+    }
+  } else {
+    for (int j = tid; j < n_cols; j += 256) mx = fmaxf(mx, row[j]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if (lane == 0) sh_max[wave] = mx;
+  __syncthreads();
+  const float gm = fmaxf(fmaxf(sh_max[0], sh_max[1]), fmaxf(sh_max[2], sh_max[3]));
+  double m = 0.0;
+  if (vec) {
+    for (int j = tid * 4; j < n_cols; j += 1024) {
+      const float4 v = *reinterpret_cast<const float4*>(row + j);
+      m += (double)mass_q(v.x - gm); m += (double)mass_q(v.y - gm); m += (double)mass_q(v.z - gm); m += (double)mass_q(v.w - gm);
+    }
+  } else {
+    for (int j = tid; j < n_cols; j += 256) m += (double)mass_q(row[j] - gm);
+  }
+  m = wave_sum_f64(m, lane);
+  if (lane == 0) sh_m[wave] = m;
+  __syncthreads();
+  if (tid == 0) {
+    const double total = (sh_m[0] + sh_m[1]) + (sh_m[2] + sh_m[3]);
+    const float z = row[t] - gm;
+    lp[r] = (float)((double)z - (log(total) - 40.0 * 0.6931471805599453094));
+  }
+}
+
+int launch_score_rows(const float* logits, int n_rows, int n_cols, int64_t ld, const int32_t* target, float* logprob, hipStream_t stream) {
+  ST_REQUIRE(logits && target && logprob, SMOLTTS_E_INVALID, "score_rows: null pointer");
+  ST_REQUIRE(n_rows > 0 && n_cols > 0 && ld >= n_cols, SMOLTTS_E_INVALID, "score_rows: bad shape rows=%d cols=%d ld=%lld", n_rows, n_cols,
+             (long long)ld);
+  ST_REQUIRE((((n_cols | ld) & 3) != 0) || ((uintptr_t)logits & 15) == 0, SMOLTTS_E_INVALID, "score_rows: rows of 4-column groups must be 16-byte aligned");
+  hipLaunchKernelGGL(score_rows_kernel, dim3(n_rows), dim3(256), 0, stream, logits, n_cols, (long)ld, target, logprob);
+  ST_CHECK_HIP(hipGetLastError());
+  return SMOLTTS_OK;
+}
+
 // ------------------------------------------------------------------------------------ layernorm
 // nn.LayerNorm(d_model) with bias, eps 1e-5 (mlx_inference/.../codec/transformer.py:113-114).
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, const float* w, const float* b, int dim, float eps,

@@ -434,6 +434,62 @@ class LMSession(ClosesOnDel):
             raise SmolttsError("no alignment heads are set (set_align_heads)")
         return self.alignment[int(slot), :int(n_frames)].cpu().numpy()
 
+    # ---- forced alignment: prompt rows measured instead of only stored (include/smoltts_hip.h at smoltts_lm_measure_rows)
+    def iter_measure_rows(self, grid, slot: int, frame_of_row, targets, chunk: Optional[int] = None):
+        """``measure_rows`` as a generator: one ``smoltts_lm_measure_rows`` call of at most ``chunk`` columns is queued per
+        ``next()``; the generator's return value is the device tensor of the scores (a serving loop runs its ticks in between)."""
+        g = np.asarray(grid)
+        if g.ndim != 2 or g.shape[0] != self.H or g.shape[1] < 1:
+            raise ValueError(f"grid must be ({self.H}, T>=1), got {g.shape}")
+        T, slot = int(g.shape[1]), int(slot)
+        frames, tgt = np.asarray(frame_of_row, dtype=np.int32).reshape(-1), np.asarray(targets, dtype=np.int32).reshape(-1)
+        if frames.shape[0] != T or tgt.shape[0] != T:
+            raise ValueError("measure_rows: one frame index and one target per grid column")
+        if not 0 <= slot < self.B:
+            raise ValueError(f"measure_rows: slot {slot} outside the session's {self.B}")
+        if tgt.max() >= self.engine.cfg.vocab_size:
+            raise ValueError("measure_rows: target id outside the vocabulary")
+        if frames.max() >= self.max_frames:
+            raise SmolttsError(f"measure_rows: frame {int(frames.max())} does not fit max_frames={self.max_frames}")
+        if T + 1 > self.max_seq:
+            raise SmolttsError(f"grid of {T} columns does not fit max_seq={self.max_seq}")
+        chunk = min(T, self.max_rows) if chunk is None else max(1, min(int(chunk), self.max_rows))
+        # the idle slot waits behind the rows: what its decode rows write there, nothing measured here reads
+        check(self.lib.smoltts_lm_park_slots(self.handle, (C.c_int32 * 1)(slot), (C.c_int32 * 1)(T), 1, current_stream_ptr()),
+              "smoltts_lm_park_slots")
+        lp = torch.full((T,), float("nan"), dtype=torch.float32, device=self.engine.device)
+        keep = [lp]
+        # a chunk ends in front of the first scored column, so that the head does not run over the prompt's text columns
+        first = int(np.argmax(tgt >= 0)) if bool((tgt >= 0).any()) else T
+        starts = list(range(0, first, chunk)) + list(range(first, T, chunk))
+        for c0, c1 in zip(starts, starts[1:] + [T]):
+            grid_d, rslot_d, rpos_d, _, n = self._rows([g[:, c0:c1]], [slot], [c0])
+            fr_d, tg_d = upload([frames[c0:c1], tgt[c0:c1]], self.engine.device)
+            scored = bool((tgt[c0:c1] >= 0).any())  # (the head runs only over chunks that hold a target)
+            check(self.lib.smoltts_lm_measure_rows(self.handle, dptr(grid_d), dptr(rslot_d), dptr(rpos_d), dptr(fr_d), dptr(tg_d), n,
+                                                   lp.data_ptr() + 4 * c0 if scored else None, current_stream_ptr()),
+                  "smoltts_lm_measure_rows")
+            keep += [grid_d, rslot_d, rpos_d, fr_d, tg_d]
+            self._keep = keep  # alive until the stream has consumed them
+            if c1 < T:
+                yield c1
+        return lp
+
+    def measure_rows(self, grid, slot: int, frame_of_row, targets, chunk: Optional[int] = None) -> np.ndarray:
+        """Teacher-forced measurement of a whole grid ((1 + n_fast, T), positions 0 .. T-1) in the idle ``slot``: its KV rows are
+        written as a chunked prefill writes them, column r measures the chosen heads as frame ``frame_of_row[r]`` of the slot
+        (< 0: not measured; read them with ``fetch_alignment`` -- ``set_align_heads`` and the slot's window, ``set_slot_align``,
+        come first), and the returned float32 [T] holds the log-probability of slow id ``targets[r]`` under column r's logits
+        (``sampling.pick_logprob``; NaN where ``targets[r] < 0``).  At most ``chunk`` columns go through per call of the library
+        (default: all that ``max_rows`` allows); the results do not depend on it.  No frame is emitted and the slot stays idle,
+        parked behind the grid.  Waits for the current stream."""
+        it = self.iter_measure_rows(grid, slot, frame_of_row, targets, chunk)
+        while True:
+            try:
+                next(it)
+            except StopIteration as done:
+                return done.value.cpu().numpy()
+
     def measure_duplicate(self, code: int = -1, n_filter: int = 0) -> None:
         """Measurement aid (this session only): issue every launch of one kernel class twice; -1 switches it off."""
         check(self.lib.smoltts_session_measure_duplicate(self.handle, int(code), int(n_filter)), "smoltts_session_measure_duplicate")

@@ -108,6 +108,18 @@ def attention_align(q: torch.Tensor, k_cache: torch.Tensor, row_pos: torch.Tenso
     return out
 
 
+def score_rows(logits: torch.Tensor, targets: torch.Tensor, out: torch.Tensor, n_cols: Optional[int] = None) -> torch.Tensor:
+    """The score of a given column per row (``smoltts_k_score_rows``; host model ``sampling.pick_logprob``): logits float32
+    [rows, ld] of which the first ``n_cols`` columns (default all) are the row; targets int32 [rows]; ``out`` float32 [rows] is
+    written in place (a row whose target lies outside [0, n_cols) keeps what it held)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert targets.dtype == torch.int32 and out.dtype == torch.float32 and targets.numel() == out.numel() == logits.shape[0]
+    assert targets.is_contiguous() and out.is_contiguous()
+    _k("smoltts_k_score_rows", dptr(logits), logits.shape[0], logits.shape[1] if n_cols is None else int(n_cols), logits.stride(0),
+       dptr(targets), dptr(out))
+    return out
+
+
 def kv3_cache(slots: int, n_heads: int, cache_len: int, device="cuda") -> torch.Tensor:
     """A zero-filled bf16x3 piece cache (include/smoltts_hip.h SMOLTTS_KV3_BYTES): uint8 [slots, heads, ceil32(cache_len) * 384]."""
     return torch.zeros(slots, n_heads, (cache_len + 31) // 32 * 32 * 384, dtype=torch.uint8, device=device)

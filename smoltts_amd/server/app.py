@@ -155,6 +155,12 @@ class TTSCore:
             raise ValueError(f"speaker prompt of P={P} positions leaves no room for a request: P + {t_min} (an empty request) + "
                              f"max_new_tokens {max_new} + 2 > max_seq_len {m.config.max_seq_len}")
 
+    def align_recording(self, pcm, rate: int, text: str, voice: str = "heart"):
+        """Forced alignment of a recording (mono samples at ``rate``) against ``text`` -> ``align.RecordingAlignment``, through the
+        scheduler (pool) where there is one, else the model.  ``ValueError``: what the call refuses; ``NoEncoderError``: no encoder."""
+        target = self.scheduler if self.scheduler is not None else self.model
+        return target.align_recording(pcm, text, voice=voice, rate=rate)
+
     def remove_voice(self, voice_id: str) -> None:
         with self._voice_lock:
             if voice_id not in self.voices or self.voices[voice_id]["prompt_positions"] is None:
@@ -795,6 +801,42 @@ def add_voice(item: AddVoiceRequest, http_request: Request):
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return {"voice_id": voice_id}
+
+
+class ForcedAlignmentRequest(BaseModel):
+    audio: str  # base64 RIFF WAV, as a voice sample's (server/voices.py)
+    text: str
+    voice: Optional[str] = None
+
+
+@eleven_router.post("/forced-alignment")
+def forced_alignment(item: ForcedAlignmentRequest, http_request: Request):
+    """ElevenLabs' forced alignment with a JSON body (base64 WAV in the forms and rates of ``/voices/add``) instead of multipart:
+    ``characters`` [{text, start, end}], ``words`` [{text, start, end, loss}] and ``loss`` -- the times read from the slow attention
+    while the recording's codes run through the model teacher-forced behind ``text``, the losses the model's own -log-probability of
+    the recording's slow tokens (align.py).  501 unless the server has ``alignment_heads``; 400 for audio that cannot
+    be read, an empty text, a recording shorter than one frame or longer than the model's context allows."""
+    import base64
+    import binascii
+
+    from .. import NoEncoderError
+    from .voices import parse_wav
+
+    core = http_request.app.state.tts_core
+    if not core.alignment_heads:
+        raise HTTPException(status_code=501, detail="this server has no alignment_heads: rank the checkpoint's heads with "
+                                                    "`python -m smoltts_amd.align rank --checkpoint DIR --texts FILE` and set them")
+    try:
+        pcm, rate = parse_wav(base64.b64decode(item.audio, validate=True))
+    except (binascii.Error, ValueError, TypeError) as e:
+        raise HTTPException(status_code=400, detail=f"audio: {e}")
+    try:
+        out = core.align_recording(pcm, rate, item.text, item.voice or "heart")
+    except NoEncoderError as e:
+        raise HTTPException(status_code=501, detail=str(e))
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+    return JSONResponse(_finite(out.to_json()))
 
 
 @eleven_router.get("/voices")

@@ -130,6 +130,8 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
                 out = sched.encode_speaker(msg[2], system_prompt=msg[3])
             elif kind == "add_voice":
                 out = sched.add_voice(msg[2], grid=msg[3], name=msg[4])
+            elif kind == "align_recording":
+                out = sched.align_recording(msg[2], msg[3], voice=msg[4], speaker=msg[5], rate=24000)
             else:
                 sched.remove_voice(msg[2])
                 out = None
@@ -142,7 +144,7 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
             msg = req_q.get()
             if msg[0] == "close":
                 break
-            if msg[0] in ("encode_voice", "add_voice", "remove_voice"):
+            if msg[0] in ("encode_voice", "add_voice", "remove_voice", "align_recording"):
                 threading.Thread(target=control, args=(msg,), name=f"smoltts-voice-{msg[1]}", daemon=True).start()
                 continue
             if msg[0] == "submit":
@@ -399,6 +401,25 @@ class GpuPool:
                 raise
             self._voices[voice_id] = (grid, name)
             return results[0]
+
+    def align_recording(self, audio, text: str, voice: str = "heart", speaker=None, rate: int = 24000):
+        """``BatchScheduler.align_recording`` on the least loaded worker -> its ``align.RecordingAlignment``.  Refused here, before
+        a worker sees the request (``ValueError``): a pool without ``alignment_heads``, an empty text, audio shorter than one
+        frame.  The parent has no tokenizer, so a recording too long for the context behind its prompt is refused by the
+        worker's scheduler, before its GPU work, and that ``ValueError`` is relayed."""
+        from ..align import no_heads_error
+        from .voices import to_codec_rate
+
+        if not self.alignment_heads:
+            raise no_heads_error()
+        if not isinstance(text, str) or not text.strip():
+            raise ValueError("forced alignment needs a text")
+        pcm = to_codec_rate(np.asarray(audio, dtype=np.float64).reshape(-1), int(rate))
+        if pcm.size < 1920:
+            raise ValueError("the audio holds no full frame (1920 samples at 24 kHz)")
+        if speaker is not None:
+            speaker = np.ascontiguousarray(np.asarray(speaker, dtype=np.int32))
+        return self._await_control(self._control(self._pick_worker(), ("align_recording", pcm, text, voice, speaker)))
 
     def remove_voice(self, voice_id: str) -> None:
         """Forget a registered voice on every worker (``KeyError`` if there is none)."""

@@ -518,6 +518,30 @@ class BatchScheduler:
         """The speaker grid of ``samples`` (``SmolTTS.create_speaker``), encoded on the worker thread between ticks."""
         return self._run_job({"voice_id": None, "samples": samples, "grid": None, "system_prompt": system_prompt, "name": None})
 
+    def align_recording(self, audio, text: str, voice: str = "heart", speaker=None, rate: int = 24000):
+        """Forced alignment (``SmolTTS.align_recording``) on the worker thread, between ticks: the Mimi
+        encode, then the recording's grid through the scratch one-slot session of ``add_voice`` at most one ``prefill_chunk``-column
+        chunk per loop turn, so the speaking slots are never held up by more than a chunk.  The scratch session has an alignment
+        buffer of its own; the serving session's windows, forms and graphs are not touched.  Blocks until the
+        ``align.RecordingAlignment`` is there.  ``ValueError`` (before the worker sees the request): no ``alignment_heads``, an
+        empty text, audio shorter than one frame, prompt plus frames beyond the session's ``max_seq`` or ``max_frames``."""
+        from ..align import check_recording_fits, no_heads_error
+        from .voices import to_codec_rate
+
+        if not self.alignment_heads:
+            raise no_heads_error()
+        if not isinstance(text, str) or not text.strip():
+            raise ValueError("forced alignment needs a text")
+        pcm = to_codec_rate(np.asarray(audio, dtype=np.float64).reshape(-1), int(rate))
+        F = pcm.size // 1920
+        if F < 1:
+            raise ValueError("the audio holds no full frame (1920 samples at 24 kHz)")
+        if speaker is None and voice in self._voices:
+            speaker = self._voices[voice].grid
+        a0 = int(self.tts.prompt_encoder.build_prompt(text, voice, speaker).shape[1])
+        check_recording_fits(a0, F, self.session.max_seq, self.session.max_frames)
+        return self._run_job({"align": True, "pcm": pcm[: F * 1920], "frames": F, "text": text, "voice": voice, "speaker": speaker})
+
     def _run_job(self, job: dict):
         job.update(done=threading.Event(), result=None, error=None)
         if self._dead is not None or self._draining:
@@ -891,7 +915,7 @@ class BatchScheduler:
             if self._jobs.empty():
                 return
             job = self._jobs.get_nowait()
-            self._job = {"job": job, "steps": self._voice_steps(job)}
+            self._job = {"job": job, "steps": self._align_steps(job) if job.get("align") else self._voice_steps(job)}
         job = self._job["job"]
         try:
             next(self._job["steps"])
@@ -905,7 +929,6 @@ class BatchScheduler:
 
     def _voice_steps(self, job):
         from ..abi import SmolttsError
-        from ..lm import LMSession
 
         grid = job["grid"]
         if grid is None:
@@ -930,9 +953,7 @@ class BatchScheduler:
             raise ValueError(f"speaker prompt of P={P} positions leaves no room for a request: P + {T_min} (an empty request) + "
                              f"max_new_tokens {self.settings.max_new_tokens} + 2 > max_seq_len {self.session.max_seq}")
         chunk = self.prefill_chunk or 128
-        if self._scratch is None:
-            self._scratch = LMSession(self.tts.lm, 1, max_seq=self.session.max_seq, max_rows=chunk, max_frames=1,
-                                      kv_dtype=self.session.kv_dtype)
+        self._scratch_session()
         # the speaker grid alone, as non-final chunks (what a direct chunked prefill of the voice's prompts writes into a slot)
         for a in range(0, P, chunk):
             self._scratch.prefill([grid[:, a: a + chunk]], [0], pos0=[a], final=False)
@@ -941,6 +962,44 @@ class BatchScheduler:
         prefix = self._scratch.save_prefix(0, P)  # on the frame stream: every later install is queued behind it
         self._voices[job["voice_id"]] = _Voice(job["voice_id"], grid, prefix, job["name"])
         job["result"] = {"voice_id": job["voice_id"], "prompt_positions": P}
+
+    def _scratch_session(self):
+        """The one-slot session the voices' prefixes are computed and recordings are measured in (created on first use).  Where the
+        scheduler has ``alignment_heads`` it holds a recording's frames and an alignment buffer of its own."""
+        from ..lm import LMSession
+
+        if self._scratch is None:
+            self._scratch = LMSession(self.tts.lm, 1, max_seq=self.session.max_seq, max_rows=self.prefill_chunk or 128,
+                                      max_frames=self.session.max_frames if self.alignment_heads else 1, kv_dtype=self.session.kv_dtype)
+            if self.alignment_heads:
+                self._scratch.set_align_heads(self.alignment_heads)
+        return self._scratch
+
+    def _align_steps(self, job):
+        """A forced alignment, a step per loop turn: the encode, then one chunk of the recording's grid per step."""
+        from ..abi import SmolttsError
+        from ..align import recording, recording_grid
+
+        tts = self.tts
+        try:
+            codes = tts.encode_audio(job["pcm"])[:, :job["frames"]]
+        except SmolttsError as e:  # the encoder refuses the audio (e.g. beyond its position limit): the client's input
+            raise ValueError(f"cannot encode the recording: {e}") from e
+        yield
+        rg = recording_grid(tts.prompt_encoder, tts.tokenizer, tts.token_config, job["text"], codes, job["voice"], job["speaker"])
+        s = self._scratch_session()
+        s.set_slot_align([0], [rg.window[0]], [rg.window[1]])
+        steps = s.iter_measure_rows(rg.grid, 0, rg.frame_of_row, rg.targets, self.prefill_chunk or 128)
+        while True:
+            try:
+                next(steps)
+            except StopIteration as done:
+                lp_dev = done.value
+                break
+            yield
+        rows, lp = s.fetch_alignment(0, rg.n_frames), lp_dev.cpu().numpy()  # (waits for the frame stream: the tick in flight)
+        s.set_slot_align([0], [0], [0])
+        job["result"] = recording(job["text"], rg, rows, lp, tts.tokenizer)
 
     # ------------------------------------------------------------------ worker: ticks and snapshots
     def _tick_and_snapshot(self) -> None:
