@@ -956,6 +956,38 @@ int smoltts_limiter_apply(SmolttsLimiter* l, const float* pcm_dev, int32_t n, do
  * 1440 required gains of samples pos - 1446 .. pos - 7, the 126 samples pos - 126 .. pos - 1.  Synchronises the stream. */
 int smoltts_limiter_slot_state(SmolttsLimiter* l, int32_t slot, int64_t* ints_host, double* values_host, void* stream);
 
+/* ------------------------------------------------------------------------------ Streamed alignment fit
+ * (ABI 9, additive) The causal fit of streamed character timestamps (smoltts_amd/csrc/align_fit.hip; the
+ * numpy model, reproduced bit for bit, is smoltts_amd/align.py StreamFit).  A slot holds one stream's fit: the frames it has
+ * consumed, the stack of pooled blocks and the token starts committed so far, in frames, fp64.  A start is committed once a block
+ * at or above the token's level began `lag` frames back, and is never revised. */
+typedef struct SmolttsAlignFit SmolttsAlignFit;
+
+/* Device slab of a fitter for max_batch slots (256-byte aligned, caller-owned): per slot a header, a stack of max_frames blocks
+ * and max_tokens starts.  0 for sizes outside 1 .. 65536 slots, 1 .. 2^20 frames or tokens.  Every slot starts off. */
+size_t smoltts_align_fit_bytes(int32_t max_batch, int32_t max_frames, int32_t max_tokens);
+int smoltts_align_fit_create(void* slab_dev, size_t slab_bytes, int32_t max_batch, int32_t max_frames, int32_t max_tokens,
+                             SmolttsAlignFit** out);
+void smoltts_align_fit_destroy(SmolttsAlignFit* a);
+
+/* Start a stream in (or, n_tokens < 0, switch off) slots_host[0 .. n_slots): n_tokens_host the text's tokens (0 .. max_tokens),
+ * lag_host the lag in frames (1 .. 64), cap_frames_host the frames the slot's request may have (1 .. max_frames): the stream
+ * ends there, or where the session's done flag stands with a frame.  A bad value refuses the call with its group of 16 slots
+ * unlaunched.  Ordered on `stream`; queue it where the slot's frame counter is 0 by the time of the next push. */
+int smoltts_align_fit_reset_slots(SmolttsAlignFit* a, const int32_t* slots_host, const int32_t* n_tokens_host, const int32_t* lag_host,
+                                  const int32_t* cap_frames_host, int32_t n_slots, void* stream);
+
+/* One launch over every slot: slot b consumes rows_dev float [max_batch][max_frames][n_pairs][2] (smoltts_session_alignment; 8-byte
+ * aligned, max_frames the handle's) from the frame it has seen up to min(n_frames_dev[b], its budget), and gives every remaining
+ * token its start once (done_dev[b] != 0 and n_frames_dev[b] > 0) or n_frames_dev[b] >= its budget: with F the frames consumed.
+ * A slot that is off or has ended, or whose counter is negative, is left alone. */
+int smoltts_align_fit_push(SmolttsAlignFit* a, const float* rows_dev, int32_t n_pairs, int32_t max_frames, const int32_t* n_frames_dev,
+                           const int32_t* done_dev, void* stream);
+
+/* Device pointers (valid for the handle's lifetime): starts double [max_batch][*max_tokens], entries [b][0 .. committed[b]) final;
+ * committed int32 [max_batch].  Each may be NULL. */
+int smoltts_align_fit_outputs(SmolttsAlignFit* a, double** starts_dev, int32_t** committed_dev, int32_t* max_tokens);
+
 /* --------------------------------------------------------------- operator-level test entry points */
 enum {  /* prologue applied to the activation operand */
   SMOLTTS_PRO_NONE = 0,

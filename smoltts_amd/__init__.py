@@ -514,6 +514,58 @@ class SmolTTS:
             msess.close()
             sess.close()
 
+    def stream_with_timestamps(self, input: str, voice: Optional[str] = "heart", generation_settings=None, overlap: bool = True,
+                               output_format: Optional[str] = None, sampling=None, timestamp_lag_frames: int = 6, **options):
+        """``stream`` of one utterance with character timestamps as it goes: yields ``(chunk, part)`` -- the
+        chunks of ``stream`` and, with the chunk whose frame committed them, the ``align.AlignmentPart`` of the characters whose
+        end became known (None: none; a part that comes without samples has an empty chunk).  A character's time follows its
+        audio by ``timestamp_lag_frames`` (1 .. 64) frames and is never revised; the parts concatenate to ``last_alignment``.
+        Needs the instance's ``alignment_heads``; ``ValueError`` with ``segment``, the trim options, ``best_of`` or
+        ``timestamps``.  The audio is ``stream``'s with the same ``sampling``; a call without ``sampling=`` runs in the
+        per-request mode, as ``__call__`` with ``timestamps`` does."""
+        import numpy as np
+
+        from .align import StreamAligner, check_lag, check_live_timestamps, window_of
+        from .config import RequestSampling
+        from .generate import LiveTimestamps, resolve_sampling, stream_pcm
+        from .mimi import MimiSession
+        from .request import parse_request
+
+        if not isinstance(input, str):
+            raise ValueError("stream_with_timestamps takes the text whole")
+        req = parse_request(input, stream=True, output_format=output_format, **options)
+        check_live_timestamps(req, True, bool(self.alignment_heads), getattr(sampling, "takes", 1) if sampling is not None else 1)
+        lag = check_lag(timestamp_lag_frames)
+        self._check_best_of(sampling, generation_settings, stream=True)
+        marked = self._marks(req.watermark)
+        voice = voice if voice is not None else "0"
+        self.last_alignment = None
+        self.last_finish_reason = None
+        prompt = np.asarray(self._get_prompt(input, voice))
+        if prompt.ndim == 3:
+            prompt = prompt[0]
+        settings = self._settings(generation_settings)
+        settings, self.last_sampling = self._bounded(input, settings, resolve_sampling(sampling if sampling is not None else RequestSampling(),
+                                                                                      settings, 1))
+        t0, t1 = window_of(prompt[0], self.tokenizer)
+        aligner = StreamAligner(input, prompt[0, t0:t1], self.tokenizer, speed=req.speed)
+        sess = self._stream_session(prompt, settings, self.last_sampling)
+        msess = live = None
+        try:
+            sess.set_align_heads(self.alignment_heads)
+            sess.set_slot_align([0], [t0], [t1])
+            live = LiveTimestamps(sess, aligner, lag)
+            msess = MimiSession(self.codec, max_batch=1, max_chunk_frames=1)
+            yield from stream_pcm(sess, msess, prompt, stop_on_eos=True, overlap=overlap, options=req, watermark=marked, live=live)
+            self.last_finish_reason = self._stream_reason(sess)
+            self.last_alignment = aligner.alignment()
+        finally:
+            if msess is not None:
+                msess.close()
+            if live is not None:
+                live.close()
+            sess.close()
+
     def _max_new(self, settings) -> int:
         return settings.max_new_tokens if settings.max_new_tokens is not None else self.config.max_seq_len
 

@@ -281,6 +281,12 @@ SIGNATURES = {
     "smoltts_limiter_chunk": (INT, "p p q i i p p p q p p"),
     "smoltts_limiter_apply": (INT, "p p i d p p p"),
     "smoltts_limiter_slot_state": (INT, "p i p p p"),
+    "smoltts_align_fit_bytes": (SIZE, "i i i"),
+    "smoltts_align_fit_create": (INT, "p z i i i p*"),
+    "smoltts_align_fit_destroy": (None, "p"),
+    "smoltts_align_fit_reset_slots": (INT, "p p p p p i p"),
+    "smoltts_align_fit_push": (INT, "p p i i p p p"),
+    "smoltts_align_fit_outputs": (INT, "p p* p* i*"),
     "smoltts_k_gemm": (INT, "GemmArgs* p"),
     "smoltts_gemm3_attn_fusable": (INT, "i i i"),
     "smoltts_k_gemm3": (INT, "Gemm3Args* p"),

@@ -205,6 +205,203 @@ def align(text: str, ids: Sequence[int], m: np.ndarray, s1: np.ndarray, tokenize
     return Alignment(list(text), start_s, end_s, ft.mass, ft.centroid)
 
 
+# ------------------------------------------------------------------------------------------------ the causal fit
+MIN_LAG, MAX_LAG, DEFAULT_LAG = 1, 64, 6
+
+
+def check_lag(lag) -> int:
+    if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not MIN_LAG <= int(lag) <= MAX_LAG:
+        raise ValueError(f"timestamp_lag_frames must be an int in {MIN_LAG} .. {MAX_LAG}, got {lag!r}")
+    return int(lag)
+
+
+def check_live_timestamps(opts, stream: bool, has_heads: bool, takes: int = 1) -> None:
+    """What every front end refuses of a request with ``live_timestamps`` (``opts``: its parsed ``request.SpeechOptions``)."""
+    if not has_heads:
+        raise ValueError("timestamps need alignment_heads: rank a checkpoint's heads with `python -m smoltts_amd.align rank`")
+    if not stream:
+        raise ValueError("live_timestamps apply to streams: use `timestamps` for a blocking request")
+    if opts.timestamps:
+        raise ValueError("live_timestamps cannot be combined with timestamps")
+    if opts.segment is not None:
+        raise ValueError("live_timestamps cannot be combined with segment: the seam cuts samples where the audio says so")
+    if opts.trims:
+        raise ValueError("live_timestamps cannot be combined with trim_silence or max_pause_s: the trim stage cuts samples where the audio says so")
+    if takes > 1:
+        raise ValueError("live_timestamps cannot be combined with best_of")
+
+
+class StreamFit:
+    """The causal fit of one stream, frame by frame: the specification of csrc/align_fit.hip, which gives the same bits.
+
+    ``push`` takes one frame's ``m`` / ``s1`` of the chosen heads.  The weighted frames are pooled as ``isotonic`` pools them, in
+    its order; token i's start is committed once a block at or above its level i - 0.5 begins at least ``lag`` frames back, as
+    ``fit``'s crossing over the blocks so far, raised to the start in front of it.  A committed start is never revised.
+    ``finish(F)`` gives every remaining token ``fit``'s value over what has been seen, cut at F.  ``lag`` is not checked here: at
+    or above the number of frames nothing commits early and the starts are ``fit``'s."""
+
+    def __init__(self, n_tokens: int, lag: int = DEFAULT_LAG):
+        self.n, self.lag = max(int(n_tokens), 0), int(lag)
+        self.frames = 0
+        self.v: List[float] = []
+        self.w: List[float] = []
+        self.f0: List[int] = []
+        self.f1: List[int] = []
+        self.starts: List[float] = [0.0] if self.n > 0 else []
+        self.finished = False
+
+    @property
+    def committed(self) -> int:
+        return len(self.starts)
+
+    def _crossing(self, i: int, lag: Optional[int], f: int) -> Optional[float]:
+        """Where the curve over the blocks passes token i's level; None: no block reaches it (or, with ``lag``, too recently)."""
+        level = i - 0.5
+        j = len(self.v)  # from the top: the uncommitted levels live there
+        while j > 0 and self.v[j - 1] >= level:
+            j -= 1
+        if j == len(self.v) or (lag is not None and f - self.f0[j] < lag):
+            return None
+        if j == 0:
+            return 0.0
+        xa, xb = self.f1[j - 1] + 0.5, self.f0[j] + 0.5
+        return xa + (level - self.v[j - 1]) / (self.v[j] - self.v[j - 1]) * (xb - xa)
+
+    def push(self, m, s1) -> None:
+        if self.finished:
+            raise ValueError("the stream has finished")
+        m, s1 = np.asarray(m, np.float32).astype(np.float64).reshape(-1), np.asarray(s1, np.float32).astype(np.float64).reshape(-1)
+        f = self.frames
+        self.frames += 1
+        measured = m.size > 0
+        mass, s = 0.0, 0.0
+        for h in range(m.size):  # one add at a time, in pair order (numpy's own sum is pairwise from 8 elements on)
+            measured = measured and bool(m[h] >= 0)
+            mass = mass + float(m[h])
+            s = s + float(s1[h])
+        if not (measured and mass >= MIN_MASS):
+            return
+        self.v.append(s / mass); self.w.append(mass); self.f0.append(f); self.f1.append(f)
+        v, w = self.v, self.w
+        while len(v) > 1 and v[-2] > v[-1]:
+            ww = w[-2] + w[-1]
+            v[-2] = (v[-2] * w[-2] + v[-1] * w[-1]) / ww
+            w[-2] = ww
+            self.f1[-2] = self.f1[-1]
+            v.pop(); w.pop(); self.f0.pop(); self.f1.pop()
+        while len(self.starts) < self.n:
+            c = self._crossing(len(self.starts), self.lag, f)
+            if c is None:
+                break
+            self.starts.append(max(c, self.starts[-1]))
+
+    def push_rows(self, rows) -> None:
+        """``rows`` [frames, heads, 2] as the session writes them."""
+        for r in np.asarray(rows, np.float32):
+            self.push(r[:, 0], r[:, 1])
+
+    def finish(self, F: int) -> np.ndarray:
+        """The stream delivers ``F`` frames of audio: the remaining starts, then all of them [n] in frames."""
+        F = int(F)
+        if not self.finished:
+            self.finished = True
+            while len(self.starts) < self.n:
+                i = len(self.starts)
+                if not self.v:
+                    c = i * (F / max(self.n, 1))
+                else:
+                    c = self._crossing(i, None, 0)
+                    c = float(F) if c is None else c
+                self.starts.append(min(max(c, self.starts[-1]), float(F)))
+        return np.asarray(self.starts, np.float64)
+
+
+@dataclass
+class AlignmentPart:
+    """The characters of a stream whose end became known since the part before, with their times in seconds."""
+    characters: List[str]
+    start_s: List[float]
+    end_s: List[float]
+
+    def to_json(self) -> dict:
+        return {"characters": list(self.characters), "character_start_times_seconds": [float(t) for t in self.start_s],
+                "character_end_times_seconds": [float(t) for t in self.end_s]}
+
+
+class StreamAligner:
+    """Committed token starts -> ``AlignmentPart``s.  ``update(starts)`` takes the starts committed so far (in frames; a prefix
+    that only grows) and returns the characters whose end they settle, or None; ``finish(starts, duration_s)`` takes all of
+    them and returns the rest, clamped to the delivered duration, the last end set to it.  Seconds are frames * FRAME_S / speed,
+    nominal at a speed other than 1 as ``align``'s are.  A part handed out is not revised; ``alignment()`` concatenates them."""
+
+    def __init__(self, text: str, ids: Sequence[int], tokenizer=None, speed: Optional[float] = None):
+        self.text = text
+        self.spans = token_spans(text, ids, tokenizer)
+        self.n = len(ids)
+        self.speed = float(speed) if speed else 1.0
+        self.scale = FRAME_S / self.speed
+        self.next_char = 0
+        self.parts: List[AlignmentPart] = []
+        self.finished = False
+
+    def _part(self, starts: np.ndarray, known: int, total: Optional[float]) -> Optional[AlignmentPart]:
+        """The characters from ``next_char`` on whose times need only starts[:known] (and, at the end, ``total``)."""
+        ts = np.asarray(starts, np.float64)[:known] * self.scale
+        if total is not None:
+            ts = np.minimum(ts, total)
+        chars, a_s, e_s = [], [], []
+        k = self.next_char
+        while k < len(self.spans):
+            a, b = self.spans[k]
+            if b > a:
+                if b < self.n:
+                    if b >= known:
+                        break
+                    start, end = float(ts[a]), float(ts[b])
+                elif total is None:
+                    break  # the last token's end is the delivered duration
+                else:
+                    start, end = float(ts[a]), total
+            else:  # a dropped character: an empty interval where it would stand
+                if a < self.n:
+                    if a >= known:
+                        break
+                    start = end = float(ts[a])
+                elif total is None:
+                    break
+                else:
+                    start = end = total
+            chars.append(self.text[k]); a_s.append(start); e_s.append(end)
+            k += 1
+        if k == self.next_char:
+            return None
+        self.next_char = k
+        part = AlignmentPart(chars, a_s, e_s)
+        self.parts.append(part)
+        return part
+
+    def duration(self, frames: int) -> float:
+        """What ``frames`` frames deliver, in seconds: their samples over the rate (the blocking route's figure), over the speed."""
+        return int(frames) * FRAME_SAMPLES / SAMPLE_RATE / self.speed
+
+    def update(self, starts) -> Optional[AlignmentPart]:
+        if self.finished:
+            raise ValueError("the stream has finished")
+        return self._part(starts, min(len(starts), self.n), None)
+
+    def finish(self, starts, duration_s: float) -> Optional[AlignmentPart]:
+        if self.finished:
+            return None
+        if len(starts) < self.n:
+            raise ValueError(f"finish needs every start: {len(starts)} of {self.n}")
+        self.finished = True
+        return self._part(starts, self.n, float(duration_s))
+
+    def alignment(self) -> Alignment:
+        return Alignment([c for p in self.parts for c in p.characters], [t for p in self.parts for t in p.start_s],
+                         [t for p in self.parts for t in p.end_s])
+
+
 # ------------------------------------------------------------------------------------------------ which heads track the text
 @dataclass
 class HeadScore:

@@ -25,7 +25,7 @@ CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libsmoltts_hip.so"
 SOURCES = ["api.hip", "gemm.hip", "gemm_b3.hip", "gemm3.hip", "attention.hip", "small_ops.hip", "lm_engine.hip", "mimi_engine.hip", "mimi_encoder.hip",
            "seanet.hip", "seanet_last.hip", "conv_xs.hip", "conv_ks.hip", "resample.hip", "tsm.hip", "flac.hip", "seam.hip", "trim.hip", "loudness.hip",
-           "watermark.hip", "limiter.hip"]
+           "watermark.hip", "limiter.hip", "align_fit.hip"]
 ARCH = "gfx950"
 # -amdgpu-kernarg-preload-count: the leading scalar arguments of a kernel arrive in SGPRs at wave launch instead of behind a
 # scalar load from memory nobody has touched since the last replay (gemm3.hip, attention.hip: the frame's launches put what

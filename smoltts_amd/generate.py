@@ -273,9 +273,46 @@ def generate_blocking(model: LMEngine, prompt: np.ndarray, generation_settings: 
     return np.concatenate(out, axis=-1)
 
 
+class LiveTimestamps:
+    """What ``stream_pcm`` needs to hand out character timestamps with its chunks: a one-slot ``AlignFitter``
+    beside ``session`` (its alignment heads and slot 0's window are set) and the ``align.StreamAligner`` of the text."""
+
+    def __init__(self, session: LMSession, aligner, lag: int):
+        from .lm import AlignFitter
+
+        self.aligner, self.lag, self.n = aligner, int(lag), int(aligner.n)
+        self.fitter = AlignFitter.for_session(session)
+        self.count = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.starts = torch.zeros(max(self.n, 1), dtype=torch.float64).pin_memory()
+
+    def start(self, cap: int) -> None:
+        """Current stream: slot 0 starts its fit; the stream ends at ``cap`` frames at the latest."""
+        self.fitter.reset_slots([0], [self.n], [self.lag], [cap])
+
+    def queue(self, session: LMSession, n_d, done_d) -> None:
+        """Current stream: the frames up to the counter ``n_d`` are fitted, and the committed starts travel to the host."""
+        self.fitter.push(session.alignment, n_d, done_d)
+        self.count.copy_(self.fitter.committed, non_blocking=True)
+        self.starts.copy_(self.fitter.starts[0, :self.starts.numel()], non_blocking=True)
+
+    def part(self, n: int, last: bool):
+        """Once the stream has been waited for: the ``align.AlignmentPart`` of this frame (None: none); ``last``: the stream ends
+        here with ``n`` frames delivered."""
+        c = int(self.count[0])
+        starts = self.starts.numpy()[:c].copy()
+        if not last:
+            return self.aligner.update(starts)
+        if c != self.n:
+            raise RuntimeError(f"the fit of a finished stream holds {c} of {self.n} starts")
+        return self.aligner.finish(starts, self.aligner.duration(n))
+
+    def close(self) -> None:
+        self.fitter.close()
+
+
 def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bool = True, max_frames: Optional[int] = None,
                overlap: bool = True, conv: Optional[StreamConverter] = None, final: bool = True,
-               options: Optional[SpeechOptions] = None, watermark=None) -> Iterator[np.ndarray]:
+               options: Optional[SpeechOptions] = None, watermark=None, live: Optional[LiveTimestamps] = None) -> Iterator[np.ndarray]:
     """One utterance in slot 0 of ``session`` -> one 1920-sample float32 chunk per generated frame, as the reference's
     ``SmolTTS.stream`` yields them (mlx_inference/src/smoltts_mlx/__init__.py:83-95: every frame of ``SingleBatchGenerator`` through
     ``codec.decode_step``), the terminating ``<|im_end|>`` frame included.
@@ -307,7 +344,11 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
     ``conv``: the utterance is one segment of a long text (``longform``): the caller's ``StreamConverter(seam=True)``, with the
     stream's stages started in slot 0 and this segment opened (``start_segments``), converts it and is not closed here;
     ``options`` and ``watermark`` are then ignored.  The end of the utterance, derived on the device, is the seam's end
-    of segment, and the end of the stream only where ``final``; the resampler's tail follows the final segment only."""
+    of segment, and the end of the stream only where ``final``; the resampler's tail follows the final segment only.
+
+    ``live`` (a ``LiveTimestamps``; one utterance, no ``conv``): the generator yields ``(chunk, align.AlignmentPart or None)``
+    instead of chunks: behind each frame's codec step the causal fit consumes the frames of the same counter snapshot the host
+    reads, and the part holds the characters whose times that committed.  A part without samples comes with an empty chunk."""
     s = session
     limit = s.max_frames if max_frames is None else min(max_frames, s.max_frames)
     dev = s.engine.device
@@ -326,6 +367,8 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
         msession.reset()
         if own:
             conv.start([0], [options if options is not None else parse_request()], [watermark is not None])
+        if live is not None:
+            live.start(limit)
     converted = conv.converts(0)
     ends_on_device, segmented = conv.ends([0])  # a stage must see the end of the stream / of the segment
     with torch.cuda.stream(lm_stream):
@@ -344,7 +387,7 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
             ev.synchronize()  # frame f is in the output ring
             out = None
             with torch.cuda.stream(codec_stream):
-                if not ends_on_device:
+                if not ends_on_device and live is None:
                     state_host[0:1].copy_(s.n_frames[0:1], non_blocking=True)
                     state_host[1:2].copy_(s.done[0:1], non_blocking=True)
                     n_d, done_d = s.n_frames[0:1], s.done[0:1]
@@ -364,18 +407,28 @@ def stream_pcm(session: LMSession, msession, prompt: np.ndarray, stop_on_eos: bo
                     out.to_host(codec_stream)
                 else:
                     pcm_host.copy_(pcm_dev, non_blocking=True)
+                if live is not None:
+                    live.queue(s, n_d, done_d)
             codec_stream.synchronize()
             n, done = int(state_host[0]), int(state_host[1])
+            part = None
+            if live is not None:  # (the stream ends with this frame by the rule of the three exits below)
+                part = live.part(min(n, limit), n <= f or bool(done and n == f + 1) or f + 1 >= limit)
             if out is not None:
                 # (a call after the slot stopped consumed nothing: its tail is that of the last frame)
                 chunk = out.chunk(0, last=final and (n <= f or bool(done and n == f + 1) or f + 1 >= limit))
                 # (a stretched frame that finalised no sample yields nothing, nor does a float stage fed no sample)
-                if chunk.size or (not ends_on_device and chunk.dtype != np.float32):
+                if live is not None:
+                    if chunk.size or part is not None:
+                        yield chunk, part
+                elif chunk.size or (not ends_on_device and chunk.dtype != np.float32):
                     yield chunk
+            elif live is not None and n <= f and part is not None:
+                yield np.zeros(0, np.float32), part
             if n <= f:  # the slot had stopped before this frame
                 break
             if out is None:
-                yield pcm_host.numpy().reshape(-1).copy()
+                yield pcm_host.numpy().reshape(-1).copy() if live is None else (pcm_host.numpy().reshape(-1).copy(), part)
             if done and n == f + 1:
                 break
             if not overlap and f + 1 < limit:

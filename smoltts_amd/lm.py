@@ -569,6 +569,61 @@ class LMSession(ClosesOnDel):
             self.handle = None
 
 
+class AlignFitter(ClosesOnDel):
+    """The causal fit of streamed character timestamps on the device (include/smoltts_hip.h at "Streamed alignment fit"; the
+    model is ``align.StreamFit``): per slot the token starts committed so far.  ``starts`` float64 [B, max_tokens] and
+    ``committed`` int32 [B] are views of the fitter's slab; ``push`` is one launch over every slot on the current stream."""
+
+    def __init__(self, device, max_batch: int, max_frames: int, max_tokens: int):
+        self.lib = load_library()
+        self.B, self.max_frames, self.max_tokens = int(max_batch), int(max_frames), int(max_tokens)
+        need = self.lib.smoltts_align_fit_bytes(self.B, self.max_frames, self.max_tokens)
+        if need == 0:
+            raise SmolttsError("smoltts_align_fit_bytes returned 0 (bad sizes)")
+        self.slab = _alloc_slab(need, device, settle=True)
+        h = C.c_void_p()
+        check(self.lib.smoltts_align_fit_create(dptr(self.slab), need, self.B, self.max_frames, self.max_tokens, C.byref(h)),
+              "smoltts_align_fit_create")
+        self.handle = h
+        sp, cp, mt = C.c_void_p(), C.c_void_p(), C.c_int32()
+        check(self.lib.smoltts_align_fit_outputs(h, C.byref(sp), C.byref(cp), C.byref(mt)), "smoltts_align_fit_outputs")
+        base = self.slab.data_ptr()
+        self.starts = self.slab[sp.value - base: sp.value - base + self.B * self.max_tokens * 8].view(torch.float64).view(self.B, self.max_tokens)
+        self.committed = self.slab[cp.value - base: cp.value - base + self.B * 4].view(torch.int32)
+
+    @classmethod
+    def for_session(cls, session: "LMSession") -> "AlignFitter":
+        return cls(session.engine.device, session.B, session.max_frames, session.max_seq)
+
+    def reset_slots(self, slots: Sequence[int], n_tokens: Sequence[Optional[int]], lag: Sequence[int], cap_frames: Sequence[int]) -> None:
+        """Start a stream in ``slots`` (``n_tokens[i]`` None: switch the slot off); ordered on the current stream."""
+        n = len(slots)
+        if n == 0:
+            return
+        if not (len(n_tokens) == len(lag) == len(cap_frames) == n):
+            raise ValueError("align fit: one entry per slot")
+        arr = lambda xs: (C.c_int32 * n)(*[int(x) for x in xs])
+        check(self.lib.smoltts_align_fit_reset_slots(self.handle, arr(slots), arr([-1 if t is None else t for t in n_tokens]), arr(lag),
+                                                     arr(cap_frames), n, current_stream_ptr()), "smoltts_align_fit_reset_slots")
+
+    def push(self, rows: torch.Tensor, n_frames: torch.Tensor, done: torch.Tensor) -> None:
+        """``rows`` float32 [B, max_frames, pairs, 2] (``LMSession.alignment``), the session's frame counters and done flags."""
+        if rows.dtype != torch.float32 or rows.dim() != 4 or rows.shape[0] != self.B or rows.shape[1] != self.max_frames or rows.shape[3] != 2 \
+                or not rows.is_contiguous():
+            raise ValueError(f"align fit: rows must be contiguous float32 [{self.B}, {self.max_frames}, pairs, 2], got {tuple(rows.shape)}")
+        for t in (n_frames, done):
+            if t.dtype != torch.int32 or t.numel() != self.B or not t.is_contiguous():
+                raise ValueError(f"align fit: counters must be contiguous int32 [{self.B}]")
+        check(self.lib.smoltts_align_fit_push(self.handle, dptr(rows), int(rows.shape[2]), self.max_frames, dptr(n_frames), dptr(done),
+                                              current_stream_ptr()), "smoltts_align_fit_push")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize()
+            self.lib.smoltts_align_fit_destroy(self.handle)
+            self.handle = None
+
+
 class PrefixKV(ClosesOnDel):
     """The slow KV rows of positions [0, P) of one prompt prefix (a cloned voice's speaker turns), in a slab of its own
     (``LMSession.save_prefix``): any session on the same engine with the same kv dtype installs it into a slot in one copy

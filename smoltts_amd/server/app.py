@@ -69,7 +69,7 @@ class TTSCore:
             return str(voice) in self.voices
 
     def _request_kw(self, text: str, speed: Optional[float], loudness=None, stream: bool = False, voice=None,
-                    timestamps: bool = False, pieces: Optional[dict] = None) -> Tuple[dict, int]:
+                    timestamps: bool = False, pieces: Optional[dict] = None, one_utterance: bool = False) -> Tuple[dict, int]:
         """(kwargs, segments): the request's options resolved -- the body's fields where it names them (null: off), else the
         server's settings -- parsed once, and handed on as the parsed value's own keywords (``SpeechOptions.given``): only the
         options that are on, so that the model sees the calls it saw before when none is.  ``loudness``: the body's
@@ -87,7 +87,7 @@ class TTSCore:
             limit = int(st("max_input_chars", 5000))
             if len(text) > limit:
                 raise ValueError(f"input has {len(text)} characters; max_input_chars is {limit}")
-            if not timestamps:  # (a request with timestamps is one utterance: chained segments have none)
+            if not timestamps and not one_utterance:  # (a request with timestamps, blocking or streamed, is one utterance: chained segments have none)
                 seg = seg_opts
         target, start = body.resolve(st("loudness", None)) if body is not None else (st("loudness", None), None)
         on, pause, thr, ceiling = bool(st("trim_silence", False)), st("max_pause_s", None), None, st("peak_limit_db", None)
@@ -304,6 +304,33 @@ class TTSCore:
             used = self._model_sampling(sampling)
             chunks = self.model.stream(input_text, str(voice), **kw, **({"sampling": used} if used is not None else {}), **sp)
         return self._stream_bytes(chunks, kw, n_seg), seed_used(used)
+
+    def stream_audio_timed(self, input_text: str, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
+                           speed: Optional[float] = None, loudness=None, info: Optional[dict] = None):
+        """``stream_audio`` of one utterance with character timestamps -> (``(bytes, align.AlignmentPart or
+        None)`` pairs, the seed the request samples with or None).  The text is spoken as one utterance whatever ``long_text``
+        says; ``ValueError``: the trim options, ``best_of``, a text the engine refuses."""
+        self._check_best_of(sampling, stream=True)
+        kw = {} if output_format == "pcm_24000" else {"output_format": output_format}
+        sp, _ = self._request_kw(input_text, speed, loudness, stream=True, voice=voice, one_utterance=True)
+        if info is not None:
+            info["watermark"] = bool(sp.get("watermark"))
+        if self.scheduler is not None:
+            req = self.scheduler.submit(input_text, str(voice), stream=True, live_timestamps=True, **kw,
+                                        **({"sampling": sampling} if sampling is not None else {}), **sp)
+            pairs, used = self.scheduler.timed_chunks(req), getattr(req, "sampling", None)
+        else:
+            used = self._model_sampling(sampling)
+            pairs = self.model.stream_with_timestamps(input_text, str(voice), **kw, **({"sampling": used} if used is not None else {}), **sp)
+        return self._timed_bytes(pairs, kw), seed_used(used)
+
+    @staticmethod
+    def _timed_bytes(pairs, kw):
+        try:
+            for chunk, part in pairs:
+                yield (np.asarray(chunk, dtype=np.float32) if not kw else np.ascontiguousarray(chunk)).tobytes(), part
+        finally:
+            pairs.close()  # a client that went away mid-stream: the scheduler takes its slot back
 
     def open_input_stream(self, voice: Union[str, int], output_format: str = "pcm_24000", sampling=None,
                           speed: Optional[float] = None, container: Optional[str] = None, loudness=None, info: Optional[dict] = None):
@@ -631,6 +658,40 @@ def stream_tts(voice_id: str, item: CreateSpeechRequest, http_request: Request,
         raise HTTPException(status_code=400, detail=str(e))
     return StreamingResponse(chunks, media_type="audio/wav", headers={
         "Content-Disposition": f'attachment; filename="speech.{kind}"', "X-Sample-Rate": rate, **_seed_headers(seed), **_mark_headers(info)})
+
+
+@eleven_router.post("/text-to-speech/{voice_id}/stream/with-timestamps")
+def stream_tts_with_timestamps(voice_id: str, item: CreateSpeechRequest, http_request: Request,
+                               output_format: StreamFormat = "pcm_24000"):
+    """ElevenLabs' streamed JSON: newline-delimited objects, one per chunk, each with ``audio_base64`` (the ``/stream`` route's
+    bytes, in its formats), ``alignment`` and ``normalized_alignment``: the characters whose times the chunk's tick committed
+    (the two are the same part), or null where the chunk carries none.  A character's time follows its audio by the server's
+    ``timestamp_lag_frames`` and is never revised (align.py).  501 unless the server has ``alignment_heads``; 400
+    with the trim options, ``best_of`` or a text the engine refuses."""
+    import base64
+    import json
+
+    core = http_request.app.state.tts_core
+    if not core.alignment_heads:
+        raise HTTPException(status_code=501, detail="this server has no alignment_heads: rank the checkpoint's heads with "
+                                                    "`python -m smoltts_amd.align rank --checkpoint DIR --texts FILE` and set them")
+    info: dict = {}
+    try:
+        pairs, seed = core.stream_audio_timed(item.text, voice=voice_id, output_format=output_format, sampling=item.request_sampling(),
+                                              speed=item.speed, loudness=item, info=info)
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+
+    def lines():
+        try:
+            for audio, part in pairs:
+                al = None if part is None else part.to_json()
+                yield (json.dumps({"audio_base64": base64.b64encode(audio).decode("ascii"), "alignment": al, "normalized_alignment": al}) + "\n").encode()
+        finally:
+            pairs.close()
+
+    return StreamingResponse(_answer_first(lines()), media_type="application/x-ndjson", headers={
+        "X-Sample-Rate": output_format.split("_")[1], **_seed_headers(seed), **_mark_headers(info)})
 
 
 class StreamInputOptions(SamplingFields, LoudnessFields):

@@ -109,8 +109,12 @@ def _worker_main(device: str, factory: Callable[[], object], req_q, res_conn) ->
 
     def pump(rid: int, req) -> None:
         try:
-            for chunk in sched.iter_chunks(req):
-                res_q.put((rid, "chunk", np.ascontiguousarray(chunk)))  # float32, or int16 / uint8 for a streamed output_format
+            if getattr(req, "live_timestamps", False):  # a stream with timestamps: each chunk travels with its part
+                for chunk, part in sched.timed_chunks(req):
+                    res_q.put((rid, "chunk", (np.ascontiguousarray(chunk), part)))
+            else:
+                for chunk in sched.iter_chunks(req):
+                    res_q.put((rid, "chunk", np.ascontiguousarray(chunk)))  # float32, or int16 / uint8 for a streamed output_format
             scores = None
             if getattr(req, "logprobs", None) is not None:
                 scores = {"logprobs": np.asarray(req.logprobs), "mean_logprob": req.mean_logprob, "takes": req.takes, "best_of": req.best_of,
@@ -263,15 +267,19 @@ class GpuPool:
 
     # ------------------------------------------------------------------ client side (the BatchScheduler interface)
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None, sampling=None, **options) -> _PoolRequest:
+               output_format: Optional[str] = None, sampling=None, live_timestamps: bool = False, **options) -> _PoolRequest:
         """As ``BatchScheduler.submit`` (the segments of one request run in one slot of one worker).  The options are parsed
         here, so that a bad request is refused before a worker sees it, and travel to the worker as the parsed value's own
-        keywords (``SpeechOptions.given``)."""
+        keywords (``SpeechOptions.given``), ``live_timestamps`` beside them; ``timed_chunks`` relays the parts with the chunks."""
         from ..request import parse_request
 
         p = parse_request(text, stream, output_format, **options)
         marked = self._marks(p.watermark)
         sampling = self._resolve_sampling(sampling)
+        if live_timestamps:
+            from ..align import check_live_timestamps
+
+            check_live_timestamps(p, stream, bool(self.alignment_heads), 1 if sampling is None else sampling.takes)
         if p.timestamps:
             if not self.alignment_heads:
                 raise ValueError("timestamps need alignment_heads: rank a checkpoint's heads with `python -m smoltts_amd.align rank`")
@@ -286,6 +294,8 @@ class GpuPool:
         w = req.worker
         msg = ("submit", req.rid, text, voice, stream, max_new_tokens)
         extra = dict(p.given(), **({} if sampling is None else {"sampling": sampling}))
+        if live_timestamps:
+            extra["live_timestamps"] = True
         self._req_qs[w].put(msg + (extra,) if extra else msg)
         return req
 
@@ -356,6 +366,16 @@ class GpuPool:
         return np.concatenate(list(self.iter_chunks(self.submit(text, voice, False, max_new_tokens))) or [np.zeros(0, np.float32)])
 
     def iter_chunks(self, req: _PoolRequest):
+        pairs = self.timed_chunks(req)
+        try:
+            for chunk, _ in pairs:
+                if len(chunk):
+                    yield chunk
+        finally:
+            pairs.close()
+
+    def timed_chunks(self, req: _PoolRequest):
+        """As ``BatchScheduler.timed_chunks``: ``(chunk, align.AlignmentPart or None)``."""
         ended = False
         try:
             while True:
@@ -365,7 +385,7 @@ class GpuPool:
                     if item is None:
                         return
                     raise item
-                yield item
+                yield item if isinstance(item, tuple) else (item, None)
         finally:
             if not ended:
                 self.cancel(req)
@@ -610,11 +630,12 @@ def scheduler_from_settings(settings):
     return BatchScheduler(model, max_batch=st.max_batch, generation_settings=st.generation.to_settings(), codec_products=st.codec_products,
                           watermark=st.watermark.to_watermark() if st.watermark is not None else None,
                           min_frames_per_byte=st.min_frames_per_byte, max_frames_per_byte=st.max_frames_per_byte,
-                          alignment_heads=st.alignment_heads)
+                          alignment_heads=st.alignment_heads, timestamp_lag_frames=st.timestamp_lag_frames)
 
 
 def synthetic_scheduler(model: str = "tiny", seed: int = 21, mimi_seed: int = 5, max_batch: int = 4, frames_per_tick: int = 2,
-                        max_new_tokens: int = 64, mimi_encoder: bool = False, watermark=None, alignment_heads=None):
+                        max_new_tokens: int = 64, mimi_encoder: bool = False, watermark=None, alignment_heads=None,
+                        timestamp_lag_frames: int = 6):
     """Seeded random weights at the named shapes (tests, rehearsals without a checkpoint); greedy.  ``mimi_encoder``: the codec
     also carries (seeded) encoder weights, so that voices can be cloned."""
     from .. import SmolTTS
@@ -630,4 +651,4 @@ def synthetic_scheduler(model: str = "tiny", seed: int = 21, mimi_seed: int = 5,
     tts = SmolTTS(state=synthetic_lm_state(cfg, seed=seed), config=cfg, mimi_state=mst)
     return BatchScheduler(tts, max_batch=max_batch, frames_per_tick=frames_per_tick,
                           generation_settings=GenerationSettings.greedy(max_new_tokens=max_new_tokens), watermark=watermark,
-                          alignment_heads=alignment_heads)
+                          alignment_heads=alignment_heads, timestamp_lag_frames=timestamp_lag_frames)

@@ -94,6 +94,10 @@ class _Request:
     alignment: object = None             # align.Alignment, set before the request's end marker
     # peak limiter: a stream is limited in its codec pass, last of the float stages; a blocking utterance whole, last
     peak_reduction_db: Optional[float] = None  # blocking: -20 log10 of the smallest gain applied (set before the audio goes out)
+    # streamed character timestamps: a stream of one utterance whose slot the device fits causally, tick by tick;
+    # ``alignment`` is then the concatenation of the parts handed out
+    live_timestamps: bool = False
+    aligner: object = None               # align.StreamAligner, made when the request takes its slot
 
 
 @dataclass
@@ -181,6 +185,7 @@ class _Snapshot:
     tick_no: int
     logprobs: object = None  # the score array, cloned only while some live slot scores
     alignment: object = None  # the alignment rows, cloned only while some live slot measures
+    fit: object = None  # (committed counts, starts) of the causal fit, cloned only while some live stream asks for timestamps
 
 
 @dataclass
@@ -192,6 +197,7 @@ class _Delivery:
     urgent: bool = False  # a stream's first chunk is in it: handed out as soon as the pass is through
     keep: object = None   # device tensors the pass reads, kept alive until it has run
     conv: object = None   # route.StreamPass: the stream conversion of the pass (None: float32 rows of ``pcm``)
+    parts: object = None  # {slot: align.AlignmentPart}: the timestamps this tick committed, handed out with its chunks
 
 
 @dataclass
@@ -218,9 +224,11 @@ class BatchScheduler:
     def __init__(self, tts, max_batch: int = 32, frames_per_tick: int = 4, generation_settings=None, max_prompt_rows: int = 4096,
                  prefill_chunk: Optional[int] = 128, side_prefill: bool = True, side_prefill_min_active: Optional[int] = None,
                  codec_products: int = 6, watermark=None, min_frames_per_byte: Optional[float] = None,
-                 max_frames_per_byte: Optional[float] = None, alignment_heads=None):
+                 max_frames_per_byte: Optional[float] = None, alignment_heads=None, timestamp_lag_frames: int = 6):
         """``alignment_heads`` (``[(layer, head), ...]``, at most 16; None: no request can ask for timestamps): the heads of the slow
         attention that ``submit(timestamps=True)`` reads character times from (align.py).
+        ``timestamp_lag_frames`` (1 .. 64): how many frames behind its audio a stream with ``live_timestamps`` commits a
+        character's time.
         ``watermark`` (a ``watermark.Watermark``; None: no request can be marked): the one key of this scheduler's marked
         requests; a request that does not say (``submit(watermark=None)``) is marked when there is one.
         ``min_frames_per_byte`` / ``max_frames_per_byte`` (None: off): bounds on every utterance's length from its text's UTF-8
@@ -237,6 +245,9 @@ class BatchScheduler:
 
         if watermark is not None and not isinstance(watermark, Watermark):
             raise ValueError("watermark must be a smoltts_amd.watermark.Watermark or None")
+        from ..align import check_lag
+
+        self.timestamp_lag_frames = check_lag(timestamp_lag_frames)
         self.watermark = watermark
         self.min_frames_per_byte, self.max_frames_per_byte = min_frames_per_byte, max_frames_per_byte
         self.tts = tts
@@ -266,8 +277,13 @@ class BatchScheduler:
 
         self.alignment_heads = check_heads(alignment_heads, tts.config)
         self._slot_align: Dict[int, tuple] = {}  # the window each slot has on the device (absent: off)
+        self._fitter = None                      # lm.AlignFitter: the streams' causal fit, one slot per LM slot
+        self._fit_on: set = set()                # the slots it is switched on in
         if self.alignment_heads:
+            from ..lm import AlignFitter
+
             self.session.set_align_heads(self.alignment_heads)
+            self._fitter = AlignFitter.for_session(self.session)  # (a slab and no launch: nothing runs until a stream asks)
         torch.cuda.current_stream().synchronize()  # (the worker's frame stream is another one)
         self.session.set_frames_per_graph(min(max(frames_per_tick, 1), 8))  # a tick is one graph launch where it fits
         self._torch = torch
@@ -315,9 +331,14 @@ class BatchScheduler:
 
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, voice: str = "heart", stream: bool = False, max_new_tokens: Optional[int] = None,
-               output_format: Optional[str] = None, sampling=None, **options) -> _Request:
+               output_format: Optional[str] = None, sampling=None, live_timestamps: bool = False, **options) -> _Request:
         """``sampling``: a ``config.RequestSampling``; missing fields take the configured settings, and a sampled request without
         a seed gets one here.  The resolved value is ``request.sampling``; its seed replays the request.
+        ``live_timestamps`` (streams of one utterance; needs the scheduler's ``alignment_heads``; ``ValueError`` without a stream,
+        with ``segment``, the trim options, ``best_of`` or ``timestamps``): ``timed_chunks(request)`` yields each chunk with the
+        ``align.AlignmentPart`` its tick committed (or None), a character's time following its audio by ``timestamp_lag_frames``
+        plus a tick at the most; ``request.alignment`` is their concatenation once the request has ended.  It is no audio option:
+        the audio is what it is without it.
         ``output_format`` and ``options``: the request's audio options, handed whole to ``request.parse_request``, which lists
         them with their ranges and refuses a bad one here, before the request is queued (``ValueError``; ``TypeError`` for a
         name it does not know).  The parsed value is ``request.opts``.  Every stage runs on the GPU: a stream's in its codec
@@ -350,6 +371,10 @@ class BatchScheduler:
         p = parse_request(text, stream, output_format, **options)
         self._check_trim(p)
         resolved = (sampling if sampling is not None else RequestSampling()).resolve(self.settings)
+        if live_timestamps:
+            from ..align import check_live_timestamps
+
+            check_live_timestamps(p, stream, bool(self.alignment_heads), resolved.takes)
         check_best_of(resolved, self.B, stream=stream, segmented=p.plan is not None)
         if p.timestamps:
             if not self.alignment_heads:
@@ -362,7 +387,8 @@ class BatchScheduler:
             raise RuntimeError("scheduler is not running: shutting down")
         req = _Request(text, voice, stream, min(max_new_tokens or self.settings.max_new_tokens, self.settings.max_new_tokens),
                        opts=p, sampling=resolved, voice_entry=self._voices.get(voice),
-                       seg=_Segmented(p.plan, resolved) if p.plan is not None else None, watermark=self._marks(p.watermark))
+                       seg=_Segmented(p.plan, resolved) if p.plan is not None else None, watermark=self._marks(p.watermark),
+                       live_timestamps=bool(live_timestamps))
         if resolved.takes > 1:
             # the parent carries the audio options and the response; its takes are plain blocking requests, admitted as slots
             # come free
@@ -471,6 +497,18 @@ class BatchScheduler:
 
     def iter_chunks(self, req: _Request):
         """Chunks of one request; abandoning the iterator (a client that went away mid-stream) cancels the request."""
+        pairs = self.timed_chunks(req)
+        try:
+            for chunk, _ in pairs:
+                if len(chunk):  # (a stream with live_timestamps may hand out a part without audio)
+                    yield chunk
+        finally:
+            pairs.close()
+
+    def timed_chunks(self, req: _Request):
+        """``(chunk, part)`` pairs of one request: ``part`` is the ``align.AlignmentPart`` of the characters whose times the
+        chunk's tick committed, None for a chunk without one and for every chunk of a request without ``live_timestamps``.
+        Abandoning the iterator cancels the request."""
         ended = False
         try:
             while True:
@@ -480,7 +518,7 @@ class BatchScheduler:
                     if item is None:
                         return
                     raise item
-                yield item
+                yield item if isinstance(item, tuple) else (item, None)
         finally:
             if not ended:
                 self.cancel(req)
@@ -575,7 +613,7 @@ class BatchScheduler:
         self._stop.set()
         self._wake.set()
         self._thread.join(timeout=30)
-        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch"):
+        for name in ("_batch_codec", "_stream_codec", "_block_ts", "_scratch", "_fitter"):
             if getattr(self, name) is not None:
                 getattr(self, name).close()
                 setattr(self, name, None)
@@ -616,6 +654,21 @@ class BatchScheduler:
             r.first_tick = self._tick_no
             r.last_tick = self._tick_no + -(-(r.max_new_tokens + 1) // self.tick) - 1  # ceil(frames / tick) ticks from first_tick on
             self._active[r.slot] = r
+        self._reset_fit(new)
+
+    def _reset_fit(self, new: List[_Request]) -> None:
+        """The causal fit of the slots that have just been armed, on the frame stream in front of their first tick (the slots'
+        frame counters stand at 0 there): a stream with ``live_timestamps`` starts its own, any other tenant switches the slot
+        off, so that nobody inherits a predecessor's state."""
+        if self._fitter is None:
+            return
+        todo = [r for r in new if r.live_timestamps or r.slot in self._fit_on]
+        if not todo:
+            return
+        for r in todo:
+            (self._fit_on.add if r.live_timestamps else self._fit_on.discard)(r.slot)
+        self._fitter.reset_slots([r.slot for r in todo], [len(r.align_ids) if r.live_timestamps else None for r in todo],
+                                 [self.timestamp_lag_frames] * len(todo), [r.max_new_tokens + 1 for r in todo])
 
     def _convert(self, pcm, n_frames_d, done_d, reqs: List[_Request], tick_no: int):
         """The stream conversion of a codec pass (``route.StreamConverter``, current stream, right behind the decode): slot b of
@@ -699,11 +752,15 @@ class BatchScheduler:
                         prompt = sg.plan.prompt(sg.k, enc, prefix, sg.prev, req.max_new_tokens, self.session.max_seq)
                     else:
                         prompt = enc.build_prompt(req.text, req.voice, v.grid) if v is not None else self.tts._get_prompt(req.text, req.voice)
-                    if req.opts.timestamps:  # the text's positions in the slot: of the whole prompt, a voice's speaker turns included
+                    if req.opts.timestamps or req.live_timestamps:  # the text's positions in the slot: of the whole prompt, a voice's speaker turns included
                         from ..align import window_of
 
                         req.align_window = window_of(prompt[0], self.tts.tokenizer)
                         req.align_ids = np.asarray(prompt[0, req.align_window[0]:req.align_window[1]]).copy()
+                        if req.live_timestamps:  # (a text its tokens do not spell is refused here, as a bad request)
+                            from ..align import StreamAligner
+
+                            req.aligner = StreamAligner(req.text, req.align_ids, self.tts.tokenizer, speed=req.opts.speed)
                     if v is not None:  # a registered voice: its speaker turns' KV rows are installed, its own turns prefilled at P
                         P = int(v.grid.shape[1])
                         req.prompt, req.pos0, req.prefix = prompt[:, P:], P, v.prefix
@@ -1010,8 +1067,15 @@ class BatchScheduler:
         s.decode(self.tick)
         scoring = any(r.slot_sampling is not None and r.slot_sampling.scored for r in list(self._active.values()) + self._retiring)
         measuring = any(r.opts.timestamps for r in list(self._active.values()) + self._retiring)
+        fit = None
+        live = [r for r in list(self._active.values()) + self._retiring if r.live_timestamps]
+        if live:
+            # the causal fit of the streams that ask for timestamps: one launch behind the frames; the host gets the committed
+            # counts and the starts (up to the longest live text), not the rows
+            self._fitter.push(s.alignment, s.n_frames, s.done)
+            fit = (self._fitter.committed.clone(), self._fitter.starts[:, :max(max(len(r.align_ids) for r in live), 1)].clone())
         snap = _Snapshot(s.codes.clone(), s.n_frames.clone(), s.done.clone(), torch.cuda.Event(), self._tick_no,
-                         s.logprobs.clone() if scoring else None, s.alignment.clone() if measuring else None)
+                         s.logprobs.clone() if scoring else None, s.alignment.clone() if measuring else None, fit)
         snap.event.record(torch.cuda.current_stream())
         self._snaps.append(snap)
         self._tick_no += 1
@@ -1032,9 +1096,10 @@ class BatchScheduler:
                 done = snap.done.to("cpu", non_blocking=True)
                 scores = snap.logprobs.to("cpu", non_blocking=True) if snap.logprobs is not None else None
                 rows = snap.alignment.to("cpu", non_blocking=True) if snap.alignment is not None else None
+                fit = [t.to("cpu", non_blocking=True) for t in snap.fit] if snap.fit is not None else None
             self._sync_copies()
             self._drain(codes.numpy(), n_frames.numpy(), done.numpy(), snap.tick_no, stream_pass, None if scores is None else scores.numpy(),
-                        None if rows is None else rows.numpy())
+                        None if rows is None else rows.numpy(), None if fit is None else [t.numpy() for t in fit])
 
     def _launch_stream_codec(self, snap: _Snapshot) -> Optional[_Delivery]:
         """The codec pass of the streaming requests for tick ``snap.tick_no``, on the codec stream, from the tick's snapshot of
@@ -1095,10 +1160,11 @@ class BatchScheduler:
         self._copy_stream.synchronize()
         self._gpu_wait_s += time.perf_counter() - t
 
-    def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery], scores=None, align_rows=None) -> None:
+    def _drain(self, codes, n_frames, done, tick_no: int, stream_pass: Optional[_Delivery], scores=None, align_rows=None, fit=None) -> None:
         from ..config import finish_reason, merge_finish_reasons
         from ..generate import semantic_columns
 
+        parts = {}         # {slot: align.AlignmentPart}: the timestamps this tick committed
         stream_items = []  # the streams' share of this tick's codec pass: (request, pcm row, samples, last?) handed out by _deliver
         urgent = False     # a stream's first chunk is among them
         nq = self.tts.config.num_codebooks
@@ -1137,6 +1203,10 @@ class BatchScheduler:
                 k = n - r.emitted
                 if r.seg is not None and k > 0:  # the next segment's context: this one's semantic frames
                     r.seg.cols.append(semantic_columns(codes[slot, r.emitted:n], tc, nq))
+                if r.live_timestamps and (k > 0 or finished):
+                    part = self._timed_part(r, fit, n, finished)
+                    if part is not None:
+                        parts[slot] = part
                 if k > 0 or finished:
                     assert k == 0 or (stream_pass is not None and r.emitted == (tick_no - r.first_tick) * self.tick), "stream bookkeeping out of step"
                     stream_items.append((r, slot, max(k, 0) * 1920, finished and not seg_more))
@@ -1191,8 +1261,24 @@ class BatchScheduler:
                     self._finished.append(r)
         if stream_items:
             d = stream_pass or _Delivery(None, None, [])
-            d.items, d.urgent = stream_items, urgent
+            d.items, d.urgent, d.parts = stream_items, urgent, parts
             self._deliveries.append(d)
+
+    def _timed_part(self, r: _Request, fit, n: int, finished: bool):
+        """The characters of a stream with ``live_timestamps`` whose times its slot's fit has committed since the part before
+        (None: none), from the snapshot's copy ``fit`` = (committed counts, starts); at the stream's end the rest, cut at the
+        frames it delivers (nominal at a speed other than 1), and ``r.alignment``."""
+        if fit is None:
+            raise RuntimeError("scheduler lost the fitted starts of a request")
+        counts, starts = fit
+        c = int(counts[r.slot])
+        if not finished:
+            return r.aligner.update(starts[r.slot, :c])
+        if c != r.aligner.n:
+            raise RuntimeError(f"the fit of a finished stream holds {c} of {r.aligner.n} starts")
+        part = r.aligner.finish(starts[r.slot, :c], r.aligner.duration(n))
+        r.alignment = r.aligner.alignment()
+        return part
 
     # ------------------------------------------------------------------ worker: codec passes and delivery
     def _codec_backlog(self) -> bool:
@@ -1313,7 +1399,18 @@ class BatchScheduler:
                     if fin:
                         self._part_done(r)
                     continue
-                if r.stream and d.conv is not None and d.conv.converts(b):
+                if r.live_timestamps:
+                    # a stream with timestamps: each chunk goes out with the part its tick committed (a part alone where the
+                    # stages hold the tick's samples back)
+                    part = d.parts.get(b) if d.parts else None
+                    if d.conv is not None and d.conv.converts(b):
+                        chunk = d.conv.chunk(b, fin)
+                    else:
+                        chunk = host[b, :n].copy() if n else np.zeros(0, np.float32)
+                    if (len(chunk) or part is not None) and not r.cancelled:
+                        r.out.put((chunk, part))
+                        self._counts["frames_delivered"] += n // 1920
+                elif r.stream and d.conv is not None and d.conv.converts(b):
                     chunk = d.conv.chunk(b, fin)  # (the tail goes out with the last chunk)
                     if chunk.size and not r.cancelled:
                         r.out.put(chunk)

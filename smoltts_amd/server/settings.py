@@ -125,6 +125,10 @@ class ServerSettings(BaseModel):
     # checkpoint track the text is the operator's to find: python -m smoltts_amd.align rank --checkpoint DIR --texts FILE
     alignment_heads: Optional[List[Tuple[int, int]]] = Field(default=None, max_length=16)
 
+    # (extension) how many frames (80 ms each) behind its audio a streamed character timestamp is committed:
+    # POST /v1/text-to-speech/{voice_id}/stream/with-timestamps.  A committed time is never revised; a longer lag sees more
+    timestamp_lag_frames: int = Field(default=6, ge=1, le=64)
+
     model_config = {"protected_namespaces": ()}
 
     @model_validator(mode="after")
